@@ -1,8 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- solid Mvoxels/s of the voxelize hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--grid 512] [--mesh torus1m]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--grid 512] [--mesh torus1m] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline needs and no more: set-up (mesh, Init, the grid's work queue), warm-up, the K timed steps, the
+outputs if --dump-outputs is given, the line.  --full adds everything else the line has reported: the same steps once more with an
+event behind each, the launch disciplines beside the headline (unprepared, kept), the secondary figures (frames in flight, texel image,
+other rule, tree walk, 256^3, bunny x16, config 4, the first call after Init), the warm LBVH build, the solid count and the CPU baseline
+(--no-extras / --no-cpu-baseline leave parts of it out).
+--dump-outputs DIR: after the timed steps, what the last step computed -- the occupancy grid a caller of Voxelize receives -- as
+float32 .npy files in DIR (grid_sample: the values of a fixed, seeded sample of 4 Mi voxels; grid_row_sums [nz, N]: the sum of every
+x row; grid_column_sums [N, N]: the sum along z of every (y, x)); with N > 1 every rank writes its share's files, suffixed _rank<r>.
 
 Called as `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment, this process touches no GPU: it
 starts the N ranks as a child `python -m torch.distributed.run` (127.0.0.1 rendezvous), waits and relays rank 0's line.
@@ -96,6 +105,26 @@ def source_hash():
     return h.hexdigest()[:16]
 
 
+DUMP_SAMPLE = 1 << 22         # voxels in --dump-outputs' seeded sample of the grid (16 MB as float32)
+
+
+def dump_outputs(grid, outdir, suffix="", samples=DUMP_SAMPLE):
+    """--dump-outputs: the occupancy grid (uint8 [nz, N, N], what Grid() hands a caller) as float32 .npy files: the values of a fixed,
+    seeded sample of `samples` voxels (every voxel when the grid is smaller), and the sums of every x row and every z column, so that a
+    voxel that differs anywhere shows in two of the three.  About 18 MB at 512^3 (ranks share the sample), well under 64 MB."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    flat = grid.reshape(-1)
+    if flat.size <= samples:
+        sample = flat
+    else:
+        sample = flat[np.random.default_rng(0x5EED).integers(0, flat.size, size=samples)]
+    arrays = {"grid_sample": sample, "grid_row_sums": grid.sum(axis=2, dtype=np.uint64),
+              "grid_column_sums": grid.sum(axis=0, dtype=np.uint64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), a.astype(np.float32))
+
+
 def cpu_baseline(vb, ib, N, mode, budget_s=15.0):  # (N > 1: a shorter sample, the other ranks wait for rank 0)
     """The oracle's scalar BVH voxelizer ('port': the reference has no CPU path) on a bounded
     sample of the same workload: evenly spaced Z slices, all host cores (OpenMP over rows)."""
@@ -172,6 +201,10 @@ def main():
                     help="plumbing test on a 1-GPU box: every rank uses cuda:0 (needs --backend gloo)")
     ap.add_argument("--dry-run", action="store_true",
                     help="plumbing test without a GPU: ranks rendezvous, reduce and print the line, no voxelizer (needs --backend gloo)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: per-step spread, unprepared / kept steps, secondary figures, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the occupancy grid: seeded sample and row / column counts) as .npy files in DIR")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -236,15 +269,16 @@ def main():
     vb = ib = None
     label = args.mesh
     bcast_ms, bcast = 0.0, {}
-    warmup_ms = None
+    warmup_ms = warm_list_ms = None
     if rank == 0:
         vb, ib, label = make_mesh(args.mesh)
         warmup_ms = vox.stats()["warmup_ms"]     # (dxv_create's one pass through every step on a four-triangle scene: the runtime's lazy parts)
         vox.InitFromArrays(vb, ib)               # upload + LBVH + candidate lists (Init work, not part of a step)
         cold_build_ms = vox.stats()["build_ms"]  # (the first build of a process behind that pass)
         cold_list_ms = vox.stats()["list_ms"]
-        vox.InitFromArrays(vb, ib)               # ... the same again: the figure config.build_roofline is made from
-        warm_list_ms = vox.stats()["list_ms"]
+        if args.full:
+            vox.InitFromArrays(vb, ib)           # ... the same again: the figure config.build_roofline is made from
+            warm_list_ms = vox.stats()["list_ms"]
     if use_dist:
         torch.cuda.synchronize()
         dist.barrier()
@@ -268,6 +302,7 @@ def main():
 
     launched = set()                             # grid sizes launched once before any warm-up (that launch allocates the frame's grid)
     untimed = [0]                                # launches made before the first warm-up step (allocations + clock spin-up)
+    last_frame = [0]                             # the frame the latest step wrote (--dump-outputs reads the last timed step's grid from it)
     prepare_ms = {}
 
     def prepare_share(n):
@@ -298,6 +333,7 @@ def main():
         def step():
             f = turn[0] % frames
             turn[0] += 1
+            last_frame[0] = f
             if inter:
                 vox.VoxelizeInterleaved(n, rank, world, zblock, mode, sync=False, frameIndex=f)
             elif nzn:
@@ -389,30 +425,37 @@ def main():
     vox.set_option("plan", 2)
     dt, step_ms_events, _ = timed_region(frames, args.steps, args.warmup, lib_events=False)
     dt_max = reduce_max(dt)
-    _, k_one, per_step = timed_region(1, args.steps, 1, per_step=True)  # the same steps once more, one in flight, with an event behind every one: their spread
-    if frames != 1:
-        step_ms_events = k_one                   # (the dominant kernel's launch duration is a one-in-flight figure: overlapping launches share the GPU)
+    if args.dump_outputs and (interleave or nz):         # (a rank whose slab is empty launched nothing: no grid)
+        vox.SetFrame(last_frame[0])
+        dump_outputs(vox.Grid(), args.dump_outputs, f"_rank{rank}" if world > 1 else "", DUMP_SAMPLE // world)
+        vox.SetFrame(0)
+    per_step = []
+    if args.full:
+        _, k_one, per_step = timed_region(1, args.steps, 1, per_step=True)  # the same steps once more, one in flight, with an event behind every one: their spread
+        if frames != 1:
+            step_ms_events = k_one               # (the dominant kernel's launch duration is a one-in-flight figure: overlapping launches share the GPU)
     st_run = st_probe()                          # of the timed rule (the extras below overwrite the launch fields)
     queued = bool(st_run["plan_bricks"]) and mode == dxv.MODE_REFERENCE
     prepared_run = queued and bool(st_run["plan_prepared"])
     # a launch that builds its queue: the queue build (the kernel in front of the brick kernel: queue + clear) on its own, a few launches with
     # the library's events
     pm = []
-    if queued and not prepared_run:
+    if args.full and queued and not prepared_run:
         for _ in range(7):
             if interleave:
                 vox.VoxelizeInterleaved(N, rank, world, zblock, mode)
             elif nz:
                 vox.Voxelize(N, mode, z0, nz)
             pm.append(vox.stats()["plan_ms"])
-    plan_ms = float(np.median(pm)) if pm else 0.0
-    kernel_ms = step_ms_events - plan_ms         # the dominant kernel's average launch duration: the step between two events minus the kernel in front of it (none when prepared)
+    # (a plain run of a queue-building step does not measure the queue build: queue_build_ms None, kernel_ms the whole step)
+    plan_ms = float(np.median(pm)) if pm else (None if queued and not prepared_run else 0.0)
+    kernel_ms = step_ms_events - (plan_ms or 0.0)  # the dominant kernel's average launch duration: the step between two events minus the kernel in front of it (none when prepared)
     # The same steps (i) with the queue built INSIDE every launch -- what a launch of a grid Init was not told does (option prepared = 0;
     # persistent waves: the launch does not know its size) -- and (ii) with the queue and the zeros of the bricks it does not run KEPT
     # from step to step (plan = 1: a static scene voxelized into the same frame again, the reference's own loop,
     # Content/Voxelizer.cpp:108-113; launched through the hardware's dispatcher once a sync has read the queue's lengths)
     kept = unprepared = None
-    if queued:
+    if args.full and queued:
         vox.set_option("prepared", 0)
         if prepared_run:
             dtu, ku, _ = timed_region(frames, args.steps, args.warmup, lib_events=False)
@@ -436,13 +479,16 @@ def main():
     rank_kernel_ms = gather(step_ms_events)      # every rank's mean step between two events: an imbalance of the partition shows here
     rank_wall_ms = gather(dt / max(args.steps, 1) * 1e3)
     kmax = max(rank_kernel_ms)
-    solid = vox.CountSolid() if nz else 0
-    tot = torch.tensor([float(solid)], dtype=torch.float64, device="cuda")
-    if use_dist:
-        dist.all_reduce(tot, op=dist.ReduceOp.SUM)
+    tot = None
+    if args.full:
+        solid = vox.CountSolid() if nz else 0
+        tot = torch.tensor([float(solid)], dtype=torch.float64, device="cuda")
+        if use_dist:
+            dist.all_reduce(tot, op=dist.ReduceOp.SUM)
 
     extras = {}
-    if not args.no_extras:
+    with_extras = args.full and not args.no_extras
+    if with_extras:
         # the same steps with two and three voxelizations in flight per GPU (the reference keeps FrameCount = 3 grids in flight,
         # Content/Voxelizer.h:24: consecutive frames write different grids and overlap on the GPU); the headline keeps ONE in flight
         # at every N so that values at different N compare like for like
@@ -451,7 +497,7 @@ def main():
             dt2 = reduce_max(dt2)
             extras[f"frames_in_flight_{other}"] = {"value": (N ** 3) * args.steps / dt2 / 1e6, "unit": "Mvoxels/s",
                                                    "ms_per_step": dt2 / args.steps * 1e3, "kernel_ms": reduce_max(k2)}
-    if world == 1 and not args.no_extras:
+    if world == 1 and with_extras:
 
         def median_ms(m, reps=5):
             vox.Voxelize(N, m)
@@ -530,7 +576,7 @@ def main():
                 extras["bunny16"] = {"workload": f"{blabel}, {N}^3, reference predicate", "ms": lm, "mvoxels_s": N ** 3 / lm / 1e3,
                                      "tree_walk_ms": tm, "tree_walk_mvoxels_s": N ** 3 / tm / 1e3}
 
-    if not args.no_extras and mode == dxv.MODE_REFERENCE and args.mesh == "torus1m":
+    if with_extras and mode == dxv.MODE_REFERENCE and args.mesh == "torus1m":
         # BASELINE config 4 beside the headline at every N: dragon x9 at 1024^3, the same partition -- a rank's share is
         # eight times the headline's, so the launch tail weighs an eighth as much in the scaling it shows
         n4, k4 = 1024, max(5, min(args.steps, 10))
@@ -548,7 +594,7 @@ def main():
                                           "ms_per_step": dt4 / k4 * 1e3, "rank_kernel_ms": rk4, "step_ms": stats_ms(step4)}
 
     cold = None
-    if rank == 0 and world == 1 and not args.no_extras and mode == dxv.MODE_REFERENCE:
+    if rank == 0 and world == 1 and with_extras and mode == dxv.MODE_REFERENCE:
         # The first call: one Init (upload, LBVH, candidate lists, the grid's work queue) and the scene's first three Voxelize calls, on a
         # context that has launched other things before (allocations of this size exist; the code is loaded)
         torch.cuda.synchronize()
@@ -630,7 +676,7 @@ def main():
                        "frames_in_flight_note": ("one voxelization in flight per GPU, at every N" if frames == 1 else
                                                  f"{frames} voxelizations in flight per GPU by --frames (frames of the one context: consecutive steps write different grids, "
                                                  "like the reference's FrameCount = 3); the default is one at every N"),
-                       "solid_voxels": int(tot.item()),
+                       "solid_voxels": int(tot.item()) if tot is not None else None,
                        "steps": args.steps, "warmup": args.warmup, "spin_ms": args.spin_ms,
                        "untimed_launches_before_warmup": untimed[0],     # one allocates the frame's grid and queue, the others spin the clocks up (--spin-ms)
                        "queue_build_ms": plan_ms, "queued_bricks": bricks,
@@ -645,14 +691,15 @@ def main():
                                        "entries": st_run["list_entries"], "build_ms": warm_list_ms if rank == 0 else None,
                                        "build_ms_first_in_process": cold_list_ms if rank == 0 else None, "built": "in Init"}
                                       if st_run.get("list_entries") else {"structure": "LBVH walk"}),
-                       "build_ms": st0["build_ms"], "build_ms_first_in_process": cold_build_ms,
-                       "build_stages_ms": {k: st0[k] for k in ("prep_ms", "sort_ms", "hierarchy_ms", "refit_ms")},
+                       # (the figures of the second, warm Init: --full only; a plain run has made one Init, the first of the process)
+                       "build_ms": st0["build_ms"] if args.full else None, "build_ms_first_in_process": cold_build_ms,
+                       "build_stages_ms": {k: st0[k] for k in ("prep_ms", "sort_ms", "hierarchy_ms", "refit_ms")} if args.full else None,
                        "build_roofline": {"bound": "hbm", "bytes": build_bytes(T), "ms": st0["build_ms"],
                                           "achieved": build_bytes(T) / (st0["build_ms"] * 1e-3) / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                                           "frac": build_bytes(T) / (st0["build_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS,
                                           "note": "LBVH build of this mesh (keys, radix sort in three passes of 10-bit digits, hierarchy, boxes, half-float node copy), "
-                                                  "B_build of SURVEY.md 8(d)"},
-                       "upload_ms": st0["upload_ms"], "scene_broadcast_ms": bcast_ms,
+                                                  "B_build of SURVEY.md 8(d)"} if args.full else None,
+                       "upload_ms": st0["upload_ms"] if args.full else None, "scene_broadcast_ms": bcast_ms,
                        "scene_broadcast": ({"bytes": bcast.get("bytes"), "collective_ms": bcast.get("broadcast_ms"),
                                             "checksum": f"{bcast.get('checksum', 0):#018x}", "ranks_equal": len(set(bcast.get("checksums", [0]))) == 1}
                                            if bcast else None),
@@ -685,7 +732,7 @@ def main():
         dist.destroy_process_group()
     vox.close()
     if rank == 0:
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(vb, ib, N, mode, budget_s=15.0 if world == 1 else 6.0)
         print(json.dumps(out), flush=True)
 

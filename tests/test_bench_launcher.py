@@ -7,6 +7,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 from conftest import ROOT
 
 
@@ -66,7 +68,7 @@ def test_two_real_ranks_on_one_gpu_through_the_launcher(grids_json):
     """The whole multi-rank path with real engines: `python bench.py --gpus 2` starts two ranks (both on cuda:0, gloo:
     RCCL refuses two ranks per GPU), rank 0 builds the LBVH and the lists, the blob is broadcast, rank 1 imports it, each
     rank voxelizes its share of the block-cyclic Z partition; the summed solid count must be the oracle's."""
-    r = run_bench("--gpus", "2", "--backend", "gloo", "--same-device", "--no-cpu-baseline", "--no-extras", "--mesh", "bunny",
+    r = run_bench("--gpus", "2", "--backend", "gloo", "--same-device", "--full", "--no-cpu-baseline", "--no-extras", "--mesh", "bunny",
                   "--grid", "128", "--steps", "3", "--warmup", "1")
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -86,3 +88,37 @@ def test_two_real_ranks_on_one_gpu_through_the_launcher(grids_json):
     assert u["ms_per_step"] > 0 and u["queue_build_ms"] > 0 and u["persistent_waves"] % 8 == 0
     k = c["kept_step"]
     assert k["ms_per_step"] > 0 and k["stored_bytes_per_launch"] == 64 * c["queued_bricks"]
+
+
+def test_help_names_full_and_dump_outputs():
+    # (argparse answers before torch is imported: no GPU, no launcher)
+    r = run_bench("--help")
+    assert r.returncode == 0, r.stderr
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_steps_grid(grids_json, tmp_path):
+    """A plain run times its steps and prints the headline, nothing else; --dump-outputs writes the last step's grid (at 128^3 the
+    sample is every voxel), the same files from run to run, and its sums are the oracle's solid count."""
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = run_bench("--mesh", "bunny", "--grid", "128", "--steps", "7", "--warmup", "2", "--dump-outputs", str(d))
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert out["steps"] == 7 and out["ms_per_step"] > 0 and out["value"] > 0 and out["higher_is_better"] is True
+        assert "cpu_baseline" not in out
+        c = out["config"]
+        assert c["unprepared_step"] is None and c["kept_step"] is None and c["first_voxelize_after_init"] is None
+        assert "frames_in_flight_2" not in c and "grid_256" not in c and c["step_ms_rank0"] is None
+        files = {f.name: np.load(f) for f in d.iterdir()}
+        assert sorted(files) == ["grid_column_sums.npy", "grid_row_sums.npy", "grid_sample.npy"]
+        assert all(a.dtype == np.float32 for a in files.values())
+        dumps.append(files)
+    a, b = dumps
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    solid = grids_json["bunny/128/reference"]["solid"]
+    assert a["grid_sample.npy"].shape == (128 ** 3,) and a["grid_sample.npy"].sum() == solid
+    assert a["grid_row_sums.npy"].shape == (128, 128) and a["grid_row_sums.npy"].sum() == solid
+    assert a["grid_column_sums.npy"].shape == (128, 128) and a["grid_column_sums.npy"].sum() == solid

@@ -1,11 +1,13 @@
 """A1 mesh ingest: the oracle's restatement and the PRODUCT's loader (csrc/obj_ingest.cpp) against
-the reference's own ObjLoader (oracle/_ref build, outputs committed under tests/golden)."""
+the reference's own ObjLoader (oracle/_ref build, outputs committed under tests/golden).  The reference's three
+asset files (Bin/Assets) are stored byte for byte, xz-compressed, under tests/golden/obj."""
+import lzma
 import os
 
 import numpy as np
 import pytest
 
-from conftest import GOLD, REF_ASSETS, load_mesh
+from conftest import GOLD, load_mesh
 
 HAND = ["quad_poly_neg", "split_vn"]
 
@@ -52,13 +54,13 @@ def test_polygon_fan_and_reversal():
 @pytest.mark.parametrize("name,file,V,nidx", [("bunny", "bunny.obj", 34835, 208998),
                                               ("dragon", "dragon.obj", 50000, 300000),
                                               ("turingbowl", "TuringBowl.obj", 23188, 68232)])
-def test_asset_fixtures_and_loaders(orc, dxvlib, name, file, V, nidx):
+def test_asset_fixtures_and_loaders(orc, dxvlib, tmp_path, name, file, V, nidx):
     vb, ib, aabb = load_mesh(name)           # produced by the reference's loader (gen_fixtures.py)
     assert vb.shape == (V, 6) and ib.shape == (nidx,)
     assert not np.isnan(vb).any()
-    path = os.path.join(REF_ASSETS, file)
-    if not os.path.exists(path):
-        pytest.skip("reference assets not present on this machine")
+    path = str(tmp_path / file)              # the loaders take a path: the asset file as the reference ships it
+    with lzma.open(os.path.join(GOLD, "obj", file + ".xz")) as src, open(path, "wb") as dst:
+        dst.write(src.read())
     import dxrvoxelizer_amd as dxv
     for loader in (orc.obj_load, dxv.obj_load):
         v2, i2, a2 = loader(path)

@@ -7,15 +7,16 @@
 # PMC passes (each in its own run, --kernel-trace only beside --pmc).  Everything lands in gpurun_out/final/.
 # usage (on the GPU box): bash tools/gpu_final.sh [quick]      quick: no soak, no soup-10M PMC, fewer repetitions
 cd "$GRAFT_REPO_ROOT" || exit 1
+REPO=$(pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/final
 QUICK=${1:-}
 rm -rf $OUT; mkdir -p $OUT
 (time python -m pytest tests -m gpu -q --maxfail=10 -p no:cacheprovider) > $OUT/pytest_gpu.log 2>&1
 python __graft_entry__.py smoke > $OUT/smoke.log 2>&1
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_flags.json 2> $OUT/bench_driver_flags.err
-python bench.py --gpus 2 --backend gloo --same-device --steps 100 > $OUT/bench_2rank_same_gpu_gloo.json 2> $OUT/bench_2rank_same_gpu_gloo.err
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 1 --steps 50 --warmup 3 --interleave --no-cpu-baseline --no-extras > $OUT/bench_torchrun_world1.log 2>&1
+python bench.py --gpus 2 --backend gloo --same-device --steps 100 --full > $OUT/bench_2rank_same_gpu_gloo.json 2> $OUT/bench_2rank_same_gpu_gloo.err
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 1 --steps 50 --warmup 3 --interleave --full --no-cpu-baseline --no-extras > $OUT/bench_torchrun_world1.log 2>&1
 for m in torus1m bunny16 dragon9; do python tools/prepared_ab.py $m 512 8 4 1,2,3 >> $OUT/launch_disciplines.jsonl 2>> $OUT/launch_disciplines.err; done
 python tools/prepared_ab.py torus1m 256 8 4 1,2 >> $OUT/launch_disciplines.jsonl 2>> $OUT/launch_disciplines.err
 python tools/prepared_ab.py dragon9 1024 8 4 1,2 >> $OUT/launch_disciplines.jsonl 2>> $OUT/launch_disciplines.err
@@ -50,7 +51,7 @@ tools/micro/l1_roof > $OUT/l1_roof.jsonl 2>&1
 cd /tmp && export TMPDIR=/tmp
 export DXV_WARMUP=0      # (profiles: dxv_create's warm-up launches are not the kernels these averages are about)
 # the timed regions alone, so that the kernel's average over this command is the average bench.py itself reports
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-extras > $OUT/prof_bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -- python3 $REPO/bench.py --full --no-cpu-baseline --no-extras > $OUT/prof_bench.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_build -- python3 $GRAFT_REPO_ROOT/tools/build_once.py soup10m 3 > $OUT/prof_build.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_build_torus1m -- python3 $GRAFT_REPO_ROOT/tools/build_once.py torus1m 6 > $OUT/prof_build_torus1m.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_refit_loop -- python3 $GRAFT_REPO_ROOT/tools/refit_loop.py torus1m 512 20 > $OUT/prof_refit_loop.log 2>&1

@@ -7,7 +7,7 @@ timeout 1200 python -m pytest ${TRY_TESTS:-tests/test_gpu_prepared.py} -m gpu -q
 tail -25 $OUT/pytest.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
 tail -3 $OUT/smoke.log
-timeout 600 python bench.py ${TRY_BENCH:---no-cpu-baseline} > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 python bench.py ${TRY_BENCH:---full --no-cpu-baseline} > $OUT/bench.json 2> $OUT/bench.err
 tail -5 $OUT/bench.err
 python - <<'PY'
 import json,os
