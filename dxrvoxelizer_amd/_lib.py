@@ -6,7 +6,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
-API_VERSION = 6          # DXV_API_VERSION of include/dxv.h (tests/test_cabi.py compares the two)
+API_VERSION = 7          # DXV_API_VERSION of include/dxv.h (tests/test_cabi.py compares the two)
 
 
 class DxvError(RuntimeError):
@@ -71,6 +71,9 @@ SYMBOLS = {
     "dxv_enable_texels": (C.c_int, [C.c_void_p, C.c_int]),
     "dxv_texels_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "dxv_render": (C.c_int, [C.c_void_p, _F32P, _F32P, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "dxv_update_frame": (C.c_int, [C.c_void_p, _F32P, _F32P, C.c_void_p, C.c_uint32, C.c_uint32]),
+    "dxv_render_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_stream_wait_frame": (C.c_int, [C.c_void_p, C.c_void_p]),
     "dxv_build_lists": (C.c_int, [C.c_void_p]),
     "dxv_build_lists_for_grid": (C.c_int, [C.c_void_p, C.c_uint32]),
     "dxv_build_parity_lists": (C.c_int, [C.c_void_p]),

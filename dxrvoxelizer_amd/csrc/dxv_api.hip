@@ -236,6 +236,9 @@ void dxv_destroy(dxv_ctx* c)
         if (f.evP0) (void)hipEventDestroy(f.evP0);
         if (f.evP1) (void)hipEventDestroy(f.evP1);
         if (f.evEnd) (void)hipEventDestroy(f.evEnd);
+        if (f.evR0) (void)hipEventDestroy(f.evR0);
+        if (f.evR1) (void)hipEventDestroy(f.evR1);
+        (void)hipFree(f.dEmpty);
         if (f.ownStream) (void)hipStreamDestroy(f.ownStream);
     }
     free_scratch(c);
@@ -243,7 +246,7 @@ void dxv_destroy(dxv_ctx* c)
     (void)hipFree(c->dFar32); (void)hipFree(c->dFarCells); (void)hipFree(c->dFarMip);
     (void)hipFree(c->dMip);
     (void)hipFree(c->dVb); (void)hipFree(c->dIb); (void)hipFree(c->dScene);
-    (void)hipFree(c->dImage); (void)hipFree(c->dEmpty); (void)hipFree(c->dListCells); (void)hipFree(c->dListEntries); (void)hipFree(c->dPlCells); (void)hipFree(c->dPlEntries); (void)hipFree(c->dPlScratch); (void)hipFree(c->dListScratchA); (void)hipFree(c->dListScratchB);
+    (void)hipFree(c->dImage); (void)hipFree(c->dListCells); (void)hipFree(c->dListEntries); (void)hipFree(c->dPlCells); (void)hipFree(c->dPlEntries); (void)hipFree(c->dPlScratch); (void)hipFree(c->dListScratchA); (void)hipFree(c->dListScratchB);
     (void)hipFree(c->dCount); (void)hipFree(c->dPacked); (void)hipFree(c->dRootInfo);
     for (auto& ev : c->ev) if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : c->evList) if (ev) (void)hipEventDestroy(ev);
@@ -549,11 +552,9 @@ int dxv_render(dxv_ctx* c, const float eye[3], const float viewProj[16], const f
     if (!c) return 1;
     Frame& f = cur_frame(c);
     const hipStream_t fs = cur_stream(c);
-    (void)fs;
     if (!eye || !viewProj || !rgbaHost || !width || !height || width > 16384 || height > 16384)
         return fail(c, "dxv_render: bad arguments");
-    const uint32_t N = f.grid_dim;
-    if (!f.dGrid || !N || f.z0 != 0 || f.nz != N || f.lastZBlock != N)
+    if (!frame_renderable(f))
         return fail(c, "dxv_render: needs the whole grid of the last dxv_voxelize (z0 = 0, nz = grid_dim) on this context");
     const float unit[4] = {0.0f, 0.0f, 0.0f, 1.0f};                 // DXRVoxelizer.cpp:37
     RayCastCB cb;
@@ -567,20 +568,13 @@ int dxv_render(dxv_ctx* c, const float eye[3], const float viewProj[16], const f
         DXV_HIP(c, hipMalloc(&c->dImage, pixels * 4));
         c->imageCap = pixels;
     }
-    if (c->optSkipEmpty && empty_brick_bytes(N) > c->emptyCap) {
-        DXV_HIP(c, hipStreamSynchronize(fs));
-        (void)hipFree(c->dEmpty); c->dEmpty = nullptr; c->emptyCap = 0;
-        DXV_HIP(c, hipMalloc(&c->dEmpty, align256(empty_brick_bytes(N))));
-        c->emptyCap = empty_brick_bytes(N);
-    }
     if (dxv_sync(c)) return 1;                                       // the grid must be complete and valid
-    DXV_HIP(c, hipEventRecord(c->ev[8], fs));
-    DXV_HIP(c, launch_raycast(cb, f.dGrid, N, width, height, c->dImage, c->optSkipEmpty ? c->dEmpty : nullptr, fs));
-    DXV_HIP(c, hipEventRecord(c->ev[9], fs));
+    // (the staging image is the context's: every frame's dxv_render ends in this host wait before another one can start)
+    if (render_frame(c, cb, width, height, reinterpret_cast<uint8_t*>(c->dImage), (size_t)width * 4, true)) return 1;
     DXV_HIP(c, hipMemcpyAsync(rgbaHost, c->dImage, pixels * 4, hipMemcpyDeviceToHost, fs));
     DXV_HIP(c, hipStreamSynchronize(fs));
-    c->renderMs = elapsed(c->ev[8], c->ev[9]);
-    c->stats.render_ms = c->renderMs;
+    f.render_ms = elapsed(f.evR0, f.evR1);
+    f.renderTimed = false;
     return 0;
 }
 
@@ -683,6 +677,7 @@ int dxv_get_stats(const dxv_ctx* c, dxv_stats* out)
     out->list_entries = f.list_entries; out->list_res = f.list_res; out->list_ms = f.lastMode == DXV_MODE_PARITY ? c->plMs : c->listMs;
     out->plan_bricks = f.plan_bricks; out->plan_waves = f.plan_waves; out->plan_ms = f.plan_ms;
     out->plan_prepared = f.lastPrepared >= 0 ? 1u : 0u;
+    out->render_ms = f.render_ms;
     return 0;
 }
 

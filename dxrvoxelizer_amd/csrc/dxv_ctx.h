@@ -110,6 +110,14 @@ struct dxv_ctx {
         hipEvent_t evEnd = nullptr;      // behind the frame's last launch, always recorded: what a refit on another stream waits for on the device
         bool usedLists = false;          // the frame's last launch went through the direction-space lists ...
         uint64_t listEpochUsed = 0;      // ... of this build (a build whose deferred check fails is withdrawn: settle_lists, sync_frame)
+        // display pass (dxv_update_frame, dxv_render_async, dxv_render): what the frame renders with, its own so that frames render side by side
+        RayCastCB cb{};                  // the ray-cast constants of the frame's last dxv_update_frame ...
+        uint32_t cbWidth = 0, cbHeight = 0;   // ... and the viewport they were made for (0: none yet)
+        uint8_t* dEmpty = nullptr;       // empty-brick flags of the frame's grid (empty_brick_bytes)
+        size_t emptyCap = 0;
+        hipEvent_t evR0 = nullptr, evR1 = nullptr;   // around the frame's last render
+        bool renderTimed = false;        // ... which was bracketed by them and not read yet (the frame's next dxv_sync reads it)
+        float render_ms = 0.0f;
     };
     Frame frames[DXV_FRAME_COUNT];
     uint32_t cur = 0;                    // dxv_set_frame
@@ -228,10 +236,7 @@ struct dxv_ctx {
     int nodesStale = 0;              // what a build / refit left behind (ensure_nodes brings it up to date before anything reads it):
                                      // 1 = the four-box copy (nodes64); 2 = every node box (dxv_refit stopped at the pyramid: deferBoxes)
     int listOpt = 0;                 // the listres option the current lists (or the decision against them) were made with
-    uint8_t* dEmpty = nullptr;       // display pass: empty-brick flags of the grid
-    size_t emptyCap = 0;
     int optSkipEmpty = 1;    // display pass: skip the samples of empty 8^3 bricks (same image)
-    float renderMs = 0.0f;
 
     hipEvent_t ev[10] = {};
     dxv_stats stats{};
@@ -296,6 +301,8 @@ int sync_frames(dxv_ctx* c);
 bool use_wide(const dxv_ctx* c, int mode);
 int safe_stack(const dxv_ctx* c, int mode);
 int launch_now(dxv_ctx* c, uint32_t frame, bool relaunch = false);
+int render_frame(dxv_ctx* c, const RayCastCB& cb, uint32_t width, uint32_t height, uint8_t* dst, size_t pitch, bool timed);
+bool frame_renderable(const Frame& f);
 // dxv_lists.hip
 struct ListScratchA { DirRecord* rec; uint32_t *counts, *offsets, *pairs, *sums; unsigned long long* total; size_t bytes; };
 ListScratchA list_scratch_a(uint8_t* base, uint32_t T);

@@ -19,6 +19,8 @@ int frame_prepare(dxv_ctx* c, uint32_t i)
     if (!f.evP0) DXV_HIP(c, hipEventCreate(&f.evP0));
     if (!f.evP1) DXV_HIP(c, hipEventCreate(&f.evP1));
     if (!f.evEnd) DXV_HIP(c, hipEventCreateWithFlags(&f.evEnd, hipEventDisableTiming));
+    if (!f.evR0) DXV_HIP(c, hipEventCreate(&f.evR0));
+    if (!f.evR1) DXV_HIP(c, hipEventCreate(&f.evR1));
     if (!f.dStatus) DXV_HIP(c, hipMalloc(&f.dStatus, 256));
     if (!f.dRedo) DXV_HIP(c, hipMalloc(&f.dRedo, sizeof(uint64_t) * kRedoCap));
     // on the frame's own stream, and finished before anything reads the words: the streams are non-blocking, a memset on the
@@ -454,6 +456,7 @@ int sync_frame(dxv_ctx* c, uint32_t i)
         DXV_HIP(c, hipMemcpyAsync(words, f.dStatus, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, fs));
         if (readQueue) DXV_HIP(c, hipMemcpyAsync(c->pin->queueLens[i], f.dQueue + f.queueHdr * kQueueHeaderWords + queue_len_word(0), sizeof(c->pin->queueLens[i]), hipMemcpyDeviceToHost, fs));
         DXV_HIP(c, hipStreamSynchronize(fs));
+        if (f.renderTimed) { f.render_ms = elapsed(f.evR0, f.evR1); f.renderTimed = false; }
         // lists this launch was queued behind without waiting for their verdict: withdrawn -> the launch again, through the tree
         if (settle_lists(c)) return 1;
         if (f.pending && f.usedLists && f.listEpochUsed == c->withdrawnEpoch && c->haveScene && f.grid_dim) {
@@ -492,9 +495,107 @@ int sync_frame(dxv_ctx* c, uint32_t i)
     return 0;
 }
 
+// The display pass of the selected frame into dst (device memory, rows `pitch` bytes apart), enqueued on the frame's stream behind
+// whatever it holds: the empty-brick flags into the frame's own scratch, the ray-cast, the frame's end event behind both (what
+// dxv_stream_wait_frame and a refit on another stream wait for).  The caller has checked the frame's grid and the target.
+int render_frame(dxv_ctx* c, const RayCastCB& cb, uint32_t width, uint32_t height, uint8_t* dst, size_t pitch, bool timed)
+{
+    Frame& f = cur_frame(c);
+    const hipStream_t fs = cur_stream(c);
+    const uint32_t N = f.grid_dim;
+    if (c->optSkipEmpty && empty_brick_bytes(N) > f.emptyCap) {
+        DXV_HIP(c, hipStreamSynchronize(fs));                           // (only this frame's stream reads the flags)
+        (void)hipFree(f.dEmpty); f.dEmpty = nullptr; f.emptyCap = 0;
+        DXV_HIP(c, hipMalloc(&f.dEmpty, align256(empty_brick_bytes(N))));
+        f.emptyCap = empty_brick_bytes(N);
+    }
+    if (timed) DXV_HIP(c, hipEventRecord(f.evR0, fs));
+    DXV_HIP(c, launch_raycast(cb, f.dGrid, N, width, height, dst, pitch, c->optSkipEmpty ? f.dEmpty : nullptr, fs));
+    if (timed) DXV_HIP(c, hipEventRecord(f.evR1, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    f.renderTimed = timed;
+    return 0;
+}
+
+// dxv_render_async / dxv_stream_wait_frame: the host waits for the selected frame's launch only when that launch can still report
+// something -- the rule of dxv_refit: a tree walk whose column can run out (redone with a deeper one), lists that failed their
+// deferred check (launched again through the tree).  Anything else is left to the device.
+static int settle_frame_launch(dxv_ctx* c)
+{
+    if (settle_lists(c)) return 1;                                     // (waits for a list build's end, not for the launch behind it)
+    Frame& f = cur_frame(c);
+    if (f.pending && (f.lastCanFail || (f.usedLists && f.listEpochUsed == c->withdrawnEpoch))) return sync_frame(c, c->cur);
+    return 0;
+}
+
+// a whole grid to render: the frame's last launch was neither a slab nor a share
+bool frame_renderable(const Frame& f)
+{
+    const uint32_t N = f.grid_dim;
+    return f.dGrid && N && f.z0 == 0 && f.nz == N && f.lastZBlock == N;
+}
+
 } // namespace dxvhost
 
 extern "C" {
+
+int dxv_update_frame(dxv_ctx* c, const float eye[3], const float viewProj[16], const float posScale[4], uint32_t width, uint32_t height)
+{
+    if (!c) return 1;
+    if (!eye || !viewProj || !width || !height || width > 16384 || height > 16384)
+        return fail(c, "dxv_update_frame: bad arguments (eye, view_proj, a viewport of 1 .. 16384 pixels per side)");
+    const float unit[4] = {0.0f, 0.0f, 0.0f, 1.0f};                 // DXRVoxelizer.cpp:37
+    RayCastCB cb;
+    if (!update_frame(c->bound, posScale ? posScale : unit, eye, viewProj, (float)width, (float)height, cb))
+        return fail(c, "dxv_update_frame: singular view/projection chain (or no mesh bound yet)");
+    Frame& f = cur_frame(c);
+    f.cb = cb;
+    f.cbWidth = width; f.cbHeight = height;
+    return 0;
+}
+
+int dxv_render_async(dxv_ctx* c, void* deviceRgba, size_t rowPitch)
+{
+    if (!c) return 1;
+    Frame& f = cur_frame(c);
+    if (!f.cbWidth) return fail(c, "dxv_render_async: frame %u has no ray-cast constants (call dxv_update_frame first)", c->cur);
+    if (!frame_renderable(f))
+        return fail(c, "dxv_render_async: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share");
+    const uint32_t w = f.cbWidth, h = f.cbHeight;
+    if (!deviceRgba || rowPitch < (size_t)w * 4 || rowPitch % 4 || reinterpret_cast<uintptr_t>(deviceRgba) % 4)
+        return fail(c, "dxv_render_async: target %p with row pitch %zu: need a 4-byte aligned pointer and a pitch that is a multiple of 4 "
+                       "and at least width * 4 = %zu", deviceRgba, rowPitch, (size_t)w * 4);
+    DXV_HIP(c, hipSetDevice(c->device));
+    // the target must be device memory of this context's device, and the whole image must lie inside its allocation
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, deviceRgba) != hipSuccess) {
+        (void)hipGetLastError();                                        // (an unknown host pointer is an error of that call: not sticky here)
+        return fail(c, "dxv_render_async: %p is not device memory (host memory is refused)", deviceRgba);
+    }
+    if (a.type != hipMemoryTypeDevice || a.device != c->device)
+        return fail(c, "dxv_render_async: %p is not device memory of device %d (memory type %d, device %d)", deviceRgba, c->device, (int)a.type, a.device);
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, deviceRgba) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, "dxv_render_async: no allocation found behind %p", deviceRgba);
+    }
+    const size_t offset = (size_t)(static_cast<uint8_t*>(deviceRgba) - static_cast<uint8_t*>(base)), need = (size_t)(h - 1) * rowPitch + (size_t)w * 4;
+    if (static_cast<uint8_t*>(deviceRgba) < static_cast<uint8_t*>(base) || offset > size || need > size - offset)
+        return fail(c, "dxv_render_async: %u x %u texels at pitch %zu need %zu bytes, the allocation behind %p has %zu", w, h, rowPitch, need,
+                    deviceRgba, offset <= size ? size - offset : (size_t)0);
+    if (settle_frame_launch(c)) return 1;
+    return render_frame(c, f.cb, w, h, static_cast<uint8_t*>(deviceRgba), rowPitch, c->optEvents != 0);
+}
+
+int dxv_stream_wait_frame(dxv_ctx* c, void* hipStream)
+{
+    if (!c) return 1;
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (settle_frame_launch(c)) return 1;
+    DXV_HIP(c, hipStreamWaitEvent(static_cast<hipStream_t>(hipStream), cur_frame(c).evEnd, 0));
+    return 0;
+}
 
 int dxv_voxelize_async(dxv_ctx* c, uint32_t N, int mode, uint32_t z0, uint32_t nz)
 {

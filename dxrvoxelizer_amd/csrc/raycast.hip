@@ -60,8 +60,10 @@ __global__ __launch_bounds__(256) void k_brick_empty(const uint8_t* __restrict__
     empty[i] = touched ? 0 : 1;
 }
 
+// rgba8: row r of the image at rgba8 + r * pitch bytes (pitch a multiple of 4, >= width * 4); only the width * 4 bytes of a row
+// are written, whatever lies behind them in the pitch is left alone
 __global__ __launch_bounds__(256) void k_raycast(RayCastCB cb, const uint8_t* __restrict__ grid, uint32_t N,
-                                                 uint32_t width, uint32_t height, uint32_t* __restrict__ rgba8,
+                                                 uint32_t width, uint32_t height, uint8_t* __restrict__ rgba8, size_t pitch,
                                                  const uint8_t* __restrict__ empty)
 {
     const uint32_t px = blockIdx.x * 16u + (threadIdx.x & 15u), py = blockIdx.y * 16u + (threadIdx.x >> 4);
@@ -76,7 +78,7 @@ __global__ __launch_bounds__(256) void k_raycast(RayCastCB cb, const uint8_t* __
         if (v > 1.0f) v = 1.0f;
         out |= (uint32_t)(v * 255.0f + 0.5f) << (8 * k);          // R8G8B8A8_UNORM
     }
-    rgba8[(size_t)py * width + px] = out;
+    *reinterpret_cast<uint32_t*>(rgba8 + (size_t)py * pitch + (size_t)px * 4u) = out;
 }
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -88,9 +90,10 @@ size_t empty_brick_bytes(uint32_t N)
     return 2 * align_up(M * M * M, 256);
 }
 
-// empty: scratch of empty_brick_bytes(N) bytes for the empty-brick flags, or NULL to march without them
+// rgba8 / pitch: the image's first row and the bytes from one row to the next (k_raycast); empty: scratch of
+// empty_brick_bytes(N) bytes for the empty-brick flags, or NULL to march without them
 hipError_t launch_raycast(const RayCastCB& cb, const uint8_t* grid, uint32_t N, uint32_t width, uint32_t height,
-                          uint32_t* rgba8, uint8_t* empty, hipStream_t s)
+                          uint8_t* rgba8, size_t pitch, uint8_t* empty, hipStream_t s)
 {
     if (empty) {
         const uint32_t M = (N + kEmptyBrick - 1) / kEmptyBrick, waves = ((M + 7u) / 8u) * M * M;
@@ -99,7 +102,7 @@ hipError_t launch_raycast(const RayCastCB& cb, const uint8_t* grid, uint32_t N, 
         k_brick_empty<<<(M * M * M + 255u) / 256u, 256, 0, s>>>(summary, M, empty);
     }
     const dim3 g((width + 15) / 16, (height + 15) / 16), b(256);
-    k_raycast<<<g, b, 0, s>>>(cb, grid, N, width, height, rgba8, empty);
+    k_raycast<<<g, b, 0, s>>>(cb, grid, N, width, height, rgba8, pitch, empty);
     return hipGetLastError();
 }
 

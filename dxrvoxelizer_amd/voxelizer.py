@@ -42,6 +42,7 @@ class Voxelizer:
         self.device = int(device)
         self._frame = 0
         self._lasts = {}
+        self._viewports = {}
         # DXV_OPTIONS="key=value,...": options for every context of a process (A/B runs of the tools without touching them)
         import os
         for kv in filter(None, os.environ.get("DXV_OPTIONS", "").split(",")):
@@ -168,6 +169,46 @@ class Voxelizer:
         out = np.empty((int(height), int(width), 4), np.uint8)
         self._check(self._lib.dxv_render(self._ctx, eye, vp, ps, int(width), int(height), out.ctypes.data_as(C.c_void_p)))
         return out
+
+    # ---- the reference's frame loop: per-frame constants, ray-cast into a device render target ----
+    def UpdateFrame(self, frameIndex, eyePt, viewProj, width, height, posScale=None):
+        """Voxelizer::UpdateFrame(frameIndex, eyePt, viewProj) (Content/Voxelizer.cpp:81-106): frame frameIndex's ray-cast
+        constants for a width x height viewport (dxv_update_frame), kept by the frame until its next UpdateFrame."""
+        self.SetFrame(frameIndex)
+        eye = np.ascontiguousarray(eyePt, np.float32).reshape(3)
+        vp = np.ascontiguousarray(viewProj, np.float32).reshape(16)
+        ps = None if posScale is None else np.ascontiguousarray(posScale, np.float32).reshape(4)
+        self._check(self._lib.dxv_update_frame(self._ctx, eye, vp, None if ps is None else ps.ctypes.data_as(C.c_void_p),
+                                               int(width), int(height)))
+        self._viewports[self._frame] = (int(height), int(width))
+        return True
+
+    def RenderAsync(self, target, frameIndex=None):
+        """renderRayCast(frameIndex) (Content/Voxelizer.cpp:371-399) into `target` on the GPU, enqueued behind the frame's launch
+        (dxv_render_async).  target: anything with data_ptr(), shape (H, W, 4) of the frame's viewport, dtype uint8, and rows
+        at least W * 4 bytes apart -- a torch tensor on this device, or a row slice big[:, :W] of a wider one.  Ordering the target
+        against other streams is the caller's (WaitFrameOn, Sync)."""
+        if frameIndex is not None:
+            self.SetFrame(frameIndex)
+        shape = tuple(int(n) for n in target.shape)
+        if len(shape) != 3 or shape[2] != 4 or not str(target.dtype).endswith("uint8"):
+            raise DxvError(f"RenderAsync: target must be uint8 of shape (H, W, 4), got {target.dtype} {shape}")
+        want = self._viewports.get(self._frame)
+        if want is not None and shape[:2] != want:
+            raise DxvError(f"RenderAsync: target is {shape[0]} x {shape[1]}, frame {self._frame}'s viewport {want[0]} x {want[1]}")
+        stride = tuple(int(n) for n in target.stride()) if callable(getattr(target, "stride", None)) else (shape[1] * 4, 4, 1)
+        if stride[1:] != (4, 1):
+            raise DxvError(f"RenderAsync: the texels of a row must be contiguous (strides {stride})")
+        pitch = stride[0] * (int(target.element_size()) if hasattr(target, "element_size") else 1)
+        self._check(self._lib.dxv_render_async(self._ctx, C.c_void_p(int(target.data_ptr())), pitch))
+        return True
+
+    def WaitFrameOn(self, stream_handle):
+        """Make a consumer's stream (a hipStream_t handle, e.g. torch's stream.cuda_stream, or an object with that attribute) wait
+        on the device for everything enqueued on the selected frame so far (dxv_stream_wait_frame)."""
+        handle = getattr(stream_handle, "cuda_stream", stream_handle)
+        self._check(self._lib.dxv_stream_wait_frame(self._ctx, C.c_void_p(int(handle)) if handle else None))
+        return True
 
     # ---- results ----------------------------------------------------------------------------
     def Grid(self):

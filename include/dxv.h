@@ -22,6 +22,8 @@ extern "C" {
 
 /* Bumped whenever an entry point changes its signature or a struct of this header its layout; dxv_api_version() returns the
  * value the loaded library was built with -- a binding compares the two before its first call.
+ * 7: dxv_update_frame / dxv_render_async / dxv_stream_wait_frame (the ray-cast into a device render target with per-frame constants);
+ *    dxv_stats.render_ms is the selected frame's;
  * 6: dxv_prepare_launch / dxv_prepare_launch_interleaved (the work queue of a static scene as Init-time structure), dxv_warmup,
  *    dxv_stats grows plan_prepared / prepare_ms / warmup_ms, options prepared / prepclear, dxv_build_lists_for_grid prepares the grid
  *    it is given;
@@ -29,7 +31,7 @@ extern "C" {
  *    queue is opt-in), options planregion / planheavy / fuse / queueheads;
  * 4: dxv_stats plan fields describe the work queue, options planorder / planregion gone, dxv_debug_plan_check, dxv_trim;
  * 3: dxv_debug_list_check takes a slab (z0, nz). */
-#define DXV_API_VERSION 6
+#define DXV_API_VERSION 7
 DXV_API int dxv_api_version(void);
 
 typedef struct dxv_ctx dxv_ctx;
@@ -67,7 +69,7 @@ typedef struct dxv_stats {
     float voxelize_ms;       /* last dxv_voxelize kernel, HIP events on the ctx stream         */
     uint32_t grid_dim, z0, nz; /* last dxv_voxelize                                            */
     uint32_t stack_entries;  /* LDS traversal stack entries per thread of the last launch      */
-    float render_ms;         /* last dxv_render kernel, HIP events                                  */
+    float render_ms;         /* the selected frame's last render (flags + ray-cast), HIP events; of a dxv_render_async: read by the frame's next dxv_sync */
     uint32_t redo_rays;      /* rays of the last launch finished by the deep-stack redo pass       */
     uint32_t row_block;      /* parity rule: rows per side of a wave's block of rows (1, 2 or 4)   */
     float tri_extent;        /* mean triangle box extent along y/z, normalised units               */
@@ -176,7 +178,7 @@ DXV_API int dxv_sync(dxv_ctx* ctx);
  * frameIndex (static const uint8_t FrameCount, Content/Voxelizer.h:24; m_grids[FrameCount], :110;
  * Render(pCommandList, frameIndex, ...), :21-22; voxelize(pCommandList, frameIndex), Content/Voxelizer.cpp:351-356),
  * so that the GPU works on one grid while the host still reads another.  dxv_set_frame selects the frame the
- * following dxv_voxelize* / dxv_sync / dxv_grid_* / dxv_texels_download / dxv_render / dxv_get_stats calls refer to
+ * following dxv_voxelize* / dxv_sync / dxv_grid_* / dxv_texels_download / dxv_render* / dxv_update_frame / dxv_get_stats calls refer to
  * (default 0).  Each frame owns its grid, texel image, status words and -- frames 1 and 2 -- an internal stream,
  * so launches of different frames overlap on the GPU; scene, candidate lists and options are shared (an extra frame
  * costs its grid).  Calls that change what the frames read (dxv_set_mesh, dxv_build, dxv_scene_import, dxv_set_stream) first
@@ -249,9 +251,48 @@ DXV_API int dxv_texels_download(dxv_ctx* ctx, uint32_t* host, size_t bytes);
  * march through the grid's alpha with a 32-step light march).  eye and view_proj (row-major, row
  * vectors: v' = v * M, as DirectXMath stores them) are what the app passes to UpdateFrame
  * (DXRVoxelizer.cpp:249-254); pos_scale = {x, y, z, scale} or NULL for the default {0,0,0,1}.
- * Renders the whole grid of the last dxv_voxelize into width*height R8G8B8A8 texels on the host. */
+ * Renders the whole grid of the last dxv_voxelize into width*height R8G8B8A8 texels on the host.
+ * Synchronous: waits for the frame's launch first and for the image's copy at the end (dxv_render_async below is the
+ * reference's frame loop, which does neither). */
 DXV_API int dxv_render(dxv_ctx* ctx, const float eye[3], const float view_proj[16], const float pos_scale[4],
                        uint32_t width, uint32_t height, uint8_t* rgba_host);
+
+/* The reference's frame loop: UpdateFrame(frameIndex, eyePt, viewProj) writes that frame's constants, Render(..., frameIndex,
+ * rtv, dsv) is voxelize + renderRayCast into a render target on the GPU, FrameCount frames are in flight and the host never waits
+ * for an image (Content/Voxelizer.cpp:81-113, :371-399; Content/Voxelizer.h:24).  All three calls refer to the frame selected
+ * by dxv_set_frame.
+ *
+ * dxv_update_frame -- Voxelizer::UpdateFrame (Content/Voxelizer.cpp:81-106): the selected frame's ray-cast constants, computed
+ * now from the scene's bound, pos_scale (NULL = {0,0,0,1}), the camera (as for dxv_render) and the viewport (the width / height
+ * the reference's Init receives, 1 .. 16384 each).  Kept by the frame until its next dxv_update_frame.  Fails on a singular
+ * view/projection chain; then nothing changes. */
+DXV_API int dxv_update_frame(dxv_ctx* ctx, const float eye[3], const float view_proj[16], const float pos_scale[4],
+                             uint32_t width, uint32_t height);
+/* dxv_render_async -- renderRayCast(frameIndex) into a caller's render target (Content/Voxelizer.cpp:371-399): the selected
+ * frame's whole grid ray-cast with that frame's constants into width x height R8G8B8A8 texels at device_rgba, row r at
+ * device_rgba + r * row_pitch bytes.  The image equals dxv_render's byte for byte.  ENQUEUED on the frame's stream behind the
+ * frame's last launch; returns without waiting.  Errors of the launch come back from dxv_sync.
+ *  - The host waits only where the device cannot be trusted (the rule of dxv_refit): when the frame's last launch can still
+ *    report something -- a tree walk whose column can run out and be redone, lists whose deferred check failed -- the frame is
+ *    synchronised first; otherwise the call only enqueues.  A prepared static scene in the reference rule (the lists, the
+ *    default) thus renders a frame with NO host round trip: dxv_voxelize_async + dxv_render_async.
+ *  - Checked on the host before anything is enqueued, each an error with a message: the frame has constants; its last launch
+ *    was the whole grid (not a slab or a share); row_pitch >= width * 4 and a multiple of 4, device_rgba 4-byte aligned;
+ *    device_rgba is device memory of this context's device (host and pinned host memory are refused) and the image lies
+ *    inside its allocation.
+ *  - Frames share nothing while rendering: each owns its constants, its empty-brick flags (option skipempty; growing them waits
+ *    for that frame's stream only) and its render events.
+ *  - The render target's own ordering belongs to the caller, as the reference keeps one render target per frame
+ *    (m_renderTargets[FrameCount]): whatever else writes or reads device_rgba must be ordered against the frame's stream by the
+ *    caller (dxv_stream_wait_frame, or a dxv_sync).  Only width * 4 bytes of each row are written: padding bytes inside the
+ *    pitch keep their values.
+ *  - Option events = 1 (default): the render is bracketed by the frame's own two events, and dxv_stats.render_ms of the frame
+ *    is read at the frame's next dxv_sync. */
+DXV_API int dxv_render_async(dxv_ctx* ctx, void* device_rgba, size_t row_pitch);
+/* dxv_stream_wait_frame -- the reference's barrier to PIXEL_SHADER_RESOURCE (Content/Voxelizer.cpp:376-378): makes hip_stream
+ * (a consumer's stream; NULL = the null stream) wait ON THE DEVICE for everything enqueued on the selected frame so far (its
+ * launch, its render).  Synchronises on the host first under the same rule as dxv_render_async. */
+DXV_API int dxv_stream_wait_frame(dxv_ctx* ctx, void* hip_stream);
 
 /* Multi-GPU: the built scene (nodes + triangle data) as one relocatable device blob, so that
  * rank 0 builds once and the host layer broadcasts it (RCCL over xGMI) to the other ranks.
@@ -363,9 +404,9 @@ DXV_API int dxv_get_stats(const dxv_ctx* ctx, dxv_stats* out);
  *                 default: all stay; a caller's knob from before queuewaves picked its own default on coarse grids)
  *   sortbits 0|8..11 (+16, +32)  diagnostic, process-wide: widest digit of the builds' radix sort (0, default: 10 or 11 bits -- three
  *                 passes for the LBVH's keys, four for the lists'); +16 / +32: tiles of 4 / 16 waves whatever the size.  Same results.
- *   events 0|1    bracket every launch with two HIP events for stats.voxelize_ms (default 1); 0 for a caller that times its own
- *                 loop of back-to-back launches (the events cost ~8 us of stream time per launch)
- *   skipempty 0|1 dxv_render: skip the samples of empty 8^3 bricks (default 1; same image)
+ *   events 0|1    bracket every launch and every dxv_render_async with two HIP events for stats.voxelize_ms / render_ms (default 1);
+ *                 0 for a caller that times its own loop of back-to-back launches (the events cost ~8 us of stream time per launch)
+ *   skipempty 0|1 dxv_render, dxv_render_async: skip the samples of empty 8^3 bricks (default 1; same image)
  *   morton 0|1, region 0..24, subbox 0|1   brick order, bricks per XCD region (log2), partial launch */
 DXV_API int dxv_set_option(dxv_ctx* ctx, const char* key, int64_t value);
 

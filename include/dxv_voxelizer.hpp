@@ -7,7 +7,8 @@
 //   void UpdateFrame(frameIndex, eyePt, viewProj);  void Render(pCommandList, frameIndex, rtv, dsv);
 //   protected: void voxelize(pCommandList, frameIndex);   // the hot call, GRID_SIZE = 64 macro
 //
-// Here: the D3D12-only parameters are gone; `voxelize` is public as Voxelize(gridDim) with the
+// Here: the D3D12-only parameters are gone (command lists, descriptor tables, formats, uploaders; the render target is a
+// device pointer and its row pitch, the viewport is SetViewport's); `voxelize` is public as Voxelize(gridDim) with the
 // grid size promoted from the GRID_SIZE macro (Content/Voxelizer.cpp:8) to a parameter; every
 // fallible call returns bool like the reference (XUSG/Core/XUSG.h:12-15) and never throws.
 // posScale is accepted and, exactly as in the reference, does not affect voxelisation
@@ -131,6 +132,27 @@ public:
 		return dxv_render(m_ctx, m_eyePt, m_viewProj, m_posScale, width, height, rgba.data()) == 0;
 	}
 
+	// The reference's frame loop (Content/Voxelizer.cpp:81-113, :371-399): FrameCount frames in flight, each with its own
+	// constants and its own render target on the GPU, and no host wait for an image.
+	//   SetViewport(width, height)                     the width / height the reference's Init receives (default 1280 x 720)
+	//   UpdateFrame(frameIndex, eyePt, viewProj)        that frame's ray-cast constants (dxv_update_frame)
+	//   Render(frameIndex, gridDim, deviceRgba, pitch)  VoxelizeAsync + the ray-cast into width x height R8G8B8A8 texels at
+	//                                                  deviceRgba (device memory, rows pitch bytes apart), enqueued (dxv_render_async)
+	//   WaitFrameOn(frameIndex, hipStream)             a consumer's stream waits on the device for that frame (dxv_stream_wait_frame)
+	// WaitFrame / WaitAll report the launches' and renders' errors.  Ordering the render targets is the caller's, as in the
+	// reference (one render target per frame).
+	void SetViewport(uint32_t width, uint32_t height) { m_width = width; m_height = height; }
+	bool UpdateFrame(uint8_t frameIndex, const float eyePt[3], const float viewProj[16])
+	{
+		if (!SetFrame(frameIndex)) return false;
+		return dxv_update_frame(m_ctx, eyePt, viewProj, m_posScale, m_width, m_height) == 0;
+	}
+	bool Render(uint8_t frameIndex, uint32_t gridDim, void* deviceRgba, size_t rowPitch)
+	{
+		return VoxelizeAsync(frameIndex, gridDim) && dxv_render_async(m_ctx, deviceRgba, rowPitch) == 0;
+	}
+	bool WaitFrameOn(uint8_t frameIndex, void* hipStream) { return SetFrame(frameIndex) && dxv_stream_wait_frame(m_ctx, hipStream) == 0; }
+
 	// Result: uint8 occupancy, x fastest, then y (top to bottom), then z.
 	bool Download(std::vector<uint8_t>& grid)
 	{
@@ -162,5 +184,6 @@ protected:
 	float		m_posScale[4] = { 0.0f, 0.0f, 0.0f, 1.0f };
 	float		m_eyePt[3] = { 8.0f, 12.0f, -14.0f };	// DXRVoxelizer.cpp:230
 	float		m_viewProj[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
+	uint32_t	m_width = 1280, m_height = 720;	// Main.cpp:17
 	std::string	m_err;
 };
