@@ -209,6 +209,7 @@ int dxv_warmup(int device, float* ms)
             (void)dxv_set_option(w, "prepared", 0);
             (void)dxv_voxelize(w, 32, DXV_MODE_REFERENCE, 0, 32);       // (through a queue of its own)
             (void)dxv_voxelize(w, 32, DXV_MODE_PARITY, 0, 32);
+            (void)dxv_voxelize(w, 32, DXV_MODE_SURFACE, 0, 32);
             std::vector<uint8_t> host(32 * 32 * 32);
             (void)dxv_grid_download(w, host.data(), host.size());
         }
@@ -238,7 +239,7 @@ void dxv_destroy(dxv_ctx* c)
         if (f.evEnd) (void)hipEventDestroy(f.evEnd);
         if (f.evR0) (void)hipEventDestroy(f.evR0);
         if (f.evR1) (void)hipEventDestroy(f.evR1);
-        (void)hipFree(f.dEmpty);
+        (void)hipFree(f.dEmpty); (void)hipFree(f.dSurf);
         if (f.ownStream) (void)hipStreamDestroy(f.ownStream);
     }
     free_scratch(c);
@@ -777,6 +778,9 @@ int dxv_set_option(dxv_ctx* c, const char* key, int64_t value)
         // tools/ablate.py builds for itself (python -m dxrvoxelizer_amd.build --ablate -> libdxv_ablate.so)
         if (value != 0) return fail(c, "option ablate: this library was built without the ablation kernels (-DDXV_ABLATE)");
 #endif
+    } else if (!strcmp(key, "surfaceitems")) {
+        if (value < 0 || value > (1 << 20)) return fail(c, "option surfaceitems: %lld not in [0, 2^20]", (long long)value);
+        c->optSurfaceItems = (int)value;
     } else if (!strcmp(key, "skipempty")) {
         if (value != 0 && value != 1) return fail(c, "option skipempty: %lld not in {0,1}", (long long)value);
         c->optSkipEmpty = (int)value;

@@ -118,6 +118,10 @@ struct dxv_ctx {
         hipEvent_t evR0 = nullptr, evR1 = nullptr;   // around the frame's last render
         bool renderTimed = false;        // ... which was bracketed by them and not read yet (the frame's next dxv_sync reads it)
         float render_ms = 0.0f;
+        // surface modes (surface.hip): the large triangles' lists of the frame's surface pass, its own (never the work queue's
+        // buffers: a kept queue of the reference rule is still needed by the frame's next mode-0 launch)
+        uint8_t* dSurf = nullptr;
+        size_t surfCap = 0;
     };
     Frame frames[DXV_FRAME_COUNT];
     uint32_t cur = 0;                    // dxv_set_frame
@@ -237,6 +241,7 @@ struct dxv_ctx {
                                      // 1 = the four-box copy (nodes64); 2 = every node box (dxv_refit stopped at the pyramid: deferBoxes)
     int listOpt = 0;                 // the listres option the current lists (or the decision against them) were made with
     int optSkipEmpty = 1;    // display pass: skip the samples of empty 8^3 bricks (same image)
+    int optSurfaceItems = 0; // surface modes: work items the large triangles' list may take (0: all 2^20 it holds; fewer: tests of a full list)
 
     hipEvent_t ev[10] = {};
     dxv_stats stats{};
@@ -278,6 +283,8 @@ inline Node32* scene_nodes32(dxv_ctx* c) { return reinterpret_cast<Node32*>(c->d
 inline Node64* scene_nodes64(dxv_ctx* c) { return reinterpret_cast<Node64*>(c->dScene + c->hdr.offNodes64); }
 inline TriPos* scene_tripos(dxv_ctx* c) { return reinterpret_cast<TriPos*>(c->dScene + c->hdr.offTriPos); }
 inline TriNrm* scene_trinrm(dxv_ctx* c) { return reinterpret_cast<TriNrm*>(c->dScene + c->hdr.offTriNrm); }
+// the ray rule a launch of this mode runs (mode 3 is the reference rule's launch, then the surface pass; mode 2 runs none)
+inline int ray_rule(int mode) { return mode == DXV_MODE_REFERENCE_SURFACE ? DXV_MODE_REFERENCE : mode; }
 inline float elapsed(hipEvent_t a, hipEvent_t b)
 {
     float ms = 0.0f;

@@ -165,6 +165,20 @@ hipError_t launch_checksum(const void* buf, size_t bytes, unsigned long long* ou
 hipError_t launch_pack_bits(const uint8_t* grid, size_t n, uint8_t* packed, hipStream_t s);
 int num_brick_shapes();
 
+// surface.hip -- the surface rule (dxv_surface.h) scattered over a partition: every voxel it accepts is set to 1, nothing else is
+// written (mode 2 clears the partition in front of it, mode 3 runs it behind the reference rule's launch)
+struct SurfaceParams {
+    const TriPos* triPos;   // T
+    uint32_t T;
+    uint8_t* grid;          // N*N*nz bytes
+    uint32_t N, z0, nz;     // slices as VoxelizeParams: global slice of lz = z0 + (lz / zBlock) * zPeriod + lz % zBlock
+    uint32_t zBlock, zPeriod;
+    uint8_t* scratch;       // surface_scratch_bytes(T): the large triangles' lists and counters (one per frame: frames run side by side)
+    uint32_t items;         // work items the list may take: 0 = all it holds (2^20); fewer: option surfaceitems (tests)
+};
+size_t surface_scratch_bytes(uint32_t T);
+hipError_t launch_surface(const SurfaceParams& p, hipStream_t s);
+
 // raycast.hip
 struct RayCastCB;
 hipError_t launch_raycast(const RayCastCB& cb, const uint8_t* grid, uint32_t N, uint32_t width, uint32_t height,

@@ -184,6 +184,26 @@ int safe_stack(const dxv_ctx* c, int mode)
     return stack_round_up((int)c->hdr.treeHeight + 3);
 }
 
+// The surface pass of the frame's partition (surface.hip), on the frame's stream behind whatever is in it: sets the voxels the surface
+// rule accepts, writes nothing else.  Reads the triangle records alone: no lists, no tree, no queue.
+static int enqueue_surface(dxv_ctx* c, uint32_t frame, hipStream_t fs)
+{
+    Frame& f = c->frames[frame];
+    const size_t bytes = surface_scratch_bytes(c->hdr.numTris);
+    if (bytes > f.surfCap) {
+        DXV_HIP(c, hipStreamSynchronize(fs));                           // (only this frame's stream uses it)
+        (void)hipFree(f.dSurf); f.dSurf = nullptr; f.surfCap = 0;
+        DXV_HIP(c, hipMalloc(&f.dSurf, bytes));
+        f.surfCap = bytes;
+    }
+    SurfaceParams sp{};
+    sp.triPos = scene_tripos(c); sp.T = c->hdr.numTris;
+    sp.grid = f.dGrid; sp.N = f.grid_dim; sp.z0 = f.z0; sp.nz = f.nz; sp.zBlock = f.lastZBlock; sp.zPeriod = f.lastZPeriod;
+    sp.scratch = f.dSurf; sp.items = (uint32_t)c->optSurfaceItems;
+    DXV_HIP(c, launch_surface(sp, fs));
+    return 0;
+}
+
 // relaunch: the same launch again with a deeper column (sync_frame, after a walk reported an overflow) -- possibly on behalf of
 // a caller that is about to replace the scene (sync_frames): it builds nothing, it takes the candidate structures that exist.
 int launch_now(dxv_ctx* c, uint32_t frame, bool relaunch)
@@ -197,7 +217,7 @@ int launch_now(dxv_ctx* c, uint32_t frame, bool relaunch)
     p.grid = f.dGrid; p.texels = c->texels ? f.dTexels : nullptr; p.status = f.dStatus;
     p.clearSig = &f.clearSig;
     p.redo = f.dRedo; p.redoCap = kRedoCap; p.redoParity = f.redoParity;
-    p.N = f.grid_dim; p.z0 = f.z0; p.nz = f.nz; p.mode = f.lastMode;
+    p.N = f.grid_dim; p.z0 = f.z0; p.nz = f.nz; p.mode = ray_rule(f.lastMode);
     p.zBlock = f.lastZBlock; p.zPeriod = f.lastZPeriod;
     p.zShift = 0;
     while ((1u << p.zShift) < p.zBlock) ++p.zShift;
@@ -212,6 +232,22 @@ int launch_now(dxv_ctx* c, uint32_t frame, bool relaunch)
     uint32_t cap = 0;                                                   // words per XCD queue of this partition
     f.list_entries = 0; f.list_res = 0;
     f.usedLists = false;
+    if (f.lastMode == DXV_MODE_SURFACE) {
+        // the surface rule alone: outside the lists' policy (no build, no launch count, no queue, no far map, no tree), nothing to
+        // report afterwards; the partition is cleared and the scatter sets its voxels
+        f.plan_bricks = 0; f.plan_waves = 0; f.plan_ms = 0.0f;
+        f.lastQueued = false; f.lastPrepared = -1; f.lastRedoParity = -1; f.lastCanFail = false;
+        f.stack_entries = 0;
+        if (c->optEvents) DXV_HIP(c, hipEventRecord(f.ev0, fs));
+        DXV_HIP(c, hipMemsetAsync(f.dGrid, 0, f.gridBytes, fs));
+        if (enqueue_surface(c, frame, fs)) return 1;
+        f.clearSig = 0; f.queueLenSig = 0;                             // (nothing of the grid may be kept by a later launch)
+        if (c->optEvents) DXV_HIP(c, hipEventRecord(f.ev1, fs));
+        DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+        f.timed = c->optEvents != 0;
+        f.pending = true;
+        return 0;
+    }
     // WHEN the lists are built and on WHICH map is dxv_policy.h's lists_step (a pure function of the state below: tests/test_policy.py
     // walks its transitions): a first launch that is large enough may build them at once (lists = 1; the build's own estimate
     // decides after its counting pass), a scene launched AGAIN without a refit in between is static and moves to the fine map, once;
@@ -400,6 +436,12 @@ int launch_now(dxv_ctx* c, uint32_t frame, bool relaunch)
             f.redoParity ^= 1u;
         }
     }
+    if (f.lastMode == DXV_MODE_REFERENCE_SURFACE) {
+        // the shell behind the solid -- behind whatever this launch rewrote, relaunches (sync_frame) included; the surface's 1s lie
+        // outside the bricks a kept queue or a kept memset would skip, so the frame keeps nothing for its next launch
+        if (enqueue_surface(c, frame, fs)) return 1;
+        f.clearSig = 0; f.queueLenSig = 0;
+    }
     if (c->optEvents) DXV_HIP(c, hipEventRecord(f.ev1, fs));
     DXV_HIP(c, hipEventRecord(f.evEnd, fs));
     f.timed = c->optEvents != 0;
@@ -412,7 +454,8 @@ int launch_now(dxv_ctx* c, uint32_t frame, bool relaunch)
 int voxelize_common(dxv_ctx* c, uint32_t N, int mode, uint32_t z0, uint32_t nzLocal, uint32_t zBlock, uint32_t zPeriod)
 {
     if (!c->haveScene) return fail(c, "dxv_voxelize: no scene (call dxv_build or dxv_scene_import first)");
-    if (mode != DXV_MODE_REFERENCE && mode != DXV_MODE_PARITY) return fail(c, "dxv_voxelize: unknown mode %d", mode);
+    if (mode != DXV_MODE_REFERENCE && mode != DXV_MODE_PARITY && mode != DXV_MODE_SURFACE && mode != DXV_MODE_REFERENCE_SURFACE)
+        return fail(c, "dxv_voxelize: unknown mode %d", mode);
     if (c->texels && mode != DXV_MODE_REFERENCE) return fail(c, "dxv_voxelize: texel output exists in reference mode only");
     DXV_HIP(c, hipSetDevice(c->device));
     Frame& f = cur_frame(c);
@@ -482,10 +525,10 @@ int sync_frame(dxv_ctx* c, uint32_t i)
         f.pending = false;
         if (!status) return 0;
         DXV_HIP(c, hipMemsetAsync(f.dStatus, 0, sizeof(uint32_t), fs));
-        if (!c->optStack && c->stackNow < safe_stack(c, f.lastMode) && c->haveScene && f.grid_dim) {
+        if (!c->optStack && c->stackNow < safe_stack(c, ray_rule(f.lastMode)) && c->haveScene && f.grid_dim) {
             // grow to the next instantiated depth (at most up to the depth that cannot overflow) and redo
             const int next = stack_round_up(c->stackNow + 1);
-            c->stackNow = next < safe_stack(c, f.lastMode) ? next : safe_stack(c, f.lastMode);
+            c->stackNow = next < safe_stack(c, ray_rule(f.lastMode)) ? next : safe_stack(c, ray_rule(f.lastMode));
             if (launch_now(c, i, true)) return 1;
             continue;
         }

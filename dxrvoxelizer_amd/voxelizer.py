@@ -9,6 +9,7 @@ import numpy as np
 from ._lib import DxvError, Stats, load_library
 
 MODE_REFERENCE, MODE_PARITY = 0, 1
+MODE_SURFACE, MODE_REFERENCE_SURFACE = 2, 3      # the conservative surface; the reference rule's solid with that shell (include/dxv.h)
 DBG_SORTED_KEYS, DBG_NODES, DBG_TRI_POS, DBG_TRI_NRM, DBG_PARENTS, DBG_NODES32, DBG_NODES64, DBG_LIST_CELLS, DBG_LIST_ENTRIES, DBG_LIST_MIP = range(10)
 
 

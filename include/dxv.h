@@ -44,7 +44,15 @@ enum {
     DXV_MODE_REFERENCE = 0,
     /* north_star's second mode on the same traversal engine: +X axis ray, watertight hit count,
      * occupancy = count & 1 (no reference counterpart). */
-    DXV_MODE_PARITY = 1
+    DXV_MODE_PARITY = 1,
+    /* The conservative (26-separating) surface: a voxel is 1 exactly when its closed box overlaps at
+     * least one closed triangle -- Akenine-Moller's separating-axis test in float32 with a fixed
+     * operation order, the box centred on the voxel centre of the ray rules,
+     * half size 1 / grid_dim.  Marks the thin walls and features a centre rule drops. */
+    DXV_MODE_SURFACE = 2,
+    /* The solid with its shell: DXV_MODE_REFERENCE's grid OR DXV_MODE_SURFACE's, voxel by voxel. */
+    DXV_MODE_REFERENCE_SURFACE = 3
+    /* Modes 2 and 3 take the same grids and partitions as 0 and 1; the texel image exists in mode 0 only. */
 };
 
 /* What dxv_debug_download copies (tests only; layouts in dxrvoxelizer_amd/csrc/dxv_types.h). */
@@ -407,6 +415,8 @@ DXV_API int dxv_get_stats(const dxv_ctx* ctx, dxv_stats* out);
  *   events 0|1    bracket every launch and every dxv_render_async with two HIP events for stats.voxelize_ms / render_ms (default 1);
  *                 0 for a caller that times its own loop of back-to-back launches (the events cost ~8 us of stream time per launch)
  *   skipempty 0|1 dxv_render, dxv_render_async: skip the samples of empty 8^3 bricks (default 1; same image)
+ *   surfaceitems 0..2^20  test hook of the surface modes: work items the large triangles' list may take (0, default: all 2^20 it
+ *                 holds); a triangle whose items do not all fit is walked whole as well.  Same grids.
  *   morton 0|1, region 0..24, subbox 0|1   brick order, bricks per XCD region (log2), partial launch */
 DXV_API int dxv_set_option(dxv_ctx* ctx, const char* key, int64_t value);
 

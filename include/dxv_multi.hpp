@@ -29,7 +29,7 @@
 class MultiVoxelizer
 {
 public:
-	enum Mode : int { REFERENCE = DXV_MODE_REFERENCE, PARITY = DXV_MODE_PARITY };
+	enum Mode : int { REFERENCE = DXV_MODE_REFERENCE, PARITY = DXV_MODE_PARITY, SURFACE = DXV_MODE_SURFACE, REFERENCE_SURFACE = DXV_MODE_REFERENCE_SURFACE };
 	// SLABS: device g of G owns the contiguous slices [g N / G, (g + 1) N / G) (north_star's partition; the GPUs that own
 	// empty space idle).  BLOCK_CYCLIC: blocks of `zblock` slices dealt round-robin (SURVEY 8(e)'s fallback, what bench.py
 	// measures; needs gridDim % (zblock * G) == 0, else SLABS is used).

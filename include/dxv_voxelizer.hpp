@@ -23,7 +23,7 @@
 class Voxelizer
 {
 public:
-	enum Mode : int { REFERENCE = DXV_MODE_REFERENCE, PARITY = DXV_MODE_PARITY };
+	enum Mode : int { REFERENCE = DXV_MODE_REFERENCE, PARITY = DXV_MODE_PARITY, SURFACE = DXV_MODE_SURFACE, REFERENCE_SURFACE = DXV_MODE_REFERENCE_SURFACE };
 
 	explicit Voxelizer(int device = 0) : m_device(device) {}
 	virtual ~Voxelizer() { dxv_destroy(m_ctx); }
