@@ -96,7 +96,7 @@ struct dxv_ctx {
         uint32_t grid_dim = 0, z0 = 0, nz = 0, stack_entries = 0, redo_rays = 0, row_block = 0, list_entries = 0, list_res = 0;
         uint32_t plan_bricks = 0, plan_waves = 0;
         float plan_ms = 0.0f;
-        // work queue of the lists kernel (traverse.hip): the frame's own, written and read on the frame's stream only
+        // work queue of the lists kernel (voxelize_lists.hip): the frame's own, written and read on the frame's stream only
         uint32_t* dQueue = nullptr;      // two headers, then the slots (dxv_device.h)
         size_t queueWords = 0;           // allocated 32-bit words
         uint32_t queueHdr = 0;           // the header (0 / 1) of the frame's current queue; the next build takes the other one ...
@@ -184,7 +184,8 @@ struct dxv_ctx {
     uint16_t* dFarMip = nullptr;
     uint32_t farR = 0, farCap = 0;   // the map it is on / was allocated for
     float farMs = 0.0f;
-    int optListedWaves = 0;          // workgroups per CU of the hardware-dispatched lists kernel (8 .. 32), or 0 = by grid and map (traverse.hip: listed_lds_pad)
+    int optListedWaves = 0;          // workgroups per CU of the hardware-dispatched lists kernel (8 .. 32), or 0 = by grid and map (voxelize_lists.hip: listed_lds_pad)
+    ListsOccupancy occupancy;        // what the runtime said about the brick kernels on this context's device, asked at first use
     int optCoop = 1;                 // 1: the lists kernel scans a lone lane's long list with its whole wave (dxv_dirmap.h: trace_reference_dm_from)
     int optFarMap = 1;               // 1: tree walks and brick-box launches of the reference rule skip the bricks none of whose rays can reach a triangle
     int optPlan = 2;                 // work queue of the lists kernel (live bricks only, built on the device inside the stream): 0 = none (brick box

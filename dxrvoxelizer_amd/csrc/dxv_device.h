@@ -71,7 +71,7 @@ hipError_t parity_lists_total(const TriPos* triPos, uint32_t T, uint32_t R, unsi
 hipError_t parity_lists_fill(const TriPos* triPos, uint32_t T, uint32_t R, uint32_t* counts, uint32_t* offsets, uint32_t* sums, uint32_t* cells,
                              uint32_t* entries, hipStream_t s);
 
-// traverse.hip
+// traverse.hip / voxelize_lists.hip / parity_rows.hip -- one launch of a ray rule over a partition
 struct VoxelizeParams {
     SceneView scene;
     uint8_t* grid;          // N*N*nz bytes
@@ -97,7 +97,7 @@ struct VoxelizeParams {
     uint32_t lists;         // 1: reference rule reads the direction-space lists of p.scene (no tree walk)
     uint64_t* clearSig;     // host word of the frame (or NULL): signature of the partial launch whose memset the grid still carries -- the same launch again skips the memset
     uint32_t ablate;        // timing-only builds of the lists kernel (wrong grids; tools/ablate.py), 0 = the real kernel
-    uint32_t* queue;        // work queue of the lists kernel (traverse.hip): the header this launch uses (64 heads, 8 lengths, every word in a line of its own)
+    uint32_t* queue;        // work queue of the lists kernel (voxelize_lists.hip): the header this launch uses (64 heads, 8 lengths, every word in a line of its own)
     uint32_t* queueSlots;   // ... its 8 x queueCap brick words
     uint32_t* queueZero;    // ... the frame's OTHER header, cleared by k_plan_bricks for the launch that builds the next queue (or NULL)
     uint32_t queueCap;
@@ -112,11 +112,18 @@ struct VoxelizeParams {
     uint32_t mipR;          // brick-box launches (k_voxelize, 4^3 bricks, reference rule): the map `mip` was made on -- every workgroup makes
                             // the queue's brick test itself and a brick that cannot hold a live ray is zeroed and left; 0: no test
     uint32_t listedWaves;   // k_voxelize_listed without the texel image fits eight waves per SIMD (64 VGPRs, 32 workgroups per CU): 8 .. 32 = held at so many
-                            // workgroups per CU by LDS it does not use; 0: by grid and map (listed_lds_pad, traverse.hip; option listedwaves)
+                            // workgroups per CU by LDS it does not use; 0: by grid and map (listed_lds_pad, voxelize_lists.hip; option listedwaves)
     uint32_t* liveMask;     // k_plan_bricks: one bit per brick of the partition, id (bz nbx + by) nbx + bx, set for every queued brick (or NULL):
                             // what the clear of a launch through a PREPARED queue reads (only the bricks nobody runs are zeroed)
 };
+// traverse.hip -- tree walks (and the lists, plan = 0) over the brick box
 hipError_t launch_voxelize(const VoxelizeParams& p, int brickShape, int stackEntries, hipStream_t s);
+hipError_t launch_voxelize_redo(const VoxelizeParams& p, hipStream_t s);   // finishes the rays on p.redo with a full-depth stack
+int stack_round_up(int want);
+int stack_for_brick(int brickShape, int want);   // the column depth compiled for this brick shape that is >= want
+int num_brick_shapes();
+
+// voxelize_lists.hip -- the work queue of the lists kernel and the two brick kernels
 // header of a queue: 64 heads (eight per queue: head h of queue x hands out the slots k = h mod 8 of that queue; head
 // number 8 x + h), then the eight lengths, every word in a 256-byte line of its own.  Queue memory of a frame: TWO headers, then
 // the slots: a launch that builds a queue takes the header the last build did not use -- all zero, because that build's
@@ -131,7 +138,7 @@ DXV_HD constexpr uint32_t queue_head_word(uint32_t x, uint32_t h) { return 64u *
 DXV_HD constexpr uint32_t queue_len_word(uint32_t x) { return 64u * (65u + x); }      // light bricks of queue x
 DXV_HD constexpr uint32_t queue_heavy_word(uint32_t x) { return 64u * (73u + x); }    // heavy bricks of queue x (the sixteen words lie behind one another: one copy for dxv_sync)
 DXV_HD constexpr uint32_t queue_slot(uint32_t k, uint32_t heavy, uint32_t cap) { return k < heavy ? k : cap - 1u - (k - heavy); }   // item k of a queue
-// work queue of the lists kernel with 4 x 4 x 4 bricks (traverse.hip): built on the device in front of the launch
+// work queue of the lists kernel with 4 x 4 x 4 bricks: built on the device in front of the launch
 uint32_t plan_layout(VoxelizeParams& p);           // fills the brick-order fields for the whole partition, returns its bricks
 uint32_t plan_region_bits(uint32_t N, uint32_t nz); // the run length (log2 bricks) a partition of this size deals to its queues
 size_t plan_queue_words(uint32_t N, uint32_t nz, uint32_t* capOut);     // 32-bit words of queue memory for a partition; *capOut = words per XCD queue
@@ -139,7 +146,11 @@ hipError_t plan_build(const VoxelizeParams& p, hipStream_t s);          // k_pla
 // rebuild: grid cleared + queue built in front of the kernel; else only the queue heads are reset (same launch as before into the same buffers)
 // (planEvents: two events recorded around the queue build of a rebuilding launch, or NULL)
 // listedLens: the eight lengths of a kept queue and how many of each are heavy (16 words) as the host last read them (one workgroup per item, dealt out by the hardware), or NULL (persistent waves)
-hipError_t launch_voxelize_queue(const VoxelizeParams& p, bool rebuild, uint32_t* wavesOut, hipEvent_t* planEvents, const uint32_t* listedLens, hipStream_t s);
+// What the runtime answered about the two brick kernels on a context's device (persistent waves the device holds at once without / with the
+// texel image; the LDS pad that holds k_voxelize_listed at 8 .. 32 workgroups per CU, -1: none).  0 = not asked yet; kept by the context,
+// filled by the launchers at first use.
+struct ListsOccupancy { uint32_t queueWaves[2] = {0, 0}; int listedPad[33] = {}; };
+hipError_t launch_voxelize_queue(const VoxelizeParams& p, ListsOccupancy& occ, bool rebuild, uint32_t* wavesOut, hipEvent_t* planEvents, const uint32_t* listedLens, hipStream_t s);
 // A launch through a queue that was PREPARED for (lists, grid, partition) -- built ONCE, in Init or by dxv_prepare_launch, like the lists
 // it is a pure function of: the host knows the sixteen counts, so the hardware deals the bricks out (k_voxelize_listed, one workgroup
 // per queued brick), and the grid is cleared inside the launch.  p.queueSlots / p.queueCap: the prepared queue's; lens: its sixteen
@@ -148,22 +159,16 @@ hipError_t launch_voxelize_queue(const VoxelizeParams& p, bool rebuild, uint32_t
 //             1 / 2 / 3: ONE dispatch -- workgroups in front of (1), behind (2) or spread evenly between (3) the bricks' zero exactly the
 //             bricks that are not queued (every voxel is written once per launch, by the brick that owns it or by the clear; needs
 //             N % 16 == 0).
-hipError_t launch_voxelize_prepared(const VoxelizeParams& p, const uint32_t lens[16], const uint32_t* live, int clearMode, uint32_t* wavesOut, hipStream_t s);
+hipError_t launch_voxelize_prepared(const VoxelizeParams& p, ListsOccupancy& occ, const uint32_t lens[16], const uint32_t* live, int clearMode, uint32_t* wavesOut, hipStream_t s);
 size_t plan_live_words(uint32_t N, uint32_t nz);   // 32-bit words of a partition's brick mask
-// test hook: every voxel's first-step decision against the queue; bits: one per brick of the partition, out: 16 words
-hipError_t launch_plan_check(const VoxelizeParams& p, uint32_t* bits, unsigned long long* out, hipStream_t s);
-hipError_t launch_voxelize_redo(const VoxelizeParams& p, hipStream_t s);   // finishes the rays on p.redo with a full-depth stack
-int stack_round_up(int want);
-int stack_for_brick(int brickShape, int want);   // the column depth compiled for this brick shape that is >= want
+
+// parity_rows.hip
 hipError_t launch_parity_rows(const VoxelizeParams& p, int rowBlock, hipStream_t s);   // parity mode: one walk per row run (1) or per 2 x 2 rows (2)
-hipError_t launch_list_check(const VoxelizeParams& p, unsigned long long* out, hipStream_t s);   // test hook: superset claim of the lists (slices [p.z0, p.z0 + p.nz))
-hipError_t launch_division_check(uint32_t N, unsigned long long* out, hipStream_t s);             // test hook: the ray set-up's divisions against `/` for every voxel of an N^3 grid (out: 10 words, zeroed by the caller)
-hipError_t launch_far_check(const VoxelizeParams& p, unsigned long long* out, hipStream_t s);    // test hook: the brick test of the brick-box launches (p.mip, p.mipR; slices [p.z0, p.z0 + p.nz))
-hipError_t launch_class_check(const VoxelizeParams& p, unsigned long long* out, hipStream_t s);  // test hook: per-triangle class of the normal test against the predicate
+
+// grid_utils.hip
 hipError_t launch_count(const uint8_t* grid, size_t n, unsigned long long* out, hipStream_t s);
 hipError_t launch_checksum(const void* buf, size_t bytes, unsigned long long* out, hipStream_t s);   // wrapping sum of the buffer's 64-bit words
 hipError_t launch_pack_bits(const uint8_t* grid, size_t n, uint8_t* packed, hipStream_t s);
-int num_brick_shapes();
 
 // surface.hip -- the surface rule (dxv_surface.h) scattered over a partition: every voxel it accepts is set to 1, nothing else is
 // written (mode 2 clears the partition in front of it, mode 3 runs it behind the reference rule's launch)

@@ -189,7 +189,7 @@ DXV_HD void dm_ray_point(float ox, float oy, float oz, uint32_t& face, float& u,
 
 // The first step of a ray through the lists -- its texel, its cell inside the texel, and whether it has any candidate at
 // all: a ray whose texel is empty, or that starts beyond the far radius of its texel's last entry, is a miss after this
-// one load.  ONE definition: the kernel (trace_reference_dm), the plan's exact checker (k_plan_check, traverse.hip) and
+// one load.  ONE definition: the kernel (trace_reference_dm), the plan's exact checker (k_plan_check, dxv_debug.hip) and
 // the exhaustive list check make this decision through it, and the brick test below bounds it from above.
 struct DirRayStart { DirCell cell; uint32_t cx, cy; float rho, near; bool live; };
 DXV_HD DirRayStart dm_ray_start(float ox, float oy, float oz, const DirMapView& dm)
@@ -207,7 +207,7 @@ DXV_HD DirRayStart dm_ray_start(float ox, float oy, float oz, const DirMapView& 
 
 // ---------------------------------------------------------------------------------------------
 // Max-mip of the texels' far radii: which 4 x 4 x 4-voxel bricks can hold a live ray at all (the launch's work queue,
-// k_plan_bricks in traverse.hip).  Key of a texel = its r1max as half bits (positive halfs order like integers), 0 for an
+// k_plan_bricks in voxelize_lists.hip).  Key of a texel = its r1max as half bits (positive halfs order like integers), 0 for an
 // empty texel; level l holds, for 6 faces of (R >> l)^2 cells, the maximum over the 2^l x 2^l texels below a cell.
 // Built from the cells (dirmap.hip: dirmap_mip), never exported: a function of the cells alone.
 // ---------------------------------------------------------------------------------------------
@@ -331,15 +331,14 @@ DXV_HD uint32_t dm_heavy_level(uint32_t R, uint32_t N)
 }
 
 // the hull of the voxel centres of brick (bx, by, bz) of 4 x 4 x 4 voxels in a partition's local brick grid (x0 <= x1 ...; y falls
-// with iy, hlsl:49).  Local slice lz <-> global slice z0 + (lz >> zShift) * zPeriod + (lz & (zBlock - 1)) (zBlock == nz: a slab);
+// with iy, hlsl:49).  Local slice lz <-> global slice: global_slice (dxv_math.h);
 // the map is increasing, so the hull's z range comes from the brick's first and last slice.
 DXV_HD void dm_brick_hull(uint32_t N, uint32_t nz, uint32_t z0, uint32_t zBlock, uint32_t zShift, uint32_t zPeriod, uint32_t bx, uint32_t by,
                           uint32_t bz, float& x0, float& x1, float& y0, float& y1, float& zlo, float& zhi)
 {
     const uint32_t ix0 = bx * 4u, iy0 = by * 4u, lz0 = bz * 4u;
     const uint32_t ix1 = ix0 + 3u < N ? ix0 + 3u : N - 1u, iy1 = iy0 + 3u < N ? iy0 + 3u : N - 1u, lz1 = lz0 + 3u < nz ? lz0 + 3u : nz - 1u;
-    const uint32_t iz0 = zBlock == nz ? z0 + lz0 : z0 + (lz0 >> zShift) * zPeriod + (lz0 & (zBlock - 1u));
-    const uint32_t iz1 = zBlock == nz ? z0 + lz1 : z0 + (lz1 >> zShift) * zPeriod + (lz1 & (zBlock - 1u));
+    const uint32_t iz0 = global_slice(z0, nz, zBlock, zShift, zPeriod, lz0), iz1 = global_slice(z0, nz, zBlock, zShift, zPeriod, lz1);
     ray_origin(N, ix0, iy1, iz0, x0, y0, zlo);
     ray_origin(N, ix1, iy0, iz1, x1, y1, zhi);
 }
@@ -783,7 +782,7 @@ static __device__ unsigned long long g_dxvPhase[kPhaseSlots * 16u];
 // 2 = scan the entries but test no triangle, 16 = the scan's loads wave-uniform (with 2: 18), 32 / 64 = two / four more loads per scan
 // round with their results unused: what one of the scan's load instructions costs
 // (split at the ray's first step: the work-queue kernel makes that step for all 64 lanes of a brick at once and collects the brick
-// it asked for in advance behind it -- k_voxelize_queue, traverse.hip)
+// it asked for in advance behind it -- k_voxelize_queue, voxelize_lists.hip)
 // HITLDS: the closest hit's V, W, det and index live in column words cap .. cap + 3 (leaf_reference_deferred_lds); best.t and best.leaf are
 // all of `best` that is meaningful then (best.leaf == -1: miss), bestDet is untouched.
 // HITLDS 2: nothing but best.t and best.leaf is kept at all (leaf_reference_min, shade_reference_again).

@@ -407,7 +407,7 @@ int launch_now(dxv_ctx* c, uint32_t frame, bool relaunch)
                 auto& q = c->prepared[prep];
                 q.used = ++c->preparedClock;
                 f.clearSig = 0; f.queueLenSig = 0;
-                DXV_HIP(c, launch_voxelize_prepared(p, q.lens, q.dLive, c->optPrepClear, &f.plan_waves, fs));
+                DXV_HIP(c, launch_voxelize_prepared(p, c->occupancy, q.lens, q.dLive, c->optPrepClear, &f.plan_waves, fs));
                 f.plan_bricks = q.bricks; f.plan_ms = 0.0f;
                 f.lastPrepared = prep;
             } else {
@@ -423,7 +423,7 @@ int launch_now(dxv_ctx* c, uint32_t frame, bool relaunch)
                     f.queueOtherClear = false;                                 // (until this launch is in the stream)
                     f.clearSig = 0; f.queueLenSig = 0;
                 }
-                DXV_HIP(c, launch_voxelize_queue(p, rebuild, &f.plan_waves, rebuild && c->optEvents ? pe : nullptr, listed, fs));
+                DXV_HIP(c, launch_voxelize_queue(p, c->occupancy, rebuild, &f.plan_waves, rebuild && c->optEvents ? pe : nullptr, listed, fs));
                 if (rebuild) { f.queueHdr ^= 1u; f.queueOtherClear = true; }
                 f.clearSig = f.ptrExposed ? 0 : sig;
                 f.lastQueued = true; f.lastRebuilt = rebuild;

@@ -104,6 +104,13 @@ DXV_HD void ray_origin(uint32_t N, uint32_t ix, uint32_t iy, uint32_t iz, float&
     oz = div_by((float)iz + 0.5f, byN) * 2.0f - 1.0f;
 }
 
+// Local slice lz of a partition -> global slice: a contiguous slab (zBlock == nz), or block-cyclic with blocks of
+// zBlock = 2^zShift slices every zPeriod.  The one copy: kernels, the host's live_ranges and dm_brick_hull.
+DXV_HD uint32_t global_slice(uint32_t z0, uint32_t nz, uint32_t zBlock, uint32_t zShift, uint32_t zPeriod, uint32_t lz)
+{
+    return zBlock == nz ? z0 + lz : z0 + (lz >> zShift) * zPeriod + (lz & (zBlock - 1u));
+}
+
 // A radial ray whose origin lies beyond the scene's root box on the side it is moving to can not
 // enter any box inside the root box: on that axis sign(d) == sign(o), so the exit distance
 // fma(hi, 1/d, -(o/d)) is negative for every box (margin 1e-5 >> the 2^-24 relative rounding of

@@ -474,7 +474,7 @@ def test_parity_row_lists_give_the_oracle_grid(orc, hostcheck, bunny):
 
 
 def test_work_queue_brick_test_never_drops_a_live_ray(orc, hostcheck, bunny, dragon):
-    """The work queue of the lists kernel (traverse.hip: k_plan_bricks) keeps a 4^3-voxel brick iff dm_box_may_be_live says
+    """The work queue of the lists kernel (voxelize_lists.hip: k_plan_bricks) keeps a 4^3-voxel brick iff dm_box_may_be_live says
     a ray of it can be live -- decided from the brick's hull, three of its corners and a max-mip of the lists' far radii
     (dxv_dirmap.h).  Replayed on the host against the per-voxel first-step decision the kernel makes (origin_leaves_root,
     dm_ray_start: the same functions): no live voxel may sit in a dropped brick, on grids whose bricks straddle the centre

@@ -6,11 +6,18 @@ import os
 from dxrvoxelizer_amd import build
 
 
+# the .usage file of every translation unit a guarded kernel lives in: the walks (k_voxelize), the work queue's two brick kernels
+# (k_voxelize_queue, k_voxelize_listed), the parity rule's row kernel (k_parity_rows)
+SOURCES = ("traverse", "voxelize_lists", "parity_rows")
+
+
 def resources():
-    usage = os.path.join(build.OBJDIR, "traverse.usage")
-    if not os.path.exists(usage):
+    if not all(os.path.exists(os.path.join(build.OBJDIR, s + ".usage")) for s in SOURCES):
         build.build(force=True)
-    return build.kernel_resources("traverse")
+    res = {}
+    for s in SOURCES:
+        res.update(build.kernel_resources(s))
+    return res
 
 
 def test_default_kernels_do_not_spill_and_keep_full_occupancy(dxvlib):

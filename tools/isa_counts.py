@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
 """Static instruction counts of the library's kernels from the compiler's gfx950 assembly (no GPU needed).
-    python tools/isa_counts.py [source.hip] [kernel name substring ...] [--asm FILE]   (default: traverse.hip, the two brick kernels)
+    python tools/isa_counts.py [source.hip] [kernel name substring ...] [--asm FILE] [--hash]   (default: voxelize_lists.hip, the two brick kernels)
 Per kernel: vector ALU / scalar ALU / vector loads / vector stores + atomics / LDS instructions, and how many correctly rounded
-divisions (v_div_fixup_f32) and square roots (v_sqrt_f32) it contains."""
+divisions (v_div_fixup_f32) and square roots (v_sqrt_f32) it contains.  --hash: also a hash of the kernel's instruction stream (its
+body without labels, comments and directives; local labels numbered in order of appearance, so a kernel that moved to another file or
+position hashes the same) -- equal hashes of two builds: the same code."""
 import collections
+import hashlib
 import os
 import re
 import subprocess
@@ -22,13 +25,25 @@ def assembly(src):
     return out
 
 
-def counts(path, wanted):
+def bodies(path, wanted):
     txt = open(path).read()
-    res = {}
     for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)^\.Lfunc_end", txt, re.S | re.M):
-        name, body = m.group(1), m.group(2)
-        if wanted and not any(w in name for w in wanted):
-            continue
+        if not wanted or any(w in m.group(1) for w in wanted):
+            yield m.group(1), m.group(2)
+
+
+def stream_hash(body):
+    labels, out = {}, []
+    for line in body.split("\n"):
+        line = line.split(";")[0].rstrip()
+        if re.match(r"\s+[a-z]", line):                        # an instruction (labels start in column 0, directives with a dot)
+            out.append(re.sub(r"\.L\w+", lambda m: labels.setdefault(m.group(0), ".L%d" % len(labels)), " ".join(line.split())))
+    return hashlib.sha256("\n".join(out).encode()).hexdigest()[:16], len(out)
+
+
+def counts(path, wanted, hashes=False):
+    res = {}
+    for name, body in bodies(path, wanted):
         c = collections.Counter()
         for line in body.split("\n"):
             op = re.match(r"\s+([a-z][a-z_0-9]+)", line)
@@ -52,6 +67,8 @@ def counts(path, wanted):
             if op == "v_div_fixup_f64":
                 c["divisions_f64"] += 1
         res[name] = dict(c)
+        if hashes:
+            res[name]["stream_sha256"], res[name]["instructions"] = stream_hash(body)
     return res
 
 
@@ -60,8 +77,8 @@ if __name__ == "__main__":
     asm = sys.argv[sys.argv.index("--asm") + 1] if "--asm" in sys.argv else None
     if asm:
         args = [a for a in args if a != asm]
-    src = args[0] if args and args[0].endswith((".hip", ".cpp")) else "traverse.hip"
+    src = args[0] if args and args[0].endswith((".hip", ".cpp")) else "voxelize_lists.hip"
     wanted = [a for a in args if a != src] or ["k_voxelize_listedILb0", "k_voxelize_queueILb0"]
     import json
-    for name, c in counts(asm or assembly(src), wanted).items():
+    for name, c in counts(asm or assembly(src), wanted, "--hash" in sys.argv).items():
         print(json.dumps({"kernel": name, **c}))
