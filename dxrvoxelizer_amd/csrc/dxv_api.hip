@@ -45,42 +45,60 @@ int alloc_scene(dxv_ctx* c, uint32_t T, uint32_t V, bool wide)
 {
     SceneHeader h;
     layout_scene(h, T, V, wide);
-    // (a scene of up to the size of the last one, and not under half of it, moves into its allocation: a free and an allocation
-    // of a hundred megabytes less on the way to the first launch)
-    if (c->dScene && (h.totalBytes > c->sceneCap || c->sceneCap > 2 * h.totalBytes)) { (void)hipFree(c->dScene); c->dScene = nullptr; c->sceneCap = 0; }
-    if (!c->dScene) { DXV_HIP(c, hipMalloc(&c->dScene, h.totalBytes)); c->sceneCap = h.totalBytes; }
+    DXV_HIP(c, c->scene.fit(h.totalBytes));
     c->sceneBytes = h.totalBytes;
     c->hdr = h;
     return 0;
 }
 
-void free_scratch(dxv_ctx* c)
-{
-    (void)hipFree(c->dKeys); (void)hipFree(c->dKeysTmp); (void)hipFree(c->dHist); (void)hipFree(c->dParents);
-    (void)hipFree(c->dPyramid); c->dPyramid = nullptr; c->pyramidSlots = 0;
-    (void)hipFree(c->dFlags); (void)hipFree(c->dFlags2);
-    c->dKeys = c->dKeysTmp = nullptr; c->dHist = c->dParents = c->dFlags = c->dFlags2 = nullptr;
-    c->scratchT = 0; c->scratchCap = 0; c->histCapWords = 0;
-}
-
 int alloc_scratch(dxv_ctx* c, uint32_t T)
 {
-    if (c->scratchT == T) return 0;
+    BuildScratch& s = c->scratch;
+    if (s.T == T) return 0;
     // (scratch made for a mesh of up to twice the triangles serves this one too)
-    if (c->scratchCap >= T && c->scratchCap / 2 <= T && radix_sort_hist_words(T) <= c->histCapWords) {
-        if (c->dPyramid && c->pyramidSlots < pyramid_slots(T)) { (void)hipFree(c->dPyramid); c->dPyramid = nullptr; c->pyramidSlots = 0; }   // (alloc_pyramid makes the larger one)
-        c->scratchT = T;
+    if (s.keys.cap >= T && s.keys.cap / 2 <= T && radix_sort_hist_words(T) <= s.hist.cap) {
+        if (s.pyramid.cap < pyramid_slots(T)) s.pyramid.release();     // (alloc_pyramid makes the larger one)
+        s.T = T;
         return 0;
     }
-    free_scratch(c);
-    DXV_HIP(c, hipMalloc(&c->dKeys, sizeof(uint64_t) * (size_t)T));
-    DXV_HIP(c, hipMalloc(&c->dKeysTmp, sizeof(uint64_t) * (size_t)T));
-    DXV_HIP(c, hipMalloc(&c->dHist, sizeof(uint32_t) * (size_t)radix_sort_hist_words(T)));
-    DXV_HIP(c, hipMalloc(&c->dParents, sizeof(uint32_t) * (2 * (size_t)T)));
-    DXV_HIP(c, hipMalloc(&c->dFlags, sizeof(uint32_t) * (size_t)T));
-    DXV_HIP(c, hipMalloc(&c->dFlags2, sizeof(uint32_t) * (size_t)T));
-    c->scratchT = T; c->scratchCap = T; c->histCapWords = radix_sort_hist_words(T);
+    s = BuildScratch{};
+    const size_t n = T, hist = radix_sort_hist_words(T);
+    hipError_t e = s.keys.reserve(n, sizeof(uint64_t) * n);
+    if (e == hipSuccess) e = s.keysTmp.reserve(n, sizeof(uint64_t) * n);
+    if (e == hipSuccess) e = s.hist.reserve(hist, sizeof(uint32_t) * hist);
+    if (e == hipSuccess) e = s.parents.reserve(2 * n, sizeof(uint32_t) * 2 * n);
+    if (e == hipSuccess) e = s.flags.reserve(n, sizeof(uint32_t) * n);
+    if (e == hipSuccess) e = s.flags2.reserve(n, sizeof(uint32_t) * n);
+    if (e != hipSuccess) {
+        s = BuildScratch{};                                             // (all of it or none: what is kept is judged by the keys' capacity)
+        return fail(c, "build scratch: hipMalloc failed: %s", hipGetErrorString(e));
+    }
+    s.T = T;
     return 0;
+}
+
+// What a new mesh, a build, a refit or an import invalidates: the scene, everything derived from it (lists, row lists, prepared
+// queues, the launch history the lists' policy reads) -- and, depending on the cause, mesh and hierarchy.
+void scene_changed(dxv_ctx* c, SceneCause why)
+{
+    drop_prepared(c);
+    c->haveScene = false;
+    c->lists.state = 0; c->specRes = 0; c->listResFloor = 0; c->listFloorTried = false; c->launchesOfScene = 0;
+    c->rowLists.state = 0; c->parityLaunchesOfScene = 0;
+    // a refit keeps the hierarchy it works on (what it leaves stale it says itself) and marks the mesh as animated
+    c->refitted = why == SceneCause::refit;
+    if (why != SceneCause::refit) { c->haveHierarchy = false; c->nodesStale = 0; }
+    // a new mesh and an imported scene replace the resident mesh (dxv_set_mesh has it back when its upload succeeds)
+    if (why == SceneCause::mesh || why == SceneCause::import) c->haveMesh = false;
+    if (why == SceneCause::mesh) c->vbCopyQueued = false;           // (build and refit: finish_build, once the copy has been waited for)
+}
+
+void fill_scene_stats(dxv_ctx* c)
+{
+    c->stats.num_tris = c->hdr.numTris; c->stats.num_verts = c->hdr.numVerts; c->stats.num_nodes = c->hdr.numNodes;
+    c->stats.tree_height = c->hdr.treeHeight;
+    c->stats.tri_extent = c->hdr.triExtent;
+    memcpy(c->stats.bound, c->bound, sizeof(c->bound));
 }
 
 // dxv_set_mesh's look at the caller's arrays: largest index, position bounds, whether every position is finite.  Chunks of the
@@ -173,7 +191,7 @@ int dxv_create(dxv_ctx** out, int device)
         return fail(nullptr, "dxv_create: hipHostMalloc failed");
     }
     memset(c->pin, 0, sizeof(dxv_ctx::Pinned));
-    if (hipMalloc(&c->dCount, 256) != hipSuccess || hipMalloc(&c->dRootInfo, 256) != hipSuccess || frame_prepare(c, 0)) {
+    if (c->count.reserve(32, 256) != hipSuccess || c->rootInfo.reserve(64, 256) != hipSuccess || frame_prepare(c, 0)) {
         dxv_destroy(c);
         return fail(nullptr, "dxv_create: hipMalloc failed");
     }
@@ -214,8 +232,8 @@ int dxv_warmup(int device, float* ms)
             (void)dxv_grid_download(w, host.data(), host.size());
         }
         std::vector<uint8_t> mb(1u << 20);                       // (a copy of a size the staging path handles in pieces)
-        void* d = nullptr;
-        if (hipMalloc(&d, mb.size()) == hipSuccess) { (void)hipMemcpy(d, mb.data(), mb.size(), hipMemcpyHostToDevice); (void)hipFree(d); }
+        DevBuf<uint8_t> d;
+        if (d.reserve(mb.size(), mb.size()) == hipSuccess) (void)hipMemcpy(d.p, mb.data(), mb.size(), hipMemcpyHostToDevice);
         dxv_destroy(w);
     }
     (void)hipGetLastError();
@@ -231,30 +249,16 @@ void dxv_destroy(dxv_ctx* c)
     for (uint32_t i = 0; i < DXV_FRAME_COUNT; ++i) {
         Frame& f = c->frames[i];
         if (frame_stream(c, i)) (void)hipStreamSynchronize(frame_stream(c, i));
-        (void)hipFree(f.dGrid); (void)hipFree(f.dTexels); (void)hipFree(f.dStatus); (void)hipFree(f.dRedo); (void)hipFree(f.dQueue);
-        if (f.ev0) (void)hipEventDestroy(f.ev0);
-        if (f.ev1) (void)hipEventDestroy(f.ev1);
-        if (f.evP0) (void)hipEventDestroy(f.evP0);
-        if (f.evP1) (void)hipEventDestroy(f.evP1);
-        if (f.evEnd) (void)hipEventDestroy(f.evEnd);
-        if (f.evR0) (void)hipEventDestroy(f.evR0);
-        if (f.evR1) (void)hipEventDestroy(f.evR1);
-        (void)hipFree(f.dEmpty); (void)hipFree(f.dSurf);
+        for (hipEvent_t ev : {f.ev0, f.ev1, f.evP0, f.evP1, f.evEnd, f.evR0, f.evR1})
+            if (ev) (void)hipEventDestroy(ev);
         if (f.ownStream) (void)hipStreamDestroy(f.ownStream);
     }
-    free_scratch(c);
-    drop_prepared(c, true);
-    (void)hipFree(c->dFar32); (void)hipFree(c->dFarCells); (void)hipFree(c->dFarMip);
-    (void)hipFree(c->dMip);
-    (void)hipFree(c->dVb); (void)hipFree(c->dIb); (void)hipFree(c->dScene);
-    (void)hipFree(c->dImage); (void)hipFree(c->dListCells); (void)hipFree(c->dListEntries); (void)hipFree(c->dPlCells); (void)hipFree(c->dPlEntries); (void)hipFree(c->dPlScratch); (void)hipFree(c->dListScratchA); (void)hipFree(c->dListScratchB);
-    (void)hipFree(c->dCount); (void)hipFree(c->dPacked); (void)hipFree(c->dRootInfo);
     for (auto& ev : c->ev) if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : c->evList) if (ev) (void)hipEventDestroy(ev);
     if (c->pin) (void)hipHostFree(c->pin);
     if (c->copyStream) (void)hipStreamDestroy(c->copyStream);
     if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
-    delete c;
+    delete c;                                                           // (every device buffer is a member that frees itself: DevBuf)
 }
 
 int dxv_api_version(void) { return DXV_API_VERSION; }
@@ -265,17 +269,13 @@ int dxv_trim(dxv_ctx* c)
     DXV_HIP(c, hipSetDevice(c->device));
     if (sync_frames(c)) return 1;
     DXV_HIP(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(c->dListScratchA); (void)hipFree(c->dListScratchB);
-    c->dListScratchA = c->dListScratchB = nullptr; c->listScratchACap = c->listScratchBCap = 0;
+    c->listScratchA.release(); c->listScratchB.release();
     c->specRes = 0;
-    if (!c->haveHierarchy) free_scratch(c);                             // (a built scene keeps keys and links: dxv_refit reads them)
+    if (!c->haveHierarchy) c->scratch = BuildScratch{};                             // (a built scene keeps keys and links: dxv_refit reads them)
     // prepared queues of lists that are gone (their slots keep their memory for the next dxv_prepare_launch of the partition: 8 MB at
     // 512^3, half a gigabyte at 2048^3); the ones in use stay
     for (auto& q : c->prepared)
-        if (q.epoch != c->listEpoch || c->listState != 1) {
-            (void)hipFree(q.dMem); (void)hipFree(q.dLive);
-            q.dMem = q.dLive = nullptr; q.words = q.liveWords = 0; q.epoch = 0; q.bricks = 0;
-        }
+        if (q.epoch != c->listEpoch || c->lists.state != 1) q = dxv_ctx::Prepared{};
     return 0;
 }
 
@@ -332,25 +332,15 @@ int dxv_set_mesh(dxv_ctx* c, const float* vb, uint32_t V, const uint32_t* ib, ui
     DXV_HIP(c, hipSetDevice(c->device));
     if (sync_frames(c)) return 1;
     DXV_HIP(c, hipStreamSynchronize(c->stream));
-    c->vbCopyQueued = false;
     memcpy(c->bound, bound, sizeof(bound));
-    drop_prepared(c);
-    c->haveMesh = false; c->haveScene = false; c->haveHierarchy = false; c->listState = 0; c->specRes = 0; c->listResFloor = 0; c->listFloorTried = false; c->refitted = false; c->launchesOfScene = 0; c->plState = 0; c->parityLaunchesOfScene = 0; c->nodesStale = 0;
+    scene_changed(c, SceneCause::mesh);
     // (a mesh of the size of the last one moves into its buffers: two frees and two allocations less on the way to the first launch)
     const size_t vbBytes = sizeof(float) * 6 * (size_t)V, ibBytes = sizeof(uint32_t) * 3 * (size_t)T;
-    if (!c->dVb || c->vbCap < vbBytes || c->vbCap > 2 * vbBytes) {
-        (void)hipFree(c->dVb); c->dVb = nullptr; c->vbCap = 0;
-        DXV_HIP(c, hipMalloc(&c->dVb, vbBytes));
-        c->vbCap = vbBytes;
-    }
-    if (!c->dIb || c->ibCap < ibBytes || c->ibCap > 2 * ibBytes) {
-        (void)hipFree(c->dIb); c->dIb = nullptr; c->ibCap = 0;
-        DXV_HIP(c, hipMalloc(&c->dIb, ibBytes));
-        c->ibCap = ibBytes;
-    }
+    DXV_HIP(c, c->vb.fit(vbBytes));
+    DXV_HIP(c, c->ib.fit(ibBytes));
     DXV_HIP(c, hipEventRecord(c->ev[8], c->stream));
-    DXV_HIP(c, hipMemcpyAsync(c->dVb, vb, sizeof(float) * 6 * (size_t)V, hipMemcpyHostToDevice, c->stream));
-    DXV_HIP(c, hipMemcpyAsync(c->dIb, ib, sizeof(uint32_t) * 3 * (size_t)T, hipMemcpyHostToDevice, c->stream));
+    DXV_HIP(c, hipMemcpyAsync(c->vb.p, vb, vbBytes, hipMemcpyHostToDevice, c->stream));
+    DXV_HIP(c, hipMemcpyAsync(c->ib.p, ib, ibBytes, hipMemcpyHostToDevice, c->stream));
     DXV_HIP(c, hipEventRecord(c->ev[9], c->stream));
     DXV_HIP(c, hipStreamSynchronize(c->stream));
     c->T = T; c->V = V;
@@ -366,10 +356,11 @@ int dxv_set_mesh(dxv_ctx* c, const float* vb, uint32_t V, const uint32_t* ib, ui
 namespace dxvhost {
 void fill_build_buffers(dxv_ctx* c, BuildBuffers& b)
 {
-    b.vb = c->dVb; b.ib = c->dIb; b.T = c->T; b.V = c->V;
+    const BuildScratch& s = c->scratch;
+    b.vb = c->vb.p; b.ib = c->ib.p; b.T = c->T; b.V = c->V;
     memcpy(b.bound, c->bound, sizeof(c->bound));
-    b.keys = c->dKeys; b.keysTmp = c->dKeysTmp; b.hist = c->dHist; b.parents = c->dParents;
-    b.flags = c->dFlags; b.flags2 = c->dFlags2; b.rootInfo = c->dRootInfo; b.pyramid = c->dPyramid;
+    b.keys = s.keys.p; b.keysTmp = s.keysTmp.p; b.hist = s.hist.p; b.parents = s.parents.p;
+    b.flags = s.flags.p; b.flags2 = s.flags2.p; b.rootInfo = c->rootInfo.p; b.pyramid = s.pyramid.p;
     b.nodes = scene_nodes(c); b.nodes32 = scene_nodes32(c); b.nodes64 = c->hdr.hasWide ? scene_nodes64(c) : nullptr; b.triPos = scene_tripos(c); b.triNrm = scene_trinrm(c);
 }
 
@@ -390,10 +381,8 @@ int ensure_nodes(dxv_ctx* c, hipStream_t stream)
 // min/max pyramid of the box merge (refit = 1): 24 B box + 4 B deepest leaf per slot
 int alloc_pyramid(dxv_ctx* c)
 {
-    if (!c->dPyramid && c->optRefit == 1 && c->T > 1) {    // refit=2 keeps the level sweeps, refit=0 the atomic pass
-        DXV_HIP(c, hipMalloc(&c->dPyramid, 28 * (size_t)pyramid_slots(c->T)));
-        c->pyramidSlots = pyramid_slots(c->T);
-    }
+    if (!c->scratch.pyramid.p && c->opt.refit == 1 && c->T > 1)     // refit=2 keeps the level sweeps, refit=0 the atomic pass
+        DXV_HIP(c, c->scratch.pyramid.reserve(pyramid_slots(c->T), 28 * (size_t)pyramid_slots(c->T)));
     return 0;
 }
 
@@ -402,7 +391,7 @@ int alloc_pyramid(dxv_ctx* c)
 int finish_build(dxv_ctx* c, const char* who, bool headerToDevice = true)
 {
     uint32_t* rootInfo = c->pin->rootInfo;
-    DXV_HIP(c, hipMemcpyAsync(rootInfo, c->dRootInfo, sizeof(c->pin->rootInfo), hipMemcpyDeviceToHost, c->stream));
+    DXV_HIP(c, hipMemcpyAsync(rootInfo, c->rootInfo.p, sizeof(c->pin->rootInfo), hipMemcpyDeviceToHost, c->stream));
     DXV_HIP(c, hipStreamSynchronize(c->stream));
     c->vbCopyQueued = false;
     if (rootInfo[7] != 1) return fail(c, "%s: did not complete", who);
@@ -421,15 +410,13 @@ int finish_build(dxv_ctx* c, const char* who, bool headerToDevice = true)
                         (double)c->hdr.rootLo[a], (double)c->hdr.rootHi[a]);
     if (c->hdr.treeHeight == 0 || c->hdr.treeHeight > 64) return fail(c, "%s: implausible tree height %u", who, c->hdr.treeHeight);
     if (headerToDevice) {
-        DXV_HIP(c, hipMemcpyAsync(c->dScene, &c->hdr, sizeof(SceneHeader), hipMemcpyHostToDevice, c->stream));
+        DXV_HIP(c, hipMemcpyAsync(c->scene.p, &c->hdr, sizeof(SceneHeader), hipMemcpyHostToDevice, c->stream));
         DXV_HIP(c, hipStreamSynchronize(c->stream));
     }
     c->haveScene = true;
     ++c->sceneEpoch;
-    c->stackNow = stack_round_up((int)(c->hdr.treeHeight + 3 < (uint32_t)c->optStack0 ? c->hdr.treeHeight + 3 : (uint32_t)c->optStack0));
-    c->stats.num_nodes = c->hdr.numNodes;
-    c->stats.tree_height = c->hdr.treeHeight;
-    c->stats.tri_extent = c->hdr.triExtent;
+    c->stackNow = initial_stack(c);
+    fill_scene_stats(c);
     return 0;
 }
 } // namespace dxvhost
@@ -439,7 +426,7 @@ extern "C" {
 int dxv_update_vertices(dxv_ctx* c, const float* vb, uint32_t V)
 {
     if (!c) return 1;
-    if (!c->haveMesh || !c->dVb) return fail(c, "dxv_update_vertices: no mesh resident on this context");
+    if (!c->haveMesh || !c->vb.p) return fail(c, "dxv_update_vertices: no mesh resident on this context");
     if (!vb || V != c->V) return fail(c, "dxv_update_vertices: vertex count must stay %u, got %u", c->V, V);
     DXV_HIP(c, hipSetDevice(c->device));
     // No wait for the frames: their launches read the scene's triangle records and lists, never the vertex buffer -- its only
@@ -447,7 +434,7 @@ int dxv_update_vertices(dxv_ctx* c, const float* vb, uint32_t V)
     // own, beside whatever the frames still have in flight (12 MB over PCIe at 1 M triangles: 0.25 ms hidden behind a launch).
     if (!c->copyStream) DXV_HIP(c, hipStreamCreateWithFlags(&c->copyStream, hipStreamNonBlocking));
     if (c->vbCopyQueued) { DXV_HIP(c, hipStreamSynchronize(c->stream)); c->vbCopyQueued = false; }    // (an earlier device update lands first)
-    DXV_HIP(c, hipMemcpyAsync(c->dVb, vb, sizeof(float) * 6 * (size_t)V, hipMemcpyHostToDevice, c->copyStream));
+    DXV_HIP(c, hipMemcpyAsync(c->vb.p, vb, sizeof(float) * 6 * (size_t)V, hipMemcpyHostToDevice, c->copyStream));
     DXV_HIP(c, hipStreamSynchronize(c->copyStream));
     return 0;
 }
@@ -455,12 +442,12 @@ int dxv_update_vertices(dxv_ctx* c, const float* vb, uint32_t V)
 int dxv_update_vertices_device(dxv_ctx* c, const void* dvb, uint32_t V)
 {
     if (!c) return 1;
-    if (!c->haveMesh || !c->dVb) return fail(c, "dxv_update_vertices_device: no mesh resident on this context");
+    if (!c->haveMesh || !c->vb.p) return fail(c, "dxv_update_vertices_device: no mesh resident on this context");
     if (!dvb || V != c->V) return fail(c, "dxv_update_vertices_device: vertex count must stay %u, got %u", c->V, V);
     DXV_HIP(c, hipSetDevice(c->device));
     // No wait for the frames (as in dxv_update_vertices): their launches never read the vertex buffer, and its readers --
     // dxv_build, dxv_refit -- run on this same stream.
-    DXV_HIP(c, hipMemcpyAsync(c->dVb, dvb, sizeof(float) * 6 * (size_t)V, hipMemcpyDeviceToDevice, c->stream));
+    DXV_HIP(c, hipMemcpyAsync(c->vb.p, dvb, sizeof(float) * 6 * (size_t)V, hipMemcpyDeviceToDevice, c->stream));
     c->vbCopyQueued = true;
     return 0;                                                          // (dxv_refit, on the same stream, comes next)
 }
@@ -468,7 +455,7 @@ int dxv_update_vertices_device(dxv_ctx* c, const void* dvb, uint32_t V)
 int dxv_refit(dxv_ctx* c)
 {
     if (!c) return 1;
-    if (!c->haveMesh || !c->haveHierarchy || c->scratchT != c->T || !c->T)
+    if (!c->haveMesh || !c->haveHierarchy || c->scratch.T != c->T || !c->T)
         return fail(c, "dxv_refit: needs a scene built on this context by dxv_build (imported scenes carry no build state)");
     DXV_HIP(c, hipSetDevice(c->device));
     // The frames' launches read what the refit is about to write.  A launch that may still have something to say (a tree walk whose
@@ -483,30 +470,27 @@ int dxv_refit(dxv_ctx* c)
         if (f.lastCanFail || (f.usedLists && f.listEpochUsed == c->withdrawnEpoch)) { if (sync_frame(c, i)) return 1; }
         else if (frame_stream(c, i) != c->stream) DXV_HIP(c, hipStreamWaitEvent(c->stream, f.evEnd, 0));
     }
-    const uint32_t hadListsOn = c->listState == 1 ? c->listRes : 0u;
-    drop_prepared(c);                                                  // (queues prepared for the old surface; no launch that reads one is un-ordered: see above)
-    c->haveScene = false; c->listState = 0; c->listResFloor = 0; c->listFloorTried = false; c->launchesOfScene = 0; c->plState = 0; c->parityLaunchesOfScene = 0;
-    c->refitted = true;
-    c->specRes = 0;
+    const uint32_t hadListsOn = c->lists.state == 1 ? c->lists.res : 0u;
+    scene_changed(c, SceneCause::refit);                               // (the queues prepared for the old surface go too; no launch that reads one is un-ordered: see above)
     if (alloc_pyramid(c)) return 1;
     BuildBuffers b{};
     fill_build_buffers(c, b);
-    if (c->optRefit != 1) b.pyramid = nullptr;
+    if (c->opt.refit != 1) b.pyramid = nullptr;
     // the wide walks' four-box copy of the hierarchy waits until a walk needs it: the next launch of a refitted mesh usually
     // goes through the lists, which are built from the triangle records alone (the half-float copy comes out of the box
     // merge's registers and is always current)
-    b.deferCopies = c->optLists != 0 && c->hdr.hasWide;
+    b.deferCopies = c->opt.lists != 0 && c->hdr.hasWide;
     // ... and so do the node boxes themselves (half of the refit's time at 1 M triangles): the refit stops at the min/max
     // pyramid, whose top is the root box the launch needs, and ensure_nodes finishes it in front of the first tree walk
-    b.deferBoxes = c->optLists != 0 && c->optDeferBoxes && b.pyramid && c->T > 1;
-    DXV_HIP(c, lbvh_refit(b, c->optRefit, c->hdr.treeHeight, c->stream, c->ev + 3));
+    b.deferBoxes = c->opt.lists != 0 && c->opt.deferboxes && b.pyramid && c->T > 1;
+    DXV_HIP(c, lbvh_refit(b, c->opt.refit, c->hdr.treeHeight, c->stream, c->ev + 3));
     c->nodesStale = b.deferBoxes ? 2 : b.deferCopies ? 1 : 0;
     // A scene that had lists (or asks for them from its first launch) will have them rebuilt by its next launch: their counting
     // pass needs the new triangle records only, so it runs here, behind the refit, and its total comes back with the root box.
     uint32_t spec = 0;
-    if (c->optLists && (hadListsOn || c->optLists == 2) && c->dListScratchA && c->listScratchACap >= list_scratch_a(nullptr, c->hdr.numTris).bytes) {
-        spec = c->optListRes ? (uint32_t)c->optListRes : list_resolution(c);     // (the base map: a mesh that is being refitted gets its lists built for one launch)
-        const ListScratchA sa = list_scratch_a(c->dListScratchA, c->hdr.numTris);
+    if (c->opt.lists && (hadListsOn || c->opt.lists == 2) && c->listScratchA.cap >= list_scratch_a(nullptr, c->hdr.numTris).bytes) {
+        spec = c->opt.listres ? (uint32_t)c->opt.listres : list_resolution(c);     // (the base map: a mesh that is being refitted gets its lists built for one launch)
+        const ListScratchA sa = list_scratch_a(c->listScratchA.p, c->hdr.numTris);
         DXV_HIP(c, hipEventRecord(c->evList[0], c->stream));
         DXV_HIP(c, dirmap_count(scene_tripos(c), c->hdr.numTris, spec, sa.rec, sa.counts, sa.pairs, sa.offsets, sa.total, c->stream));
         DXV_HIP(c, hipEventRecord(c->evList[1], c->stream));
@@ -524,18 +508,17 @@ int dxv_build(dxv_ctx* c)
     if (!c->haveMesh) return fail(c, "dxv_build: no mesh (call dxv_set_mesh first)");
     DXV_HIP(c, hipSetDevice(c->device));
     if (sync_frames(c)) return 1;
-    drop_prepared(c);
-    c->haveScene = false; c->haveHierarchy = false; c->listState = 0; c->specRes = 0; c->listResFloor = 0; c->listFloorTried = false; c->refitted = false; c->launchesOfScene = 0; c->plState = 0; c->parityLaunchesOfScene = 0; c->nodesStale = 0;
-    if (alloc_scene(c, c->T, c->V, c->optWide != 0)) return 1;
+    scene_changed(c, SceneCause::build);
+    if (alloc_scene(c, c->T, c->V, c->opt.wide != 0)) return 1;
     if (alloc_scratch(c, c->T)) return 1;
     if (alloc_pyramid(c)) return 1;
     memcpy(c->hdr.bound, c->bound, sizeof(c->bound));
 
     BuildBuffers b{};
     fill_build_buffers(c, b);
-    if (c->optRefit != 1) b.pyramid = nullptr;
-    b.deferCopies = c->optLists != 0 && c->hdr.hasWide;                // (as in dxv_refit: 0.6 ms of a 10 M-triangle build that most scenes never need)
-    DXV_HIP(c, lbvh_build(b, c->optRefit, c->stream, c->ev));
+    if (c->opt.refit != 1) b.pyramid = nullptr;
+    b.deferCopies = c->opt.lists != 0 && c->hdr.hasWide;                // (as in dxv_refit: 0.6 ms of a 10 M-triangle build that most scenes never need)
+    DXV_HIP(c, lbvh_build(b, c->opt.refit, c->stream, c->ev));
     c->nodesStale = b.deferCopies ? 1 : 0;
     if (finish_build(c, "dxv_build")) return 1;
     c->haveHierarchy = true;
@@ -563,16 +546,11 @@ int dxv_render(dxv_ctx* c, const float eye[3], const float viewProj[16], const f
         return fail(c, "dxv_render: singular view/projection chain");
     DXV_HIP(c, hipSetDevice(c->device));
     const size_t pixels = (size_t)width * height;
-    if (pixels > c->imageCap) {
-        DXV_HIP(c, hipStreamSynchronize(fs));
-        (void)hipFree(c->dImage); c->dImage = nullptr; c->imageCap = 0;
-        DXV_HIP(c, hipMalloc(&c->dImage, pixels * 4));
-        c->imageCap = pixels;
-    }
+    DXV_HIP(c, c->image.reserve(pixels, pixels * 4, fs));
     if (dxv_sync(c)) return 1;                                       // the grid must be complete and valid
     // (the staging image is the context's: every frame's dxv_render ends in this host wait before another one can start)
-    if (render_frame(c, cb, width, height, reinterpret_cast<uint8_t*>(c->dImage), (size_t)width * 4, true)) return 1;
-    DXV_HIP(c, hipMemcpyAsync(rgbaHost, c->dImage, pixels * 4, hipMemcpyDeviceToHost, fs));
+    if (render_frame(c, cb, width, height, reinterpret_cast<uint8_t*>(c->image.p), (size_t)width * 4, true)) return 1;
+    DXV_HIP(c, hipMemcpyAsync(rgbaHost, c->image.p, pixels * 4, hipMemcpyDeviceToHost, fs));
     DXV_HIP(c, hipStreamSynchronize(fs));
     f.render_ms = elapsed(f.evR0, f.evR1);
     f.renderTimed = false;
@@ -586,23 +564,33 @@ void* dxv_grid_device_ptr(dxv_ctx* c)
     // here on every launch into this frame clears the grid itself instead of trusting what it wrote there last
     cur_frame(c).clearSig = 0;
     cur_frame(c).ptrExposed = true;
-    return cur_frame(c).dGrid;
+    return cur_frame(c).grid.p;
 }
-const void* dxv_grid_device_ptr_ro(const dxv_ctx* c) { return c ? c->frames[c->cur].dGrid : nullptr; }
+const void* dxv_grid_device_ptr_ro(const dxv_ctx* c) { return c ? c->frames[c->cur].grid.p : nullptr; }
 size_t dxv_grid_bytes(const dxv_ctx* c) { return c ? c->frames[c->cur].gridBytes : 0; }
+
+// the download and count entries: an unchecked launch of the selected frame is finished (with its redo, if any) first ...
+static int finish_launch(dxv_ctx* c)
+{
+    if (cur_frame(c).pending && dxv_sync(c)) return 1;
+    DXV_HIP(c, hipSetDevice(c->device));
+    return 0;
+}
+// ... and the result comes back over the frame's stream, which is waited for
+static int read_back(dxv_ctx* c, void* host, const void* src, size_t bytes)
+{
+    DXV_HIP(c, hipMemcpyAsync(host, src, bytes, hipMemcpyDeviceToHost, cur_stream(c)));
+    DXV_HIP(c, hipStreamSynchronize(cur_stream(c)));
+    return 0;
+}
 
 int dxv_grid_download(dxv_ctx* c, uint8_t* host, size_t bytes)
 {
     if (!c) return 1;
     Frame& f = cur_frame(c);
-    const hipStream_t fs = cur_stream(c);
-    (void)fs;
     if (!host || bytes != f.gridBytes || !f.gridBytes) return fail(c, "dxv_grid_download: expected %zu bytes, got %zu", f.gridBytes, bytes);
-    if (f.pending && dxv_sync(c)) return 1;          // an unchecked launch: finish it (and its redo, if any) first
-    DXV_HIP(c, hipSetDevice(c->device));
-    DXV_HIP(c, hipMemcpyAsync(host, f.dGrid, bytes, hipMemcpyDeviceToHost, fs));
-    DXV_HIP(c, hipStreamSynchronize(fs));
-    return 0;
+    if (finish_launch(c)) return 1;
+    return read_back(c, host, f.grid.p, bytes);
 }
 
 size_t dxv_grid_packed_bytes(const dxv_ctx* c) { return c ? (c->frames[c->cur].gridBytes + 7) / 8 : 0; }
@@ -611,37 +599,23 @@ int dxv_grid_download_packed(dxv_ctx* c, uint8_t* host, size_t bytes)
 {
     if (!c) return 1;
     Frame& f = cur_frame(c);
-    const hipStream_t fs = cur_stream(c);
-    (void)fs;
     const size_t want = (f.gridBytes + 7) / 8;
     if (!host || !want || bytes != want) return fail(c, "dxv_grid_download_packed: expected %zu bytes, got %zu", want, bytes);
-    if (f.pending && dxv_sync(c)) return 1;          // an unchecked launch: finish it (and its redo, if any) first
-    DXV_HIP(c, hipSetDevice(c->device));
-    if (want > c->packedCap) {
-        DXV_HIP(c, hipStreamSynchronize(fs));
-        (void)hipFree(c->dPacked); c->dPacked = nullptr; c->packedCap = 0;
-        DXV_HIP(c, hipMalloc(&c->dPacked, align256(want)));
-        c->packedCap = want;
-    }
-    DXV_HIP(c, launch_pack_bits(f.dGrid, f.gridBytes, c->dPacked, fs));
-    DXV_HIP(c, hipMemcpyAsync(host, c->dPacked, want, hipMemcpyDeviceToHost, fs));
-    DXV_HIP(c, hipStreamSynchronize(fs));
-    return 0;
+    if (finish_launch(c)) return 1;
+    DXV_HIP(c, c->packed.reserve(want, align256(want), cur_stream(c)));
+    DXV_HIP(c, launch_pack_bits(f.grid.p, f.gridBytes, c->packed.p, cur_stream(c)));
+    return read_back(c, host, c->packed.p, want);
 }
 
 int dxv_grid_count(dxv_ctx* c, uint64_t* solid)
 {
     if (!c) return 1;
     Frame& f = cur_frame(c);
-    const hipStream_t fs = cur_stream(c);
-    (void)fs;
     if (!solid || !f.gridBytes) return fail(c, "dxv_grid_count: no grid");
-    if (f.pending && dxv_sync(c)) return 1;          // an unchecked launch: finish it (and its redo, if any) first
-    DXV_HIP(c, hipSetDevice(c->device));
-    DXV_HIP(c, launch_count(f.dGrid, f.gridBytes, c->dCount, fs));
+    if (finish_launch(c)) return 1;
+    DXV_HIP(c, launch_count(f.grid.p, f.gridBytes, c->count.p, cur_stream(c)));
     unsigned long long v = 0;
-    DXV_HIP(c, hipMemcpyAsync(&v, c->dCount, sizeof(v), hipMemcpyDeviceToHost, fs));
-    DXV_HIP(c, hipStreamSynchronize(fs));
+    if (read_back(c, &v, c->count.p, sizeof(v))) return 1;
     *solid = v;
     return 0;
 }
@@ -657,15 +631,10 @@ int dxv_texels_download(dxv_ctx* c, uint32_t* host, size_t bytes)
 {
     if (!c) return 1;
     Frame& f = cur_frame(c);
-    const hipStream_t fs = cur_stream(c);
-    (void)fs;
-    if (!c->texels || !f.dTexels) return fail(c, "dxv_texels_download: texel output not enabled");
+    if (!c->texels || !f.texels.p) return fail(c, "dxv_texels_download: texel output not enabled");
     if (!host || bytes != f.gridBytes * 4) return fail(c, "dxv_texels_download: expected %zu bytes, got %zu", f.gridBytes * 4, bytes);
-    if (f.pending && dxv_sync(c)) return 1;          // an unchecked launch: finish it (and its redo, if any) first
-    DXV_HIP(c, hipSetDevice(c->device));
-    DXV_HIP(c, hipMemcpyAsync(host, f.dTexels, bytes, hipMemcpyDeviceToHost, fs));
-    DXV_HIP(c, hipStreamSynchronize(fs));
-    return 0;
+    if (finish_launch(c)) return 1;
+    return read_back(c, host, f.texels.p, bytes);
 }
 
 int dxv_get_stats(const dxv_ctx* c, dxv_stats* out)
@@ -675,135 +644,54 @@ int dxv_get_stats(const dxv_ctx* c, dxv_stats* out)
     const Frame& f = c->frames[c->cur];
     out->voxelize_ms = f.voxelize_ms; out->grid_dim = f.grid_dim; out->z0 = f.z0; out->nz = f.nz;
     out->stack_entries = f.stack_entries; out->redo_rays = f.redo_rays; out->row_block = f.row_block;
-    out->list_entries = f.list_entries; out->list_res = f.list_res; out->list_ms = f.lastMode == DXV_MODE_PARITY ? c->plMs : c->listMs;
+    out->list_entries = f.list_entries; out->list_res = f.list_res; out->list_ms = f.lastMode == DXV_MODE_PARITY ? c->rowLists.ms : c->lists.ms;
     out->plan_bricks = f.plan_bricks; out->plan_waves = f.plan_waves; out->plan_ms = f.plan_ms;
     out->plan_prepared = f.lastPrepared >= 0 ? 1u : 0u;
     out->render_ms = f.render_ms;
     return 0;
 }
 
+// dxv_policy.h holds the table: every key, the values it accepts, where its value lives.  Here: look up, check, store -- and the
+// few keys whose setting does more than that.
 int dxv_set_option(dxv_ctx* c, const char* key, int64_t value)
 {
     if (!c || !key) return 1;
-    if (!strcmp(key, "brick")) {
-        if (value < 0 || value >= num_brick_shapes()) return fail(c, "option brick: %lld out of range", (long long)value);
-        c->optBrick = (int)value;
-    } else if (!strcmp(key, "stack")) {
-        if (value != 0 && (value < 0 || value > 64 || stack_round_up((int)value) != (int)value))
-            return fail(c, "option stack: %lld not in {0,8,12,16,24,32,48,64}", (long long)value);
-        c->optStack = (int)value;
-    } else if (!strcmp(key, "refit")) {
-        if (value < 0 || value > 2) return fail(c, "option refit: %lld not in {0,1,2}", (long long)value);
-        c->optRefit = (int)value;
-    } else if (!strcmp(key, "deferboxes")) {
-        if (value < 0 || value > 1) return fail(c, "option deferboxes: %lld not in {0,1}", (long long)value);
-        c->optDeferBoxes = (int)value;
-    } else if (!strcmp(key, "subbox")) {
-        if (value != 0 && value != 1) return fail(c, "option subbox: %lld not in {0,1}", (long long)value);
-        c->optSubbox = (int)value;
-    } else if (!strcmp(key, "wide")) {
-        if (value < 0 || value > 2) return fail(c, "option wide: %lld not in {0,1,2}", (long long)value);
-        c->optWide = (int)value;
+    const OptionRow* row = find_option(key);
+    if (!row) return fail(c, "unknown option '%s'", key);
+    if (!option_accepts(row->rule, value) || (row->effect == OptionEffect::brick && value >= num_brick_shapes()))
+        return fail(c, "option %s: %lld %s", key, (long long)value, row->refusal);
+    int& slot = c->opt.*row->where;
+    switch (row->effect) {                                              // what has to happen in front of the store
+    case OptionEffect::ablate:
+#if !defined(DXV_ABLATE)
+        // the timing-only variants of the lists kernel write wrong grids by design: they exist only in the library that
+        // tools/ablate.py builds for itself (python -m dxrvoxelizer_amd.build --ablate -> libdxv_ablate.so)
+        if (value != 0) return fail(c, "option ablate: this library was built without the ablation kernels (-DDXV_ABLATE)");
+#endif
+        break;
+    case OptionEffect::plistres:
+        if (slot != (int)value) { if (sync_frames(c)) return 1; c->rowLists.state = 0; }     // the next parity launch rebuilds the row lists
+        break;
+    case OptionEffect::listres:
+        if (slot != (int)value && sync_frames(c)) return 1;             // the next launch rebuilds the lists: nothing may still read them
+        break;
+    default: break;
+    }
+    slot = (int)value;
+    switch (row->effect) {                                              // ... and behind it
+    case OptionEffect::wide:
         // the wide copy is a section of the scene: a scene built without it is built again
         if (value && c->haveScene && !c->hdr.hasWide) {
             if (!c->haveMesh) return fail(c, "option wide: this scene was imported without wide nodes; set the option on the exporting context before dxv_build");
             return dxv_build(c);
         }
-    } else if (!strcmp(key, "lists")) {
-        if (value < 0 || value > 2) return fail(c, "option lists: %lld not in {0,1,2}", (long long)value);
-        c->optLists = (int)value;
-    } else if (!strcmp(key, "plan")) {
-        if (value < 0 || value > 2) return fail(c, "option plan: %lld not in {0,1,2}", (long long)value);
-        c->optPlan = (int)value;
-    } else if (!strcmp(key, "prepared")) {
-        if (value != 0 && value != 1) return fail(c, "option prepared: %lld not in {0,1}", (long long)value);
-        c->optPrepared = (int)value;
-    } else if (!strcmp(key, "listedwaves")) {
-        if (value != 0 && (value < 8 || value > 32)) return fail(c, "option listedwaves: %lld not in {0,8..32}", (long long)value);
-        c->optListedWaves = (int)value;
-    } else if (!strcmp(key, "coop")) {
-        if (value != 0 && value != 1) return fail(c, "option coop: %lld not in {0,1}", (long long)value);
-        c->optCoop = (int)value;
-    } else if (!strcmp(key, "farmap")) {
-        if (value != 0 && value != 1) return fail(c, "option farmap: %lld not in {0,1}", (long long)value);
-        c->optFarMap = (int)value;
-    } else if (!strcmp(key, "prepclear")) {
-        if (value < 0 || value > 3) return fail(c, "option prepclear: %lld not in {0,1,2,3}", (long long)value);
-        c->optPrepClear = (int)value;
-    } else if (!strcmp(key, "queuewaves")) {
-        if (value < 0 || value > (1 << 20)) return fail(c, "option queuewaves: %lld not in [0, 2^20]", (long long)value);
-        c->optQueueWaves = (int)value;
-    } else if (!strcmp(key, "queuemin")) {
-        if (value < 0 || value > 4096) return fail(c, "option queuemin: %lld not in [0, 4096]", (long long)value);
-        c->optQueueMin = (int)value;
-    } else if (!strcmp(key, "sortbits")) {
-        if (value < 0 || value > 63 || ((value & 15) != 0 && ((value & 15) < 8 || (value & 15) > 11)))
-            return fail(c, "option sortbits: %lld not 0 or 8..11 (+16 / +32)", (long long)value);
-        radix_sort_set_plan((int)value);
-    } else if (!strcmp(key, "queueheads")) {
-        if (value != 1 && value != 2 && value != 4 && value != 8) return fail(c, "option queueheads: %lld not in {1,2,4,8}", (long long)value);
-        c->optQueueHeads = (int)value;
-    } else if (!strcmp(key, "planregion")) {
-        if (value != 0 && (value < 6 || value > 8)) return fail(c, "option planregion: %lld not in {0,6,7,8}", (long long)value);
-        c->optPlanRegion = (int)value;
-    } else if (!strcmp(key, "planheavy")) {
-        if (value < 0 || value > 65535) return fail(c, "option planheavy: %lld not in [0, 65535]", (long long)value);
-        c->optPlanHeavy = (int)value;
-    } else if (!strcmp(key, "fuse")) {
-        if (value != 0 && value != 1) return fail(c, "option fuse: %lld not in {0,1}", (long long)value);
-        c->optFuse = (int)value;
-    } else if (!strcmp(key, "events")) {
-        if (value != 0 && value != 1) return fail(c, "option events: %lld not in {0,1}", (long long)value);
-        c->optEvents = (int)value;
-    } else if (!strcmp(key, "plistres")) {
-        if (value != 0 && (value < 16 || value > 4096 || (value & (value - 1)))) return fail(c, "option plistres: %lld is not 0 or a power of two in [16, 4096]", (long long)value);
-        if (c->optPlistRes != (int)value) { if (sync_frames(c)) return 1; c->plState = 0; }     // the next parity launch rebuilds the row lists
-        c->optPlistRes = (int)value;
-    } else if (!strcmp(key, "plists")) {
-        if (value < 0 || value > 2) return fail(c, "option plists: %lld not in {0,1,2}", (long long)value);
-        c->optPlists = (int)value;
-    } else if (!strcmp(key, "listres")) {
-        if (value != 0 && (value < 16 || value > 4096 || (value & (value - 1)))) return fail(c, "option listres: %lld is not 0 or a power of two in [16, 4096]", (long long)value);
-        if (c->optListRes != (int)value && sync_frames(c)) return 1;     // the next launch rebuilds the lists: nothing may still read them
-        c->optListRes = (int)value;
-    } else if (!strcmp(key, "dispatch")) {
-        if (value < 0 || value > 2) return fail(c, "option dispatch: %lld not in {0,1,2}", (long long)value);
-        c->optDispatch = (int)value;
-    } else if (!strcmp(key, "ablate")) {
-#if defined(DXV_ABLATE)
-        if (value != 0 && value != 1 && value != 2 && value != 4 && value != 6 && value != 8 && value != 16 && value != 18 && value != 32 && value != 64) return fail(c, "option ablate: %lld not in {0,1,2,4,6,8,16,18,32,64}", (long long)value);
-        c->optAblate = (int)value;
-#else
-        // the timing-only variants of the lists kernel write wrong grids by design: they exist only in the library that
-        // tools/ablate.py builds for itself (python -m dxrvoxelizer_amd.build --ablate -> libdxv_ablate.so)
-        if (value != 0) return fail(c, "option ablate: this library was built without the ablation kernels (-DDXV_ABLATE)");
-#endif
-    } else if (!strcmp(key, "surfaceitems")) {
-        if (value < 0 || value > (1 << 20)) return fail(c, "option surfaceitems: %lld not in [0, 2^20]", (long long)value);
-        c->optSurfaceItems = (int)value;
-    } else if (!strcmp(key, "skipempty")) {
-        if (value != 0 && value != 1) return fail(c, "option skipempty: %lld not in {0,1}", (long long)value);
-        c->optSkipEmpty = (int)value;
-    } else if (!strcmp(key, "rowblock")) {
-        if (value != 0 && value != 1 && value != 2 && value != 4) return fail(c, "option rowblock: %lld not in {0,1,2,4}", (long long)value);
-        c->optRowBlock = (int)value;
-    } else if (!strcmp(key, "rows")) {
-        if (value != 0 && value != 1) return fail(c, "option rows: %lld not in {0,1}", (long long)value);
-        c->optRows = (int)value;
-    } else if (!strcmp(key, "queue")) {
-        if (value != 0 && value != 1) return fail(c, "option queue: %lld not in {0,1}", (long long)value);
-        c->optQueue = (int)value;
-    } else if (!strcmp(key, "stack0")) {
-        if (value < 8 || value > 64 || stack_round_up((int)value) != (int)value) return fail(c, "option stack0: bad depth %lld", (long long)value);
-        c->optStack0 = (int)value;
-        if (c->haveScene) c->stackNow = stack_round_up((int)(c->hdr.treeHeight + 3 < (uint32_t)value ? c->hdr.treeHeight + 3 : (uint32_t)value));
-    } else if (!strcmp(key, "region")) {
-        if (value < 0 || value > 24) return fail(c, "option region: %lld not in [0,24]", (long long)value);
-        c->optRegion = (int)value;
-    } else if (!strcmp(key, "morton")) {
-        if (value != 0 && value != 1) return fail(c, "option morton: %lld not in {0,1}", (long long)value);
-        c->optMorton = (int)value;
-    } else return fail(c, "unknown option '%s'", key);
+        break;
+    case OptionEffect::stack0:
+        if (c->haveScene) c->stackNow = initial_stack(c);
+        break;
+    case OptionEffect::sortbits: radix_sort_set_plan((int)value); break;     // (the plan is the process's, not the context's)
+    default: break;
+    }
     return 0;
 }
 

@@ -27,12 +27,12 @@ BlobLayout blob_layout(size_t sceneBytes, uint32_t listRes, uint32_t listCount, 
     }
     return b;
 }
-bool lists_exportable(const dxv_ctx* c) { return c->listState == 1 && c->listOpt == c->optListRes; }
-bool plists_exportable(const dxv_ctx* c) { return c->plState == 1 && (c->optPlistRes == 0 || (uint32_t)c->optPlistRes == c->plRes); }
+bool lists_exportable(const dxv_ctx* c) { return c->lists.state == 1 && c->lists.opt == c->opt.listres; }
+bool plists_exportable(const dxv_ctx* c) { return c->rowLists.state == 1 && (c->opt.plistres == 0 || (uint32_t)c->opt.plistres == c->rowLists.res); }
 BlobLayout export_layout(const dxv_ctx* c)
 {
     const bool l = lists_exportable(c), pl = plists_exportable(c);
-    return blob_layout(c->sceneBytes, l ? c->listRes : 0u, l ? c->listEntries : 0u, pl ? c->plRes : 0u, pl ? c->plEntries : 0u);
+    return blob_layout(c->sceneBytes, l ? c->lists.res : 0u, l ? c->lists.count : 0u, pl ? c->rowLists.res : 0u, pl ? c->rowLists.count : 0u);
 }
 } // namespace
 
@@ -54,20 +54,20 @@ int dxv_scene_export(dxv_ctx* c, void* dst, size_t bytes)
     if (!dst || bytes != b.total) return fail(c, "dxv_scene_export: expected %zu bytes, got %zu", b.total, bytes);
     DXV_HIP(c, hipSetDevice(c->device));
     if (ensure_nodes(c, c->stream)) return 1;
-    DXV_HIP(c, hipMemcpyAsync(dst, c->dScene, c->sceneBytes, hipMemcpyDeviceToDevice, c->stream));
+    DXV_HIP(c, hipMemcpyAsync(dst, c->scene.p, c->sceneBytes, hipMemcpyDeviceToDevice, c->stream));
     SceneHeader h = c->hdr;
     h.offListCells = h.offListEntries = 0; h.listRes = h.listCount = 0;
     h.offPlCells = h.offPlEntries = 0; h.plRes = h.plCount = 0;
     uint8_t* out = static_cast<uint8_t*>(dst);
     if (withLists) {
-        DXV_HIP(c, hipMemcpyAsync(out + b.offCells, c->dListCells, b.cellBytes, hipMemcpyDeviceToDevice, c->stream));
-        if (b.entryBytes) DXV_HIP(c, hipMemcpyAsync(out + b.offEntries, c->dListEntries, b.entryBytes, hipMemcpyDeviceToDevice, c->stream));
-        h.offListCells = b.offCells; h.offListEntries = b.offEntries; h.listRes = c->listRes; h.listCount = c->listEntries;
+        DXV_HIP(c, hipMemcpyAsync(out + b.offCells, c->lists.cells.p, b.cellBytes, hipMemcpyDeviceToDevice, c->stream));
+        if (b.entryBytes) DXV_HIP(c, hipMemcpyAsync(out + b.offEntries, c->lists.entries.p, b.entryBytes, hipMemcpyDeviceToDevice, c->stream));
+        h.offListCells = b.offCells; h.offListEntries = b.offEntries; h.listRes = c->lists.res; h.listCount = c->lists.count;
     }
     if (withPl) {
-        DXV_HIP(c, hipMemcpyAsync(out + b.offPlCells, c->dPlCells, b.plCellBytes, hipMemcpyDeviceToDevice, c->stream));
-        if (b.plEntryBytes) DXV_HIP(c, hipMemcpyAsync(out + b.offPlEntries, c->dPlEntries, b.plEntryBytes, hipMemcpyDeviceToDevice, c->stream));
-        h.offPlCells = b.offPlCells; h.offPlEntries = b.offPlEntries; h.plRes = c->plRes; h.plCount = c->plEntries;
+        DXV_HIP(c, hipMemcpyAsync(out + b.offPlCells, c->rowLists.cells.p, b.plCellBytes, hipMemcpyDeviceToDevice, c->stream));
+        if (b.plEntryBytes) DXV_HIP(c, hipMemcpyAsync(out + b.offPlEntries, c->rowLists.entries.p, b.plEntryBytes, hipMemcpyDeviceToDevice, c->stream));
+        h.offPlCells = b.offPlCells; h.offPlEntries = b.offPlEntries; h.plRes = c->rowLists.res; h.plCount = c->rowLists.count;
     }
     h.totalBytes = b.total;
     DXV_HIP(c, hipMemcpyAsync(dst, &h, sizeof(h), hipMemcpyHostToDevice, c->stream));     // the blob's own header (the resident one keeps the scene's size)
@@ -80,9 +80,9 @@ int dxv_scene_checksum(dxv_ctx* c, const void* device_blob, size_t bytes, uint64
     if (!c || !sum) return 1;
     if (!device_blob || bytes < 8) return fail(c, "dxv_scene_checksum: no blob");
     DXV_HIP(c, hipSetDevice(c->device));
-    DXV_HIP(c, launch_checksum(device_blob, bytes, c->dCount, c->stream));
+    DXV_HIP(c, launch_checksum(device_blob, bytes, c->count.p, c->stream));
     unsigned long long v = 0;
-    DXV_HIP(c, hipMemcpyAsync(&v, c->dCount, sizeof(v), hipMemcpyDeviceToHost, c->stream));
+    DXV_HIP(c, hipMemcpyAsync(&v, c->count.p, sizeof(v), hipMemcpyDeviceToHost, c->stream));
     DXV_HIP(c, hipStreamSynchronize(c->stream));
     *sum = v;
     return 0;
@@ -112,71 +112,44 @@ int dxv_scene_import(dxv_ctx* c, const void* src, size_t bytes)
         (withPl && (h.offPlCells != b.offPlCells || h.offPlEntries != b.offPlEntries)) || (!withPl && (h.offPlCells || h.offPlEntries || h.plCount)))
         return fail(c, "dxv_scene_import: inconsistent header (T=%u, bytes=%zu)", h.numTris, bytes);
     if (sync_frames(c)) return 1;
-    drop_prepared(c);
-    c->haveScene = false; c->listState = 0; c->specRes = 0; c->listResFloor = 0; c->listFloorTried = false; c->refitted = false; c->launchesOfScene = 0; c->plState = 0; c->parityLaunchesOfScene = 0; c->nodesStale = 0;
+    scene_changed(c, SceneCause::import);
     // An imported scene carries no mesh and no build state: drop what an earlier dxv_set_mesh / dxv_build left on this
     // context, so that dxv_build, dxv_refit and dxv_update_vertices fail cleanly instead of running the imported
     // triangle count over the old, smaller buffers.
     DXV_HIP(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(c->dVb); (void)hipFree(c->dIb);
-    c->dVb = nullptr; c->dIb = nullptr; c->vbCap = c->ibCap = 0; c->haveMesh = false; c->haveHierarchy = false;
-    free_scratch(c);
+    c->vb.release(); c->ib.release();
+    c->scratch = BuildScratch{};
     if (alloc_scene(c, h.numTris, h.numVerts, h.hasWide != 0)) return 1;
-    DXV_HIP(c, hipMemcpyAsync(c->dScene, src, want.totalBytes, hipMemcpyDeviceToDevice, c->stream));
+    DXV_HIP(c, hipMemcpyAsync(c->scene.p, src, want.totalBytes, hipMemcpyDeviceToDevice, c->stream));
     if (withLists) {
         // the lists travel with the scene: adopt them instead of building them again (1-5 ms per rank at 1 M triangles)
-        const size_t cells = 6 * (size_t)h.listRes * h.listRes;
-        if (cells > c->listCellCap) {
-            (void)hipFree(c->dListCells); c->dListCells = nullptr; c->listCellCap = 0;
-            DXV_HIP(c, hipMalloc(&c->dListCells, cells * sizeof(DirCell)));
-            c->listCellCap = cells;
-        }
-        if ((size_t)h.listCount > c->listEntryCap) {
-            (void)hipFree(c->dListEntries); c->dListEntries = nullptr; c->listEntryCap = 0;
-            DXV_HIP(c, hipMalloc(&c->dListEntries, ((size_t)h.listCount + 4) * sizeof(DirEntry)));
-            c->listEntryCap = h.listCount;
-        }
+        DXV_HIP(c, c->lists.reserve(h.listRes, h.listCount));
         const uint8_t* in = static_cast<const uint8_t*>(src);
-        DXV_HIP(c, hipMemcpyAsync(c->dListCells, in + b.offCells, b.cellBytes, hipMemcpyDeviceToDevice, c->stream));
-        if (b.entryBytes) DXV_HIP(c, hipMemcpyAsync(c->dListEntries, in + b.offEntries, b.entryBytes, hipMemcpyDeviceToDevice, c->stream));
+        DXV_HIP(c, hipMemcpyAsync(c->lists.cells.p, in + b.offCells, b.cellBytes, hipMemcpyDeviceToDevice, c->stream));
+        if (b.entryBytes) DXV_HIP(c, hipMemcpyAsync(c->lists.entries.p, in + b.offEntries, b.entryBytes, hipMemcpyDeviceToDevice, c->stream));
         // The kernel indexes the entries with what the cells say and the triangle records with what the entries say: a blob
         // whose header is consistent but whose payload is not (cut short, corrupted, another version's) must not get that far.
         uint32_t bad[2] = {0, 0};
-        DXV_HIP(c, dirmap_validate(c->dListCells, h.listRes, c->dListEntries, h.listCount, h.numTris, c->dRootInfo, c->stream));
-        DXV_HIP(c, hipMemcpyAsync(bad, c->dRootInfo, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
+        DXV_HIP(c, dirmap_validate(c->lists.cells.p, h.listRes, c->lists.entries.p, h.listCount, h.numTris, c->rootInfo.p, c->stream));
+        DXV_HIP(c, hipMemcpyAsync(bad, c->rootInfo.p, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
         DXV_HIP(c, hipStreamSynchronize(c->stream));
         if (bad[0] || bad[1])
             return fail(c, "dxv_scene_import: the list section is inconsistent (%u texels point outside the %u entries, %u entries name a triangle >= %u)",
                         bad[0], h.listCount, bad[1], h.numTris);
         // the max-mip of the far radii is a function of the cells: made here, not carried in the blob
-        if (dm_mip_words(h.listRes) > c->mipCap) {
-            (void)hipFree(c->dMip); c->dMip = nullptr; c->mipCap = 0;
-            DXV_HIP(c, hipMalloc(&c->dMip, sizeof(uint16_t) * (size_t)dm_mip_buffer_words(h.listRes)));
-            c->mipCap = dm_mip_words(h.listRes);
-        }
-        DXV_HIP(c, dirmap_mip(c->dListCells, h.listRes, c->dMip, c->stream));
+        DXV_HIP(c, dirmap_mip(c->lists.cells.p, h.listRes, c->lists.mip.p, c->stream));
         DXV_HIP(c, hipStreamSynchronize(c->stream));
     }
     if (withPl) {
         // ... and so do the row lists of the parity rule (1.6 ms per rank at 1 M triangles)
-        const size_t cellWords = 2 * (size_t)h.plRes * h.plRes;
-        if (cellWords > c->plCellCap) {
-            (void)hipFree(c->dPlCells); c->dPlCells = nullptr; c->plCellCap = 0;
-            DXV_HIP(c, hipMalloc(&c->dPlCells, cellWords * sizeof(uint32_t)));
-            c->plCellCap = cellWords;
-        }
-        if ((size_t)h.plCount + 8 > c->plEntryCap) {
-            (void)hipFree(c->dPlEntries); c->dPlEntries = nullptr; c->plEntryCap = 0;
-            DXV_HIP(c, hipMalloc(&c->dPlEntries, ((size_t)h.plCount + 8) * sizeof(uint32_t)));
-            c->plEntryCap = (size_t)h.plCount + 8;
-        }
+        DXV_HIP(c, c->rowLists.reserve(h.plRes, h.plCount));
         const uint8_t* in = static_cast<const uint8_t*>(src);
-        DXV_HIP(c, hipMemcpyAsync(c->dPlCells, in + b.offPlCells, b.plCellBytes, hipMemcpyDeviceToDevice, c->stream));
-        if (b.plEntryBytes) DXV_HIP(c, hipMemcpyAsync(c->dPlEntries, in + b.offPlEntries, b.plEntryBytes, hipMemcpyDeviceToDevice, c->stream));
-        DXV_HIP(c, hipMemsetAsync(c->dPlEntries + h.plCount, 0, 8 * sizeof(uint32_t), c->stream));       // (the kernel fetches up to three slots behind a list)
+        DXV_HIP(c, hipMemcpyAsync(c->rowLists.cells.p, in + b.offPlCells, b.plCellBytes, hipMemcpyDeviceToDevice, c->stream));
+        if (b.plEntryBytes) DXV_HIP(c, hipMemcpyAsync(c->rowLists.entries.p, in + b.offPlEntries, b.plEntryBytes, hipMemcpyDeviceToDevice, c->stream));
+        DXV_HIP(c, hipMemsetAsync(c->rowLists.entries.p + h.plCount, 0, 8 * sizeof(uint32_t), c->stream));       // (the kernel fetches up to three slots behind a list)
         uint32_t bad[2] = {0, 0};
-        DXV_HIP(c, parity_lists_validate(c->dPlCells, h.plRes, c->dPlEntries, h.plCount, h.numTris, c->dRootInfo, c->stream));
-        DXV_HIP(c, hipMemcpyAsync(bad, c->dRootInfo, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
+        DXV_HIP(c, parity_lists_validate(c->rowLists.cells.p, h.plRes, c->rowLists.entries.p, h.plCount, h.numTris, c->rootInfo.p, c->stream));
+        DXV_HIP(c, hipMemcpyAsync(bad, c->rootInfo.p, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
         DXV_HIP(c, hipStreamSynchronize(c->stream));
         if (bad[0] || bad[1])
             return fail(c, "dxv_scene_import: the row-list section is inconsistent (%u texels point outside the %u entries, %u entries name a triangle >= %u)",
@@ -185,25 +158,22 @@ int dxv_scene_import(dxv_ctx* c, const void* src, size_t bytes)
     const uint32_t listRes = h.listRes, listCount = h.listCount, plRes = h.plRes, plCount = h.plCount;
     h.offListCells = h.offListEntries = 0; h.listRes = h.listCount = 0; h.totalBytes = want.totalBytes;   // the resident header describes the resident scene
     h.offPlCells = h.offPlEntries = 0; h.plRes = h.plCount = 0;
-    DXV_HIP(c, hipMemcpyAsync(c->dScene, &h, sizeof(h), hipMemcpyHostToDevice, c->stream));
+    DXV_HIP(c, hipMemcpyAsync(c->scene.p, &h, sizeof(h), hipMemcpyHostToDevice, c->stream));
     DXV_HIP(c, hipStreamSynchronize(c->stream));
     c->hdr = h;
     c->T = h.numTris; c->V = h.numVerts;
     memcpy(c->bound, h.bound, sizeof(c->bound));
     c->haveScene = true;
     ++c->sceneEpoch;
-    if (withLists && (c->optListRes == 0 || (uint32_t)c->optListRes == listRes)) {   // (an explicit listres of another size: built here as asked)
-        c->listEntries = listCount; c->listRes = listRes; c->listState = 1; c->listOpt = c->optListRes; c->listMs = 0.0f;
+    if (withLists && (c->opt.listres == 0 || (uint32_t)c->opt.listres == listRes)) {   // (an explicit listres of another size: built here as asked)
+        c->lists.count = listCount; c->lists.res = listRes; c->lists.state = 1; c->lists.opt = c->opt.listres; c->lists.ms = 0.0f;
         ++c->listEpoch;
     }
-    if (withPl && (c->optPlistRes == 0 || (uint32_t)c->optPlistRes == plRes)) {
-        c->plEntries = plCount; c->plRes = plRes; c->plState = 1; c->plMs = 0.0f;
+    if (withPl && (c->opt.plistres == 0 || (uint32_t)c->opt.plistres == plRes)) {
+        c->rowLists.count = plCount; c->rowLists.res = plRes; c->rowLists.state = 1; c->rowLists.ms = 0.0f;
     }
-    c->stackNow = stack_round_up((int)(h.treeHeight + 3 < (uint32_t)c->optStack0 ? h.treeHeight + 3 : (uint32_t)c->optStack0));
-    c->stats.num_tris = h.numTris; c->stats.num_verts = h.numVerts; c->stats.num_nodes = h.numNodes;
-    c->stats.tree_height = h.treeHeight;
-    c->stats.tri_extent = h.triExtent;
-    memcpy(c->stats.bound, h.bound, sizeof(h.bound));
+    c->stackNow = initial_stack(c);
+    fill_scene_stats(c);
     return 0;
 }
 

@@ -94,35 +94,38 @@ static hipError_t launch_list_check(const VoxelizeParams& p, unsigned long long*
 }
 } // namespace dxv
 
+// one checker over `words` zeroed 64-bit counters on stream s, the first `back` of them read into out
+template <class LaunchFn>
+static int run_check(dxv_ctx* c, const char* who, size_t words, size_t back, uint64_t* out, hipStream_t s, LaunchFn launch)
+{
+    DevBuf<unsigned long long> d;                                       // (a temporary of the call: freed when it returns)
+    DXV_HIP(c, d.reserve(words, words * sizeof(unsigned long long)));
+    hipError_t e = hipMemsetAsync(d.p, 0, words * sizeof(unsigned long long), s);
+    if (e == hipSuccess) e = launch(d.p);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d.p, back * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(c, "%s failed: %s", who, hipGetErrorString(e));
+    return 0;
+}
+
 extern "C" int dxv_debug_list_check(dxv_ctx* c, uint32_t N, uint32_t z0, uint32_t nz, uint64_t out[34])
 {
     if (!c || !out) return 1;
     if (!c->haveScene) return fail(c, "dxv_debug_list_check: no scene");
-    if (N < 2 || (N & 1u) || N > 2048) return fail(c, "dxv_debug_list_check: grid_dim must be even and in [2, 2048], got %u", N);
-    if (nz == 0 || z0 >= N || nz > N - z0) return fail(c, "dxv_debug_list_check: slab [%u, %u+%u) outside the grid (N=%u)", z0, z0, nz, N);
+    if (check_slab(c, "dxv_debug_list_check", N, z0, nz)) return 1;
     if (c->hdr.treeHeight + 1 > 64) return fail(c, "dxv_debug_list_check: tree too deep for the checker's stack");
     DXV_HIP(c, hipSetDevice(c->device));
     if (sync_frames(c)) return 1;
-    if (c->listState == 0 || c->listOpt != c->optListRes) {
+    if (c->lists.state == 0 || c->lists.opt != c->opt.listres) {
         if (build_lists(c, c->stream)) return 1;
     }
-    if (c->listState != 1) return fail(c, "dxv_debug_list_check: this scene has no lists (over the caps)");
+    if (c->lists.state != 1) return fail(c, "dxv_debug_list_check: this scene has no lists (over the caps)");
     if (ensure_nodes(c, c->stream)) return 1;
-    unsigned long long* dOut = nullptr;
-    DXV_HIP(c, hipMalloc(&dOut, 34 * sizeof(unsigned long long)));
     VoxelizeParams p{};
-    p.scene.nodes = scene_nodes32(c); p.scene.triPos = scene_tripos(c); p.scene.triNrm = scene_trinrm(c);
-    memcpy(p.scene.rootLo, c->hdr.rootLo, 12);
-    memcpy(p.scene.rootHi, c->hdr.rootHi, 12);
-    p.scene.dmCells = c->dListCells; p.scene.dmEntries = c->dListEntries; p.scene.dmR = c->listRes;
+    scene_params(c, p.scene);
+    lists_params(c, p.scene);
     p.N = N; p.z0 = z0; p.nz = nz;
-    hipError_t e = hipMemsetAsync(dOut, 0, 34 * sizeof(unsigned long long), c->stream);
-    if (e == hipSuccess) e = launch_list_check(p, dOut, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dOut, 34 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(dOut);
-    if (e != hipSuccess) return fail(c, "dxv_debug_list_check failed: %s", hipGetErrorString(e));
-    return 0;
+    return run_check(c, "dxv_debug_list_check", 34, 34, out, c->stream, [&](unsigned long long* d) { return launch_list_check(p, d, c->stream); });
 }
 
 namespace dxv {
@@ -179,26 +182,15 @@ extern "C" int dxv_debug_class_check(dxv_ctx* c, uint32_t N, uint32_t z0, uint32
 {
     if (!c || !out) return 1;
     if (!c->haveScene) return fail(c, "dxv_debug_class_check: no scene");
-    if (N < 2 || (N & 1u) || N > 2048) return fail(c, "dxv_debug_class_check: grid_dim must be even and in [2, 2048], got %u", N);
-    if (nz == 0 || z0 >= N || nz > N - z0) return fail(c, "dxv_debug_class_check: slab [%u, %u+%u) outside the grid (N=%u)", z0, z0, nz, N);
+    if (check_slab(c, "dxv_debug_class_check", N, z0, nz)) return 1;
     if (c->hdr.treeHeight + 1 > 64) return fail(c, "dxv_debug_class_check: tree too deep for the checker's stack");
     DXV_HIP(c, hipSetDevice(c->device));
     if (sync_frames(c)) return 1;
     if (ensure_nodes(c, c->stream)) return 1;
-    unsigned long long* dOut = nullptr;
-    DXV_HIP(c, hipMalloc(&dOut, 34 * sizeof(unsigned long long)));
     VoxelizeParams p{};
-    p.scene.nodes = scene_nodes32(c); p.scene.triPos = scene_tripos(c); p.scene.triNrm = scene_trinrm(c);
-    memcpy(p.scene.rootLo, c->hdr.rootLo, 12);
-    memcpy(p.scene.rootHi, c->hdr.rootHi, 12);
+    scene_params(c, p.scene);
     p.N = N; p.z0 = z0; p.nz = nz;
-    hipError_t e = hipMemsetAsync(dOut, 0, 34 * sizeof(unsigned long long), c->stream);
-    if (e == hipSuccess) e = launch_class_check(p, dOut, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dOut, 34 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(dOut);
-    if (e != hipSuccess) return fail(c, "dxv_debug_class_check failed: %s", hipGetErrorString(e));
-    return 0;
+    return run_check(c, "dxv_debug_class_check", 34, 34, out, c->stream, [&](unsigned long long* d) { return launch_class_check(p, d, c->stream); });
 }
 
 namespace dxv {
@@ -270,15 +262,11 @@ extern "C" int dxv_debug_division_check(dxv_ctx* c, uint32_t n_first, uint32_t n
     if (!c || !out) return 1;
     if (n_first < 2 || (n_first & 1u) || n_last > 2048 || n_last < n_first) return fail(c, "dxv_debug_division_check: need even 2 <= n_first <= n_last <= 2048");
     DXV_HIP(c, hipSetDevice(c->device));
-    unsigned long long* dOut = nullptr;
-    DXV_HIP(c, hipMalloc(&dOut, 10 * sizeof(unsigned long long)));
-    hipError_t e = hipMemsetAsync(dOut, 0, 10 * sizeof(unsigned long long), c->stream);
-    for (uint32_t N = n_first; N <= n_last && e == hipSuccess; N += 2u) e = launch_division_check(N, dOut, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dOut, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(dOut);
-    if (e != hipSuccess) return fail(c, "dxv_debug_division_check failed: %s", hipGetErrorString(e));
-    return 0;
+    return run_check(c, "dxv_debug_division_check", 10, 8, out, c->stream, [&](unsigned long long* d) {
+        hipError_t e = hipSuccess;
+        for (uint32_t N = n_first; N <= n_last && e == hipSuccess; N += 2u) e = launch_division_check(N, d, c->stream);
+        return e;
+    });
 }
 
 namespace dxv {
@@ -330,33 +318,22 @@ extern "C" int dxv_debug_far_check(dxv_ctx* c, uint32_t N, uint32_t z0, uint32_t
 {
     if (!c || !out) return 1;
     if (!c->haveScene) return fail(c, "dxv_debug_far_check: no scene");
-    if (N < 2 || (N & 1u) || N > 2048) return fail(c, "dxv_debug_far_check: grid_dim must be even and in [2, 2048], got %u", N);
-    if (nz == 0 || z0 >= N || nz > N - z0) return fail(c, "dxv_debug_far_check: slab [%u, %u+%u) outside the grid (N=%u)", z0, z0, nz, N);
+    if (check_slab(c, "dxv_debug_far_check", N, z0, nz)) return 1;
     if (c->hdr.treeHeight + 1 > 64) return fail(c, "dxv_debug_far_check: tree too deep for the checker's stack");
     DXV_HIP(c, hipSetDevice(c->device));
     if (sync_frames(c)) return 1;
     if (ensure_nodes(c, c->stream)) return 1;
     VoxelizeParams p{};
-    p.scene.nodes = scene_nodes32(c); p.scene.triPos = scene_tripos(c); p.scene.triNrm = scene_trinrm(c);
-    memcpy(p.scene.rootLo, c->hdr.rootLo, 12);
-    memcpy(p.scene.rootHi, c->hdr.rootHi, 12);
+    scene_params(c, p.scene);
     p.N = N; p.z0 = z0; p.nz = nz;
     if (lists_mip) {
-        if (c->listState != 1 || !c->dMip) return fail(c, "dxv_debug_far_check: this scene has no lists");
-        p.mip = c->dMip; p.mipR = c->listRes;
+        if (c->lists.state != 1 || !c->lists.mip.p) return fail(c, "dxv_debug_far_check: this scene has no lists");
+        p.mip = c->lists.mip.p; p.mipR = c->lists.res;
     } else {
         if (ensure_far_map(c, c->stream)) return 1;
-        p.mip = c->dFarMip; p.mipR = c->farR;
+        p.mip = c->farMap.mip.p; p.mipR = c->farMap.R;
     }
-    unsigned long long* dOut = nullptr;
-    DXV_HIP(c, hipMalloc(&dOut, 12 * sizeof(unsigned long long)));
-    hipError_t e = hipMemsetAsync(dOut, 0, 12 * sizeof(unsigned long long), c->stream);
-    if (e == hipSuccess) e = launch_far_check(p, dOut, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dOut, 12 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(dOut);
-    if (e != hipSuccess) return fail(c, "dxv_debug_far_check failed: %s", hipGetErrorString(e));
-    return 0;
+    return run_check(c, "dxv_debug_far_check", 12, 12, out, c->stream, [&](unsigned long long* d) { return launch_far_check(p, d, c->stream); });
 }
 
 namespace dxv {
@@ -433,36 +410,33 @@ extern "C" int dxv_debug_plan_check(dxv_ctx* c, uint64_t out[16])
     bool prepared = f.lastPrepared >= 0 && c->prepared[f.lastPrepared].epoch == c->listEpoch;
     if (prepared) {
         const auto& q = c->prepared[f.lastPrepared];
-        prepared = q.N == f.grid_dim && q.z0 == f.z0 && q.nz == f.nz && q.zBlock == f.lastZBlock && q.zPeriod == f.lastZPeriod && q.dMem;
+        prepared = q.N == f.grid_dim && q.z0 == f.z0 && q.nz == f.nz && q.zBlock == f.lastZBlock && q.zPeriod == f.lastZPeriod && q.mem.p;
     }
-    if (!c->haveScene || c->listState != 1 || !(prepared || (f.lastQueued && f.dQueue)) || !f.grid_dim)
+    if (!c->haveScene || c->lists.state != 1 || !(prepared || (f.lastQueued && f.queue.p)) || !f.grid_dim)
         return fail(c, "dxv_debug_plan_check: the current frame's last launch did not go through a work queue");
     DXV_HIP(c, hipSetDevice(c->device));
     if (sync_frames(c)) return 1;
     const hipStream_t fs = cur_stream(c);
     VoxelizeParams p{};
-    memcpy(p.scene.rootLo, c->hdr.rootLo, 12);
-    memcpy(p.scene.rootHi, c->hdr.rootHi, 12);
-    p.scene.dmCells = c->dListCells; p.scene.dmEntries = c->dListEntries; p.scene.dmR = c->listRes;
-    p.N = f.grid_dim; p.z0 = f.z0; p.nz = f.nz; p.zBlock = f.lastZBlock; p.zPeriod = f.lastZPeriod;
-    while ((1u << p.zShift) < p.zBlock) ++p.zShift;
+    scene_params(c, p.scene);
+    lists_params(c, p.scene);
+    p.N = f.grid_dim; p.z0 = f.z0; p.nz = f.nz; p.zBlock = f.lastZBlock; p.zPeriod = f.lastZPeriod; p.zShift = z_shift(p.zBlock);
     uint32_t cap = 0;
     (void)plan_queue_words(p.N, p.nz, &cap);
-    p.queue = f.dQueue + f.queueHdr * kQueueHeaderWords; p.queueSlots = f.dQueue + kQueueSlotsAt; p.queueCap = cap; p.mip = c->dMip;
+    p.queue = f.queue.p + f.queueHdr * kQueueHeaderWords; p.queueSlots = f.queue.p + kQueueSlotsAt; p.queueCap = cap; p.mip = c->lists.mip.p;
     if (prepared) {                                                     // (a queue of the context's, built by dxv_prepare_launch: same layout behind ONE header)
         const auto& q = c->prepared[f.lastPrepared];
-        p.queue = q.dMem; p.queueSlots = q.dMem + kQueueHeaderWords; p.queueCap = q.cap;
+        p.queue = q.mem.p; p.queueSlots = q.mem.p + kQueueHeaderWords; p.queueCap = q.cap;
     }
     VoxelizeParams q = p;
     const uint32_t nb = plan_layout(q);
-    uint32_t* bits = nullptr;
-    unsigned long long* dOut = nullptr;
-    DXV_HIP(c, hipMalloc(&bits, sizeof(uint32_t) * (((size_t)nb + 31u) / 32u)));
-    hipError_t e = hipMalloc(&dOut, 16 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = launch_plan_check(p, bits, dOut, fs);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dOut, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, fs);
+    DevBuf<uint32_t> bits;
+    DevBuf<unsigned long long> dOut;
+    DXV_HIP(c, bits.reserve(((size_t)nb + 31u) / 32u, sizeof(uint32_t) * (((size_t)nb + 31u) / 32u)));
+    hipError_t e = dOut.reserve(16, 16 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = launch_plan_check(p, bits.p, dOut.p, fs);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dOut.p, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, fs);
     if (e == hipSuccess) e = hipStreamSynchronize(fs);
-    (void)hipFree(bits); (void)hipFree(dOut);
     if (e != hipSuccess) return fail(c, "dxv_debug_plan_check failed: %s", hipGetErrorString(e));
     return 0;
 }
@@ -486,18 +460,18 @@ extern "C" int dxv_debug_download(dxv_ctx* c, int what, void* host, size_t bytes
     if (settle_lists(c)) return 1;
     if ((what == DXV_DBG_NODES || what == DXV_DBG_NODES32 || what == DXV_DBG_NODES64) && c->haveScene && ensure_nodes(c, c->stream)) return 1;
     switch (what) {
-    case DXV_DBG_SORTED_KEYS: src = c->dKeys; want = sizeof(uint64_t) * T; if (c->scratchT != c->T) src = nullptr; break;
-    case DXV_DBG_PARENTS: src = c->dParents; want = sizeof(uint32_t) * (2 * T - 1); if (c->scratchT != c->T) src = nullptr; break;
+    case DXV_DBG_SORTED_KEYS: src = c->scratch.keys.p; want = sizeof(uint64_t) * T; if (c->scratch.T != c->T) src = nullptr; break;
+    case DXV_DBG_PARENTS: src = c->scratch.parents.p; want = sizeof(uint32_t) * (2 * T - 1); if (c->scratch.T != c->T) src = nullptr; break;
     case DXV_DBG_NODES: if (c->haveScene) { src = scene_nodes(c); want = sizeof(Node) * (size_t)c->hdr.numNodes; } break;
     case DXV_DBG_NODES32: if (c->haveScene) { src = scene_nodes32(c); want = sizeof(Node32) * (size_t)c->hdr.numNodes; } break;
     case DXV_DBG_NODES64: if (c->haveScene && c->hdr.hasWide) { src = scene_nodes64(c); want = sizeof(Node64) * (size_t)c->hdr.numNodes; } break;
     case DXV_DBG_TRI_POS: if (c->haveScene) { src = scene_tripos(c); want = sizeof(TriPos) * T; } break;
     case DXV_DBG_TRI_NRM: if (c->haveScene) { src = scene_trinrm(c); want = sizeof(TriNrm) * T; } break;
-    case DXV_DBG_LIST_CELLS: if (c->haveScene && c->listState == 1) { src = c->dListCells; want = sizeof(DirCell) * 6 * (size_t)c->listRes * c->listRes; } break;
-    case DXV_DBG_LIST_ENTRIES: if (c->haveScene && c->listState == 1) { src = c->dListEntries; want = sizeof(DirEntry) * (size_t)c->listEntries; } break;
-    case DXV_DBG_LIST_MIP: if (c->haveScene && c->listState == 1 && c->dMip) { src = c->dMip; want = sizeof(uint16_t) * (size_t)dm_mip_words(c->listRes); } break;
+    case DXV_DBG_LIST_CELLS: if (c->haveScene && c->lists.state == 1) { src = c->lists.cells.p; want = sizeof(DirCell) * 6 * (size_t)c->lists.res * c->lists.res; } break;
+    case DXV_DBG_LIST_ENTRIES: if (c->haveScene && c->lists.state == 1) { src = c->lists.entries.p; want = sizeof(DirEntry) * (size_t)c->lists.count; } break;
+    case DXV_DBG_LIST_MIP: if (c->haveScene && c->lists.state == 1 && c->lists.mip.p) { src = c->lists.mip.p; want = sizeof(uint16_t) * (size_t)dm_mip_words(c->lists.res); } break;
 #if defined(DXV_QUEUE_TIMES)
-    case 100: src = c->frames[c->cur].dRedo; want = sizeof(uint64_t) * kRedoCap; break;      // per-wave start / end ticks of the last queue launch
+    case 100: src = c->frames[c->cur].redo.p; want = sizeof(uint64_t) * kRedoCap; break;      // per-wave start / end ticks of the last queue launch
 #endif
     default: return fail(c, "dxv_debug_download: unknown selector %d", what);
     }

@@ -2,9 +2,11 @@
 // are built and on WHICH cube map, and whether a launch builds its work queue, keeps it, or has the hardware deal it out.
 // dxv_lists.hip / dxv_frames.hip carry the decisions out; tests/hostcheck compiles this header for the CPU and
 // tests/test_policy.py walks every transition (static scene, dynamic scene, the C-ABI's own rules, options) as a table.
+// The options of dxv_set_option are a table here as well: what each key accepts and where its value lives.
 // No HIP, no context: nothing here touches a device.
 #pragma once
 #include <stdint.h>
+#include <string.h>
 
 namespace dxv {
 
@@ -140,6 +142,133 @@ inline QueueLaunch queue_policy(const QueueState& q, uint64_t sig, uint64_t voxe
     const bool sizeKnown = q.lensSig == sig && q.queuedBricks != 0u;
     if (sizeKnown && (q.optDispatch == 1 || (q.optDispatch == 2 && voxels <= (1ull << 25)))) return QueueLaunch::kept_hardware;
     return QueueLaunch::kept_persistent;
+}
+
+// ---------------------------------------------------------------------------------------------
+// options (dxv_set_option; include/dxv.h documents what they do): the values a context holds, and one row per key -- its name, the
+// values it accepts, the words a refusal ends in, where the value is stored and whether setting it does more than store it
+// (dxv_api.hip carries those few out).  tests/test_policy.py checks every row against expectations written out there.
+// ---------------------------------------------------------------------------------------------
+struct Options {
+    int brick = 4;           // 4x4x4 voxels = one wavefront per workgroup (fastest in the r01 sweeps)
+    int stack = 0;           // 0 = adaptive (start small, grow on overflow), else forced depth
+    int deferboxes = 1;      // dxv_refit with lists wanted: node boxes only when a tree walk asks for them (0: always, as dxv_build does)
+    int refit = 1;           // box merge of build and refit: 1 = min/max pyramid (default), 2 = level sweeps, 0 = atomic one-pass climb (17-30x slower, cross-check)
+    int morton = 1;          // Morton brick order
+    int queue = 1;           // postponed-leaf traversal
+    int subbox = 1;          // launch only the bricks around the scene's root box, memset the rest
+    int wide = 2;            // reference rule: 2 = four-box nodes on wave-uniform visits (-2...-7 % everywhere measured),
+                             // 1 = on every visit (-8 % on low-poly meshes, +10 % on 1 M triangles at 256^3), 0 = binary only
+    int rows = 1;            // parity mode: one tree walk per grid row (k_parity_rows) instead of per voxel
+    int rowblock = 0;        // rows per side of a wave's block of rows: 0 = by triangle size, 1, 2
+    int ablate = 0;          // timing-only variants of the lists kernel (results are wrong by design; tools/ablate.py)
+    int region = 6;          // log2 bricks per XCD region (64 bricks: balanced and L2 friendly in the r01 sweeps)
+    int stack0 = 20;         // adaptive mode starts with this many entries (stack + leaf queue share them)
+    int lists = 1;           // reference rule through the lists (-40...-60 % against the tree walk, profiles/r01/final/ab_lists.jsonl):
+                             // 1 = from a scene's second launch on (from the first when that launch is large: build_lists), 2 = from the first, 0 = tree walk
+    int listres = 0;         // texels per face side; 0 = by triangle count (list_resolution)
+    int listedwaves = 0;     // workgroups per CU of the hardware-dispatched lists kernel (8 .. 32), or 0 = by grid and map (voxelize_lists.hip: listed_lds_pad)
+    int coop = 1;            // 1: the lists kernel scans a lone lane's long list with its whole wave (dxv_dirmap.h: trace_reference_dm_from)
+    int farmap = 1;          // 1: tree walks and brick-box launches of the reference rule skip the bricks none of whose rays can reach a triangle
+    int plan = 2;            // work queue of the lists kernel (live bricks only, built on the device inside the stream): 0 = none (brick box
+                             // in Morton order), 1 = built when lists, partition or buffers differ from the frame's last launch (opt-in), 2 = on every launch (default: nothing carried)
+    int queuewaves = 0;      // persistent waves of a queue launch; 0 = what the device holds at once
+    int queuemin = 0;        // persistent waves: at least this many bricks per wave (surplus waves leave at once); 0 (default) = every wave stays.
+                             // 12: torus-1M / bunny x16 at 256^3 -13 / -11 %, but dragon x9 +11 % at 256^3 and +35 % on a rank's share: not a
+                             // rule a launch can apply blind (profiles/r05/ab_surplus_waves_leave.jsonl, short_launches_queuemin12.jsonl)
+    int queueheads = 8;      // heads per queue (persistent waves): 1, 2, 4, 8
+    int planregion = 0;      // log2 of the run of Morton bricks dealt to one queue: 6, 7, 8; 0 = by the partition's size (plan_region_bits)
+    int planheavy = 0;       // list length beyond which a brick starts early; 0 = long for this scene (k_dm_heavy_thresholds), 65535: no brick does
+    int fuse = 1;            // 1: the queue build clears the grid as well (one kernel in front of the brick kernel); 0: memsets in front of it
+    int dispatch = 1;        // a kept queue whose lengths the host knows: 0 = persistent waves all the same, 1 = one workgroup per
+                             // queued brick dealt out by the hardware (-1 ... -10 % per launch, and back-to-back launches overlap
+                             // their ends: profiles/r04/ab_dispatch_kept_queue.jsonl), 2 = that for partitions of up to 2^25 voxels only
+    int events = 1;          // bracket every launch with two HIP events (stats.voxelize_ms); 0: none (a caller timing its own loop)
+    int prepared = 1;        // launches of a prepared partition use its queue (1, default); 0: they build their own like any other launch
+    int prepclear = 2;       // how such a launch clears: 0 = a clear kernel in front of the brick kernel, 1 / 2 = only the bricks nobody runs,
+                             // by workgroups in front of / behind the bricks' in the SAME dispatch
+    int plistres = 0;        // texels per side of the row lists' grid; 0 = by triangle count
+    int plists = 1;          // 1 = from a scene's second parity launch, 2 = from the first, 0 = tree walk
+    int skipempty = 1;       // display pass: skip the samples of empty 8^3 bricks (same image)
+    int surfaceitems = 0;    // surface modes: work items the large triangles' list may take (0: all 2^20 it holds; fewer: tests of a full list)
+    int sortbits = 0;        // digit plan of the radix sort as last set through this context (the plan itself is the process's: radix_sort_set_plan)
+};
+
+struct OptionRule {
+    enum Kind { range, pow2, set, sortbits } kind;   // [lo, hi]; a power of two in [lo, hi]; a member of `members`; sortbits' own
+    bool orZero;                                     // ... or 0
+    int64_t lo, hi;
+    int64_t members[11];                             // (set: ended by -1)
+};
+constexpr OptionRule in_range(int64_t lo, int64_t hi) { return {OptionRule::range, false, lo, hi, {}}; }
+constexpr OptionRule zero_or_range(int64_t lo, int64_t hi) { return {OptionRule::range, true, lo, hi, {}}; }
+constexpr OptionRule zero_or_pow2(int64_t lo, int64_t hi) { return {OptionRule::pow2, true, lo, hi, {}}; }
+template <class... V> constexpr OptionRule one_of(V... v) { return {OptionRule::set, false, 0, 0, {(int64_t)v..., -1}}; }
+constexpr OptionRule kOnOff = in_range(0, 1);
+constexpr OptionRule kSortBits = {OptionRule::sortbits, false, 0, 63, {}};    // 0 or 8..11 bits per digit, + 16 / + 32 / + 48
+
+// what dxv_set_option does for a key beyond checking and storing its value
+enum class OptionEffect { none, brick, wide, listres, plistres, stack0, sortbits, ablate };
+struct OptionRow { const char* name; OptionRule rule; const char* refusal; int Options::*where; OptionEffect effect; };
+
+// (stack, stack0: the column depths the brick kernels are compiled for -- stack_round_up, traverse.hip)
+constexpr OptionRow kOptions[] = {
+    {"brick", in_range(0, 7), "out of range", &Options::brick, OptionEffect::brick},          // (... and below num_brick_shapes())
+    {"stack", one_of(0, 8, 12, 16, 20, 24, 32, 48, 64), "not in {0,8,12,16,20,24,32,48,64}", &Options::stack, OptionEffect::none},
+    {"refit", in_range(0, 2), "not in {0,1,2}", &Options::refit, OptionEffect::none},
+    {"deferboxes", kOnOff, "not in {0,1}", &Options::deferboxes, OptionEffect::none},
+    {"subbox", kOnOff, "not in {0,1}", &Options::subbox, OptionEffect::none},
+    {"wide", in_range(0, 2), "not in {0,1,2}", &Options::wide, OptionEffect::wide},
+    {"lists", in_range(0, 2), "not in {0,1,2}", &Options::lists, OptionEffect::none},
+    {"plan", in_range(0, 2), "not in {0,1,2}", &Options::plan, OptionEffect::none},
+    {"prepared", kOnOff, "not in {0,1}", &Options::prepared, OptionEffect::none},
+    {"listedwaves", zero_or_range(8, 32), "not in {0,8..32}", &Options::listedwaves, OptionEffect::none},
+    {"coop", kOnOff, "not in {0,1}", &Options::coop, OptionEffect::none},
+    {"farmap", kOnOff, "not in {0,1}", &Options::farmap, OptionEffect::none},
+    {"prepclear", in_range(0, 3), "not in {0,1,2,3}", &Options::prepclear, OptionEffect::none},
+    {"queuewaves", in_range(0, 1 << 20), "not in [0, 2^20]", &Options::queuewaves, OptionEffect::none},
+    {"queuemin", in_range(0, 4096), "not in [0, 4096]", &Options::queuemin, OptionEffect::none},
+    {"sortbits", kSortBits, "not 0 or 8..11 (+16 / +32)", &Options::sortbits, OptionEffect::sortbits},
+    {"queueheads", one_of(1, 2, 4, 8), "not in {1,2,4,8}", &Options::queueheads, OptionEffect::none},
+    {"planregion", zero_or_range(6, 8), "not in {0,6,7,8}", &Options::planregion, OptionEffect::none},
+    {"planheavy", in_range(0, 65535), "not in [0, 65535]", &Options::planheavy, OptionEffect::none},
+    {"fuse", kOnOff, "not in {0,1}", &Options::fuse, OptionEffect::none},
+    {"events", kOnOff, "not in {0,1}", &Options::events, OptionEffect::none},
+    {"plistres", zero_or_pow2(16, 4096), "is not 0 or a power of two in [16, 4096]", &Options::plistres, OptionEffect::plistres},
+    {"plists", in_range(0, 2), "not in {0,1,2}", &Options::plists, OptionEffect::none},
+    {"listres", zero_or_pow2(16, 4096), "is not 0 or a power of two in [16, 4096]", &Options::listres, OptionEffect::listres},
+    {"dispatch", in_range(0, 2), "not in {0,1,2}", &Options::dispatch, OptionEffect::none},
+    {"ablate", one_of(0, 1, 2, 4, 6, 8, 16, 18, 32, 64), "not in {0,1,2,4,6,8,16,18,32,64}", &Options::ablate, OptionEffect::ablate},
+    {"surfaceitems", in_range(0, 1 << 20), "not in [0, 2^20]", &Options::surfaceitems, OptionEffect::none},
+    {"skipempty", kOnOff, "not in {0,1}", &Options::skipempty, OptionEffect::none},
+    {"rowblock", one_of(0, 1, 2, 4), "not in {0,1,2,4}", &Options::rowblock, OptionEffect::none},
+    {"rows", kOnOff, "not in {0,1}", &Options::rows, OptionEffect::none},
+    {"queue", kOnOff, "not in {0,1}", &Options::queue, OptionEffect::none},
+    {"stack0", one_of(8, 12, 16, 20, 24, 32, 48, 64), "not in {8,12,16,20,24,32,48,64}", &Options::stack0, OptionEffect::stack0},
+    {"region", in_range(0, 24), "not in [0,24]", &Options::region, OptionEffect::none},
+    {"morton", kOnOff, "not in {0,1}", &Options::morton, OptionEffect::none},
+};
+constexpr int kOptionCount = (int)(sizeof(kOptions) / sizeof(kOptions[0]));
+
+inline const OptionRow* find_option(const char* name)
+{
+    for (const OptionRow& row : kOptions)
+        if (!strcmp(name, row.name)) return &row;
+    return nullptr;
+}
+inline bool option_accepts(const OptionRule& r, int64_t v)
+{
+    if (r.orZero && v == 0) return true;
+    switch (r.kind) {
+    case OptionRule::range: return v >= r.lo && v <= r.hi;
+    case OptionRule::pow2: return v >= r.lo && v <= r.hi && !(v & (v - 1));
+    case OptionRule::set:
+        for (int i = 0; r.members[i] >= 0; ++i)
+            if (r.members[i] == v) return true;
+        return false;
+    case OptionRule::sortbits: return v >= r.lo && v <= r.hi && ((v & 15) == 0 || ((v & 15) >= 8 && (v & 15) <= 11));
+    }
+    return false;
 }
 
 } // namespace dxv

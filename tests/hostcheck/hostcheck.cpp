@@ -949,4 +949,17 @@ __attribute__((visibility("default"))) int hc_queue_policy_prepared(int optPlan,
     q.optPrepared = optPrepared; q.prepared = prepared != 0;
     return (int)queue_policy(q, sig, voxels);
 }
+// the option table of dxv_set_option (dxv_policy.h: kOptions): its keys, and whether a key accepts a value (-1: no such key)
+__attribute__((visibility("default"))) int hc_option_count(void) { return kOptionCount; }
+__attribute__((visibility("default"))) const char* hc_option_name(int i) { return i >= 0 && i < kOptionCount ? kOptions[i].name : nullptr; }
+__attribute__((visibility("default"))) int hc_option_accepts(const char* name, int64_t value)
+{
+    const OptionRow* row = find_option(name);
+    return row ? (option_accepts(row->rule, value) ? 1 : 0) : -1;
+}
+__attribute__((visibility("default"))) int hc_option_default(const char* name)
+{
+    const OptionRow* row = find_option(name);
+    return row ? Options{}.*row->where : -1;
+}
 }

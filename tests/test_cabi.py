@@ -30,10 +30,12 @@ def test_library_exports_every_declared_symbol(dxvlib):
     assert sorted(_lib.SYMBOLS) == names          # the Python binding covers the whole header
 
 
-def test_every_option_the_library_takes_is_documented_in_the_header():
-    """dxv_set_option's keys (csrc/dxv_api.hip) against the list in include/dxv.h: a knob nobody can read about is a bug of the boundary."""
-    src = open(os.path.join(ROOT, "dxrvoxelizer_amd", "csrc", "dxv_api.hip")).read()
-    keys = set(re.findall(r'strcmp\(key, "([a-z0-9]+)"\)', src))
+def test_every_option_the_library_takes_is_documented_in_the_header(hostcheck):
+    """dxv_set_option's keys (the option table of csrc/dxv_policy.h, read through tests/hostcheck) against the list in include/dxv.h: a knob
+    nobody can read about is a bug of the boundary."""
+    L = hostcheck.lib
+    L.hc_option_name.restype = C.c_char_p
+    keys = {L.hc_option_name(i).decode() for i in range(L.hc_option_count())}
     assert {"plan", "prepared", "prepclear", "lists", "coop", "farmap"} <= keys
     header = open(os.path.join(ROOT, "include", "dxv.h")).read()
     doc = header[header.index("Tuning knobs"):header.index("DXV_API int dxv_set_option")]

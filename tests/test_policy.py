@@ -178,3 +178,69 @@ def test_far_map_of_a_scene_without_lists_is_made_at_its_second_launch(pol):
     assert pol.hc_far_map_build_now(0, 1) == 1            # launched again unchanged: made now
     assert pol.hc_far_map_build_now(0, 7) == 1
     assert pol.hc_far_map_build_now(1, 1) == 0            # there already
+
+
+# dxv_set_option's table (dxv_policy.h: kOptions).  Written out here, not read back from the table: the default, values that must be
+# accepted (both ends of a range, every member of a set) and values that must be refused (one outside on each side, gaps of a set).
+POW2 = [0, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096]
+NOT_POW2 = [-1, 1, 8, 15, 17, 24, 48, 4095, 4097, 8192]
+DEPTHS = [8, 12, 16, 20, 24, 32, 48, 64]
+ON_OFF = dict(yes=[0, 1], no=[-1, 2])
+UP_TO_2 = dict(yes=[0, 1, 2], no=[-1, 3])
+OPTIONS = {
+    "brick": dict(default=4, yes=[0, 4, 7], no=[-1, 8]),
+    "stack": dict(default=0, yes=[0] + DEPTHS, no=[-1, 4, 7, 9, 10, 18, 28, 40, 56, 65, 128]),
+    "refit": dict(default=1, **UP_TO_2),
+    "deferboxes": dict(default=1, **ON_OFF),
+    "subbox": dict(default=1, **ON_OFF),
+    "wide": dict(default=2, **UP_TO_2),
+    "lists": dict(default=1, **UP_TO_2),
+    "plan": dict(default=2, **UP_TO_2),
+    "prepared": dict(default=1, **ON_OFF),
+    "listedwaves": dict(default=0, yes=[0, 8, 20, 32], no=[-1, 1, 7, 33]),
+    "coop": dict(default=1, **ON_OFF),
+    "farmap": dict(default=1, **ON_OFF),
+    "prepclear": dict(default=2, yes=[0, 1, 2, 3], no=[-1, 4]),
+    "queuewaves": dict(default=0, yes=[0, 1 << 20], no=[-1, (1 << 20) + 1]),
+    "queuemin": dict(default=0, yes=[0, 12, 4096], no=[-1, 4097]),
+    "sortbits": dict(default=0, yes=[0, 8, 9, 10, 11, 16, 24, 27, 32, 40, 43, 48, 59], no=[-1, 1, 7, 12, 15, 17, 23, 28, 44, 60, 63, 64]),
+    "queueheads": dict(default=8, yes=[1, 2, 4, 8], no=[-1, 0, 3, 5, 6, 7, 9, 16]),
+    "planregion": dict(default=0, yes=[0, 6, 7, 8], no=[-1, 1, 5, 9]),
+    "planheavy": dict(default=0, yes=[0, 65535], no=[-1, 65536]),
+    "fuse": dict(default=1, **ON_OFF),
+    "events": dict(default=1, **ON_OFF),
+    "plistres": dict(default=0, yes=POW2, no=NOT_POW2),
+    "plists": dict(default=1, **UP_TO_2),
+    "listres": dict(default=0, yes=POW2, no=NOT_POW2),
+    "dispatch": dict(default=1, **UP_TO_2),
+    "ablate": dict(default=0, yes=[0, 1, 2, 4, 6, 8, 16, 18, 32, 64], no=[-1, 3, 5, 7, 10, 12, 17, 20, 24, 33, 48, 65, 128]),
+    "surfaceitems": dict(default=0, yes=[0, 1 << 20], no=[-1, (1 << 20) + 1]),
+    "skipempty": dict(default=1, **ON_OFF),
+    "rowblock": dict(default=0, yes=[0, 1, 2, 4], no=[-1, 3, 5, 8]),
+    "rows": dict(default=1, **ON_OFF),
+    "queue": dict(default=1, **ON_OFF),
+    "stack0": dict(default=20, yes=DEPTHS, no=[-1, 0, 4, 7, 9, 10, 18, 28, 40, 56, 65, 128]),
+    "region": dict(default=6, yes=[0, 6, 24], no=[-1, 25]),
+    "morton": dict(default=1, **ON_OFF),
+}
+
+
+def test_option_table_accepts_what_the_chain_accepted(pol):
+    """Every key of the table with its default, the values dxv_set_option takes for it and values it refuses -- the accepted sets of the
+    strcmp chain the table replaced, written out above; a key the table has and this test does not (or the other way round) fails."""
+    pol.hc_option_name.restype = C.c_char_p
+    pol.hc_option_name.argtypes = [C.c_int]
+    pol.hc_option_accepts.argtypes = [C.c_char_p, C.c_int64]
+    pol.hc_option_default.argtypes = [C.c_char_p]
+    names = [pol.hc_option_name(i).decode() for i in range(pol.hc_option_count())]
+    assert len(names) == len(set(names)) == 34
+    assert sorted(names) == sorted(OPTIONS)
+    assert pol.hc_option_name(len(names)) is None and pol.hc_option_accepts(b"nosuchoption", 0) == -1
+    for name, want in OPTIONS.items():
+        key = name.encode()
+        assert pol.hc_option_default(key) == want["default"], name
+        assert pol.hc_option_accepts(key, want["default"]) == 1, name
+        for v in want["yes"]:
+            assert pol.hc_option_accepts(key, v) == 1, (name, v)
+        for v in want["no"] + [-(1 << 40), 1 << 40]:
+            assert pol.hc_option_accepts(key, v) == 0, (name, v)
