@@ -74,6 +74,12 @@ SYMBOLS = {
     "dxv_update_frame": (C.c_int, [C.c_void_p, _F32P, _F32P, C.c_void_p, C.c_uint32, C.c_uint32]),
     "dxv_render_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "dxv_stream_wait_frame": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "dxv_distance_async": (C.c_int, [C.c_void_p, C.c_int]),
+    "dxv_distance": (C.c_int, [C.c_void_p, C.c_int]),
+    "dxv_distance_device_ptr": (C.c_void_p, [C.c_void_p]),
+    "dxv_distance_bytes": (C.c_size_t, [C.c_void_p]),
+    "dxv_distance_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_distance_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "dxv_build_lists": (C.c_int, [C.c_void_p]),
     "dxv_build_lists_for_grid": (C.c_int, [C.c_void_p, C.c_uint32]),
     "dxv_build_parity_lists": (C.c_int, [C.c_void_p]),

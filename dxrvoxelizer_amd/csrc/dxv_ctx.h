@@ -205,6 +205,15 @@ struct dxv_ctx {
         // surface modes (surface.hip): the large triangles' lists of the frame's surface pass, its own (never the work queue's
         // buffers: a kept queue of the reference rule is still needed by the frame's next mode-0 launch)
         DevBuf<uint8_t> surf;
+        // distance field (distance.hip; dxv_distance_async): the field of the frame's grid and the scratch of its three passes, the
+        // frame's own so that frames compute theirs side by side; the scratch goes with dxv_trim, the field stays
+        DevBuf<int32_t> dist;            // (cap: voxels) 4 bytes per voxel, int32 or float32
+        DevBuf<uint8_t> distScratch;     // (cap: bytes) distance_scratch_bytes: the x pass's 16-bit values, the y pass's squares
+        uint32_t distDim = 0;            // grid side of the frame's last field (0: none yet)
+        bool distCurrent = false;        // ... which is the field of the frame's last launch (a new launch makes it stale)
+        hipEvent_t evD0 = nullptr, evD1 = nullptr;   // around the frame's last field
+        bool distTimed = false;          // ... which was bracketed by them and not read yet (the frame's next dxv_sync reads it)
+        float dist_ms = 0.0f;
     };
     Frame frames[DXV_FRAME_COUNT];
     uint32_t cur = 0;                    // dxv_set_frame

@@ -184,6 +184,11 @@ struct SurfaceParams {
 size_t surface_scratch_bytes(uint32_t T);
 hipError_t launch_surface(const SurfaceParams& p, hipStream_t s);
 
+// distance.hip -- the exact signed distance field of a whole N^3 grid (dxv_distance.h): format 0 = int32 s * d2, 1 = float32 s * sqrt(d2);
+// field: 4 * N^3 bytes, scratch: distance_scratch_bytes(N); grid, field and scratch are three different allocations
+size_t distance_scratch_bytes(uint32_t N);
+hipError_t launch_distance(const uint8_t* grid, uint32_t N, int format, void* field, uint8_t* scratch, hipStream_t s);
+
 // raycast.hip
 struct RayCastCB;
 hipError_t launch_raycast(const RayCastCB& cb, const uint8_t* grid, uint32_t N, uint32_t width, uint32_t height,

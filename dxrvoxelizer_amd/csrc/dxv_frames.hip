@@ -21,6 +21,8 @@ int frame_prepare(dxv_ctx* c, uint32_t i)
     if (!f.evEnd) DXV_HIP(c, hipEventCreateWithFlags(&f.evEnd, hipEventDisableTiming));
     if (!f.evR0) DXV_HIP(c, hipEventCreate(&f.evR0));
     if (!f.evR1) DXV_HIP(c, hipEventCreate(&f.evR1));
+    if (!f.evD0) DXV_HIP(c, hipEventCreate(&f.evD0));
+    if (!f.evD1) DXV_HIP(c, hipEventCreate(&f.evD1));
     DXV_HIP(c, f.status.reserve(64, 256));
     DXV_HIP(c, f.redo.reserve(kRedoCap, sizeof(uint64_t) * kRedoCap));
     // on the frame's own stream, and finished before anything reads the words: the streams are non-blocking, a memset on the
@@ -538,6 +540,7 @@ int voxelize_common(dxv_ctx* c, uint32_t N, int mode, uint32_t z0, uint32_t nzLo
     f.gridBytes = bytes;
     f.grid_dim = N; f.z0 = z0; f.nz = nzLocal;
     f.lastMode = mode; f.lastZBlock = zBlock; f.lastZPeriod = zPeriod;
+    f.distCurrent = false;                                              // (a field of the grid this launch replaces is stale)
     return launch_now(c, c->cur);
 }
 
@@ -554,6 +557,7 @@ int sync_frame(dxv_ctx* c, uint32_t i)
         if (readQueue) DXV_HIP(c, hipMemcpyAsync(c->pin->queueLens[i], f.queue.p + f.queueHdr * kQueueHeaderWords + queue_len_word(0), sizeof(c->pin->queueLens[i]), hipMemcpyDeviceToHost, fs));
         DXV_HIP(c, hipStreamSynchronize(fs));
         if (f.renderTimed) { f.render_ms = elapsed(f.evR0, f.evR1); f.renderTimed = false; }
+        if (f.distTimed) { f.dist_ms = elapsed(f.evD0, f.evD1); f.distTimed = false; }
         // lists this launch was queued behind without waiting for their verdict: withdrawn -> the launch again, through the tree
         if (settle_lists(c)) return 1;
         if (f.pending && f.usedLists && f.listEpochUsed == c->withdrawnEpoch && c->haveScene && f.grid_dim) {
@@ -673,6 +677,82 @@ int dxv_render_async(dxv_ctx* c, void* deviceRgba, size_t rowPitch)
                     deviceRgba, offset <= size ? size - offset : (size_t)0);
     if (settle_frame_launch(c)) return 1;
     return render_frame(c, f.cb, w, h, static_cast<uint8_t*>(deviceRgba), rowPitch, c->opt.events != 0);
+}
+
+// The distance field of the selected frame's grid (distance.hip), enqueued on the frame's stream behind whatever it holds -- under
+// dxv_render_async's host-wait rule, then the frame's end event behind it.  Field and scratch are the frame's own; growing them waits
+// for that frame's stream only.
+int dxv_distance_async(dxv_ctx* c, int format)
+{
+    if (!c) return 1;
+    if (format != DXV_DIST_SQ_I32 && format != DXV_DIST_F32)
+        return fail(c, "dxv_distance: unknown format %d (DXV_DIST_SQ_I32 = 0, DXV_DIST_F32 = 1)", format);
+    Frame& f = cur_frame(c);
+    if (!f.grid.p || !f.grid_dim) return fail(c, "dxv_distance: frame %u has no grid yet (call dxv_voxelize first)", c->cur);
+    if (!frame_renderable(f))
+        return fail(c, "dxv_distance: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share");
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (settle_frame_launch(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    const uint32_t N = f.grid_dim;
+    const size_t voxels = (size_t)N * N * N, scratch = distance_scratch_bytes(N);
+    f.distCurrent = false; f.distDim = 0;
+    DXV_HIP(c, f.dist.reserve(voxels, align256(voxels * sizeof(int32_t)), fs));
+    DXV_HIP(c, f.distScratch.reserve(scratch, scratch, fs));
+    const bool timed = c->opt.events != 0;
+    if (timed) DXV_HIP(c, hipEventRecord(f.evD0, fs));
+    DXV_HIP(c, launch_distance(f.grid.p, N, format, f.dist.p, f.distScratch.p, fs));
+    if (timed) DXV_HIP(c, hipEventRecord(f.evD1, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    f.distTimed = timed;
+    f.distDim = N; f.distCurrent = true;
+    return 0;
+}
+
+int dxv_distance(dxv_ctx* c, int format)
+{
+    if (dxv_distance_async(c, format)) return 1;
+    return dxv_sync(c);
+}
+
+// the frame's field, or the reason there is none to hand out: NULL + message
+static const int32_t* current_field(const dxv_ctx* c, const char* who)
+{
+    const Frame& f = c->frames[c->cur];
+    dxv_ctx* w = const_cast<dxv_ctx*>(c);                               // (the message is the one thing an accessor writes)
+    if (!f.distDim || !f.dist.p) { (void)fail(w, "%s: frame %u has no distance field yet (call dxv_distance first)", who, c->cur); return nullptr; }
+    if (!f.distCurrent) { (void)fail(w, "%s: frame %u was launched again since its distance field was made: the field is stale", who, c->cur); return nullptr; }
+    return f.dist.p;
+}
+
+const void* dxv_distance_device_ptr(const dxv_ctx* c) { return c ? current_field(c, "dxv_distance_device_ptr") : nullptr; }
+
+size_t dxv_distance_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame& f = c->frames[c->cur];
+    return f.distCurrent ? (size_t)f.distDim * f.distDim * f.distDim * sizeof(int32_t) : 0;
+}
+
+int dxv_distance_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c) return 1;
+    const int32_t* field = current_field(c, "dxv_distance_download");
+    if (!field) return 1;
+    const size_t want = dxv_distance_bytes(c);
+    if (!host || bytes != want) return fail(c, "dxv_distance_download: expected %zu bytes, got %zu", want, bytes);
+    if (dxv_sync(c)) return 1;
+    DXV_HIP(c, hipMemcpyAsync(host, field, bytes, hipMemcpyDeviceToHost, cur_stream(c)));
+    DXV_HIP(c, hipStreamSynchronize(cur_stream(c)));
+    return 0;
+}
+
+int dxv_distance_ms(dxv_ctx* c, float* ms)
+{
+    if (!c) return 1;
+    if (!ms) return fail(c, "dxv_distance_ms: ms is NULL");
+    *ms = cur_frame(c).dist_ms;
+    return 0;
 }
 
 int dxv_stream_wait_frame(dxv_ctx* c, void* hipStream)

@@ -10,6 +10,7 @@ from ._lib import DxvError, Stats, load_library
 
 MODE_REFERENCE, MODE_PARITY = 0, 1
 MODE_SURFACE, MODE_REFERENCE_SURFACE = 2, 3      # the conservative surface; the reference rule's solid with that shell (include/dxv.h)
+DIST_SQ_I32, DIST_F32 = 0, 1                     # formats of the distance field (include/dxv.h)
 DBG_SORTED_KEYS, DBG_NODES, DBG_TRI_POS, DBG_TRI_NRM, DBG_PARENTS, DBG_NODES32, DBG_NODES64, DBG_LIST_CELLS, DBG_LIST_ENTRIES, DBG_LIST_MIP = range(10)
 
 
@@ -44,6 +45,7 @@ class Voxelizer:
         self._frame = 0
         self._lasts = {}
         self._viewports = {}
+        self._dist_formats = {}
         # DXV_OPTIONS="key=value,...": options for every context of a process (A/B runs of the tools without touching them)
         import os
         for kv in filter(None, os.environ.get("DXV_OPTIONS", "").split(",")):
@@ -252,6 +254,43 @@ class Voxelizer:
         if writable:
             return self._lib.dxv_grid_device_ptr(self._ctx)
         return self._lib.dxv_grid_device_ptr_ro(self._ctx)
+
+    # ---- the distance field of the frame's grid ---------------------------------------------------
+    def DistanceField(self, format=DIST_F32, sync=True, frameIndex=None):
+        """The exact signed distance field of the selected frame's whole grid (dxv_distance / dxv_distance_async): negative inside,
+        voxel units, centre to centre.  format DIST_SQ_I32: int32 s * d2; DIST_F32: float32 s * sqrt(d2).  sync=True returns it as a
+        numpy array [N, N, N] (z, y, x); sync=False only enqueues it behind the frame's launch and returns True (distance_device_ptr,
+        Distance after a Sync)."""
+        if frameIndex is not None:
+            self.SetFrame(frameIndex)
+        if format not in (DIST_SQ_I32, DIST_F32):
+            raise DxvError(f"DistanceField: unknown format {format!r} (DIST_SQ_I32 = 0, DIST_F32 = 1)")
+        fn = self._lib.dxv_distance if sync else self._lib.dxv_distance_async
+        self._check(fn(self._ctx, int(format)))
+        self._dist_formats[self._frame] = int(format)
+        return self.Distance() if sync else True
+
+    def Distance(self):
+        """numpy copy of the selected frame's field (dxv_distance_download; synchronises the frame)."""
+        nbytes = self._lib.dxv_distance_bytes(self._ctx)
+        n = round((nbytes // 4) ** (1.0 / 3.0))
+        out = np.empty((n, n, n), np.float32 if self._dist_formats.get(self._frame) == DIST_F32 else np.int32)
+        self._check(self._lib.dxv_distance_download(self._ctx, out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+    def distance_device_ptr(self):
+        """Device pointer of the selected frame's field (dxv_distance_device_ptr), for consumers on the GPU; raises where the
+        library refuses (no field yet, or the frame was launched again since)."""
+        p = self._lib.dxv_distance_device_ptr(self._ctx)
+        if not p:
+            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
+        return p
+
+    def distance_ms(self):
+        """Device time of the selected frame's last field, read at the frame's Sync (dxv_distance_ms)."""
+        ms = C.c_float()
+        self._check(self._lib.dxv_distance_ms(self._ctx, C.byref(ms)))
+        return ms.value
 
     def grid_bytes(self):
         return self._lib.dxv_grid_bytes(self._ctx)

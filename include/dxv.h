@@ -186,7 +186,7 @@ DXV_API int dxv_sync(dxv_ctx* ctx);
  * frameIndex (static const uint8_t FrameCount, Content/Voxelizer.h:24; m_grids[FrameCount], :110;
  * Render(pCommandList, frameIndex, ...), :21-22; voxelize(pCommandList, frameIndex), Content/Voxelizer.cpp:351-356),
  * so that the GPU works on one grid while the host still reads another.  dxv_set_frame selects the frame the
- * following dxv_voxelize* / dxv_sync / dxv_grid_* / dxv_texels_download / dxv_render* / dxv_update_frame / dxv_get_stats calls refer to
+ * following dxv_voxelize* / dxv_sync / dxv_grid_* / dxv_texels_download / dxv_render* / dxv_update_frame / dxv_distance* / dxv_get_stats calls refer to
  * (default 0).  Each frame owns its grid, texel image, status words and -- frames 1 and 2 -- an internal stream,
  * so launches of different frames overlap on the GPU; scene, candidate lists and options are shared (an extra frame
  * costs its grid).  Calls that change what the frames read (dxv_set_mesh, dxv_build, dxv_scene_import, dxv_set_stream) first
@@ -301,6 +301,46 @@ DXV_API int dxv_render_async(dxv_ctx* ctx, void* device_rgba, size_t row_pitch);
  * (a consumer's stream; NULL = the null stream) wait ON THE DEVICE for everything enqueued on the selected frame so far (its
  * launch, its render).  Synchronises on the host first under the same rule as dxv_render_async. */
 DXV_API int dxv_stream_wait_frame(dxv_ctx* ctx, void* hip_stream);
+
+/* The exact signed distance field of the selected frame's grid, computed on the device (no reference counterpart, like the surface
+ * modes): what collision and clearance queries, offsetting, sphere tracing and level sets read next to the occupancy byte.  The input
+ * is the WHOLE grid of the frame's last launch, any mode; a voxel is solid iff its byte is non-zero.  For voxel p = (ix, iy, iz)
+ *     d2(p) = min over voxels q of the same grid with solid(q) != solid(p) of (px-qx)^2 + (py-qy)^2 + (pz-qz)^2     (integers)
+ *     s(p)  = -1 if solid(p) else +1
+ * One 4-byte element per voxel, same index as the grid (id = (iz*N + iy)*N + ix), in one of two formats.
+ * Distances are in voxel units, CENTRE TO CENTRE: a voxel next to the boundary has |d| = 1, none has 0.  A caller who places the
+ * boundary half-way between two voxels subtracts 0.5 from the magnitude of DXV_DIST_F32.  d2 <= 3 * 2047^2 < 2^24, so the
+ * conversion to float is exact and the correctly rounded square root makes DXV_DIST_F32 as reproducible as the integers. */
+enum {
+    DXV_DIST_SQ_I32 = 0,     /* int32   s(p) * d2(p);                no q exists (grid all empty / all solid): s(p) * 0x7fffffff */
+    DXV_DIST_F32 = 1         /* float32 s(p) * sqrtf((float)d2(p));  no q exists: s(p) * INFINITY                                */
+};
+/* dxv_distance_async -- ENQUEUED on the frame's stream behind the frame's last launch (and behind a render, if one is there);
+ * returns without waiting.  Errors of the launch come back from dxv_sync.
+ *  - The host waits only under dxv_render_async's rule: when the frame's last launch can still report something, the frame is
+ *    synchronised first; otherwise the call only enqueues.  A prepared static scene gets dxv_voxelize_async + dxv_distance_async
+ *    with no host round trip.
+ *  - Checked on the host before anything is enqueued, each an error with a message: the format is one of the two; the frame has been
+ *    launched; its last launch was the whole grid (a slab's or a share's field would need its neighbours' voxels).
+ *  - Field (4 * N^3 bytes) and scratch (6 * N^3 bytes: three separable passes, x by bit scans over packed rows, y and z by exact
+ *    lower envelopes of parabolas) belong to the frame: frames compute their fields side by side.  dxv_trim gives the scratch back.
+ *  - What the field describes is the grid as it is when the kernels run: a caller who wrote through dxv_grid_device_ptr gets the
+ *    field of what was written (ordering against the frame's stream is the caller's).
+ *  - Option events = 1 (default): the field is bracketed by the frame's own two events; dxv_distance_ms reads them.
+ * dxv_distance -- the same + dxv_sync. */
+DXV_API int dxv_distance_async(dxv_ctx* ctx, int format);
+DXV_API int dxv_distance(dxv_ctx* ctx, int format);
+/* The selected frame's field on the device (valid after dxv_sync or on the frame's stream; dxv_stream_wait_frame orders a consumer's
+ * stream behind it) and its size, 4 * N^3.  NULL / 0 before the frame's first field.  A field is STALE once its frame is launched
+ * again: the pointer, the size and the download then fail (NULL, 0, 1; message through dxv_last_error) rather than hand out the
+ * field of a grid that is gone. */
+DXV_API const void* dxv_distance_device_ptr(const dxv_ctx* ctx);
+DXV_API size_t dxv_distance_bytes(const dxv_ctx* ctx);
+/* Copy the field to the host (bytes must be dxv_distance_bytes); synchronises the frame first. */
+DXV_API int dxv_distance_download(dxv_ctx* ctx, void* host, size_t bytes);
+/* Device time of the selected frame's last field in milliseconds (its three kernels, HIP events), read at the frame's dxv_sync:
+ * 0 before that, and under option events = 0.  (A getter of its own: dxv_stats keeps its layout.) */
+DXV_API int dxv_distance_ms(dxv_ctx* ctx, float* ms);
 
 /* Multi-GPU: the built scene (nodes + triangle data) as one relocatable device blob, so that
  * rank 0 builds once and the host layer broadcasts it (RCCL over xGMI) to the other ranks.
@@ -457,7 +497,7 @@ DXV_API int dxv_debug_plan_check(dxv_ctx* ctx, uint64_t out[16]);
 
 /* Give back what the context keeps only to make the next build faster: the list build's scratch (up to 16 GiB per buffer
  * after a 10 M-triangle scene), the LBVH build's scratch when no refit can follow (imported scenes), the memory of prepared queues
- * whose lists are gone.  Nothing a launch reads. */
+ * whose lists are gone, the scratch of the frames' distance fields (the fields stay).  Nothing a launch reads. */
 DXV_API int dxv_trim(dxv_ctx* ctx);
 
 /* Test hook: copy an internal device array to the host (enum above). */

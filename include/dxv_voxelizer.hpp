@@ -153,6 +153,18 @@ public:
 	}
 	bool WaitFrameOn(uint8_t frameIndex, void* hipStream) { return SetFrame(frameIndex) && dxv_stream_wait_frame(m_ctx, hipStream) == 0; }
 
+	// The exact signed distance field of that frame's whole grid (dxv_distance_async: enqueued behind the frame's launch, 4 bytes per
+	// voxel, DXV_DIST_SQ_I32 or DXV_DIST_F32, negative inside, voxel units centre to centre).  DeviceDistance / DownloadDistance refer to
+	// the frame last selected; WaitFrame reports the kernels' errors.
+	bool DistanceField(uint8_t frameIndex, int format = DXV_DIST_F32) { return SetFrame(frameIndex) && dxv_distance_async(m_ctx, format) == 0; }
+	const void* DeviceDistance() const { return m_ctx ? dxv_distance_device_ptr(m_ctx) : nullptr; }
+	bool DownloadDistance(std::vector<uint8_t>& field)
+	{
+		if (!m_ctx) return setError("DownloadDistance before Init");
+		field.resize(dxv_distance_bytes(m_ctx));
+		return dxv_distance_download(m_ctx, field.data(), field.size()) == 0;
+	}
+
 	// Result: uint8 occupancy, x fastest, then y (top to bottom), then z.
 	bool Download(std::vector<uint8_t>& grid)
 	{
