@@ -199,6 +199,7 @@ struct dxv_ctx {
         RayCastCB cb{};                  // the ray-cast constants of the frame's last dxv_update_frame ...
         uint32_t cbWidth = 0, cbHeight = 0;   // ... and the viewport they were made for (0: none yet)
         DevBuf<uint8_t> empty;           // empty-brick flags of the frame's grid (empty_brick_bytes)
+        uint32_t emptyDim = 0;           // grid side of the frame's last render with flags (0: none yet; dxv_debug_download reads them)
         hipEvent_t evR0 = nullptr, evR1 = nullptr;   // around the frame's last render
         bool renderTimed = false;        // ... which was bracketed by them and not read yet (the frame's next dxv_sync reads it)
         float render_ms = 0.0f;

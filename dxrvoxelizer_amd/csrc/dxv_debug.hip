@@ -457,6 +457,7 @@ extern "C" int dxv_debug_download(dxv_ctx* c, int what, void* host, size_t bytes
     const void* src = nullptr;
     size_t want = 0;
     const size_t T = c->T;
+    hipStream_t s = c->stream;
     if (settle_lists(c)) return 1;
     if ((what == DXV_DBG_NODES || what == DXV_DBG_NODES32 || what == DXV_DBG_NODES64) && c->haveScene && ensure_nodes(c, c->stream)) return 1;
     switch (what) {
@@ -470,6 +471,17 @@ extern "C" int dxv_debug_download(dxv_ctx* c, int what, void* host, size_t bytes
     case DXV_DBG_LIST_CELLS: if (c->haveScene && c->lists.state == 1) { src = c->lists.cells.p; want = sizeof(DirCell) * 6 * (size_t)c->lists.res * c->lists.res; } break;
     case DXV_DBG_LIST_ENTRIES: if (c->haveScene && c->lists.state == 1) { src = c->lists.entries.p; want = sizeof(DirEntry) * (size_t)c->lists.count; } break;
     case DXV_DBG_LIST_MIP: if (c->haveScene && c->lists.state == 1 && c->lists.mip.p) { src = c->lists.mip.p; want = sizeof(uint16_t) * (size_t)dm_mip_words(c->lists.res); } break;
+    case DXV_DBG_BRICK_EMPTY:
+    case DXV_DBG_BRICK_SUMMARY: {                                       // (written on the frame's stream by its last render with flags: launch_raycast)
+        const Frame& f = cur_frame(c);
+        if (!f.emptyDim || !f.empty.p) return fail(c, "dxv_debug_download: frame %u has not been rendered with empty-brick flags (option skipempty = 1)", c->cur);
+        if (f.emptyDim != f.grid_dim) return fail(c, "dxv_debug_download: frame %u's flags are of a %u^3 grid, its grid is %u^3 now (render it again)", c->cur, f.emptyDim, f.grid_dim);
+        const size_t M = (f.emptyDim + kEmptyBrick - 1) / kEmptyBrick;
+        src = f.empty.p + (what == DXV_DBG_BRICK_SUMMARY ? empty_brick_bytes(f.emptyDim) / 2 : 0);      // (the summaries: the scratch's second half)
+        want = M * M * M;
+        s = cur_stream(c);
+        break;
+    }
 #if defined(DXV_QUEUE_TIMES)
     case 100: src = c->frames[c->cur].redo.p; want = sizeof(uint64_t) * kRedoCap; break;      // per-wave start / end ticks of the last queue launch
 #endif
@@ -478,7 +490,7 @@ extern "C" int dxv_debug_download(dxv_ctx* c, int what, void* host, size_t bytes
     if (!src) return fail(c, "dxv_debug_download: selector %d not available", what);
     if (bytes != want) return fail(c, "dxv_debug_download: expected %zu bytes, got %zu", want, bytes);
     DXV_HIP(c, hipSetDevice(c->device));
-    DXV_HIP(c, hipMemcpyAsync(host, src, bytes, hipMemcpyDeviceToHost, c->stream));
-    DXV_HIP(c, hipStreamSynchronize(c->stream));
+    DXV_HIP(c, hipMemcpyAsync(host, src, bytes, hipMemcpyDeviceToHost, s));
+    DXV_HIP(c, hipStreamSynchronize(s));
     return 0;
 }

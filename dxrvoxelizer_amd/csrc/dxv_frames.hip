@@ -604,6 +604,7 @@ int render_frame(dxv_ctx* c, const RayCastCB& cb, uint32_t width, uint32_t heigh
     DXV_HIP(c, launch_raycast(cb, f.grid.p, N, width, height, dst, pitch, c->opt.skipempty ? f.empty.p : nullptr, fs));
     if (timed) DXV_HIP(c, hipEventRecord(f.evR1, fs));
     DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    if (c->opt.skipempty) f.emptyDim = N;
     f.renderTimed = timed;
     return 0;
 }

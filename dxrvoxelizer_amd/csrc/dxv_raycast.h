@@ -87,6 +87,19 @@ DXV_HD bool compute_start_point(float pos[3], const float dir[3])
     return isHit;
 }
 
+// The ray of one pixel (PSRayCast.hlsl:124-127): pos = ScreenToLocal(float3(sspos.xy, 0)), dir = normalize(pos - eye)
+DXV_HD void pixel_ray(const RayCastCB& cb, float sx, float sy, float pos[3], float dir[3])
+{
+    const float* m = cb.screenToLocal;
+    // mul(float4(p, 1), M) then / w
+    const float hx = (sx * m[0] + sy * m[4]) + m[12], hy = (sx * m[1] + sy * m[5]) + m[13];
+    const float hz = (sx * m[2] + sy * m[6]) + m[14], hw = (sx * m[3] + sy * m[7]) + m[15];
+    pos[0] = hx / hw; pos[1] = hy / hw; pos[2] = hz / hw;
+    dir[0] = pos[0] - cb.eyePt[0]; dir[1] = pos[1] - cb.eyePt[1]; dir[2] = pos[2] - cb.eyePt[2];
+    const float dl = __builtin_sqrtf((dir[0] * dir[0] + dir[1] * dir[1]) + dir[2] * dir[2]);
+    dir[0] /= dl; dir[1] /= dl; dir[2] /= dl;
+}
+
 // One pixel, sspos = (px + 0.5, py + 0.5) (SV_POSITION).  rgba in [0,1] (PSRayCast.hlsl:118-187).
 DXV_HD void raycast_pixel(const RayCastCB& cb, const uint8_t* grid, uint32_t N, float sx, float sy, float rgba[4],
                           const uint8_t* empty = nullptr)
@@ -94,14 +107,8 @@ DXV_HD void raycast_pixel(const RayCastCB& cb, const uint8_t* grid, uint32_t N, 
     const float clear[3] = {0.0f, 0.2f, 0.4f};                                  // SharedConst.h:8
     const float maxDist = 2.0f * __builtin_sqrtf(3.0f);
     const float stepScale = maxDist / (float)kNumSamples, lightStepScale = maxDist / (float)kNumLightSamples;
-    const float* m = cb.screenToLocal;
-    // ScreenToLocal(float3(sspos.xy, 0)): mul(float4(p, 1), M) then / w
-    const float hx = (sx * m[0] + sy * m[4]) + m[12], hy = (sx * m[1] + sy * m[5]) + m[13];
-    const float hz = (sx * m[2] + sy * m[6]) + m[14], hw = (sx * m[3] + sy * m[7]) + m[15];
-    float pos[3] = {hx / hw, hy / hw, hz / hw};
-    float dir[3] = {pos[0] - cb.eyePt[0], pos[1] - cb.eyePt[1], pos[2] - cb.eyePt[2]};
-    const float dl = __builtin_sqrtf((dir[0] * dir[0] + dir[1] * dir[1]) + dir[2] * dir[2]);
-    dir[0] /= dl; dir[1] /= dl; dir[2] /= dl;
+    float pos[3], dir[3];
+    pixel_ray(cb, sx, sy, pos, dir);
     if (!compute_start_point(pos, dir)) { rgba[0] = clear[0]; rgba[1] = clear[1]; rgba[2] = clear[2]; rgba[3] = 0.0f; return; }
     const float step[3] = {dir[0] * stepScale, dir[1] * stepScale, dir[2] * stepScale};
     const float ll = __builtin_sqrtf((cb.lightPt[0] * cb.lightPt[0] + cb.lightPt[1] * cb.lightPt[1]) + cb.lightPt[2] * cb.lightPt[2]);

@@ -12,6 +12,7 @@ MODE_REFERENCE, MODE_PARITY = 0, 1
 MODE_SURFACE, MODE_REFERENCE_SURFACE = 2, 3      # the conservative surface; the reference rule's solid with that shell (include/dxv.h)
 DIST_SQ_I32, DIST_F32 = 0, 1                     # formats of the distance field (include/dxv.h)
 DBG_SORTED_KEYS, DBG_NODES, DBG_TRI_POS, DBG_TRI_NRM, DBG_PARENTS, DBG_NODES32, DBG_NODES64, DBG_LIST_CELLS, DBG_LIST_ENTRIES, DBG_LIST_MIP = range(10)
+DBG_BRICK_EMPTY, DBG_BRICK_SUMMARY = 10, 11         # the display pass's empty-brick flags and the summaries behind them
 
 
 def obj_load(path):
@@ -377,7 +378,8 @@ class Voxelizer:
                   DBG_PARENTS: ((2 * T - 1,), np.uint32), DBG_NODES32: ((st["num_nodes"], 8), np.uint32),
                   DBG_NODES64: ((st["num_nodes"], 16), np.uint32),
                   DBG_LIST_CELLS: ((6 * st["list_res"] ** 2, 4), np.uint32), DBG_LIST_ENTRIES: ((st["list_entries"], 4), np.uint32),
-                  DBG_LIST_MIP: ((sum(6 * (st["list_res"] >> l) ** 2 for l in range(max(st["list_res"], 1).bit_length())),), np.uint16)}
+                  DBG_LIST_MIP: ((sum(6 * (st["list_res"] >> l) ** 2 for l in range(max(st["list_res"], 1).bit_length())),), np.uint16),
+                  DBG_BRICK_EMPTY: (((st["grid_dim"] + 7) // 8,) * 3, np.uint8), DBG_BRICK_SUMMARY: (((st["grid_dim"] + 7) // 8,) * 3, np.uint8)}
         shape, dt = shapes[what]
         out = np.empty(shape, dt)
         self._check(self._lib.dxv_debug_download(self._ctx, what, out.ctypes.data_as(C.c_void_p), out.nbytes))

@@ -66,7 +66,12 @@ enum {
     DXV_DBG_NODES64 = 6,     /* max(T-1,1) x 64 B wide traversal nodes (up to 4 boxes each)   */
     DXV_DBG_LIST_CELLS = 7,  /* 6 R R x 16 B: begin, end, far radius of every texel's list       */
     DXV_DBG_LIST_ENTRIES = 8,/* stats.list_entries x 16 B entries of the direction-space lists  */
-    DXV_DBG_LIST_MIP = 9     /* max-mip of the texels' far radii: 16-bit words, levels R^2 .. 1 x 6 faces */
+    DXV_DBG_LIST_MIP = 9,    /* max-mip of the texels' far radii: 16-bit words, levels R^2 .. 1 x 6 faces */
+    /* The display pass's empty-brick flags of the selected frame's last render with option skipempty = 1, M = ceil(grid_dim / 8):
+     * refused when the frame has not been rendered with flags, or was launched at another grid size since. */
+    DXV_DBG_BRICK_EMPTY = 10,  /* M^3 bytes [bz][by][bx]: 1 where voxels [8b, 8b+8] per axis (clipped to the grid) are all 0 */
+    DXV_DBG_BRICK_SUMMARY = 11 /* M^3 bytes behind them: bit0 any voxel of the brick, bit1 any on its x=0 face, bit2 z=0 face,
+                                * bit3 x=0,z=0 edge, bit4 y=0 face, bit5 x=0,y=0 edge, bit6 y=0,z=0 edge, bit7 its corner voxel */
 };
 
 typedef struct dxv_stats {

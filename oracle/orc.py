@@ -179,6 +179,12 @@ def render(grid, bound, eye, view_proj, width, height, pos_scale=(0, 0, 0, 1), c
     if cb is not None:
         cbv = np.ascontiguousarray(np.concatenate([np.ravel(c) for c in cb]), np.float32)
         cbp = cbv.ctypes.data_as(C.c_void_p)
+    # orc_voxelize leaves OpenMP at one thread per processor of the machine; a render of a few hundred pixels on a box that may use a few
+    # of many then spends a tenth of a second starting threads.  The image does not depend on the thread count (one pixel, one thread).
+    n = usable_cores()
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit():
+        n = max(1, min(n, int(os.environ["OMP_NUM_THREADS"])))
+    lib().omp_set_num_threads(n)                                       # (libgomp's, through the oracle library that links it)
     rc = lib().orc_render(g.reshape(-1), g.shape[0], np.ascontiguousarray(bound, np.float32),
                           np.ascontiguousarray(pos_scale, np.float32), np.ascontiguousarray(eye, np.float32),
                           np.ascontiguousarray(view_proj, np.float32).reshape(-1), width, height, cbp, out.reshape(-1))

@@ -906,6 +906,38 @@ __attribute__((visibility("default"))) void hc_render(const uint8_t* grid, uint3
         }
 }
 
+// hc_render with the empty-brick flags a caller hands in (sample_alpha's lookup of them; M^3 bytes, M = ceil(N / 8))
+__attribute__((visibility("default"))) void hc_render_flags(const uint8_t* grid, uint32_t N, const float* cb22, uint32_t width,
+                                                            uint32_t height, const uint8_t* empty, uint8_t* rgba8)
+{
+    RayCastCB cb;
+    memcpy(cb.lightPt, cb22, 12); memcpy(cb.eyePt, cb22 + 3, 12); memcpy(cb.screenToLocal, cb22 + 6, 64);
+#pragma omp parallel for schedule(dynamic, 4)
+    for (int64_t py = 0; py < (int64_t)height; ++py)
+        for (uint32_t px = 0; px < width; ++px) {
+            float c[4];
+            raycast_pixel(cb, grid, N, (float)px + 0.5f, (float)py + 0.5f, c, empty);
+            for (int k = 0; k < 4; ++k) {
+                float v = c[k];
+                if (!(v > 0.0f)) v = 0.0f;
+                if (v > 1.0f) v = 1.0f;
+                rgba8[((size_t)py * width + px) * 4 + k] = (uint8_t)(v * 255.0f + 0.5f);
+            }
+        }
+}
+
+// the rays the march starts from: per pixel the near-plane point and the normalised direction (pixel_ray), 6 floats
+__attribute__((visibility("default"))) void hc_pixel_rays(const float* cb22, uint32_t width, uint32_t height, float* out6)
+{
+    RayCastCB cb;
+    memcpy(cb.lightPt, cb22, 12); memcpy(cb.eyePt, cb22 + 3, 12); memcpy(cb.screenToLocal, cb22 + 6, 64);
+    for (uint32_t py = 0; py < height; ++py)
+        for (uint32_t px = 0; px < width; ++px) {
+            float* o = out6 + ((size_t)py * width + px) * 6;
+            pixel_ray(cb, (float)px + 0.5f, (float)py + 0.5f, o, o + 3);
+        }
+}
+
 } // extern "C"
 
 // ---------------------------------------------------------------------------------------------

@@ -30,6 +30,18 @@ def test_library_exports_every_declared_symbol(dxvlib):
     assert sorted(_lib.SYMBOLS) == names          # the Python binding covers the whole header
 
 
+def test_debug_selectors_of_header_and_binding_agree():
+    """every DXV_DBG_* of include/dxv.h has its DBG_* in the Python binding with the same value (the display pass's empty-brick
+    flags and summaries among them)"""
+    from dxrvoxelizer_amd import voxelizer
+    text = open(os.path.join(ROOT, "include", "dxv.h")).read()
+    header = {name: int(val) for name, val in re.findall(r"\bDXV_DBG_(\w+)\s*=\s*(\d+)", text)}
+    assert len(header) == 12 and sorted(header.values()) == list(range(12))
+    assert {"BRICK_EMPTY", "BRICK_SUMMARY"} <= set(header)
+    for name, val in header.items():
+        assert getattr(voxelizer, "DBG_" + name) == val, name
+
+
 def test_every_option_the_library_takes_is_documented_in_the_header(hostcheck):
     """dxv_set_option's keys (the option table of csrc/dxv_policy.h, read through tests/hostcheck) against the list in include/dxv.h: a knob
     nobody can read about is a bug of the boundary."""

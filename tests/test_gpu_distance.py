@@ -11,6 +11,7 @@ import pytest
 
 import distance_restated as dr
 from conftest import GOLD, load_mesh
+from raycast_restated import write_grid
 from test_gpu_configs import make, sha
 
 pytestmark = pytest.mark.gpu
@@ -49,17 +50,6 @@ def test_field_of_mesh_grids_equals_restatement(dxv, name, N, modes):
             assert grid.any() and (want < 0).any() and (want > 0).any()
     finally:
         v.close()
-
-
-def write_grid(v, grid):
-    """overwrite the selected frame's grid through dxv_grid_device_ptr, the way tests/test_gpu_prepared.py poisons it"""
-    import torch
-    from dxrvoxelizer_amd.slabs import device_grid_tensor
-    v.Sync()
-    t = device_grid_tensor(v, "cuda")
-    assert t.numel() == grid.size
-    t.copy_(torch.from_numpy(np.ascontiguousarray(grid, np.uint8).reshape(-1)))
-    torch.cuda.synchronize()
 
 
 def arbitrary_grids(N):
