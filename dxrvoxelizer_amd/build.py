@@ -16,8 +16,8 @@ CSRC = os.path.join(HERE, "csrc")
 OBJDIR = os.path.join(HERE, "csrc", "build")
 LIB = os.path.join(HERE, "libdxv.so")
 
-SOURCES = ["dxv_api.hip", "dxv_lists.hip", "dxv_frames.hip", "dxv_blob.hip", "dxv_debug.hip", "lbvh.hip", "radix_sort.hip", "traverse.hip", "voxelize_lists.hip", "parity_rows.hip", "grid_utils.hip",
-           "raycast.hip", "dirmap.hip", "surface.hip", "distance.hip", "obj_ingest.cpp"]
+SOURCES = ["dxv_api.hip", "dxv_lists.hip", "dxv_frames.hip", "dxv_blob.hip", "dxv_debug.hip", "lbvh.hip", "radix_sort.hip", "traverse.hip", "plan_bricks.hip", "voxelize_lists.hip", "parity_rows.hip", "grid_utils.hip",
+           "raycast.hip", "dirmap.hip", "parity_lists.hip", "surface.hip", "distance.hip", "obj_ingest.cpp"]
 HEADERS = ["dxv_device.h", "dxv_math.h", "dxv_trace.h", "dxv_types.h", "dxv_raycast.h", "dxv_dirmap.h", "dxv_ctx.h", "dxv_policy.h", "dxv_surface.h", "dxv_brick.h", "dxv_distance.h", os.path.join("..", "..", "include", "dxv.h")]
 
 # -ffp-contract=off: the arithmetic of the path has a fixed operation order; the only fused
@@ -83,7 +83,7 @@ def build(force=False, save_temps=False, verbose=False, ablate=False, defines=()
 
 
 def kernel_resources(src="traverse"):
-    """{kernel name: {"vgprs": n, "scratch": bytes per lane, "lds": bytes, "occupancy": waves/SIMD}}
+    """{kernel name: {"vgprs": n, "sgprs": n, "scratch": bytes per lane, "lds": bytes, "occupancy": waves/SIMD}}
     from the compiler's resource remarks of the last build."""
     import re
     path = os.path.join(OBJDIR, src + ".usage")
@@ -95,7 +95,7 @@ def kernel_resources(src="traverse"):
             continue
         if cur is None:
             continue
-        for key, pat in (("vgprs", r" VGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
+        for key, pat in (("vgprs", r" VGPRs: (\d+)"), ("sgprs", r"TotalSGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
                          ("lds", r"LDS Size \[bytes/block\]: (\d+)"), ("occupancy", r"Occupancy \[waves/SIMD\]: (\d+)")):
             m = re.search(pat, line)
             if m:

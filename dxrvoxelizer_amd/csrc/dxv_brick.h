@@ -1,4 +1,4 @@
-// dxv_brick.h -- what the kernels over 4 x 4 x 4 bricks share on the device (traverse.hip, voxelize_lists.hip, dxv_debug.hip):
+// dxv_brick.h -- what the kernels over 4 x 4 x 4 bricks share on the device (traverse.hip, voxelize_lists.hip, plan_bricks.hip, dxv_debug.hip):
 // the launch order's brick numbering, lane -> voxel, and the brick's epilogue.
 #pragma once
 #include "dxv_device.h"
@@ -31,6 +31,15 @@ __device__ __forceinline__ void brick_of_lin(const VoxelizeParams& p, uint32_t l
     bx += p.bx0; by += p.by0; bz += p.bz0;
 }
 
+// The lane's number in its wave, asked for where it is wanted: the brick kernels ask again rather than keep it (or threadIdx.x) in a vector
+// register through a brick's body (store_brick).
+__device__ __forceinline__ uint32_t lane_id()
+{
+    uint32_t lane;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+    return lane;
+}
+
 // lane -> voxel of brick (bx, by, bz): local coordinates, lz the local slice
 __device__ __forceinline__ void brick_voxel(uint32_t bx, uint32_t by, uint32_t bz, uint32_t lane, uint32_t& ix, uint32_t& iy, uint32_t& lz)
 {
@@ -44,7 +53,7 @@ __device__ __forceinline__ void brick_voxel_clamped(uint32_t N, uint32_t nz, uin
 }
 
 // The epilogue of the two brick kernels (k_voxelize_queue, k_voxelize_listed): the lane's texel, and the brick's 64 result bytes as
-// 16 dwords.  `lane` is asked for again BEHIND the body by the caller (v_mbcnt): nothing of the lane's voxel is kept in vector
+// 16 dwords.  `lane` is asked for again BEHIND the body by the caller (lane_id): nothing of the lane's voxel is kept in vector
 // registers through the scan and the triangle tests -- held across them the coordinates cost a wave per SIMD.
 // p: pointer to the launch's VoxelizeParams, wherever the kernel keeps them (k_voxelize_queue: the kernel-argument segment) -- the texel
 // image's address is asked for where it is used, not in front of the branch.

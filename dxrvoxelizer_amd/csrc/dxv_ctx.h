@@ -98,7 +98,7 @@ struct Lists {
         return e;
     }
 };
-// row lists of the parity rule (dirmap.hip): built like the direction-space lists, on a scene's second parity launch or on
+// row lists of the parity rule (parity_lists.hip): built like the direction-space lists, on a scene's second parity launch or on
 // a large first one; an importing context adopts the ones in the blob or builds its own from the triangle records (0.2 ms)
 struct RowLists {
     DevBuf<uint32_t> cells, entries;
@@ -182,7 +182,7 @@ struct dxv_ctx {
         uint32_t grid_dim = 0, z0 = 0, nz = 0, stack_entries = 0, redo_rays = 0, row_block = 0, list_entries = 0, list_res = 0;
         uint32_t plan_bricks = 0, plan_waves = 0;
         float plan_ms = 0.0f;
-        // work queue of the lists kernel (voxelize_lists.hip): the frame's own, written and read on the frame's stream only
+        // work queue of the lists kernel (plan_bricks.hip): the frame's own, written and read on the frame's stream only
         DevBuf<uint32_t> queue;          // two headers, then the slots (dxv_device.h); cap: 32-bit words
         uint32_t queueHdr = 0;           // the header (0 / 1) of the frame's current queue; the next build takes the other one ...
         bool queueOtherClear = false;    // ... which is all zero (cleared at the allocation, then by every build's k_plan_bricks)

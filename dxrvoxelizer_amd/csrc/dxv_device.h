@@ -66,12 +66,16 @@ hipError_t dirmap_far(const TriPos* triPos, uint32_t T, uint32_t R, uint32_t* fa
 // out[1] = entries whose triangle slot is >= T
 hipError_t dirmap_validate(const DirCell* cells, uint32_t R, const DirEntry* entries, uint32_t n, uint32_t T, uint32_t* out, hipStream_t s);
 
+// offsets[0 .. n) = exclusive scan of counts[0 .. n); sums: ceil(n / 1024) words of scratch
+hipError_t scan_exclusive(const uint32_t* counts, uint32_t n, uint32_t* sums, uint32_t* offsets, hipStream_t s);
+
+// parity_lists.hip -- row lists of the parity rule (pl_rect, dxv_dirmap.h); validate: as dirmap_validate
 hipError_t parity_lists_validate(const uint32_t* cells, uint32_t R, const uint32_t* entries, uint32_t n, uint32_t T, uint32_t* out, hipStream_t s);
 hipError_t parity_lists_total(const TriPos* triPos, uint32_t T, uint32_t R, unsigned long long* total, hipStream_t s);
 hipError_t parity_lists_fill(const TriPos* triPos, uint32_t T, uint32_t R, uint32_t* counts, uint32_t* offsets, uint32_t* sums, uint32_t* cells,
                              uint32_t* entries, hipStream_t s);
 
-// traverse.hip / voxelize_lists.hip / parity_rows.hip -- one launch of a ray rule over a partition
+// traverse.hip / plan_bricks.hip / voxelize_lists.hip / parity_rows.hip -- one launch of a ray rule over a partition
 struct VoxelizeParams {
     SceneView scene;
     uint8_t* grid;          // N*N*nz bytes
@@ -97,7 +101,7 @@ struct VoxelizeParams {
     uint32_t lists;         // 1: reference rule reads the direction-space lists of p.scene (no tree walk)
     uint64_t* clearSig;     // host word of the frame (or NULL): signature of the partial launch whose memset the grid still carries -- the same launch again skips the memset
     uint32_t ablate;        // timing-only builds of the lists kernel (wrong grids; tools/ablate.py), 0 = the real kernel
-    uint32_t* queue;        // work queue of the lists kernel (voxelize_lists.hip): the header this launch uses (64 heads, 8 lengths, every word in a line of its own)
+    uint32_t* queue;        // work queue of the lists kernel (plan_bricks.hip): the header this launch uses (64 heads, 8 lengths, every word in a line of its own)
     uint32_t* queueSlots;   // ... its 8 x queueCap brick words
     uint32_t* queueZero;    // ... the frame's OTHER header, cleared by k_plan_bricks for the launch that builds the next queue (or NULL)
     uint32_t queueCap;
@@ -123,7 +127,7 @@ int stack_round_up(int want);
 int stack_for_brick(int brickShape, int want);   // the column depth compiled for this brick shape that is >= want
 int num_brick_shapes();
 
-// voxelize_lists.hip -- the work queue of the lists kernel and the two brick kernels
+// plan_bricks.hip -- the work queue of the lists kernel
 // header of a queue: 64 heads (eight per queue: head h of queue x hands out the slots k = h mod 8 of that queue; head
 // number 8 x + h), then the eight lengths, every word in a 256-byte line of its own.  Queue memory of a frame: TWO headers, then
 // the slots: a launch that builds a queue takes the header the last build did not use -- all zero, because that build's
@@ -143,6 +147,9 @@ uint32_t plan_layout(VoxelizeParams& p);           // fills the brick-order fiel
 uint32_t plan_region_bits(uint32_t N, uint32_t nz); // the run length (log2 bricks) a partition of this size deals to its queues
 size_t plan_queue_words(uint32_t N, uint32_t nz, uint32_t* capOut);     // 32-bit words of queue memory for a partition; *capOut = words per XCD queue
 hipError_t plan_build(const VoxelizeParams& p, hipStream_t s);          // k_plan_bricks into the (zero) header p.queue; p.queueSlots, p.queueCap, p.mip set
+size_t plan_live_words(uint32_t N, uint32_t nz);   // 32-bit words of a partition's brick mask
+hipError_t plan_clear_grid(const VoxelizeParams& p, hipStream_t s);     // zeros the partition's grid (and texel image): the clear of k_plan_bricks as a kernel of its own
+// voxelize_lists.hip -- the two brick kernels that run the queue
 // rebuild: grid cleared + queue built in front of the kernel; else only the queue heads are reset (same launch as before into the same buffers)
 // (planEvents: two events recorded around the queue build of a rebuilding launch, or NULL)
 // listedLens: the eight lengths of a kept queue and how many of each are heavy (16 words) as the host last read them (one workgroup per item, dealt out by the hardware), or NULL (persistent waves)
@@ -160,7 +167,6 @@ hipError_t launch_voxelize_queue(const VoxelizeParams& p, ListsOccupancy& occ, b
 //             bricks that are not queued (every voxel is written once per launch, by the brick that owns it or by the clear; needs
 //             N % 16 == 0).
 hipError_t launch_voxelize_prepared(const VoxelizeParams& p, ListsOccupancy& occ, const uint32_t lens[16], const uint32_t* live, int clearMode, uint32_t* wavesOut, hipStream_t s);
-size_t plan_live_words(uint32_t N, uint32_t nz);   // 32-bit words of a partition's brick mask
 
 // parity_rows.hip
 hipError_t launch_parity_rows(const VoxelizeParams& p, int rowBlock, hipStream_t s);   // parity mode: one walk per row run (1) or per 2 x 2 rows (2)

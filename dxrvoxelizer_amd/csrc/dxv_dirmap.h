@@ -207,7 +207,7 @@ DXV_HD DirRayStart dm_ray_start(float ox, float oy, float oz, const DirMapView& 
 
 // ---------------------------------------------------------------------------------------------
 // Max-mip of the texels' far radii: which 4 x 4 x 4-voxel bricks can hold a live ray at all (the launch's work queue,
-// k_plan_bricks in voxelize_lists.hip).  Key of a texel = its r1max as half bits (positive halfs order like integers), 0 for an
+// k_plan_bricks in plan_bricks.hip).  Key of a texel = its r1max as half bits (positive halfs order like integers), 0 for an
 // empty texel; level l holds, for 6 faces of (R >> l)^2 cells, the maximum over the 2^l x 2^l texels below a cell.
 // Built from the cells (dirmap.hip: dirmap_mip), never exported: a function of the cells alone.
 // ---------------------------------------------------------------------------------------------
@@ -953,7 +953,7 @@ DXV_HD void trace_reference_dm_from(Ray& r, const DirMapView& dm, const DirRaySt
     DXV_PHASE_END();
 }
 
-// Row lists of the parity rule (dirmap.hip): the texels of the R x R grid over the (y, z) plane that a triangle's padded box --
+// Row lists of the parity rule (parity_lists.hip): the texels of the R x R grid over the (y, z) plane that a triangle's padded box --
 // the box parity_row_setup tests a row against -- reaches; a row's texel is (dm_texel(oy), dm_texel(oz)), monotone in the
 // coordinate, so a row inside the box lies in a texel of the rectangle.
 DXV_HD void pl_rect(const TriPos& tp, uint32_t R, uint32_t& j0, uint32_t& j1, uint32_t& k0, uint32_t& k1)

@@ -187,7 +187,7 @@ static int build_lists_into(dxv_ctx* c, Lists& l, hipStream_t stream, uint64_t f
     return defer ? 0 : settle(c, l);
 }
 
-// Row lists of the parity rule (dirmap.hip).  Resolution: the finest grid, from 512 (below 20 k triangles), 2048 (up to 3 M) or
+// Row lists of the parity rule (parity_lists.hip).  Resolution: the finest grid, from 512 (below 20 k triangles), 2048 (up to 3 M) or
 // 4096 texels per side downwards, whose lists stay within 24 entries per triangle + 8 M (an entry is 4 bytes; measured at
 // 512^3, 1 M triangles: 256 -> 0.62 ms, 512 -> 0.34, 1024 -> 0.24, 2048 -> 0.20; the walk over the tree: 0.65); scenes over that
 // cap on every grid (big triangles cover many texels) or with more than 256 entries per texel keep the tree walk

@@ -639,7 +639,7 @@ struct SceneView {
     const void* dmEntries;
     uint32_t dmR;
     uint32_t dmCoop;        // 1: a lone lane's long list is scanned by its whole wave (trace_reference_dm_from; option coop)
-    const uint32_t* plCells;    // row lists of the parity rule (dirmap.hip): (begin, count) per texel of the plR x plR grid over (y, z); NULL: none
+    const uint32_t* plCells;    // row lists of the parity rule (parity_lists.hip): (begin, count) per texel of the plR x plR grid over (y, z); NULL: none
     const uint32_t* plEntries;  // triangle slots
     uint32_t plR;
 };

@@ -82,7 +82,7 @@ struct SceneHeader {
     // the ranks that import the scene need not build them again.  0 / 0 when the blob carries none.
     uint64_t offListCells, offListEntries;
     uint32_t listRes, listCount;
-    // ... and the row lists of the parity rule (dirmap.hip): plRes x plRes cells of (begin, count), plCount triangle slots
+    // ... and the row lists of the parity rule (parity_lists.hip): plRes x plRes cells of (begin, count), plCount triangle slots
     uint64_t offPlCells, offPlEntries;
     uint32_t plRes, plCount;
     uint32_t pad[14];

@@ -44,7 +44,7 @@ struct WaveStack {
 // might cross) -- the launcher decides by the mean triangle extent.
 // WIDE: the walk takes the four-box nodes (Node64) -- half as many dependent scalar fetches, which is
 // what the walk waits on (triangle arithmetic is 6 % of the kernel).
-// LISTS (RB = 1): the candidates of a row come from the row lists of the parity rule (dirmap.hip) -- one cell, then the
+// LISTS (RB = 1): the candidates of a row come from the row lists of the parity rule (parity_lists.hip) -- one cell, then the
 // triangles of its list four at a time -- instead of from a walk of the tree.
 template <int CH, int RB, bool WIDE, bool LISTS = false>
 __global__ __launch_bounds__(64, RB == 1 ? 8 : 6) void k_parity_rows(VoxelizeParams p)   // <= 64 / 80 VGPRs

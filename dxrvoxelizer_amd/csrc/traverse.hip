@@ -12,7 +12,7 @@
 // (stack[entry][thread]: consecutive lanes hit consecutive banks); a ray that runs out of it is
 // listed and finished by k_voxelize_redo with a deep column, never ignored (dxv_api.hip).
 // Parity mode normally runs k_parity_rows (one wave-uniform walk per block of grid rows, parity_rows.hip); the reference rule's
-// default path is the work queue and the two brick kernels of voxelize_lists.hip.
+// default path is the work queue (plan_bricks.hip) and the two brick kernels of voxelize_lists.hip.
 #include "dxv_brick.h"
 #include "dxv_dirmap.h"
 

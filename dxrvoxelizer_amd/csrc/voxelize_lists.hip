@@ -1,6 +1,7 @@
-// voxelize_lists.hip -- the reference rule through the direction-space lists: the work queue of live 4 x 4 x 4 bricks and the two
-// brick kernels that run it (k_voxelize_queue: persistent waves; k_voxelize_listed: one workgroup per queued brick) -- the
-// product's hot path.  The same brick body over a brick box, without a queue: k_voxelize<..., WALK 4>, traverse.hip.
+// voxelize_lists.hip -- the reference rule through the direction-space lists: the two brick kernels that run the work queue of live
+// 4 x 4 x 4 bricks (k_voxelize_queue: persistent waves; k_voxelize_listed: one workgroup per queued brick) -- the product's hot path --
+// and the equal shares they take of it.  The queue itself and how it is built: plan_bricks.hip.  The same brick body over a brick box,
+// without a queue: k_voxelize<..., WALK 4>, traverse.hip.
 #include "dxv_brick.h"
 #include "dxv_dirmap.h"
 #include <algorithm>
@@ -8,161 +9,7 @@
 
 namespace dxv {
 
-// ---------------------------------------------------------------------------------------------
-// Work queue of the lists kernel (4 x 4 x 4 bricks): WHICH bricks a launch runs, decided on the device inside the stream.
-//  * which: a ray that starts beyond the last entry of its texel (or whose texel is empty, or whose origin has left the
-//    root box) is a miss after one load -- on torus-1M four waves in ten of a launch over the brick box held no other
-//    ray.  k_plan_bricks decides per BRICK, conservatively (dm_box_may_be_live, dxv_dirmap.h: the brick's footprint in
-//    direction space and its smallest start radius against a max-mip of the texels' far radii; a false positive costs a
-//    wave that finds nothing, a false negative cannot happen -- k_plan_check, dxv_debug.hip, is the exhaustive proof obligation);
-//  * layout: regions of 256 consecutive bricks of the Morton order (8 x 8 x 4 bricks) are dealt round-robin to eight
-//    queues, one per XCD (blocks b and b + 8 share one), so that an XCD's private L2 sees compact regions; a region's
-//    workgroup appends its live bricks to its queue with one atomic add (small partitions: runs of 128 bricks, one add per
-//    wave -- k_plan_bricks).  Queue memory (dxv_device.h): two headers -- eight heads per queue and the eight lengths, every
-//    word in a 256-byte line of its own; a build takes the one the last build left cleared -- and 8 x cap brick words
-//    (bx | by << 10 | bz << 20);
-//  * how: k_voxelize_queue is launched with as many single-wave workgroups as the GPU holds at once.  Every wave takes its
-//    bricks one at a time from a head of its XCD's queue with a returning atomic add, asked for one brick ahead.  Which
-//    XCD a block really runs on is a matter of speed only: every head of every queue has its home waves by block number.
-//    No host round trip: the launch's size does not depend on how many bricks are live.
-//  * order: as built -- Morton order, regions dealt round-robin.  Measured and dropped (profiles/r04/ab_queue_*): dealing finer or to
-//    the shortest queue; a second queue per XCD, run last, for the bricks near or across the outer end of their lists (three
-//    definitions); and, for queues that are launched again, orders made on the device from MEASURED times -- the cheapest chunks of
-//    64 slots last (-3 % of a rank's share, +1 % on a whole grid), all chunks by cost (-6 % / +4 %), the bricks that took over three
-//    times the mean first and the shortest last (nothing): none earns a second copy of the queue.
-// Bricks that are not queued are zero because k_plan_bricks clears the partition's grid while it builds the queue.
-// ---------------------------------------------------------------------------------------------
 [[maybe_unused]] constexpr uint32_t kQueueNoPrefetch = 1024u;
-constexpr uint32_t kPlanRegionBits = 8u;                               // regions of 256 consecutive bricks = one workgroup of k_plan_bricks
-// (header layout: queue_len_word / queue_head_word in dxv_device.h -- every queue's two words in a 256-byte line of its own:
-// returning atomics on ONE line serialise at ~90 per us for all eight queues together, 2.7 ms of a launch when first tried)
-
-// The launch's zeros travel with the queue build: workgroup b clears the b-th share of the grid (and of the texel image) with
-// 16-byte stores while its threads wait for their four mip words -- one kernel in front of the brick kernel instead of a memset
-// of the grid, a memset of the header and this one (three dependent dispatches: ~5 us each on top of their own time).
-// Block 0 clears the frame's other header for the launch that builds the next queue.
-__device__ __forceinline__ void plan_clear(uint8_t* base, size_t bytes, uint32_t nblocks)
-{
-    const size_t chunk = (((bytes + nblocks - 1u) / nblocks) + 15u) & ~(size_t)15u;
-    const size_t lo = (size_t)blockIdx.x * chunk;
-    if (lo >= bytes) return;
-    const size_t hi = lo + chunk < bytes ? lo + chunk : bytes, full = lo + ((hi - lo) & ~(size_t)15u);
-    // (non-temporal stores: 134 MB of zeros that nobody reads before the brick kernel has overwritten a fifth of them should not push
-    // the lists out of the L2s and the memory-side cache on their way -- plain stores: the queue build 0.0375 instead of 0.0328 ms and
-    // the brick kernel behind it 0.681 instead of 0.666, profiles/r05/ab_nontemporal_grid_stores.jsonl)
-    typedef uint32_t Zero4 __attribute__((ext_vector_type(4)));
-    const Zero4 z = {0u, 0u, 0u, 0u};
-    for (size_t o = lo + 16u * threadIdx.x; o < full; o += 16u * 256u) __builtin_nontemporal_store(z, reinterpret_cast<Zero4*>(base + o));
-    if (full + threadIdx.x < hi) base[full + threadIdx.x] = 0;           // (a grid whose bytes are no multiple of 16: the last block's tail)
-}
-
-__global__ __launch_bounds__(256) void k_plan_bricks(VoxelizeParams p, uint32_t nb)
-{
-    __shared__ uint32_t heavyCount[4], lightCount[4], heavyBase[4], lightBase[4];
-    const uint32_t lin = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    bool live = false;
-    uint32_t bx = 0, by = 0, bz = 0;
-    float x0 = 0.0f, x1 = 0.0f, y0 = 0.0f, y1 = 0.0f, z0 = 0.0f, z1 = 0.0f;    // the brick's hull: for `live` here, for `heavy` below
-    if (lin < nb) {
-        brick_of_lin(p, lin, bx, by, bz);
-        dm_brick_hull(p.N, p.nz, p.z0, p.zBlock, p.zShift, p.zPeriod, bx, by, bz, x0, x1, y0, y1, z0, z1);
-        live = dm_box_may_be_live(x0, x1, y0, y1, z0, z1, p.scene.rootLo, p.scene.rootHi, p.mip, p.scene.dmR);
-    }
-    if (p.planClear) {
-        plan_clear(p.grid, (size_t)p.N * p.N * p.nz, gridDim.x);
-        if (p.texels) plan_clear(reinterpret_cast<uint8_t*>(p.texels), (size_t)p.N * p.N * p.nz * 4u, gridDim.x);
-    }
-    if (p.queueZero && blockIdx.x == 0u)
-        for (uint32_t k = threadIdx.x; k < kQueueHeaderWords; k += 256u) p.queueZero[k] = 0u;
-    // heavy: one of the brick's rays can look into a list that is long for this scene (one and a half times the mean of the count
-    // mip at the level of a brick's patch of texels: k_dm_heavy_thresholds) -- 2 - 6 % of the queued bricks, among them 99 % of those
-    // that take three times the mean and more (profiles/r05/brick_features.jsonl)
-    bool heavy = false;
-    if (live) {
-        const uint16_t* countMip = p.mip + dm_mip_words(p.scene.dmR);
-        // (maps too small to have such a level -- R < 8 -- have no word: no brick is heavy there)
-        const uint32_t longList = p.planHeavy ? p.planHeavy : dm_mip_levels(p.scene.dmR) > kDmHeavyLevelMin ? countMip[dm_mip_words(p.scene.dmR) + dm_heavy_level(p.scene.dmR, p.N)] : 0xffffu;
-        heavy = dm_box_max_count(x0, x1, y0, y1, z0, z1, countMip, p.scene.dmR) > longList;
-    }
-    const unsigned long long mh = __ballot(live && heavy), ml = __ballot(live && !heavy);
-    if (lane == 0u) { heavyCount[w] = (uint32_t)__builtin_popcountll(mh); lightCount[w] = (uint32_t)__builtin_popcountll(ml); }
-    __syncthreads();
-    // Runs of 2^planRegionBits consecutive Morton bricks go to one queue, the runs dealt round-robin: 256 (8 x 8 x 4 bricks, the whole
-    // workgroup: an XCD's L2 sees compact pieces of the grid), 128 or 64 (one wave each).
-    const uint32_t wavesPerRun = 1u << (p.planRegionBits - 6u), first = w & ~(wavesPerRun - 1u);
-    const uint32_t x = (lin >> p.planRegionBits) & 7u;
-    if (lane == 0u && w == first) {
-        uint32_t nh = 0, nl = 0;
-        for (uint32_t k = 0; k < wavesPerRun; ++k) { nh += heavyCount[first + k]; nl += lightCount[first + k]; }
-        heavyBase[first] = nh ? atomicAdd(p.queue + queue_heavy_word(x), nh) : 0u;
-        lightBase[first] = nl ? atomicAdd(p.queue + queue_len_word(x), nl) : 0u;
-    }
-    __syncthreads();
-    if (!live) return;
-    const unsigned long long before = (1ull << lane) - 1ull;
-    uint32_t rank = (uint32_t)__builtin_popcountll((heavy ? mh : ml) & before);
-    for (uint32_t k = first; k < w; ++k) rank += heavy ? heavyCount[k] : lightCount[k];
-    // (heavy bricks from slot 0 upwards, the others from the far end downwards: queue_slot)
-    const uint32_t slot = heavy ? heavyBase[first] + rank : p.queueCap - 1u - (lightBase[first] + rank);
-    p.queueSlots[(size_t)x * p.queueCap + slot] = bx | (by << 10) | (bz << 20);
-    if (p.liveMask) {                                                   // (a queue that is being prepared: the bit the launches' clear reads)
-        const uint32_t nbx = (p.N + 3u) / 4u, id = (bz * nbx + by) * nbx + bx;
-        atomicOr(p.liveMask + (id >> 5), 1u << (id & 31u));
-    }
-}
-size_t plan_live_words(uint32_t N, uint32_t nz)
-{
-    const uint64_t nbx = (N + 3u) / 4u, nbz = (nz + 3u) / 4u;
-    return (size_t)((nbx * nbx * nbz + 31u) / 32u) + 4u;
-}
-
-// the brick order of the whole partition (no brick box): what k_plan_bricks, the checker and the host agree on
-uint32_t plan_layout(VoxelizeParams& p)
-{
-    const uint32_t nbx = (p.N + 3u) / 4u, nby = nbx, nbz = (p.nz + 3u) / 4u;
-    p.nbx = nbx; p.nby = nby; p.nbz = nbz;
-    p.bx0 = p.by0 = p.bz0 = 0;
-    uint32_t m = 0;
-    while (m < 10 && !((nbx >> m) & 1u) && !((nby >> m) & 1u) && !((nbz >> m) & 1u)) ++m;
-    p.mortonBits = m;
-    p.superX = nbx >> m;
-    p.superY = nby >> m;
-    return nbx * nby * nbz;
-}
-// Run length by partition size.  Large partitions: 256 bricks (an XCD's L2 sees compact pieces of the grid, and with thousands of
-// runs per queue the eight queues end within 2 % of each other).  Small ones -- a 256^3 grid, a rank's share of 512^3 at 4 ranks
-// or more: 2^19 bricks or fewer -- take shorter runs: a queue of a few hundred runs of very different cost ends 10 - 20 % away
-// from its neighbours, and the launch ends with the longest.  (Runs of 64 until round 6; since every XCD runs an equal share of all
-// eight queues -- queue_item -- their imbalance matters less than an XCD's locality: 128 is -3 % at 256^3 and -2 ... -3 % on a
-// rank's share of the 1 M-triangle meshes at 512^3, +1.5 % on dragon x9's: profiles/r06/ab_planregion_at_eight_waves.jsonl.)
-uint32_t plan_region_bits(uint32_t N, uint32_t nz)
-{
-    const uint64_t nb = (uint64_t)((N + 3u) / 4u) * ((N + 3u) / 4u) * ((nz + 3u) / 4u);
-    return nb <= (1ull << 19) ? 7u : kPlanRegionBits;
-}
-// words of queue memory a partition needs (two headers + eight queues, each able to hold every run dealt to it in full, whatever
-// the run length)
-size_t plan_queue_words(uint32_t N, uint32_t nz, uint32_t* capOut)
-{
-    const uint64_t nb = (uint64_t)((N + 3u) / 4u) * ((N + 3u) / 4u) * ((nz + 3u) / 4u);
-    uint64_t cap = 0;
-    for (uint32_t rb = 6u; rb <= kPlanRegionBits; ++rb) {
-        const uint64_t runs = (nb + (1u << rb) - 1u) >> rb, c = ((runs + 7u) / 8u) << rb;
-        if (c > cap) cap = c;
-    }
-    if (capOut) *capOut = (uint32_t)cap;
-    return kQueueSlotsAt + 8u * (size_t)cap;
-}
-
-// one workgroup per 256 bricks into the header p.queue, which the caller vouches is all zero; p.queueSlots / p.queueCap / p.mip set by the caller
-hipError_t plan_build(const VoxelizeParams& pin, hipStream_t s)
-{
-    VoxelizeParams p = pin;
-    const uint32_t nb = plan_layout(p), nr = (nb + (1u << kPlanRegionBits) - 1u) >> kPlanRegionBits;
-    if (p.planRegionBits < 6u || p.planRegionBits > kPlanRegionBits) p.planRegionBits = kPlanRegionBits;
-    k_plan_bricks<<<dim3(nr), dim3(256), 0, s>>>(p, nb);
-    return hipGetLastError();
-}
 
 // ---------------------------------------------------------------------------------------------
 // Eight queues of unequal length, eight XCDs of equal appetite.  Runs of bricks are dealt to the queues by their number, not by
@@ -190,8 +37,7 @@ __device__ __forceinline__ uint32_t prefix8(uint32_t v)                 // inclu
 }
 __device__ __forceinline__ uint32_t queue_lens(const uint32_t* hdr, uint32_t& T, uint32_t& H)   // lane a < 8: items of queue a, of which H heavy; T = ceil(total / 8)
 {
-    uint32_t lane;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+    const uint32_t lane = lane_id();
     H = lane < 8u ? hdr[queue_heavy_word(0) + 64u * lane] : 0u;
     const uint32_t L = lane < 8u ? hdr[queue_len_word(0) + 64u * lane] + H : 0u;
     T = ((uint32_t)__builtin_amdgcn_readlane((int)prefix8(L), 7) + 7u) >> 3;
@@ -200,11 +46,11 @@ __device__ __forceinline__ uint32_t queue_lens(const uint32_t* hdr, uint32_t& T,
 // item j (< T) of XCD x: queue and slot; false: none (the last few of the 8 T items when the total is no multiple of 8)
 __device__ __forceinline__ bool queue_item(const uint32_t* hdr, uint32_t cap, uint32_t x, uint32_t j, uint32_t& y, uint32_t& slot)
 {
-    uint32_t T, H, lane, k;
+    uint32_t T, H, k;
     const uint32_t L = queue_lens(hdr, T, H), lenX = (uint32_t)__builtin_amdgcn_readlane((int)L, (int)x);
     if (j < lenX) { y = x; k = j; }                             // (j < T: one of the queue's own first T)
     else {
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+        const uint32_t lane = lane_id();
         const uint32_t spare = lane < 8u && L < T ? T - L : 0u, extra = L > T ? L - T : 0u;
         const uint32_t spareBefore = prefix8(spare) - spare, extraBefore = prefix8(extra) - extra;
         // the (j - len_x)-th slot this XCD has to spare, counted behind the spare slots of the XCDs 0 .. x - 1, is given the g-th
@@ -338,12 +184,12 @@ __global__ __launch_bounds__(64, 6) void k_voxelize_queue(VoxelizeParams p)
             sc.dmCells = pp->scene.dmCells; sc.dmEntries = pp->scene.dmEntries; sc.dmR = pp->scene.dmR; sc.dmCoop = pp->scene.dmCoop;
 #pragma unroll
             for (int a = 0; a < 3; ++a) { sc.rootLo[a] = pp->scene.rootLo[a]; sc.rootHi[a] = pp->scene.rootHi[a]; }
+            // (the brick's set-up, down to origin_leaves_root: written out once more in k_voxelize_listed -- one helper for both changes both kernels' instruction streams)
             const uint32_t N = pp->N, nz = pp->nz;
             const uint32_t bx = w & 1023u, by = (w >> 10) & 1023u, bz = w >> 20;
             // (the lane number anew for every brick, and once more behind the body: nothing of the loop lives in vector registers
             // through the body)
-            uint32_t tid;
-            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(tid));
+            uint32_t tid = lane_id();
             uint32_t ix, iy, lz;
             brick_voxel_clamped(N, nz, bx, by, bz, tid, ix, iy, lz);
             // (global_slice, dxv_math.h, written out: called with these operands the helper leaves this kernel one instruction with its operands
@@ -386,7 +232,7 @@ __global__ __launch_bounds__(64, 6) void k_voxelize_queue(VoxelizeParams p)
             uint32_t texel = 0;
             const uint8_t occ = TEXELS ? shade_reference<4, 0>(sc, r, best, bestDet, &texel) : shade_reference_again(sc, r, best.leaf);
             // the lane's voxel once more (nothing of it was kept through the body: store_brick, dxv_brick.h)
-            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(tid));
+            tid = lane_id();
             store_brick<TEXELS>(pp, N, nz, bx, by, bz, tid, occ, texel);
 #if defined(DXV_QUEUE_TIMES)
             { const uint64_t now = __builtin_amdgcn_s_memrealtime(); tLast = tBrick; if (now - tBrick > tMax) tMax = now - tBrick; tBrick = now; ++nBricks; }
@@ -485,12 +331,6 @@ __device__ __forceinline__ void clear_dead_bricks(const VoxelizeParams& p, const
         }
     }
 }
-// ... and the clear as a kernel of its own (clearMode 0, and every grid whose side is no multiple of 16): the whole partition
-__global__ __launch_bounds__(256) void k_clear_grid(VoxelizeParams p)
-{
-    plan_clear(p.grid, (size_t)p.N * p.N * p.nz, gridDim.x);
-    if (p.texels) plan_clear(reinterpret_cast<uint8_t*>(p.texels), (size_t)p.N * p.N * p.nz * 4u, gridDim.x);
-}
 
 template <bool TEXELS>
 __global__ __launch_bounds__(64, 6) void k_voxelize_listed(VoxelizeParams p, QueueLens lens, ClearShare clr)
@@ -543,6 +383,7 @@ __global__ __launch_bounds__(64, 6) void k_voxelize_listed(VoxelizeParams p, Que
         asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w) : "s"(slot) : "memory");
     }
     const SceneView& sc = p.scene;
+    // (the brick's set-up, down to origin_leaves_root: the same sequence as in k_voxelize_queue, see there)
     const uint32_t N = p.N, nz = p.nz;
     const uint32_t bx = w & 1023u, by = (w >> 10) & 1023u, bz = w >> 20;
     const uint32_t tid = threadIdx.x;
@@ -570,8 +411,7 @@ __global__ __launch_bounds__(64, 6) void k_voxelize_listed(VoxelizeParams p, Que
     const uint8_t occ = TEXELS ? shade_reference_lds(sc, r, best.leaf, stk, 16, &texel) : shade_reference_again(sc, r, best.leaf);
     // the lane's voxel once more (nothing of it is kept through the body: with the texel image on, the lane's coordinates held across the
     // scan cost the kernel its seventh wave per SIMD -- k_voxelize_queue does the same)
-    uint32_t lane;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+    const uint32_t lane = lane_id();
     store_brick<TEXELS>(&p, N, nz, bx, by, bz, lane, occ, texel);
 #if defined(DXV_PHASE_TIMES)
     { const unsigned long long now_ = __builtin_amdgcn_s_memrealtime(); if (threadIdx.x == 0u) atomicAdd(g_dxvPhase + (size_t)(blockIdx.x & (kPhaseSlots - 1u)) * 16u + 5, now_ - tPhase5_); }
@@ -709,11 +549,8 @@ hipError_t launch_voxelize_prepared(const VoxelizeParams& p, ListsOccupancy& occ
         blocks = (blocks + 7u) & ~(uint64_t)7u;
         clr.live = live; clr.blocks = (uint32_t)blocks; clr.where = (uint32_t)clearMode;
     } else {
-        // (about one workgroup of 256 threads per 64 KiB, at least 8 and at most 8,192)
-        uint32_t nb = (uint32_t)((bytes + 65535u) >> 16);
-        nb = nb < 8u ? 8u : nb > 8192u ? 8192u : nb;
-        k_clear_grid<<<dim3(nb), dim3(256), 0, s>>>(p);
-        if (!listedLen) return hipGetLastError();
+        const hipError_t e = plan_clear_grid(p, s);                     // (a kernel of its own in front of the bricks': plan_bricks.hip)
+        if (e != hipSuccess || !listedLen) return e;
     }
     const uint32_t wgs = 8u * listedLen + clr.blocks;
     if (p.texels) k_voxelize_listed<true><<<dim3(wgs), dim3(64), 0, s>>>(p, lens, clr);

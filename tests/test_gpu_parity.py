@@ -1160,7 +1160,7 @@ def test_update_vertices_from_a_device_buffer(dxv, orc, bunny):
 
 @pytest.mark.gpu
 def test_parity_row_lists_equal_tree_walk_and_oracle(dxv, orc, bunny, dragon):
-    """The parity rule through its row lists (`plists`, dirmap.hip: per texel of the (y, z) plane the triangles whose padded box
+    """The parity rule through its row lists (`plists`, parity_lists.hip: per texel of the (y, z) plane the triangles whose padded box
     reaches it) gives the grids of the row walk over the tree and of the oracle: assets, lattice-snapped adversarial meshes
     (cube-spanning triangles: over the size cap, the tree answers), slabs, block-cyclic ranks, rows longer than a wave's run,
     refits, the policy of option plists = 1."""

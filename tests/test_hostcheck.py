@@ -443,7 +443,7 @@ def test_normal_class_agrees_with_the_predicate_everywhere_on_the_triangle(hostc
 
 
 def test_parity_row_lists_give_the_oracle_grid(orc, hostcheck, bunny):
-    """The parity rule through row lists of the (y, z) plane (pl_rect, dxv_dirmap.h; the device builder and kernel: dirmap.hip,
+    """The parity rule through row lists of the (y, z) plane (pl_rect, dxv_dirmap.h; the device builder and kernel: parity_lists.hip,
     k_parity_rows<.., LISTS>): every triangle whose padded box covers a row's point is in the row's texel, once -- so counting
     over the list equals counting over all triangles.  Host replay against the oracle on the bunny and on lattice-snapped
     adversarial meshes (box edges ON texel borders and row coordinates), coarse and fine grids."""
@@ -474,7 +474,7 @@ def test_parity_row_lists_give_the_oracle_grid(orc, hostcheck, bunny):
 
 
 def test_work_queue_brick_test_never_drops_a_live_ray(orc, hostcheck, bunny, dragon):
-    """The work queue of the lists kernel (voxelize_lists.hip: k_plan_bricks) keeps a 4^3-voxel brick iff dm_box_may_be_live says
+    """The work queue of the lists kernel (plan_bricks.hip: k_plan_bricks) keeps a 4^3-voxel brick iff dm_box_may_be_live says
     a ray of it can be live -- decided from the brick's hull, three of its corners and a max-mip of the lists' far radii
     (dxv_dirmap.h).  Replayed on the host against the per-voxel first-step decision the kernel makes (origin_leaves_root,
     dm_ray_start: the same functions): no live voxel may sit in a dropped brick, on grids whose bricks straddle the centre

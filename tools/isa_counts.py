@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """Static instruction counts of the library's kernels from the compiler's gfx950 assembly (no GPU needed).
     python tools/isa_counts.py [source.hip] [kernel name substring ...] [--asm FILE] [--hash]   (default: voxelize_lists.hip, the two brick kernels)
+    python tools/isa_counts.py --all [--usage]      (every kernel of every .hip of the build, sorted by name: name and stream hash)
 Per kernel: vector ALU / scalar ALU / vector loads / vector stores + atomics / LDS instructions, and how many correctly rounded
 divisions (v_div_fixup_f32) and square roots (v_sqrt_f32) it contains.  --hash: also a hash of the kernel's instruction stream (its
 body without labels, comments and directives; local labels numbered in order of appearance, so a kernel that moved to another file or
-position hashes the same) -- equal hashes of two builds: the same code."""
+position hashes the same) -- equal hashes of two builds: the same code.  --all --usage: instead of the hash, the compiler's resource
+remarks of the last build (csrc/build/*.usage): VGPRs, SGPRs, LDS, scratch, occupancy."""
 import collections
 import hashlib
 import os
@@ -27,8 +29,9 @@ def assembly(src):
 
 def bodies(path, wanted):
     txt = open(path).read()
-    for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)^\.Lfunc_end", txt, re.S | re.M):
-        if not wanted or any(w in m.group(1) for w in wanted):
+    kernels = set(re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", txt, re.M))
+    for m in re.finditer(r"^(\w+):[^\n]*\n(.*?)^\.Lfunc_end", txt, re.S | re.M):
+        if any(w in m.group(1) for w in wanted) if wanted else m.group(1) in kernels:
             yield m.group(1), m.group(2)
 
 
@@ -72,7 +75,23 @@ def counts(path, wanted, hashes=False):
     return res
 
 
+def all_kernels(usage):
+    """one line per kernel of every .hip in the build's SOURCES, sorted by kernel name (file and position do not appear)"""
+    rows = []                                                  # (a list: a kernel instantiated in two translation units appears twice)
+    for src in (s for s in B.SOURCES if s.endswith(".hip")):
+        if usage:
+            rows += B.kernel_resources(os.path.splitext(src)[0]).items()
+        else:
+            rows += [(k, {"stream_sha256": c["stream_sha256"], "instructions": c["instructions"]}) for k, c in counts(assembly(src), [], True).items()]
+    return sorted(rows, key=lambda r: (r[0], sorted(r[1].items())))
+
+
 if __name__ == "__main__":
+    if "--all" in sys.argv:
+        import json
+        for name, c in all_kernels("--usage" in sys.argv):
+            print(json.dumps({"kernel": name, **c}))
+        sys.exit(0)
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     asm = sys.argv[sys.argv.index("--asm") + 1] if "--asm" in sys.argv else None
     if asm:
