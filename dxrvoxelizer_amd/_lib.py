@@ -80,6 +80,9 @@ SYMBOLS = {
     "dxv_distance_bytes": (C.c_size_t, [C.c_void_p]),
     "dxv_distance_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "dxv_distance_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "dxv_fill_async": (C.c_int, [C.c_void_p, C.c_int]),
+    "dxv_fill": (C.c_int, [C.c_void_p, C.c_int]),
+    "dxv_fill_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "dxv_build_lists": (C.c_int, [C.c_void_p]),
     "dxv_build_lists_for_grid": (C.c_int, [C.c_void_p, C.c_uint32]),
     "dxv_build_parity_lists": (C.c_int, [C.c_void_p]),

@@ -215,6 +215,17 @@ struct dxv_ctx {
         hipEvent_t evD0 = nullptr, evD1 = nullptr;   // around the frame's last field
         bool distTimed = false;          // ... which was bracketed by them and not read yet (the frame's next dxv_sync reads it)
         float dist_ms = 0.0f;
+        // exterior flood fill (fill.hip; dxv_fill_async): the two bit masks and the control block of the frame's fill, its own so that
+        // frames fill side by side; goes with dxv_trim
+        DevBuf<uint8_t> fillScratch;     // (cap: bytes) fill_scratch_bytes
+        bool fillPending = false;        // a batch is in the stream whose verdict (converged or not) nobody has read yet: the frame can still
+                                         // report something, and its next synchronisation reads it and goes on if need be (settle_fill)
+        int fillWhat = 0;                // ... DXV_FILL_SOLID / DXV_FILL_INTERIOR, for the write-back of the batches that follow
+        uint32_t fillBatch = 0;          // ... rounds per batch (option fillrounds as it stood at dxv_fill_async)
+        uint32_t fillRounds = 0;         // rounds of the frame's last fill so far, the confirming one included
+        hipEvent_t evF0 = nullptr, evF1 = nullptr;   // around the frame's last fill (evF1: behind its last batch)
+        bool fillTimed = false;          // ... which was bracketed by them and not read yet
+        float fill_ms = 0.0f;
     };
     Frame frames[DXV_FRAME_COUNT];
     uint32_t cur = 0;                    // dxv_set_frame
@@ -243,6 +254,7 @@ struct dxv_ctx {
         uint32_t status[DXV_FRAME_COUNT][4];
         uint32_t queueLens[DXV_FRAME_COUNT][16 * 64];    // the sixteen count words of a frame's queue (light and heavy bricks of the eight queues; each in a 256-byte line of its own)
         uint32_t preparedLens[16 * 64];                  // ... of a queue that is being prepared
+        uint32_t fillCtl[DXV_FRAME_COUNT][64];           // the control block of a frame's last fill batch (kFillMaxRounds words)
     };
     Pinned* pin = nullptr;
     hipEvent_t evList[4] = {};       // around the counting pass, around the rest of the build

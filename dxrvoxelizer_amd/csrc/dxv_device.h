@@ -195,6 +195,14 @@ hipError_t launch_surface(const SurfaceParams& p, hipStream_t s);
 size_t distance_scratch_bytes(uint32_t N);
 hipError_t launch_distance(const uint8_t* grid, uint32_t N, int format, void* field, uint8_t* scratch, hipStream_t s);
 
+// fill.hip -- the exterior flood fill of a whole N^3 grid (dxv_fill.h), in place: one batch = (first: the grid packed into the free and
+// reached masks,) `rounds` rounds (1 .. kFillMaxRounds), the write-back of what = 0 (walls and what they enclose) or 1 (the enclosed voxels
+// alone).  scratch: fill_scratch_bytes(N), the two masks and the batch's control block -- word k != 0: round k changed something; the
+// batch has converged exactly when the word of its last round is 0.  A batch with first = false goes on from the masks of the one before.
+size_t fill_scratch_bytes(uint32_t N);
+uint32_t* fill_control(uint8_t* scratch, uint32_t N);
+hipError_t launch_fill(uint8_t* grid, uint32_t N, int what, uint8_t* scratch, uint32_t rounds, bool first, hipStream_t s);
+
 // raycast.hip
 struct RayCastCB;
 hipError_t launch_raycast(const RayCastCB& cb, const uint8_t* grid, uint32_t N, uint32_t width, uint32_t height,

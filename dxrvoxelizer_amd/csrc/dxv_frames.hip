@@ -2,6 +2,7 @@
 // dxv_sync reads back (sync_frame), and the C-ABI entry points around them.  Whether a launch builds its queue, keeps it or has
 // the hardware deal it out is dxv_policy.h's queue_policy.
 #include "dxv_ctx.h"
+#include "dxv_fill.h"
 
 using namespace dxv;
 using namespace dxvhost;
@@ -23,6 +24,8 @@ int frame_prepare(dxv_ctx* c, uint32_t i)
     if (!f.evR1) DXV_HIP(c, hipEventCreate(&f.evR1));
     if (!f.evD0) DXV_HIP(c, hipEventCreate(&f.evD0));
     if (!f.evD1) DXV_HIP(c, hipEventCreate(&f.evD1));
+    if (!f.evF0) DXV_HIP(c, hipEventCreate(&f.evF0));
+    if (!f.evF1) DXV_HIP(c, hipEventCreate(&f.evF1));
     DXV_HIP(c, f.status.reserve(64, 256));
     DXV_HIP(c, f.redo.reserve(kRedoCap, sizeof(uint64_t) * kRedoCap));
     // on the frame's own stream, and finished before anything reads the words: the streams are non-blocking, a memset on the
@@ -541,11 +544,12 @@ int voxelize_common(dxv_ctx* c, uint32_t N, int mode, uint32_t z0, uint32_t nzLo
     f.grid_dim = N; f.z0 = z0; f.nz = nzLocal;
     f.lastMode = mode; f.lastZBlock = zBlock; f.lastZPeriod = zPeriod;
     f.distCurrent = false;                                              // (a field of the grid this launch replaces is stale)
+    f.fillPending = false;                                              // (... and a fill of it that has not converged yet is dropped: its batch in the stream ends in front of this launch)
     return launch_now(c, c->cur);
 }
 
-// dxv_sync of one frame: wait for its stream, read its status words, redo the launch with a deeper column if asked to
-int sync_frame(dxv_ctx* c, uint32_t i)
+// dxv_sync of one frame, the launch's half: wait for its stream, read its status words, redo the launch with a deeper column if asked to
+static int sync_launch(dxv_ctx* c, uint32_t i)
 {
     Frame& f = c->frames[i];
     const hipStream_t fs = frame_stream(c, i);
@@ -591,6 +595,43 @@ int sync_frame(dxv_ctx* c, uint32_t i)
     return 0;
 }
 
+// ... and the fill's half, behind it (the stream has been waited for): the verdict of the frame's last fill batch.  A batch whose last
+// round still changed a word has not converged: further batches -- rounds and write-back, from the masks the frame's scratch still
+// holds -- are enqueued and waited for until one has (the pattern of settle_lists: what only the host can decide is decided where the
+// frame is synchronised anyway).  A flood over V voxels reaches at least one new voxel per live round: fewer than V rounds.
+static int settle_fill(dxv_ctx* c, uint32_t i)
+{
+    Frame& f = c->frames[i];
+    const hipStream_t fs = frame_stream(c, i);
+    const uint32_t* ctl = c->pin->fillCtl[i];
+    const uint32_t N = f.grid_dim;
+    const uint64_t most = f.fillBatch ? (uint64_t)N * N * N / f.fillBatch + 2u : 0u;
+    for (uint64_t batch = 0; f.fillPending; ++batch) {
+        uint32_t live = 0;
+        while (live < f.fillBatch && ctl[live]) ++live;
+        if (live < f.fillBatch) {                                       // round `live` changed nothing: the confirming round
+            f.fillRounds += live + 1u;
+            f.fillPending = false;
+            break;
+        }
+        f.fillRounds += f.fillBatch;
+        if (batch >= most) return fail(c, "dxv_fill: no fixed point after %u rounds on a grid of %u^3 voxels", f.fillRounds, N);
+        DXV_HIP(c, launch_fill(f.grid.p, N, f.fillWhat, f.fillScratch.p, f.fillBatch, false, fs));
+        if (f.fillTimed) DXV_HIP(c, hipEventRecord(f.evF1, fs));
+        DXV_HIP(c, hipMemcpyAsync(c->pin->fillCtl[i], fill_control(f.fillScratch.p, N), sizeof(c->pin->fillCtl[i]), hipMemcpyDeviceToHost, fs));
+        DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+        DXV_HIP(c, hipStreamSynchronize(fs));
+    }
+    if (f.fillTimed) { f.fill_ms = elapsed(f.evF0, f.evF1); f.fillTimed = false; }
+    return 0;
+}
+
+int sync_frame(dxv_ctx* c, uint32_t i)
+{
+    if (sync_launch(c, i)) return 1;
+    return settle_fill(c, i);
+}
+
 // The display pass of the selected frame into dst (device memory, rows `pitch` bytes apart), enqueued on the frame's stream behind
 // whatever it holds: the empty-brick flags into the frame's own scratch, the ray-cast, the frame's end event behind both (what
 // dxv_stream_wait_frame and a refit on another stream wait for).  The caller has checked the frame's grid and the target.
@@ -617,6 +658,7 @@ static int settle_frame_launch(dxv_ctx* c)
     if (settle_lists(c)) return 1;                                     // (waits for a list build's end, not for the launch behind it)
     Frame& f = cur_frame(c);
     if (f.pending && (f.lastCanFail || (f.usedLists && f.listEpochUsed == c->withdrawnEpoch))) return sync_frame(c, c->cur);
+    if (f.fillPending) return sync_frame(c, c->cur);                    // a fill whose verdict is not in yet: what is behind it must see the final grid
     return 0;
 }
 
@@ -753,6 +795,56 @@ int dxv_distance_ms(dxv_ctx* c, float* ms)
     if (!c) return 1;
     if (!ms) return fail(c, "dxv_distance_ms: ms is NULL");
     *ms = cur_frame(c).dist_ms;
+    return 0;
+}
+
+// The exterior flood fill of the selected frame's grid (fill.hip), in place, enqueued on the frame's stream behind whatever it holds --
+// under dxv_render_async's host-wait rule: one batch of rounds, the write-back, the batch's control block into page-locked words, the
+// frame's end event.  Whether the batch converged is read where the frame is next synchronised (settle_fill).
+int dxv_fill_async(dxv_ctx* c, int what)
+{
+    if (!c) return 1;
+    if (what != DXV_FILL_SOLID && what != DXV_FILL_INTERIOR)
+        return fail(c, "dxv_fill: unknown kind %d (DXV_FILL_SOLID = 0, DXV_FILL_INTERIOR = 1)", what);
+    Frame& f = cur_frame(c);
+    if (!f.grid.p || !f.grid_dim) return fail(c, "dxv_fill: frame %u has no grid yet (call dxv_voxelize first)", c->cur);
+    if (!frame_renderable(f))
+        return fail(c, "dxv_fill: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share");
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (settle_frame_launch(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    const uint32_t N = f.grid_dim;
+    const size_t scratch = fill_scratch_bytes(N);
+    DXV_HIP(c, f.fillScratch.reserve(scratch, scratch, fs));
+    const bool timed = c->opt.events != 0;
+    f.fillWhat = what;
+    f.fillBatch = c->opt.fillrounds ? (uint32_t)c->opt.fillrounds : kFillRoundsDefault;
+    f.fillRounds = 0;
+    // the grid stops being what the frame's last launch wrote: a kept queue's zeros are gone (the next launch clears everything; the
+    // caller holds no pointer because of this, so ptrExposed stays), and a field made of the grid before is stale
+    f.clearSig = 0;
+    f.distCurrent = false;
+    if (timed) DXV_HIP(c, hipEventRecord(f.evF0, fs));
+    DXV_HIP(c, launch_fill(f.grid.p, N, what, f.fillScratch.p, f.fillBatch, true, fs));
+    if (timed) DXV_HIP(c, hipEventRecord(f.evF1, fs));
+    DXV_HIP(c, hipMemcpyAsync(c->pin->fillCtl[c->cur], fill_control(f.fillScratch.p, N), sizeof(c->pin->fillCtl[c->cur]), hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    f.fillTimed = timed;
+    f.fillPending = true;
+    return 0;
+}
+
+int dxv_fill(dxv_ctx* c, int what)
+{
+    if (dxv_fill_async(c, what)) return 1;
+    return dxv_sync(c);
+}
+
+int dxv_fill_info(dxv_ctx* c, float* ms, uint32_t* rounds)
+{
+    if (!c) return 1;
+    if (ms) *ms = cur_frame(c).fill_ms;
+    if (rounds) *rounds = cur_frame(c).fillRounds;
     return 0;
 }
 

@@ -191,6 +191,8 @@ struct Options {
     int plists = 1;          // 1 = from a scene's second parity launch, 2 = from the first, 0 = tree walk
     int skipempty = 1;       // display pass: skip the samples of empty 8^3 bricks (same image)
     int surfaceitems = 0;    // surface modes: work items the large triangles' list may take (0: all 2^20 it holds; fewer: tests of a full list)
+    int fillrounds = 0;      // dxv_fill*: rounds of one batch (1 .. 64); 0 = kFillRoundsDefault (dxv_fill.h).  Same grids: a fill that needs more is
+                             // continued where its frame is next synchronised
     int sortbits = 0;        // digit plan of the radix sort as last set through this context (the plan itself is the process's: radix_sort_set_plan)
 };
 
@@ -249,10 +251,17 @@ constexpr OptionRow kOptions[] = {
     {"morton", kOnOff, "not in {0,1}", &Options::morton, OptionEffect::none},
 };
 constexpr int kOptionCount = (int)(sizeof(kOptions) / sizeof(kOptions[0]));
+// kOptions is the set of keys of the strcmp chain it replaced, and tests/test_policy.py writes that set out key by key.  Keys of what
+// has been added since -- the passes over a frame's finished grid -- are rows of the same kind in a table of their own.
+constexpr OptionRow kGridPassOptions[] = {
+    {"fillrounds", in_range(0, 64), "not in [0, 64]", &Options::fillrounds, OptionEffect::none},
+};
 
 inline const OptionRow* find_option(const char* name)
 {
     for (const OptionRow& row : kOptions)
+        if (!strcmp(name, row.name)) return &row;
+    for (const OptionRow& row : kGridPassOptions)
         if (!strcmp(name, row.name)) return &row;
     return nullptr;
 }

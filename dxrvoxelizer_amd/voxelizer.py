@@ -11,6 +11,7 @@ from ._lib import DxvError, Stats, load_library
 MODE_REFERENCE, MODE_PARITY = 0, 1
 MODE_SURFACE, MODE_REFERENCE_SURFACE = 2, 3      # the conservative surface; the reference rule's solid with that shell (include/dxv.h)
 DIST_SQ_I32, DIST_F32 = 0, 1                     # formats of the distance field (include/dxv.h)
+FILL_SOLID, FILL_INTERIOR = 0, 1                  # what the flood fill leaves (include/dxv.h)
 DBG_SORTED_KEYS, DBG_NODES, DBG_TRI_POS, DBG_TRI_NRM, DBG_PARENTS, DBG_NODES32, DBG_NODES64, DBG_LIST_CELLS, DBG_LIST_ENTRIES, DBG_LIST_MIP = range(10)
 DBG_BRICK_EMPTY, DBG_BRICK_SUMMARY = 10, 11         # the display pass's empty-brick flags and the summaries behind them
 
@@ -292,6 +293,26 @@ class Voxelizer:
         ms = C.c_float()
         self._check(self._lib.dxv_distance_ms(self._ctx, C.byref(ms)))
         return ms.value
+
+    # ---- the exterior flood fill of the frame's grid -----------------------------------------------
+    def Fill(self, what=FILL_SOLID, sync=True, frameIndex=None):
+        """Flood the empty space of the selected frame's whole grid from the grid's border (6-connectivity) and replace the grid, in
+        place, by what the flood did not reach (dxv_fill / dxv_fill_async): FILL_SOLID the walls and everything they enclose,
+        FILL_INTERIOR the enclosed voxels alone.  Voxelize(N, MODE_SURFACE); Fill() is the solid of a mesh whose normals and
+        watertightness cannot be trusted.  sync=False only enqueues it behind the frame's launch."""
+        if frameIndex is not None:
+            self.SetFrame(frameIndex)
+        if what not in (FILL_SOLID, FILL_INTERIOR):
+            raise DxvError(f"Fill: unknown kind {what!r} (FILL_SOLID = 0, FILL_INTERIOR = 1)")
+        fn = self._lib.dxv_fill if sync else self._lib.dxv_fill_async
+        self._check(fn(self._ctx, int(what)))
+        return True
+
+    def fill_info(self):
+        """(ms, rounds) of the selected frame's last fill as of its last Sync (dxv_fill_info)."""
+        ms, rounds = C.c_float(), C.c_uint32()
+        self._check(self._lib.dxv_fill_info(self._ctx, C.byref(ms), C.byref(rounds)))
+        return ms.value, rounds.value
 
     def grid_bytes(self):
         return self._lib.dxv_grid_bytes(self._ctx)

@@ -191,7 +191,7 @@ DXV_API int dxv_sync(dxv_ctx* ctx);
  * frameIndex (static const uint8_t FrameCount, Content/Voxelizer.h:24; m_grids[FrameCount], :110;
  * Render(pCommandList, frameIndex, ...), :21-22; voxelize(pCommandList, frameIndex), Content/Voxelizer.cpp:351-356),
  * so that the GPU works on one grid while the host still reads another.  dxv_set_frame selects the frame the
- * following dxv_voxelize* / dxv_sync / dxv_grid_* / dxv_texels_download / dxv_render* / dxv_update_frame / dxv_distance* / dxv_get_stats calls refer to
+ * following dxv_voxelize* / dxv_sync / dxv_grid_* / dxv_texels_download / dxv_render* / dxv_update_frame / dxv_distance* / dxv_fill* / dxv_get_stats calls refer to
  * (default 0).  Each frame owns its grid, texel image, status words and -- frames 1 and 2 -- an internal stream,
  * so launches of different frames overlap on the GPU; scene, candidate lists and options are shared (an extra frame
  * costs its grid).  Calls that change what the frames read (dxv_set_mesh, dxv_build, dxv_scene_import, dxv_set_stream) first
@@ -347,6 +347,44 @@ DXV_API int dxv_distance_download(dxv_ctx* ctx, void* host, size_t bytes);
  * 0 before that, and under option events = 0.  (A getter of its own: dxv_stats keeps its layout.) */
 DXV_API int dxv_distance_ms(dxv_ctx* ctx, float* ms);
 
+/* Exterior flood fill: a robust solid from any grid (no reference counterpart; what binvox does by default).  The ray rules trust the mesh --
+ * its normals (mode 0), its being watertight (mode 1); the conservative surface (mode 2) trusts neither, and this pass turns it into a
+ * solid: mark what the surface touches, flood the empty space from the border of the grid, call everything the flood cannot reach solid.
+ * The same pass closes the internal cavities of any grid.  Input: the WHOLE grid of the selected frame's last launch, any mode (bytes a
+ * caller wrote through dxv_grid_device_ptr count too).  For voxel p = (ix, iy, iz) of an N^3 grid
+ *     wall(p)    iff byte(p) != 0
+ *     border(p)  iff any of ix, iy, iz is 0 or N-1
+ *     outside    = the smallest set O with: every p with !wall(p) and border(p) is in O;
+ *                  if p in O, q is one of p's 6 face neighbours inside the grid and !wall(q), then q in O
+ * Free voxels that touch only along an edge or a corner are NOT connected: the conservative surface separates 26-connected paths, so a
+ * 6-connected flood cannot leak through it.  "Reachable from the border" is a set, so the result is unique: the device's grid equals a
+ * restatement byte for byte.  An all-zero grid stays all zero; an all-wall grid becomes all 1 (SOLID) or all 0 (INTERIOR). */
+enum {
+    DXV_FILL_SOLID = 0,      /* byte'(p) = 1 if !outside(p) else 0:              the walls and everything they enclose */
+    DXV_FILL_INTERIOR = 1    /* byte'(p) = 1 if !outside(p) && !wall(p) else 0:  the enclosed voxels alone             */
+};
+/* dxv_fill_async -- the result REPLACES the frame's grid in place, bytes exactly 0 or 1: dxv_grid_*, dxv_grid_count, the packed download,
+ * dxv_render* and dxv_distance* then work on the filled grid.  ENQUEUED on the frame's stream behind its launch (render, field); returns
+ * without waiting.
+ *  - The host waits only under dxv_render_async's rule: when the frame's last launch can still report something, the frame is
+ *    synchronised first; otherwise the call only enqueues.
+ *  - Checked on the host before anything is enqueued, each an error with a message: `what` is one of the two; the frame has been
+ *    launched; its last launch was the whole grid (a slab's or a share's flood would need its neighbours' voxels).
+ *  - A flood has no bound on its rounds that is both safe and cheap.  The call enqueues ONE batch of rounds (option fillrounds) and the
+ *    write-back; a round returns at once when the round before it changed nothing; whether the batch reached the fixed point is one
+ *    page-locked word that is read where the frame is next synchronised, and that synchronisation enqueues further batches from the bit
+ *    masks kept in the frame's scratch until one converges.  After dxv_sync the grid is always exact; until then the frame counts as one
+ *    that can still report something: dxv_render_async, dxv_distance_async, dxv_stream_wait_frame, dxv_grid_* and a second
+ *    dxv_fill_async settle a pending fill first.  The next dxv_voxelize* simply overwrites the grid.
+ *  - The scratch (two bit masks, about N^3 / 4 bytes) belongs to the frame: frames fill side by side.  dxv_trim gives it back.
+ *  - A distance field made before the fill is stale after it; the texel image is not touched.
+ * dxv_fill -- the same + dxv_sync. */
+DXV_API int dxv_fill_async(dxv_ctx* ctx, int what);
+DXV_API int dxv_fill(dxv_ctx* ctx, int what);
+/* The selected frame's last fill as of the frame's last dxv_sync: device time in milliseconds from its first kernel to its last write-back
+ * (HIP events, option events = 1; else 0) and the rounds it took, the confirming one included.  Either pointer may be NULL. */
+DXV_API int dxv_fill_info(dxv_ctx* ctx, float* ms, uint32_t* rounds);
+
 /* Multi-GPU: the built scene (nodes + triangle data) as one relocatable device blob, so that
  * rank 0 builds once and the host layer broadcasts it (RCCL over xGMI) to the other ranks.
  * export copies the blob into caller-provided DEVICE memory; import adopts a blob from DEVICE
@@ -462,6 +500,8 @@ DXV_API int dxv_get_stats(const dxv_ctx* ctx, dxv_stats* out);
  *   skipempty 0|1 dxv_render, dxv_render_async: skip the samples of empty 8^3 bricks (default 1; same image)
  *   surfaceitems 0..2^20  test hook of the surface modes: work items the large triangles' list may take (0, default: all 2^20 it
  *                 holds); a triangle whose items do not all fit is walked whole as well.  Same grids.
+ *   fillrounds 0..64  dxv_fill*: rounds of one batch (0, default: 4 -- the meshes measured take 2 or 3); a fill that needs more is continued
+ *                 where its frame is next synchronised.  Same grids.
  *   morton 0|1, region 0..24, subbox 0|1   brick order, bricks per XCD region (log2), partial launch */
 DXV_API int dxv_set_option(dxv_ctx* ctx, const char* key, int64_t value);
 
@@ -502,7 +542,7 @@ DXV_API int dxv_debug_plan_check(dxv_ctx* ctx, uint64_t out[16]);
 
 /* Give back what the context keeps only to make the next build faster: the list build's scratch (up to 16 GiB per buffer
  * after a 10 M-triangle scene), the LBVH build's scratch when no refit can follow (imported scenes), the memory of prepared queues
- * whose lists are gone, the scratch of the frames' distance fields (the fields stay).  Nothing a launch reads. */
+ * whose lists are gone, the scratch of the frames' distance fields (the fields stay) and of their flood fills.  Nothing a launch reads. */
 DXV_API int dxv_trim(dxv_ctx* ctx);
 
 /* Test hook: copy an internal device array to the host (enum above). */

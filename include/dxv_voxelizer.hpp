@@ -165,6 +165,12 @@ public:
 		return dxv_distance_download(m_ctx, field.data(), field.size()) == 0;
 	}
 
+	// The exterior flood fill of that frame's whole grid, in place (dxv_fill / dxv_fill_async): DXV_FILL_SOLID leaves the walls and everything
+	// they enclose, DXV_FILL_INTERIOR the enclosed voxels alone.  Voxelize(gridDim, SURFACE) && Fill() is the solid of a mesh whose
+	// normals and watertightness cannot be trusted.  Refers to the frame last selected; sync = false only enqueues (WaitFrame reports).
+	bool Fill(int what = DXV_FILL_SOLID, bool sync = true) { return m_ctx && (sync ? dxv_fill(m_ctx, what) : dxv_fill_async(m_ctx, what)) == 0; }
+	bool FillInfo(float& ms, uint32_t& rounds) { return m_ctx && dxv_fill_info(m_ctx, &ms, &rounds) == 0; }
+
 	// Result: uint8 occupancy, x fastest, then y (top to bottom), then z.
 	bool Download(std::vector<uint8_t>& grid)
 	{
