@@ -80,6 +80,14 @@ SYMBOLS = {
     "dxv_distance_bytes": (C.c_size_t, [C.c_void_p]),
     "dxv_distance_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "dxv_distance_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "dxv_mesh_distance_async": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_int]),
+    "dxv_mesh_distance": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_int]),
+    "dxv_mesh_distance_device_ptr": (C.c_void_p, [C.c_void_p]),
+    "dxv_mesh_distance_bytes": (C.c_size_t, [C.c_void_p]),
+    "dxv_mesh_distance_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_mesh_distance_triangles_device_ptr": (C.c_void_p, [C.c_void_p]),
+    "dxv_mesh_distance_triangles_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_mesh_distance_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "dxv_fill_async": (C.c_int, [C.c_void_p, C.c_int]),
     "dxv_fill": (C.c_int, [C.c_void_p, C.c_int]),
     "dxv_fill_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),

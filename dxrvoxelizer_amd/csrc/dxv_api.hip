@@ -249,7 +249,7 @@ void dxv_destroy(dxv_ctx* c)
     for (uint32_t i = 0; i < DXV_FRAME_COUNT; ++i) {
         Frame& f = c->frames[i];
         if (frame_stream(c, i)) (void)hipStreamSynchronize(frame_stream(c, i));
-        for (hipEvent_t ev : {f.ev0, f.ev1, f.evP0, f.evP1, f.evEnd, f.evR0, f.evR1, f.evD0, f.evD1, f.evF0, f.evF1})
+        for (hipEvent_t ev : {f.ev0, f.ev1, f.evP0, f.evP1, f.evEnd, f.evR0, f.evR1, f.evD0, f.evD1, f.evF0, f.evF1, f.evM0, f.evM1})
             if (ev) (void)hipEventDestroy(ev);
         if (f.ownStream) (void)hipStreamDestroy(f.ownStream);
     }
@@ -368,9 +368,19 @@ void fill_build_buffers(dxv_ctx* c, BuildBuffers& b)
 
 // The half-float / four-box copies of the hierarchy after a refit that skipped them (dxv_refit): made now, on `stream`, and
 // finished before anyone else can launch a walk on another stream.
+int wait_scene_readers(dxv_ctx* c, hipStream_t stream)
+{
+    for (uint32_t i = 0; i < DXV_FRAME_COUNT; ++i) {
+        Frame& f = c->frames[i];
+        if (f.ready && f.sceneReadPending && frame_stream(c, i) != stream) DXV_HIP(c, hipStreamWaitEvent(stream, f.evEnd, 0));
+    }
+    return 0;
+}
+
 int ensure_nodes(dxv_ctx* c, hipStream_t stream)
 {
     if (!c->nodesStale) return 0;
+    if (wait_scene_readers(c, stream)) return 1;                        // (a mesh distance walk of another frame may still read the boxes)
     BuildBuffers b{};
     fill_build_buffers(c, b);
     if (c->nodesStale == 2) DXV_HIP(c, lbvh_refit_boxes(b, stream));
@@ -472,6 +482,9 @@ int dxv_refit(dxv_ctx* c)
         if (f.lastCanFail || (f.usedLists && f.listEpochUsed == c->withdrawnEpoch)) { if (sync_frame(c, i)) return 1; }
         else if (frame_stream(c, i) != c->stream) DXV_HIP(c, hipStreamWaitEvent(c->stream, f.evEnd, 0));
     }
+    // ... and so is a pass behind a launch that reads nodes and triangle records (dxv_mesh_distance_async), whether or not the
+    // launch itself has been checked since: the frame's end event lies behind it
+    if (wait_scene_readers(c, c->stream)) return 1;
     const uint32_t hadListsOn = c->lists.state == 1 ? c->lists.res : 0u;
     scene_changed(c, SceneCause::refit);                               // (the queues prepared for the old surface go too; no launch that reads one is un-ordered: see above)
     if (alloc_pyramid(c)) return 1;

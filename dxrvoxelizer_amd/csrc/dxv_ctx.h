@@ -215,6 +215,21 @@ struct dxv_ctx {
         hipEvent_t evD0 = nullptr, evD1 = nullptr;   // around the frame's last field
         bool distTimed = false;          // ... which was bracketed by them and not read yet (the frame's next dxv_sync reads it)
         float dist_ms = 0.0f;
+        // mesh distance field (mesh_distance.hip; dxv_mesh_distance_async): the field of the frame's last launch -- a slab's has nz slices --
+        // and, when asked for, the nearest triangles; the frame's own, kept by dxv_trim
+        DevBuf<float> mdist;             // (cap: voxels)
+        DevBuf<uint32_t> mdistTri;       // (cap: voxels)
+        uint32_t mdistDim = 0;           // grid side of the frame's last mesh distance field (0: none yet) ...
+        uint32_t mdistNz = 0;            // ... and its slices
+        int mdistFormat = 0;             // ... its format
+        bool mdistHasTri = false;        // ... and whether the nearest triangles were made with it
+        bool mdistCurrent = false;       // the field belongs to the frame's grid as it is (a new launch or a fill makes it stale)
+        bool sceneReadPending = false;   // a mesh distance kernel that reads nodes and triangle records may still be running on the frame's stream: whatever
+                                         // rewrites them on another stream (dxv_refit, ensure_nodes) waits for the frame's end event first; any
+                                         // synchronisation of the frame clears it (the passes over the grid alone -- render, field, fill -- never set it)
+        hipEvent_t evM0 = nullptr, evM1 = nullptr;   // around the frame's last mesh distance field
+        bool mdistTimed = false;         // ... which was bracketed by them and not read yet (the frame's next dxv_sync reads it)
+        float mdist_ms = 0.0f;
         // exterior flood fill (fill.hip; dxv_fill_async): the two bit masks and the control block of the frame's fill, its own so that
         // frames fill side by side; goes with dxv_trim
         DevBuf<uint8_t> fillScratch;     // (cap: bytes) fill_scratch_bytes
@@ -351,6 +366,7 @@ void layout_scene(SceneHeader& h, uint32_t T, uint32_t V, bool wide);
 int alloc_scene(dxv_ctx* c, uint32_t T, uint32_t V, bool wide);
 int alloc_scratch(dxv_ctx* c, uint32_t T);
 void fill_build_buffers(dxv_ctx* c, BuildBuffers& b);
+int wait_scene_readers(dxv_ctx* c, hipStream_t stream);   // `stream` waits, on the device, for the frames' passes that still read the scene (sceneReadPending)
 int ensure_nodes(dxv_ctx* c, hipStream_t stream);       // the hierarchy's traversal copies after a refit that skipped them
 enum class SceneCause { mesh, build, refit, import };
 void scene_changed(dxv_ctx* c, SceneCause why);         // everything a new mesh, a build, a refit or an import invalidates

@@ -203,6 +203,20 @@ size_t fill_scratch_bytes(uint32_t N);
 uint32_t* fill_control(uint8_t* scratch, uint32_t N);
 hipError_t launch_fill(uint8_t* grid, uint32_t N, int what, uint8_t* scratch, uint32_t rounds, bool first, hipStream_t s);
 
+// mesh_distance.hip -- the exact distance from the voxel centres of slices [z0, z0 + nz) of an N^3 grid to the mesh, signed by the grid's
+// bytes (dxv_mesh_distance.h): walk = the nearest-triangle query over the two-box nodes (a tree no higher than kMdStack), else every
+// triangle for every voxel.  field: 4 bytes per voxel, element ((iz - z0) * N + iy) * N + ix like the grid; tris: the same, or null.
+struct MeshDistanceParams {
+    const uint8_t* grid;
+    float* field;
+    uint32_t* tris;         // tri(p), or null: not wanted
+    uint32_t N, z0, nz;
+    int format;             // DXV_MDIST_VOXELS_F32 / DXV_MDIST_UNITS_F32
+    float cap;              // md_cap(N, band): what every minimum starts from
+    float cullAbs;          // md_cull_abs(root box)
+};
+hipError_t launch_mesh_distance(const Node* nodes, const TriPos* triPos, uint32_t T, const MeshDistanceParams& p, bool walk, hipStream_t s);
+
 // raycast.hip
 struct RayCastCB;
 hipError_t launch_raycast(const RayCastCB& cb, const uint8_t* grid, uint32_t N, uint32_t width, uint32_t height,

@@ -2,6 +2,7 @@
 // dxv_sync reads back (sync_frame), and the C-ABI entry points around them.  Whether a launch builds its queue, keeps it or has
 // the hardware deal it out is dxv_policy.h's queue_policy.
 #include "dxv_ctx.h"
+#include "dxv_mesh_distance.h"
 #include "dxv_fill.h"
 
 using namespace dxv;
@@ -24,6 +25,8 @@ int frame_prepare(dxv_ctx* c, uint32_t i)
     if (!f.evR1) DXV_HIP(c, hipEventCreate(&f.evR1));
     if (!f.evD0) DXV_HIP(c, hipEventCreate(&f.evD0));
     if (!f.evD1) DXV_HIP(c, hipEventCreate(&f.evD1));
+    if (!f.evM0) DXV_HIP(c, hipEventCreate(&f.evM0));
+    if (!f.evM1) DXV_HIP(c, hipEventCreate(&f.evM1));
     if (!f.evF0) DXV_HIP(c, hipEventCreate(&f.evF0));
     if (!f.evF1) DXV_HIP(c, hipEventCreate(&f.evF1));
     DXV_HIP(c, f.status.reserve(64, 256));
@@ -544,6 +547,7 @@ int voxelize_common(dxv_ctx* c, uint32_t N, int mode, uint32_t z0, uint32_t nzLo
     f.grid_dim = N; f.z0 = z0; f.nz = nzLocal;
     f.lastMode = mode; f.lastZBlock = zBlock; f.lastZPeriod = zPeriod;
     f.distCurrent = false;                                              // (a field of the grid this launch replaces is stale)
+    f.mdistCurrent = false;
     f.fillPending = false;                                              // (... and a fill of it that has not converged yet is dropped: its batch in the stream ends in front of this launch)
     return launch_now(c, c->cur);
 }
@@ -560,8 +564,10 @@ static int sync_launch(dxv_ctx* c, uint32_t i)
         DXV_HIP(c, hipMemcpyAsync(words, f.status.p, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, fs));
         if (readQueue) DXV_HIP(c, hipMemcpyAsync(c->pin->queueLens[i], f.queue.p + f.queueHdr * kQueueHeaderWords + queue_len_word(0), sizeof(c->pin->queueLens[i]), hipMemcpyDeviceToHost, fs));
         DXV_HIP(c, hipStreamSynchronize(fs));
+        f.sceneReadPending = false;                                     // (whatever read the scene on this stream has finished)
         if (f.renderTimed) { f.render_ms = elapsed(f.evR0, f.evR1); f.renderTimed = false; }
         if (f.distTimed) { f.dist_ms = elapsed(f.evD0, f.evD1); f.distTimed = false; }
+        if (f.mdistTimed) { f.mdist_ms = elapsed(f.evM0, f.evM1); f.mdistTimed = false; }
         // lists this launch was queued behind without waiting for their verdict: withdrawn -> the launch again, through the tree
         if (settle_lists(c)) return 1;
         if (f.pending && f.usedLists && f.listEpochUsed == c->withdrawnEpoch && c->haveScene && f.grid_dim) {
@@ -798,6 +804,101 @@ int dxv_distance_ms(dxv_ctx* c, float* ms)
     return 0;
 }
 
+// The distance from the voxel centres of the selected frame's last launch to the MESH (mesh_distance.hip), signed by the frame's grid:
+// enqueued on the frame's stream behind whatever it holds, under dxv_render_async's host-wait rule (a pending fill is settled by it),
+// then the frame's end event; the frame is marked as reading the scene (sceneReadPending) until it is next synchronised, and dxv_refit and
+// ensure_nodes make their stream wait for that event before they rewrite triangle records or node boxes.  Unlike the
+// grid's own field a contiguous slab needs nothing from its neighbours; a share's slices are not one block of the field and are refused.
+int dxv_mesh_distance_async(dxv_ctx* c, int format, uint32_t bandVoxels, int wantTriangles)
+{
+    if (!c) return 1;
+    if (format != DXV_MDIST_VOXELS_F32 && format != DXV_MDIST_UNITS_F32)
+        return fail(c, "dxv_mesh_distance: unknown format %d (DXV_MDIST_VOXELS_F32 = 0, DXV_MDIST_UNITS_F32 = 1)", format);
+    if (bandVoxels > kMdMaxBand) return fail(c, "dxv_mesh_distance: a band of %u voxels (0 = none, at most %u)", bandVoxels, kMdMaxBand);
+    Frame& f = cur_frame(c);
+    if (!f.grid.p || !f.grid_dim || !f.nz) return fail(c, "dxv_mesh_distance: frame %u has no grid yet (call dxv_voxelize first)", c->cur);
+    if (f.lastZBlock != f.nz)
+        return fail(c, "dxv_mesh_distance: the frame's last launch was an interleaved share; needs the whole grid or a contiguous slab");
+    if (!c->haveScene) return fail(c, "dxv_mesh_distance: no scene with a built hierarchy (call dxv_build or dxv_scene_import first)");
+    if (c->hdr.treeHeight > (uint32_t)kMdStack)
+        return fail(c, "dxv_mesh_distance: tree height %u exceeds the walk's column of %d entries", c->hdr.treeHeight, kMdStack);
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (settle_frame_launch(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    const bool walk = c->opt.mdistwalk != 0;
+    if (walk && ensure_nodes(c, fs)) return 1;                          // after a refit that deferred the node boxes, as before a tree walk
+    const uint32_t N = f.grid_dim;
+    const size_t voxels = (size_t)N * N * f.nz;
+    f.mdistCurrent = false; f.mdistDim = 0;
+    DXV_HIP(c, f.mdist.reserve(voxels, align256(voxels * sizeof(float)), fs));
+    if (wantTriangles) DXV_HIP(c, f.mdistTri.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
+    MeshDistanceParams p{};
+    p.grid = f.grid.p; p.field = f.mdist.p; p.tris = wantTriangles ? f.mdistTri.p : nullptr;
+    p.N = N; p.z0 = f.z0; p.nz = f.nz;
+    p.format = format;
+    p.cap = md_cap(N, bandVoxels);
+    p.cullAbs = md_cull_abs(c->hdr.rootLo, c->hdr.rootHi);
+    const bool timed = c->opt.events != 0;
+    if (timed) DXV_HIP(c, hipEventRecord(f.evM0, fs));
+    DXV_HIP(c, launch_mesh_distance(scene_nodes(c), scene_tripos(c), c->hdr.numTris, p, walk, fs));
+    if (timed) DXV_HIP(c, hipEventRecord(f.evM1, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    f.mdistTimed = timed;
+    f.sceneReadPending = true;
+    f.mdistDim = N; f.mdistNz = f.nz; f.mdistFormat = format; f.mdistHasTri = wantTriangles != 0; f.mdistCurrent = true;
+    return 0;
+}
+
+int dxv_mesh_distance(dxv_ctx* c, int format, uint32_t bandVoxels, int wantTriangles)
+{
+    if (dxv_mesh_distance_async(c, format, bandVoxels, wantTriangles)) return 1;
+    return dxv_sync(c);
+}
+
+// the frame's mesh distance field (triangles: its nearest triangles), or the reason there is none to hand out: NULL + message
+static const void* current_mesh_field(const dxv_ctx* c, const char* who, bool triangles)
+{
+    const Frame& f = c->frames[c->cur];
+    dxv_ctx* w = const_cast<dxv_ctx*>(c);                               // (the message is the one thing an accessor writes)
+    if (!f.mdistDim || !f.mdist.p) { (void)fail(w, "%s: frame %u has no mesh distance field yet (call dxv_mesh_distance first)", who, c->cur); return nullptr; }
+    if (!f.mdistCurrent) { (void)fail(w, "%s: frame %u was launched or filled again since its mesh distance field was made: the field is stale", who, c->cur); return nullptr; }
+    if (triangles && !f.mdistHasTri) { (void)fail(w, "%s: frame %u's mesh distance field was made without triangles (want_triangles = 0)", who, c->cur); return nullptr; }
+    return triangles ? static_cast<const void*>(f.mdistTri.p) : static_cast<const void*>(f.mdist.p);
+}
+
+const void* dxv_mesh_distance_device_ptr(const dxv_ctx* c) { return c ? current_mesh_field(c, "dxv_mesh_distance_device_ptr", false) : nullptr; }
+const void* dxv_mesh_distance_triangles_device_ptr(const dxv_ctx* c) { return c ? current_mesh_field(c, "dxv_mesh_distance_triangles_device_ptr", true) : nullptr; }
+
+size_t dxv_mesh_distance_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame& f = c->frames[c->cur];
+    return f.mdistCurrent ? (size_t)f.mdistDim * f.mdistDim * f.mdistNz * sizeof(float) : 0;
+}
+
+static int mesh_field_download(dxv_ctx* c, const char* who, bool triangles, void* host, size_t bytes)
+{
+    if (!c) return 1;
+    const void* field = current_mesh_field(c, who, triangles);
+    if (!field) return 1;
+    const size_t want = dxv_mesh_distance_bytes(c);
+    if (!host || bytes != want) return fail(c, "%s: expected %zu bytes, got %zu", who, want, bytes);
+    if (dxv_sync(c)) return 1;
+    DXV_HIP(c, hipMemcpyAsync(host, field, bytes, hipMemcpyDeviceToHost, cur_stream(c)));
+    DXV_HIP(c, hipStreamSynchronize(cur_stream(c)));
+    return 0;
+}
+int dxv_mesh_distance_download(dxv_ctx* c, void* host, size_t bytes) { return mesh_field_download(c, "dxv_mesh_distance_download", false, host, bytes); }
+int dxv_mesh_distance_triangles_download(dxv_ctx* c, void* host, size_t bytes) { return mesh_field_download(c, "dxv_mesh_distance_triangles_download", true, host, bytes); }
+
+int dxv_mesh_distance_ms(dxv_ctx* c, float* ms)
+{
+    if (!c) return 1;
+    if (!ms) return fail(c, "dxv_mesh_distance_ms: ms is NULL");
+    *ms = cur_frame(c).mdist_ms;
+    return 0;
+}
+
 // The exterior flood fill of the selected frame's grid (fill.hip), in place, enqueued on the frame's stream behind whatever it holds --
 // under dxv_render_async's host-wait rule: one batch of rounds, the write-back, the batch's control block into page-locked words, the
 // frame's end event.  Whether the batch converged is read where the frame is next synchronised (settle_fill).
@@ -824,6 +925,7 @@ int dxv_fill_async(dxv_ctx* c, int what)
     // caller holds no pointer because of this, so ptrExposed stays), and a field made of the grid before is stale
     f.clearSig = 0;
     f.distCurrent = false;
+    f.mdistCurrent = false;
     if (timed) DXV_HIP(c, hipEventRecord(f.evF0, fs));
     DXV_HIP(c, launch_fill(f.grid.p, N, what, f.fillScratch.p, f.fillBatch, true, fs));
     if (timed) DXV_HIP(c, hipEventRecord(f.evF1, fs));

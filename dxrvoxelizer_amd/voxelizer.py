@@ -11,6 +11,7 @@ from ._lib import DxvError, Stats, load_library
 MODE_REFERENCE, MODE_PARITY = 0, 1
 MODE_SURFACE, MODE_REFERENCE_SURFACE = 2, 3      # the conservative surface; the reference rule's solid with that shell (include/dxv.h)
 DIST_SQ_I32, DIST_F32 = 0, 1                     # formats of the distance field (include/dxv.h)
+MDIST_VOXELS_F32, MDIST_UNITS_F32 = 0, 1          # formats of the mesh distance field (include/dxv.h)
 FILL_SOLID, FILL_INTERIOR = 0, 1                  # what the flood fill leaves (include/dxv.h)
 DBG_SORTED_KEYS, DBG_NODES, DBG_TRI_POS, DBG_TRI_NRM, DBG_PARENTS, DBG_NODES32, DBG_NODES64, DBG_LIST_CELLS, DBG_LIST_ENTRIES, DBG_LIST_MIP = range(10)
 DBG_BRICK_EMPTY, DBG_BRICK_SUMMARY = 10, 11         # the display pass's empty-brick flags and the summaries behind them
@@ -292,6 +293,58 @@ class Voxelizer:
         """Device time of the selected frame's last field, read at the frame's Sync (dxv_distance_ms)."""
         ms = C.c_float()
         self._check(self._lib.dxv_distance_ms(self._ctx, C.byref(ms)))
+        return ms.value
+
+    # ---- the distance from the voxel centres to the mesh -------------------------------------------
+    def MeshDistanceField(self, format=MDIST_VOXELS_F32, band=0, triangles=False, sync=True, frameIndex=None):
+        """The exact Euclidean distance from every voxel centre of the selected frame's last launch (the whole grid or a contiguous slab)
+        to the nearest triangle, negative where the frame's grid byte is non-zero (dxv_mesh_distance / dxv_mesh_distance_async).
+        format MDIST_VOXELS_F32: voxel units like DistanceField; MDIST_UNITS_F32: normalised units.  band > 0 caps the distance at that
+        many voxels; triangles=True keeps the nearest triangle's index per voxel (MeshDistanceTriangles).  sync=True returns the field as
+        a float32 numpy array [nz, N, N] (z, y, x); sync=False only enqueues it behind the frame's launch and returns True."""
+        if frameIndex is not None:
+            self.SetFrame(frameIndex)
+        if format not in (MDIST_VOXELS_F32, MDIST_UNITS_F32):
+            raise DxvError(f"MeshDistanceField: unknown format {format!r} (MDIST_VOXELS_F32 = 0, MDIST_UNITS_F32 = 1)")
+        fn = self._lib.dxv_mesh_distance if sync else self._lib.dxv_mesh_distance_async
+        self._check(fn(self._ctx, int(format), int(band), 1 if triangles else 0))
+        return self.MeshDistance() if sync else True
+
+    def _mdist_array(self, dtype):
+        """an empty array of the selected frame's field: the library's own record of the frame's last launch (dxv_get_stats: grid_dim, nz),
+        which is the field's while the field is current"""
+        nbytes = self._lib.dxv_mesh_distance_bytes(self._ctx)
+        st = self.stats()
+        n, nz = (st["grid_dim"], st["nz"]) if nbytes else (0, 0)
+        if n * n * nz * 4 != nbytes:
+            raise DxvError(f"mesh distance field of {nbytes} bytes does not belong to the frame's last launch ({n}^2 x {nz} voxels)")
+        return np.empty((nz, n, n), dtype)
+
+    def MeshDistance(self):
+        """numpy copy of the selected frame's mesh distance field (dxv_mesh_distance_download; synchronises the frame)."""
+        out = self._mdist_array(np.float32)
+        self._check(self._lib.dxv_mesh_distance_download(self._ctx, out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+    def MeshDistanceTriangles(self):
+        """numpy copy (uint32) of the nearest triangle per voxel, 0xffffffff beyond the band (dxv_mesh_distance_triangles_download); raises
+        when the field was made without them."""
+        out = self._mdist_array(np.uint32)
+        self._check(self._lib.dxv_mesh_distance_triangles_download(self._ctx, out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+    def mesh_distance_device_ptr(self):
+        """Device pointer of the selected frame's mesh distance field (dxv_mesh_distance_device_ptr); raises where the library refuses
+        (no field yet, or the frame was launched or filled again since)."""
+        p = self._lib.dxv_mesh_distance_device_ptr(self._ctx)
+        if not p:
+            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
+        return p
+
+    def mesh_distance_ms(self):
+        """Device time of the selected frame's last mesh distance field, read at the frame's Sync (dxv_mesh_distance_ms)."""
+        ms = C.c_float()
+        self._check(self._lib.dxv_mesh_distance_ms(self._ctx, C.byref(ms)))
         return ms.value
 
     # ---- the exterior flood fill of the frame's grid -----------------------------------------------

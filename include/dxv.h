@@ -385,6 +385,53 @@ DXV_API int dxv_fill(dxv_ctx* ctx, int what);
  * (HIP events, option events = 1; else 0) and the rounds it took, the confirming one included.  Either pointer may be NULL. */
 DXV_API int dxv_fill_info(dxv_ctx* ctx, float* ms, uint32_t* rounds);
 
+/* The exact signed distance from every voxel centre to the MESH, computed on the device by a nearest-triangle query over the scene's
+ * hierarchy (no reference counterpart).  dxv_distance above is the field of the GRID -- integer geometry, no |d| below 1, its zero set the
+ * staircase of the voxelization; this one is the Euclidean distance to the nearest triangle to sub-voxel accuracy, what collision and
+ * clearance queries, offsetting, sphere tracing and level sets want.  Only its SIGN is the grid's: negative where the frame's grid byte
+ * is non-zero, so dxv_voxelize + dxv_mesh_distance gives the field of a well-behaved mesh and dxv_voxelize(DXV_MODE_SURFACE) +
+ * dxv_fill(DXV_FILL_INTERIOR) + dxv_mesh_distance a robust signed field of a leaky one.
+ * For voxel p with centre ((ix+.5)/N*2-1, -((iy+.5)/N*2-1), (iz+.5)/N*2-1) -- the ray rule's -- and the scene's normalised triangles
+ *     f(p; a,b,c) = the smallest of the squared distances from p to the nearest point of each edge and to the foot of the perpendicular
+ *                   on the face where it lies inside (float32, fixed order: DESIGN.md section 2 writes every operation out)
+ *     d2(p)       = min over the triangles of f;  with a band of B > 0 voxels capped at (B * 2/N)^2
+ *     tri(p)      = the smallest index (in the caller's index buffer) among the triangles with f == d2(p); 0xffffffff where the cap is
+ *                   strictly smaller than every f
+ * A minimum does not depend on the order of its terms: the field equals a brute-force restatement bit for bit.  Against the same formula
+ * in float64 sqrt(d2) is within 2^-16 normalised units and never more than 2^-20 too small.
+ * One float per voxel of the frame's LAST LAUNCH, element ((iz - z0) * N + iy) * N + ix like the grid: the whole grid or a contiguous
+ * slab (which needs nothing from its neighbours). */
+enum {
+    DXV_MDIST_VOXELS_F32 = 0,    /* s(p) * (sqrtf(d2(p)) * (0.5f * N)):  voxel units, like dxv_distance                              */
+    DXV_MDIST_UNITS_F32 = 1      /* s(p) * sqrtf(d2(p)):                 normalised units (times bound[3] = object space)            */
+};
+/* dxv_mesh_distance_async -- ENQUEUED on the frame's stream behind its launch (render, field, fill); returns without waiting.
+ *  - The host waits only under dxv_render_async's rule; a pending fill is settled first.  After a dxv_refit that deferred the node boxes
+ *    they are brought up to date first, as before a tree walk.
+ *  - Checked on the host before anything is enqueued, each an error with a message: the format is one of the two; band_voxels <= 4096
+ *    (0: no band); the frame has been launched; its last launch was not an interleaved share; the context has a scene (built or imported).
+ *  - want_triangles != 0: tri(p) is stored beside the field (4 more bytes per voxel).
+ *  - Field and triangles belong to the frame: frames compute theirs side by side.  dxv_trim keeps them.
+ *  - The sign is the grid's as it is when the kernel runs (bytes written through dxv_grid_device_ptr count), the distances are the
+ *    scene's as it is then.
+ *  - Option events = 1 (default): bracketed by the frame's own two events; dxv_mesh_distance_ms reads them.
+ * dxv_mesh_distance -- the same + dxv_sync. */
+DXV_API int dxv_mesh_distance_async(dxv_ctx* ctx, int format, uint32_t band_voxels, int want_triangles);
+DXV_API int dxv_mesh_distance(dxv_ctx* ctx, int format, uint32_t band_voxels, int want_triangles);
+/* The selected frame's field on the device (valid after dxv_sync or on the frame's stream) and its size, 4 bytes per voxel of the launch.
+ * NULL / 0 before the frame's first field.  The field is STALE once its frame is launched or filled again: pointer, size and download
+ * then fail (NULL, 0, 1; message through dxv_last_error). */
+DXV_API const void* dxv_mesh_distance_device_ptr(const dxv_ctx* ctx);
+DXV_API size_t dxv_mesh_distance_bytes(const dxv_ctx* ctx);
+DXV_API int dxv_mesh_distance_download(dxv_ctx* ctx, void* host, size_t bytes);
+/* ... and its nearest triangles, uint32 per voxel (dxv_mesh_distance_bytes as well): NULL / 1 with a message when the field was made
+ * without them. */
+DXV_API const void* dxv_mesh_distance_triangles_device_ptr(const dxv_ctx* ctx);
+DXV_API int dxv_mesh_distance_triangles_download(dxv_ctx* ctx, void* host, size_t bytes);
+/* Device time of the selected frame's last mesh distance field in milliseconds (HIP events), read at the frame's dxv_sync: 0 before
+ * that, and under option events = 0. */
+DXV_API int dxv_mesh_distance_ms(dxv_ctx* ctx, float* ms);
+
 /* Multi-GPU: the built scene (nodes + triangle data) as one relocatable device blob, so that
  * rank 0 builds once and the host layer broadcasts it (RCCL over xGMI) to the other ranks.
  * export copies the blob into caller-provided DEVICE memory; import adopts a blob from DEVICE
@@ -502,6 +549,8 @@ DXV_API int dxv_get_stats(const dxv_ctx* ctx, dxv_stats* out);
  *                 holds); a triangle whose items do not all fit is walked whole as well.  Same grids.
  *   fillrounds 0..64  dxv_fill*: rounds of one batch (0, default: 4 -- the meshes measured take 2 or 3); a fill that needs more is continued
  *                 where its frame is next synchronised.  Same grids.
+ *   mdistwalk 0|1 dxv_mesh_distance*: 1 (default) = nearest-triangle query over the hierarchy; 0 = every triangle for every voxel, the
+ *                 on-device cross-check (seconds on large scenes).  Same field.
  *   morton 0|1, region 0..24, subbox 0|1   brick order, bricks per XCD region (log2), partial launch */
 DXV_API int dxv_set_option(dxv_ctx* ctx, const char* key, int64_t value);
 

@@ -165,6 +165,21 @@ public:
 		return dxv_distance_download(m_ctx, field.data(), field.size()) == 0;
 	}
 
+	// The exact distance from the voxel centres of that frame's last launch to the mesh, signed by the frame's grid (dxv_mesh_distance_async:
+	// enqueued behind the frame's launch and fill, one float per voxel, DXV_MDIST_VOXELS_F32 or DXV_MDIST_UNITS_F32; bandVoxels > 0 caps it).
+	// DeviceMeshDistance / DownloadMeshDistance refer to the frame last selected; WaitFrame reports the kernel's errors.
+	bool MeshDistanceField(uint8_t frameIndex, int format = DXV_MDIST_VOXELS_F32, uint32_t bandVoxels = 0, bool triangles = false)
+	{
+		return SetFrame(frameIndex) && dxv_mesh_distance_async(m_ctx, format, bandVoxels, triangles ? 1 : 0) == 0;
+	}
+	const void* DeviceMeshDistance() const { return m_ctx ? dxv_mesh_distance_device_ptr(m_ctx) : nullptr; }
+	bool DownloadMeshDistance(std::vector<float>& field)
+	{
+		if (!m_ctx) return setError("DownloadMeshDistance before Init");
+		field.resize(dxv_mesh_distance_bytes(m_ctx) / sizeof(float));
+		return dxv_mesh_distance_download(m_ctx, field.data(), field.size() * sizeof(float)) == 0;
+	}
+
 	// The exterior flood fill of that frame's whole grid, in place (dxv_fill / dxv_fill_async): DXV_FILL_SOLID leaves the walls and everything
 	// they enclose, DXV_FILL_INTERIOR the enclosed voxels alone.  Voxelize(gridDim, SURFACE) && Fill() is the solid of a mesh whose
 	// normals and watertightness cannot be trusted.  Refers to the frame last selected; sync = false only enqueues (WaitFrame reports).
