@@ -88,6 +88,14 @@ SYMBOLS = {
     "dxv_mesh_distance_triangles_device_ptr": (C.c_void_p, [C.c_void_p]),
     "dxv_mesh_distance_triangles_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "dxv_mesh_distance_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "dxv_isosurface_async": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int]),
+    "dxv_isosurface": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int]),
+    "dxv_isosurface_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "dxv_isosurface_vertices_device_ptr": (C.c_void_p, [C.c_void_p]),
+    "dxv_isosurface_indices_device_ptr": (C.c_void_p, [C.c_void_p]),
+    "dxv_isosurface_vertices_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_isosurface_indices_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_isosurface_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "dxv_fill_async": (C.c_int, [C.c_void_p, C.c_int]),
     "dxv_fill": (C.c_int, [C.c_void_p, C.c_int]),
     "dxv_fill_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),

@@ -212,6 +212,7 @@ struct dxv_ctx {
         DevBuf<uint8_t> distScratch;     // (cap: bytes) distance_scratch_bytes: the x pass's 16-bit values, the y pass's squares
         uint32_t distDim = 0;            // grid side of the frame's last field (0: none yet)
         bool distCurrent = false;        // ... which is the field of the frame's last launch (a new launch makes it stale)
+        int distFormat = 0;              // ... and its format (DXV_DIST_SQ_I32 / DXV_DIST_F32)
         hipEvent_t evD0 = nullptr, evD1 = nullptr;   // around the frame's last field
         bool distTimed = false;          // ... which was bracketed by them and not read yet (the frame's next dxv_sync reads it)
         float dist_ms = 0.0f;
@@ -241,6 +242,17 @@ struct dxv_ctx {
         hipEvent_t evF0 = nullptr, evF1 = nullptr;   // around the frame's last fill (evF1: behind its last batch)
         bool fillTimed = false;          // ... which was bracketed by them and not read yet
         float fill_ms = 0.0f;
+        // isosurface (isosurface.hip; dxv_isosurface_async): the triangle mesh of one of the frame's fields and the scratch of its extraction
+        // (a bit per lattice cell, two counts per 64 cells, the scan's sums), the frame's own; the scratch goes with dxv_trim, the mesh stays
+        DevBuf<uint8_t> isoVb;           // (cap: vertices) 24 bytes each
+        DevBuf<uint32_t> isoIb;          // (cap: index words)
+        DevBuf<uint8_t> isoScratch;      // (cap: bytes) iso_scratch_bytes
+        uint32_t isoVertices = 0, isoTriangles = 0;   // of the frame's last mesh
+        bool isoHave = false;            // the frame has had a mesh extracted (an empty one counts) ...
+        bool isoCurrent = false;         // ... and it belongs to the frame's grid as it is (a new launch or a fill makes it stale)
+        hipEvent_t evI0 = nullptr, evI1 = nullptr;   // around the frame's last extraction
+        bool isoTimed = false;           // ... which was bracketed by them and not read yet (the frame's next dxv_sync reads it)
+        float iso_ms = 0.0f;
     };
     Frame frames[DXV_FRAME_COUNT];
     uint32_t cur = 0;                    // dxv_set_frame
@@ -270,6 +282,7 @@ struct dxv_ctx {
         uint32_t queueLens[DXV_FRAME_COUNT][16 * 64];    // the sixteen count words of a frame's queue (light and heavy bricks of the eight queues; each in a 256-byte line of its own)
         uint32_t preparedLens[16 * 64];                  // ... of a queue that is being prepared
         uint32_t fillCtl[DXV_FRAME_COUNT][64];           // the control block of a frame's last fill batch (kFillMaxRounds words)
+        unsigned long long isoTotals[DXV_FRAME_COUNT][2]; // vertices and quads of the mesh a frame is extracting: sizes its buffers
     };
     Pinned* pin = nullptr;
     hipEvent_t evList[4] = {};       // around the counting pass, around the rest of the build

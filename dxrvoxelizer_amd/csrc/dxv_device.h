@@ -217,6 +217,29 @@ struct MeshDistanceParams {
 };
 hipError_t launch_mesh_distance(const Node* nodes, const TriPos* triPos, uint32_t T, const MeshDistanceParams& p, bool walk, hipStream_t s);
 
+// isosurface.hip -- a triangle mesh from a float32 field of a whole N^3 grid by naive Surface Nets (dxv_isosurface.h): count + scan, ONE
+// read of the two totals by the caller, emit.  scratch: iso_scratch_bytes(N) -- one bit per lattice cell, two counts per 64 cells, the
+// scan's block sums, the totals.  vb: 24 bytes per vertex, ib: three uint32 per triangle, two triangles per quad.
+struct IsoVertex;
+struct IsoCounts;
+struct IsoParams {
+    const float* field;     // N^3 floats, element (iz * N + iy) * N + ix
+    uint32_t N;
+    float iso, P;           // the level, and one voxel in the field's unit: what a sample outside the grid is worth
+    int object;             // 0: vertices in voxel index space, 1: in object space through `bound` (triangles turned round: y is mirrored)
+    float bound[4];
+    uint64_t* masks;        // iso_scratch_layout fills these four
+    IsoCounts* bases;
+    unsigned long long* sums;
+    unsigned long long* totals;   // {vertices, quads} of the whole mesh
+    IsoVertex* vb;
+    uint32_t* ib;
+};
+size_t iso_scratch_bytes(uint32_t N);
+void iso_scratch_layout(uint8_t* scratch, uint32_t N, IsoParams& p);
+hipError_t launch_iso_count(const IsoParams& p, hipStream_t s);
+hipError_t launch_iso_emit(const IsoParams& p, hipStream_t s);
+
 // raycast.hip
 struct RayCastCB;
 hipError_t launch_raycast(const RayCastCB& cb, const uint8_t* grid, uint32_t N, uint32_t width, uint32_t height,

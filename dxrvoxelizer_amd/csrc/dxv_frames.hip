@@ -4,6 +4,7 @@
 #include "dxv_ctx.h"
 #include "dxv_mesh_distance.h"
 #include "dxv_fill.h"
+#include "dxv_isosurface.h"
 
 using namespace dxv;
 using namespace dxvhost;
@@ -29,6 +30,8 @@ int frame_prepare(dxv_ctx* c, uint32_t i)
     if (!f.evM1) DXV_HIP(c, hipEventCreate(&f.evM1));
     if (!f.evF0) DXV_HIP(c, hipEventCreate(&f.evF0));
     if (!f.evF1) DXV_HIP(c, hipEventCreate(&f.evF1));
+    if (!f.evI0) DXV_HIP(c, hipEventCreate(&f.evI0));
+    if (!f.evI1) DXV_HIP(c, hipEventCreate(&f.evI1));
     DXV_HIP(c, f.status.reserve(64, 256));
     DXV_HIP(c, f.redo.reserve(kRedoCap, sizeof(uint64_t) * kRedoCap));
     // on the frame's own stream, and finished before anything reads the words: the streams are non-blocking, a memset on the
@@ -548,6 +551,7 @@ int voxelize_common(dxv_ctx* c, uint32_t N, int mode, uint32_t z0, uint32_t nzLo
     f.lastMode = mode; f.lastZBlock = zBlock; f.lastZPeriod = zPeriod;
     f.distCurrent = false;                                              // (a field of the grid this launch replaces is stale)
     f.mdistCurrent = false;
+    f.isoCurrent = false;
     f.fillPending = false;                                              // (... and a fill of it that has not converged yet is dropped: its batch in the stream ends in front of this launch)
     return launch_now(c, c->cur);
 }
@@ -568,6 +572,7 @@ static int sync_launch(dxv_ctx* c, uint32_t i)
         if (f.renderTimed) { f.render_ms = elapsed(f.evR0, f.evR1); f.renderTimed = false; }
         if (f.distTimed) { f.dist_ms = elapsed(f.evD0, f.evD1); f.distTimed = false; }
         if (f.mdistTimed) { f.mdist_ms = elapsed(f.evM0, f.evM1); f.mdistTimed = false; }
+        if (f.isoTimed) { f.iso_ms = elapsed(f.evI0, f.evI1); f.isoTimed = false; }
         // lists this launch was queued behind without waiting for their verdict: withdrawn -> the launch again, through the tree
         if (settle_lists(c)) return 1;
         if (f.pending && f.usedLists && f.listEpochUsed == c->withdrawnEpoch && c->haveScene && f.grid_dim) {
@@ -754,7 +759,7 @@ int dxv_distance_async(dxv_ctx* c, int format)
     if (timed) DXV_HIP(c, hipEventRecord(f.evD1, fs));
     DXV_HIP(c, hipEventRecord(f.evEnd, fs));
     f.distTimed = timed;
-    f.distDim = N; f.distCurrent = true;
+    f.distDim = N; f.distFormat = format; f.distCurrent = true;
     return 0;
 }
 
@@ -899,6 +904,137 @@ int dxv_mesh_distance_ms(dxv_ctx* c, float* ms)
     return 0;
 }
 
+// The isosurface of one of the selected frame's fields (isosurface.hip; dxv_isosurface.h has the rule), enqueued on the frame's stream behind
+// whatever it holds, under dxv_render_async's host-wait rule: the count and scan kernels, the two totals into page-locked words and the
+// one wait for them -- the pattern of dxv_prepare_launch's sixteen counts: the mesh's buffers cannot be sized without them --, then the emit
+// kernel and the frame's end event, which nobody waits for here.
+int dxv_isosurface_async(dxv_ctx* c, int source, float iso, int space)
+{
+    if (!c) return 1;
+    if (source != DXV_ISO_MESH_DISTANCE && source != DXV_ISO_GRID_DISTANCE)
+        return fail(c, "dxv_isosurface: unknown source %d (DXV_ISO_MESH_DISTANCE = 0, DXV_ISO_GRID_DISTANCE = 1)", source);
+    if (space != DXV_ISO_SPACE_VOXELS && space != DXV_ISO_SPACE_OBJECT)
+        return fail(c, "dxv_isosurface: unknown space %d (DXV_ISO_SPACE_VOXELS = 0, DXV_ISO_SPACE_OBJECT = 1)", space);
+    if (!std::isfinite(iso)) return fail(c, "dxv_isosurface: iso must be finite, got %g", (double)iso);
+    Frame& f = cur_frame(c);
+    const float* field = nullptr;
+    uint32_t N = 0;
+    float P = 1.0f;
+    if (source == DXV_ISO_MESH_DISTANCE) {
+        if (!f.mdistDim || !f.mdist.p) return fail(c, "dxv_isosurface: frame %u has no mesh distance field yet (call dxv_mesh_distance first)", c->cur);
+        if (!f.mdistCurrent) return fail(c, "dxv_isosurface: frame %u was launched or filled again since its mesh distance field was made: the field is stale", c->cur);
+        if (f.mdistNz != f.mdistDim)
+            return fail(c, "dxv_isosurface: the frame's mesh distance field is a slab's (%u of %u slices); needs the field of the whole grid", f.mdistNz, f.mdistDim);
+        field = f.mdist.p; N = f.mdistDim;
+        if (f.mdistFormat == DXV_MDIST_UNITS_F32) P = 2.0f / (float)N;
+    } else {
+        if (!f.distDim || !f.dist.p) return fail(c, "dxv_isosurface: frame %u has no distance field yet (call dxv_distance first)", c->cur);
+        if (!f.distCurrent) return fail(c, "dxv_isosurface: frame %u was launched or filled again since its distance field was made: the field is stale", c->cur);
+        if (f.distFormat != DXV_DIST_F32) return fail(c, "dxv_isosurface: the frame's distance field is in the int32 format; needs DXV_DIST_F32");
+        field = reinterpret_cast<const float*>(f.dist.p); N = f.distDim;
+    }
+    if (space == DXV_ISO_SPACE_OBJECT && !c->haveScene)
+        return fail(c, "dxv_isosurface: DXV_ISO_SPACE_OBJECT needs the scene's bound and the context has no scene (call dxv_build or dxv_scene_import, or ask for DXV_ISO_SPACE_VOXELS)");
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (settle_frame_launch(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    const size_t scratch = iso_scratch_bytes(N);
+    DXV_HIP(c, f.isoScratch.reserve(scratch, scratch, fs));
+    IsoParams p{};
+    p.field = field; p.N = N; p.iso = iso; p.P = P; p.object = space == DXV_ISO_SPACE_OBJECT;
+    memcpy(p.bound, c->bound, sizeof(p.bound));
+    iso_scratch_layout(f.isoScratch.p, N, p);
+    const bool timed = c->opt.events != 0;
+    unsigned long long* totals = c->pin->isoTotals[c->cur];
+    if (timed) DXV_HIP(c, hipEventRecord(f.evI0, fs));
+    DXV_HIP(c, launch_iso_count(p, fs));
+    DXV_HIP(c, hipMemcpyAsync(totals, p.totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipStreamSynchronize(fs));
+    const unsigned long long vertices = totals[0], quads = totals[1];
+    if (vertices > kIsoMaxCount || quads > kIsoMaxCount / 6u) {
+        f.isoTimed = false;                                             // (the first event was recorded again: the pair is no pair any more)
+        return fail(c, "dxv_isosurface: a mesh of %llu vertices and %llu index words; at most %llu of each (the frame's earlier mesh is kept)", vertices,
+                    6u * quads, (unsigned long long)kIsoMaxCount);
+    }
+    f.isoCurrent = false;
+    if (vertices) {
+        DXV_HIP(c, f.isoVb.reserve((size_t)vertices, align256((size_t)vertices * sizeof(IsoVertex)), fs));
+        if (quads) DXV_HIP(c, f.isoIb.reserve(6 * (size_t)quads, align256(6 * (size_t)quads * sizeof(uint32_t)), fs));
+        p.vb = reinterpret_cast<IsoVertex*>(f.isoVb.p); p.ib = f.isoIb.p;
+        DXV_HIP(c, launch_iso_emit(p, fs));
+    }
+    if (timed) DXV_HIP(c, hipEventRecord(f.evI1, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    f.isoTimed = timed;
+    f.isoVertices = (uint32_t)vertices; f.isoTriangles = (uint32_t)(2u * quads);
+    f.isoHave = true; f.isoCurrent = true;
+    return 0;
+}
+
+int dxv_isosurface(dxv_ctx* c, int source, float iso, int space)
+{
+    if (dxv_isosurface_async(c, source, iso, space)) return 1;
+    return dxv_sync(c);
+}
+
+// whether the frame has a mesh to hand out: 0, or 1 with the reason as the message
+static int current_mesh(const dxv_ctx* c, const char* who)
+{
+    const Frame& f = c->frames[c->cur];
+    dxv_ctx* w = const_cast<dxv_ctx*>(c);                               // (the message is the one thing an accessor writes)
+    if (!f.isoHave) return fail(w, "%s: frame %u has no isosurface yet (call dxv_isosurface first)", who, c->cur);
+    if (!f.isoCurrent) return fail(w, "%s: frame %u was launched or filled again since its isosurface was made: the mesh is stale", who, c->cur);
+    return 0;
+}
+
+int dxv_isosurface_counts(dxv_ctx* c, uint32_t* vertices, uint32_t* triangles)
+{
+    if (!c) return 1;
+    if (current_mesh(c, "dxv_isosurface_counts")) return 1;
+    if (vertices) *vertices = cur_frame(c).isoVertices;
+    if (triangles) *triangles = cur_frame(c).isoTriangles;
+    return 0;
+}
+
+const void* dxv_isosurface_vertices_device_ptr(const dxv_ctx* c)
+{
+    if (!c || current_mesh(c, "dxv_isosurface_vertices_device_ptr")) return nullptr;
+    return c->frames[c->cur].isoVertices ? c->frames[c->cur].isoVb.p : nullptr;
+}
+const void* dxv_isosurface_indices_device_ptr(const dxv_ctx* c)
+{
+    if (!c || current_mesh(c, "dxv_isosurface_indices_device_ptr")) return nullptr;
+    return c->frames[c->cur].isoTriangles ? c->frames[c->cur].isoIb.p : nullptr;
+}
+
+static int mesh_download(dxv_ctx* c, const char* who, const void* src, size_t want, void* host, size_t bytes)
+{
+    if ((!host && want) || bytes != want) return fail(c, "%s: expected %zu bytes, got %zu", who, want, bytes);
+    if (dxv_sync(c)) return 1;
+    if (!want) return 0;
+    DXV_HIP(c, hipMemcpyAsync(host, src, bytes, hipMemcpyDeviceToHost, cur_stream(c)));
+    DXV_HIP(c, hipStreamSynchronize(cur_stream(c)));
+    return 0;
+}
+int dxv_isosurface_vertices_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || current_mesh(c, "dxv_isosurface_vertices_download")) return 1;
+    return mesh_download(c, "dxv_isosurface_vertices_download", cur_frame(c).isoVb.p, (size_t)cur_frame(c).isoVertices * sizeof(IsoVertex), host, bytes);
+}
+int dxv_isosurface_indices_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || current_mesh(c, "dxv_isosurface_indices_download")) return 1;
+    return mesh_download(c, "dxv_isosurface_indices_download", cur_frame(c).isoIb.p, (size_t)cur_frame(c).isoTriangles * 3u * sizeof(uint32_t), host, bytes);
+}
+
+int dxv_isosurface_ms(dxv_ctx* c, float* ms)
+{
+    if (!c) return 1;
+    if (!ms) return fail(c, "dxv_isosurface_ms: ms is NULL");
+    *ms = cur_frame(c).iso_ms;
+    return 0;
+}
+
 // The exterior flood fill of the selected frame's grid (fill.hip), in place, enqueued on the frame's stream behind whatever it holds --
 // under dxv_render_async's host-wait rule: one batch of rounds, the write-back, the batch's control block into page-locked words, the
 // frame's end event.  Whether the batch converged is read where the frame is next synchronised (settle_fill).
@@ -926,6 +1062,7 @@ int dxv_fill_async(dxv_ctx* c, int what)
     f.clearSig = 0;
     f.distCurrent = false;
     f.mdistCurrent = false;
+    f.isoCurrent = false;
     if (timed) DXV_HIP(c, hipEventRecord(f.evF0, fs));
     DXV_HIP(c, launch_fill(f.grid.p, N, what, f.fillScratch.p, f.fillBatch, true, fs));
     if (timed) DXV_HIP(c, hipEventRecord(f.evF1, fs));

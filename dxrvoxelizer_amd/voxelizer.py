@@ -13,6 +13,8 @@ MODE_SURFACE, MODE_REFERENCE_SURFACE = 2, 3      # the conservative surface; the
 DIST_SQ_I32, DIST_F32 = 0, 1                     # formats of the distance field (include/dxv.h)
 MDIST_VOXELS_F32, MDIST_UNITS_F32 = 0, 1          # formats of the mesh distance field (include/dxv.h)
 FILL_SOLID, FILL_INTERIOR = 0, 1                  # what the flood fill leaves (include/dxv.h)
+ISO_MESH_DISTANCE, ISO_GRID_DISTANCE = 0, 1       # the field an isosurface is taken from (include/dxv.h)
+ISO_SPACE_VOXELS, ISO_SPACE_OBJECT = 0, 1         # ... and the space its vertices are in
 DBG_SORTED_KEYS, DBG_NODES, DBG_TRI_POS, DBG_TRI_NRM, DBG_PARENTS, DBG_NODES32, DBG_NODES64, DBG_LIST_CELLS, DBG_LIST_ENTRIES, DBG_LIST_MIP = range(10)
 DBG_BRICK_EMPTY, DBG_BRICK_SUMMARY = 10, 11         # the display pass's empty-brick flags and the summaries behind them
 
@@ -345,6 +347,50 @@ class Voxelizer:
         """Device time of the selected frame's last mesh distance field, read at the frame's Sync (dxv_mesh_distance_ms)."""
         ms = C.c_float()
         self._check(self._lib.dxv_mesh_distance_ms(self._ctx, C.byref(ms)))
+        return ms.value
+
+    # ---- the isosurface of one of the frame's fields ------------------------------------------------
+    def Isosurface(self, source=ISO_MESH_DISTANCE, iso=0.0, space=ISO_SPACE_OBJECT, sync=True, frameIndex=None):
+        """A closed triangle mesh of the level `iso` of the selected frame's mesh distance field (ISO_MESH_DISTANCE) or of its grid distance
+        field in DIST_F32 (ISO_GRID_DISTANCE), by naive Surface Nets on the device (dxv_isosurface / dxv_isosurface_async); iso in the
+        field's unit.  space ISO_SPACE_OBJECT: the space of the mesh Init was given, so (vb, ib) go back into InitFromArrays as they are;
+        ISO_SPACE_VOXELS: voxel index space.  sync=True returns (vb [V, 6] float32 {pos, nrm}, ib [3T] uint32); sync=False only enqueues
+        the emit pass (the call still reads the mesh's two sizes once) and returns True (IsosurfaceMesh after a Sync)."""
+        if frameIndex is not None:
+            self.SetFrame(frameIndex)
+        if source not in (ISO_MESH_DISTANCE, ISO_GRID_DISTANCE):
+            raise DxvError(f"Isosurface: unknown source {source!r} (ISO_MESH_DISTANCE = 0, ISO_GRID_DISTANCE = 1)")
+        if space not in (ISO_SPACE_VOXELS, ISO_SPACE_OBJECT):
+            raise DxvError(f"Isosurface: unknown space {space!r} (ISO_SPACE_VOXELS = 0, ISO_SPACE_OBJECT = 1)")
+        fn = self._lib.dxv_isosurface if sync else self._lib.dxv_isosurface_async
+        self._check(fn(self._ctx, int(source), float(iso), int(space)))
+        return self.IsosurfaceMesh() if sync else True
+
+    def IsosurfaceCounts(self):
+        """(vertices, triangles) of the selected frame's mesh (dxv_isosurface_counts); raises where the library refuses (no mesh yet, or
+        the frame was launched or filled again since)."""
+        nv, nt = C.c_uint32(), C.c_uint32()
+        self._check(self._lib.dxv_isosurface_counts(self._ctx, C.byref(nv), C.byref(nt)))
+        return nv.value, nt.value
+
+    def IsosurfaceMesh(self):
+        """numpy copies (vb [V, 6] float32, ib [3T] uint32) of the selected frame's mesh (dxv_isosurface_*_download; synchronises the frame)."""
+        nv, nt = self.IsosurfaceCounts()
+        vb, ib = np.empty((nv, 6), np.float32), np.empty(3 * nt, np.uint32)
+        self._check(self._lib.dxv_isosurface_vertices_download(self._ctx, vb.ctypes.data_as(C.c_void_p), vb.nbytes))
+        self._check(self._lib.dxv_isosurface_indices_download(self._ctx, ib.ctypes.data_as(C.c_void_p), ib.nbytes))
+        return vb, ib
+
+    def isosurface_device_ptrs(self):
+        """Device pointers (vertices, indices) of the selected frame's mesh, for consumers on the GPU; (None, None) for the empty mesh;
+        raises where the library refuses."""
+        self.IsosurfaceCounts()
+        return self._lib.dxv_isosurface_vertices_device_ptr(self._ctx), self._lib.dxv_isosurface_indices_device_ptr(self._ctx)
+
+    def isosurface_ms(self):
+        """Device time of the selected frame's last extraction, read at the frame's Sync (dxv_isosurface_ms)."""
+        ms = C.c_float()
+        self._check(self._lib.dxv_isosurface_ms(self._ctx, C.byref(ms)))
         return ms.value
 
     # ---- the exterior flood fill of the frame's grid -----------------------------------------------

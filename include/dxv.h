@@ -191,7 +191,7 @@ DXV_API int dxv_sync(dxv_ctx* ctx);
  * frameIndex (static const uint8_t FrameCount, Content/Voxelizer.h:24; m_grids[FrameCount], :110;
  * Render(pCommandList, frameIndex, ...), :21-22; voxelize(pCommandList, frameIndex), Content/Voxelizer.cpp:351-356),
  * so that the GPU works on one grid while the host still reads another.  dxv_set_frame selects the frame the
- * following dxv_voxelize* / dxv_sync / dxv_grid_* / dxv_texels_download / dxv_render* / dxv_update_frame / dxv_distance* / dxv_fill* / dxv_get_stats calls refer to
+ * following dxv_voxelize* / dxv_sync / dxv_grid_* / dxv_texels_download / dxv_render* / dxv_update_frame / dxv_distance* / dxv_fill* / dxv_isosurface* / dxv_get_stats calls refer to
  * (default 0).  Each frame owns its grid, texel image, status words and -- frames 1 and 2 -- an internal stream,
  * so launches of different frames overlap on the GPU; scene, candidate lists and options are shared (an extra frame
  * costs its grid).  Calls that change what the frames read (dxv_set_mesh, dxv_build, dxv_scene_import, dxv_set_stream) first
@@ -432,6 +432,56 @@ DXV_API int dxv_mesh_distance_triangles_download(dxv_ctx* ctx, void* host, size_
  * that, and under option events = 0. */
 DXV_API int dxv_mesh_distance_ms(dxv_ctx* ctx, float* ms);
 
+/* Isosurface extraction: a closed triangle mesh from one of the selected frame's signed fields, on the device (no reference counterpart) --
+ * the watertight remesh of a leaky model (dxv_voxelize(DXV_MODE_SURFACE) + dxv_fill(DXV_FILL_INTERIOR) + dxv_mesh_distance + dxv_isosurface),
+ * an offset surface at iso != 0, a collision proxy at a chosen resolution.  Naive Surface Nets: one vertex in every lattice cell with a sign
+ * change, one quad (two triangles) on every lattice edge with one; no case tables, closed and consistently oriented by construction, every
+ * arithmetic step fixed (DESIGN.md section 2 writes each out), so the buffers equal a restatement byte for byte.
+ *     samples   s(i,j,k) = field[(k*N + j)*N + i] - iso inside the grid; one layer of padding around it is worth +P, one voxel in the field's
+ *               unit (1 for the voxel-unit formats, 2 / N for DXV_MDIST_UNITS_F32): a solid that touches the grid's border is capped.
+ *               inside(v) iff v < 0 (so -0, +0 and NaN are outside)
+ *     vertices  one per cell (cx,cy,cz), each index 0 .. N, whose 8 corners -- the samples c - 1 + (dx,dy,dz) -- are neither all inside nor
+ *               all outside: the mean of the linear crossings of the cell's edges (the middle of an edge with a non-finite end), with the
+ *               normalised sum of the edges' differences as its normal, pointing out of the solid; ascending cell index
+ *               (cz*(N+1) + cy)*(N+1) + cx.  24 bytes {float3 pos, float3 nrm}: an input of dxv_set_mesh as it is
+ *     triangles two per crossing lattice edge, over the four cells around it, (b-a) x (c-a) pointing out of the solid in the output space;
+ *               uint32 indices; ascending owning cell (the one whose minimum corner is the edge's first sample), then axis x, y, z
+ * An all-positive field gives the empty mesh: 0 vertices, 0 triangles, NULL pointers, downloads of 0 bytes -- a success. */
+enum {
+    DXV_ISO_MESH_DISTANCE = 0,   /* the frame's dxv_mesh_distance field, either format; must be the whole grid's, not a slab's */
+    DXV_ISO_GRID_DISTANCE = 1    /* the frame's dxv_distance field in DXV_DIST_F32 (the int32 format is refused)             */
+};
+enum {
+    DXV_ISO_SPACE_VOXELS = 0,    /* voxel index space: coordinate i is the centre of voxel i                                  */
+    DXV_ISO_SPACE_OBJECT = 1     /* q = (p + 0.5) / N * 2 - 1 with y and the normal's y negated, then q * bound[3] + bound[0..2]: the mesh's own
+                                  * space (needs the scene's bound); every triangle is turned round, because y is mirrored    */
+};
+/* dxv_isosurface_async -- count and scan kernels ENQUEUED on the frame's stream behind whatever it holds, then ONE host read of two totals
+ * (vertices, quads: the mesh's buffers cannot be sized without them), then the emit kernel enqueued; returns without waiting for that.
+ *  - The host waits before that only under dxv_render_async's rule; a pending fill is settled first.
+ *  - Checked on the host before anything is enqueued, each an error with a message: source and space are known; iso is finite; the frame has
+ *    that field and it is not stale; a grid distance field is DXV_DIST_F32; a mesh distance field is the whole grid's; DXV_ISO_SPACE_OBJECT
+ *    has a scene to take the bound from.  A mesh of more than 2^31 - 1 vertices or index words is refused once its totals are known.
+ *  - Mesh (grow-only vertex and index buffers) and scratch (one bit per lattice cell, two counts per 64 cells) belong to the frame: frames
+ *    extract side by side.  dxv_trim gives the scratch back, the mesh stays.
+ *  - The mesh is STALE once its frame is launched or filled again: counts, pointers and downloads then fail with a message.
+ *  - Option events = 1 (default): bracketed by the frame's own two events; dxv_isosurface_ms reads them at the frame's dxv_sync.
+ * dxv_isosurface -- the same + dxv_sync. */
+DXV_API int dxv_isosurface_async(dxv_ctx* ctx, int source, float iso, int space);
+DXV_API int dxv_isosurface(dxv_ctx* ctx, int source, float iso, int space);
+/* Vertices and triangles of the selected frame's mesh (either pointer may be NULL). */
+DXV_API int dxv_isosurface_counts(dxv_ctx* ctx, uint32_t* vertices, uint32_t* triangles);
+/* The mesh on the device (valid after dxv_sync or on the frame's stream): 24 bytes per vertex, 12 per triangle.  NULL for the empty mesh,
+ * and -- with a message -- before the frame's first mesh or when it is stale. */
+DXV_API const void* dxv_isosurface_vertices_device_ptr(const dxv_ctx* ctx);
+DXV_API const void* dxv_isosurface_indices_device_ptr(const dxv_ctx* ctx);
+/* Copies to the host (bytes must be 24 * vertices / 12 * triangles; 0 bytes of the empty mesh are accepted); synchronise the frame first. */
+DXV_API int dxv_isosurface_vertices_download(dxv_ctx* ctx, void* host, size_t bytes);
+DXV_API int dxv_isosurface_indices_download(dxv_ctx* ctx, void* host, size_t bytes);
+/* Device time of the selected frame's last extraction in milliseconds (HIP events; the host's read of the totals lies inside it), read at
+ * the frame's dxv_sync: 0 before that, and under option events = 0. */
+DXV_API int dxv_isosurface_ms(dxv_ctx* ctx, float* ms);
+
 /* Multi-GPU: the built scene (nodes + triangle data) as one relocatable device blob, so that
  * rank 0 builds once and the host layer broadcasts it (RCCL over xGMI) to the other ranks.
  * export copies the blob into caller-provided DEVICE memory; import adopts a blob from DEVICE
@@ -591,7 +641,8 @@ DXV_API int dxv_debug_plan_check(dxv_ctx* ctx, uint64_t out[16]);
 
 /* Give back what the context keeps only to make the next build faster: the list build's scratch (up to 16 GiB per buffer
  * after a 10 M-triangle scene), the LBVH build's scratch when no refit can follow (imported scenes), the memory of prepared queues
- * whose lists are gone, the scratch of the frames' distance fields (the fields stay) and of their flood fills.  Nothing a launch reads. */
+ * whose lists are gone, the scratch of the frames' distance fields (the fields stay), of their flood fills and of their isosurfaces (the
+ * meshes stay).  Nothing a launch reads. */
 DXV_API int dxv_trim(dxv_ctx* ctx);
 
 /* Test hook: copy an internal device array to the host (enum above). */

@@ -180,6 +180,29 @@ public:
 		return dxv_mesh_distance_download(m_ctx, field.data(), field.size() * sizeof(float)) == 0;
 	}
 
+	// The isosurface of one of that frame's fields as a closed triangle mesh (dxv_isosurface_async: naive Surface Nets on the device; source
+	// DXV_ISO_MESH_DISTANCE or DXV_ISO_GRID_DISTANCE, the mesh in DXV_ISO_SPACE_OBJECT -- the space of the mesh Init was given -- or in
+	// DXV_ISO_SPACE_VOXELS).  The buffers have the layout Init's own take: 6 floats per vertex, 3 uint32 per triangle.  IsosurfaceCounts,
+	// DeviceIsosurface* and DownloadIsosurface refer to the frame last selected; WaitFrame reports the kernels' errors.
+	bool Isosurface(uint8_t frameIndex, int source = DXV_ISO_MESH_DISTANCE, float iso = 0.0f, int space = DXV_ISO_SPACE_OBJECT)
+	{
+		return SetFrame(frameIndex) && dxv_isosurface_async(m_ctx, source, iso, space) == 0;
+	}
+	bool IsosurfaceCounts(uint32_t& vertices, uint32_t& triangles) { return m_ctx && dxv_isosurface_counts(m_ctx, &vertices, &triangles) == 0; }
+	const void* DeviceIsosurfaceVertices() const { return m_ctx ? dxv_isosurface_vertices_device_ptr(m_ctx) : nullptr; }
+	const void* DeviceIsosurfaceIndices() const { return m_ctx ? dxv_isosurface_indices_device_ptr(m_ctx) : nullptr; }
+	bool DownloadIsosurface(std::vector<float>& vb, std::vector<uint32_t>& ib)
+	{
+		uint32_t vertices = 0, triangles = 0;
+		if (!m_ctx) return setError("DownloadIsosurface before Init");
+		if (dxv_isosurface_counts(m_ctx, &vertices, &triangles)) return false;
+		vb.resize(6 * (size_t)vertices);
+		ib.resize(3 * (size_t)triangles);
+		return dxv_isosurface_vertices_download(m_ctx, vb.data(), vb.size() * sizeof(float)) == 0 &&
+		       dxv_isosurface_indices_download(m_ctx, ib.data(), ib.size() * sizeof(uint32_t)) == 0;
+	}
+	bool IsosurfaceMs(float& ms) { return m_ctx && dxv_isosurface_ms(m_ctx, &ms) == 0; }
+
 	// The exterior flood fill of that frame's whole grid, in place (dxv_fill / dxv_fill_async): DXV_FILL_SOLID leaves the walls and everything
 	// they enclose, DXV_FILL_INTERIOR the enclosed voxels alone.  Voxelize(gridDim, SURFACE) && Fill() is the solid of a mesh whose
 	// normals and watertightness cannot be trusted.  Refers to the frame last selected; sync = false only enqueues (WaitFrame reports).
