@@ -96,6 +96,15 @@ SYMBOLS = {
     "dxv_isosurface_vertices_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "dxv_isosurface_indices_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "dxv_isosurface_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "dxv_octree_async": (C.c_int, [C.c_void_p]),
+    "dxv_octree": (C.c_int, [C.c_void_p]),
+    "dxv_octree_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "dxv_octree_device_ptr": (C.c_void_p, [C.c_void_p]),
+    "dxv_octree_bytes": (C.c_size_t, [C.c_void_p]),
+    "dxv_octree_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_octree_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "dxv_octree_expand_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    "dxv_octree_expand": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
     "dxv_fill_async": (C.c_int, [C.c_void_p, C.c_int]),
     "dxv_fill": (C.c_int, [C.c_void_p, C.c_int]),
     "dxv_fill_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),

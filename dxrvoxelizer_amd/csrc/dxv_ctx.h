@@ -25,11 +25,13 @@ constexpr uint32_t kRedoCap = 1u << 21;   // (diagnostic build: the list doubles
 #else
 constexpr uint32_t kRedoCap = 1u << 16;   // rays per launch the redo pass takes before the column is grown instead
 #endif
+constexpr uint32_t kOctStatusWord = 3;    // the word of a frame's status block an octree expansion raises (words 0 .. 2 are the launch's)
 inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 }
 
 using namespace dxv;
 using dxvhost::kRedoCap;
+using dxvhost::kOctStatusWord;
 
 // A device allocation together with the capacity it was made for.  The two cannot disagree (p is null exactly when cap is 0), the
 // memory is freed exactly once (release, or the end of the owner) and the value moves but does not copy -- so nothing that owns
@@ -253,6 +255,19 @@ struct dxv_ctx {
         hipEvent_t evI0 = nullptr, evI1 = nullptr;   // around the frame's last extraction
         bool isoTimed = false;           // ... which was bracketed by them and not read yet (the frame's next dxv_sync reads it)
         float iso_ms = 0.0f;
+        // sparse voxel octree (octree.hip; dxv_octree_async): the nodes of the frame's grid and the scratch of their build (two bytes per cell of
+        // levels 0 .. L - 1, a bit per cell, a count per 64 cells, the scan's sums), the frame's own; the scratch goes with dxv_trim, the nodes stay
+        DevBuf<uint32_t> octNodes;       // (cap: nodes) 8 bytes each
+        DevBuf<uint8_t> octScratch;      // (cap: bytes) oct_scratch_bytes
+        uint32_t octLevels = 0, octCount = 0;         // L and the nodes of the frame's last tree ...
+        uint32_t octLevelFirst[12] = {}; // ... and the first node of every level, [L] the total
+        bool octHave = false;            // the frame has had a tree built ...
+        bool octCurrent = false;         // ... and it belongs to the frame's grid as it is (a new launch, a fill or an expansion makes it stale)
+        hipEvent_t evO0 = nullptr, evO1 = nullptr;   // around the frame's last build
+        bool octTimed = false;           // ... which was bracketed by them and not read yet (the frame's next dxv_sync reads it)
+        float oct_ms = 0.0f;
+        bool octExpandPending = false;   // dxv_octree_expand_async read a CALLER's tree whose verdict (status word kOctStatusWord: an index that could not be
+                                         // followed) nobody has read yet: the frame can still report something, and its next synchronisation reads it
     };
     Frame frames[DXV_FRAME_COUNT];
     uint32_t cur = 0;                    // dxv_set_frame
@@ -283,6 +298,7 @@ struct dxv_ctx {
         uint32_t preparedLens[16 * 64];                  // ... of a queue that is being prepared
         uint32_t fillCtl[DXV_FRAME_COUNT][64];           // the control block of a frame's last fill batch (kFillMaxRounds words)
         unsigned long long isoTotals[DXV_FRAME_COUNT][2]; // vertices and quads of the mesh a frame is extracting: sizes its buffers
+        unsigned long long octTotals[DXV_FRAME_COUNT][12]; // level_first[0 .. L] of the tree a frame is building: sizes its node buffer
     };
     Pinned* pin = nullptr;
     hipEvent_t evList[4] = {};       // around the counting pass, around the rest of the build

@@ -240,6 +240,26 @@ void iso_scratch_layout(uint8_t* scratch, uint32_t N, IsoParams& p);
 hipError_t launch_iso_count(const IsoParams& p, hipStream_t s);
 hipError_t launch_iso_emit(const IsoParams& p, hipStream_t s);
 
+// octree.hip -- the sparse voxel octree of a whole N^3 grid (dxv_octree.h): reduce + scan, ONE read of the L + 1 level totals by the caller,
+// emit; and the way back, a grid from a tree.  scratch: oct_scratch_bytes(N) -- 2 bytes per cell of levels 0 .. L - 1, one bit per cell, one
+// count per 64 cells, the scan's block sums, level_first.  nodes: 8 bytes each.
+struct OctParams {
+    const uint8_t* grid;    // N^3 bytes, element (iz * N + iy) * N + ix; a voxel is solid iff its byte is non-zero
+    uint32_t N, L;          // oct_scratch_layout fills L and the five below
+    uint16_t* cells;        // the dense cell words
+    uint64_t* masks;        // "has a node", one bit per dense cell
+    uint32_t* bases;        // per 64 cells: the nodes among them, then the nodes in front of them
+    unsigned long long* sums;
+    unsigned long long* levelFirst;   // [0 .. L]: the nodes in front of every level, and the total
+    uint32_t* nodes;
+};
+size_t oct_scratch_bytes(uint32_t N);
+void oct_scratch_layout(uint8_t* scratch, uint32_t N, OctParams& p);
+hipError_t launch_oct_count(const OctParams& p, hipStream_t s);
+hipError_t launch_oct_emit(const OctParams& p, hipStream_t s);
+// every voxel of the grid of side N becomes 0 or 1 from a tree of `count` nodes (4-byte aligned, not trusted); *bad = 1 if it cannot be followed
+hipError_t launch_oct_expand(uint8_t* grid, uint32_t N, const uint32_t* nodes, uint32_t count, uint32_t* bad, hipStream_t s);
+
 // raycast.hip
 struct RayCastCB;
 hipError_t launch_raycast(const RayCastCB& cb, const uint8_t* grid, uint32_t N, uint32_t width, uint32_t height,

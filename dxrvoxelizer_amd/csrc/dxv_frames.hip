@@ -5,6 +5,7 @@
 #include "dxv_mesh_distance.h"
 #include "dxv_fill.h"
 #include "dxv_isosurface.h"
+#include "dxv_octree.h"
 
 using namespace dxv;
 using namespace dxvhost;
@@ -32,6 +33,8 @@ int frame_prepare(dxv_ctx* c, uint32_t i)
     if (!f.evF1) DXV_HIP(c, hipEventCreate(&f.evF1));
     if (!f.evI0) DXV_HIP(c, hipEventCreate(&f.evI0));
     if (!f.evI1) DXV_HIP(c, hipEventCreate(&f.evI1));
+    if (!f.evO0) DXV_HIP(c, hipEventCreate(&f.evO0));
+    if (!f.evO1) DXV_HIP(c, hipEventCreate(&f.evO1));
     DXV_HIP(c, f.status.reserve(64, 256));
     DXV_HIP(c, f.redo.reserve(kRedoCap, sizeof(uint64_t) * kRedoCap));
     // on the frame's own stream, and finished before anything reads the words: the streams are non-blocking, a memset on the
@@ -535,7 +538,7 @@ int voxelize_common(dxv_ctx* c, uint32_t N, int mode, uint32_t z0, uint32_t nzLo
     // the frame's previous launch is checked before its grid is reused -- when it can have anything to report: a launch
     // through the lists has no column to run out of, and the next launch simply queues behind it on the frame's stream
     // (no host round trip between back-to-back launches: 20 us of a 0.15 ms launch at 8 ranks)
-    if (f.pending && f.lastCanFail && sync_frame(c, c->cur)) return 1;
+    if (((f.pending && f.lastCanFail) || f.octExpandPending) && sync_frame(c, c->cur)) return 1;
     const size_t bytes = (size_t)N * N * nzLocal;
     if (bytes > f.grid.cap) {
         DXV_HIP(c, f.grid.reserve(bytes, align256(bytes), fs));
@@ -552,6 +555,7 @@ int voxelize_common(dxv_ctx* c, uint32_t N, int mode, uint32_t z0, uint32_t nzLo
     f.distCurrent = false;                                              // (a field of the grid this launch replaces is stale)
     f.mdistCurrent = false;
     f.isoCurrent = false;
+    f.octCurrent = false;
     f.fillPending = false;                                              // (... and a fill of it that has not converged yet is dropped: its batch in the stream ends in front of this launch)
     return launch_now(c, c->cur);
 }
@@ -567,12 +571,14 @@ static int sync_launch(dxv_ctx* c, uint32_t i)
         const bool readQueue = f.pending && f.lastQueued;
         DXV_HIP(c, hipMemcpyAsync(words, f.status.p, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, fs));
         if (readQueue) DXV_HIP(c, hipMemcpyAsync(c->pin->queueLens[i], f.queue.p + f.queueHdr * kQueueHeaderWords + queue_len_word(0), sizeof(c->pin->queueLens[i]), hipMemcpyDeviceToHost, fs));
+        if (f.octExpandPending) DXV_HIP(c, hipMemcpyAsync(words + kOctStatusWord, f.status.p + kOctStatusWord, sizeof(uint32_t), hipMemcpyDeviceToHost, fs));
         DXV_HIP(c, hipStreamSynchronize(fs));
         f.sceneReadPending = false;                                     // (whatever read the scene on this stream has finished)
         if (f.renderTimed) { f.render_ms = elapsed(f.evR0, f.evR1); f.renderTimed = false; }
         if (f.distTimed) { f.dist_ms = elapsed(f.evD0, f.evD1); f.distTimed = false; }
         if (f.mdistTimed) { f.mdist_ms = elapsed(f.evM0, f.evM1); f.mdistTimed = false; }
         if (f.isoTimed) { f.iso_ms = elapsed(f.evI0, f.evI1); f.isoTimed = false; }
+        if (f.octTimed) { f.oct_ms = elapsed(f.evO0, f.evO1); f.octTimed = false; }
         // lists this launch was queued behind without waiting for their verdict: withdrawn -> the launch again, through the tree
         if (settle_lists(c)) return 1;
         if (f.pending && f.usedLists && f.listEpochUsed == c->withdrawnEpoch && c->haveScene && f.grid_dim) {
@@ -637,10 +643,24 @@ static int settle_fill(dxv_ctx* c, uint32_t i)
     return 0;
 }
 
+// ... and the verdict of an expansion from a caller's tree (sync_launch has read the word): an index that could not be followed left empty
+// voxels behind and is reported here, once
+static int settle_expand(dxv_ctx* c, uint32_t i)
+{
+    Frame& f = c->frames[i];
+    if (!f.octExpandPending) return 0;
+    f.octExpandPending = false;
+    if (!c->pin->status[i][kOctStatusWord]) return 0;
+    DXV_HIP(c, hipMemsetAsync(f.status.p + kOctStatusWord, 0, sizeof(uint32_t), frame_stream(c, i)));
+    return fail(c, "dxv_octree_expand: the tree given for frame %u cannot be followed (a child index at or beyond its node count, or cells still mixed "
+                   "after all its levels); the voxels behind such an index were left empty", i);
+}
+
 int sync_frame(dxv_ctx* c, uint32_t i)
 {
     if (sync_launch(c, i)) return 1;
-    return settle_fill(c, i);
+    if (settle_fill(c, i)) return 1;
+    return settle_expand(c, i);
 }
 
 // The display pass of the selected frame into dst (device memory, rows `pitch` bytes apart), enqueued on the frame's stream behind
@@ -669,6 +689,7 @@ static int settle_frame_launch(dxv_ctx* c)
     if (settle_lists(c)) return 1;                                     // (waits for a list build's end, not for the launch behind it)
     Frame& f = cur_frame(c);
     if (f.pending && (f.lastCanFail || (f.usedLists && f.listEpochUsed == c->withdrawnEpoch))) return sync_frame(c, c->cur);
+    if (f.octExpandPending) return sync_frame(c, c->cur);               // an expansion from a caller's tree whose verdict is not in yet
     if (f.fillPending) return sync_frame(c, c->cur);                    // a fill whose verdict is not in yet: what is behind it must see the final grid
     return 0;
 }
@@ -1035,6 +1056,173 @@ int dxv_isosurface_ms(dxv_ctx* c, float* ms)
     return 0;
 }
 
+// The sparse voxel octree of the selected frame's grid (octree.hip; dxv_octree.h has the rule), enqueued on the frame's stream behind whatever
+// it holds, under dxv_render_async's host-wait rule: the reduce and scan kernels, the L + 1 level totals into page-locked words and the one
+// wait for them -- the pattern of dxv_isosurface_async: the node buffer cannot be sized without the last of them --, then the emit kernel and
+// the frame's end event, which nobody waits for here.
+int dxv_octree_async(dxv_ctx* c)
+{
+    if (!c) return 1;
+    Frame& f = cur_frame(c);
+    if (!f.grid.p || !f.grid_dim) return fail(c, "dxv_octree: frame %u has no grid yet (call dxv_voxelize first)", c->cur);
+    if (!frame_renderable(f))
+        return fail(c, "dxv_octree: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share");
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (settle_frame_launch(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    const uint32_t N = f.grid_dim;
+    const size_t scratch = oct_scratch_bytes(N);
+    DXV_HIP(c, f.octScratch.reserve(scratch, scratch, fs));
+    OctParams p{};
+    p.grid = f.grid.p;
+    oct_scratch_layout(f.octScratch.p, N, p);
+    const uint32_t L = p.L;
+    const bool timed = c->opt.events != 0;
+    unsigned long long* totals = c->pin->octTotals[c->cur];
+    if (timed) DXV_HIP(c, hipEventRecord(f.evO0, fs));
+    DXV_HIP(c, launch_oct_count(p, fs));
+    DXV_HIP(c, hipMemcpyAsync(totals, p.levelFirst, (L + 1u) * sizeof(unsigned long long), hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipStreamSynchronize(fs));
+    const unsigned long long nodes = totals[L];
+    if (!nodes || nodes > kOctMaxNodes) {
+        f.octTimed = false;                                             // (the first event was recorded again: the pair is no pair any more)
+        return fail(c, "dxv_octree: a tree of %llu nodes; at least the root and at most %llu (the frame's earlier tree is kept)", nodes,
+                    (unsigned long long)kOctMaxNodes);
+    }
+    f.octCurrent = false;
+    DXV_HIP(c, f.octNodes.reserve((size_t)nodes, align256((size_t)nodes * 2u * sizeof(uint32_t)), fs));
+    p.nodes = f.octNodes.p;
+    DXV_HIP(c, launch_oct_emit(p, fs));
+    if (timed) DXV_HIP(c, hipEventRecord(f.evO1, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    f.octTimed = timed;
+    f.octLevels = L; f.octCount = (uint32_t)nodes;
+    for (uint32_t l = 0; l < 12u; ++l) f.octLevelFirst[l] = l <= L ? (uint32_t)totals[l] : 0u;
+    f.octHave = true; f.octCurrent = true;
+    return 0;
+}
+
+int dxv_octree(dxv_ctx* c)
+{
+    if (dxv_octree_async(c)) return 1;
+    return dxv_sync(c);
+}
+
+// whether the frame has a tree to hand out: 0, or 1 with the reason as the message
+static int current_tree(const dxv_ctx* c, const char* who)
+{
+    const Frame& f = c->frames[c->cur];
+    dxv_ctx* w = const_cast<dxv_ctx*>(c);                               // (the message is the one thing an accessor writes)
+    if (!f.octHave) return fail(w, "%s: frame %u has no octree yet (call dxv_octree first)", who, c->cur);
+    if (!f.octCurrent) return fail(w, "%s: frame %u was launched, filled or expanded again since its octree was made: the tree is stale", who, c->cur);
+    return 0;
+}
+
+int dxv_octree_info(dxv_ctx* c, uint32_t* levels, uint32_t* nodes, uint32_t level_first[12])
+{
+    if (!c) return 1;
+    if (current_tree(c, "dxv_octree_info")) return 1;
+    const Frame& f = cur_frame(c);
+    if (levels) *levels = f.octLevels;
+    if (nodes) *nodes = f.octCount;
+    if (level_first) memcpy(level_first, f.octLevelFirst, sizeof(f.octLevelFirst));
+    return 0;
+}
+
+const void* dxv_octree_device_ptr(const dxv_ctx* c)
+{
+    if (!c || current_tree(c, "dxv_octree_device_ptr")) return nullptr;
+    return c->frames[c->cur].octNodes.p;
+}
+
+size_t dxv_octree_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame& f = c->frames[c->cur];
+    return f.octHave && f.octCurrent ? (size_t)f.octCount * 2u * sizeof(uint32_t) : 0;
+}
+
+int dxv_octree_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || current_tree(c, "dxv_octree_download")) return 1;
+    const size_t want = dxv_octree_bytes(c);
+    if (!host || bytes != want) return fail(c, "dxv_octree_download: expected %zu bytes, got %zu", want, bytes);
+    if (dxv_sync(c)) return 1;
+    DXV_HIP(c, hipMemcpyAsync(host, cur_frame(c).octNodes.p, bytes, hipMemcpyDeviceToHost, cur_stream(c)));
+    DXV_HIP(c, hipStreamSynchronize(cur_stream(c)));
+    return 0;
+}
+
+int dxv_octree_ms(dxv_ctx* c, float* ms)
+{
+    if (!c) return 1;
+    if (!ms) return fail(c, "dxv_octree_ms: ms is NULL");
+    *ms = cur_frame(c).oct_ms;
+    return 0;
+}
+
+// The selected frame's grid from an octree (octree.hip: k_oct_expand), in place, enqueued on the frame's stream behind whatever it holds --
+// under dxv_render_async's host-wait rule and dxv_fill_async's rules for the grid.  A caller's tree is not trusted: the kernel compares every
+// index with `nodes` before it follows it, and what it had to refuse is read where the frame is next synchronised (settle_expand).
+int dxv_octree_expand_async(dxv_ctx* c, const void* deviceNodes, uint32_t nodes, uint32_t levels)
+{
+    if (!c) return 1;
+    Frame& f = cur_frame(c);
+    if (!f.grid.p || !f.grid_dim) return fail(c, "dxv_octree_expand: frame %u has no grid yet (call dxv_voxelize first)", c->cur);
+    if (!frame_renderable(f))
+        return fail(c, "dxv_octree_expand: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share");
+    const uint32_t N = f.grid_dim, L = oct_levels(N);
+    DXV_HIP(c, hipSetDevice(c->device));
+    const bool own = deviceNodes == nullptr;
+    if (own) {
+        if (current_tree(c, "dxv_octree_expand")) return 1;
+        deviceNodes = f.octNodes.p; nodes = f.octCount;                 // (a current tree is the tree of this grid: its levels are L)
+    } else {
+        if (!nodes) return fail(c, "dxv_octree_expand: a tree of 0 nodes (the root is always there: nodes >= 1)");
+        if (nodes > kOctMaxNodes) return fail(c, "dxv_octree_expand: a tree of %u nodes; at most %llu", nodes, (unsigned long long)kOctMaxNodes);
+        if (levels != L) return fail(c, "dxv_octree_expand: a tree of %u levels; the frame's grid of %u^3 voxels has %u", levels, N, L);
+        if (reinterpret_cast<uintptr_t>(deviceNodes) % 4) return fail(c, "dxv_octree_expand: nodes at %p: need a 4-byte aligned pointer", deviceNodes);
+        // the nodes must be device memory of this context's device, and all of them must lie inside its allocation (dxv_render_async's check)
+        hipPointerAttribute_t a{};
+        if (hipPointerGetAttributes(&a, deviceNodes) != hipSuccess) {
+            (void)hipGetLastError();                                    // (an unknown host pointer is an error of that call: not sticky here)
+            return fail(c, "dxv_octree_expand: %p is not device memory (host memory is refused)", deviceNodes);
+        }
+        if (a.type != hipMemoryTypeDevice || a.device != c->device)
+            return fail(c, "dxv_octree_expand: %p is not device memory of device %d (memory type %d, device %d)", deviceNodes, c->device, (int)a.type, a.device);
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, const_cast<void*>(deviceNodes)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, "dxv_octree_expand: no allocation found behind %p", deviceNodes);
+        }
+        const uint8_t* first = static_cast<const uint8_t*>(deviceNodes);
+        const size_t offset = (size_t)(first - static_cast<uint8_t*>(base)), need = (size_t)nodes * 2u * sizeof(uint32_t);
+        if (first < static_cast<uint8_t*>(base) || offset > size || need > size - offset)
+            return fail(c, "dxv_octree_expand: %u nodes need %zu bytes, the allocation behind %p has %zu", nodes, need, deviceNodes,
+                        offset <= size ? size - offset : (size_t)0);
+    }
+    if (settle_frame_launch(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    // the grid stops being what the frame's last launch wrote (dxv_fill_async's rules): a kept queue's zeros are gone, and whatever was made
+    // of the grid before -- fields, the mesh, the frame's own tree -- is stale
+    f.clearSig = 0;
+    f.distCurrent = false;
+    f.mdistCurrent = false;
+    f.isoCurrent = false;
+    f.octCurrent = false;
+    DXV_HIP(c, launch_oct_expand(f.grid.p, N, static_cast<const uint32_t*>(deviceNodes), nodes, f.status.p + kOctStatusWord, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    if (!own) f.octExpandPending = true;                                // (the frame's own tree was made by the build: it has nothing to report)
+    return 0;
+}
+
+int dxv_octree_expand(dxv_ctx* c, const void* deviceNodes, uint32_t nodes, uint32_t levels)
+{
+    if (dxv_octree_expand_async(c, deviceNodes, nodes, levels)) return 1;
+    return dxv_sync(c);
+}
+
 // The exterior flood fill of the selected frame's grid (fill.hip), in place, enqueued on the frame's stream behind whatever it holds --
 // under dxv_render_async's host-wait rule: one batch of rounds, the write-back, the batch's control block into page-locked words, the
 // frame's end event.  Whether the batch converged is read where the frame is next synchronised (settle_fill).
@@ -1063,6 +1251,7 @@ int dxv_fill_async(dxv_ctx* c, int what)
     f.distCurrent = false;
     f.mdistCurrent = false;
     f.isoCurrent = false;
+    f.octCurrent = false;
     if (timed) DXV_HIP(c, hipEventRecord(f.evF0, fs));
     DXV_HIP(c, launch_fill(f.grid.p, N, what, f.fillScratch.p, f.fillBatch, true, fs));
     if (timed) DXV_HIP(c, hipEventRecord(f.evF1, fs));

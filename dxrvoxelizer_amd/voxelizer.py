@@ -393,6 +393,72 @@ class Voxelizer:
         self._check(self._lib.dxv_isosurface_ms(self._ctx, C.byref(ms)))
         return ms.value
 
+    # ---- the sparse voxel octree of the frame's grid ------------------------------------------------
+    def Octree(self, sync=True, frameIndex=None):
+        """The sparse voxel octree of the selected frame's whole grid, built on the device (dxv_octree / dxv_octree_async; include/dxv.h has
+        the rule): one 8-byte node for the root and for every mixed cell, full and empty cells have none.  sync=True returns (nodes [n, 2]
+        uint32 {word0, word1}, level_first [L + 1]); sync=False only enqueues the emit pass (the call still reads the level totals once)
+        and returns True (OctreeNodes after a Sync)."""
+        if frameIndex is not None:
+            self.SetFrame(frameIndex)
+        fn = self._lib.dxv_octree if sync else self._lib.dxv_octree_async
+        self._check(fn(self._ctx))
+        return self.OctreeNodes() if sync else True
+
+    def OctreeInfo(self):
+        """(levels L, nodes, level_first [L + 1]) of the selected frame's tree (dxv_octree_info); raises where the library refuses (no tree
+        yet, or the frame was launched, filled or expanded again since)."""
+        levels, nodes, first = C.c_uint32(), C.c_uint32(), (C.c_uint32 * 12)()
+        self._check(self._lib.dxv_octree_info(self._ctx, C.byref(levels), C.byref(nodes), first))
+        return levels.value, nodes.value, [int(v) for v in first[:levels.value + 1]]
+
+    def OctreeNodes(self):
+        """numpy copy (nodes [n, 2] uint32, level_first) of the selected frame's tree (dxv_octree_download; synchronises the frame)."""
+        _, n, first = self.OctreeInfo()
+        nodes = np.empty((n, 2), np.uint32)
+        self._check(self._lib.dxv_octree_download(self._ctx, nodes.ctypes.data_as(C.c_void_p), nodes.nbytes))
+        return nodes, first
+
+    def octree_device_ptr(self):
+        """Device pointer of the selected frame's nodes (dxv_octree_device_ptr), for consumers on the GPU; raises where the library refuses."""
+        p = self._lib.dxv_octree_device_ptr(self._ctx)
+        if not p:
+            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
+        return p
+
+    def octree_bytes(self):
+        return self._lib.dxv_octree_bytes(self._ctx)
+
+    def octree_ms(self):
+        """Device time of the selected frame's last octree build, read at the frame's Sync (dxv_octree_ms)."""
+        ms = C.c_float()
+        self._check(self._lib.dxv_octree_ms(self._ctx, C.byref(ms)))
+        return ms.value
+
+    def OctreeExpand(self, nodes=None, levels=None, count=None, sync=True, frameIndex=None):
+        """Write the selected frame's whole grid from an octree, every voxel 0 or 1 (dxv_octree_expand / dxv_octree_expand_async).
+        nodes=None: the frame's own current tree.  Otherwise a tree on this device: a torch tensor of uint32 / int32 words, two per node
+        (anything with data_ptr() and numel()), or a device pointer with count = its nodes; levels = the tree's L, which must be the L of
+        the frame's grid.  The tree is not trusted: an index it holds that cannot be followed fails the frame's next Sync."""
+        if frameIndex is not None:
+            self.SetFrame(frameIndex)
+        fn = self._lib.dxv_octree_expand if sync else self._lib.dxv_octree_expand_async
+        if nodes is None:
+            self._check(fn(self._ctx, None, 0, 0))
+            return True
+        if hasattr(nodes, "data_ptr"):
+            if int(nodes.element_size()) != 4 or int(nodes.numel()) % 2 or not nodes.is_contiguous():
+                raise DxvError(f"OctreeExpand: nodes must be contiguous 32-bit words, two per node, got {nodes.dtype} {tuple(nodes.shape)}")
+            ptr, count = int(nodes.data_ptr()), int(nodes.numel()) // 2 if count is None else int(count)
+        else:
+            if count is None:
+                raise DxvError("OctreeExpand: a device pointer needs count = the number of its nodes")
+            ptr = int(nodes)
+        if levels is None:
+            raise DxvError("OctreeExpand: a caller's tree needs levels = its L")
+        self._check(fn(self._ctx, C.c_void_p(ptr), int(count), int(levels)))
+        return True
+
     # ---- the exterior flood fill of the frame's grid -----------------------------------------------
     def Fill(self, what=FILL_SOLID, sync=True, frameIndex=None):
         """Flood the empty space of the selected frame's whole grid from the grid's border (6-connectivity) and replace the grid, in

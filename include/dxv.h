@@ -191,7 +191,7 @@ DXV_API int dxv_sync(dxv_ctx* ctx);
  * frameIndex (static const uint8_t FrameCount, Content/Voxelizer.h:24; m_grids[FrameCount], :110;
  * Render(pCommandList, frameIndex, ...), :21-22; voxelize(pCommandList, frameIndex), Content/Voxelizer.cpp:351-356),
  * so that the GPU works on one grid while the host still reads another.  dxv_set_frame selects the frame the
- * following dxv_voxelize* / dxv_sync / dxv_grid_* / dxv_texels_download / dxv_render* / dxv_update_frame / dxv_distance* / dxv_fill* / dxv_isosurface* / dxv_get_stats calls refer to
+ * following dxv_voxelize* / dxv_sync / dxv_grid_* / dxv_texels_download / dxv_render* / dxv_update_frame / dxv_distance* / dxv_fill* / dxv_isosurface* / dxv_octree* / dxv_get_stats calls refer to
  * (default 0).  Each frame owns its grid, texel image, status words and -- frames 1 and 2 -- an internal stream,
  * so launches of different frames overlap on the GPU; scene, candidate lists and options are shared (an extra frame
  * costs its grid).  Calls that change what the frames read (dxv_set_mesh, dxv_build, dxv_scene_import, dxv_set_stream) first
@@ -482,6 +482,63 @@ DXV_API int dxv_isosurface_indices_download(dxv_ctx* ctx, void* host, size_t byt
  * the frame's dxv_sync: 0 before that, and under option events = 0. */
 DXV_API int dxv_isosurface_ms(dxv_ctx* ctx, float* ms);
 
+/* Sparse voxel octree: the selected frame's grid as a tree that is sparse on BOTH sides of the surface, built on the device (no reference
+ * counterpart) -- the compact form of a solid for renderers, collision code and storage, and, with dxv_octree_expand, a way to move a grid:
+ * build on one context, copy a few megabytes, get the grid back on another.  Every grid can feed it: all four modes, a filled grid, bytes
+ * written through dxv_grid_device_ptr.  Every step is fixed, so the node array equals a restatement byte for byte.
+ *     input     the WHOLE grid of the frame's last launch, N even, 2 <= N <= 2048; a voxel is solid iff its byte is non-zero
+ *     cube      S = the smallest power of two >= N, L = log2 S (1 .. 11); the tree covers [0, S)^3, voxels outside the grid are empty
+ *     cells     a cell of level l (0 .. L) has side S >> l; a level-L cell is a voxel, full or empty; a cell above is empty if its eight children
+ *               are, full if all eight are full, else mixed; child o = dx | dy << 1 | dz << 2 from the child's position bits
+ *     nodes     one for the root and for every mixed cell of levels 1 .. L - 1 (full and empty cells have none), two little-endian uint32:
+ *               word1 = mixed (bit o: child o is mixed) | full << 8 (bit o: child o is full), bits 16 - 31 zero; at level L - 1 mixed is 0
+ *               word0 = the index of the node of the lowest-numbered mixed child, 0 when mixed is 0; the node of mixed child o is
+ *                       word0 + popcount(mixed & ((1 << o) - 1))
+ *     order     levels 0, 1, .. L - 1 one after another; inside a level ascending Morton code of the cell position (per bit triple x lowest,
+ *               then y, then z): a node's mixed children are consecutive, and the array is unique
+ *     table     level_first[0 .. L]: the index of the first node of each level, level_first[L] the total; a level may be empty
+ * An all-empty grid is the one node (0, 0x0000), an all-solid 8^3 grid the one node (0, 0xFF00). */
+/* dxv_octree_async -- reduce and scan kernels ENQUEUED on the frame's stream behind whatever it holds, then ONE host read of the L + 1 level
+ * totals (the node buffer cannot be sized without the last of them), then the emit kernel enqueued; returns without waiting for that.
+ *  - The host waits before that only under dxv_render_async's rule; a pending fill is settled first.
+ *  - Checked on the host before anything is enqueued, each an error with a message: the frame has been launched; its last launch was the whole
+ *    grid, not a slab or a share.  A tree of more than 2^31 - 1 nodes is refused once its totals are known.
+ *  - The grid is read once, as it is when the kernels run (bytes written through dxv_grid_device_ptr count).
+ *  - Nodes (a grow-only buffer) and scratch belong to the frame: frames build side by side.  The scratch is, for C = 128 + (8^L - 64) / 7 (L >= 2;
+ *    64 for L = 1) dense cells of levels 0 .. L - 1 and W = C / 64: 2 C + 8 W + 4 W + 8 ceil(W / 1024) + 96 bytes, each of the five parts rounded up
+ *    to 256 -- 0.31 S^3 + 1 KiB, below S^3 / 2 from S = 16 on.  dxv_trim gives it back, the nodes stay.
+ *  - The tree is STALE once its frame is launched, filled or expanded again: info, pointer, size and download then fail with a message.
+ *  - Option events = 1 (default): bracketed by the frame's own two events; dxv_octree_ms reads them at the frame's dxv_sync.
+ * dxv_octree -- the same + dxv_sync. */
+DXV_API int dxv_octree_async(dxv_ctx* ctx);
+DXV_API int dxv_octree(dxv_ctx* ctx);
+/* L, the node count and level_first of the selected frame's tree (any pointer may be NULL; entries of level_first beyond [L] are 0). */
+DXV_API int dxv_octree_info(dxv_ctx* ctx, uint32_t* levels, uint32_t* nodes, uint32_t level_first[12]);
+/* The nodes on the device (valid after dxv_sync or on the frame's stream), 8 bytes each, and their size.  NULL / 0 -- the pointer with a
+ * message -- before the frame's first tree or when it is stale. */
+DXV_API const void* dxv_octree_device_ptr(const dxv_ctx* ctx);
+DXV_API size_t dxv_octree_bytes(const dxv_ctx* ctx);
+/* Copy to the host (bytes must be dxv_octree_bytes); synchronises the frame first. */
+DXV_API int dxv_octree_download(dxv_ctx* ctx, void* host, size_t bytes);
+/* Device time of the selected frame's last build in milliseconds (HIP events; the host's read of the totals lies inside it), read at the
+ * frame's dxv_sync: 0 before that, and under option events = 0. */
+DXV_API int dxv_octree_ms(dxv_ctx* ctx, float* ms);
+/* dxv_octree_expand_async -- the selected frame's grid FROM an octree, in place: every voxel of the grid becomes a byte of exactly 0 or 1
+ * (voxels of the cube beyond the grid are skipped); ENQUEUED on the frame's stream behind whatever it holds, returns without waiting.
+ *  - dxv_fill_async's rules: the frame's last launch was the whole grid; the host waits only under dxv_render_async's rule; fields, the mesh and
+ *    the frame's own octree made of the grid before are stale after it; the frame's next launch clears its whole grid.
+ *  - device_nodes == NULL: the frame's own current tree (`nodes` and `levels` are ignored); stale or none is an error.
+ *  - Otherwise a caller's buffer, checked on the host before anything is enqueued, each an error with a message: it is device memory of this
+ *    context's device and `nodes` * 8 bytes lie inside its allocation (dxv_render_async's check); it is 4-byte aligned; nodes >= 1; `levels`
+ *    equals the L of the frame's grid.
+ *  - A caller's buffer is not trusted: every index read from it is compared with `nodes` before it is followed, and a descent stops after L
+ *    levels -- never an access outside the buffer.  An index that is refused leaves empty voxels and raises the frame's status: the frame's
+ *    next dxv_sync fails with a message, and until then the frame counts as one that can still report something (the next call that
+ *    enqueues behind it waits for that verdict first).
+ * dxv_octree_expand -- the same + dxv_sync. */
+DXV_API int dxv_octree_expand_async(dxv_ctx* ctx, const void* device_nodes, uint32_t nodes, uint32_t levels);
+DXV_API int dxv_octree_expand(dxv_ctx* ctx, const void* device_nodes, uint32_t nodes, uint32_t levels);
+
 /* Multi-GPU: the built scene (nodes + triangle data) as one relocatable device blob, so that
  * rank 0 builds once and the host layer broadcasts it (RCCL over xGMI) to the other ranks.
  * export copies the blob into caller-provided DEVICE memory; import adopts a blob from DEVICE
@@ -641,8 +698,8 @@ DXV_API int dxv_debug_plan_check(dxv_ctx* ctx, uint64_t out[16]);
 
 /* Give back what the context keeps only to make the next build faster: the list build's scratch (up to 16 GiB per buffer
  * after a 10 M-triangle scene), the LBVH build's scratch when no refit can follow (imported scenes), the memory of prepared queues
- * whose lists are gone, the scratch of the frames' distance fields (the fields stay), of their flood fills and of their isosurfaces (the
- * meshes stay).  Nothing a launch reads. */
+ * whose lists are gone, the scratch of the frames' distance fields (the fields stay), of their flood fills, of their isosurfaces (the
+ * meshes stay) and of their octrees (the nodes stay).  Nothing a launch reads. */
 DXV_API int dxv_trim(dxv_ctx* ctx);
 
 /* Test hook: copy an internal device array to the host (enum above). */

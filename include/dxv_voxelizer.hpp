@@ -203,6 +203,24 @@ public:
 	}
 	bool IsosurfaceMs(float& ms) { return m_ctx && dxv_isosurface_ms(m_ctx, &ms) == 0; }
 
+	// The sparse voxel octree of that frame's grid (dxv_octree_async: one 8-byte node for the root and for every mixed cell; include/dxv.h has
+	// the rule), enqueued behind the frame's launch.  OctreeInfo, DeviceOctree and DownloadOctree refer to the frame last selected;
+	// WaitFrame reports the kernels' errors.  OctreeExpand writes the frame's grid from a tree on this device (nullptr: the frame's own).
+	bool Octree(uint8_t frameIndex) { return SetFrame(frameIndex) && dxv_octree_async(m_ctx) == 0; }
+	bool OctreeInfo(uint32_t& levels, uint32_t& nodes, uint32_t levelFirst[12]) { return m_ctx && dxv_octree_info(m_ctx, &levels, &nodes, levelFirst) == 0; }
+	const void* DeviceOctree() const { return m_ctx ? dxv_octree_device_ptr(m_ctx) : nullptr; }
+	bool DownloadOctree(std::vector<uint32_t>& nodes)
+	{
+		if (!m_ctx) return setError("DownloadOctree before Init");
+		nodes.resize(dxv_octree_bytes(m_ctx) / sizeof(uint32_t));
+		return dxv_octree_download(m_ctx, nodes.data(), nodes.size() * sizeof(uint32_t)) == 0;
+	}
+	bool OctreeMs(float& ms) { return m_ctx && dxv_octree_ms(m_ctx, &ms) == 0; }
+	bool OctreeExpand(uint8_t frameIndex, const void* deviceNodes = nullptr, uint32_t nodes = 0, uint32_t levels = 0)
+	{
+		return SetFrame(frameIndex) && dxv_octree_expand_async(m_ctx, deviceNodes, nodes, levels) == 0;
+	}
+
 	// The exterior flood fill of that frame's whole grid, in place (dxv_fill / dxv_fill_async): DXV_FILL_SOLID leaves the walls and everything
 	// they enclose, DXV_FILL_INTERIOR the enclosed voxels alone.  Voxelize(gridDim, SURFACE) && Fill() is the solid of a mesh whose
 	// normals and watertightness cannot be trusted.  Refers to the frame last selected; sync = false only enqueues (WaitFrame reports).
