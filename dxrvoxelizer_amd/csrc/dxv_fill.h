@@ -9,6 +9,7 @@
 #pragma once
 #include <stddef.h>
 #include "dxv_types.h"
+#include "dxv_solid.h"
 
 namespace dxv {
 
@@ -47,19 +48,13 @@ DXV_HD uint32_t fill_free_byte(const uint8_t* row, uint32_t N, uint32_t j)
     uint32_t b = 0;
     for (uint32_t k = 0; k < 8u; ++k) {
         const uint32_t x = 8u * j + k;
-        if (x < N && row[x] == 0) b |= 1u << k;
+        if (x < N && !solid(row[x])) b |= 1u << k;
     }
     return b;
 }
-// ... from eight bytes loaded as one word (N % 8 == 0: every row starts on an 8-byte boundary of the grid): bit k = byte k is zero
-DXV_HD uint32_t fill_free_byte(uint64_t eight)
-{
-    uint64_t nz = eight | (eight >> 4);
-    nz |= nz >> 2;
-    nz |= nz >> 1;
-    nz = ~nz & 0x0101010101010101ull;                                   // bit 8k = byte k is zero
-    return (uint32_t)((nz * 0x0102040810204080ull) >> 56);                // gathers bit 8k into bit 56 + k (no two terms meet: no carries)
-}
+// ... from eight bytes loaded as one word (N % 8 == 0: every row starts on an 8-byte boundary of the grid): bit k = byte k is zero,
+// the complement of the library's solid rule (dxv_solid.h)
+DXV_HD uint32_t fill_free_byte(uint64_t eight) { return ~solid_bits(eight) & 0xffu; }
 // the free voxels of the grid's border among these eight
 DXV_HD uint32_t fill_seed_byte(uint32_t free8, uint32_t N, uint32_t j, uint32_t iy, uint32_t iz)
 {

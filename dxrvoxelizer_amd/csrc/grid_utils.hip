@@ -1,5 +1,6 @@
 // grid_utils.hip -- small streaming kernels over a finished grid or buffer: checksum, solid-voxel count, bit-packed copy.
 #include "dxv_device.h"
+#include "dxv_solid.h"
 
 namespace dxv {
 
@@ -22,7 +23,7 @@ hipError_t launch_checksum(const void* buf, size_t bytes, unsigned long long* ou
     return hipGetLastError();
 }
 
-// Solid-voxel count: 16 B per lane streaming reduction, one atomic per workgroup.
+// Solid-voxel count (a voxel is solid iff its byte is non-zero: dxv_solid.h): 16 B per lane streaming reduction, one atomic per workgroup.
 __global__ __launch_bounds__(256) void k_count(const uint8_t* __restrict__ grid, size_t n, unsigned long long* out)
 {
     __shared__ unsigned long long part[4];
@@ -31,9 +32,10 @@ __global__ __launch_bounds__(256) void k_count(const uint8_t* __restrict__ grid,
     unsigned long long c = 0;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) {
         const uint4 v = g16[i];
-        c += __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w); // bytes are 0 or 1
+        const unsigned long long lo = ((unsigned long long)v.y << 32) | v.x, hi = ((unsigned long long)v.w << 32) | v.z;
+        c += solid_popc(solid_marks(lo)) + solid_popc(solid_marks(hi));     // any byte: one mark per non-zero byte
     }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 15)) c += grid[n16 * 16 + threadIdx.x];
+    if (blockIdx.x == 0 && threadIdx.x < (n & 15)) c += solid(grid[n16 * 16 + threadIdx.x]) ? 1u : 0u;
     for (int off = 32; off; off >>= 1) c += __shfl_down(c, off);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
     __syncthreads();
@@ -52,25 +54,21 @@ hipError_t launch_count(const uint8_t* grid, size_t n, unsigned long long* out, 
 }
 
 // Bit-packed copy of the occupancy bytes for the host: output byte j holds voxels 8j .. 8j+7,
-// voxel 8j+i in bit i.  One lane reads 16 grid bytes and writes 2; HBM bound (9/8 B per voxel).
+// voxel 8j+i in bit i, set iff the voxel's byte is non-zero (dxv_solid.h: the body's words and the tail's bytes by the same rule).
+// One lane reads 16 grid bytes and writes 2; HBM bound (9/8 B per voxel).
 __global__ __launch_bounds__(256) void k_pack_bits(const uint8_t* __restrict__ grid, size_t n, uint8_t* __restrict__ packed)
 {
-    constexpr unsigned long long kGather = 0x0102040810204080ull;   // byte i (0 or 1) -> bit 56 + i of the product
     const size_t n16 = n / 16;
     const uint4* g16 = reinterpret_cast<const uint4*>(grid);
     uint16_t* p16 = reinterpret_cast<uint16_t*>(packed);
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) {
         const uint4 v = g16[i];
         const unsigned long long lo = ((unsigned long long)v.y << 32) | v.x, hi = ((unsigned long long)v.w << 32) | v.z;
-        p16[i] = (uint16_t)(((lo * kGather) >> 56) | (((hi * kGather) >> 56) << 8));
+        p16[i] = (uint16_t)(solid_bits(lo) | (solid_bits(hi) << 8));
     }
     if (blockIdx.x == 0 && threadIdx.x < 2) {                       // the last n % 16 voxels: at most two bytes
         const size_t first = n16 * 16 + (size_t)threadIdx.x * 8;
-        if (first < n) {
-            uint32_t b = 0;
-            for (size_t k = 0; k < 8 && first + k < n; ++k) b |= (uint32_t)(grid[first + k] & 1u) << k;
-            packed[first / 8] = (uint8_t)b;
-        }
+        if (first < n) packed[first / 8] = (uint8_t)solid_bits(grid + first, n - first);
     }
 }
 

@@ -228,8 +228,9 @@ class Voxelizer:
 
     def GridBits(self, out=None):
         """The grid as one bit per voxel, packed on the device (dxv_grid_download_packed): uint8
-        [ceil(nz*N*N/8)], voxel 8j+i in bit i of byte j == np.packbits(Grid().ravel(),
-        bitorder="little").  `out` may be any writable uint8 buffer of that size, e.g. pinned."""
+        [ceil(nz*N*N/8)], voxel 8j+i in bit i of byte j, set iff the voxel's byte is non-zero
+        == np.packbits(Grid().ravel(), bitorder="little") (numpy, too, takes every non-zero byte
+        for 1).  `out` may be any writable uint8 buffer of that size, e.g. pinned."""
         nbytes = self._lib.dxv_grid_packed_bytes(self._ctx)
         if out is None:
             out = np.empty(nbytes, np.uint8)
@@ -248,6 +249,8 @@ class Voxelizer:
         self._check(self._lib.dxv_enable_texels(self._ctx, int(bool(on))))
 
     def CountSolid(self):
+        """Solid voxels of the selected frame's grid, counted on the device (dxv_grid_count); a voxel is solid iff its byte is
+        non-zero == np.count_nonzero(Grid())."""
         v = C.c_uint64()
         self._check(self._lib.dxv_grid_count(self._ctx, C.byref(v)))
         return v.value

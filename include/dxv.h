@@ -245,12 +245,15 @@ DXV_API const void* dxv_grid_device_ptr_ro(const dxv_ctx* ctx);
 DXV_API size_t dxv_grid_bytes(const dxv_ctx* ctx);
 DXV_API int dxv_grid_download(dxv_ctx* ctx, uint8_t* host, size_t bytes);
 /* The same grid as one BIT per voxel, packed on the device before it crosses PCIe (8x fewer
- * bytes): voxel 8j+i of the last launch's slab is bit i of byte j; bytes = dxv_grid_packed_bytes
- * = ceil(dxv_grid_bytes / 8).  What the reference's consumer reads is this one bit (alpha,
- * Shaders/PSRayCast.hlsl:108). */
+ * bytes): voxel 8j+i of the last launch's slab is bit i of byte j, set iff the voxel is solid; a voxel
+ * is solid iff its byte is non-zero (the grid as it is when the kernel runs: a caller who wrote through
+ * dxv_grid_device_ptr gets the bits of what was written, whatever the bytes).  The bits behind the last
+ * voxel are 0.  bytes = dxv_grid_packed_bytes = ceil(dxv_grid_bytes / 8).  What the reference's consumer
+ * reads is this one bit (alpha, Shaders/PSRayCast.hlsl:108). */
 DXV_API size_t dxv_grid_packed_bytes(const dxv_ctx* ctx);
 DXV_API int dxv_grid_download_packed(dxv_ctx* ctx, uint8_t* host, size_t bytes);
-/* Number of solid voxels of the last grid, reduced on the device. */
+/* Number of solid voxels of the selected frame's grid (the last launch's slab), reduced on the device; a voxel is solid iff its byte
+ * is non-zero -- the popcount of dxv_grid_download_packed's bits. */
 DXV_API int dxv_grid_count(dxv_ctx* ctx, uint64_t* solid);
 
 /* The same grid as the reference's R10G10B10A2_UNORM texels (float4(Normal, 1), hlsl:83-84,

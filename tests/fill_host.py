@@ -15,7 +15,7 @@ def library():
     if _LIB is None:
         src = os.path.join(ROOT, "tests", "hostcheck", "fill_check.cpp")
         so = os.path.join(ROOT, "tests", "hostcheck", "libfillcheck.so")
-        deps = [src] + [os.path.join(ROOT, "dxrvoxelizer_amd", "csrc", h) for h in ("dxv_fill.h", "dxv_types.h", "dxv_policy.h")]
+        deps = [src] + [os.path.join(ROOT, "dxrvoxelizer_amd", "csrc", h) for h in ("dxv_fill.h", "dxv_solid.h", "dxv_types.h", "dxv_policy.h")]
         if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
             subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fopenmp", "-ffp-contract=off", "-Wall", "-Werror",
                                    "-Wno-unknown-pragmas", "-o", so, src])

@@ -778,9 +778,9 @@ def test_device_resident_full_grid_by_allgather(dxv, dragon, tmp_path):
     v.close()
 
 
-@pytest.mark.parametrize("n,z0,nz", [(64, 0, 64), (2, 0, 2), (6, 1, 3), (10, 0, 7), (256, 100, 9)])
+@pytest.mark.parametrize("n,z0,nz", [(64, 0, 64), (2, 0, 2), (6, 1, 3), (10, 0, 7), (256, 100, 9), (258, 0, 258)])
 def test_bit_packed_download_equals_packbits(vox, bunny, n, z0, nz):
-    """dxv_grid_download_packed: voxel 8j+i in bit i of byte j, any slab size (ragged tails)."""
+    """dxv_grid_download_packed: voxel 8j+i in bit i of byte j, any slab size (ragged tails; 258^3: the kernel's loop goes round twice)."""
     vb, ib, _ = bunny
     vox.InitDynamic(vb, ib)
     vox.Voxelize(n, 0, z0, nz)
