@@ -441,6 +441,35 @@ extern "C" int dxv_debug_plan_check(dxv_ctx* c, uint64_t out[16])
     return 0;
 }
 
+// the order of the PREPARED queue the current frame's last launch ran (queue_order.hip: k_order_check)
+extern "C" int dxv_debug_queue_order(dxv_ctx* c, uint64_t out[4])
+{
+    if (!c || !out) return 1;
+    Frame& f = cur_frame(c);
+    if (settle_lists(c)) return 1;
+    const int slot = f.lastPrepared;
+    if (!c->haveScene || c->lists.state != 1 || slot < 0 || c->prepared[slot].epoch != c->listEpoch || !c->prepared[slot].mem.p)
+        return fail(c, "dxv_debug_queue_order: the current frame's last launch did not go through a prepared queue");
+    const auto& q = c->prepared[slot];
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (sync_frames(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    VoxelizeParams p{};
+    scene_params(c, p.scene);
+    lists_params(c, p.scene);
+    p.N = q.N; p.z0 = q.z0; p.nz = q.nz; p.zBlock = q.zBlock; p.zPeriod = q.zPeriod; p.zShift = z_shift(q.zBlock);
+    p.queue = q.mem.p; p.queueSlots = q.mem.p + kQueueHeaderWords; p.queueCap = q.cap;
+    DevBuf<uint32_t> tiles;
+    DevBuf<unsigned long long> dOut;
+    DXV_HIP(c, tiles.reserve(queue_order_check_words(), sizeof(uint32_t) * queue_order_check_words()));
+    hipError_t e = dOut.reserve(4, 4 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = launch_queue_order_check(p, tiles.p, dOut.p, fs);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dOut.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, fs);
+    if (e == hipSuccess) e = hipStreamSynchronize(fs);
+    if (e != hipSuccess) return fail(c, "dxv_debug_queue_order failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
 extern "C" int dxv_debug_download(dxv_ctx* c, int what, void* host, size_t bytes)
 {
     if (!c || !host) return 1;

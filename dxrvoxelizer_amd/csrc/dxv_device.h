@@ -149,6 +149,18 @@ size_t plan_queue_words(uint32_t N, uint32_t nz, uint32_t* capOut);     // 32-bi
 hipError_t plan_build(const VoxelizeParams& p, hipStream_t s);          // k_plan_bricks into the (zero) header p.queue; p.queueSlots, p.queueCap, p.mip set
 size_t plan_live_words(uint32_t N, uint32_t nz);   // 32-bit words of a partition's brick mask
 hipError_t plan_clear_grid(const VoxelizeParams& p, hipStream_t s);     // zeros the partition's grid (and texel image): the clear of k_plan_bricks as a kernel of its own
+// queue_order.hip -- the direction-major order of a PREPARED queue: the bricks k_plan_bricks queued, sorted by (class, direction tile,
+// start radius), whole tiles dealt round-robin to the eight queues.  Two steps around ONE read of the sixteen new counts by the caller
+// (a queue must be able to hold what the deal gives it): sort -- p.queueSlots / p.queueCap / lens16 = the queue as built, n (> 0) its
+// bricks, scratch = queue_order_scratch_bytes(n) bytes; *sorted and *counts (sixteen words: the heavy bricks of the eight new queues,
+// then the others) point into the scratch -- and write -- p.queue = a zero header, p.queueSlots / p.queueCap = where the queues go,
+// lens16 = the NEW eight lengths, of which heavy.
+size_t queue_order_scratch_bytes(uint32_t n);
+hipError_t queue_order_sort(const VoxelizeParams& p, const uint32_t lens16[16], uint32_t n, uint8_t* scratch, const uint64_t** sorted, const uint32_t** counts, hipStream_t s);
+hipError_t queue_order_write(const VoxelizeParams& p, const uint32_t lens16[16], uint32_t n, const uint64_t* sorted, hipStream_t s);
+// (test hook: out[0] items, out[1] tiles in more than one queue's own share, out[2] neighbours out of order; tiles: queue_order_check_words() words)
+size_t queue_order_check_words();
+hipError_t launch_queue_order_check(const VoxelizeParams& p, uint32_t* tiles, unsigned long long* out, hipStream_t s);
 // voxelize_lists.hip -- the two brick kernels that run the queue
 // rebuild: grid cleared + queue built in front of the kernel; else only the queue heads are reset (same launch as before into the same buffers)
 // (planEvents: two events recorded around the queue build of a rebuilding launch, or NULL)

@@ -144,9 +144,45 @@ static int prepare_partition(dxv_ctx* c, uint32_t N, uint32_t z0, uint32_t nzLoc
     DXV_HIP(c, hipMemsetAsync(q.live.p, 0, sizeof(uint32_t) * liveWords, s));
     DXV_HIP(c, plan_build(p, s));
     DXV_HIP(c, hipMemcpyAsync(c->pin->preparedLens, q.mem.p + queue_len_word(0), sizeof(c->pin->preparedLens), hipMemcpyDeviceToHost, s));
-    DXV_HIP(c, hipEventRecord(c->ev[9], s));
     DXV_HIP(c, hipStreamSynchronize(s));
     q.bricks = decode_queue_lens(c->pin->preparedLens, q.lens);
+#if !defined(DXV_PREPARED_ORDER_MORTON)                                 // (scratch builds: the order as built, for an A/B)
+    // A queue that is launched again and again is worth a sort: direction-major, whole map tiles dealt to the XCDs (queue_order.hip).
+    // The same bricks in another order: the live mask stands.  Two more host round trips of an Init, for the number of keys and for
+    // the new counts -- the deal knows nothing of a queue's capacity, so a queue that is given more than it holds gets more memory.
+    DevBuf<uint8_t> orderOnce;
+    if (q.bricks) {
+        // (the sort's scratch: the list build's key buffers where the context still has them -- the build is over, settle_lists above --
+        // else an allocation of this call's own, ~0.1 ms inside prepare_ms)
+        const size_t scratchBytes = queue_order_scratch_bytes(q.bricks);
+        uint8_t* orderScratch = c->listScratchB.p;
+        if (c->listScratchB.cap < scratchBytes) {
+            DXV_HIP(c, orderOnce.reserve(scratchBytes, scratchBytes));
+            orderScratch = orderOnce.p;
+        }
+        const uint64_t* sorted = nullptr;
+        const uint32_t* counts = nullptr;
+        DXV_HIP(c, queue_order_sort(p, q.lens, q.bricks, orderScratch, &sorted, &counts, s));
+        DXV_HIP(c, hipMemcpyAsync(c->pin->preparedLens, counts, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        DXV_HIP(c, hipStreamSynchronize(s));
+        uint32_t longest = 0;
+        for (uint32_t x = 0; x < 8u; ++x) {
+            q.lens[8u + x] = c->pin->preparedLens[x];
+            q.lens[x] = c->pin->preparedLens[x] + c->pin->preparedLens[8u + x];
+            longest = q.lens[x] > longest ? q.lens[x] : longest;
+        }
+        if (longest > cap) {
+            cap = (longest + 63u) & ~63u;
+            const size_t grown = kQueueHeaderWords + 8u * (size_t)cap;
+            DXV_HIP(c, q.mem.reserve(grown, sizeof(uint32_t) * grown));
+            p.queue = q.mem.p; p.queueSlots = q.mem.p + kQueueHeaderWords; p.queueCap = cap;
+        }
+        DXV_HIP(c, hipMemsetAsync(q.mem.p, 0, sizeof(uint32_t) * kQueueHeaderWords, s));
+        DXV_HIP(c, queue_order_write(p, q.lens, q.bricks, sorted, s));
+    }
+#endif
+    DXV_HIP(c, hipEventRecord(c->ev[9], s));
+    DXV_HIP(c, hipStreamSynchronize(s));
     q.N = N; q.z0 = z0; q.nz = nzLocal; q.zBlock = zBlock; q.zPeriod = zPeriod; q.regionBits = p.planRegionBits; q.planHeavy = p.planHeavy; q.cap = cap;
     q.ms = elapsed(c->ev[8], c->ev[9]);
     q.used = ++c->preparedClock;

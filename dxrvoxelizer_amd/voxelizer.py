@@ -540,6 +540,14 @@ class Voxelizer:
         return {"live_voxels": int(out[0]), "live_bricks": int(out[1]), "queued_bricks": int(out[2]), "violations": int(out[3]),
                 "duplicates": int(out[4]), "first": [int(v) for v in out[5:5 + int(min(out[3], 11))]]}
 
+    def queue_order(self):
+        """dxv_debug_queue_order for the prepared queue the current frame's last launch ran: dict with items, shared_tiles (direction
+        tiles in more than one queue's own share: must be 0), descents (neighbours of one class of one queue out of order: must be 0) and
+        checksum (over queue, item number and brick word: two builds of one queue give the same)."""
+        out = np.zeros(4, np.uint64)
+        self._check(self._lib.dxv_debug_queue_order(self._ctx, out.ctypes.data_as(C.c_void_p)))
+        return {"items": int(out[0]), "shared_tiles": int(out[1]), "descents": int(out[2]), "checksum": int(out[3])}
+
     def division_check(self, n_first, n_last):
         """dxv_debug_division_check: (voxel origins checked, origins where a set-up word differs from the IEEE quotient's, first ids) over
         every even grid size in [n_first, n_last]."""

@@ -207,8 +207,9 @@ DXV_API int dxv_sync_all(dxv_ctx* ctx);
 /* The work queue of a STATIC scene as Init-time structure.  Which 4^3-voxel bricks of a (grid, partition) can hold a live ray is a
  * pure function of the scene's candidate lists, the grid size and the partition -- exactly like the lists are of the scene -- so it
  * can be built where the reference builds everything its frames trace through: once, in Init (Content/Voxelizer.cpp:73, :264-326),
- * leaving a frame ONE dispatch (:351-369).  dxv_prepare_launch builds that queue now (k_plan_bricks once, 0.02 ms at 512^3, plus one
- * host round trip for its sixteen counts) for slices [z0, z0 + nz) of a grid_dim^3 grid -- _interleaved: for rank's share of the
+ * leaving a frame ONE dispatch (:351-369).  dxv_prepare_launch builds that queue now (k_plan_bricks once, then a sort of the queued
+ * bricks into direction-major order -- the order the lists they read are laid out in; 0.3 ms at 512^3 with three host round trips
+ * for its counts) for slices [z0, z0 + nz) of a grid_dim^3 grid -- _interleaved: for rank's share of the
  * block-cyclic partition -- and keeps it with the context, for all its frames, until the scene or its lists change (dxv_set_mesh,
  * dxv_build, dxv_refit, dxv_scene_import, a rebuild of the lists: all drop it).  Every later dxv_voxelize* of that grid_dim and
  * partition in reference mode is then: the grid cleared (only the bricks nobody runs, by workgroups of the same dispatch) + one
@@ -698,6 +699,13 @@ DXV_API int dxv_debug_far_check(dxv_ctx* ctx, uint32_t grid_dim, uint32_t z0, ui
  * out[0] = live voxels, out[1] = bricks with a live voxel, out[2] = queued bricks, out[3] = live bricks that are NOT queued (must
  * be 0), out[4] = bricks queued more than once (must be 0), out[5 + k] = brick word (bx | by << 10 | bz << 20) of the first 11. */
 DXV_API int dxv_debug_plan_check(dxv_ctx* ctx, uint64_t out[16]);
+
+/* Test hook: the order of the PREPARED queue that the current frame's last launch ran (direction-major, whole map tiles dealt to
+ * the eight queues), read back on the device.  out[0] = queued items, out[1] = direction tiles that appear in more than one queue
+ * within the queues' own first ceil(items / 8) items (must be 0), out[2] = neighbouring items of one class (heavy / other) of one
+ * queue whose (direction tile, start radius) falls (must be 0), out[3] = a wrapping sum over every (queue, item number, brick word):
+ * the same for two builds of the same queue. */
+DXV_API int dxv_debug_queue_order(dxv_ctx* ctx, uint64_t out[4]);
 
 /* Give back what the context keeps only to make the next build faster: the list build's scratch (up to 16 GiB per buffer
  * after a 10 M-triangle scene), the LBVH build's scratch when no refit can follow (imported scenes), the memory of prepared queues
