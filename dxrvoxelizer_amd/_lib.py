@@ -105,6 +105,19 @@ SYMBOLS = {
     "dxv_octree_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "dxv_octree_expand_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
     "dxv_octree_expand": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    "dxv_components_async": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "dxv_components": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "dxv_components_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dxv_components_labels_device_ptr": (C.c_void_p, [C.c_void_p]),
+    "dxv_components_labels_bytes": (C.c_size_t, [C.c_void_p]),
+    "dxv_components_table_device_ptr": (C.c_void_p, [C.c_void_p]),
+    "dxv_components_table_bytes": (C.c_size_t, [C.c_void_p]),
+    "dxv_components_labels_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_components_table_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_components_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "dxv_components_select_async": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
+    "dxv_components_select": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
+    "dxv_components_select_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "dxv_fill_async": (C.c_int, [C.c_void_p, C.c_int]),
     "dxv_fill": (C.c_int, [C.c_void_p, C.c_int]),
     "dxv_fill_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),

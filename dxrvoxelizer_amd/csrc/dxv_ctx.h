@@ -268,6 +268,25 @@ struct dxv_ctx {
         float oct_ms = 0.0f;
         bool octExpandPending = false;   // dxv_octree_expand_async read a CALLER's tree whose verdict (status word kOctStatusWord: an index that could not be
                                          // followed) nobody has read yet: the frame can still report something, and its next synchronisation reads it
+        // connected components (components.hip; dxv_components_async): labels and table of the frame's grid and the scratch of their build
+        // (two bits per voxel, a count per 64 voxels, the scan's sums; 32 bytes per component for the stats), the frame's own; the scratch
+        // goes with dxv_trim, labels and table stay
+        DevBuf<uint32_t> compLabels;     // (cap: voxels)
+        DevBuf<uint8_t> compTable;       // (cap: components) 24 bytes each
+        DevBuf<uint8_t> compScratch;     // (cap: bytes) comp_scratch_bytes
+        DevBuf<uint8_t> compWork;        // (cap: bytes) the stats of a build, then the counters and keep flags of a select
+        uint32_t compCount = 0, compDim = 0;          // K and the grid side of the frame's last labelling ...
+        int compOf = 0, compConnectivity = 0;         // ... and what it was asked for
+        bool compHave = false;           // the frame has had its grid labelled ...
+        bool compCurrent = false;        // ... and the labels belong to the frame's grid as it is (a new launch, a fill, an expansion or a select makes them stale)
+        hipEvent_t evC0 = nullptr, evC1 = nullptr;   // around the frame's last labelling
+        bool compTimed = false;          // ... which was bracketed by them and not read yet (the frame's next dxv_sync reads it)
+        float comp_ms = 0.0f;
+        bool selPending = false;         // a select's four counters are on their way into page-locked words: the frame's next synchronisation reads them
+        int selRule = 0;
+        uint32_t selComponents = 0;      // K of the labels that select edited from
+        uint32_t selKept = 0, selDropped = 0;         // of the frame's last select, as of its last synchronisation
+        uint64_t selChanged = 0;
     };
     Frame frames[DXV_FRAME_COUNT];
     uint32_t cur = 0;                    // dxv_set_frame
@@ -299,6 +318,8 @@ struct dxv_ctx {
         uint32_t fillCtl[DXV_FRAME_COUNT][64];           // the control block of a frame's last fill batch (kFillMaxRounds words)
         unsigned long long isoTotals[DXV_FRAME_COUNT][2]; // vertices and quads of the mesh a frame is extracting: sizes its buffers
         unsigned long long octTotals[DXV_FRAME_COUNT][12]; // level_first[0 .. L] of the tree a frame is building: sizes its node buffer
+        unsigned long long compTotal[DXV_FRAME_COUNT];    // K of the labelling a frame is building: sizes its table
+        unsigned long long compSel[DXV_FRAME_COUNT][4];   // kept, dropped, voxels changed and the largest component's key of a frame's last select
     };
     Pinned* pin = nullptr;
     hipEvent_t evList[4] = {};       // around the counting pass, around the rest of the build

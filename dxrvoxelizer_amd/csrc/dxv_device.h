@@ -272,6 +272,35 @@ hipError_t launch_oct_emit(const OctParams& p, hipStream_t s);
 // every voxel of the grid of side N becomes 0 or 1 from a tree of `count` nodes (4-byte aligned, not trusted); *bad = 1 if it cannot be followed
 hipError_t launch_oct_expand(uint8_t* grid, uint32_t N, const uint32_t* nodes, uint32_t count, uint32_t* bad, hipStream_t s);
 
+// components.hip -- the connected components of a whole N^3 grid (dxv_components.h): pack, init, merge, compress, number; ONE read of K by the
+// caller; the table.  scratch: comp_scratch_bytes(N) -- the member mask (a bit per voxel), the root bits (a bit per voxel), a count per 64
+// voxels, the scan's block sums, the total.  labels: N^3 uint32; table: 24 bytes per component; stats: 32 bytes per component of scratch.
+struct CompRecord;
+struct CompStats;
+struct CompParams {
+    const uint8_t* grid;    // N^3 bytes, element (iz * N + iy) * N + ix; a voxel is solid iff its byte is non-zero
+    uint32_t N;
+    int of;                 // DXV_COMP_SOLID / DXV_COMP_EMPTY
+    uint32_t connectivity;  // 6 / 26
+    uint32_t* labels;       // parent during the build, then the labels
+    uint64_t* mask;         // comp_scratch_layout fills these five
+    uint64_t* rootMask;
+    uint32_t* bases;
+    unsigned long long* sums;
+    unsigned long long* total;    // K
+    CompStats* stats;
+    CompRecord* table;
+};
+size_t comp_scratch_bytes(uint32_t N);
+void comp_scratch_layout(uint8_t* scratch, uint32_t N, CompParams& p);
+hipError_t launch_comp_label(const CompParams& p, hipStream_t s);
+hipError_t launch_comp_stats(const CompParams& p, uint32_t K, hipStream_t s);
+// dxv_components_select: `work` -- comp_select_bytes(K) -- holds {kept, dropped, voxels changed, the maximum of comp_best_key}, then K keep flags
+size_t comp_select_bytes(uint32_t K);
+unsigned long long* comp_select_counters(uint8_t* work);
+hipError_t launch_comp_select(uint8_t* grid, uint32_t N, int of, const uint32_t* labels, const CompRecord* table, uint32_t K, int rule, uint32_t arg, uint8_t* work,
+                              hipStream_t s);
+
 // raycast.hip
 struct RayCastCB;
 hipError_t launch_raycast(const RayCastCB& cb, const uint8_t* grid, uint32_t N, uint32_t width, uint32_t height,

@@ -6,6 +6,7 @@
 #include "dxv_fill.h"
 #include "dxv_isosurface.h"
 #include "dxv_octree.h"
+#include "dxv_components.h"
 
 using namespace dxv;
 using namespace dxvhost;
@@ -35,6 +36,8 @@ int frame_prepare(dxv_ctx* c, uint32_t i)
     if (!f.evI1) DXV_HIP(c, hipEventCreate(&f.evI1));
     if (!f.evO0) DXV_HIP(c, hipEventCreate(&f.evO0));
     if (!f.evO1) DXV_HIP(c, hipEventCreate(&f.evO1));
+    if (!f.evC0) DXV_HIP(c, hipEventCreate(&f.evC0));
+    if (!f.evC1) DXV_HIP(c, hipEventCreate(&f.evC1));
     DXV_HIP(c, f.status.reserve(64, 256));
     DXV_HIP(c, f.redo.reserve(kRedoCap, sizeof(uint64_t) * kRedoCap));
     // on the frame's own stream, and finished before anything reads the words: the streams are non-blocking, a memset on the
@@ -592,6 +595,7 @@ int voxelize_common(dxv_ctx* c, uint32_t N, int mode, uint32_t z0, uint32_t nzLo
     f.mdistCurrent = false;
     f.isoCurrent = false;
     f.octCurrent = false;
+    f.compCurrent = false;
     f.fillPending = false;                                              // (... and a fill of it that has not converged yet is dropped: its batch in the stream ends in front of this launch)
     return launch_now(c, c->cur);
 }
@@ -615,6 +619,15 @@ static int sync_launch(dxv_ctx* c, uint32_t i)
         if (f.mdistTimed) { f.mdist_ms = elapsed(f.evM0, f.evM1); f.mdistTimed = false; }
         if (f.isoTimed) { f.iso_ms = elapsed(f.evI0, f.evI1); f.isoTimed = false; }
         if (f.octTimed) { f.oct_ms = elapsed(f.evO0, f.evO1); f.octTimed = false; }
+        if (f.compTimed) { f.comp_ms = elapsed(f.evC0, f.evC1); f.compTimed = false; }
+        if (f.selPending) {                                             // the counters of the frame's last select (k_comp_keep has the LARGEST case)
+            const unsigned long long* sel = c->pin->compSel[i];
+            const bool largest = f.selRule == DXV_SELECT_LARGEST && f.selComponents;
+            f.selKept = largest ? 1u : (uint32_t)sel[0];
+            f.selDropped = largest ? f.selComponents - 1u : (uint32_t)sel[1];
+            f.selChanged = largest ? sel[2] - (sel[3] >> 32) : sel[2];
+            f.selPending = false;
+        }
         // lists this launch was queued behind without waiting for their verdict: withdrawn -> the launch again, through the tree
         if (settle_lists(c)) return 1;
         if (f.pending && f.usedLists && f.listEpochUsed == c->withdrawnEpoch && c->haveScene && f.grid_dim) {
@@ -1247,6 +1260,7 @@ int dxv_octree_expand_async(dxv_ctx* c, const void* deviceNodes, uint32_t nodes,
     f.mdistCurrent = false;
     f.isoCurrent = false;
     f.octCurrent = false;
+    f.compCurrent = false;
     DXV_HIP(c, launch_oct_expand(f.grid.p, N, static_cast<const uint32_t*>(deviceNodes), nodes, f.status.p + kOctStatusWord, fs));
     DXV_HIP(c, hipEventRecord(f.evEnd, fs));
     if (!own) f.octExpandPending = true;                                // (the frame's own tree was made by the build: it has nothing to report)
@@ -1257,6 +1271,174 @@ int dxv_octree_expand(dxv_ctx* c, const void* deviceNodes, uint32_t nodes, uint3
 {
     if (dxv_octree_expand_async(c, deviceNodes, nodes, levels)) return 1;
     return dxv_sync(c);
+}
+
+// The connected components of the selected frame's grid (components.hip; dxv_components.h has the rule's routines), enqueued on the frame's
+// stream behind whatever it holds, under dxv_render_async's host-wait rule: pack, init, merge, compress and the numbering, K into a
+// page-locked word and the one wait for it -- the pattern of dxv_octree_async: the table cannot be sized without it --, then the stats kernels
+// and the frame's end event, which nobody waits for here.
+int dxv_components_async(dxv_ctx* c, int of, int connectivity)
+{
+    if (!c) return 1;
+    if (of != DXV_COMP_SOLID && of != DXV_COMP_EMPTY) return fail(c, "dxv_components: unknown kind %d (DXV_COMP_SOLID = 0, DXV_COMP_EMPTY = 1)", of);
+    if (connectivity != 6 && connectivity != 26) return fail(c, "dxv_components: connectivity %d (6 or 26)", connectivity);
+    Frame& f = cur_frame(c);
+    if (!f.grid.p || !f.grid_dim) return fail(c, "dxv_components: frame %u has no grid yet (call dxv_voxelize first)", c->cur);
+    if (!frame_renderable(f))
+        return fail(c, "dxv_components: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share");
+    const uint32_t N = f.grid_dim;
+    if (N > kCompMaxN) return fail(c, "dxv_components: a grid of %u^3 voxels; at most %u^3 (a label and a linear index must fit 32 bits)", N, kCompMaxN);
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (settle_frame_launch(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    const size_t voxels = (size_t)N * N * N, scratch = comp_scratch_bytes(N);
+    DXV_HIP(c, f.compScratch.reserve(scratch, scratch, fs));
+    f.compCurrent = false;                                              // (the build writes into the frame's label buffer: what it held is gone)
+    DXV_HIP(c, f.compLabels.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
+    CompParams p{};
+    p.grid = f.grid.p; p.of = of; p.connectivity = (uint32_t)connectivity; p.labels = f.compLabels.p;
+    comp_scratch_layout(f.compScratch.p, N, p);
+    const bool timed = c->opt.events != 0;
+    unsigned long long* total = &c->pin->compTotal[c->cur];
+    f.compTimed = false;                                                // (the first event is recorded again: an earlier pair is no pair any more)
+    if (timed) DXV_HIP(c, hipEventRecord(f.evC0, fs));
+    DXV_HIP(c, launch_comp_label(p, fs));
+    DXV_HIP(c, hipMemcpyAsync(total, p.total, sizeof(unsigned long long), hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipStreamSynchronize(fs));
+    const uint32_t K = (uint32_t)*total;
+    if (K) {
+        DXV_HIP(c, f.compTable.reserve(K, align256((size_t)K * sizeof(CompRecord)), fs));
+        DXV_HIP(c, f.compWork.reserve((size_t)K * sizeof(CompStats), align256((size_t)K * sizeof(CompStats)), fs));
+        p.table = reinterpret_cast<CompRecord*>(f.compTable.p);
+        p.stats = reinterpret_cast<CompStats*>(f.compWork.p);
+        DXV_HIP(c, launch_comp_stats(p, K, fs));
+    }
+    if (timed) DXV_HIP(c, hipEventRecord(f.evC1, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    f.compTimed = timed;
+    f.compCount = K; f.compDim = N; f.compOf = of; f.compConnectivity = connectivity;
+    f.compHave = true; f.compCurrent = true;
+    return 0;
+}
+
+int dxv_components(dxv_ctx* c, int of, int connectivity)
+{
+    if (dxv_components_async(c, of, connectivity)) return 1;
+    return dxv_sync(c);
+}
+
+// whether the frame has labels to hand out: 0, or 1 with the reason as the message
+static int current_labels(const dxv_ctx* c, const char* who)
+{
+    const Frame& f = c->frames[c->cur];
+    dxv_ctx* w = const_cast<dxv_ctx*>(c);                               // (the message is the one thing an accessor writes)
+    if (!f.compHave) return fail(w, "%s: frame %u has no components yet (call dxv_components first)", who, c->cur);
+    if (!f.compCurrent)
+        return fail(w, "%s: frame %u was launched, filled, expanded or selected again since its components were labelled: labels and table are stale", who, c->cur);
+    return 0;
+}
+
+int dxv_components_info(dxv_ctx* c, uint32_t* count, int* of, int* connectivity)
+{
+    if (!c) return 1;
+    if (current_labels(c, "dxv_components_info")) return 1;
+    const Frame& f = cur_frame(c);
+    if (count) *count = f.compCount;
+    if (of) *of = f.compOf;
+    if (connectivity) *connectivity = f.compConnectivity;
+    return 0;
+}
+
+const void* dxv_components_labels_device_ptr(const dxv_ctx* c)
+{
+    if (!c || current_labels(c, "dxv_components_labels_device_ptr")) return nullptr;
+    return c->frames[c->cur].compLabels.p;
+}
+size_t dxv_components_labels_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame& f = c->frames[c->cur];
+    return f.compHave && f.compCurrent ? (size_t)f.compDim * f.compDim * f.compDim * sizeof(uint32_t) : 0;
+}
+const void* dxv_components_table_device_ptr(const dxv_ctx* c)
+{
+    if (!c || current_labels(c, "dxv_components_table_device_ptr")) return nullptr;
+    return c->frames[c->cur].compCount ? c->frames[c->cur].compTable.p : nullptr;
+}
+size_t dxv_components_table_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame& f = c->frames[c->cur];
+    return f.compHave && f.compCurrent ? (size_t)f.compCount * sizeof(CompRecord) : 0;
+}
+
+int dxv_components_labels_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || current_labels(c, "dxv_components_labels_download")) return 1;
+    return mesh_download(c, "dxv_components_labels_download", cur_frame(c).compLabels.p, dxv_components_labels_bytes(c), host, bytes);
+}
+int dxv_components_table_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || current_labels(c, "dxv_components_table_download")) return 1;
+    return mesh_download(c, "dxv_components_table_download", cur_frame(c).compTable.p, dxv_components_table_bytes(c), host, bytes);
+}
+
+int dxv_components_ms(dxv_ctx* c, float* ms)
+{
+    if (!c) return 1;
+    if (!ms) return fail(c, "dxv_components_ms: ms is NULL");
+    *ms = cur_frame(c).comp_ms;
+    return 0;
+}
+
+// The selected frame's grid edited from its labels (components.hip: k_comp_keep, k_comp_edit), in place, enqueued on the frame's stream behind
+// whatever it holds -- under dxv_render_async's host-wait rule and dxv_fill_async's rules for the grid.  The four counters go into page-locked
+// words and are read where the frame is next synchronised.
+int dxv_components_select_async(dxv_ctx* c, int rule, uint32_t arg)
+{
+    if (!c) return 1;
+    if (rule != DXV_SELECT_LARGEST && rule != DXV_SELECT_MIN_VOXELS && rule != DXV_SELECT_BORDER)
+        return fail(c, "dxv_components_select: unknown rule %d (DXV_SELECT_LARGEST = 0, DXV_SELECT_MIN_VOXELS = 1, DXV_SELECT_BORDER = 2)", rule);
+    if (rule != DXV_SELECT_MIN_VOXELS && arg) return fail(c, "dxv_components_select: rule %d takes no argument (arg must be 0, got %u)", rule, arg);
+    if (current_labels(c, "dxv_components_select")) return 1;
+    Frame& f = cur_frame(c);
+    if (!f.grid.p || f.grid_dim != f.compDim || !frame_renderable(f))
+        return fail(c, "dxv_components_select: the labels of frame %u do not belong to its grid: they are stale", c->cur);
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (settle_frame_launch(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    const uint32_t K = f.compCount;
+    const size_t work = comp_select_bytes(K);
+    DXV_HIP(c, f.compWork.reserve(work, work, fs));
+    // the grid stops being what the frame's last launch wrote (dxv_fill_async's rules): a kept queue's zeros are gone, and whatever was made
+    // of the grid before -- fields, the mesh, the tree, these labels -- is stale
+    f.clearSig = 0;
+    f.distCurrent = false;
+    f.mdistCurrent = false;
+    f.isoCurrent = false;
+    f.octCurrent = false;
+    f.compCurrent = false;
+    DXV_HIP(c, launch_comp_select(f.grid.p, f.compDim, f.compOf, f.compLabels.p, reinterpret_cast<const CompRecord*>(f.compTable.p), K, rule, arg, f.compWork.p, fs));
+    DXV_HIP(c, hipMemcpyAsync(c->pin->compSel[c->cur], comp_select_counters(f.compWork.p), sizeof(c->pin->compSel[c->cur]), hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    f.selPending = true; f.selRule = rule; f.selComponents = K;
+    return 0;
+}
+
+int dxv_components_select(dxv_ctx* c, int rule, uint32_t arg)
+{
+    if (dxv_components_select_async(c, rule, arg)) return 1;
+    return dxv_sync(c);
+}
+
+int dxv_components_select_info(dxv_ctx* c, uint32_t* kept, uint32_t* dropped, uint64_t* voxels_changed)
+{
+    if (!c) return 1;
+    const Frame& f = cur_frame(c);
+    if (kept) *kept = f.selKept;
+    if (dropped) *dropped = f.selDropped;
+    if (voxels_changed) *voxels_changed = f.selChanged;
+    return 0;
 }
 
 // The exterior flood fill of the selected frame's grid (fill.hip), in place, enqueued on the frame's stream behind whatever it holds --
@@ -1288,6 +1470,7 @@ int dxv_fill_async(dxv_ctx* c, int what)
     f.mdistCurrent = false;
     f.isoCurrent = false;
     f.octCurrent = false;
+    f.compCurrent = false;
     if (timed) DXV_HIP(c, hipEventRecord(f.evF0, fs));
     DXV_HIP(c, launch_fill(f.grid.p, N, what, f.fillScratch.p, f.fillBatch, true, fs));
     if (timed) DXV_HIP(c, hipEventRecord(f.evF1, fs));

@@ -15,6 +15,9 @@ MDIST_VOXELS_F32, MDIST_UNITS_F32 = 0, 1          # formats of the mesh distance
 FILL_SOLID, FILL_INTERIOR = 0, 1                  # what the flood fill leaves (include/dxv.h)
 ISO_MESH_DISTANCE, ISO_GRID_DISTANCE = 0, 1       # the field an isosurface is taken from (include/dxv.h)
 ISO_SPACE_VOXELS, ISO_SPACE_OBJECT = 0, 1         # ... and the space its vertices are in
+COMP_SOLID, COMP_EMPTY = 0, 1                     # what connected components are taken of (include/dxv.h)
+SELECT_LARGEST, SELECT_MIN_VOXELS, SELECT_BORDER = 0, 1, 2   # which components SelectComponents keeps
+COMP_RECORD = np.dtype([("first", "<u4"), ("voxels", "<u4"), ("lo", "<u2", (3,)), ("hi", "<u2", (3,)), ("flags", "<u4")])   # a row of the components' table, 24 bytes
 DBG_SORTED_KEYS, DBG_NODES, DBG_TRI_POS, DBG_TRI_NRM, DBG_PARENTS, DBG_NODES32, DBG_NODES64, DBG_LIST_CELLS, DBG_LIST_ENTRIES, DBG_LIST_MIP = range(10)
 DBG_BRICK_EMPTY, DBG_BRICK_SUMMARY = 10, 11         # the display pass's empty-brick flags and the summaries behind them
 
@@ -461,6 +464,69 @@ class Voxelizer:
             raise DxvError("OctreeExpand: a caller's tree needs levels = its L")
         self._check(fn(self._ctx, C.c_void_p(ptr), int(count), int(levels)))
         return True
+
+    # ---- the connected components of the frame's grid ----------------------------------------------
+    def Components(self, of=COMP_SOLID, connectivity=6, sync=True, frameIndex=None):
+        """Label the connected components of the selected frame's whole grid on the device (dxv_components / dxv_components_async; include/dxv.h
+        has the rule): of = COMP_SOLID the non-zero voxels, COMP_EMPTY the zero ones; connectivity 6 or 26; components numbered 1 .. K by their
+        smallest linear index.  sync=True returns (labels [N, N, N] uint32, table), the table a structured array with fields first, voxels,
+        lo, hi, flags; sync=False only enqueues the stats pass (the call still reads K once) and returns True."""
+        if frameIndex is not None:
+            self.SetFrame(frameIndex)
+        fn = self._lib.dxv_components if sync else self._lib.dxv_components_async
+        self._check(fn(self._ctx, int(of), int(connectivity)))
+        return (self.ComponentLabels(), self.ComponentTable()) if sync else True
+
+    def components_info(self):
+        """(K, of, connectivity) of the selected frame's labelling (dxv_components_info); raises where the library refuses (none yet, or stale)."""
+        count, of, conn = C.c_uint32(), C.c_int(), C.c_int()
+        self._check(self._lib.dxv_components_info(self._ctx, C.byref(count), C.byref(of), C.byref(conn)))
+        return count.value, of.value, conn.value
+
+    def ComponentLabels(self):
+        """numpy copy [N, N, N] uint32 of the selected frame's labels (dxv_components_labels_download; synchronises the frame)."""
+        self.components_info()
+        nbytes = self._lib.dxv_components_labels_bytes(self._ctx)
+        side = self.stats()["grid_dim"]                                 # labels are current: made of the grid of the frame's last launch
+        if side ** 3 * 4 != nbytes:
+            raise DxvError(f"component labels of {nbytes} bytes do not belong to the frame's last launch ({side}^3 voxels)")
+        labels = np.empty((side, side, side), np.uint32)
+        self._check(self._lib.dxv_components_labels_download(self._ctx, labels.ctypes.data_as(C.c_void_p), labels.nbytes))
+        return labels
+
+    def ComponentTable(self):
+        """numpy copy [K] of the selected frame's table, dtype COMP_RECORD (dxv_components_table_download; synchronises the frame)."""
+        count, _, _ = self.components_info()
+        table = np.empty(count, COMP_RECORD)
+        self._check(self._lib.dxv_components_table_download(self._ctx, table.ctypes.data_as(C.c_void_p), table.nbytes))
+        return table
+
+    def component_device_ptrs(self):
+        """(labels, table) device pointers of the selected frame's labelling, for consumers on the GPU; the table's is None when K = 0."""
+        labels = self._lib.dxv_components_labels_device_ptr(self._ctx)
+        if not labels:
+            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
+        return labels, self._lib.dxv_components_table_device_ptr(self._ctx)
+
+    def components_ms(self):
+        """Device time of the selected frame's last labelling, read at the frame's Sync (dxv_components_ms)."""
+        ms = C.c_float()
+        self._check(self._lib.dxv_components_ms(self._ctx, C.byref(ms)))
+        return ms.value
+
+    def SelectComponents(self, rule, arg=0, sync=True):
+        """Edit the selected frame's grid in place from its current labels (dxv_components_select / _async): the voxels of every component
+        that rule does not keep become 0 (labels of COMP_SOLID) or 1 (COMP_EMPTY).  SELECT_LARGEST keeps the component with the most voxels,
+        SELECT_MIN_VOXELS those with voxels >= arg, SELECT_BORDER those that touch the grid's border.  The labels are stale afterwards."""
+        fn = self._lib.dxv_components_select if sync else self._lib.dxv_components_select_async
+        self._check(fn(self._ctx, int(rule), int(arg)))
+        return True
+
+    def select_info(self):
+        """(kept, dropped, voxels_changed) of the selected frame's last SelectComponents as of its last Sync (dxv_components_select_info)."""
+        kept, dropped, changed = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self._check(self._lib.dxv_components_select_info(self._ctx, C.byref(kept), C.byref(dropped), C.byref(changed)))
+        return kept.value, dropped.value, changed.value
 
     # ---- the exterior flood fill of the frame's grid -----------------------------------------------
     def Fill(self, what=FILL_SOLID, sync=True, frameIndex=None):

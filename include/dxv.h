@@ -191,7 +191,7 @@ DXV_API int dxv_sync(dxv_ctx* ctx);
  * frameIndex (static const uint8_t FrameCount, Content/Voxelizer.h:24; m_grids[FrameCount], :110;
  * Render(pCommandList, frameIndex, ...), :21-22; voxelize(pCommandList, frameIndex), Content/Voxelizer.cpp:351-356),
  * so that the GPU works on one grid while the host still reads another.  dxv_set_frame selects the frame the
- * following dxv_voxelize* / dxv_sync / dxv_grid_* / dxv_texels_download / dxv_render* / dxv_update_frame / dxv_distance* / dxv_fill* / dxv_isosurface* / dxv_octree* / dxv_get_stats calls refer to
+ * following dxv_voxelize* / dxv_sync / dxv_grid_* / dxv_texels_download / dxv_render* / dxv_update_frame / dxv_distance* / dxv_fill* / dxv_isosurface* / dxv_octree* / dxv_components* / dxv_get_stats calls refer to
  * (default 0).  Each frame owns its grid, texel image, status words and -- frames 1 and 2 -- an internal stream,
  * so launches of different frames overlap on the GPU; scene, candidate lists and options are shared (an extra frame
  * costs its grid).  Calls that change what the frames read (dxv_set_mesh, dxv_build, dxv_scene_import, dxv_set_stream) first
@@ -543,6 +543,69 @@ DXV_API int dxv_octree_ms(dxv_ctx* ctx, float* ms);
 DXV_API int dxv_octree_expand_async(dxv_ctx* ctx, const void* device_nodes, uint32_t nodes, uint32_t levels);
 DXV_API int dxv_octree_expand(dxv_ctx* ctx, const void* device_nodes, uint32_t nodes, uint32_t levels);
 
+/* Connected components: what the selected frame's grid CONSISTS of, labelled on the device (no reference counterpart) -- how many separate
+ * pieces the solid has, whether a piece is a 40-voxel floater left by a leaky normal, how many closed cavities there are and how big, which
+ * voxels to drop so that only the main body is kept: the analysis step between a grid and its field, mesh or tree.  Input: the WHOLE N^3 grid
+ * of the selected frame's last launch, as it is when the kernels run (bytes written through dxv_grid_device_ptr count).
+ *     member(p)    of = DXV_COMP_SOLID: byte(p) != 0 (dxv_solid.h)      of = DXV_COMP_EMPTY: byte(p) == 0
+ *     adjacent     p != q, both inside the grid, |dx|,|dy|,|dz| <= 1, and for connectivity 6: |dx|+|dy|+|dz| == 1; for 26: any
+ *     component    a class of the transitive closure of `adjacent` over the members
+ *     first(C)     the smallest linear index (iz*N + iy)*N + ix of C's voxels
+ *     numbering    components 1 .. K by ascending first(C)
+ *     labels[p]    uint32: the number of p's component, 0 when !member(p)
+ *     table[k-1]   24 bytes, little endian: uint32 first; uint32 voxels; uint16 lo[3] (x, y, z); uint16 hi[3]; uint32 flags
+ *                  flags bit 0: the component has a voxel on the grid's border (any of ix, iy, iz is 0 or N-1); other bits 0
+ * Nothing is left to choice, so labels and table are unique: the device's equal a restatement byte for byte.  (The numbering is also the one
+ * scipy.ndimage.label gives.) */
+enum { DXV_COMP_SOLID = 0, DXV_COMP_EMPTY = 1 };
+enum { DXV_SELECT_LARGEST = 0, DXV_SELECT_MIN_VOXELS = 1, DXV_SELECT_BORDER = 2 };
+/* dxv_components_async -- pack, union-find and numbering kernels ENQUEUED on the frame's stream behind whatever it holds, then ONE host read
+ * of K from a page-locked word (the table cannot be sized without it), then the stats kernels enqueued; returns without waiting for those.
+ *  - The host waits before that only under dxv_render_async's rule; a pending fill is settled first.
+ *  - Checked on the host before anything is enqueued, each an error with a message: `of` is one of the two kinds; connectivity is 6 or 26; the
+ *    frame has been launched; its last launch was the whole grid, not a slab or a share; N <= 1624 (a label and a linear index must both fit a
+ *    uint32: 1625^3 < 2^32 < 1626^3, and N is even).
+ *  - Labels (N^3 * 4 bytes), table and scratch (two bits per voxel, 4 bytes per 64 voxels, 32 bytes per component) belong to the frame: frames
+ *    label side by side.  dxv_trim gives the scratch back and keeps labels and table.
+ *  - Labels and table are STALE once the frame is launched, filled, expanded or selected again: info, pointers, sizes and downloads then
+ *    fail with a message.
+ *  - Option events = 1 (default): bracketed by the frame's own two events; dxv_components_ms reads them at the frame's dxv_sync.
+ * dxv_components -- the same + dxv_sync. */
+DXV_API int dxv_components_async(dxv_ctx* ctx, int of, int connectivity);
+DXV_API int dxv_components(dxv_ctx* ctx, int of, int connectivity);
+/* K, the kind and the connectivity of the selected frame's labelling (any pointer may be NULL). */
+DXV_API int dxv_components_info(dxv_ctx* ctx, uint32_t* count, int* of, int* connectivity);
+/* Labels and table on the device (valid after dxv_sync or on the frame's stream) and their sizes: N^3 * 4 and K * 24 bytes.  NULL / 0 -- the
+ * pointers with a message -- before the frame's first labelling or when it is stale; the table's pointer is NULL when K = 0. */
+DXV_API const void* dxv_components_labels_device_ptr(const dxv_ctx* ctx);
+DXV_API size_t dxv_components_labels_bytes(const dxv_ctx* ctx);
+DXV_API const void* dxv_components_table_device_ptr(const dxv_ctx* ctx);
+DXV_API size_t dxv_components_table_bytes(const dxv_ctx* ctx);
+/* Copies to the host (bytes must be the size above; 0 bytes of an empty table are accepted); synchronise the frame first. */
+DXV_API int dxv_components_labels_download(dxv_ctx* ctx, void* host, size_t bytes);
+DXV_API int dxv_components_table_download(dxv_ctx* ctx, void* host, size_t bytes);
+/* Device time of the selected frame's last labelling in milliseconds (HIP events; the host's read of K lies inside it), read at the frame's
+ * dxv_sync: 0 before that, and under option events = 0. */
+DXV_API int dxv_components_ms(dxv_ctx* ctx, float* ms);
+/* dxv_components_select_async -- the selected frame's grid edited IN PLACE from its current labels; ENQUEUED on the frame's stream behind
+ * whatever it holds, returns without waiting.  A component is kept under
+ *     DXV_SELECT_LARGEST     it has the most voxels; ties go to the smaller number.  arg must be 0.
+ *     DXV_SELECT_MIN_VOXELS  voxels >= arg
+ *     DXV_SELECT_BORDER      flags & 1.  arg must be 0.
+ * A voxel of a component that is not kept becomes 0 when of = DXV_COMP_SOLID and 1 when of = DXV_COMP_EMPTY; every other byte stays as it is,
+ * values other than 0 and 1 included.  So dxv_components(SOLID) + select(LARGEST) removes floaters; dxv_components(EMPTY) + select(MIN_VOXELS, m)
+ * closes cavities and pores below m voxels; after dxv_components(EMPTY, 6) + select(BORDER) the grid's != 0 set is dxv_fill(DXV_FILL_SOLID)'s.
+ *  - dxv_fill_async's rules for the grid: the host waits only under dxv_render_async's rule; fields, the mesh and the tree made before are
+ *    stale after it, and so are the labels themselves; a kept queue's zeros are dropped: the frame's next launch clears its whole grid.
+ *  - Checked on the host before anything is enqueued, each an error with a message: the rule is one of the three; arg is 0 where the rule takes
+ *    none; the frame has labels and they are not stale.
+ * dxv_components_select -- the same + dxv_sync. */
+DXV_API int dxv_components_select_async(dxv_ctx* ctx, int rule, uint32_t arg);
+DXV_API int dxv_components_select(dxv_ctx* ctx, int rule, uint32_t arg);
+/* The selected frame's last select as of the frame's last dxv_sync: components kept and dropped, and the voxels whose component was dropped
+ * (any pointer may be NULL). */
+DXV_API int dxv_components_select_info(dxv_ctx* ctx, uint32_t* kept, uint32_t* dropped, uint64_t* voxels_changed);
+
 /* Multi-GPU: the built scene (nodes + triangle data) as one relocatable device blob, so that
  * rank 0 builds once and the host layer broadcasts it (RCCL over xGMI) to the other ranks.
  * export copies the blob into caller-provided DEVICE memory; import adopts a blob from DEVICE
@@ -710,7 +773,7 @@ DXV_API int dxv_debug_queue_order(dxv_ctx* ctx, uint64_t out[4]);
 /* Give back what the context keeps only to make the next build faster: the list build's scratch (up to 16 GiB per buffer
  * after a 10 M-triangle scene), the LBVH build's scratch when no refit can follow (imported scenes), the memory of prepared queues
  * whose lists are gone, the scratch of the frames' distance fields (the fields stay), of their flood fills, of their isosurfaces (the
- * meshes stay) and of their octrees (the nodes stay).  Nothing a launch reads. */
+ * meshes stay), of their octrees (the nodes stay) and of their connected components (labels and table stay).  Nothing a launch reads. */
 DXV_API int dxv_trim(dxv_ctx* ctx);
 
 /* Test hook: copy an internal device array to the host (enum above). */

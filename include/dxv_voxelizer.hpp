@@ -221,6 +221,31 @@ public:
 		return SetFrame(frameIndex) && dxv_octree_expand_async(m_ctx, deviceNodes, nodes, levels) == 0;
 	}
 
+	// The connected components of that frame's whole grid (dxv_components_async: labels 1 .. K by ascending smallest index and a 24-byte record per
+	// component; include/dxv.h has the rule), enqueued behind the frame's launch.  The accessors refer to the frame last selected; WaitFrame
+	// reports the kernels' errors.  SelectComponents edits the frame's grid in place from its labels: Components(f) && SelectComponents(
+	// DXV_SELECT_LARGEST) removes floaters, Components(f, DXV_COMP_EMPTY) && SelectComponents(DXV_SELECT_MIN_VOXELS, m) closes cavities below m voxels.
+	struct ComponentRecord { uint32_t first, voxels; uint16_t lo[3], hi[3]; uint32_t flags; };
+	bool Components(uint8_t frameIndex, int of = DXV_COMP_SOLID, int connectivity = 6) { return SetFrame(frameIndex) && dxv_components_async(m_ctx, of, connectivity) == 0; }
+	bool ComponentsInfo(uint32_t& count, int& of, int& connectivity) { return m_ctx && dxv_components_info(m_ctx, &count, &of, &connectivity) == 0; }
+	const void* DeviceComponentLabels() const { return m_ctx ? dxv_components_labels_device_ptr(m_ctx) : nullptr; }
+	const void* DeviceComponentTable() const { return m_ctx ? dxv_components_table_device_ptr(m_ctx) : nullptr; }
+	bool DownloadComponents(std::vector<uint32_t>& labels, std::vector<ComponentRecord>& table)
+	{
+		if (!m_ctx) return setError("DownloadComponents before Init");
+		static_assert(sizeof(ComponentRecord) == 24, "a row of the table is 24 bytes");
+		labels.resize(dxv_components_labels_bytes(m_ctx) / sizeof(uint32_t));
+		table.resize(dxv_components_table_bytes(m_ctx) / sizeof(ComponentRecord));
+		return dxv_components_labels_download(m_ctx, labels.data(), labels.size() * sizeof(uint32_t)) == 0 &&
+			dxv_components_table_download(m_ctx, table.data(), table.size() * sizeof(ComponentRecord)) == 0;
+	}
+	bool ComponentsMs(float& ms) { return m_ctx && dxv_components_ms(m_ctx, &ms) == 0; }
+	bool SelectComponents(int rule, uint32_t arg = 0, bool sync = true)
+	{
+		return m_ctx && (sync ? dxv_components_select(m_ctx, rule, arg) : dxv_components_select_async(m_ctx, rule, arg)) == 0;
+	}
+	bool SelectInfo(uint32_t& kept, uint32_t& dropped, uint64_t& voxelsChanged) { return m_ctx && dxv_components_select_info(m_ctx, &kept, &dropped, &voxelsChanged) == 0; }
+
 	// The exterior flood fill of that frame's whole grid, in place (dxv_fill / dxv_fill_async): DXV_FILL_SOLID leaves the walls and everything
 	// they enclose, DXV_FILL_INTERIOR the enclosed voxels alone.  Voxelize(gridDim, SURFACE) && Fill() is the solid of a mesh whose
 	// normals and watertightness cannot be trusted.  Refers to the frame last selected; sync = false only enqueues (WaitFrame reports).
