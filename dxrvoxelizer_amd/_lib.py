@@ -121,6 +121,9 @@ SYMBOLS = {
     "dxv_fill_async": (C.c_int, [C.c_void_p, C.c_int]),
     "dxv_fill": (C.c_int, [C.c_void_p, C.c_int]),
     "dxv_fill_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "dxv_morph_async": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
+    "dxv_morph": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
+    "dxv_morph_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "dxv_build_lists": (C.c_int, [C.c_void_p]),
     "dxv_build_lists_for_grid": (C.c_int, [C.c_void_p, C.c_uint32]),
     "dxv_build_parity_lists": (C.c_int, [C.c_void_p]),

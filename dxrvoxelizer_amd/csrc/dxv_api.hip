@@ -249,7 +249,7 @@ void dxv_destroy(dxv_ctx* c)
     for (uint32_t i = 0; i < DXV_FRAME_COUNT; ++i) {
         Frame& f = c->frames[i];
         if (frame_stream(c, i)) (void)hipStreamSynchronize(frame_stream(c, i));
-        for (hipEvent_t ev : {f.ev0, f.ev1, f.evP0, f.evP1, f.evEnd, f.evR0, f.evR1, f.evD0, f.evD1, f.evF0, f.evF1, f.evM0, f.evM1, f.evI0, f.evI1, f.evO0, f.evO1, f.evC0, f.evC1})
+        for (hipEvent_t ev : {f.ev0, f.ev1, f.evP0, f.evP1, f.evEnd, f.evR0, f.evR1, f.evD0, f.evD1, f.evF0, f.evF1, f.evM0, f.evM1, f.evI0, f.evI1, f.evO0, f.evO1, f.evC0, f.evC1, f.evX0, f.evX1})
             if (ev) (void)hipEventDestroy(ev);
         if (f.ownStream) (void)hipStreamDestroy(f.ownStream);
     }
@@ -275,6 +275,7 @@ int dxv_trim(dxv_ctx* c)
     for (auto& f : c->frames) f.isoScratch.release();                   // (the bits, counts and sums of an isosurface extraction; a frame's mesh itself stays)
     for (auto& f : c->frames) f.octScratch.release();                   // (the dense cell words, bits and counts of an octree build; a frame's nodes themselves stay)
     for (auto& f : c->frames) { f.compScratch.release(); f.compWork.release(); }   // (the masks, counts and stats of a labelling; a frame's labels and table themselves stay)
+    for (auto& f : c->frames) f.morphScratch.release();                 // (the masks and planes of a morph: (R + 3) bits per voxel)
     c->specRes = 0;
     if (!c->haveHierarchy) c->scratch = BuildScratch{};                             // (a built scene keeps keys and links: dxv_refit reads them)
     // prepared queues of lists that are gone (their slots keep their memory for the next dxv_prepare_launch of the partition: 8 MB at

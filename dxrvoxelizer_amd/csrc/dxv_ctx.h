@@ -287,6 +287,14 @@ struct dxv_ctx {
         uint32_t selComponents = 0;      // K of the labels that select edited from
         uint32_t selKept = 0, selDropped = 0;         // of the frame's last select, as of its last synchronisation
         uint64_t selChanged = 0;
+        // morphology (morph.hip; dxv_morph_async): the bit masks and planes of the frame's morph, its own so that frames morph side by side;
+        // goes with dxv_trim
+        DevBuf<uint8_t> morphScratch;    // (cap: bytes) morph_scratch_bytes
+        hipEvent_t evX0 = nullptr, evX1 = nullptr;   // around the frame's last morph
+        bool morphTimed = false;         // ... which was bracketed by them and not read yet (the frame's next dxv_sync reads it)
+        float morph_ms = 0.0f;
+        bool morphPending = false;       // a morph's two counters are on their way into page-locked words: the frame's next synchronisation reads them
+        uint64_t morphSet = 0, morphCleared = 0;      // of the frame's last morph, as of its last synchronisation
     };
     Frame frames[DXV_FRAME_COUNT];
     uint32_t cur = 0;                    // dxv_set_frame
@@ -320,6 +328,7 @@ struct dxv_ctx {
         unsigned long long octTotals[DXV_FRAME_COUNT][12]; // level_first[0 .. L] of the tree a frame is building: sizes its node buffer
         unsigned long long compTotal[DXV_FRAME_COUNT];    // K of the labelling a frame is building: sizes its table
         unsigned long long compSel[DXV_FRAME_COUNT][4];   // kept, dropped, voxels changed and the largest component's key of a frame's last select
+        unsigned long long morphCount[DXV_FRAME_COUNT][2]; // voxels set and voxels cleared by a frame's last morph
     };
     Pinned* pin = nullptr;
     hipEvent_t evList[4] = {};       // around the counting pass, around the rest of the build

@@ -301,6 +301,13 @@ unsigned long long* comp_select_counters(uint8_t* work);
 hipError_t launch_comp_select(uint8_t* grid, uint32_t N, int of, const uint32_t* labels, const CompRecord* table, uint32_t K, int rule, uint32_t arg, uint8_t* work,
                               hipStream_t s);
 
+// morph.hip -- DILATE / ERODE / OPEN / CLOSE (0 .. 3) of a whole N^3 grid by the Euclidean ball of squared radius r2 (1 .. 4096; dxv_morph.h), in
+// place, bytes 0 / 1.  form 1: word-parallel on bit masks and R = floor(sqrt(r2)) planes; form 2: the distance field and its threshold, per
+// half.  scratch: morph_scratch_bytes(N, op, r2, form); it begins with {voxels set, voxels cleared}
+size_t morph_scratch_bytes(uint32_t N, int op, uint32_t r2, int form);
+unsigned long long* morph_counters(uint8_t* scratch);
+hipError_t launch_morph(uint8_t* grid, uint32_t N, int op, uint32_t r2, int form, uint8_t* scratch, hipStream_t s);
+
 // raycast.hip
 struct RayCastCB;
 hipError_t launch_raycast(const RayCastCB& cb, const uint8_t* grid, uint32_t N, uint32_t width, uint32_t height,

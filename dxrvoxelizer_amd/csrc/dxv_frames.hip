@@ -7,6 +7,7 @@
 #include "dxv_isosurface.h"
 #include "dxv_octree.h"
 #include "dxv_components.h"
+#include "dxv_morph.h"
 
 using namespace dxv;
 using namespace dxvhost;
@@ -38,6 +39,8 @@ int frame_prepare(dxv_ctx* c, uint32_t i)
     if (!f.evO1) DXV_HIP(c, hipEventCreate(&f.evO1));
     if (!f.evC0) DXV_HIP(c, hipEventCreate(&f.evC0));
     if (!f.evC1) DXV_HIP(c, hipEventCreate(&f.evC1));
+    if (!f.evX0) DXV_HIP(c, hipEventCreate(&f.evX0));
+    if (!f.evX1) DXV_HIP(c, hipEventCreate(&f.evX1));
     DXV_HIP(c, f.status.reserve(64, 256));
     DXV_HIP(c, f.redo.reserve(kRedoCap, sizeof(uint64_t) * kRedoCap));
     // on the frame's own stream, and finished before anything reads the words: the streams are non-blocking, a memset on the
@@ -627,6 +630,12 @@ static int sync_launch(dxv_ctx* c, uint32_t i)
             f.selDropped = largest ? f.selComponents - 1u : (uint32_t)sel[1];
             f.selChanged = largest ? sel[2] - (sel[3] >> 32) : sel[2];
             f.selPending = false;
+        }
+        if (f.morphTimed) { f.morph_ms = elapsed(f.evX0, f.evX1); f.morphTimed = false; }
+        if (f.morphPending) {                                           // the counters of the frame's last morph
+            f.morphSet = c->pin->morphCount[i][0];
+            f.morphCleared = c->pin->morphCount[i][1];
+            f.morphPending = false;
         }
         // lists this launch was queued behind without waiting for their verdict: withdrawn -> the launch again, through the tree
         if (settle_lists(c)) return 1;
@@ -1492,6 +1501,62 @@ int dxv_fill_info(dxv_ctx* c, float* ms, uint32_t* rounds)
     if (!c) return 1;
     if (ms) *ms = cur_frame(c).fill_ms;
     if (rounds) *rounds = cur_frame(c).fillRounds;
+    return 0;
+}
+
+// Morphology of the selected frame's grid by the Euclidean ball (morph.hip), in place, enqueued on the frame's stream behind whatever it holds
+// -- under dxv_render_async's host-wait rule and dxv_fill_async's rules for the grid.  A fixed chain of kernels: nothing to settle; the two
+// counters go into page-locked words and are read where the frame is next synchronised.
+int dxv_morph_async(dxv_ctx* c, int op, uint32_t radius_sq)
+{
+    if (!c) return 1;
+    if (op != DXV_MORPH_DILATE && op != DXV_MORPH_ERODE && op != DXV_MORPH_OPEN && op != DXV_MORPH_CLOSE)
+        return fail(c, "dxv_morph: unknown operation %d (DXV_MORPH_DILATE = 0, DXV_MORPH_ERODE = 1, DXV_MORPH_OPEN = 2, DXV_MORPH_CLOSE = 3)", op);
+    if (radius_sq < 1u || radius_sq > kMorphMaxRadiusSq)
+        return fail(c, "dxv_morph: radius_sq %u is not in [1, %u]", radius_sq, kMorphMaxRadiusSq);
+    Frame& f = cur_frame(c);
+    if (!f.grid.p || !f.grid_dim) return fail(c, "dxv_morph: frame %u has no grid yet (call dxv_voxelize first)", c->cur);
+    if (!frame_renderable(f))
+        return fail(c, "dxv_morph: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share");
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (settle_frame_launch(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    const uint32_t N = f.grid_dim;
+    const int form = morph_form(radius_sq, c->opt.morphform);
+    const size_t scratch = morph_scratch_bytes(N, op, radius_sq, form);
+    DXV_HIP(c, f.morphScratch.reserve(scratch, scratch, fs));
+    const bool timed = c->opt.events != 0;
+    // the grid stops being what the frame's last launch wrote (dxv_fill_async's rules): a kept queue's zeros are gone, and whatever was made
+    // of the grid before -- fields, the mesh, the tree, labels -- is stale
+    f.clearSig = 0;
+    f.distCurrent = false;
+    f.mdistCurrent = false;
+    f.isoCurrent = false;
+    f.octCurrent = false;
+    f.compCurrent = false;
+    if (timed) DXV_HIP(c, hipEventRecord(f.evX0, fs));
+    DXV_HIP(c, launch_morph(f.grid.p, N, op, radius_sq, form, f.morphScratch.p, fs));
+    if (timed) DXV_HIP(c, hipEventRecord(f.evX1, fs));
+    DXV_HIP(c, hipMemcpyAsync(c->pin->morphCount[c->cur], morph_counters(f.morphScratch.p), sizeof(c->pin->morphCount[c->cur]), hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    f.morphTimed = timed;
+    f.morphPending = true;
+    return 0;
+}
+
+int dxv_morph(dxv_ctx* c, int op, uint32_t radius_sq)
+{
+    if (dxv_morph_async(c, op, radius_sq)) return 1;
+    return dxv_sync(c);
+}
+
+int dxv_morph_info(dxv_ctx* c, float* ms, uint64_t* voxels_set, uint64_t* voxels_cleared)
+{
+    if (!c) return 1;
+    const Frame& f = cur_frame(c);
+    if (ms) *ms = f.morph_ms;
+    if (voxels_set) *voxels_set = f.morphSet;
+    if (voxels_cleared) *voxels_cleared = f.morphCleared;
     return 0;
 }
 

@@ -13,6 +13,7 @@ MODE_SURFACE, MODE_REFERENCE_SURFACE = 2, 3      # the conservative surface; the
 DIST_SQ_I32, DIST_F32 = 0, 1                     # formats of the distance field (include/dxv.h)
 MDIST_VOXELS_F32, MDIST_UNITS_F32 = 0, 1          # formats of the mesh distance field (include/dxv.h)
 FILL_SOLID, FILL_INTERIOR = 0, 1                  # what the flood fill leaves (include/dxv.h)
+MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3     # the operations of Morph (include/dxv.h)
 ISO_MESH_DISTANCE, ISO_GRID_DISTANCE = 0, 1       # the field an isosurface is taken from (include/dxv.h)
 ISO_SPACE_VOXELS, ISO_SPACE_OBJECT = 0, 1         # ... and the space its vertices are in
 COMP_SOLID, COMP_EMPTY = 0, 1                     # what connected components are taken of (include/dxv.h)
@@ -547,6 +548,24 @@ class Voxelizer:
         ms, rounds = C.c_float(), C.c_uint32()
         self._check(self._lib.dxv_fill_info(self._ctx, C.byref(ms), C.byref(rounds)))
         return ms.value, rounds.value
+
+    # ---- morphology of the frame's grid by the Euclidean ball ----------------------------------------
+    def Morph(self, op, radiusSq, sync=True, frameIndex=None):
+        """Grow or shrink the solid of the selected frame's whole grid by the ball { v : |v|^2 <= radiusSq } (1 .. 4096), in place, bytes 0 / 1
+        (dxv_morph / dxv_morph_async; include/dxv.h has the rule): MORPH_DILATE, MORPH_ERODE, MORPH_OPEN = dilate(erode), MORPH_CLOSE =
+        erode(dilate).  Voxels outside the grid do not exist.  Voxelize(N, MODE_SURFACE); Morph(MORPH_DILATE, r2); Fill(); Morph(MORPH_ERODE, r2)
+        seals holes narrower than the ball.  sync=False only enqueues it behind whatever the frame's stream holds."""
+        if frameIndex is not None:
+            self.SetFrame(frameIndex)
+        fn = self._lib.dxv_morph if sync else self._lib.dxv_morph_async
+        self._check(fn(self._ctx, int(op), int(radiusSq)))
+        return True
+
+    def morph_info(self):
+        """(ms, voxels_set, voxels_cleared) of the selected frame's last morph as of its last Sync (dxv_morph_info)."""
+        ms, was_set, cleared = C.c_float(), C.c_uint64(), C.c_uint64()
+        self._check(self._lib.dxv_morph_info(self._ctx, C.byref(ms), C.byref(was_set), C.byref(cleared)))
+        return ms.value, was_set.value, cleared.value
 
     def grid_bytes(self):
         return self._lib.dxv_grid_bytes(self._ctx)

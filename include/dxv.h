@@ -389,6 +389,45 @@ DXV_API int dxv_fill(dxv_ctx* ctx, int what);
  * (HIP events, option events = 1; else 0) and the rounds it took, the confirming one included.  Either pointer may be NULL. */
 DXV_API int dxv_fill_info(dxv_ctx* ctx, float* ms, uint32_t* rounds);
 
+/* Morphology: the solid of a grid grown or shrunk by the exact Euclidean ball (no reference counterpart).  Offsets and clearance, hollowing
+ * (S minus its erosion), opening (spikes thinner than the ball go), closing -- and the remedy where a hole in the mesh wider than a voxel
+ * defeats dxv_fill: dilate, fill, erode.  Input: the WHOLE grid of the selected frame's last launch, any mode (bytes a caller wrote through
+ * dxv_grid_device_ptr count too); solid(p) iff byte(p) != 0.  radius_sq is an integer r2 and the ball B = { v in Z^3 : vx^2 + vy^2 + vz^2 <= r2 }:
+ *     DXV_MORPH_DILATE  out(p) = 1 iff there is q in the grid with solid(q)  and |p - q|^2 <= r2
+ *     DXV_MORPH_ERODE   out(p) = 1 iff solid(p) and there is NO q in the grid with !solid(q) and |p - q|^2 <= r2
+ *     DXV_MORPH_OPEN    DILATE(ERODE(grid))
+ *     DXV_MORPH_CLOSE   ERODE(DILATE(grid))
+ * Voxels outside the grid do not exist (dxv_distance's "voxels q of the same grid"): they are not solid for DILATE and not empty for ERODE,
+ * so ERODE does not eat a solid where it touches the grid's border and an all-solid grid stays all solid.  With this convention CLOSE is
+ * extensive, OPEN anti-extensive and both are idempotent.  Integer geometry: the device's grid equals a restatement byte for byte.  A second,
+ * independent statement of the same rule, with d = DXV_DIST_SQ_I32 of the same grid:
+ *     DILATE(p) == solid(p) || d(p) <= r2          ERODE(p) == solid(p) && -d(p) > r2 */
+enum {
+    DXV_MORPH_DILATE = 0,
+    DXV_MORPH_ERODE = 1,
+    DXV_MORPH_OPEN = 2,
+    DXV_MORPH_CLOSE = 3
+};
+/* dxv_morph_async -- the result REPLACES the frame's grid in place, bytes exactly 0 or 1, like dxv_fill.  ENQUEUED on the frame's stream behind
+ * its launch (render, field, fill); returns without waiting.
+ *  - The host waits only under dxv_render_async's rule; a pending fill is settled first.
+ *  - Checked on the host before anything is enqueued, each an error with a message: op is one of the four; 1 <= radius_sq <= 4096 (the ball
+ *    reaches at most 64 voxels along an axis); the frame has been launched; its last launch was the whole grid.
+ *  - A fixed number of kernels: no rounds, nothing for a later dxv_sync to settle.  OPEN and CLOSE stay in bit masks between their halves.
+ *  - Everything a fill makes stale is stale after a morph: distance field, mesh-distance sign, isosurface, octree, components.  The texel
+ *    image is not touched.
+ *  - Two forms of the same bytes (option morphform): up to radius_sq 1024 word-parallel on bit masks, whose cost grows with radius_sq; above it
+ *    the distance field of the grid and its threshold per half, whose cost does not.
+ *  - The scratch (bit masks: 3 + floor(sqrt(radius_sq)) bits per voxel, one more for OPEN and CLOSE; above radius_sq 1024 a field and its
+ *    passes, 10 bytes per voxel) belongs to the frame: frames morph side by side.  dxv_trim gives it back.
+ * dxv_morph -- the same + dxv_sync. */
+DXV_API int dxv_morph_async(dxv_ctx* ctx, int op, uint32_t radius_sq);
+DXV_API int dxv_morph(dxv_ctx* ctx, int op, uint32_t radius_sq);
+/* The selected frame's last morph as of the frame's last dxv_sync: device time in milliseconds from its first kernel to its write-back (HIP
+ * events, option events = 1; else 0), the voxels that became solid and the voxels that became empty.  All 0 before the frame's first morph;
+ * any pointer may be NULL. */
+DXV_API int dxv_morph_info(dxv_ctx* ctx, float* ms, uint64_t* voxels_set, uint64_t* voxels_cleared);
+
 /* The exact signed distance from every voxel centre to the MESH, computed on the device by a nearest-triangle query over the scene's
  * hierarchy (no reference counterpart).  dxv_distance above is the field of the GRID -- integer geometry, no |d| below 1, its zero set the
  * staircase of the voxelization; this one is the Euclidean distance to the nearest triangle to sub-voxel accuracy, what collision and
@@ -723,6 +762,8 @@ DXV_API int dxv_get_stats(const dxv_ctx* ctx, dxv_stats* out);
  *                 holds); a triangle whose items do not all fit is walked whole as well.  Same grids.
  *   fillrounds 0..64  dxv_fill*: rounds of one batch (0, default: 4 -- the meshes measured take 2 or 3); a fill that needs more is continued
  *                 where its frame is next synchronised.  Same grids.
+ *   morphform 0..2  dxv_morph*: 0 (default) = by the radius: bit planes up to radius_sq 1024, above it the distance field of the grid and its
+ *                 threshold, per half; 1 / 2 = always the planes / always the field (measurement, cross-check).  Same grids.
  *   mdistwalk 0|1 dxv_mesh_distance*: 1 (default) = nearest-triangle query over the hierarchy; 0 = every triangle for every voxel, the
  *                 on-device cross-check (seconds on large scenes).  Same field.
  *   morton 0|1, region 0..24, subbox 0|1   brick order, bricks per XCD region (log2), partial launch */
@@ -772,7 +813,7 @@ DXV_API int dxv_debug_queue_order(dxv_ctx* ctx, uint64_t out[4]);
 
 /* Give back what the context keeps only to make the next build faster: the list build's scratch (up to 16 GiB per buffer
  * after a 10 M-triangle scene), the LBVH build's scratch when no refit can follow (imported scenes), the memory of prepared queues
- * whose lists are gone, the scratch of the frames' distance fields (the fields stay), of their flood fills, of their isosurfaces (the
+ * whose lists are gone, the scratch of the frames' distance fields (the fields stay), of their flood fills and morphs, of their isosurfaces (the
  * meshes stay), of their octrees (the nodes stay) and of their connected components (labels and table stay).  Nothing a launch reads. */
 DXV_API int dxv_trim(dxv_ctx* ctx);
 

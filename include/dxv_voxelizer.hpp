@@ -251,6 +251,11 @@ public:
 	// normals and watertightness cannot be trusted.  Refers to the frame last selected; sync = false only enqueues (WaitFrame reports).
 	bool Fill(int what = DXV_FILL_SOLID, bool sync = true) { return m_ctx && (sync ? dxv_fill(m_ctx, what) : dxv_fill_async(m_ctx, what)) == 0; }
 	bool FillInfo(float& ms, uint32_t& rounds) { return m_ctx && dxv_fill_info(m_ctx, &ms, &rounds) == 0; }
+	// That frame's solid grown or shrunk by the Euclidean ball of squared radius radiusSq (1 .. 4096), in place (dxv_morph / dxv_morph_async):
+	// DXV_MORPH_DILATE, _ERODE, _OPEN, _CLOSE.  Voxelize(gridDim, SURFACE) && Morph(DXV_MORPH_DILATE, r2) && Fill() && Morph(DXV_MORPH_ERODE, r2)
+	// is the solid of a mesh with holes narrower than the ball.
+	bool Morph(int op, uint32_t radiusSq, bool sync = true) { return m_ctx && (sync ? dxv_morph(m_ctx, op, radiusSq) : dxv_morph_async(m_ctx, op, radiusSq)) == 0; }
+	bool MorphInfo(float& ms, uint64_t& voxelsSet, uint64_t& voxelsCleared) { return m_ctx && dxv_morph_info(m_ctx, &ms, &voxelsSet, &voxelsCleared) == 0; }
 
 	// Result: uint8 occupancy, x fastest, then y (top to bottom), then z.
 	bool Download(std::vector<uint8_t>& grid)
