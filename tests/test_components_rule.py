@@ -12,6 +12,7 @@ import pytest
 import components_host as ch
 import components_restated as cr
 import fill_restated as fr
+import grid_sides as gs
 from conftest import ROOT
 
 KINDS = (cr.SOLID, cr.EMPTY)
@@ -84,6 +85,17 @@ def test_product_routines_equal_restatement_on_random_walls(density):
 def test_random_grid_has_the_component_counts_that_make_the_comparison_one():
     g = fr.random_walls(32, 0.3, 32)                                    # measured once: 2088 solid components under 6, 14 under 26
     assert len(cr.label(g, cr.SOLID, 6)[1]) > 1000 and 1 < len(cr.label(g, cr.SOLID, 26)[1]) < 100
+
+
+@pytest.mark.parametrize("N", gs.SWEEP)                                # every even side to 72 (tests/grid_sides.py): rows of less than a word, one word, one word and 2 to 8 bits
+def test_product_routines_on_the_sweep_grids(N):
+    for name, g in gs.grids(N):
+        kinds = KINDS
+        if N > 40 and name.startswith("random"):                        # (the restatement takes a second per labelling there: the kind with many components)
+            kinds = (cr.EMPTY,) if name == "random 0.6" else (cr.SOLID,)
+        counts = check_product(g, f"{N} {name}", kinds=kinds)
+        if N >= 8 and name == "random 0.3":
+            assert counts[cr.SOLID, 6] > 1
 
 
 @pytest.mark.parametrize("N", [2, 4, 30, 64, 66])                      # rows of less than a word, one word, one word and two bits

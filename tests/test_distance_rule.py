@@ -10,6 +10,7 @@ import pytest
 
 import distance_host
 import distance_restated as dr
+import grid_sides as gs
 from conftest import ROOT
 
 
@@ -75,6 +76,14 @@ def test_product_scans_equal_restatement_on_random_grids(N, density, seed):
     want = dr.distance_sq(g)
     assert np.array_equal(distance_host.distance(g, 0), want)
     assert np.array_equal(distance_host.distance(g, 1).view(np.uint32), dr.to_f32(want).view(np.uint32))
+
+
+@pytest.mark.parametrize("N", gs.SWEEP)                                # every even side to 72 (tests/grid_sides.py): every length of a row's last word
+def test_product_scans_equal_restatement_on_the_sweep_grids(N):
+    for name, g in gs.grids(N):
+        want = dr.distance_sq(g)
+        assert np.array_equal(distance_host.distance(g, 0), want), (N, name)
+        assert np.array_equal(distance_host.distance(g, 1).view(np.uint32), dr.to_f32(want).view(np.uint32)), (N, name)
 
 
 def test_product_scans_on_shapes_and_sentinels():

@@ -10,17 +10,11 @@ import pytest
 
 import fill_host
 import fill_restated as fr
+import grid_sides as gs
 from conftest import ROOT
+from grid_sides import hollow_box
 
 KINDS = (fr.SOLID, fr.INTERIOR)
-
-
-def hollow_box(N, lo, hi):
-    """a closed shell: the faces of the box [lo, hi]^3"""
-    g = np.zeros((N, N, N), np.uint8)
-    g[lo:hi + 1, lo:hi + 1, lo:hi + 1] = 1
-    g[lo + 1:hi, lo + 1:hi, lo + 1:hi] = 0
-    return g
 
 
 # ---- the restatement against grids whose answer can be written down --------------------------------------------------------------
@@ -101,8 +95,13 @@ def test_product_routines_equal_restatement_on_random_walls(density):
     check_product(fr.random_walls(30, density, 30, bytes_other_than_one=True), f"bytes, density {density}")
 
 
-@pytest.mark.parametrize("N", [2, 4, 30, 64, 66, 96, 130])              # rows of one, one and a half, two and three words
+@pytest.mark.parametrize("N", sorted(set(gs.SWEEP) | {2, 4, 30, 64, 66, 96, 130}))     # every even side to 72 (tests/grid_sides.py); rows of one and a half and of three words
 def test_product_routines_on_row_lengths(N):
+    if N in gs.SWEEP:
+        for name, g in gs.grids(N):
+            out, _ = check_product(g, f"{N} {name}")
+            if name == "hollow box":
+                assert int((~out & (g == 0)).sum()) == (N - 4) ** 3
     check_product(fr.random_walls(N, 0.6, N, bytes_other_than_one=True), N)
     g = np.zeros((N, N, N), np.uint8)
     check_product(g, f"{N} empty")

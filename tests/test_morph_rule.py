@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import fill_restated as fr
+import grid_sides as gs
 import morph_host
 import morph_restated as mr
 from conftest import ROOT
@@ -88,10 +89,14 @@ def check_product(g, r2, what_for, restate=mr.morph):
             assert (was_set, cleared) == mr.counts(g, want), (what_for, r2, op, eight)
 
 
-@pytest.mark.parametrize("N", [2, 6, 16, 24, 30, 64, 66])               # rows of one word, and of a word and two bits
+@pytest.mark.parametrize("N", gs.SWEEP)                                # every even side to 72 (tests/grid_sides.py): rows of one word, and of a word and 2 to 8 bits
 def test_product_routines_equal_restatement(N):
-    for what, g in grids(N):
-        for r2 in RADII if N <= 30 else (1, 4, 10):
+    if N in (2, 6, 16, 24, 30, 64, 66):
+        for what, g in grids(N):
+            for r2 in RADII if N <= 30 else (1, 4, 10):
+                check_product(g, r2, (N, what))
+    for what, g in gs.grids(N):
+        for r2 in (1, 10):
             check_product(g, r2, (N, what))
 
 

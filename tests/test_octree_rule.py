@@ -8,11 +8,12 @@ import subprocess
 import numpy as np
 import pytest
 
+import grid_sides as gs
 import octree_host as oh
 import octree_restated as orr
 from conftest import ROOT
 
-SIDES = [2, 4, 6, 8, 30, 66]
+SIDES = sorted(set(gs.SWEEP) | {2, 4, 6, 8, 30, 66})                   # every even side to 72 (tests/grid_sides.py): partial 8^3 bricks of every size
 
 
 def as_pairs(nodes):
@@ -39,7 +40,7 @@ def test_hand_cases_word_for_word(build):
 
 
 def grids(N):
-    return list(orr.rule_grids(N))
+    return list(orr.rule_grids(N)) + list(gs.grids(N))
 
 
 @pytest.mark.parametrize("N", SIDES)
