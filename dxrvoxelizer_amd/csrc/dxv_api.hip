@@ -1,6 +1,6 @@
 // dxv_api.hip -- the C-ABI of libdxv.so (include/dxv.h): context, device memory, mesh, build and refit, results,
-// options.  The other entry points: dxv_frames.hip (launches), dxv_lists.hip (candidate lists), dxv_blob.hip (scene blob),
-// dxv_debug.hip (test hooks).  There is no CPU fallback anywhere in this library: without a HIP device dxv_create fails.
+// options.  The other entry points: dxv_frames.hip (launches), dxv_products.hip (what is made of a frame's grid), dxv_lists.hip
+// (candidate lists), dxv_blob.hip (scene blob), dxv_debug.hip (test hooks).  There is no CPU fallback anywhere in this library: without a HIP device dxv_create fails.
 #include "dxv_ctx.h"
 #include <chrono>
 
@@ -249,8 +249,10 @@ void dxv_destroy(dxv_ctx* c)
     for (uint32_t i = 0; i < DXV_FRAME_COUNT; ++i) {
         Frame& f = c->frames[i];
         if (frame_stream(c, i)) (void)hipStreamSynchronize(frame_stream(c, i));
-        for (hipEvent_t ev : {f.ev0, f.ev1, f.evP0, f.evP1, f.evEnd, f.evR0, f.evR1, f.evD0, f.evD1, f.evF0, f.evF1, f.evM0, f.evM1, f.evI0, f.evI1, f.evO0, f.evO1, f.evC0, f.evC1, f.evX0, f.evX1})
-            if (ev) (void)hipEventDestroy(ev);
+        for (Timer& t : f.timers)
+            for (hipEvent_t ev : {t.e0, t.e1})
+                if (ev) (void)hipEventDestroy(ev);
+        if (f.evEnd) (void)hipEventDestroy(f.evEnd);
         if (f.ownStream) (void)hipStreamDestroy(f.ownStream);
     }
     for (auto& ev : c->ev) if (ev) (void)hipEventDestroy(ev);
@@ -571,8 +573,7 @@ int dxv_render(dxv_ctx* c, const float eye[3], const float viewProj[16], const f
     if (render_frame(c, cb, width, height, reinterpret_cast<uint8_t*>(c->image.p), (size_t)width * 4, true)) return 1;
     DXV_HIP(c, hipMemcpyAsync(rgbaHost, c->image.p, pixels * 4, hipMemcpyDeviceToHost, fs));
     DXV_HIP(c, hipStreamSynchronize(fs));
-    f.render_ms = elapsed(f.evR0, f.evR1);
-    f.renderTimed = false;
+    timer_read(f.timers[kTimerRender]);
     return 0;
 }
 
@@ -666,7 +667,7 @@ int dxv_get_stats(const dxv_ctx* c, dxv_stats* out)
     out->list_entries = f.list_entries; out->list_res = f.list_res; out->list_ms = f.lastMode == DXV_MODE_PARITY ? c->rowLists.ms : c->lists.ms;
     out->plan_bricks = f.plan_bricks; out->plan_waves = f.plan_waves; out->plan_ms = f.plan_ms;
     out->plan_prepared = f.lastPrepared >= 0 ? 1u : 0u;
-    out->render_ms = f.render_ms;
+    out->render_ms = f.timers[kTimerRender].ms;
     return 0;
 }
 

@@ -1,6 +1,7 @@
 // dxv_ctx.h -- the context of libdxv.so and what its translation units share: dxv_api.hip (context, mesh, build, options,
 // results), dxv_lists.hip (the candidate lists' policy and builds), dxv_frames.hip (frames, launches, work queues),
-// dxv_blob.hip (the scene blob that travels between GPUs), dxv_debug.hip (test hooks).  Nothing here is exported.
+// dxv_products.hip (what is made of a frame's grid: fields, mesh, tree, labels, and the edits in place), dxv_blob.hip (the
+// scene blob that travels between GPUs), dxv_debug.hip (test hooks).  Nothing here is exported.
 #pragma once
 #include "../../include/dxv.h"
 #include "dxv_device.h"
@@ -132,6 +133,15 @@ struct BuildScratch {
     uint32_t T = 0;                  // triangles the scratch is in use for (0: none)
 };
 
+// A pair of events around one piece of a frame's work and the time last read from it.  armed: both events are in the frame's stream and
+// nobody has read them yet -- the frame's next synchronisation does (timer_begin, timer_end, timer_read below).
+struct Timer { hipEvent_t e0 = nullptr, e1 = nullptr; bool armed = false; float ms = 0; };
+// ... and what a frame times.  The launch's pair and its queue build's are here for their events alone: when they are read is the launch's
+// business (Frame::timed, lastRebuilt -> voxelize_ms, plan_ms), so they stand in front of kTimerFirstOperator: a synchronisation of the frame
+// reads the armed pairs from there on (sync_launch), and a new operator's slot goes behind it.
+enum TimerUse { kTimerLaunch, kTimerQueue, kTimerRender, kTimerDistance, kTimerMeshDistance, kTimerFill, kTimerIso, kTimerOctree, kTimerComponents, kTimerMorph, kTimers,
+                kTimerFirstOperator = kTimerRender };
+
 struct dxv_ctx {
     int device = 0;
     hipStream_t ownStream = nullptr;
@@ -169,13 +179,16 @@ struct dxv_ctx {
         DevBuf<uint64_t> redo;           // voxels whose LDS column was too small, finished by the redo pass
         uint32_t redoParity = 0;
         int lastRedoParity = -1;         // counter of the last launch (-1: that launch has none)
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the frame's last launch
+        Timer timers[kTimers];           // the frame's event pairs and the times read from them (TimerUse)
         int lastMode = 0;
         uint32_t lastZBlock = 1, lastZPeriod = 1;
         bool pending = false;            // a voxelize launch has not been checked by dxv_sync yet
-        bool timed = true;               // ... and it was bracketed by the frame's two events (option events)
+        bool timed = true;               // ... and it was bracketed by the launch's two events (option events)
         bool lastCanFail = true;         // ... and it can report something (a walk's column can run out; the lists have no column)
         bool ready = false;              // status words, redo list, events and stream exist
+        uint64_t gridVersion = 1;        // counts what rewrote the grid: launches and the edits in place (grid_rewritten).  What is made of the grid
+                                         // remembers the version it was made of (distVersion ...; 0: none, or being rebuilt) and is current exactly
+                                         // while the two are equal
         uint64_t clearSig = 0;           // the partial launch whose memset this grid still carries (launch_shape, traverse.hip); 0 = none
         bool ptrExposed = false;         // dxv_grid_device_ptr handed this grid out for writing: the caller may write through the pointer at any
                                          // time, so no memset is ever kept for it again (until the grid is reallocated)
@@ -191,7 +204,6 @@ struct dxv_ctx {
         bool lastQueued = false;         // the frame's last launch went through the queue (dxv_sync reads its lengths for the stats)
         bool lastRebuilt = false;        // ... and built it (plan_ms is that build's)
         int lastPrepared = -1;           // the frame's last launch ran this PREPARED queue of the context (-1: none)
-        hipEvent_t evP0 = nullptr, evP1 = nullptr;   // around the queue build of the frame's last launch (option events)
         uint32_t queueLens[16] = {};     // the lengths of the frame's eight queues and how many of each are heavy, as last read by dxv_sync ...
         uint64_t queueLenSig = 0;        // ... for the queue of this signature (clearSig); 0: not known
         hipEvent_t evEnd = nullptr;      // behind the frame's last launch, always recorded: what a refit on another stream waits for on the device
@@ -202,9 +214,6 @@ struct dxv_ctx {
         uint32_t cbWidth = 0, cbHeight = 0;   // ... and the viewport they were made for (0: none yet)
         DevBuf<uint8_t> empty;           // empty-brick flags of the frame's grid (empty_brick_bytes)
         uint32_t emptyDim = 0;           // grid side of the frame's last render with flags (0: none yet; dxv_debug_download reads them)
-        hipEvent_t evR0 = nullptr, evR1 = nullptr;   // around the frame's last render
-        bool renderTimed = false;        // ... which was bracketed by them and not read yet (the frame's next dxv_sync reads it)
-        float render_ms = 0.0f;
         // surface modes (surface.hip): the large triangles' lists of the frame's surface pass, its own (never the work queue's
         // buffers: a kept queue of the reference rule is still needed by the frame's next mode-0 launch)
         DevBuf<uint8_t> surf;
@@ -213,11 +222,8 @@ struct dxv_ctx {
         DevBuf<int32_t> dist;            // (cap: voxels) 4 bytes per voxel, int32 or float32
         DevBuf<uint8_t> distScratch;     // (cap: bytes) distance_scratch_bytes: the x pass's 16-bit values, the y pass's squares
         uint32_t distDim = 0;            // grid side of the frame's last field (0: none yet)
-        bool distCurrent = false;        // ... which is the field of the frame's last launch (a new launch makes it stale)
+        uint64_t distVersion = 0;        // ... and the grid version it was made of
         int distFormat = 0;              // ... and its format (DXV_DIST_SQ_I32 / DXV_DIST_F32)
-        hipEvent_t evD0 = nullptr, evD1 = nullptr;   // around the frame's last field
-        bool distTimed = false;          // ... which was bracketed by them and not read yet (the frame's next dxv_sync reads it)
-        float dist_ms = 0.0f;
         // mesh distance field (mesh_distance.hip; dxv_mesh_distance_async): the field of the frame's last launch -- a slab's has nz slices --
         // and, when asked for, the nearest triangles; the frame's own, kept by dxv_trim
         DevBuf<float> mdist;             // (cap: voxels)
@@ -226,13 +232,10 @@ struct dxv_ctx {
         uint32_t mdistNz = 0;            // ... and its slices
         int mdistFormat = 0;             // ... its format
         bool mdistHasTri = false;        // ... and whether the nearest triangles were made with it
-        bool mdistCurrent = false;       // the field belongs to the frame's grid as it is (a new launch or a fill makes it stale)
+        uint64_t mdistVersion = 0;       // ... and the grid version it was made of
         bool sceneReadPending = false;   // a mesh distance kernel that reads nodes and triangle records may still be running on the frame's stream: whatever
                                          // rewrites them on another stream (dxv_refit, ensure_nodes) waits for the frame's end event first; any
                                          // synchronisation of the frame clears it (the passes over the grid alone -- render, field, fill -- never set it)
-        hipEvent_t evM0 = nullptr, evM1 = nullptr;   // around the frame's last mesh distance field
-        bool mdistTimed = false;         // ... which was bracketed by them and not read yet (the frame's next dxv_sync reads it)
-        float mdist_ms = 0.0f;
         // exterior flood fill (fill.hip; dxv_fill_async): the two bit masks and the control block of the frame's fill, its own so that
         // frames fill side by side; goes with dxv_trim
         DevBuf<uint8_t> fillScratch;     // (cap: bytes) fill_scratch_bytes
@@ -241,9 +244,7 @@ struct dxv_ctx {
         int fillWhat = 0;                // ... DXV_FILL_SOLID / DXV_FILL_INTERIOR, for the write-back of the batches that follow
         uint32_t fillBatch = 0;          // ... rounds per batch (option fillrounds as it stood at dxv_fill_async)
         uint32_t fillRounds = 0;         // rounds of the frame's last fill so far, the confirming one included
-        hipEvent_t evF0 = nullptr, evF1 = nullptr;   // around the frame's last fill (evF1: behind its last batch)
-        bool fillTimed = false;          // ... which was bracketed by them and not read yet
-        float fill_ms = 0.0f;
+                                         // (its timer's second event is recorded again behind every further batch, and settle_fill reads the pair)
         // isosurface (isosurface.hip; dxv_isosurface_async): the triangle mesh of one of the frame's fields and the scratch of its extraction
         // (a bit per lattice cell, two counts per 64 cells, the scan's sums), the frame's own; the scratch goes with dxv_trim, the mesh stays
         DevBuf<uint8_t> isoVb;           // (cap: vertices) 24 bytes each
@@ -251,10 +252,7 @@ struct dxv_ctx {
         DevBuf<uint8_t> isoScratch;      // (cap: bytes) iso_scratch_bytes
         uint32_t isoVertices = 0, isoTriangles = 0;   // of the frame's last mesh
         bool isoHave = false;            // the frame has had a mesh extracted (an empty one counts) ...
-        bool isoCurrent = false;         // ... and it belongs to the frame's grid as it is (a new launch or a fill makes it stale)
-        hipEvent_t evI0 = nullptr, evI1 = nullptr;   // around the frame's last extraction
-        bool isoTimed = false;           // ... which was bracketed by them and not read yet (the frame's next dxv_sync reads it)
-        float iso_ms = 0.0f;
+        uint64_t isoVersion = 0;         // ... of this grid version
         // sparse voxel octree (octree.hip; dxv_octree_async): the nodes of the frame's grid and the scratch of their build (two bytes per cell of
         // levels 0 .. L - 1, a bit per cell, a count per 64 cells, the scan's sums), the frame's own; the scratch goes with dxv_trim, the nodes stay
         DevBuf<uint32_t> octNodes;       // (cap: nodes) 8 bytes each
@@ -262,10 +260,7 @@ struct dxv_ctx {
         uint32_t octLevels = 0, octCount = 0;         // L and the nodes of the frame's last tree ...
         uint32_t octLevelFirst[12] = {}; // ... and the first node of every level, [L] the total
         bool octHave = false;            // the frame has had a tree built ...
-        bool octCurrent = false;         // ... and it belongs to the frame's grid as it is (a new launch, a fill or an expansion makes it stale)
-        hipEvent_t evO0 = nullptr, evO1 = nullptr;   // around the frame's last build
-        bool octTimed = false;           // ... which was bracketed by them and not read yet (the frame's next dxv_sync reads it)
-        float oct_ms = 0.0f;
+        uint64_t octVersion = 0;         // ... of this grid version
         bool octExpandPending = false;   // dxv_octree_expand_async read a CALLER's tree whose verdict (status word kOctStatusWord: an index that could not be
                                          // followed) nobody has read yet: the frame can still report something, and its next synchronisation reads it
         // connected components (components.hip; dxv_components_async): labels and table of the frame's grid and the scratch of their build
@@ -278,10 +273,7 @@ struct dxv_ctx {
         uint32_t compCount = 0, compDim = 0;          // K and the grid side of the frame's last labelling ...
         int compOf = 0, compConnectivity = 0;         // ... and what it was asked for
         bool compHave = false;           // the frame has had its grid labelled ...
-        bool compCurrent = false;        // ... and the labels belong to the frame's grid as it is (a new launch, a fill, an expansion or a select makes them stale)
-        hipEvent_t evC0 = nullptr, evC1 = nullptr;   // around the frame's last labelling
-        bool compTimed = false;          // ... which was bracketed by them and not read yet (the frame's next dxv_sync reads it)
-        float comp_ms = 0.0f;
+        uint64_t compVersion = 0;        // ... of this grid version
         bool selPending = false;         // a select's four counters are on their way into page-locked words: the frame's next synchronisation reads them
         int selRule = 0;
         uint32_t selComponents = 0;      // K of the labels that select edited from
@@ -290,9 +282,6 @@ struct dxv_ctx {
         // morphology (morph.hip; dxv_morph_async): the bit masks and planes of the frame's morph, its own so that frames morph side by side;
         // goes with dxv_trim
         DevBuf<uint8_t> morphScratch;    // (cap: bytes) morph_scratch_bytes
-        hipEvent_t evX0 = nullptr, evX1 = nullptr;   // around the frame's last morph
-        bool morphTimed = false;         // ... which was bracketed by them and not read yet (the frame's next dxv_sync reads it)
-        float morph_ms = 0.0f;
         bool morphPending = false;       // a morph's two counters are on their way into page-locked words: the frame's next synchronisation reads them
         uint64_t morphSet = 0, morphCleared = 0;      // of the frame's last morph, as of its last synchronisation
     };
@@ -420,6 +409,27 @@ inline float elapsed(hipEvent_t a, hipEvent_t b)
     return ms;
 }
 
+// The grid of a frame was rewritten, by a launch or in place: whatever was made of it before is stale from here on.  (An edit in place
+// also drops the kept memset, clearSig = 0, next to this call; a launch keeps its own account of that.)
+inline void grid_rewritten(Frame& f) { ++f.gridVersion; }
+// A frame's timers.  begin: the pair is disarmed before its first event is recorded again -- a first event recorded again and an old second
+// one are no pair; end: armed once the second event is in the stream (whatever the caller enqueues behind it: both events can be read); read: what a synchronisation of the frame does with an armed pair.
+inline hipError_t timer_begin(Timer& t, bool timed, hipStream_t s)
+{
+    t.armed = false;
+    return timed ? hipEventRecord(t.e0, s) : hipSuccess;
+}
+inline hipError_t timer_end(Timer& t, bool timed, hipStream_t s)
+{
+    const hipError_t e = timed ? hipEventRecord(t.e1, s) : hipSuccess;
+    t.armed = timed && e == hipSuccess;
+    return e;
+}
+inline void timer_read(Timer& t)
+{
+    if (t.armed) { t.ms = elapsed(t.e0, t.e1); t.armed = false; }
+}
+
 // dxv_api.hip
 void layout_scene(SceneHeader& h, uint32_t T, uint32_t V, bool wide);
 int alloc_scene(dxv_ctx* c, uint32_t T, uint32_t V, bool wide);
@@ -441,10 +451,18 @@ int safe_stack(const dxv_ctx* c, int mode);
 int launch_now(dxv_ctx* c, uint32_t frame, bool relaunch = false);
 int render_frame(dxv_ctx* c, const RayCastCB& cb, uint32_t width, uint32_t height, uint8_t* dst, size_t pitch, bool timed);
 bool frame_renderable(const Frame& f);
+int settle_frame_launch(dxv_ctx* c);                       // the host waits for the selected frame only when it can still report something
+// `ptr` is device memory of this context's device and `need` bytes from it lie inside its allocation: 0; 1 with the message set; or, where
+// the range does not fit, 2 with the bytes the allocation has from `ptr` on in *room -- the sentence about that is the caller's own
+int check_device_range(dxv_ctx* c, const char* who, const void* ptr, size_t need, size_t* room);
 // argument checks of the entries that take a grid, a slab of it or a rank's interleaved share: 0, or 1 with the message set
 int check_grid(dxv_ctx* c, const char* who, uint32_t N, bool orZero = false);
 int check_slab(dxv_ctx* c, const char* who, uint32_t N, uint32_t z0, uint32_t nz);
 int check_interleave(dxv_ctx* c, const char* who, uint32_t N, uint32_t rank, uint32_t world, uint32_t zblock);
+// dxv_products.hip
+void read_products(dxv_ctx* c, uint32_t i);                // the counters of the frame's last select and morph, once its stream has been waited for
+int settle_fill(dxv_ctx* c, uint32_t i);                   // the verdict of the frame's last fill batch; further batches until one has converged
+int settle_expand(dxv_ctx* c, uint32_t i);                 // the verdict of an expansion from a caller's tree
 // dxv_lists.hip
 struct ListScratchA { DirRecord* rec; uint32_t *counts, *offsets, *pairs, *sums; unsigned long long* total; size_t bytes; };
 ListScratchA list_scratch_a(uint8_t* base, uint32_t T);

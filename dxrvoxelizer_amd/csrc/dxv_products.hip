@@ -1,0 +1,754 @@
+// dxv_products.hip -- what is made of a frame's grid, and what edits it in place: distance field, mesh distance field, isosurface, octree and
+// its expansion, components and select, fill, morph -- the host side of each (the kernels: distance.hip, mesh_distance.hip, isosurface.hip,
+// octree.hip, components.hip, fill.hip, morph.hip), the accessors of what they made, and their halves of a frame's synchronisation.
+#include "dxv_ctx.h"
+#include "dxv_mesh_distance.h"
+#include "dxv_fill.h"
+#include "dxv_isosurface.h"
+#include "dxv_octree.h"
+#include "dxv_components.h"
+#include "dxv_morph.h"
+
+using namespace dxv;
+using namespace dxvhost;
+
+namespace dxvhost {
+
+// the refusals of whatever works on the whole grid of the selected frame
+static int check_whole_grid(dxv_ctx* c, const char* who)
+{
+    const Frame& f = cur_frame(c);
+    if (!f.grid.p || !f.grid_dim) return fail(c, "%s: frame %u has no grid yet (call dxv_voxelize first)", who, c->cur);
+    if (!frame_renderable(f)) return fail(c, "%s: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share", who);
+    return 0;
+}
+
+// `want` bytes of something the selected frame holds and the caller has found current, into `host`, behind a synchronisation of the frame.
+// (A NULL host is refused where there is something to copy: a current field has a side of at least 2 and a tree has its root, so only a mesh
+// without vertices or a labelling without components gets as far as want == 0.)
+static int download_current(dxv_ctx* c, const char* who, const void* src, size_t want, void* host, size_t bytes)
+{
+    if ((!host && want) || bytes != want) return fail(c, "%s: expected %zu bytes, got %zu", who, want, bytes);
+    if (dxv_sync(c)) return 1;
+    if (!want) return 0;
+    DXV_HIP(c, hipMemcpyAsync(host, src, bytes, hipMemcpyDeviceToHost, cur_stream(c)));
+    DXV_HIP(c, hipStreamSynchronize(cur_stream(c)));
+    return 0;
+}
+
+// dxv_*_ms: the time the selected frame's last synchronisation read from one of its timers
+static int timer_ms(dxv_ctx* c, const char* who, TimerUse use, float* ms)
+{
+    if (!c) return 1;
+    if (!ms) return fail(c, "%s: ms is NULL", who);
+    *ms = cur_frame(c).timers[use].ms;
+    return 0;
+}
+
+// dxv_sync of one frame (sync_launch, once the stream has been waited for): the counters a select and a morph left in page-locked words
+void read_products(dxv_ctx* c, uint32_t i)
+{
+    Frame& f = c->frames[i];
+    if (f.selPending) {                                                 // the counters of the frame's last select (k_comp_keep has the LARGEST case)
+        const unsigned long long* sel = c->pin->compSel[i];
+        const bool largest = f.selRule == DXV_SELECT_LARGEST && f.selComponents;
+        f.selKept = largest ? 1u : (uint32_t)sel[0];
+        f.selDropped = largest ? f.selComponents - 1u : (uint32_t)sel[1];
+        f.selChanged = largest ? sel[2] - (sel[3] >> 32) : sel[2];
+        f.selPending = false;
+    }
+    if (f.morphPending) {                                               // the counters of the frame's last morph
+        f.morphSet = c->pin->morphCount[i][0];
+        f.morphCleared = c->pin->morphCount[i][1];
+        f.morphPending = false;
+    }
+}
+
+// ... and the fill's half, behind it (the stream has been waited for): the verdict of the frame's last fill batch.  A batch whose last
+// round still changed a word has not converged: further batches -- rounds and write-back, from the masks the frame's scratch still
+// holds -- are enqueued and waited for until one has (the pattern of settle_lists: what only the host can decide is decided where the
+// frame is synchronised anyway).  A flood over V voxels reaches at least one new voxel per live round: fewer than V rounds.
+int settle_fill(dxv_ctx* c, uint32_t i)
+{
+    Frame& f = c->frames[i];
+    const hipStream_t fs = frame_stream(c, i);
+    const uint32_t* ctl = c->pin->fillCtl[i];
+    Timer& t = f.timers[kTimerFill];
+    const uint32_t N = f.grid_dim;
+    const uint64_t most = f.fillBatch ? (uint64_t)N * N * N / f.fillBatch + 2u : 0u;
+    for (uint64_t batch = 0; f.fillPending; ++batch) {
+        uint32_t live = 0;
+        while (live < f.fillBatch && ctl[live]) ++live;
+        if (live < f.fillBatch) {                                       // round `live` changed nothing: the confirming round
+            f.fillRounds += live + 1u;
+            f.fillPending = false;
+            break;
+        }
+        f.fillRounds += f.fillBatch;
+        if (batch >= most) return fail(c, "dxv_fill: no fixed point after %u rounds on a grid of %u^3 voxels", f.fillRounds, N);
+        DXV_HIP(c, launch_fill(f.grid.p, N, f.fillWhat, f.fillScratch.p, f.fillBatch, false, fs));
+        if (t.armed) DXV_HIP(c, hipEventRecord(t.e1, fs));
+        DXV_HIP(c, hipMemcpyAsync(c->pin->fillCtl[i], fill_control(f.fillScratch.p, N), sizeof(c->pin->fillCtl[i]), hipMemcpyDeviceToHost, fs));
+        DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+        DXV_HIP(c, hipStreamSynchronize(fs));
+    }
+    timer_read(t);
+    return 0;
+}
+
+// ... and the verdict of an expansion from a caller's tree (sync_launch has read the word): an index that could not be followed left empty
+// voxels behind and is reported here, once
+int settle_expand(dxv_ctx* c, uint32_t i)
+{
+    Frame& f = c->frames[i];
+    if (!f.octExpandPending) return 0;
+    f.octExpandPending = false;
+    if (!c->pin->status[i][kOctStatusWord]) return 0;
+    DXV_HIP(c, hipMemsetAsync(f.status.p + kOctStatusWord, 0, sizeof(uint32_t), frame_stream(c, i)));
+    return fail(c, "dxv_octree_expand: the tree given for frame %u cannot be followed (a child index at or beyond its node count, or cells still mixed "
+                   "after all its levels); the voxels behind such an index were left empty", i);
+}
+
+} // namespace dxvhost
+
+extern "C" {
+
+// The distance field of the selected frame's grid (distance.hip), enqueued on the frame's stream behind whatever it holds -- under
+// dxv_render_async's host-wait rule, then the frame's end event behind it.  Field and scratch are the frame's own; growing them waits
+// for that frame's stream only.
+int dxv_distance_async(dxv_ctx* c, int format)
+{
+    if (!c) return 1;
+    if (format != DXV_DIST_SQ_I32 && format != DXV_DIST_F32)
+        return fail(c, "dxv_distance: unknown format %d (DXV_DIST_SQ_I32 = 0, DXV_DIST_F32 = 1)", format);
+    if (check_whole_grid(c, "dxv_distance")) return 1;
+    Frame& f = cur_frame(c);
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (settle_frame_launch(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    const uint32_t N = f.grid_dim;
+    const size_t voxels = (size_t)N * N * N, scratch = distance_scratch_bytes(N);
+    f.distVersion = 0; f.distDim = 0;
+    DXV_HIP(c, f.dist.reserve(voxels, align256(voxels * sizeof(int32_t)), fs));
+    DXV_HIP(c, f.distScratch.reserve(scratch, scratch, fs));
+    const bool timed = c->opt.events != 0;
+    DXV_HIP(c, timer_begin(f.timers[kTimerDistance], timed, fs));
+    DXV_HIP(c, launch_distance(f.grid.p, N, format, f.dist.p, f.distScratch.p, fs));
+    DXV_HIP(c, timer_end(f.timers[kTimerDistance], timed, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    f.distDim = N; f.distFormat = format; f.distVersion = f.gridVersion;
+    return 0;
+}
+
+int dxv_distance(dxv_ctx* c, int format)
+{
+    if (dxv_distance_async(c, format)) return 1;
+    return dxv_sync(c);
+}
+
+// the frame's field, or the reason there is none to hand out: NULL + message
+static const int32_t* current_field(const dxv_ctx* c, const char* who)
+{
+    const Frame& f = c->frames[c->cur];
+    dxv_ctx* w = const_cast<dxv_ctx*>(c);                               // (the message is the one thing an accessor writes)
+    if (!f.distDim || !f.dist.p) { (void)fail(w, "%s: frame %u has no distance field yet (call dxv_distance first)", who, c->cur); return nullptr; }
+    if (f.distVersion != f.gridVersion) { (void)fail(w, "%s: frame %u was launched again since its distance field was made: the field is stale", who, c->cur); return nullptr; }
+    return f.dist.p;
+}
+
+const void* dxv_distance_device_ptr(const dxv_ctx* c) { return c ? current_field(c, "dxv_distance_device_ptr") : nullptr; }
+
+size_t dxv_distance_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame& f = c->frames[c->cur];
+    return f.distVersion == f.gridVersion ? (size_t)f.distDim * f.distDim * f.distDim * sizeof(int32_t) : 0;
+}
+
+int dxv_distance_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c) return 1;
+    const int32_t* field = current_field(c, "dxv_distance_download");
+    if (!field) return 1;
+    return download_current(c, "dxv_distance_download", field, dxv_distance_bytes(c), host, bytes);
+}
+
+int dxv_distance_ms(dxv_ctx* c, float* ms) { return timer_ms(c, "dxv_distance_ms", kTimerDistance, ms); }
+
+// The distance from the voxel centres of the selected frame's last launch to the MESH (mesh_distance.hip), signed by the frame's grid:
+// enqueued on the frame's stream behind whatever it holds, under dxv_render_async's host-wait rule (a pending fill is settled by it),
+// then the frame's end event; the frame is marked as reading the scene (sceneReadPending) until it is next synchronised, and dxv_refit and
+// ensure_nodes make their stream wait for that event before they rewrite triangle records or node boxes.  Unlike the
+// grid's own field a contiguous slab needs nothing from its neighbours; a share's slices are not one block of the field and are refused.
+int dxv_mesh_distance_async(dxv_ctx* c, int format, uint32_t bandVoxels, int wantTriangles)
+{
+    if (!c) return 1;
+    if (format != DXV_MDIST_VOXELS_F32 && format != DXV_MDIST_UNITS_F32)
+        return fail(c, "dxv_mesh_distance: unknown format %d (DXV_MDIST_VOXELS_F32 = 0, DXV_MDIST_UNITS_F32 = 1)", format);
+    if (bandVoxels > kMdMaxBand) return fail(c, "dxv_mesh_distance: a band of %u voxels (0 = none, at most %u)", bandVoxels, kMdMaxBand);
+    Frame& f = cur_frame(c);
+    if (!f.grid.p || !f.grid_dim || !f.nz) return fail(c, "dxv_mesh_distance: frame %u has no grid yet (call dxv_voxelize first)", c->cur);
+    if (f.lastZBlock != f.nz)
+        return fail(c, "dxv_mesh_distance: the frame's last launch was an interleaved share; needs the whole grid or a contiguous slab");
+    if (!c->haveScene) return fail(c, "dxv_mesh_distance: no scene with a built hierarchy (call dxv_build or dxv_scene_import first)");
+    if (c->hdr.treeHeight > (uint32_t)kMdStack)
+        return fail(c, "dxv_mesh_distance: tree height %u exceeds the walk's column of %d entries", c->hdr.treeHeight, kMdStack);
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (settle_frame_launch(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    const bool walk = c->opt.mdistwalk != 0;
+    if (walk && ensure_nodes(c, fs)) return 1;                          // after a refit that deferred the node boxes, as before a tree walk
+    const uint32_t N = f.grid_dim;
+    const size_t voxels = (size_t)N * N * f.nz;
+    f.mdistVersion = 0; f.mdistDim = 0;
+    DXV_HIP(c, f.mdist.reserve(voxels, align256(voxels * sizeof(float)), fs));
+    if (wantTriangles) DXV_HIP(c, f.mdistTri.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
+    MeshDistanceParams p{};
+    p.grid = f.grid.p; p.field = f.mdist.p; p.tris = wantTriangles ? f.mdistTri.p : nullptr;
+    p.N = N; p.z0 = f.z0; p.nz = f.nz;
+    p.format = format;
+    p.cap = md_cap(N, bandVoxels);
+    p.cullAbs = md_cull_abs(c->hdr.rootLo, c->hdr.rootHi);
+    const bool timed = c->opt.events != 0;
+    DXV_HIP(c, timer_begin(f.timers[kTimerMeshDistance], timed, fs));
+    DXV_HIP(c, launch_mesh_distance(scene_nodes(c), scene_tripos(c), c->hdr.numTris, p, walk, fs));
+    DXV_HIP(c, timer_end(f.timers[kTimerMeshDistance], timed, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    f.sceneReadPending = true;
+    f.mdistDim = N; f.mdistNz = f.nz; f.mdistFormat = format; f.mdistHasTri = wantTriangles != 0; f.mdistVersion = f.gridVersion;
+    return 0;
+}
+
+int dxv_mesh_distance(dxv_ctx* c, int format, uint32_t bandVoxels, int wantTriangles)
+{
+    if (dxv_mesh_distance_async(c, format, bandVoxels, wantTriangles)) return 1;
+    return dxv_sync(c);
+}
+
+// the frame's mesh distance field (triangles: its nearest triangles), or the reason there is none to hand out: NULL + message
+static const void* current_mesh_field(const dxv_ctx* c, const char* who, bool triangles)
+{
+    const Frame& f = c->frames[c->cur];
+    dxv_ctx* w = const_cast<dxv_ctx*>(c);                               // (the message is the one thing an accessor writes)
+    if (!f.mdistDim || !f.mdist.p) { (void)fail(w, "%s: frame %u has no mesh distance field yet (call dxv_mesh_distance first)", who, c->cur); return nullptr; }
+    if (f.mdistVersion != f.gridVersion) { (void)fail(w, "%s: frame %u was launched or filled again since its mesh distance field was made: the field is stale", who, c->cur); return nullptr; }
+    if (triangles && !f.mdistHasTri) { (void)fail(w, "%s: frame %u's mesh distance field was made without triangles (want_triangles = 0)", who, c->cur); return nullptr; }
+    return triangles ? static_cast<const void*>(f.mdistTri.p) : static_cast<const void*>(f.mdist.p);
+}
+
+const void* dxv_mesh_distance_device_ptr(const dxv_ctx* c) { return c ? current_mesh_field(c, "dxv_mesh_distance_device_ptr", false) : nullptr; }
+const void* dxv_mesh_distance_triangles_device_ptr(const dxv_ctx* c) { return c ? current_mesh_field(c, "dxv_mesh_distance_triangles_device_ptr", true) : nullptr; }
+
+size_t dxv_mesh_distance_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame& f = c->frames[c->cur];
+    return f.mdistVersion == f.gridVersion ? (size_t)f.mdistDim * f.mdistDim * f.mdistNz * sizeof(float) : 0;
+}
+
+static int mesh_field_download(dxv_ctx* c, const char* who, bool triangles, void* host, size_t bytes)
+{
+    if (!c) return 1;
+    const void* field = current_mesh_field(c, who, triangles);
+    if (!field) return 1;
+    return download_current(c, who, field, dxv_mesh_distance_bytes(c), host, bytes);
+}
+int dxv_mesh_distance_download(dxv_ctx* c, void* host, size_t bytes) { return mesh_field_download(c, "dxv_mesh_distance_download", false, host, bytes); }
+int dxv_mesh_distance_triangles_download(dxv_ctx* c, void* host, size_t bytes) { return mesh_field_download(c, "dxv_mesh_distance_triangles_download", true, host, bytes); }
+
+int dxv_mesh_distance_ms(dxv_ctx* c, float* ms) { return timer_ms(c, "dxv_mesh_distance_ms", kTimerMeshDistance, ms); }
+
+// The isosurface of one of the selected frame's fields (isosurface.hip; dxv_isosurface.h has the rule), enqueued on the frame's stream behind
+// whatever it holds, under dxv_render_async's host-wait rule: the count and scan kernels, the two totals into page-locked words and the
+// one wait for them -- the pattern of dxv_prepare_launch's sixteen counts: the mesh's buffers cannot be sized without them --, then the emit
+// kernel and the frame's end event, which nobody waits for here.
+int dxv_isosurface_async(dxv_ctx* c, int source, float iso, int space)
+{
+    if (!c) return 1;
+    if (source != DXV_ISO_MESH_DISTANCE && source != DXV_ISO_GRID_DISTANCE)
+        return fail(c, "dxv_isosurface: unknown source %d (DXV_ISO_MESH_DISTANCE = 0, DXV_ISO_GRID_DISTANCE = 1)", source);
+    if (space != DXV_ISO_SPACE_VOXELS && space != DXV_ISO_SPACE_OBJECT)
+        return fail(c, "dxv_isosurface: unknown space %d (DXV_ISO_SPACE_VOXELS = 0, DXV_ISO_SPACE_OBJECT = 1)", space);
+    if (!std::isfinite(iso)) return fail(c, "dxv_isosurface: iso must be finite, got %g", (double)iso);
+    Frame& f = cur_frame(c);
+    const float* field = nullptr;
+    uint32_t N = 0;
+    float P = 1.0f;
+    if (source == DXV_ISO_MESH_DISTANCE) {
+        if (!f.mdistDim || !f.mdist.p) return fail(c, "dxv_isosurface: frame %u has no mesh distance field yet (call dxv_mesh_distance first)", c->cur);
+        if (f.mdistVersion != f.gridVersion) return fail(c, "dxv_isosurface: frame %u was launched or filled again since its mesh distance field was made: the field is stale", c->cur);
+        if (f.mdistNz != f.mdistDim)
+            return fail(c, "dxv_isosurface: the frame's mesh distance field is a slab's (%u of %u slices); needs the field of the whole grid", f.mdistNz, f.mdistDim);
+        field = f.mdist.p; N = f.mdistDim;
+        if (f.mdistFormat == DXV_MDIST_UNITS_F32) P = 2.0f / (float)N;
+    } else {
+        if (!f.distDim || !f.dist.p) return fail(c, "dxv_isosurface: frame %u has no distance field yet (call dxv_distance first)", c->cur);
+        if (f.distVersion != f.gridVersion) return fail(c, "dxv_isosurface: frame %u was launched or filled again since its distance field was made: the field is stale", c->cur);
+        if (f.distFormat != DXV_DIST_F32) return fail(c, "dxv_isosurface: the frame's distance field is in the int32 format; needs DXV_DIST_F32");
+        field = reinterpret_cast<const float*>(f.dist.p); N = f.distDim;
+    }
+    if (space == DXV_ISO_SPACE_OBJECT && !c->haveScene)
+        return fail(c, "dxv_isosurface: DXV_ISO_SPACE_OBJECT needs the scene's bound and the context has no scene (call dxv_build or dxv_scene_import, or ask for DXV_ISO_SPACE_VOXELS)");
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (settle_frame_launch(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    const size_t scratch = iso_scratch_bytes(N);
+    DXV_HIP(c, f.isoScratch.reserve(scratch, scratch, fs));
+    IsoParams p{};
+    p.field = field; p.N = N; p.iso = iso; p.P = P; p.object = space == DXV_ISO_SPACE_OBJECT;
+    memcpy(p.bound, c->bound, sizeof(p.bound));
+    iso_scratch_layout(f.isoScratch.p, N, p);
+    const bool timed = c->opt.events != 0;
+    unsigned long long* totals = c->pin->isoTotals[c->cur];
+    DXV_HIP(c, timer_begin(f.timers[kTimerIso], timed, fs));
+    DXV_HIP(c, launch_iso_count(p, fs));
+    DXV_HIP(c, hipMemcpyAsync(totals, p.totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipStreamSynchronize(fs));
+    const unsigned long long vertices = totals[0], quads = totals[1];
+    if (vertices > kIsoMaxCount || quads > kIsoMaxCount / 6u)
+        return fail(c, "dxv_isosurface: a mesh of %llu vertices and %llu index words; at most %llu of each (the frame's earlier mesh is kept)", vertices,
+                    6u * quads, (unsigned long long)kIsoMaxCount);
+    f.isoVersion = 0;
+    if (vertices) {
+        DXV_HIP(c, f.isoVb.reserve((size_t)vertices, align256((size_t)vertices * sizeof(IsoVertex)), fs));
+        if (quads) DXV_HIP(c, f.isoIb.reserve(6 * (size_t)quads, align256(6 * (size_t)quads * sizeof(uint32_t)), fs));
+        p.vb = reinterpret_cast<IsoVertex*>(f.isoVb.p); p.ib = f.isoIb.p;
+        DXV_HIP(c, launch_iso_emit(p, fs));
+    }
+    DXV_HIP(c, timer_end(f.timers[kTimerIso], timed, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    f.isoVertices = (uint32_t)vertices; f.isoTriangles = (uint32_t)(2u * quads);
+    f.isoHave = true; f.isoVersion = f.gridVersion;
+    return 0;
+}
+
+int dxv_isosurface(dxv_ctx* c, int source, float iso, int space)
+{
+    if (dxv_isosurface_async(c, source, iso, space)) return 1;
+    return dxv_sync(c);
+}
+
+// whether the frame has a mesh to hand out: 0, or 1 with the reason as the message
+static int current_mesh(const dxv_ctx* c, const char* who)
+{
+    const Frame& f = c->frames[c->cur];
+    dxv_ctx* w = const_cast<dxv_ctx*>(c);                               // (the message is the one thing an accessor writes)
+    if (!f.isoHave) return fail(w, "%s: frame %u has no isosurface yet (call dxv_isosurface first)", who, c->cur);
+    if (f.isoVersion != f.gridVersion) return fail(w, "%s: frame %u was launched or filled again since its isosurface was made: the mesh is stale", who, c->cur);
+    return 0;
+}
+
+int dxv_isosurface_counts(dxv_ctx* c, uint32_t* vertices, uint32_t* triangles)
+{
+    if (!c) return 1;
+    if (current_mesh(c, "dxv_isosurface_counts")) return 1;
+    if (vertices) *vertices = cur_frame(c).isoVertices;
+    if (triangles) *triangles = cur_frame(c).isoTriangles;
+    return 0;
+}
+
+const void* dxv_isosurface_vertices_device_ptr(const dxv_ctx* c)
+{
+    if (!c || current_mesh(c, "dxv_isosurface_vertices_device_ptr")) return nullptr;
+    return c->frames[c->cur].isoVertices ? c->frames[c->cur].isoVb.p : nullptr;
+}
+const void* dxv_isosurface_indices_device_ptr(const dxv_ctx* c)
+{
+    if (!c || current_mesh(c, "dxv_isosurface_indices_device_ptr")) return nullptr;
+    return c->frames[c->cur].isoTriangles ? c->frames[c->cur].isoIb.p : nullptr;
+}
+
+int dxv_isosurface_vertices_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || current_mesh(c, "dxv_isosurface_vertices_download")) return 1;
+    return download_current(c, "dxv_isosurface_vertices_download", cur_frame(c).isoVb.p, (size_t)cur_frame(c).isoVertices * sizeof(IsoVertex), host, bytes);
+}
+int dxv_isosurface_indices_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || current_mesh(c, "dxv_isosurface_indices_download")) return 1;
+    return download_current(c, "dxv_isosurface_indices_download", cur_frame(c).isoIb.p, (size_t)cur_frame(c).isoTriangles * 3u * sizeof(uint32_t), host, bytes);
+}
+
+int dxv_isosurface_ms(dxv_ctx* c, float* ms) { return timer_ms(c, "dxv_isosurface_ms", kTimerIso, ms); }
+
+// The sparse voxel octree of the selected frame's grid (octree.hip; dxv_octree.h has the rule), enqueued on the frame's stream behind whatever
+// it holds, under dxv_render_async's host-wait rule: the reduce and scan kernels, the L + 1 level totals into page-locked words and the one
+// wait for them -- the pattern of dxv_isosurface_async: the node buffer cannot be sized without the last of them --, then the emit kernel and
+// the frame's end event, which nobody waits for here.
+int dxv_octree_async(dxv_ctx* c)
+{
+    if (!c) return 1;
+    if (check_whole_grid(c, "dxv_octree")) return 1;
+    Frame& f = cur_frame(c);
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (settle_frame_launch(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    const uint32_t N = f.grid_dim;
+    const size_t scratch = oct_scratch_bytes(N);
+    DXV_HIP(c, f.octScratch.reserve(scratch, scratch, fs));
+    OctParams p{};
+    p.grid = f.grid.p;
+    oct_scratch_layout(f.octScratch.p, N, p);
+    const uint32_t L = p.L;
+    const bool timed = c->opt.events != 0;
+    unsigned long long* totals = c->pin->octTotals[c->cur];
+    DXV_HIP(c, timer_begin(f.timers[kTimerOctree], timed, fs));
+    DXV_HIP(c, launch_oct_count(p, fs));
+    DXV_HIP(c, hipMemcpyAsync(totals, p.levelFirst, (L + 1u) * sizeof(unsigned long long), hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipStreamSynchronize(fs));
+    const unsigned long long nodes = totals[L];
+    if (!nodes || nodes > kOctMaxNodes)
+        return fail(c, "dxv_octree: a tree of %llu nodes; at least the root and at most %llu (the frame's earlier tree is kept)", nodes,
+                    (unsigned long long)kOctMaxNodes);
+    f.octVersion = 0;
+    DXV_HIP(c, f.octNodes.reserve((size_t)nodes, align256((size_t)nodes * 2u * sizeof(uint32_t)), fs));
+    p.nodes = f.octNodes.p;
+    DXV_HIP(c, launch_oct_emit(p, fs));
+    DXV_HIP(c, timer_end(f.timers[kTimerOctree], timed, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    f.octLevels = L; f.octCount = (uint32_t)nodes;
+    for (uint32_t l = 0; l < 12u; ++l) f.octLevelFirst[l] = l <= L ? (uint32_t)totals[l] : 0u;
+    f.octHave = true; f.octVersion = f.gridVersion;
+    return 0;
+}
+
+int dxv_octree(dxv_ctx* c)
+{
+    if (dxv_octree_async(c)) return 1;
+    return dxv_sync(c);
+}
+
+// whether the frame has a tree to hand out: 0, or 1 with the reason as the message
+static int current_tree(const dxv_ctx* c, const char* who)
+{
+    const Frame& f = c->frames[c->cur];
+    dxv_ctx* w = const_cast<dxv_ctx*>(c);                               // (the message is the one thing an accessor writes)
+    if (!f.octHave) return fail(w, "%s: frame %u has no octree yet (call dxv_octree first)", who, c->cur);
+    if (f.octVersion != f.gridVersion) return fail(w, "%s: frame %u was launched, filled or expanded again since its octree was made: the tree is stale", who, c->cur);
+    return 0;
+}
+
+int dxv_octree_info(dxv_ctx* c, uint32_t* levels, uint32_t* nodes, uint32_t level_first[12])
+{
+    if (!c) return 1;
+    if (current_tree(c, "dxv_octree_info")) return 1;
+    const Frame& f = cur_frame(c);
+    if (levels) *levels = f.octLevels;
+    if (nodes) *nodes = f.octCount;
+    if (level_first) memcpy(level_first, f.octLevelFirst, sizeof(f.octLevelFirst));
+    return 0;
+}
+
+const void* dxv_octree_device_ptr(const dxv_ctx* c)
+{
+    if (!c || current_tree(c, "dxv_octree_device_ptr")) return nullptr;
+    return c->frames[c->cur].octNodes.p;
+}
+
+size_t dxv_octree_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame& f = c->frames[c->cur];
+    return f.octHave && f.octVersion == f.gridVersion ? (size_t)f.octCount * 2u * sizeof(uint32_t) : 0;
+}
+
+int dxv_octree_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || current_tree(c, "dxv_octree_download")) return 1;
+    return download_current(c, "dxv_octree_download", cur_frame(c).octNodes.p, dxv_octree_bytes(c), host, bytes);
+}
+
+int dxv_octree_ms(dxv_ctx* c, float* ms) { return timer_ms(c, "dxv_octree_ms", kTimerOctree, ms); }
+
+// The selected frame's grid from an octree (octree.hip: k_oct_expand), in place, enqueued on the frame's stream behind whatever it holds --
+// under dxv_render_async's host-wait rule and dxv_fill_async's rules for the grid.  A caller's tree is not trusted: the kernel compares every
+// index with `nodes` before it follows it, and what it had to refuse is read where the frame is next synchronised (settle_expand).
+int dxv_octree_expand_async(dxv_ctx* c, const void* deviceNodes, uint32_t nodes, uint32_t levels)
+{
+    if (!c) return 1;
+    if (check_whole_grid(c, "dxv_octree_expand")) return 1;
+    Frame& f = cur_frame(c);
+    const uint32_t N = f.grid_dim, L = oct_levels(N);
+    DXV_HIP(c, hipSetDevice(c->device));
+    const bool own = deviceNodes == nullptr;
+    if (own) {
+        if (current_tree(c, "dxv_octree_expand")) return 1;
+        deviceNodes = f.octNodes.p; nodes = f.octCount;                 // (a current tree is the tree of this grid: its levels are L)
+    } else {
+        if (!nodes) return fail(c, "dxv_octree_expand: a tree of 0 nodes (the root is always there: nodes >= 1)");
+        if (nodes > kOctMaxNodes) return fail(c, "dxv_octree_expand: a tree of %u nodes; at most %llu", nodes, (unsigned long long)kOctMaxNodes);
+        if (levels != L) return fail(c, "dxv_octree_expand: a tree of %u levels; the frame's grid of %u^3 voxels has %u", levels, N, L);
+        if (reinterpret_cast<uintptr_t>(deviceNodes) % 4) return fail(c, "dxv_octree_expand: nodes at %p: need a 4-byte aligned pointer", deviceNodes);
+        const size_t need = (size_t)nodes * 2u * sizeof(uint32_t);
+        size_t room = 0;
+        if (const int r = check_device_range(c, "dxv_octree_expand", deviceNodes, need, &room))
+            return r == 1 ? 1 : fail(c, "dxv_octree_expand: %u nodes need %zu bytes, the allocation behind %p has %zu", nodes, need, deviceNodes, room);
+    }
+    if (settle_frame_launch(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    // the grid stops being what the frame's last launch wrote (dxv_fill_async's rules): a kept queue's zeros are gone, and whatever was made
+    // of the grid before -- fields, the mesh, the frame's own tree -- is stale
+    f.clearSig = 0;
+    grid_rewritten(f);
+    DXV_HIP(c, launch_oct_expand(f.grid.p, N, static_cast<const uint32_t*>(deviceNodes), nodes, f.status.p + kOctStatusWord, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    if (!own) f.octExpandPending = true;                                // (the frame's own tree was made by the build: it has nothing to report)
+    return 0;
+}
+
+int dxv_octree_expand(dxv_ctx* c, const void* deviceNodes, uint32_t nodes, uint32_t levels)
+{
+    if (dxv_octree_expand_async(c, deviceNodes, nodes, levels)) return 1;
+    return dxv_sync(c);
+}
+
+// The connected components of the selected frame's grid (components.hip; dxv_components.h has the rule's routines), enqueued on the frame's
+// stream behind whatever it holds, under dxv_render_async's host-wait rule: pack, init, merge, compress and the numbering, K into a
+// page-locked word and the one wait for it -- the pattern of dxv_octree_async: the table cannot be sized without it --, then the stats kernels
+// and the frame's end event, which nobody waits for here.
+int dxv_components_async(dxv_ctx* c, int of, int connectivity)
+{
+    if (!c) return 1;
+    if (of != DXV_COMP_SOLID && of != DXV_COMP_EMPTY) return fail(c, "dxv_components: unknown kind %d (DXV_COMP_SOLID = 0, DXV_COMP_EMPTY = 1)", of);
+    if (connectivity != 6 && connectivity != 26) return fail(c, "dxv_components: connectivity %d (6 or 26)", connectivity);
+    if (check_whole_grid(c, "dxv_components")) return 1;
+    Frame& f = cur_frame(c);
+    const uint32_t N = f.grid_dim;
+    if (N > kCompMaxN) return fail(c, "dxv_components: a grid of %u^3 voxels; at most %u^3 (a label and a linear index must fit 32 bits)", N, kCompMaxN);
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (settle_frame_launch(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    const size_t voxels = (size_t)N * N * N, scratch = comp_scratch_bytes(N);
+    DXV_HIP(c, f.compScratch.reserve(scratch, scratch, fs));
+    f.compVersion = 0;                                                  // (the build writes into the frame's label buffer: what it held is gone)
+    DXV_HIP(c, f.compLabels.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
+    CompParams p{};
+    p.grid = f.grid.p; p.of = of; p.connectivity = (uint32_t)connectivity; p.labels = f.compLabels.p;
+    comp_scratch_layout(f.compScratch.p, N, p);
+    const bool timed = c->opt.events != 0;
+    unsigned long long* total = &c->pin->compTotal[c->cur];
+    DXV_HIP(c, timer_begin(f.timers[kTimerComponents], timed, fs));
+    DXV_HIP(c, launch_comp_label(p, fs));
+    DXV_HIP(c, hipMemcpyAsync(total, p.total, sizeof(unsigned long long), hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipStreamSynchronize(fs));
+    const uint32_t K = (uint32_t)*total;
+    if (K) {
+        DXV_HIP(c, f.compTable.reserve(K, align256((size_t)K * sizeof(CompRecord)), fs));
+        DXV_HIP(c, f.compWork.reserve((size_t)K * sizeof(CompStats), align256((size_t)K * sizeof(CompStats)), fs));
+        p.table = reinterpret_cast<CompRecord*>(f.compTable.p);
+        p.stats = reinterpret_cast<CompStats*>(f.compWork.p);
+        DXV_HIP(c, launch_comp_stats(p, K, fs));
+    }
+    DXV_HIP(c, timer_end(f.timers[kTimerComponents], timed, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    f.compCount = K; f.compDim = N; f.compOf = of; f.compConnectivity = connectivity;
+    f.compHave = true; f.compVersion = f.gridVersion;
+    return 0;
+}
+
+int dxv_components(dxv_ctx* c, int of, int connectivity)
+{
+    if (dxv_components_async(c, of, connectivity)) return 1;
+    return dxv_sync(c);
+}
+
+// whether the frame has labels to hand out: 0, or 1 with the reason as the message
+static int current_labels(const dxv_ctx* c, const char* who)
+{
+    const Frame& f = c->frames[c->cur];
+    dxv_ctx* w = const_cast<dxv_ctx*>(c);                               // (the message is the one thing an accessor writes)
+    if (!f.compHave) return fail(w, "%s: frame %u has no components yet (call dxv_components first)", who, c->cur);
+    if (f.compVersion != f.gridVersion)
+        return fail(w, "%s: frame %u was launched, filled, expanded or selected again since its components were labelled: labels and table are stale", who, c->cur);
+    return 0;
+}
+
+int dxv_components_info(dxv_ctx* c, uint32_t* count, int* of, int* connectivity)
+{
+    if (!c) return 1;
+    if (current_labels(c, "dxv_components_info")) return 1;
+    const Frame& f = cur_frame(c);
+    if (count) *count = f.compCount;
+    if (of) *of = f.compOf;
+    if (connectivity) *connectivity = f.compConnectivity;
+    return 0;
+}
+
+const void* dxv_components_labels_device_ptr(const dxv_ctx* c)
+{
+    if (!c || current_labels(c, "dxv_components_labels_device_ptr")) return nullptr;
+    return c->frames[c->cur].compLabels.p;
+}
+size_t dxv_components_labels_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame& f = c->frames[c->cur];
+    return f.compHave && f.compVersion == f.gridVersion ? (size_t)f.compDim * f.compDim * f.compDim * sizeof(uint32_t) : 0;
+}
+const void* dxv_components_table_device_ptr(const dxv_ctx* c)
+{
+    if (!c || current_labels(c, "dxv_components_table_device_ptr")) return nullptr;
+    return c->frames[c->cur].compCount ? c->frames[c->cur].compTable.p : nullptr;
+}
+size_t dxv_components_table_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame& f = c->frames[c->cur];
+    return f.compHave && f.compVersion == f.gridVersion ? (size_t)f.compCount * sizeof(CompRecord) : 0;
+}
+
+int dxv_components_labels_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || current_labels(c, "dxv_components_labels_download")) return 1;
+    return download_current(c, "dxv_components_labels_download", cur_frame(c).compLabels.p, dxv_components_labels_bytes(c), host, bytes);
+}
+int dxv_components_table_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || current_labels(c, "dxv_components_table_download")) return 1;
+    return download_current(c, "dxv_components_table_download", cur_frame(c).compTable.p, dxv_components_table_bytes(c), host, bytes);
+}
+
+int dxv_components_ms(dxv_ctx* c, float* ms) { return timer_ms(c, "dxv_components_ms", kTimerComponents, ms); }
+
+// The selected frame's grid edited from its labels (components.hip: k_comp_keep, k_comp_edit), in place, enqueued on the frame's stream behind
+// whatever it holds -- under dxv_render_async's host-wait rule and dxv_fill_async's rules for the grid.  The four counters go into page-locked
+// words and are read where the frame is next synchronised.
+int dxv_components_select_async(dxv_ctx* c, int rule, uint32_t arg)
+{
+    if (!c) return 1;
+    if (rule != DXV_SELECT_LARGEST && rule != DXV_SELECT_MIN_VOXELS && rule != DXV_SELECT_BORDER)
+        return fail(c, "dxv_components_select: unknown rule %d (DXV_SELECT_LARGEST = 0, DXV_SELECT_MIN_VOXELS = 1, DXV_SELECT_BORDER = 2)", rule);
+    if (rule != DXV_SELECT_MIN_VOXELS && arg) return fail(c, "dxv_components_select: rule %d takes no argument (arg must be 0, got %u)", rule, arg);
+    if (current_labels(c, "dxv_components_select")) return 1;
+    Frame& f = cur_frame(c);
+    if (!f.grid.p || f.grid_dim != f.compDim || !frame_renderable(f))
+        return fail(c, "dxv_components_select: the labels of frame %u do not belong to its grid: they are stale", c->cur);
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (settle_frame_launch(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    const uint32_t K = f.compCount;
+    const size_t work = comp_select_bytes(K);
+    DXV_HIP(c, f.compWork.reserve(work, work, fs));
+    // the grid stops being what the frame's last launch wrote (dxv_fill_async's rules): a kept queue's zeros are gone, and whatever was made
+    // of the grid before -- fields, the mesh, the tree, these labels -- is stale
+    f.clearSig = 0;
+    grid_rewritten(f);
+    DXV_HIP(c, launch_comp_select(f.grid.p, f.compDim, f.compOf, f.compLabels.p, reinterpret_cast<const CompRecord*>(f.compTable.p), K, rule, arg, f.compWork.p, fs));
+    DXV_HIP(c, hipMemcpyAsync(c->pin->compSel[c->cur], comp_select_counters(f.compWork.p), sizeof(c->pin->compSel[c->cur]), hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    f.selPending = true; f.selRule = rule; f.selComponents = K;
+    return 0;
+}
+
+int dxv_components_select(dxv_ctx* c, int rule, uint32_t arg)
+{
+    if (dxv_components_select_async(c, rule, arg)) return 1;
+    return dxv_sync(c);
+}
+
+int dxv_components_select_info(dxv_ctx* c, uint32_t* kept, uint32_t* dropped, uint64_t* voxels_changed)
+{
+    if (!c) return 1;
+    const Frame& f = cur_frame(c);
+    if (kept) *kept = f.selKept;
+    if (dropped) *dropped = f.selDropped;
+    if (voxels_changed) *voxels_changed = f.selChanged;
+    return 0;
+}
+
+// The exterior flood fill of the selected frame's grid (fill.hip), in place, enqueued on the frame's stream behind whatever it holds --
+// under dxv_render_async's host-wait rule: one batch of rounds, the write-back, the batch's control block into page-locked words, the
+// frame's end event.  Whether the batch converged is read where the frame is next synchronised (settle_fill).
+int dxv_fill_async(dxv_ctx* c, int what)
+{
+    if (!c) return 1;
+    if (what != DXV_FILL_SOLID && what != DXV_FILL_INTERIOR)
+        return fail(c, "dxv_fill: unknown kind %d (DXV_FILL_SOLID = 0, DXV_FILL_INTERIOR = 1)", what);
+    if (check_whole_grid(c, "dxv_fill")) return 1;
+    Frame& f = cur_frame(c);
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (settle_frame_launch(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    const uint32_t N = f.grid_dim;
+    const size_t scratch = fill_scratch_bytes(N);
+    DXV_HIP(c, f.fillScratch.reserve(scratch, scratch, fs));
+    const bool timed = c->opt.events != 0;
+    f.fillWhat = what;
+    f.fillBatch = c->opt.fillrounds ? (uint32_t)c->opt.fillrounds : kFillRoundsDefault;
+    f.fillRounds = 0;
+    // the grid stops being what the frame's last launch wrote: a kept queue's zeros are gone (the next launch clears everything; the
+    // caller holds no pointer because of this, so ptrExposed stays), and a field made of the grid before is stale
+    f.clearSig = 0;
+    grid_rewritten(f);
+    DXV_HIP(c, timer_begin(f.timers[kTimerFill], timed, fs));
+    DXV_HIP(c, launch_fill(f.grid.p, N, what, f.fillScratch.p, f.fillBatch, true, fs));
+    DXV_HIP(c, timer_end(f.timers[kTimerFill], timed, fs));
+    DXV_HIP(c, hipMemcpyAsync(c->pin->fillCtl[c->cur], fill_control(f.fillScratch.p, N), sizeof(c->pin->fillCtl[c->cur]), hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    f.fillPending = true;
+    return 0;
+}
+
+int dxv_fill(dxv_ctx* c, int what)
+{
+    if (dxv_fill_async(c, what)) return 1;
+    return dxv_sync(c);
+}
+
+int dxv_fill_info(dxv_ctx* c, float* ms, uint32_t* rounds)
+{
+    if (!c) return 1;
+    if (ms) *ms = cur_frame(c).timers[kTimerFill].ms;
+    if (rounds) *rounds = cur_frame(c).fillRounds;
+    return 0;
+}
+
+// Morphology of the selected frame's grid by the Euclidean ball (morph.hip), in place, enqueued on the frame's stream behind whatever it holds
+// -- under dxv_render_async's host-wait rule and dxv_fill_async's rules for the grid.  A fixed chain of kernels: nothing to settle; the two
+// counters go into page-locked words and are read where the frame is next synchronised.
+int dxv_morph_async(dxv_ctx* c, int op, uint32_t radius_sq)
+{
+    if (!c) return 1;
+    if (op != DXV_MORPH_DILATE && op != DXV_MORPH_ERODE && op != DXV_MORPH_OPEN && op != DXV_MORPH_CLOSE)
+        return fail(c, "dxv_morph: unknown operation %d (DXV_MORPH_DILATE = 0, DXV_MORPH_ERODE = 1, DXV_MORPH_OPEN = 2, DXV_MORPH_CLOSE = 3)", op);
+    if (radius_sq < 1u || radius_sq > kMorphMaxRadiusSq)
+        return fail(c, "dxv_morph: radius_sq %u is not in [1, %u]", radius_sq, kMorphMaxRadiusSq);
+    if (check_whole_grid(c, "dxv_morph")) return 1;
+    Frame& f = cur_frame(c);
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (settle_frame_launch(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    const uint32_t N = f.grid_dim;
+    const int form = morph_form(radius_sq, c->opt.morphform);
+    const size_t scratch = morph_scratch_bytes(N, op, radius_sq, form);
+    DXV_HIP(c, f.morphScratch.reserve(scratch, scratch, fs));
+    const bool timed = c->opt.events != 0;
+    // the grid stops being what the frame's last launch wrote (dxv_fill_async's rules): a kept queue's zeros are gone, and whatever was made
+    // of the grid before -- fields, the mesh, the tree, labels -- is stale
+    f.clearSig = 0;
+    grid_rewritten(f);
+    DXV_HIP(c, timer_begin(f.timers[kTimerMorph], timed, fs));
+    DXV_HIP(c, launch_morph(f.grid.p, N, op, radius_sq, form, f.morphScratch.p, fs));
+    DXV_HIP(c, timer_end(f.timers[kTimerMorph], timed, fs));
+    DXV_HIP(c, hipMemcpyAsync(c->pin->morphCount[c->cur], morph_counters(f.morphScratch.p), sizeof(c->pin->morphCount[c->cur]), hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    f.morphPending = true;
+    return 0;
+}
+
+int dxv_morph(dxv_ctx* c, int op, uint32_t radius_sq)
+{
+    if (dxv_morph_async(c, op, radius_sq)) return 1;
+    return dxv_sync(c);
+}
+
+int dxv_morph_info(dxv_ctx* c, float* ms, uint64_t* voxels_set, uint64_t* voxels_cleared)
+{
+    if (!c) return 1;
+    const Frame& f = cur_frame(c);
+    if (ms) *ms = f.timers[kTimerMorph].ms;
+    if (voxels_set) *voxels_set = f.morphSet;
+    if (voxels_cleared) *voxels_cleared = f.morphCleared;
+    return 0;
+}
+} // extern "C"

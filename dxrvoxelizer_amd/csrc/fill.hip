@@ -5,7 +5,7 @@
 //   k_fill_write    the masks -> the grid's bytes (0 / 1): the one write of the grid
 // A batch is `rounds` rounds behind one another.  Whether a round changed a word is word `round` of the batch's control block; the
 // kernels of a round return at once when the round before them left its word 0, so a batch costs what its live rounds cost, and the
-// host reads the block where the frame is next synchronised (dxv_frames.hip: settle_fill).  No workgroup waits for another, every
+// host reads the block where the frame is next synchronised (dxv_products.hip: settle_fill).  No workgroup waits for another, every
 // loop is bounded by N; no LDS, no scratch memory.
 #include "dxv_device.h"
 #include "dxv_fill.h"
