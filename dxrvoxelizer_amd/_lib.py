@@ -124,6 +124,9 @@ SYMBOLS = {
     "dxv_morph_async": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
     "dxv_morph": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
     "dxv_morph_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "dxv_thin_async": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
+    "dxv_thin": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
+    "dxv_thin_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     "dxv_build_lists": (C.c_int, [C.c_void_p]),
     "dxv_build_lists_for_grid": (C.c_int, [C.c_void_p, C.c_uint32]),
     "dxv_build_parity_lists": (C.c_int, [C.c_void_p]),

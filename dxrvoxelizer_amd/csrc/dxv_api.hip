@@ -278,6 +278,7 @@ int dxv_trim(dxv_ctx* c)
     for (auto& f : c->frames) f.octScratch.release();                   // (the dense cell words, bits and counts of an octree build; a frame's nodes themselves stay)
     for (auto& f : c->frames) { f.compScratch.release(); f.compWork.release(); }   // (the masks, counts and stats of a labelling; a frame's labels and table themselves stay)
     for (auto& f : c->frames) f.morphScratch.release();                 // (the masks and planes of a morph: (R + 3) bits per voxel)
+    for (auto& f : c->frames) f.thinScratch.release();                  // (the masks of a thin, 3 1/8 bits per voxel: sync_frames has settled every thin)
     c->specRes = 0;
     if (!c->haveHierarchy) c->scratch = BuildScratch{};                             // (a built scene keeps keys and links: dxv_refit reads them)
     // prepared queues of lists that are gone (their slots keep their memory for the next dxv_prepare_launch of the partition: 8 MB at
@@ -592,7 +593,7 @@ size_t dxv_grid_bytes(const dxv_ctx* c) { return c ? c->frames[c->cur].gridBytes
 // the download and count entries: an unchecked launch of the selected frame is finished (with its redo, if any) first ...
 static int finish_launch(dxv_ctx* c)
 {
-    if ((cur_frame(c).pending || cur_frame(c).fillPending || cur_frame(c).octExpandPending) && dxv_sync(c)) return 1;       // (a fill whose verdict is not read yet: the grid may not be final)
+    if ((cur_frame(c).pending || cur_frame(c).fillPending || cur_frame(c).thinPending || cur_frame(c).octExpandPending) && dxv_sync(c)) return 1;       // (a fill or a thin whose verdict is not read yet: the grid may not be final)
     DXV_HIP(c, hipSetDevice(c->device));
     return 0;
 }

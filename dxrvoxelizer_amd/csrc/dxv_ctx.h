@@ -139,7 +139,7 @@ struct Timer { hipEvent_t e0 = nullptr, e1 = nullptr; bool armed = false; float 
 // ... and what a frame times.  The launch's pair and its queue build's are here for their events alone: when they are read is the launch's
 // business (Frame::timed, lastRebuilt -> voxelize_ms, plan_ms), so they stand in front of kTimerFirstOperator: a synchronisation of the frame
 // reads the armed pairs from there on (sync_launch), and a new operator's slot goes behind it.
-enum TimerUse { kTimerLaunch, kTimerQueue, kTimerRender, kTimerDistance, kTimerMeshDistance, kTimerFill, kTimerIso, kTimerOctree, kTimerComponents, kTimerMorph, kTimers,
+enum TimerUse { kTimerLaunch, kTimerQueue, kTimerRender, kTimerDistance, kTimerMeshDistance, kTimerFill, kTimerIso, kTimerOctree, kTimerComponents, kTimerMorph, kTimerThin, kTimers,
                 kTimerFirstOperator = kTimerRender };
 
 struct dxv_ctx {
@@ -284,6 +284,19 @@ struct dxv_ctx {
         DevBuf<uint8_t> morphScratch;    // (cap: bytes) morph_scratch_bytes
         bool morphPending = false;       // a morph's two counters are on their way into page-locked words: the frame's next synchronisation reads them
         uint64_t morphSet = 0, morphCleared = 0;      // of the frame's last morph, as of its last synchronisation
+        // thinning (thin.hip; dxv_thin_async): the bit masks and the control block of the frame's thin, its own so that frames thin side by side;
+        // goes with dxv_trim
+        DevBuf<uint8_t> thinScratch;     // (cap: bytes) thin_scratch_bytes
+        bool thinPending = false;        // a batch is in the stream whose verdict (fixed point or not) nobody has read yet: the frame can still
+                                         // report something, and its next synchronisation reads it and goes on if need be (settle_thin)
+        int thinKind = 0;                // ... DXV_THIN_CURVE / DXV_THIN_KERNEL, for the batches that follow
+        uint32_t thinBatch = 0;          // ... iterations per batch (option thinrounds as it stood at dxv_thin_async)
+        uint32_t thinInBatch = 0;        // ... iterations of the batch in the stream (the last one of a bounded thin may be shorter)
+        uint32_t thinLeft = 0;           // ... iterations max_iterations still allows behind that batch (thinBounded)
+        bool thinBounded = false;        // ... max_iterations != 0
+        uint32_t thinIterations = 0;     // iterations of the frame's last thin so far, the confirming one included
+        uint64_t thinRemoved = 0;        // voxels it removed, as of the frame's last synchronisation
+        bool thinConverged = false;      // it stopped at an iteration that removed nothing (false: max_iterations stopped it first, or none yet)
     };
     Frame frames[DXV_FRAME_COUNT];
     uint32_t cur = 0;                    // dxv_set_frame
@@ -318,6 +331,7 @@ struct dxv_ctx {
         unsigned long long compTotal[DXV_FRAME_COUNT];    // K of the labelling a frame is building: sizes its table
         unsigned long long compSel[DXV_FRAME_COUNT][4];   // kept, dropped, voxels changed and the largest component's key of a frame's last select
         unsigned long long morphCount[DXV_FRAME_COUNT][2]; // voxels set and voxels cleared by a frame's last morph
+        dxv::ThinControl thinCtl[DXV_FRAME_COUNT];       // the control block of a frame's last thin batch and the voxels removed so far
     };
     Pinned* pin = nullptr;
     hipEvent_t evList[4] = {};       // around the counting pass, around the rest of the build
@@ -462,6 +476,7 @@ int check_interleave(dxv_ctx* c, const char* who, uint32_t N, uint32_t rank, uin
 // dxv_products.hip
 void read_products(dxv_ctx* c, uint32_t i);                // the counters of the frame's last select and morph, once its stream has been waited for
 int settle_fill(dxv_ctx* c, uint32_t i);                   // the verdict of the frame's last fill batch; further batches until one has converged
+int settle_thin(dxv_ctx* c, uint32_t i);                   // ... of the frame's last thin batch; further batches until the fixed point or max_iterations
 int settle_expand(dxv_ctx* c, uint32_t i);                 // the verdict of an expansion from a caller's tree
 // dxv_lists.hip
 struct ListScratchA { DirRecord* rec; uint32_t *counts, *offsets, *pairs, *sums; unsigned long long* total; size_t bytes; };

@@ -307,6 +307,23 @@ hipError_t launch_comp_select(uint8_t* grid, uint32_t N, int of, const uint32_t*
 size_t morph_scratch_bytes(uint32_t N, int op, uint32_t r2, int form);
 unsigned long long* morph_counters(uint8_t* scratch);
 hipError_t launch_morph(uint8_t* grid, uint32_t N, int op, uint32_t r2, int form, uint8_t* scratch, hipStream_t s);
+// ... its pack (grid -> the solid mask and the "a byte here is neither 0 nor 1" bits, one per eight voxels) and its write-back (was, now: the solid
+// masks before and after; counters: {voxels set, voxels cleared}, added to) for the operators that work on the same masks
+void launch_morph_pack(const uint8_t* grid, uint32_t N, uint8_t* mask, uint64_t* loose, hipStream_t s);
+void launch_morph_write(const uint8_t* was, const uint8_t* now, const uint64_t* loose, uint32_t N, uint8_t* grid, unsigned long long* counters, hipStream_t s);
+
+// thin.hip -- topology-preserving thinning of a whole N^3 grid (dxv_thin.h), kind 0 = CURVE, 1 = KERNEL, in place, bytes 0 / 1: one batch =
+// (first: the grid packed into the solid mask,) `iterations` iterations (1 .. kThinMaxRounds) of border + eight sub-iterations, the write-back.
+// scratch: thin_scratch_bytes(N); it begins with the batch's control block -- word k != 0: iteration k removed something; the batch has reached
+// the fixed point exactly when one of its words is 0 -- and the voxels removed since the first batch.  A batch with first = false goes on from
+// the masks of the one before.
+struct ThinControl {
+    uint32_t live[64];                // (kThinMaxRounds)
+    unsigned long long removed;
+    unsigned long long written[2];    // the write-back's own counters: nobody reads them
+};
+size_t thin_scratch_bytes(uint32_t N);
+hipError_t launch_thin(uint8_t* grid, uint32_t N, int kind, uint8_t* scratch, uint32_t iterations, bool first, hipStream_t s);
 
 // raycast.hip
 struct RayCastCB;

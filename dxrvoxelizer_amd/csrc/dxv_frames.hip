@@ -574,6 +574,7 @@ int voxelize_common(dxv_ctx* c, uint32_t N, int mode, uint32_t z0, uint32_t nzLo
     f.lastMode = mode; f.lastZBlock = zBlock; f.lastZPeriod = zPeriod;
     grid_rewritten(f);                                                  // (whatever was made of the grid this launch replaces is stale)
     f.fillPending = false;                                              // (... and a fill of it that has not converged yet is dropped: its batch in the stream ends in front of this launch)
+    if (f.thinPending) { f.thinPending = false; f.thinConverged = false; }      // (... and a thin of it likewise: it stopped where that batch ended)
     return launch_now(c, c->cur);
 }
 
@@ -592,7 +593,7 @@ static int sync_launch(dxv_ctx* c, uint32_t i)
         DXV_HIP(c, hipStreamSynchronize(fs));
         f.sceneReadPending = false;                                     // (whatever read the scene on this stream has finished)
         for (int u = kTimerFirstOperator; u < kTimers; ++u)
-            if (u != kTimerFill) timer_read(f.timers[u]);               // (the fill's pair is settle_fill's: further batches move its second event)
+            if (u != kTimerFill && u != kTimerThin) timer_read(f.timers[u]);    // (the fill's pair is settle_fill's, the thin's settle_thin's: further batches move their second event)
         read_products(c, i);
         // lists this launch was queued behind without waiting for their verdict: withdrawn -> the launch again, through the tree
         if (settle_lists(c)) return 1;
@@ -632,6 +633,7 @@ int sync_frame(dxv_ctx* c, uint32_t i)
 {
     if (sync_launch(c, i)) return 1;
     if (settle_fill(c, i)) return 1;
+    if (settle_thin(c, i)) return 1;
     return settle_expand(c, i);
 }
 
@@ -661,7 +663,7 @@ int settle_frame_launch(dxv_ctx* c)
     Frame& f = cur_frame(c);
     if (f.pending && (f.lastCanFail || (f.usedLists && f.listEpochUsed == c->withdrawnEpoch))) return sync_frame(c, c->cur);
     if (f.octExpandPending) return sync_frame(c, c->cur);               // an expansion from a caller's tree whose verdict is not in yet
-    if (f.fillPending) return sync_frame(c, c->cur);                    // a fill whose verdict is not in yet: what is behind it must see the final grid
+    if (f.fillPending || f.thinPending) return sync_frame(c, c->cur);   // a fill or a thin whose verdict is not in yet: what is behind it must see the final grid
     return 0;
 }
 

@@ -193,6 +193,8 @@ struct Options {
     int surfaceitems = 0;    // surface modes: work items the large triangles' list may take (0: all 2^20 it holds; fewer: tests of a full list)
     int fillrounds = 0;      // dxv_fill*: rounds of one batch (1 .. 64); 0 = kFillRoundsDefault (dxv_fill.h).  Same grids: a fill that needs more is
                              // continued where its frame is next synchronised
+    int thinrounds = 0;      // dxv_thin*: iterations of one batch (1 .. 64); 0 = kThinRoundsDefault (dxv_thin.h).  Same grids: a thin that needs more is
+                             // continued where its frame is next synchronised
     int morphform = 0;       // dxv_morph*: 0 = by the radius (dxv_morph.h: morph_form), 1 = bit planes, 2 = distance field + threshold.  Same grids.
     int mdistwalk = 1;       // dxv_mesh_distance*: 1 = the nearest-triangle query over the hierarchy, 0 = every triangle for every voxel (cross-check; same field)
     int sortbits = 0;        // digit plan of the radix sort as last set through this context (the plan itself is the process's: radix_sort_set_plan)
@@ -259,6 +261,7 @@ constexpr OptionRow kGridPassOptions[] = {
     {"fillrounds", in_range(0, 64), "not in [0, 64]", &Options::fillrounds, OptionEffect::none},
     {"mdistwalk", kOnOff, "not in {0,1}", &Options::mdistwalk, OptionEffect::none},
     {"morphform", in_range(0, 2), "not in {0,1,2}", &Options::morphform, OptionEffect::none},
+    {"thinrounds", in_range(0, 64), "not in [0, 64]", &Options::thinrounds, OptionEffect::none},
 };
 
 inline const OptionRow* find_option(const char* name)

@@ -1,6 +1,6 @@
 // dxv_products.hip -- what is made of a frame's grid, and what edits it in place: distance field, mesh distance field, isosurface, octree and
-// its expansion, components and select, fill, morph -- the host side of each (the kernels: distance.hip, mesh_distance.hip, isosurface.hip,
-// octree.hip, components.hip, fill.hip, morph.hip), the accessors of what they made, and their halves of a frame's synchronisation.
+// its expansion, components and select, fill, morph, thin -- the host side of each (the kernels: distance.hip, mesh_distance.hip, isosurface.hip,
+// octree.hip, components.hip, fill.hip, morph.hip, thin.hip), the accessors of what they made, and their halves of a frame's synchronisation.
 #include "dxv_ctx.h"
 #include "dxv_mesh_distance.h"
 #include "dxv_fill.h"
@@ -8,6 +8,7 @@
 #include "dxv_octree.h"
 #include "dxv_components.h"
 #include "dxv_morph.h"
+#include "dxv_thin.h"
 
 using namespace dxv;
 using namespace dxvhost;
@@ -89,6 +90,46 @@ int settle_fill(dxv_ctx* c, uint32_t i)
         DXV_HIP(c, launch_fill(f.grid.p, N, f.fillWhat, f.fillScratch.p, f.fillBatch, false, fs));
         if (t.armed) DXV_HIP(c, hipEventRecord(t.e1, fs));
         DXV_HIP(c, hipMemcpyAsync(c->pin->fillCtl[i], fill_control(f.fillScratch.p, N), sizeof(c->pin->fillCtl[i]), hipMemcpyDeviceToHost, fs));
+        DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+        DXV_HIP(c, hipStreamSynchronize(fs));
+    }
+    timer_read(t);
+    return 0;
+}
+
+// ... and the thin's, beside it (the stream has been waited for): the verdict of the frame's last thin batch, by the fill's discipline.  A batch all
+// of whose iterations removed something has not reached the fixed point: unless max_iterations has been used up, a further batch -- iterations and
+// write-back, from the masks the frame's scratch still holds -- is enqueued and waited for.  Every live iteration removes at least one of the
+// V voxels: fewer than V iterations.
+int settle_thin(dxv_ctx* c, uint32_t i)
+{
+    Frame& f = c->frames[i];
+    const hipStream_t fs = frame_stream(c, i);
+    const ThinControl& ctl = c->pin->thinCtl[i];
+    Timer& t = f.timers[kTimerThin];
+    const uint32_t N = f.grid_dim;
+    const uint64_t most = f.thinBatch ? (uint64_t)N * N * N / f.thinBatch + 2u : 0u;
+    for (uint64_t batch = 0; f.thinPending; ++batch) {
+        uint32_t live = 0;
+        while (live < f.thinInBatch && ctl.live[live]) ++live;
+        f.thinRemoved = ctl.removed;
+        if (live < f.thinInBatch) {                                     // iteration `live` removed nothing: the confirming iteration
+            f.thinIterations += live + 1u;
+            f.thinConverged = true;
+            f.thinPending = false;
+            break;
+        }
+        f.thinIterations += f.thinInBatch;
+        if (f.thinBounded && !f.thinLeft) {                             // max_iterations stopped it first
+            f.thinPending = false;
+            break;
+        }
+        if (batch >= most) return fail(c, "dxv_thin: no fixed point after %u iterations on a grid of %u^3 voxels", f.thinIterations, N);
+        f.thinInBatch = thin_batch(f.thinBatch, f.thinBounded ? f.thinLeft : 0u);
+        if (f.thinBounded) f.thinLeft -= f.thinInBatch;
+        DXV_HIP(c, launch_thin(f.grid.p, N, f.thinKind, f.thinScratch.p, f.thinInBatch, false, fs));
+        if (t.armed) DXV_HIP(c, hipEventRecord(t.e1, fs));
+        DXV_HIP(c, hipMemcpyAsync(&c->pin->thinCtl[i], f.thinScratch.p, sizeof(ThinControl), hipMemcpyDeviceToHost, fs));
         DXV_HIP(c, hipEventRecord(f.evEnd, fs));
         DXV_HIP(c, hipStreamSynchronize(fs));
     }
@@ -749,6 +790,63 @@ int dxv_morph_info(dxv_ctx* c, float* ms, uint64_t* voxels_set, uint64_t* voxels
     if (ms) *ms = f.timers[kTimerMorph].ms;
     if (voxels_set) *voxels_set = f.morphSet;
     if (voxels_cleared) *voxels_cleared = f.morphCleared;
+    return 0;
+}
+
+// Topology-preserving thinning of the selected frame's grid (thin.hip), in place, enqueued on the frame's stream behind whatever it holds -- under
+// dxv_render_async's host-wait rule and dxv_fill_async's rules for the grid: one batch of iterations, the write-back, the batch's control block
+// into page-locked words, the frame's end event.  Whether the batch reached the fixed point is read where the frame is next synchronised
+// (settle_thin).
+int dxv_thin_async(dxv_ctx* c, int kind, uint32_t max_iterations)
+{
+    if (!c) return 1;
+    if (kind != DXV_THIN_CURVE && kind != DXV_THIN_KERNEL)
+        return fail(c, "dxv_thin: unknown kind %d (DXV_THIN_CURVE = 0, DXV_THIN_KERNEL = 1)", kind);
+    if (check_whole_grid(c, "dxv_thin")) return 1;
+    Frame& f = cur_frame(c);
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (settle_frame_launch(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    const uint32_t N = f.grid_dim;
+    if (N > kThinMaxN || (N & 1u)) return fail(c, "dxv_thin: a grid of side %u (needs an even side of at most %u)", N, kThinMaxN);
+    const size_t scratch = thin_scratch_bytes(N);
+    DXV_HIP(c, f.thinScratch.reserve(scratch, scratch, fs));
+    const bool timed = c->opt.events != 0;
+    f.thinKind = kind;
+    f.thinBatch = c->opt.thinrounds ? (uint32_t)c->opt.thinrounds : kThinRoundsDefault;
+    f.thinBounded = max_iterations != 0u;
+    f.thinInBatch = thin_batch(f.thinBatch, max_iterations);
+    f.thinLeft = f.thinBounded ? max_iterations - f.thinInBatch : 0u;
+    f.thinIterations = 0;
+    f.thinRemoved = 0;
+    f.thinConverged = false;
+    // the grid stops being what the frame's last launch wrote (dxv_fill_async's rules): a kept queue's zeros are gone, and whatever was made
+    // of the grid before -- fields, the mesh, the tree, labels -- is stale
+    f.clearSig = 0;
+    grid_rewritten(f);
+    DXV_HIP(c, timer_begin(f.timers[kTimerThin], timed, fs));
+    DXV_HIP(c, launch_thin(f.grid.p, N, kind, f.thinScratch.p, f.thinInBatch, true, fs));
+    DXV_HIP(c, timer_end(f.timers[kTimerThin], timed, fs));
+    DXV_HIP(c, hipMemcpyAsync(&c->pin->thinCtl[c->cur], f.thinScratch.p, sizeof(ThinControl), hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    f.thinPending = true;
+    return 0;
+}
+
+int dxv_thin(dxv_ctx* c, int kind, uint32_t max_iterations)
+{
+    if (dxv_thin_async(c, kind, max_iterations)) return 1;
+    return dxv_sync(c);
+}
+
+int dxv_thin_info(dxv_ctx* c, float* ms, uint32_t* iterations, uint64_t* voxels_removed, int* converged)
+{
+    if (!c) return 1;
+    const Frame& f = cur_frame(c);
+    if (ms) *ms = f.timers[kTimerThin].ms;
+    if (iterations) *iterations = f.thinIterations;
+    if (voxels_removed) *voxels_removed = f.thinRemoved;
+    if (converged) *converged = f.thinConverged ? 1 : 0;
     return 0;
 }
 } // extern "C"

@@ -138,6 +138,16 @@ __global__ __launch_bounds__(256) void k_morph_threshold(uint8_t* grid, const in
     }
 }
 
+// pack and write-back for another operator on bit masks (thin.hip): the same two kernels, launched on its stream with its buffers
+void launch_morph_pack(const uint8_t* grid, uint32_t N, uint8_t* mask, uint64_t* loose, hipStream_t s)
+{
+    k_morph_pack<<<(uint32_t)((fill_mask_words(N) * 8u + 255u) / 256u), 256, 0, s>>>(grid, N, 0, mask, loose);
+}
+void launch_morph_write(const uint8_t* was, const uint8_t* now, const uint64_t* loose, uint32_t N, uint8_t* grid, unsigned long long* counters, hipStream_t s)
+{
+    k_morph_write<<<(uint32_t)((fill_mask_words(N) * 8u + 255u) / 256u), 256, 0, s>>>(was, 0, now, loose, N, grid, counters);
+}
+
 // scratch of one call: {voxels set, voxels cleared} in a line of their own, then
 //   planes: the packed mask, one result mask per half, the "neither 0 nor 1" bits, the R planes
 //   field:  the field (4 B per voxel) and the scratch of its passes (distance_scratch_bytes, 6 B per voxel)

@@ -14,6 +14,7 @@ DIST_SQ_I32, DIST_F32 = 0, 1                     # formats of the distance field
 MDIST_VOXELS_F32, MDIST_UNITS_F32 = 0, 1          # formats of the mesh distance field (include/dxv.h)
 FILL_SOLID, FILL_INTERIOR = 0, 1                  # what the flood fill leaves (include/dxv.h)
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3     # the operations of Morph (include/dxv.h)
+THIN_CURVE, THIN_KERNEL = 0, 1                                      # the kinds of Thin (include/dxv.h)
 ISO_MESH_DISTANCE, ISO_GRID_DISTANCE = 0, 1       # the field an isosurface is taken from (include/dxv.h)
 ISO_SPACE_VOXELS, ISO_SPACE_OBJECT = 0, 1         # ... and the space its vertices are in
 COMP_SOLID, COMP_EMPTY = 0, 1                     # what connected components are taken of (include/dxv.h)
@@ -566,6 +567,24 @@ class Voxelizer:
         ms, was_set, cleared = C.c_float(), C.c_uint64(), C.c_uint64()
         self._check(self._lib.dxv_morph_info(self._ctx, C.byref(ms), C.byref(was_set), C.byref(cleared)))
         return ms.value, was_set.value, cleared.value
+
+    # ---- topology-preserving thinning of the frame's grid ---------------------------------------------
+    def Thin(self, kind, max_iterations=0, sync=True, frameIndex=None):
+        """Thin the solid of the selected frame's whole grid without changing its topology, in place, bytes 0 / 1 (dxv_thin / dxv_thin_async;
+        include/dxv.h has the rule): THIN_CURVE leaves a curve skeleton, THIN_KERNEL the topological kernel (a voxel per blob, a ring per
+        handle).  Voxels outside the grid are empty.  max_iterations=0: to the fixed point.  Voxelize(N, MODE_SURFACE); Fill(); Thin(THIN_CURVE)
+        is the centre line of a mesh.  sync=False only enqueues one batch of iterations behind whatever the frame's stream holds."""
+        if frameIndex is not None:
+            self.SetFrame(frameIndex)
+        fn = self._lib.dxv_thin if sync else self._lib.dxv_thin_async
+        self._check(fn(self._ctx, int(kind), int(max_iterations)))
+        return True
+
+    def thin_info(self):
+        """(ms, iterations, voxels_removed, converged) of the selected frame's last thin as of its last Sync (dxv_thin_info)."""
+        ms, iterations, removed, converged = C.c_float(), C.c_uint32(), C.c_uint64(), C.c_int()
+        self._check(self._lib.dxv_thin_info(self._ctx, C.byref(ms), C.byref(iterations), C.byref(removed), C.byref(converged)))
+        return ms.value, iterations.value, removed.value, converged.value
 
     def grid_bytes(self):
         return self._lib.dxv_grid_bytes(self._ctx)

@@ -428,6 +428,57 @@ DXV_API int dxv_morph(dxv_ctx* ctx, int op, uint32_t radius_sq);
  * any pointer may be NULL. */
 DXV_API int dxv_morph_info(dxv_ctx* ctx, float* ms, uint64_t* voxels_set, uint64_t* voxels_cleared);
 
+/* Thinning: the solid of a grid reduced to its skeleton without a change of topology (no reference counterpart).  dxv_morph(ERODE) shrinks a
+ * solid but breaks thin parts apart and makes small ones vanish; this operator removes only voxels whose removal changes no piece, cavity or
+ * tunnel.  Centre lines of pipes, vessels and limbs; a graph of the shape; with dxv_components a check of genus.
+ * Input: the WHOLE grid of the selected frame's last launch, in any mode.  Bytes written through dxv_grid_device_ptr count too.  solid(p) iff
+ * byte(p) != 0.
+ * Outside the grid: voxels outside the grid are EMPTY for this operator.  This is UNLIKE dxv_morph, where they do not exist.  The consequence
+ * is that an all-solid grid thins from its border.
+ * Neighbourhoods of voxel p: N26*(p) is the 26 voxels around p, N18*(p) those of them that share a face or an edge with p, N6*(p) those
+ * that share a face.
+ * Simple voxel.  Two counts decide it:
+ *     T26(p) = the number of 26-connected components of the solid voxels of N26*(p)
+ *     T6(p)  = the number of 6-connected components of the EMPTY voxels of N18*(p) that contain a voxel of N6*(p)
+ * p is simple iff T26(p) == 1 && T6(p) == 1.  This is the Bertrand-Malandain characterisation for (26, 6) connectivity.  Removing a simple
+ * voxel changes no piece, cavity or tunnel.
+ * Subfields: sub(p) = (x & 1) | (y & 1) << 1 | (z & 1) << 2 has eight values.  Two distinct voxels of one subfield are never 26-adjacent.
+ * One ITERATION, from the current solid set S:
+ *     1. B = { p in S : some voxel of N6*(p) is empty }.  This is the border as it is at the START of the iteration.
+ *     2. For s = 0, 1, ..., 7 in this order, remove at once from S every p that meets all of: p is in B and still in S; sub(p) == s; p is
+ *        simple in the current S; p is not kept by the kind.
+ * Whether p is simple depends only on N26*(p), and no other voxel of p's subfield lies in N26*(p): removing a subfield's voxels together
+ * equals removing them one by one in any order.  So the result is a function of the grid alone -- it depends on the fixed subfield order and
+ * on nothing else (a mirrored grid thins to other bytes) -- and the device's grid equals a restatement byte for byte.
+ * Stopping: iterations repeat until one removes nothing -- that iteration is the confirming one, counted like the fill's confirming round
+ * -- or until max_iterations of them have run.  max_iterations == 0 means to the fixed point. */
+enum {
+    DXV_THIN_CURVE = 0,      /* keeps p when exactly one voxel of N26*(p) is solid in the current S, a curve's end point: a curve skeleton */
+    DXV_THIN_KERNEL = 1      /* keeps nothing: the topological kernel, one voxel per simply connected piece, a closed one-voxel ring for a torus */
+};
+/* dxv_thin_async -- the result REPLACES the frame's grid in place, bytes exactly 0 or 1, like dxv_fill and dxv_morph.  ENQUEUED on the frame's
+ * stream behind its launch (render, field, fill, morph); returns without waiting.
+ *  - The host waits only under dxv_render_async's rule; a pending fill is settled first.
+ *  - Checked on the host before anything is enqueued, each an error with a message: the kind is one of the two; the frame has been launched;
+ *    its last launch was the whole grid.
+ *  - Unbounded iterations by the fill's discipline.  The call enqueues ONE batch of iterations (option thinrounds) and the write-back; an
+ *    iteration returns at once when the one before it removed nothing; whether the batch reached the fixed point or max_iterations is a
+ *    page-locked block that is read where the frame is next synchronised, and that synchronisation enqueues further batches from the bit masks
+ *    kept in the frame's scratch until one confirms.  After dxv_sync the grid is always exact; until then the frame counts as one that can
+ *    still report something: dxv_render_async, dxv_distance_async, dxv_fill_async, dxv_morph_async, dxv_components_async, dxv_octree_async,
+ *    dxv_isosurface_async, dxv_stream_wait_frame, dxv_grid_* and a second dxv_thin_async settle a pending thin first.  The next dxv_voxelize*
+ *    simply overwrites the grid.
+ *  - Everything a morph makes stale is stale after a thin: distance field, mesh-distance sign, isosurface, octree, components.  The texel
+ *    image is not touched.
+ *  - The scratch (four bit masks, about 3 1/8 bits per voxel) belongs to the frame: frames thin side by side.  dxv_trim gives it back.
+ * dxv_thin -- the same + dxv_sync. */
+DXV_API int dxv_thin_async(dxv_ctx* ctx, int kind, uint32_t max_iterations);
+DXV_API int dxv_thin(dxv_ctx* ctx, int kind, uint32_t max_iterations);
+/* The selected frame's last thin as of the frame's last dxv_sync: device time in milliseconds from its first kernel to its last write-back (HIP
+ * events, option events = 1; else 0), the iterations it ran, the confirming one included, the voxels it removed, and converged = 0 only when
+ * max_iterations stopped it first.  All 0 before the frame's first thin; any pointer may be NULL. */
+DXV_API int dxv_thin_info(dxv_ctx* ctx, float* ms, uint32_t* iterations, uint64_t* voxels_removed, int* converged);
+
 /* The exact signed distance from every voxel centre to the MESH, computed on the device by a nearest-triangle query over the scene's
  * hierarchy (no reference counterpart).  dxv_distance above is the field of the GRID -- integer geometry, no |d| below 1, its zero set the
  * staircase of the voxelization; this one is the Euclidean distance to the nearest triangle to sub-voxel accuracy, what collision and
@@ -762,6 +813,8 @@ DXV_API int dxv_get_stats(const dxv_ctx* ctx, dxv_stats* out);
  *                 holds); a triangle whose items do not all fit is walked whole as well.  Same grids.
  *   fillrounds 0..64  dxv_fill*: rounds of one batch (0, default: 4 -- the meshes measured take 2 or 3); a fill that needs more is continued
  *                 where its frame is next synchronised.  Same grids.
+ *   thinrounds 0..64  dxv_thin*: iterations of one batch (0, default: 16); a thin that needs more is continued where its frame is next
+ *                 synchronised.  Same grids.
  *   morphform 0..2  dxv_morph*: 0 (default) = by the radius: bit planes up to radius_sq 1024, above it the distance field of the grid and its
  *                 threshold, per half; 1 / 2 = always the planes / always the field (measurement, cross-check).  Same grids.
  *   mdistwalk 0|1 dxv_mesh_distance*: 1 (default) = nearest-triangle query over the hierarchy; 0 = every triangle for every voxel, the
@@ -813,7 +866,7 @@ DXV_API int dxv_debug_queue_order(dxv_ctx* ctx, uint64_t out[4]);
 
 /* Give back what the context keeps only to make the next build faster: the list build's scratch (up to 16 GiB per buffer
  * after a 10 M-triangle scene), the LBVH build's scratch when no refit can follow (imported scenes), the memory of prepared queues
- * whose lists are gone, the scratch of the frames' distance fields (the fields stay), of their flood fills and morphs, of their isosurfaces (the
+ * whose lists are gone, the scratch of the frames' distance fields (the fields stay), of their flood fills, morphs and thins, of their isosurfaces (the
  * meshes stay), of their octrees (the nodes stay) and of their connected components (labels and table stay).  Nothing a launch reads. */
 DXV_API int dxv_trim(dxv_ctx* ctx);
 

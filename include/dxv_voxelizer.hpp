@@ -256,6 +256,16 @@ public:
 	// is the solid of a mesh with holes narrower than the ball.
 	bool Morph(int op, uint32_t radiusSq, bool sync = true) { return m_ctx && (sync ? dxv_morph(m_ctx, op, radiusSq) : dxv_morph_async(m_ctx, op, radiusSq)) == 0; }
 	bool MorphInfo(float& ms, uint64_t& voxelsSet, uint64_t& voxelsCleared) { return m_ctx && dxv_morph_info(m_ctx, &ms, &voxelsSet, &voxelsCleared) == 0; }
+	// That frame's solid thinned without a change of topology, in place (dxv_thin / dxv_thin_async): DXV_THIN_CURVE leaves a curve skeleton,
+	// DXV_THIN_KERNEL the topological kernel; maxIterations = 0: to the fixed point.  Voxels outside the grid are empty.
+	bool Thin(int kind, uint32_t maxIterations = 0, bool sync = true) { return m_ctx && (sync ? dxv_thin(m_ctx, kind, maxIterations) : dxv_thin_async(m_ctx, kind, maxIterations)) == 0; }
+	bool ThinInfo(float& ms, uint32_t& iterations, uint64_t& voxelsRemoved, bool& converged)
+	{
+		int c = 0;
+		const bool ok = m_ctx && dxv_thin_info(m_ctx, &ms, &iterations, &voxelsRemoved, &c) == 0;
+		converged = c != 0;
+		return ok;
+	}
 
 	// Result: uint8 occupancy, x fastest, then y (top to bottom), then z.
 	bool Download(std::vector<uint8_t>& grid)
