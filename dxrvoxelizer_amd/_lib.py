@@ -115,6 +115,12 @@ SYMBOLS = {
     "dxv_components_labels_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "dxv_components_table_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "dxv_components_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "dxv_measure_async": (C.c_int, [C.c_void_p]),
+    "dxv_measure": (C.c_int, [C.c_void_p]),
+    "dxv_measure_table_device_ptr": (C.c_void_p, [C.c_void_p]),
+    "dxv_measure_table_bytes": (C.c_size_t, [C.c_void_p]),
+    "dxv_measure_table_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_measure_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "dxv_components_select_async": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
     "dxv_components_select": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
     "dxv_components_select_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),

@@ -367,6 +367,15 @@ static bool comp_params_ok(const CompParams& p)
            p.labels && p.mask && p.rootMask && p.bases && p.sums && p.total;
 }
 
+// the pack alone: the member mask of a labelling made again from the grid it was made of (dxv_measure, once dxv_trim has released the mask)
+hipError_t launch_comp_pack(const uint8_t* grid, uint32_t N, int of, uint64_t* mask, hipStream_t s)
+{
+    if (N < 2u || N > kCompMaxN || (N & 1u) || (of != COMP_SOLID && of != COMP_EMPTY) || !grid || !mask) return hipErrorInvalidValue;
+    const size_t maskBytes = fill_mask_words(N) * 8u;
+    k_comp_pack<<<(uint32_t)((maskBytes + 255u) / 256u), 256, 0, s>>>(grid, N, of, reinterpret_cast<uint8_t*>(mask));
+    return hipGetLastError();
+}
+
 // pack .. number: p.labels holds the labels, p.rootMask and p.bases the roots, *p.total = K
 hipError_t launch_comp_label(const CompParams& p, hipStream_t s)
 {

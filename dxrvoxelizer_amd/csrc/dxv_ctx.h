@@ -139,7 +139,7 @@ struct Timer { hipEvent_t e0 = nullptr, e1 = nullptr; bool armed = false; float 
 // ... and what a frame times.  The launch's pair and its queue build's are here for their events alone: when they are read is the launch's
 // business (Frame::timed, lastRebuilt -> voxelize_ms, plan_ms), so they stand in front of kTimerFirstOperator: a synchronisation of the frame
 // reads the armed pairs from there on (sync_launch), and a new operator's slot goes behind it.
-enum TimerUse { kTimerLaunch, kTimerQueue, kTimerRender, kTimerDistance, kTimerMeshDistance, kTimerFill, kTimerIso, kTimerOctree, kTimerComponents, kTimerMorph, kTimerThin, kTimers,
+enum TimerUse { kTimerLaunch, kTimerQueue, kTimerRender, kTimerDistance, kTimerMeshDistance, kTimerFill, kTimerIso, kTimerOctree, kTimerComponents, kTimerMorph, kTimerThin, kTimerMeasure, kTimers,
                 kTimerFirstOperator = kTimerRender };
 
 struct dxv_ctx {
@@ -274,6 +274,11 @@ struct dxv_ctx {
         int compOf = 0, compConnectivity = 0;         // ... and what it was asked for
         bool compHave = false;           // the frame has had its grid labelled ...
         uint64_t compVersion = 0;        // ... of this grid version
+        // the measures of that labelling (measure.hip; dxv_measure_async): K + 1 records of 96 bytes, the frame's own; stays with dxv_trim like the labels
+        DevBuf<uint8_t> measTable;       // (cap: records)
+        uint32_t measCount = 0;          // K of the labelling the table was made of
+        bool measHave = false;           // the frame has had a labelling measured ...
+        uint64_t measVersion = 0;        // ... of this grid version; 0 once the frame is labelled again
         bool selPending = false;         // a select's four counters are on their way into page-locked words: the frame's next synchronisation reads them
         int selRule = 0;
         uint32_t selComponents = 0;      // K of the labels that select edited from

@@ -300,6 +300,13 @@ size_t comp_select_bytes(uint32_t K);
 unsigned long long* comp_select_counters(uint8_t* work);
 hipError_t launch_comp_select(uint8_t* grid, uint32_t N, int of, const uint32_t* labels, const CompRecord* table, uint32_t K, int rule, uint32_t arg, uint8_t* work,
                               hipStream_t s);
+// ... its pack alone: grid -> the member mask (the first block of the scratch), for what reads the mask of a labelling after dxv_trim
+hipError_t launch_comp_pack(const uint8_t* grid, uint32_t N, int of, uint64_t* mask, hipStream_t s);
+
+// measure.hip -- the integral measures of the K components of a labelling (dxv_measure.h): table = measure_table_bytes(K) = (K + 1) * 96 bytes,
+// record 0 the sum of the others; mask: the labelling's member mask; labels: N^3 uint32.  Nothing but the table is written.
+size_t measure_table_bytes(uint32_t K);
+hipError_t launch_measure(const uint64_t* mask, uint32_t N, uint32_t connectivity, const uint32_t* labels, uint32_t K, uint8_t* table, hipStream_t s);
 
 // morph.hip -- DILATE / ERODE / OPEN / CLOSE (0 .. 3) of a whole N^3 grid by the Euclidean ball of squared radius r2 (1 .. 4096; dxv_morph.h), in
 // place, bytes 0 / 1.  form 1: word-parallel on bit masks and R = floor(sqrt(r2)) planes; form 2: the distance field and its threshold, per

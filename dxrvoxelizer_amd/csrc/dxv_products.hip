@@ -1,12 +1,13 @@
 // dxv_products.hip -- what is made of a frame's grid, and what edits it in place: distance field, mesh distance field, isosurface, octree and
-// its expansion, components and select, fill, morph, thin -- the host side of each (the kernels: distance.hip, mesh_distance.hip, isosurface.hip,
-// octree.hip, components.hip, fill.hip, morph.hip, thin.hip), the accessors of what they made, and their halves of a frame's synchronisation.
+// its expansion, components, their measures and select, fill, morph, thin -- the host side of each (the kernels: distance.hip, mesh_distance.hip,
+// isosurface.hip, octree.hip, components.hip, measure.hip, fill.hip, morph.hip, thin.hip), the accessors of what they made, and their halves of a frame's synchronisation.
 #include "dxv_ctx.h"
 #include "dxv_mesh_distance.h"
 #include "dxv_fill.h"
 #include "dxv_isosurface.h"
 #include "dxv_octree.h"
 #include "dxv_components.h"
+#include "dxv_measure.h"
 #include "dxv_morph.h"
 #include "dxv_thin.h"
 
@@ -562,6 +563,7 @@ int dxv_components_async(dxv_ctx* c, int of, int connectivity)
     const size_t voxels = (size_t)N * N * N, scratch = comp_scratch_bytes(N);
     DXV_HIP(c, f.compScratch.reserve(scratch, scratch, fs));
     f.compVersion = 0;                                                  // (the build writes into the frame's label buffer: what it held is gone)
+    f.measVersion = 0;                                                  // (... and a measure of the labels it held with it)
     DXV_HIP(c, f.compLabels.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
     CompParams p{};
     p.grid = f.grid.p; p.of = of; p.connectivity = (uint32_t)connectivity; p.labels = f.compLabels.p;
@@ -650,6 +652,72 @@ int dxv_components_table_download(dxv_ctx* c, void* host, size_t bytes)
 }
 
 int dxv_components_ms(dxv_ctx* c, float* ms) { return timer_ms(c, "dxv_components_ms", kTimerComponents, ms); }
+
+// The integral measures of the selected frame's current labelling (measure.hip; dxv_measure.h has the rule's routines), enqueued on the frame's
+// stream behind whatever it holds, under dxv_render_async's host-wait rule.  K is known from the labelling: nothing is read back.  The member
+// mask is the labelling's own; once dxv_trim has released it, it is packed again from the grid, which a current labelling guarantees unchanged.
+int dxv_measure_async(dxv_ctx* c)
+{
+    if (!c) return 1;
+    if (check_whole_grid(c, "dxv_measure")) return 1;
+    if (current_labels(c, "dxv_measure")) return 1;
+    Frame& f = cur_frame(c);
+    if (f.grid_dim != f.compDim) return fail(c, "dxv_measure: the labels of frame %u do not belong to its grid: they are stale", c->cur);
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (settle_frame_launch(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    const uint32_t N = f.compDim, K = f.compCount;
+    const bool packed = f.compScratch.p != nullptr;                     // (the mask of the frame's last labelling: this one, it is current)
+    const size_t scratch = comp_scratch_bytes(N);
+    DXV_HIP(c, f.compScratch.reserve(scratch, scratch, fs));
+    f.measVersion = 0;
+    DXV_HIP(c, f.measTable.reserve((size_t)K + 1u, align256(measure_table_bytes(K)), fs));
+    CompParams p{};
+    comp_scratch_layout(f.compScratch.p, N, p);
+    const bool timed = c->opt.events != 0;
+    DXV_HIP(c, timer_begin(f.timers[kTimerMeasure], timed, fs));
+    if (!packed) DXV_HIP(c, launch_comp_pack(f.grid.p, N, f.compOf, p.mask, fs));
+    DXV_HIP(c, launch_measure(p.mask, N, (uint32_t)f.compConnectivity, f.compLabels.p, K, f.measTable.p, fs));
+    DXV_HIP(c, timer_end(f.timers[kTimerMeasure], timed, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    f.measCount = K; f.measHave = true; f.measVersion = f.gridVersion;
+    return 0;
+}
+
+int dxv_measure(dxv_ctx* c)
+{
+    if (dxv_measure_async(c)) return 1;
+    return dxv_sync(c);
+}
+
+// whether the frame has a measure to hand out: 0, or 1 with the reason as the message
+static int current_measure(const dxv_ctx* c, const char* who)
+{
+    const Frame& f = c->frames[c->cur];
+    dxv_ctx* w = const_cast<dxv_ctx*>(c);                               // (the message is the one thing an accessor writes)
+    if (!f.measHave) return fail(w, "%s: frame %u has no measure yet (call dxv_measure first)", who, c->cur);
+    if (f.measVersion != f.gridVersion || f.compVersion != f.gridVersion)
+        return fail(w, "%s: frame %u was launched, edited or labelled again since its components were measured: the measure is stale", who, c->cur);
+    return 0;
+}
+
+const void* dxv_measure_table_device_ptr(const dxv_ctx* c)
+{
+    if (!c || current_measure(c, "dxv_measure_table_device_ptr")) return nullptr;
+    return c->frames[c->cur].measTable.p;
+}
+size_t dxv_measure_table_bytes(const dxv_ctx* c)
+{
+    if (!c || current_measure(c, "dxv_measure_table_bytes")) return 0;
+    return measure_table_bytes(c->frames[c->cur].measCount);
+}
+int dxv_measure_table_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || current_measure(c, "dxv_measure_table_download")) return 1;
+    return download_current(c, "dxv_measure_table_download", cur_frame(c).measTable.p, dxv_measure_table_bytes(c), host, bytes);
+}
+
+int dxv_measure_ms(dxv_ctx* c, float* ms) { return timer_ms(c, "dxv_measure_ms", kTimerMeasure, ms); }
 
 // The selected frame's grid edited from its labels (components.hip: k_comp_keep, k_comp_edit), in place, enqueued on the frame's stream behind
 // whatever it holds -- under dxv_render_async's host-wait rule and dxv_fill_async's rules for the grid.  The four counters go into page-locked

@@ -20,6 +20,8 @@ ISO_SPACE_VOXELS, ISO_SPACE_OBJECT = 0, 1         # ... and the space its vertic
 COMP_SOLID, COMP_EMPTY = 0, 1                     # what connected components are taken of (include/dxv.h)
 SELECT_LARGEST, SELECT_MIN_VOXELS, SELECT_BORDER = 0, 1, 2   # which components SelectComponents keeps
 COMP_RECORD = np.dtype([("first", "<u4"), ("voxels", "<u4"), ("lo", "<u2", (3,)), ("hi", "<u2", (3,)), ("flags", "<u4")])   # a row of the components' table, 24 bytes
+# a row of the measures' table, 96 bytes (include/dxv.h over dxv_measure_async)
+MEASURE_RECORD = np.dtype([("voxels", "<u8"), ("sum", "<u8", (3,)), ("sum2", "<u8", (3,)), ("prod", "<u8", (3,)), ("faces", "<u8"), ("euler", "<i8")])
 DBG_SORTED_KEYS, DBG_NODES, DBG_TRI_POS, DBG_TRI_NRM, DBG_PARENTS, DBG_NODES32, DBG_NODES64, DBG_LIST_CELLS, DBG_LIST_ENTRIES, DBG_LIST_MIP = range(10)
 DBG_BRICK_EMPTY, DBG_BRICK_SUMMARY = 10, 11         # the display pass's empty-brick flags and the summaries behind them
 
@@ -39,6 +41,36 @@ def obj_load(path):
     finally:
         lib.dxv_free(vb)
         lib.dxv_free(ib)
+
+
+def betti_numbers(pieces, cavities, euler):
+    """(b0, b1, b2) from the pieces, the cavities and the Euler number b0 - b1 + b2 of a solid"""
+    return int(pieces), int(pieces) + int(cavities) - int(euler), int(cavities)
+
+
+def mass_properties(table):
+    """Mass properties of every record of a measures' table (dtype MEASURE_RECORD), in voxel units and at unit density, as a dict of float64
+    arrays over the records: volume [R]; centroid [R, 3], at voxel centres (ix + 1/2); area [R] = faces; inertia [R, 3, 3], the tensor about
+    the centroid with each voxel's own cube (1/6 per axis).  The central second moments are formed exactly, in Python integers, before the
+    one division: V * sum2 - sum^2 reaches 1e25, and a difference of floats of that size would keep no digit of a small box far from the
+    origin.  A record without voxels has a centroid of NaN and zeros elsewhere.  A pure host function."""
+    table = np.atleast_1d(np.asarray(table, MEASURE_RECORD))
+    R = len(table)
+    out = {"volume": np.zeros(R), "centroid": np.full((R, 3), np.nan), "area": np.zeros(R), "inertia": np.zeros((R, 3, 3))}
+    for r, rec in enumerate(table):
+        V = int(rec["voxels"])
+        out["volume"][r], out["area"][r] = V, int(rec["faces"])
+        if not V:
+            continue
+        s, s2, pr = [int(a) for a in rec["sum"]], [int(a) for a in rec["sum2"]], [int(a) for a in rec["prod"]]
+        central = [V * s2[a] - s[a] * s[a] for a in range(3)]           # V * sum of (x - mean)^2, exact
+        for a in range(3):
+            b, c = (a + 1) % 3, (a + 2) % 3
+            out["centroid"][r, a] = (2 * s[a] + V) / (2 * V)
+            out["inertia"][r, a, a] = (6 * (central[b] + central[c]) + V * V) / (6 * V)
+            cross = V * pr[a] - s[a] * s[b]                             # prod[a] pairs axis a with axis a + 1: xy, yz, zx
+            out["inertia"][r, a, b] = out["inertia"][r, b, a] = -cross / V
+    return out
 
 
 class Voxelizer:
@@ -515,6 +547,51 @@ class Voxelizer:
         ms = C.c_float()
         self._check(self._lib.dxv_components_ms(self._ctx, C.byref(ms)))
         return ms.value
+
+    # ---- the integral measures of the frame's labelling -----------------------------------------------
+    def Measure(self, sync=True, frameIndex=None):
+        """Measure every component of the selected frame's current labelling on the device (dxv_measure / dxv_measure_async; include/dxv.h has
+        the rule): voxels, first and second moments of the voxel indices, exposed faces and the Euler characteristic by the labelling's
+        connectivity, K + 1 records with record 0 the sum of the others.  sync=True returns MeasureTable(); sync=False only enqueues it."""
+        if frameIndex is not None:
+            self.SetFrame(frameIndex)
+        fn = self._lib.dxv_measure if sync else self._lib.dxv_measure_async
+        self._check(fn(self._ctx))
+        return self.MeasureTable() if sync else True
+
+    def MeasureTable(self):
+        """numpy copy [K + 1] of the selected frame's measures, dtype MEASURE_RECORD (dxv_measure_table_download; synchronises the frame)."""
+        nbytes = self._lib.dxv_measure_table_bytes(self._ctx)
+        if not nbytes:
+            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
+        table = np.empty(nbytes // MEASURE_RECORD.itemsize, MEASURE_RECORD)
+        self._check(self._lib.dxv_measure_table_download(self._ctx, table.ctypes.data_as(C.c_void_p), table.nbytes))
+        return table
+
+    def measure_device_ptr(self):
+        """Device pointer of the selected frame's measures, (K + 1) * 96 bytes, for consumers on the GPU."""
+        ptr = self._lib.dxv_measure_table_device_ptr(self._ctx)
+        if not ptr:
+            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
+        return ptr
+
+    def measure_ms(self):
+        """Device time of the selected frame's last measure, read at the frame's Sync (dxv_measure_ms)."""
+        ms = C.c_float()
+        self._check(self._lib.dxv_measure_ms(self._ctx, C.byref(ms)))
+        return ms.value
+
+    def Betti(self, frameIndex=None):
+        """(b0, b1, b2) of the selected frame's solid as a complex of closed unit cubes: pieces, handles, cavities.  Components(COMP_EMPTY, 6)
+        gives b2, the empty components that do not reach the grid's border; Components(COMP_SOLID, 26) and Measure give b0 = K and the
+        Euler number, and b1 = b0 + b2 - euler.  The solid labelling and its measure stay current."""
+        if frameIndex is not None:
+            self.SetFrame(frameIndex)
+        _, empty = self.Components(COMP_EMPTY, 6)
+        b2 = int(np.count_nonzero((empty["flags"] & 1) == 0))
+        self._check(self._lib.dxv_components(self._ctx, COMP_SOLID, 26))
+        b0 = self.components_info()[0]
+        return betti_numbers(b0, b2, int(self.Measure()[0]["euler"]))
 
     def SelectComponents(self, rule, arg=0, sync=True):
         """Edit the selected frame's grid in place from its current labels (dxv_components_select / _async): the voxels of every component

@@ -430,7 +430,7 @@ DXV_API int dxv_morph_info(dxv_ctx* ctx, float* ms, uint64_t* voxels_set, uint64
 
 /* Thinning: the solid of a grid reduced to its skeleton without a change of topology (no reference counterpart).  dxv_morph(ERODE) shrinks a
  * solid but breaks thin parts apart and makes small ones vanish; this operator removes only voxels whose removal changes no piece, cavity or
- * tunnel.  Centre lines of pipes, vessels and limbs; a graph of the shape; with dxv_components a check of genus.
+ * tunnel.  Centre lines of pipes, vessels and limbs; a graph of the shape; with dxv_components and dxv_measure a check of genus.
  * Input: the WHOLE grid of the selected frame's last launch, in any mode.  Bytes written through dxv_grid_device_ptr count too.  solid(p) iff
  * byte(p) != 0.
  * Outside the grid: voxels outside the grid are EMPTY for this operator.  This is UNLIKE dxv_morph, where they do not exist.  The consequence
@@ -677,6 +677,51 @@ DXV_API int dxv_components_table_download(dxv_ctx* ctx, void* host, size_t bytes
 /* Device time of the selected frame's last labelling in milliseconds (HIP events; the host's read of K lies inside it), read at the frame's
  * dxv_sync: 0 before that, and under option events = 0. */
 DXV_API int dxv_components_ms(dxv_ctx* ctx, float* ms);
+
+/* Integral measures: HOW MUCH there is of each component of the selected frame's current labelling, and of all members together -- volume,
+ * centre of mass and inertia (from the moments), surface area, and the Euler number, from which the handles and cavities of a solid follow
+ * (no reference counterpart).  Input: the labelling as dxv_components left it -- kind `of`, connectivity 6 or 26, K components numbered
+ * 1 .. K, label 0 for a non-member.  It must exist and be current: the staleness rule is that of dxv_components_select.  Voxels outside the
+ * grid are non-members, as in dxv_components' adjacency.
+ * Output: a table of K + 1 records.  Record k (1 .. K) is component k; record 0 is the sum of the others (every measure is additive: every
+ * voxel and every cell counted belongs to exactly one component).  K = 0 gives one all-zero record.  A record, 96 bytes, little endian, for
+ * component C:
+ *     offset  0  uint64    voxels    |C|
+ *     offset  8  uint64[3] sum       the sums of ix, iy, iz over C (voxel indices, not centres)
+ *     offset 32  uint64[3] sum2      the sums of ix^2, iy^2, iz^2
+ *     offset 56  uint64[3] prod      the sums of ix*iy, iy*iz, iz*ix
+ *     offset 80  uint64    faces     pairs (p, d): p in C, d one of the six axis steps, p + d a non-member or outside the grid
+ *     offset 88  int64     euler     the Euler characteristic of C, by the connectivity of the labelling (so that each cell lies in one component):
+ *         connectivity 26   of the complex of closed unit cubes of C: #corners - #edges + #faces - #cubes, a lattice corner, edge or face
+ *                           counting iff at least one of the 8, 4 or 2 voxels round it is in C.  (All members round one cell are mutually
+ *                           26-adjacent.)  For of = DXV_COMP_SOLID record 0 is the Euler number of the solid, the invariant dxv_thin keeps.
+ *         connectivity 6    v - e + f - c: v = |C|, e the 6-adjacent pairs inside C, f the axis-aligned 2 x 2 x 1 squares inside C, c the
+ *                           2 x 2 x 2 blocks inside C.  (Every such cell is 6-connected.)
+ * A box has euler 1, a hollow box 2, a box with a through tunnel 0, under both.  No sum overflows for N <= 1624, the bound of the labelling:
+ * the largest, a sum of ix^2, stays below 1624^5 ~ 1.13e16 < 2^63.  All measures are integers and nothing is left to choice: the device's
+ * table equals a restatement byte for byte.
+ * dxv_measure_async -- ENQUEUED on the frame's stream behind whatever it holds; returns without waiting and reads nothing back (K is known
+ * from the labelling).  One pass over the labelling's member mask; the grid, the labels and the component table are read, never written.
+ *  - The host waits only under dxv_render_async's rule; a pending fill or thin is settled first.
+ *  - Checked on the host before anything is enqueued, each an error with a message: the frame has been launched (the whole grid); it has a
+ *    current labelling.
+ *  - The table belongs to the frame: frames measure side by side.  dxv_trim keeps it, as it keeps labels; a measure after dxv_trim packs the
+ *    member mask again from the grid.
+ *  - The measure is STALE exactly when its labelling is -- the frame was launched, filled, morphed, thinned, expanded or selected again --
+ *    and once the frame is labelled again: pointer, size and download then fail with a message.
+ *  - Option events = 1 (default): bracketed by the frame's own two events; dxv_measure_ms reads them at the frame's dxv_sync.
+ * dxv_measure -- the same + dxv_sync. */
+DXV_API int dxv_measure_async(dxv_ctx* ctx);
+DXV_API int dxv_measure(dxv_ctx* ctx);
+/* The table on the device (valid after dxv_sync or on the frame's stream) and its size, (K + 1) * 96 bytes.  NULL / 0 with a message before
+ * the frame's first measure or when it is stale. */
+DXV_API const void* dxv_measure_table_device_ptr(const dxv_ctx* ctx);
+DXV_API size_t dxv_measure_table_bytes(const dxv_ctx* ctx);
+/* Copies it to the host (bytes must be the size above); synchronises the frame first. */
+DXV_API int dxv_measure_table_download(dxv_ctx* ctx, void* host, size_t bytes);
+/* Device time of the selected frame's last measure in milliseconds (HIP events), read at the frame's dxv_sync: 0 before that, and under
+ * option events = 0. */
+DXV_API int dxv_measure_ms(dxv_ctx* ctx, float* ms);
 /* dxv_components_select_async -- the selected frame's grid edited IN PLACE from its current labels; ENQUEUED on the frame's stream behind
  * whatever it holds, returns without waiting.  A component is kept under
  *     DXV_SELECT_LARGEST     it has the most voxels; ties go to the smaller number.  arg must be 0.

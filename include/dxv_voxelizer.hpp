@@ -246,6 +246,62 @@ public:
 	}
 	bool SelectInfo(uint32_t& kept, uint32_t& dropped, uint64_t& voxelsChanged) { return m_ctx && dxv_components_select_info(m_ctx, &kept, &dropped, &voxelsChanged) == 0; }
 
+	// The integral measures of the selected frame's current labelling (dxv_measure / dxv_measure_async; include/dxv.h has the rule): a 96-byte
+	// record per component and record 0 for all of them together.  MassProperties turns a record into volume, centroid (at voxel centres),
+	// area and the inertia tensor about the centroid, in voxel units at unit density; the central second moments are formed exactly in 128 bits
+	// before the one division.  Betti gives the pieces, handles and cavities of the solid as a complex of closed unit cubes: it labels the empty
+	// space (6), then the solid (26), measures it, and leaves that labelling and its measure current.
+	struct MeasureRecord { uint64_t voxels, sum[3], sum2[3], prod[3], faces; int64_t euler; };
+	struct MassRecord { double volume, centroid[3], area, inertia[3][3]; };
+	bool Measure(bool sync = true) { return m_ctx && (sync ? dxv_measure(m_ctx) : dxv_measure_async(m_ctx)) == 0; }
+	const void* DeviceMeasureTable() const { return m_ctx ? dxv_measure_table_device_ptr(m_ctx) : nullptr; }
+	bool MeasureTable(std::vector<MeasureRecord>& table)
+	{
+		if (!m_ctx) return setError("MeasureTable before Init");
+		static_assert(sizeof(MeasureRecord) == 96, "a row of the table is 96 bytes");
+		const size_t bytes = dxv_measure_table_bytes(m_ctx);
+		if (!bytes) return false;
+		table.resize(bytes / sizeof(MeasureRecord));
+		return dxv_measure_table_download(m_ctx, table.data(), bytes) == 0;
+	}
+	bool MeasureMs(float& ms) { return m_ctx && dxv_measure_ms(m_ctx, &ms) == 0; }
+	static MassRecord MassProperties(const MeasureRecord& r)
+	{
+		typedef unsigned __int128 u128;
+		MassRecord out = {};
+		out.volume = (double)r.voxels;
+		out.area = (double)r.faces;
+		if (!r.voxels) return out;
+		const u128 V = r.voxels;
+		u128 central[3];                                                   // V * the sum of (x - mean)^2 >= 0, exact
+		for (int a = 0; a < 3; ++a) {
+			central[a] = V * r.sum2[a] - (u128)r.sum[a] * r.sum[a];
+			out.centroid[a] = (double)(2 * (u128)r.sum[a] + V) / (double)(2 * V);
+		}
+		for (int a = 0; a < 3; ++a) {
+			const int b = (a + 1) % 3, c = (a + 2) % 3;
+			out.inertia[a][a] = (double)(6 * (central[b] + central[c]) + V * V) / (double)(6 * V);
+			const u128 pos = V * r.prod[a], neg = (u128)r.sum[a] * r.sum[b];   // prod[a] pairs axis a with axis a + 1: xy, yz, zx
+			out.inertia[a][b] = out.inertia[b][a] = pos >= neg ? -((double)(pos - neg) / (double)V) : (double)(neg - pos) / (double)V;
+		}
+		return out;
+	}
+	bool Betti(uint32_t& b0, uint32_t& b1, uint32_t& b2)
+	{
+		if (!m_ctx) return setError("Betti before Init");
+		if (dxv_components(m_ctx, DXV_COMP_EMPTY, 6)) return false;
+		std::vector<ComponentRecord> empty(dxv_components_table_bytes(m_ctx) / sizeof(ComponentRecord));
+		std::vector<MeasureRecord> table;
+		if (dxv_components_table_download(m_ctx, empty.data(), empty.size() * sizeof(ComponentRecord))) return false;
+		uint32_t cavities = 0, pieces = 0;
+		for (const ComponentRecord& r : empty) cavities += (r.flags & 1u) ? 0u : 1u;
+		int of = 0, connectivity = 0;
+		if (dxv_components(m_ctx, DXV_COMP_SOLID, 26) || !ComponentsInfo(pieces, of, connectivity) || !Measure() || !MeasureTable(table)) return false;
+		b0 = pieces; b2 = cavities;
+		b1 = (uint32_t)((int64_t)pieces + (int64_t)cavities - table[0].euler);
+		return true;
+	}
+
 	// The exterior flood fill of that frame's whole grid, in place (dxv_fill / dxv_fill_async): DXV_FILL_SOLID leaves the walls and everything
 	// they enclose, DXV_FILL_INTERIOR the enclosed voxels alone.  Voxelize(gridDim, SURFACE) && Fill() is the solid of a mesh whose
 	// normals and watertightness cannot be trusted.  Refers to the frame last selected; sync = false only enqueues (WaitFrame reports).
