@@ -121,6 +121,15 @@ SYMBOLS = {
     "dxv_measure_table_bytes": (C.c_size_t, [C.c_void_p]),
     "dxv_measure_table_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "dxv_measure_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "dxv_thickness_async": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
+    "dxv_thickness": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
+    "dxv_thickness_device_ptr": (C.c_void_p, [C.c_void_p]),
+    "dxv_thickness_bytes": (C.c_size_t, [C.c_void_p]),
+    "dxv_thickness_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_thickness_histogram_bytes": (C.c_size_t, [C.c_void_p]),
+    "dxv_thickness_histogram_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_thickness_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "dxv_thickness_stage_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "dxv_components_select_async": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
     "dxv_components_select": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
     "dxv_components_select_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),

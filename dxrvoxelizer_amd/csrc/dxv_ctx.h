@@ -139,7 +139,9 @@ struct Timer { hipEvent_t e0 = nullptr, e1 = nullptr; bool armed = false; float 
 // ... and what a frame times.  The launch's pair and its queue build's are here for their events alone: when they are read is the launch's
 // business (Frame::timed, lastRebuilt -> voxelize_ms, plan_ms), so they stand in front of kTimerFirstOperator: a synchronisation of the frame
 // reads the armed pairs from there on (sync_launch), and a new operator's slot goes behind it.
-enum TimerUse { kTimerLaunch, kTimerQueue, kTimerRender, kTimerDistance, kTimerMeshDistance, kTimerFill, kTimerIso, kTimerOctree, kTimerComponents, kTimerMorph, kTimerThin, kTimerMeasure, kTimers,
+enum TimerUse { kTimerLaunch, kTimerQueue, kTimerRender, kTimerDistance, kTimerMeshDistance, kTimerFill, kTimerIso, kTimerOctree, kTimerComponents, kTimerMorph, kTimerThin, kTimerMeasure, kTimerThickness,
+                kTimerThickStage0, kTimerThickStageLast = kTimerThickStage0 + dxv::THICK_STAGES - 1,     // the six stages of a thickness, each a pair of its own
+                kTimers,
                 kTimerFirstOperator = kTimerRender };
 
 struct dxv_ctx {
@@ -302,6 +304,15 @@ struct dxv_ctx {
         uint32_t thinIterations = 0;     // iterations of the frame's last thin so far, the confirming one included
         uint64_t thinRemoved = 0;        // voxels it removed, as of the frame's last synchronisation
         bool thinConverged = false;      // it stopped at an iteration that removed nothing (false: max_iterations stopped it first, or none yet)
+        // local thickness (thickness.hip; dxv_thickness_async): the map and the histogram of the frame's grid and the scratch of their making (two
+        // fields, a byte per voxel, the fields' passes: 15 bytes per voxel), the frame's own; the scratch goes with dxv_trim, map and histogram stay
+        DevBuf<uint32_t> thick;          // (cap: voxels)
+        DevBuf<unsigned long long> thickHist;   // (cap: bins)
+        DevBuf<uint8_t> thickScratch;    // (cap: bytes) thickness_scratch_bytes
+        uint32_t thickDim = 0, thickCap = 0;    // grid side and cap_sq of the frame's last map (0: none yet) ...
+        uint64_t thickVersion = 0;       // ... and the grid version it was made of
+        bool thickPending = false;       // its four counters are on their way into page-locked words: the frame's next synchronisation reads them
+        uint64_t thickCentres = 0, thickItems = 0, thickTested = 0, thickSent = 0;   // of the frame's last thickness, as of its last synchronisation
     };
     Frame frames[DXV_FRAME_COUNT];
     uint32_t cur = 0;                    // dxv_set_frame
@@ -337,6 +348,7 @@ struct dxv_ctx {
         unsigned long long compSel[DXV_FRAME_COUNT][4];   // kept, dropped, voxels changed and the largest component's key of a frame's last select
         unsigned long long morphCount[DXV_FRAME_COUNT][2]; // voxels set and voxels cleared by a frame's last morph
         dxv::ThinControl thinCtl[DXV_FRAME_COUNT];       // the control block of a frame's last thin batch and the voxels removed so far
+        unsigned long long thickCount[DXV_FRAME_COUNT][4]; // centres painted, work items, voxels tested and atomics sent of a frame's last thickness
     };
     Pinned* pin = nullptr;
     hipEvent_t evList[4] = {};       // around the counting pass, around the rest of the build
@@ -479,7 +491,7 @@ int check_grid(dxv_ctx* c, const char* who, uint32_t N, bool orZero = false);
 int check_slab(dxv_ctx* c, const char* who, uint32_t N, uint32_t z0, uint32_t nz);
 int check_interleave(dxv_ctx* c, const char* who, uint32_t N, uint32_t rank, uint32_t world, uint32_t zblock);
 // dxv_products.hip
-void read_products(dxv_ctx* c, uint32_t i);                // the counters of the frame's last select and morph, once its stream has been waited for
+void read_products(dxv_ctx* c, uint32_t i);                // the counters of the frame's last select, morph and thickness, once its stream has been waited for
 int settle_fill(dxv_ctx* c, uint32_t i);                   // the verdict of the frame's last fill batch; further batches until one has converged
 int settle_thin(dxv_ctx* c, uint32_t i);                   // ... of the frame's last thin batch; further batches until the fixed point or max_iterations
 int settle_expand(dxv_ctx* c, uint32_t i);                 // the verdict of an expansion from a caller's tree

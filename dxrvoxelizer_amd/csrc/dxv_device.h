@@ -332,6 +332,30 @@ struct ThinControl {
 size_t thin_scratch_bytes(uint32_t N);
 hipError_t launch_thin(uint8_t* grid, uint32_t N, int kind, uint8_t* scratch, uint32_t iterations, bool first, hipStream_t s);
 
+// thickness.hip -- the exact local thickness of a whole N^3 grid (dxv_thickness.h): W = N^3 uint32, hist = cap + 1 uint64, both the caller's;
+// everything else in scratch = thickness_scratch_bytes(N), laid out by thickness_layout.  Six stages, enqueued one by one so that the caller can
+// put its events between them; nothing is read back: thickness_counters points at {centres painted, work items, voxels the paint tested, atomics it
+// sent} in the scratch, the first two valid behind the select.  The grid is only read.
+struct ThickParams {
+    uint32_t N;
+    int of;                           // DXV_COMP_SOLID / DXV_COMP_EMPTY
+    uint32_t cap, cull;               // cap_sq; option thickcull
+    uint32_t count;                   // 1: the paint counts what it tests and sends (option thickstages)
+    uint32_t* W;
+    unsigned long long* hist;
+    int32_t *F, *G;                   // thickness_layout fills these and the ones below: the grid's field; E's field, then Top's
+    uint32_t* B;                      // a byte per voxel: E, then Top, then the work items of the voxel as a centre
+    unsigned long long* sums;         // per block of 1024 voxels {centres, items} in front of it, then the two totals and the paint's two counters
+    uint8_t* passes;                  // distance_scratch_bytes(N)
+    uint32_t *centres, *firstItem;    // the compacted centres (in G) and every centre's first item within its block (in the passes' scratch)
+};
+enum { THICK_STAGE_FIELD, THICK_STAGE_TOP, THICK_STAGE_CULL, THICK_STAGE_SELECT, THICK_STAGE_PAINT, THICK_STAGE_HISTOGRAM, THICK_STAGES };
+size_t thickness_scratch_bytes(uint32_t N);
+size_t thickness_histogram_bytes(uint32_t cap);
+void thickness_layout(uint8_t* scratch, uint32_t N, ThickParams& p);
+const unsigned long long* thickness_counters(const ThickParams& p);
+hipError_t launch_thickness_stage(const uint8_t* grid, const ThickParams& p, int stage, hipStream_t s);
+
 // raycast.hip
 struct RayCastCB;
 hipError_t launch_raycast(const RayCastCB& cb, const uint8_t* grid, uint32_t N, uint32_t width, uint32_t height,

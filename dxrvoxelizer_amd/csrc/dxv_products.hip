@@ -1,6 +1,6 @@
 // dxv_products.hip -- what is made of a frame's grid, and what edits it in place: distance field, mesh distance field, isosurface, octree and
 // its expansion, components, their measures and select, fill, morph, thin -- the host side of each (the kernels: distance.hip, mesh_distance.hip,
-// isosurface.hip, octree.hip, components.hip, measure.hip, fill.hip, morph.hip, thin.hip), the accessors of what they made, and their halves of a frame's synchronisation.
+// isosurface.hip, octree.hip, components.hip, measure.hip, thickness.hip, fill.hip, morph.hip, thin.hip), the accessors of what they made, and their halves of a frame's synchronisation.
 #include "dxv_ctx.h"
 #include "dxv_mesh_distance.h"
 #include "dxv_fill.h"
@@ -10,6 +10,7 @@
 #include "dxv_measure.h"
 #include "dxv_morph.h"
 #include "dxv_thin.h"
+#include "dxv_thickness.h"
 
 using namespace dxv;
 using namespace dxvhost;
@@ -63,6 +64,13 @@ void read_products(dxv_ctx* c, uint32_t i)
         f.morphSet = c->pin->morphCount[i][0];
         f.morphCleared = c->pin->morphCount[i][1];
         f.morphPending = false;
+    }
+    if (f.thickPending) {                                               // the counters of the frame's last thickness
+        f.thickCentres = c->pin->thickCount[i][0];
+        f.thickItems = c->pin->thickCount[i][1];
+        f.thickTested = c->pin->thickCount[i][2];
+        f.thickSent = c->pin->thickCount[i][3];
+        f.thickPending = false;
     }
 }
 
@@ -718,6 +726,113 @@ int dxv_measure_table_download(dxv_ctx* c, void* host, size_t bytes)
 }
 
 int dxv_measure_ms(dxv_ctx* c, float* ms) { return timer_ms(c, "dxv_measure_ms", kTimerMeasure, ms); }
+
+// The local thickness of the selected frame's grid (thickness.hip; dxv_thickness.h has the rule's routines), enqueued on the frame's stream behind
+// whatever it holds, under dxv_render_async's host-wait rule.  A fixed chain of kernels that read their counts from device memory: nothing is
+// read back, the four counters go into page-locked words and are read where the frame is next synchronised.  Map, histogram and scratch are the
+// frame's own; the field of the grid is made into the scratch, never into the frame's distance field.
+int dxv_thickness_async(dxv_ctx* c, int of, uint32_t cap_sq)
+{
+    if (!c) return 1;
+    if (of != DXV_COMP_SOLID && of != DXV_COMP_EMPTY) return fail(c, "dxv_thickness: unknown kind %d (DXV_COMP_SOLID = 0, DXV_COMP_EMPTY = 1)", of);
+    if (cap_sq < kThickMinCapSq || cap_sq > kThickMaxCapSq) return fail(c, "dxv_thickness: cap_sq %u is not in [%u, %u]", cap_sq, kThickMinCapSq, kThickMaxCapSq);
+    if (check_whole_grid(c, "dxv_thickness")) return 1;
+    Frame& f = cur_frame(c);
+    const uint32_t N = f.grid_dim;
+    if (N > kThickMaxN) return fail(c, "dxv_thickness: a grid of %u^3 voxels; at most %u^3 (a centre's linear index must fit 30 bits)", N, kThickMaxN);
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (settle_frame_launch(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    const size_t voxels = (size_t)N * N * N, scratch = thickness_scratch_bytes(N);
+    f.thickVersion = 0; f.thickDim = 0;
+    DXV_HIP(c, f.thick.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
+    DXV_HIP(c, f.thickHist.reserve(kThickMaxCapSq + 1u, align256(thickness_histogram_bytes(kThickMaxCapSq)), fs));
+    DXV_HIP(c, f.thickScratch.reserve(scratch, scratch, fs));
+    ThickParams p{};
+    p.of = of; p.cap = cap_sq; p.cull = (uint32_t)c->opt.thickcull; p.count = c->opt.thickstages ? 1u : 0u; p.W = f.thick.p; p.hist = f.thickHist.p;
+    thickness_layout(f.thickScratch.p, N, p);
+    const bool timed = c->opt.events != 0, staged = timed && c->opt.thickstages != 0;      // (the stages' own pairs only for a caller that measures)
+    DXV_HIP(c, timer_begin(f.timers[kTimerThickness], timed, fs));
+    for (int stage = 0; stage < THICK_STAGES; ++stage) {
+        Timer& t = f.timers[kTimerThickStage0 + stage];
+        if (!staged) t.ms = 0.0f;
+        DXV_HIP(c, timer_begin(t, staged, fs));
+        DXV_HIP(c, launch_thickness_stage(f.grid.p, p, stage, fs));
+        DXV_HIP(c, timer_end(t, staged, fs));
+    }
+    DXV_HIP(c, timer_end(f.timers[kTimerThickness], timed, fs));
+    DXV_HIP(c, hipMemcpyAsync(c->pin->thickCount[c->cur], thickness_counters(p), sizeof(c->pin->thickCount[c->cur]), hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    f.thickPending = true;
+    f.thickDim = N; f.thickCap = cap_sq; f.thickVersion = f.gridVersion;
+    return 0;
+}
+
+int dxv_thickness(dxv_ctx* c, int of, uint32_t cap_sq)
+{
+    if (dxv_thickness_async(c, of, cap_sq)) return 1;
+    return dxv_sync(c);
+}
+
+// whether the frame has a thickness map to hand out: 0, or 1 with the reason as the message
+static int current_thickness(const dxv_ctx* c, const char* who)
+{
+    const Frame& f = c->frames[c->cur];
+    dxv_ctx* w = const_cast<dxv_ctx*>(c);                               // (the message is the one thing an accessor writes)
+    if (!f.thickDim || !f.thick.p) return fail(w, "%s: frame %u has no thickness map yet (call dxv_thickness first)", who, c->cur);
+    if (f.thickVersion != f.gridVersion)
+        return fail(w, "%s: frame %u was launched or edited again since its thickness map was made: map and histogram are stale", who, c->cur);
+    return 0;
+}
+
+const void* dxv_thickness_device_ptr(const dxv_ctx* c)
+{
+    if (!c || current_thickness(c, "dxv_thickness_device_ptr")) return nullptr;
+    return c->frames[c->cur].thick.p;
+}
+size_t dxv_thickness_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame& f = c->frames[c->cur];
+    return f.thickDim && f.thickVersion == f.gridVersion ? (size_t)f.thickDim * f.thickDim * f.thickDim * sizeof(uint32_t) : 0;
+}
+int dxv_thickness_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || current_thickness(c, "dxv_thickness_download")) return 1;
+    return download_current(c, "dxv_thickness_download", cur_frame(c).thick.p, dxv_thickness_bytes(c), host, bytes);
+}
+size_t dxv_thickness_histogram_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame& f = c->frames[c->cur];
+    return f.thickDim && f.thickVersion == f.gridVersion ? thickness_histogram_bytes(f.thickCap) : 0;
+}
+int dxv_thickness_histogram_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || current_thickness(c, "dxv_thickness_histogram_download")) return 1;
+    return download_current(c, "dxv_thickness_histogram_download", cur_frame(c).thickHist.p, dxv_thickness_histogram_bytes(c), host, bytes);
+}
+
+int dxv_thickness_info(dxv_ctx* c, float* ms, uint64_t* centres_painted, uint64_t* work_items)
+{
+    if (!c) return 1;
+    const Frame& f = cur_frame(c);
+    if (ms) *ms = f.timers[kTimerThickness].ms;
+    if (centres_painted) *centres_painted = f.thickCentres;
+    if (work_items) *work_items = f.thickItems;
+    return 0;
+}
+
+int dxv_thickness_stage_info(dxv_ctx* c, float ms[6], uint64_t* voxels_tested, uint64_t* atomics_sent)
+{
+    if (!c) return 1;
+    if (!ms) return fail(c, "dxv_thickness_stage_info: ms is NULL");
+    const Frame& f = cur_frame(c);
+    for (int stage = 0; stage < THICK_STAGES; ++stage) ms[stage] = f.timers[kTimerThickStage0 + stage].ms;
+    if (voxels_tested) *voxels_tested = f.thickTested;
+    if (atomics_sent) *atomics_sent = f.thickSent;
+    return 0;
+}
 
 // The selected frame's grid edited from its labels (components.hip: k_comp_keep, k_comp_edit), in place, enqueued on the frame's stream behind
 // whatever it holds -- under dxv_render_async's host-wait rule and dxv_fill_async's rules for the grid.  The four counters go into page-locked

@@ -73,6 +73,14 @@ def mass_properties(table):
     return out
 
 
+def thickness_voxels(field):
+    """A thickness map (ThicknessField: squared radii) in voxels, float32: 2 sqrt(W) - 1 on members, 0 elsewhere -- the diameter of the largest
+    voxel-centred ball through the voxel.  A slab k voxels thick reads 2 ceil(k / 2) - 1: balls are centred on voxels, so even thicknesses read
+    as the next odd one."""
+    W = np.asarray(field)
+    return np.where(W > 0, np.float32(2) * np.sqrt(W.astype(np.float32)) - np.float32(1), np.float32(0)).astype(np.float32)
+
+
 class Voxelizer:
     """bool-returning calls of the reference become exceptions (DxvError) here."""
 
@@ -592,6 +600,62 @@ class Voxelizer:
         self._check(self._lib.dxv_components(self._ctx, COMP_SOLID, 26))
         b0 = self.components_info()[0]
         return betti_numbers(b0, b2, int(self.Measure()[0]["euler"]))
+
+    # ---- the local thickness of the frame's grid ------------------------------------------------------
+    def Thickness(self, of=COMP_SOLID, capSq=4096, sync=True, frameIndex=None):
+        """The exact local thickness of the selected frame's whole grid on the device (dxv_thickness / dxv_thickness_async; include/dxv.h has the
+        rule): per member voxel -- of = COMP_SOLID the non-zero voxels, COMP_EMPTY the zero ones -- the largest R(c) = min(D2(c), capSq) of a
+        member c whose open ball { |p - c|^2 < R(c) } holds the voxel, 0 for the others; 2 <= capSq <= 4096.  The minimum wall of a part, and
+        with COMP_EMPTY channel widths and pore sizes.  The grid and the frame's other products stay as they are.  sync=True returns
+        ThicknessField(); sync=False only enqueues it."""
+        if frameIndex is not None:
+            self.SetFrame(frameIndex)
+        fn = self._lib.dxv_thickness if sync else self._lib.dxv_thickness_async
+        self._check(fn(self._ctx, int(of), int(capSq)))
+        return self.ThicknessField() if sync else True
+
+    def ThicknessField(self):
+        """numpy copy uint32 [N, N, N] (z, y, x) of the selected frame's thickness map, squared radii (dxv_thickness_download; synchronises
+        the frame); thickness_voxels turns it into voxels."""
+        nbytes = self._lib.dxv_thickness_bytes(self._ctx)
+        if not nbytes:
+            self._lib.dxv_thickness_device_ptr(self._ctx)              # (sets the message: none yet, or stale)
+            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
+        n = round((nbytes // 4) ** (1.0 / 3.0))
+        out = np.empty((n, n, n), np.uint32)
+        self._check(self._lib.dxv_thickness_download(self._ctx, out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+    def ThicknessHistogram(self):
+        """numpy copy uint64 [capSq + 1] of the selected frame's thickness histogram: bin v the voxels with W == v, bin 0 those that are no
+        members (dxv_thickness_histogram_download; synchronises the frame).  Its first non-zero bin above 0 is the minimum wall."""
+        nbytes = self._lib.dxv_thickness_histogram_bytes(self._ctx)
+        if not nbytes:
+            self._lib.dxv_thickness_device_ptr(self._ctx)
+            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
+        out = np.empty(nbytes // 8, np.uint64)
+        self._check(self._lib.dxv_thickness_histogram_download(self._ctx, out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+    def thickness_device_ptr(self):
+        """Device pointer of the selected frame's thickness map, 4 * N^3 bytes, for consumers on the GPU."""
+        ptr = self._lib.dxv_thickness_device_ptr(self._ctx)
+        if not ptr:
+            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
+        return ptr
+
+    def ThicknessInfo(self):
+        """(ms, centres_painted, work_items) of the selected frame's last thickness as of its last Sync (dxv_thickness_info)."""
+        ms, centres, items = C.c_float(), C.c_uint64(), C.c_uint64()
+        self._check(self._lib.dxv_thickness_info(self._ctx, C.byref(ms), C.byref(centres), C.byref(items)))
+        return ms.value, centres.value, items.value
+
+    def thickness_stage_info(self):
+        """({stage: ms}, voxels_tested, atomics_sent) of the selected frame's last thickness as of its last Sync (dxv_thickness_stage_info): the
+        six stages' device times, the voxels the paint loaded and compared, the atomic maxima it sent (which vary from run to run)."""
+        ms, tested, sent = (C.c_float * 6)(), C.c_uint64(), C.c_uint64()
+        self._check(self._lib.dxv_thickness_stage_info(self._ctx, ms, C.byref(tested), C.byref(sent)))
+        return dict(zip(("field", "top", "cull", "select", "paint", "histogram"), (float(m) for m in ms))), tested.value, sent.value
 
     def SelectComponents(self, rule, arg=0, sync=True):
         """Edit the selected frame's grid in place from its current labels (dxv_components_select / _async): the voxels of every component

@@ -466,9 +466,9 @@ enum {
  *    page-locked block that is read where the frame is next synchronised, and that synchronisation enqueues further batches from the bit masks
  *    kept in the frame's scratch until one confirms.  After dxv_sync the grid is always exact; until then the frame counts as one that can
  *    still report something: dxv_render_async, dxv_distance_async, dxv_fill_async, dxv_morph_async, dxv_components_async, dxv_octree_async,
- *    dxv_isosurface_async, dxv_stream_wait_frame, dxv_grid_* and a second dxv_thin_async settle a pending thin first.  The next dxv_voxelize*
- *    simply overwrites the grid.
- *  - Everything a morph makes stale is stale after a thin: distance field, mesh-distance sign, isosurface, octree, components.  The texel
+ *    dxv_isosurface_async, dxv_thickness_async, dxv_stream_wait_frame, dxv_grid_* and a second dxv_thin_async settle a pending thin first.  The
+ *    next dxv_voxelize* simply overwrites the grid.
+ *  - Everything a morph makes stale is stale after a thin: distance field, mesh-distance sign, isosurface, octree, components, thickness.  The texel
  *    image is not touched.
  *  - The scratch (four bit masks, about 3 1/8 bits per voxel) belongs to the frame: frames thin side by side.  dxv_trim gives it back.
  * dxv_thin -- the same + dxv_sync. */
@@ -741,6 +741,57 @@ DXV_API int dxv_components_select(dxv_ctx* ctx, int rule, uint32_t arg);
  * (any pointer may be NULL). */
 DXV_API int dxv_components_select_info(dxv_ctx* ctx, uint32_t* kept, uint32_t* dropped, uint64_t* voxels_changed);
 
+/* Local thickness: how thick is the part HERE (no reference counterpart).  dxv_distance gives a voxel's depth -- a voxel at the surface of a
+ * thick slab has depth 1 -- and dxv_morph(OPEN, r2) says whether a voxel lies in a part at least so thick for ONE radius; this operator gives,
+ * per voxel, the largest ball inside the part that reaches the voxel: the minimum wall of a part to print or cast, the necks where it would
+ * break, the radius along a dxv_thin skeleton, and, taken of the EMPTY space, channel widths and pore sizes.
+ * Input: the WHOLE grid of the selected frame's last launch, in any mode.  Bytes written through dxv_grid_device_ptr count too.  solid(p) iff
+ * byte(p) != 0.  Only voxels inside the grid exist, as for dxv_distance and dxv_morph.
+ * of = DXV_COMP_SOLID (0) or DXV_COMP_EMPTY (1) picks the members M; cap_sq is an integer, 2 <= cap_sq <= 4096.  Integers only:
+ *     D2(c) = min over voxels q of the grid, q not in M, of |c - q|^2      for c in M   (dxv_distance's d2; no such q: +infinity)
+ *     R(c)  = min(D2(c), cap_sq)                                            the open ball { p : |p - c|^2 < R(c) } lies inside M
+ *     W(p)  = max { R(c) : c in M, |p - c|^2 < R(c) }                       for p in M;   W(p) = 0 for p not in M
+ * So 1 <= W(p) <= cap_sq on members, and an all-member grid gives cap_sq everywhere.  A second, independent statement of the same rule, with
+ * OPEN(r2) the dxv_morph opening of M and OPEN(0) = M:
+ *     W(p) = 1 + max { r2 in 0 .. cap_sq - 1 : p in OPEN(r2) }
+ * Two things that are NOT true.  Discrete openings are not nested: { W > r2 } contains OPEN(r2) but does not equal it; only
+ * { W == cap_sq } == OPEN(cap_sq - 1) is an equality.  And the capped map is not min(uncapped map, cap_sq): the rule above is the definition.
+ * Output: one uint32 per voxel, element (iz * N + iy) * N + ix like the grid, 4 N^3 bytes; and a histogram of cap_sq + 1 uint64, bin v the
+ * voxels with W == v, bin 0 the voxels that are no members: the thickness (pore size) distribution, its first non-zero bin above 0 the minimum
+ * wall.  A set function of the grid: the device's bytes equal a restatement byte for byte, whatever the order of the atomics.
+ * In voxels: 2 sqrt(W) - 1 on members (the host mirrors' thickness_voxels).  A slab k voxels thick reads 2 ceil(k / 2) - 1: balls are centred on
+ * voxels, so even thicknesses read as the next odd one.
+ * dxv_thickness_async -- ENQUEUED on the frame's stream behind whatever it holds; returns without waiting and reads nothing back: a fixed chain
+ * of kernels whose counts stay in device memory.  The grid is read and none of the frame's other products is written -- a current distance
+ * field stays current and unchanged: the operator makes its fields in its own scratch.
+ *  - The host waits only under dxv_render_async's rule; a pending fill or thin is settled first.
+ *  - Checked on the host before anything is enqueued, each an error with a message: of is one of the two; 2 <= cap_sq <= 4096; the frame has
+ *    been launched; its last launch was the whole grid; grid_dim <= 1024 (a centre's index is kept in 30 bits).
+ *  - Map, histogram and scratch (15 bytes per voxel) belong to the frame: frames run side by side.  dxv_trim gives the scratch back.
+ *  - Map and histogram are STALE once the frame is launched, filled, morphed, thinned, expanded or selected again: pointer, sizes and
+ *    downloads then fail with a message.
+ *  - Option events = 1 (default): bracketed by the frame's own events, read at the frame's dxv_sync.
+ * dxv_thickness -- the same + dxv_sync. */
+DXV_API int dxv_thickness_async(dxv_ctx* ctx, int of, uint32_t cap_sq);
+DXV_API int dxv_thickness(dxv_ctx* ctx, int of, uint32_t cap_sq);
+/* The map on the device (valid after dxv_sync or on the frame's stream) and its size, 4 * grid_dim^3 bytes.  NULL / 0 (the pointer with a
+ * message) before the frame's first thickness or when it is stale. */
+DXV_API const void* dxv_thickness_device_ptr(const dxv_ctx* ctx);
+DXV_API size_t dxv_thickness_bytes(const dxv_ctx* ctx);
+/* Copies it to the host (bytes must be the size above); synchronises the frame first. */
+DXV_API int dxv_thickness_download(dxv_ctx* ctx, void* host, size_t bytes);
+/* The histogram: (cap_sq + 1) * 8 bytes, and its copy to the host under the same rules. */
+DXV_API size_t dxv_thickness_histogram_bytes(const dxv_ctx* ctx);
+DXV_API int dxv_thickness_histogram_download(dxv_ctx* ctx, void* host, size_t bytes);
+/* The selected frame's last thickness as of the frame's last dxv_sync: device time in milliseconds from its first kernel to its histogram (HIP
+ * events, option events = 1; else 0), the centres whose balls were painted voxel by voxel and the work items -- (centre, z slice) pairs -- they
+ * made.  All 0 before the frame's first thickness; any pointer may be NULL. */
+DXV_API int dxv_thickness_info(dxv_ctx* ctx, float* ms, uint64_t* centres_painted, uint64_t* work_items);
+/* ... and, for measurements, under option thickstages = 1 (else all 0): the times of its six stages, each between events of its own -- the grid's field; E, its field and Top; Top's field
+ * (the cull); select, scan and compaction; paint; histogram -- with the voxels the paint loaded and compared and the atomic maxima it sent.
+ * The latter depends on the order the work items ran in and differs from run to run; the two pointers may be NULL. */
+DXV_API int dxv_thickness_stage_info(dxv_ctx* ctx, float ms[6], uint64_t* voxels_tested, uint64_t* atomics_sent);
+
 /* Multi-GPU: the built scene (nodes + triangle data) as one relocatable device blob, so that
  * rank 0 builds once and the host layer broadcasts it (RCCL over xGMI) to the other ranks.
  * export copies the blob into caller-provided DEVICE memory; import adopts a blob from DEVICE
@@ -862,6 +913,11 @@ DXV_API int dxv_get_stats(const dxv_ctx* ctx, dxv_stats* out);
  *                 synchronised.  Same grids.
  *   morphform 0..2  dxv_morph*: 0 (default) = by the radius: bit planes up to radius_sq 1024, above it the distance field of the grid and its
  *                 threshold, per half; 1 / 2 = always the planes / always the field (measurement, cross-check).  Same grids.
+ *   thickcull 0..3  dxv_thickness*: which centres are left out of the paint because their ball cannot raise anything: bit 0 = those whose ball
+ *                 lies inside the capped part, bit 1 = those whose ball lies inside a 26-neighbour's (3, default: both; 0: every centre with
+ *                 2 <= R < cap_sq is painted; measurement, cross-check).  Same map, same histogram.
+ *   thickstages 0|1  dxv_thickness*: 1 = every stage stands between events of its own and the paint counts the voxels it tests and the atomics it
+ *                 sends, for dxv_thickness_stage_info (measurement: twelve more event records per call); 0 (default): neither.  Same map.
  *   mdistwalk 0|1 dxv_mesh_distance*: 1 (default) = nearest-triangle query over the hierarchy; 0 = every triangle for every voxel, the
  *                 on-device cross-check (seconds on large scenes).  Same field.
  *   morton 0|1, region 0..24, subbox 0|1   brick order, bricks per XCD region (log2), partial launch */
@@ -911,7 +967,7 @@ DXV_API int dxv_debug_queue_order(dxv_ctx* ctx, uint64_t out[4]);
 
 /* Give back what the context keeps only to make the next build faster: the list build's scratch (up to 16 GiB per buffer
  * after a 10 M-triangle scene), the LBVH build's scratch when no refit can follow (imported scenes), the memory of prepared queues
- * whose lists are gone, the scratch of the frames' distance fields (the fields stay), of their flood fills, morphs and thins, of their isosurfaces (the
+ * whose lists are gone, the scratch of the frames' distance fields (the fields stay), of their flood fills, morphs, thins and thickness maps (the maps stay), of their isosurfaces (the
  * meshes stay), of their octrees (the nodes stay) and of their connected components (labels and table stay).  Nothing a launch reads. */
 DXV_API int dxv_trim(dxv_ctx* ctx);
 

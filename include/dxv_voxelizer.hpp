@@ -16,6 +16,7 @@
 #pragma once
 #include "dxv.h"
 
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -301,6 +302,31 @@ public:
 		b1 = (uint32_t)((int64_t)pieces + (int64_t)cavities - table[0].euler);
 		return true;
 	}
+
+	// The exact local thickness of the selected frame's whole grid (dxv_thickness / dxv_thickness_async; include/dxv.h has the rule): per member
+	// voxel the squared radius of the largest voxel-centred ball inside the members that holds it, capped at capSq (2 .. 4096); of = DXV_COMP_EMPTY
+	// measures channels and pores.  The grid and the frame's other products stay as they are.  ThicknessVoxels turns a squared radius into
+	// voxels, 2 sqrt(W) - 1: a slab k voxels thick reads 2 ceil(k / 2) - 1, so even thicknesses read as the next odd one.
+	bool Thickness(int of = DXV_COMP_SOLID, uint32_t capSq = 4096, bool sync = true) { return m_ctx && (sync ? dxv_thickness(m_ctx, of, capSq) : dxv_thickness_async(m_ctx, of, capSq)) == 0; }
+	const void* DeviceThickness() const { return m_ctx ? dxv_thickness_device_ptr(m_ctx) : nullptr; }
+	bool ThicknessField(std::vector<uint32_t>& field)
+	{
+		if (!m_ctx) return setError("ThicknessField before Init");
+		const size_t bytes = dxv_thickness_bytes(m_ctx);
+		if (!bytes) return false;
+		field.resize(bytes / sizeof(uint32_t));
+		return dxv_thickness_download(m_ctx, field.data(), bytes) == 0;
+	}
+	bool ThicknessHistogram(std::vector<uint64_t>& histogram)
+	{
+		if (!m_ctx) return setError("ThicknessHistogram before Init");
+		const size_t bytes = dxv_thickness_histogram_bytes(m_ctx);
+		if (!bytes) return false;
+		histogram.resize(bytes / sizeof(uint64_t));
+		return dxv_thickness_histogram_download(m_ctx, histogram.data(), bytes) == 0;
+	}
+	bool ThicknessInfo(float& ms, uint64_t& centresPainted, uint64_t& workItems) { return m_ctx && dxv_thickness_info(m_ctx, &ms, &centresPainted, &workItems) == 0; }
+	static float ThicknessVoxels(uint32_t w) { return w ? 2.0f * sqrtf((float)w) - 1.0f : 0.0f; }
 
 	// The exterior flood fill of that frame's whole grid, in place (dxv_fill / dxv_fill_async): DXV_FILL_SOLID leaves the walls and everything
 	// they enclose, DXV_FILL_INTERIOR the enclosed voxels alone.  Voxelize(gridDim, SURFACE) && Fill() is the solid of a mesh whose
