@@ -130,6 +130,15 @@ SYMBOLS = {
     "dxv_thickness_histogram_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "dxv_thickness_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "dxv_thickness_stage_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "dxv_geodesic_async": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32]),
+    "dxv_geodesic": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32]),
+    "dxv_geodesic_device_ptr": (C.c_void_p, [C.c_void_p]),
+    "dxv_geodesic_bytes": (C.c_size_t, [C.c_void_p]),
+    "dxv_geodesic_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_geodesic_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                    C.POINTER(C.c_uint32)]),
+    "dxv_geodesic_work_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "dxv_geodesic_path": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "dxv_components_select_async": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
     "dxv_components_select": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
     "dxv_components_select_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),

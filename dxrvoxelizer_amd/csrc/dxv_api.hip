@@ -280,6 +280,7 @@ int dxv_trim(dxv_ctx* c)
     for (auto& f : c->frames) f.morphScratch.release();                 // (the masks and planes of a morph: (R + 3) bits per voxel)
     for (auto& f : c->frames) f.thinScratch.release();                  // (the masks of a thin, 3 1/8 bits per voxel: sync_frames has settled every thin)
     for (auto& f : c->frames) f.thickScratch.release();                 // (the fields, bytes and passes of a thickness, 15 bytes per voxel; a frame's map and histogram themselves stay)
+    for (auto& f : c->frames) { f.geoScratch.release(); f.geoSeeds.release(); f.geoPath.release(); }   // (control block, flags and queue of a geodesic, 6 bytes per 8^3 tile, a list's seeds, a path's words; a frame's map itself stays)
     c->specRes = 0;
     if (!c->haveHierarchy) c->scratch = BuildScratch{};                             // (a built scene keeps keys and links: dxv_refit reads them)
     // prepared queues of lists that are gone (their slots keep their memory for the next dxv_prepare_launch of the partition: 8 MB at

@@ -141,6 +141,7 @@ struct Timer { hipEvent_t e0 = nullptr, e1 = nullptr; bool armed = false; float 
 // reads the armed pairs from there on (sync_launch), and a new operator's slot goes behind it.
 enum TimerUse { kTimerLaunch, kTimerQueue, kTimerRender, kTimerDistance, kTimerMeshDistance, kTimerFill, kTimerIso, kTimerOctree, kTimerComponents, kTimerMorph, kTimerThin, kTimerMeasure, kTimerThickness,
                 kTimerThickStage0, kTimerThickStageLast = kTimerThickStage0 + dxv::THICK_STAGES - 1,     // the six stages of a thickness, each a pair of its own
+                kTimerGeodesic,
                 kTimers,
                 kTimerFirstOperator = kTimerRender };
 
@@ -313,6 +314,26 @@ struct dxv_ctx {
         uint64_t thickVersion = 0;       // ... and the grid version it was made of
         bool thickPending = false;       // its four counters are on their way into page-locked words: the frame's next synchronisation reads them
         uint64_t thickCentres = 0, thickItems = 0, thickTested = 0, thickSent = 0;   // of the frame's last thickness, as of its last synchronisation
+        // geodesic distance (geodesic.hip; dxv_geodesic_async): the map of the frame's grid, and the scratch of its making -- control block, live
+        // flags, queue; the seeds of a list; the words of a path --, the frame's own so that frames run side by side; the scratch goes with
+        // dxv_trim, the map stays
+        DevBuf<uint32_t> geo;            // (cap: voxels)
+        DevBuf<uint8_t> geoScratch;      // (cap: bytes) geodesic_scratch_bytes
+        DevBuf<uint32_t> geoSeeds;       // (cap: indices) the seeds of a list
+        DevBuf<uint32_t> geoPath;        // (cap: words) dxv_geodesic_path: length, status, voxel indices
+        std::vector<uint32_t> geoList;   // the caller's list, copied before dxv_geodesic_async returns: what the upload reads
+        uint32_t geoDim = 0;             // grid side of the frame's last map (0: none yet) ...
+        uint64_t geoVersion = 0;         // ... and the grid version it was made of
+        int geoMetric = 0;               // ... DXV_GEO_FACES / DXV_GEO_CHAMFER, for the batches that follow and for the path
+        uint32_t geoLimit = 0;           // ... its limit (0: none)
+        bool geoPending = false;         // a batch is in the stream whose verdict (fixed point or not) nobody has read yet: the frame's next
+                                         // synchronisation reads it and goes on if need be (settle_geodesic)
+        uint32_t geoBatch = 0;           // ... rounds per batch (option georounds as it stood at dxv_geodesic_async)
+        uint32_t geoRounds = 0;          // rounds of the frame's last geodesic so far, the confirming one included
+        uint64_t geoTilesRun = 0;        // ... the tiles its rounds ran, the most of one round, and the rounds with fewer than kGeoSparseTiles
+        uint32_t geoMostLive = 0, geoSparseRounds = 0;
+        uint64_t geoSeedsUsed = 0, geoReached = 0, geoUnreached = 0;    // its tally, as of the frame's last synchronisation
+        uint32_t geoFarthest = 0, geoFarthestVoxel = 0xFFFFFFFFu;
     };
     Frame frames[DXV_FRAME_COUNT];
     uint32_t cur = 0;                    // dxv_set_frame
@@ -349,6 +370,7 @@ struct dxv_ctx {
         unsigned long long morphCount[DXV_FRAME_COUNT][2]; // voxels set and voxels cleared by a frame's last morph
         dxv::ThinControl thinCtl[DXV_FRAME_COUNT];       // the control block of a frame's last thin batch and the voxels removed so far
         unsigned long long thickCount[DXV_FRAME_COUNT][4]; // centres painted, work items, voxels tested and atomics sent of a frame's last thickness
+        dxv::GeoControl geoCtl[DXV_FRAME_COUNT];         // the control block of a frame's last geodesic batch and the tally behind it
     };
     Pinned* pin = nullptr;
     hipEvent_t evList[4] = {};       // around the counting pass, around the rest of the build
@@ -494,6 +516,7 @@ int check_interleave(dxv_ctx* c, const char* who, uint32_t N, uint32_t rank, uin
 void read_products(dxv_ctx* c, uint32_t i);                // the counters of the frame's last select, morph and thickness, once its stream has been waited for
 int settle_fill(dxv_ctx* c, uint32_t i);                   // the verdict of the frame's last fill batch; further batches until one has converged
 int settle_thin(dxv_ctx* c, uint32_t i);                   // ... of the frame's last thin batch; further batches until the fixed point or max_iterations
+int settle_geodesic(dxv_ctx* c, uint32_t i);               // ... of the frame's last geodesic batch; further batches until a round finds nothing live
 int settle_expand(dxv_ctx* c, uint32_t i);                 // the verdict of an expansion from a caller's tree
 // dxv_lists.hip
 struct ListScratchA { DirRecord* rec; uint32_t *counts, *offsets, *pairs, *sums; unsigned long long* total; size_t bytes; };

@@ -356,6 +356,23 @@ void thickness_layout(uint8_t* scratch, uint32_t N, ThickParams& p);
 const unsigned long long* thickness_counters(const ThickParams& p);
 hipError_t launch_thickness_stage(const uint8_t* grid, const ThickParams& p, int stage, hipStream_t s);
 
+// geodesic.hip -- the geodesic distance inside a whole N^3 grid (dxv_geodesic.h): map = N^3 uint32, the caller's; everything else in scratch =
+// geodesic_scratch_bytes(N): the batch's control block -- word k = the live tiles of round k; the batch has reached the fixed point exactly when
+// one of its words is 0 --, the tally {seeds used, reached, unreached, key}, two sets of live flags (a byte per 8^3 tile) and the queue (a word
+// per tile).  launch_geodesic_init: the map's first words and the live flags of round 0 from the grid and the seeds -- `seeds` is a device
+// pointer, N^3 bytes for GEO_SEEDS_MASK, seedCount voxel indices for GEO_SEEDS_LIST.  launch_geodesic_batch: `rounds` rounds (1 .. kGeoMaxRounds),
+// the first of them round `base` of the call, then the tally.  The grid is read by the init alone.
+struct GeoControl {
+    uint32_t live[64];                // (kGeoMaxRounds)
+    unsigned long long tally[4];      // GeoTally
+};
+size_t geodesic_scratch_bytes(uint32_t N);
+hipError_t launch_geodesic_init(const uint8_t* grid, uint32_t N, int of, int seedsKind, const void* seeds, uint32_t seedCount, uint32_t* map, uint8_t* scratch, hipStream_t s);
+hipError_t launch_geodesic_batch(uint32_t* map, uint32_t N, int metric, uint32_t limit, uint8_t* scratch, uint32_t rounds, uint32_t base, hipStream_t s);
+// ... and the path from `target` down to a seed, by one wave: out = {voxels on the path, 0 or 1: no neighbour continued it}, then min(length,
+// capacity) voxel indices
+hipError_t launch_geodesic_path(const uint32_t* map, uint32_t N, int metric, uint32_t target, uint32_t* out, uint32_t capacity, hipStream_t s);
+
 // raycast.hip
 struct RayCastCB;
 hipError_t launch_raycast(const RayCastCB& cb, const uint8_t* grid, uint32_t N, uint32_t width, uint32_t height,

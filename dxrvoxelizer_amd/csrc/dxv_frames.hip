@@ -575,6 +575,7 @@ int voxelize_common(dxv_ctx* c, uint32_t N, int mode, uint32_t z0, uint32_t nzLo
     grid_rewritten(f);                                                  // (whatever was made of the grid this launch replaces is stale)
     f.fillPending = false;                                              // (... and a fill of it that has not converged yet is dropped: its batch in the stream ends in front of this launch)
     if (f.thinPending) { f.thinPending = false; f.thinConverged = false; }      // (... and a thin of it likewise: it stopped where that batch ended)
+    f.geoPending = false;                                               // (... and a geodesic map of it: stale from here on, nobody can read it)
     return launch_now(c, c->cur);
 }
 
@@ -593,7 +594,7 @@ static int sync_launch(dxv_ctx* c, uint32_t i)
         DXV_HIP(c, hipStreamSynchronize(fs));
         f.sceneReadPending = false;                                     // (whatever read the scene on this stream has finished)
         for (int u = kTimerFirstOperator; u < kTimers; ++u)
-            if (u != kTimerFill && u != kTimerThin) timer_read(f.timers[u]);    // (the fill's pair is settle_fill's, the thin's settle_thin's: further batches move their second event)
+            if (u != kTimerFill && u != kTimerThin && u != kTimerGeodesic) timer_read(f.timers[u]);    // (the fill's pair is settle_fill's, the thin's settle_thin's, the geodesic's settle_geodesic's: further batches move their second event)
         read_products(c, i);
         // lists this launch was queued behind without waiting for their verdict: withdrawn -> the launch again, through the tree
         if (settle_lists(c)) return 1;
@@ -634,6 +635,7 @@ int sync_frame(dxv_ctx* c, uint32_t i)
     if (sync_launch(c, i)) return 1;
     if (settle_fill(c, i)) return 1;
     if (settle_thin(c, i)) return 1;
+    if (settle_geodesic(c, i)) return 1;
     return settle_expand(c, i);
 }
 
@@ -664,6 +666,7 @@ int settle_frame_launch(dxv_ctx* c)
     if (f.pending && (f.lastCanFail || (f.usedLists && f.listEpochUsed == c->withdrawnEpoch))) return sync_frame(c, c->cur);
     if (f.octExpandPending) return sync_frame(c, c->cur);               // an expansion from a caller's tree whose verdict is not in yet
     if (f.fillPending || f.thinPending) return sync_frame(c, c->cur);   // a fill or a thin whose verdict is not in yet: what is behind it must see the final grid
+    if (f.geoPending) return sync_frame(c, c->cur);                     // a geodesic whose verdict is not in yet: its further batches go in front of whatever comes now
     return 0;
 }
 

@@ -1,6 +1,6 @@
 // dxv_products.hip -- what is made of a frame's grid, and what edits it in place: distance field, mesh distance field, isosurface, octree and
 // its expansion, components, their measures and select, fill, morph, thin -- the host side of each (the kernels: distance.hip, mesh_distance.hip,
-// isosurface.hip, octree.hip, components.hip, measure.hip, thickness.hip, fill.hip, morph.hip, thin.hip), the accessors of what they made, and their halves of a frame's synchronisation.
+// isosurface.hip, octree.hip, components.hip, measure.hip, thickness.hip, geodesic.hip, fill.hip, morph.hip, thin.hip), the accessors of what they made, and their halves of a frame's synchronisation.
 #include "dxv_ctx.h"
 #include "dxv_mesh_distance.h"
 #include "dxv_fill.h"
@@ -11,6 +11,7 @@
 #include "dxv_morph.h"
 #include "dxv_thin.h"
 #include "dxv_thickness.h"
+#include "dxv_geodesic.h"
 
 using namespace dxv;
 using namespace dxvhost;
@@ -139,6 +140,46 @@ int settle_thin(dxv_ctx* c, uint32_t i)
         DXV_HIP(c, launch_thin(f.grid.p, N, f.thinKind, f.thinScratch.p, f.thinInBatch, false, fs));
         if (t.armed) DXV_HIP(c, hipEventRecord(t.e1, fs));
         DXV_HIP(c, hipMemcpyAsync(&c->pin->thinCtl[i], f.thinScratch.p, sizeof(ThinControl), hipMemcpyDeviceToHost, fs));
+        DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+        DXV_HIP(c, hipStreamSynchronize(fs));
+    }
+    timer_read(t);
+    return 0;
+}
+
+// ... and the geodesic's (the stream has been waited for): the verdict of the frame's last geodesic batch, by the fill's discipline.  Word k of the
+// control block is the number of live tiles of round k: a batch all of whose rounds had some has not reached the fixed point, and a further batch
+// -- rounds from the flags the frame's scratch still holds, then the tally again -- is enqueued and waited for.  Every live round but the last
+// lowers at least one word; the guard against a map that never settles is V rounds.
+int settle_geodesic(dxv_ctx* c, uint32_t i)
+{
+    Frame& f = c->frames[i];
+    const hipStream_t fs = frame_stream(c, i);
+    const GeoControl& ctl = c->pin->geoCtl[i];
+    Timer& t = f.timers[kTimerGeodesic];
+    const uint32_t N = f.geoDim;
+    const uint64_t most = f.geoBatch ? (uint64_t)N * N * N / f.geoBatch + 2u : 0u;
+    for (uint64_t batch = 0; f.geoPending; ++batch) {
+        uint32_t live = 0;
+        while (live < f.geoBatch && ctl.live[live]) ++live;
+        for (uint32_t k = 0; k < live; ++k) {                           // what the batch's live rounds ran (dxv_geodesic_work_info)
+            f.geoTilesRun += ctl.live[k];
+            if (ctl.live[k] > f.geoMostLive) f.geoMostLive = ctl.live[k];
+            if (ctl.live[k] < kGeoSparseTiles) ++f.geoSparseRounds;
+        }
+        if (live < f.geoBatch) {                                        // round `live` found nothing live: the confirming round
+            GeoTally tally{ctl.tally[0], ctl.tally[1], ctl.tally[2], ctl.tally[3]};
+            f.geoRounds += live + 1u;
+            f.geoSeedsUsed = tally.seeds; f.geoReached = tally.reached; f.geoUnreached = tally.unreached;
+            f.geoFarthest = geo_tally_farthest(tally); f.geoFarthestVoxel = geo_tally_farthest_voxel(tally);
+            f.geoPending = false;
+            break;
+        }
+        f.geoRounds += f.geoBatch;
+        if (batch >= most) return fail(c, "dxv_geodesic: no fixed point after %u rounds on a grid of %u^3 voxels", f.geoRounds, N);
+        DXV_HIP(c, launch_geodesic_batch(f.geo.p, N, f.geoMetric, f.geoLimit, f.geoScratch.p, f.geoBatch, f.geoRounds, fs));
+        if (t.armed) DXV_HIP(c, hipEventRecord(t.e1, fs));
+        DXV_HIP(c, hipMemcpyAsync(&c->pin->geoCtl[i], f.geoScratch.p, sizeof(GeoControl), hipMemcpyDeviceToHost, fs));
         DXV_HIP(c, hipEventRecord(f.evEnd, fs));
         DXV_HIP(c, hipStreamSynchronize(fs));
     }
@@ -831,6 +872,164 @@ int dxv_thickness_stage_info(dxv_ctx* c, float ms[6], uint64_t* voxels_tested, u
     for (int stage = 0; stage < THICK_STAGES; ++stage) ms[stage] = f.timers[kTimerThickStage0 + stage].ms;
     if (voxels_tested) *voxels_tested = f.thickTested;
     if (atomics_sent) *atomics_sent = f.thickSent;
+    return 0;
+}
+
+// The geodesic distance inside the selected frame's grid (geodesic.hip; dxv_geodesic.h has the rule's routines), enqueued on the frame's stream
+// behind whatever it holds, under dxv_render_async's host-wait rule and the fill's discipline: the init, ONE batch of rounds, the tally, the
+// batch's control block into page-locked words, the frame's end event.  Whether the batch reached the fixed point is read where the frame is
+// next synchronised (settle_geodesic).  Everything is refused before anything is enqueued or allocated; the grid is only read.
+int dxv_geodesic_async(dxv_ctx* c, int of, int metric, int seeds_kind, const void* seeds, uint32_t seed_count, uint32_t limit)
+{
+    if (!c) return 1;
+    if (of != DXV_COMP_SOLID && of != DXV_COMP_EMPTY) return fail(c, "dxv_geodesic: unknown kind %d (DXV_COMP_SOLID = 0, DXV_COMP_EMPTY = 1)", of);
+    if (metric != DXV_GEO_FACES && metric != DXV_GEO_CHAMFER) return fail(c, "dxv_geodesic: unknown metric %d (DXV_GEO_FACES = 0, DXV_GEO_CHAMFER = 1)", metric);
+    if (seeds_kind != DXV_GEO_SEEDS_BORDER && seeds_kind != DXV_GEO_SEEDS_LIST && seeds_kind != DXV_GEO_SEEDS_MASK)
+        return fail(c, "dxv_geodesic: unknown seed kind %d (DXV_GEO_SEEDS_BORDER = 0, DXV_GEO_SEEDS_LIST = 1, DXV_GEO_SEEDS_MASK = 2)", seeds_kind);
+    if (seeds_kind == DXV_GEO_SEEDS_LIST && seed_count && !seeds) return fail(c, "dxv_geodesic: a list of %u seeds at NULL", seed_count);
+    if (seeds_kind == DXV_GEO_SEEDS_MASK && !seeds) return fail(c, "dxv_geodesic: the seed mask is NULL");
+    if (check_whole_grid(c, "dxv_geodesic")) return 1;
+    Frame& f = cur_frame(c);
+    const uint32_t N = f.grid_dim;
+    if (N > kGeoMaxN) return fail(c, "dxv_geodesic: a grid of %u^3 voxels; at most %u^3", N, kGeoMaxN);
+    if (!geo_fits(N, metric))
+        return fail(c, "dxv_geodesic: a grid of %u^3 voxels under metric %d: a path of weight %u per step can reach the codes of the map (wmax (N^3 - 1) must stay below 0xFFFFFFFE)", N,
+                    metric, geo_max_weight(metric));
+    const size_t voxels = (size_t)N * N * N;
+    if (seeds_kind == DXV_GEO_SEEDS_LIST) {
+        const uint32_t* list = static_cast<const uint32_t*>(seeds);
+        for (uint32_t k = 0; k < seed_count; ++k)
+            if (list[k] >= voxels) return fail(c, "dxv_geodesic: seed %u is voxel %u, outside the grid of %u^3 = %zu voxels", k, list[k], N, voxels);
+    }
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (seeds_kind == DXV_GEO_SEEDS_MASK) {
+        size_t room = 0;
+        const int r = check_device_range(c, "dxv_geodesic", seeds, voxels, &room);
+        if (r == 2) return fail(c, "dxv_geodesic: the seed mask has %zu bytes from %p on, the grid has %zu voxels", room, seeds, voxels);
+        if (r) return 1;
+    }
+    if (settle_frame_launch(c)) return 1;                               // (a pending fill, thin, expansion or geodesic of the frame first)
+    const hipStream_t fs = cur_stream(c);
+    const size_t scratch = geodesic_scratch_bytes(N);
+    f.geoVersion = 0; f.geoDim = 0;
+    DXV_HIP(c, f.geo.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
+    DXV_HIP(c, f.geoScratch.reserve(scratch, scratch, fs));
+    const void* deviceSeeds = seeds;
+    if (seeds_kind == DXV_GEO_SEEDS_LIST) {
+        // the frame's own copy of the list (no geodesic of the frame is in flight: settle_frame_launch), uploaded from there
+        const uint32_t* list = static_cast<const uint32_t*>(seeds);
+        f.geoList.assign(list, list + seed_count);
+        deviceSeeds = nullptr;
+        if (seed_count) {
+            DXV_HIP(c, f.geoSeeds.reserve(seed_count, align256((size_t)seed_count * sizeof(uint32_t)), fs));
+            DXV_HIP(c, hipMemcpyAsync(f.geoSeeds.p, f.geoList.data(), (size_t)seed_count * sizeof(uint32_t), hipMemcpyHostToDevice, fs));
+            deviceSeeds = f.geoSeeds.p;
+        }
+    }
+    const bool timed = c->opt.events != 0;
+    f.geoMetric = metric; f.geoLimit = limit;
+    f.geoBatch = c->opt.georounds ? (uint32_t)c->opt.georounds : kGeoRoundsDefault;
+    f.geoRounds = 0; f.geoTilesRun = 0; f.geoMostLive = 0; f.geoSparseRounds = 0;
+    DXV_HIP(c, timer_begin(f.timers[kTimerGeodesic], timed, fs));
+    DXV_HIP(c, launch_geodesic_init(f.grid.p, N, of, seeds_kind, deviceSeeds, seed_count, f.geo.p, f.geoScratch.p, fs));
+    DXV_HIP(c, launch_geodesic_batch(f.geo.p, N, metric, limit, f.geoScratch.p, f.geoBatch, 0u, fs));
+    DXV_HIP(c, timer_end(f.timers[kTimerGeodesic], timed, fs));
+    DXV_HIP(c, hipMemcpyAsync(&c->pin->geoCtl[c->cur], f.geoScratch.p, sizeof(GeoControl), hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    f.geoPending = true;
+    f.geoDim = N; f.geoVersion = f.gridVersion;
+    return 0;
+}
+
+int dxv_geodesic(dxv_ctx* c, int of, int metric, int seeds_kind, const void* seeds, uint32_t seed_count, uint32_t limit)
+{
+    if (dxv_geodesic_async(c, of, metric, seeds_kind, seeds, seed_count, limit)) return 1;
+    return dxv_sync(c);
+}
+
+// whether the frame has a geodesic map to hand out: 0, or 1 with the reason as the message
+static int current_geodesic(const dxv_ctx* c, const char* who)
+{
+    const Frame& f = c->frames[c->cur];
+    dxv_ctx* w = const_cast<dxv_ctx*>(c);                               // (the message is the one thing an accessor writes)
+    if (!f.geoDim || !f.geo.p) return fail(w, "%s: frame %u has no geodesic map yet (call dxv_geodesic first)", who, c->cur);
+    if (f.geoVersion != f.gridVersion) return fail(w, "%s: frame %u was launched or edited again since its geodesic map was made: the map is stale", who, c->cur);
+    return 0;
+}
+
+const void* dxv_geodesic_device_ptr(const dxv_ctx* c)
+{
+    if (!c || current_geodesic(c, "dxv_geodesic_device_ptr")) return nullptr;
+    return c->frames[c->cur].geo.p;
+}
+size_t dxv_geodesic_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame& f = c->frames[c->cur];
+    return f.geoDim && f.geoVersion == f.gridVersion ? (size_t)f.geoDim * f.geoDim * f.geoDim * sizeof(uint32_t) : 0;
+}
+int dxv_geodesic_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || current_geodesic(c, "dxv_geodesic_download")) return 1;
+    return download_current(c, "dxv_geodesic_download", cur_frame(c).geo.p, dxv_geodesic_bytes(c), host, bytes);
+}
+
+int dxv_geodesic_info(dxv_ctx* c, float* ms, uint32_t* rounds, uint64_t* seeds_used, uint64_t* reached, uint64_t* unreached, uint32_t* farthest, uint32_t* farthest_voxel)
+{
+    if (!c || current_geodesic(c, "dxv_geodesic_info")) return 1;
+    const Frame& f = cur_frame(c);
+    if (ms) *ms = f.timers[kTimerGeodesic].ms;
+    if (rounds) *rounds = f.geoRounds;
+    if (seeds_used) *seeds_used = f.geoSeedsUsed;
+    if (reached) *reached = f.geoReached;
+    if (unreached) *unreached = f.geoUnreached;
+    if (farthest) *farthest = f.geoFarthest;
+    if (farthest_voxel) *farthest_voxel = f.geoFarthestVoxel;
+    return 0;
+}
+
+int dxv_geodesic_work_info(dxv_ctx* c, uint64_t* tiles_run, uint32_t* most_live_tiles, uint32_t* sparse_rounds)
+{
+    if (!c || current_geodesic(c, "dxv_geodesic_work_info")) return 1;
+    const Frame& f = cur_frame(c);
+    if (tiles_run) *tiles_run = f.geoTilesRun;
+    if (most_live_tiles) *most_live_tiles = f.geoMostLive;
+    if (sparse_rounds) *sparse_rounds = f.geoSparseRounds;
+    return 0;
+}
+
+// The path from `target` down to a seed of the selected frame's current map, synchronous: the frame is synchronised, the target's word is read,
+// one wave walks down (geodesic.hip: k_geo_path) into the frame's own words, and min(length, capacity) of them come back.
+int dxv_geodesic_path(dxv_ctx* c, uint32_t target, uint32_t* host_path, uint32_t capacity, uint32_t* length)
+{
+    if (!c || current_geodesic(c, "dxv_geodesic_path")) return 1;
+    if (!length) return fail(c, "dxv_geodesic_path: length is NULL");
+    if (capacity && !host_path) return fail(c, "dxv_geodesic_path: room for %u voxels at NULL", capacity);
+    Frame& f = cur_frame(c);
+    const uint32_t N = f.geoDim;
+    const size_t voxels = (size_t)N * N * N;
+    if (target >= voxels) return fail(c, "dxv_geodesic_path: target %u is outside the grid of %u^3 = %zu voxels", target, N, voxels);
+    if (dxv_sync(c)) return 1;
+    const hipStream_t fs = cur_stream(c);
+    uint32_t word = 0;
+    DXV_HIP(c, hipMemcpyAsync(&word, f.geo.p + target, sizeof(word), hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipStreamSynchronize(fs));
+    if (word >= kGeoUnreached)
+        return fail(c, "dxv_geodesic_path: target %u holds no distance (%s)", target, word == kGeoNone ? "DXV_GEO_NONE: it is no member" : "DXV_GEO_UNREACHED: no path reaches it");
+    const uint64_t longest = (uint64_t)word / geo_min_weight(f.geoMetric) + 1u;     // (every step lowers the word by the least weight or more)
+    const uint32_t room = (uint64_t)capacity < longest ? capacity : (uint32_t)longest;
+    DXV_HIP(c, f.geoPath.reserve((size_t)room + 2u, align256(((size_t)room + 2u) * sizeof(uint32_t)), fs));
+    DXV_HIP(c, launch_geodesic_path(f.geo.p, N, f.geoMetric, target, f.geoPath.p, room, fs));
+    uint32_t head[2] = {0, 0};
+    DXV_HIP(c, hipMemcpyAsync(head, f.geoPath.p, sizeof(head), hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipStreamSynchronize(fs));
+    if (head[1] || head[0] > longest) return fail(c, "dxv_geodesic_path: no neighbour continues the path after %u voxels from target %u: the map is no fixed point", head[0], target);
+    *length = head[0];
+    const uint32_t give = head[0] < room ? head[0] : room;
+    if (give) {
+        DXV_HIP(c, hipMemcpyAsync(host_path, f.geoPath.p + 2, (size_t)give * sizeof(uint32_t), hipMemcpyDeviceToHost, fs));
+        DXV_HIP(c, hipStreamSynchronize(fs));
+    }
     return 0;
 }
 

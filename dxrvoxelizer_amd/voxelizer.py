@@ -18,6 +18,9 @@ THIN_CURVE, THIN_KERNEL = 0, 1                                      # the kinds 
 ISO_MESH_DISTANCE, ISO_GRID_DISTANCE = 0, 1       # the field an isosurface is taken from (include/dxv.h)
 ISO_SPACE_VOXELS, ISO_SPACE_OBJECT = 0, 1         # ... and the space its vertices are in
 COMP_SOLID, COMP_EMPTY = 0, 1                     # what connected components are taken of (include/dxv.h)
+GEO_FACES, GEO_CHAMFER = 0, 1                     # the metrics of Geodesic (include/dxv.h)
+GEO_SEEDS_BORDER, GEO_SEEDS_LIST, GEO_SEEDS_MASK = 0, 1, 2
+GEO_NONE, GEO_UNREACHED = 0xFFFFFFFF, 0xFFFFFFFE  # ... and the two codes of its map
 SELECT_LARGEST, SELECT_MIN_VOXELS, SELECT_BORDER = 0, 1, 2   # which components SelectComponents keeps
 COMP_RECORD = np.dtype([("first", "<u4"), ("voxels", "<u4"), ("lo", "<u2", (3,)), ("hi", "<u2", (3,)), ("flags", "<u4")])   # a row of the components' table, 24 bytes
 # a row of the measures' table, 96 bytes (include/dxv.h over dxv_measure_async)
@@ -656,6 +659,85 @@ class Voxelizer:
         ms, tested, sent = (C.c_float * 6)(), C.c_uint64(), C.c_uint64()
         self._check(self._lib.dxv_thickness_stage_info(self._ctx, ms, C.byref(tested), C.byref(sent)))
         return dict(zip(("field", "top", "cull", "select", "paint", "histogram"), (float(m) for m in ms))), tested.value, sent.value
+
+    # ---- the geodesic distance inside the frame's grid ---------------------------------------------------
+    def Geodesic(self, of=COMP_SOLID, metric=GEO_CHAMFER, seeds="border", limit=0, sync=True, frameIndex=None):
+        """The geodesic distance inside the selected frame's whole grid on the device (dxv_geodesic / dxv_geodesic_async; include/dxv.h has the
+        rule): per member voxel -- of = COMP_SOLID the non-zero voxels, COMP_EMPTY the zero ones -- the length of the shortest path of member
+        voxels to the nearest seed, GEO_FACES over the 6 face neighbours at weight 1, GEO_CHAMFER over the 26 neighbours at weights 3 / 4 / 5;
+        GEO_NONE on the others, GEO_UNREACHED where no path exists or, with limit != 0, is longer than limit.  seeds: "border"; a 1-D array of
+        voxel indices (iz * N + iy) * N + ix; an [N, N, N] bool / uint8 host array (its non-zero voxels, sent as indices); or a torch uint8 / bool
+        tensor of N^3 elements on the frame's device (read in place, after the tensor's stream has been waited for).  The grid and the frame's
+        other products stay as they are.  sync=True returns GeodesicField(); sync=False only enqueues one batch of rounds."""
+        if frameIndex is not None:
+            self.SetFrame(frameIndex)
+        fn = self._lib.dxv_geodesic if sync else self._lib.dxv_geodesic_async
+        if isinstance(seeds, str):
+            if seeds != "border":
+                raise DxvError(f"Geodesic: unknown seeds {seeds!r} (\"border\", an index array, an [N, N, N] array or a device tensor)")
+            rc = fn(self._ctx, int(of), int(metric), GEO_SEEDS_BORDER, None, 0, int(limit))
+        elif hasattr(seeds, "data_ptr"):                                # a device tensor: a mask read in place
+            import torch
+            if not seeds.is_cuda or seeds.dtype not in (torch.uint8, torch.bool) or not seeds.is_contiguous():
+                raise DxvError("Geodesic: a seed tensor must be a contiguous uint8 or bool tensor on the device")
+            n = self.stats()["grid_dim"]
+            if seeds.numel() != n ** 3:
+                raise DxvError(f"Geodesic: the seed tensor has {seeds.numel()} elements, the grid has {n ** 3} voxels")
+            torch.cuda.current_stream(seeds.device).synchronize()       # (its writer is ordered before the frame's stream reads it)
+            rc = fn(self._ctx, int(of), int(metric), GEO_SEEDS_MASK, C.c_void_p(seeds.data_ptr()), 0, int(limit))
+        else:
+            a = np.asarray(seeds)
+            if a.ndim == 3:
+                a = np.flatnonzero(a)
+            if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+                raise DxvError("Geodesic: a seed index is outside the grid")
+            a = np.ascontiguousarray(a.reshape(-1), np.uint32)
+            rc = fn(self._ctx, int(of), int(metric), GEO_SEEDS_LIST, a.ctypes.data_as(C.c_void_p) if a.size else None, int(a.size), int(limit))
+        self._check(rc)
+        return self.GeodesicField() if sync else True
+
+    def GeodesicField(self):
+        """numpy copy uint32 [N, N, N] (z, y, x) of the selected frame's geodesic map (dxv_geodesic_download; synchronises the frame)."""
+        nbytes = self._lib.dxv_geodesic_bytes(self._ctx)
+        if not nbytes:
+            self._lib.dxv_geodesic_device_ptr(self._ctx)               # (sets the message: none yet, or stale)
+            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
+        n = round((nbytes // 4) ** (1.0 / 3.0))
+        out = np.empty((n, n, n), np.uint32)
+        self._check(self._lib.dxv_geodesic_download(self._ctx, out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+    def geodesic_device_ptr(self):
+        """Device pointer of the selected frame's geodesic map, 4 * N^3 bytes, for consumers on the GPU (exact after Sync)."""
+        ptr = self._lib.dxv_geodesic_device_ptr(self._ctx)
+        if not ptr:
+            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
+        return ptr
+
+    def GeodesicInfo(self):
+        """{ms, rounds, seeds_used, reached, unreached, farthest, farthest_voxel} of the selected frame's last geodesic as of its last Sync
+        (dxv_geodesic_info).  rounds may differ from run to run; nothing reached: farthest 0 at voxel 0xFFFFFFFF."""
+        ms, rounds, far, voxel = C.c_float(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        used, reached, unreached = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self._lib.dxv_geodesic_info(self._ctx, C.byref(ms), C.byref(rounds), C.byref(used), C.byref(reached), C.byref(unreached), C.byref(far), C.byref(voxel)))
+        return {"ms": ms.value, "rounds": rounds.value, "seeds_used": used.value, "reached": reached.value, "unreached": unreached.value, "farthest": far.value,
+                "farthest_voxel": voxel.value}
+
+    def geodesic_work_info(self):
+        """{tiles_run, most_live_tiles, sparse_rounds} of the selected frame's last geodesic as of its last Sync (dxv_geodesic_work_info): the live
+        8^3 tiles summed over its rounds, the most of one round, the rounds with fewer than 1024 live tiles.  They differ from run to run."""
+        tiles, most, sparse = C.c_uint64(), C.c_uint32(), C.c_uint32()
+        self._check(self._lib.dxv_geodesic_work_info(self._ctx, C.byref(tiles), C.byref(most), C.byref(sparse)))
+        return {"tiles_run": tiles.value, "most_live_tiles": most.value, "sparse_rounds": sparse.value}
+
+    def GeodesicPath(self, target):
+        """uint32 voxel indices of a shortest path from target down to a seed of the selected frame's map (dxv_geodesic_path; synchronous): at every
+        voxel the first neighbour, in order of increasing index, whose value plus the step's weight is the voxel's own."""
+        length = C.c_uint32()
+        self._check(self._lib.dxv_geodesic_path(self._ctx, int(target), None, 0, C.byref(length)))
+        out = np.empty(length.value, np.uint32)
+        self._check(self._lib.dxv_geodesic_path(self._ctx, int(target), out.ctypes.data_as(C.c_void_p), len(out), C.byref(length)))
+        return out[:length.value]
 
     def SelectComponents(self, rule, arg=0, sync=True):
         """Edit the selected frame's grid in place from its current labels (dxv_components_select / _async): the voxels of every component

@@ -466,7 +466,7 @@ enum {
  *    page-locked block that is read where the frame is next synchronised, and that synchronisation enqueues further batches from the bit masks
  *    kept in the frame's scratch until one confirms.  After dxv_sync the grid is always exact; until then the frame counts as one that can
  *    still report something: dxv_render_async, dxv_distance_async, dxv_fill_async, dxv_morph_async, dxv_components_async, dxv_octree_async,
- *    dxv_isosurface_async, dxv_thickness_async, dxv_stream_wait_frame, dxv_grid_* and a second dxv_thin_async settle a pending thin first.  The
+ *    dxv_isosurface_async, dxv_thickness_async, dxv_geodesic_async, dxv_stream_wait_frame, dxv_grid_* and a second dxv_thin_async settle a pending thin first.  The
  *    next dxv_voxelize* simply overwrites the grid.
  *  - Everything a morph makes stale is stale after a thin: distance field, mesh-distance sign, isosurface, octree, components, thickness.  The texel
  *    image is not touched.
@@ -792,6 +792,86 @@ DXV_API int dxv_thickness_info(dxv_ctx* ctx, float* ms, uint64_t* centres_painte
  * The latter depends on the order the work items ran in and differs from run to run; the two pointers may be NULL. */
 DXV_API int dxv_thickness_stage_info(dxv_ctx* ctx, float ms[6], uint64_t* voxels_tested, uint64_t* atomics_sent);
 
+/* Geodesic distance: how far one place is from another THROUGH the part, or through its empty space (no reference counterpart).  dxv_distance is
+ * the straight-line distance to the other kind of voxel and dxv_fill knows only whether the border can be reached; this operator gives, per
+ * member voxel, the length of the shortest path of member voxels to the nearest seed: the length of a dxv_thin skeleton branch, the path between
+ * two points of a vessel, the tortuosity of a pore space, how deep a cavity lies behind its channel, and with a limit the geodesic dilation of a
+ * marker inside a mask.
+ * Input: the WHOLE grid of the selected frame's last launch, in any mode.  Bytes written through dxv_grid_device_ptr count too.  solid(p) iff
+ * byte(p) != 0.  Only voxels inside the grid exist.
+ * of = DXV_COMP_SOLID (0) or DXV_COMP_EMPTY (1) picks the members M.  metric picks the steps:
+ *     DXV_GEO_FACES   = 0   the 6 face neighbours, weight 1                            (G counts steps)
+ *     DXV_GEO_CHAMFER = 1   the 26 neighbours: weight 3 face, 4 edge, 5 corner         (G / 3 approximates voxels)
+ * A step from p to q is allowed iff both are members and q is a neighbour of p under the metric.  An edge or corner step does not ask about the
+ * voxels it squeezes between: the adjacency dxv_components uses at connectivity 26.
+ * The seed set S is one of three kinds:
+ *     DXV_GEO_SEEDS_BORDER = 0   every voxel with a coordinate equal to 0 or N - 1; seeds and seed_count are ignored
+ *     DXV_GEO_SEEDS_LIST   = 1   seeds is a HOST array of seed_count uint32 voxel indices (iz * N + iy) * N + ix, copied before the call returns;
+ *                                duplicates are allowed, an index >= N^3 is refused
+ *     DXV_GEO_SEEDS_MASK   = 2   seeds is a DEVICE pointer to N^3 bytes, a voxel is a seed iff its byte != 0; it is read on the frame's stream: the
+ *                                caller keeps it valid and orders its writer before the call; seed_count is ignored
+ * For every kind, seeds that are not members are ignored: seeds_used of dxv_geodesic_info counts the others, |S n M|.
+ *     G(p) = min over paths p0 in S n M, p1, ..., pk = p of allowed steps, of the sum of their weights      (0 on seeds)
+ *     out(p) = DXV_GEO_NONE      (0xFFFFFFFF)  p not in M
+ *              DXV_GEO_UNREACHED (0xFFFFFFFE)  p in M and no path exists, or limit != 0 and G(p) > limit
+ *              G(p)                            otherwise
+ * limit = 0 means no limit; a voxel with G == limit is kept.  Under a limit the kept values still equal the unlimited G, because every prefix of
+ * a shortest path is shorter.  A second, independent statement of the same rule, with out_0 the map of limit 0:
+ *     out_limit == where(out_0 <= limit, out_0, UNREACHED) on members
+ * An empty S n M is not an error: every member reads UNREACHED.
+ * Output: one uint32 per voxel, element (iz * N + iy) * N + ix like the grid, 4 N^3 bytes.  With integer weights G is the unique least fixed
+ * point of a relaxation: the device's bytes equal a restatement byte for byte, in whatever order its workgroups run.  A tally goes with it, by
+ * one deterministic reduction on the device: the seeds used, the members reached, the members unreached, `farthest` = the greatest G written
+ * and `farthest_voxel` = the smallest index that holds it (nothing reached: 0 and 0xFFFFFFFF).
+ * dxv_geodesic_async -- ENQUEUED on the frame's stream behind whatever it holds; returns without waiting.  The grid is read and none of the
+ * frame's other products is written.
+ *  - Rounds without a bound that is both safe and cheap, by the fill's discipline.  The call enqueues the map's first words, ONE batch of rounds
+ *    (option georounds) and the tally; whether the batch reached the fixed point is read where the frame is next synchronised, and further
+ *    batches are enqueued and waited for there until a round finds nothing to do.  After dxv_sync the map is exact; on the frame's stream alone it
+ *    is exact only if one batch was enough.  A map that has not settled after N^3 rounds is an error with a message.
+ *  - The host waits only under dxv_render_async's rule; a pending fill, thin, expansion or geodesic of the frame is settled first.
+ *  - Checked on the host before anything is enqueued, each an error with a message: of, metric and the seed kind are valid; a LIST has a
+ *    non-NULL pointer unless its count is 0, and no index is out of range; a MASK pointer is non-NULL and device memory of N^3 bytes; the frame
+ *    has been launched; its last launch was the whole grid; wmax (N^3 - 1) < 0xFFFFFFFE with wmax = 1 or 5, so that no path length can collide
+ *    with the two codes (CHAMFER: grid_dim <= 950); grid_dim <= 1024 in any case.
+ *  - Map and scratch belong to the frame: frames run side by side.  The map is 4 bytes per voxel; the scratch -- a control block, two sets of
+ *    live flags and a queue of 8^3 tiles, 6 bytes per tile = 3/256 byte per voxel, the seeds of a list, the words of a path -- goes back with
+ *    dxv_trim, the map stays.
+ *  - The map is STALE once the frame's grid version moves -- it is launched, filled, morphed, thinned, expanded or selected again: pointer,
+ *    size, download, info and path then fail with a message.
+ *  - Option events = 1 (default): bracketed by the frame's own events, read at the frame's dxv_sync.
+ * dxv_geodesic -- the same + dxv_sync. */
+enum { DXV_GEO_FACES = 0, DXV_GEO_CHAMFER = 1 };
+enum { DXV_GEO_SEEDS_BORDER = 0, DXV_GEO_SEEDS_LIST = 1, DXV_GEO_SEEDS_MASK = 2 };
+#define DXV_GEO_NONE 0xFFFFFFFFu
+#define DXV_GEO_UNREACHED 0xFFFFFFFEu
+DXV_API int dxv_geodesic_async(dxv_ctx* ctx, int of, int metric, int seeds_kind, const void* seeds, uint32_t seed_count, uint32_t limit);
+DXV_API int dxv_geodesic(dxv_ctx* ctx, int of, int metric, int seeds_kind, const void* seeds, uint32_t seed_count, uint32_t limit);
+/* The map on the device (exact after dxv_sync) and its size, 4 * grid_dim^3 bytes.  NULL / 0 (the pointer with a message) before the frame's
+ * first geodesic or when it is stale. */
+DXV_API const void* dxv_geodesic_device_ptr(const dxv_ctx* ctx);
+DXV_API size_t dxv_geodesic_bytes(const dxv_ctx* ctx);
+/* Copies it to the host (bytes must be the size above); synchronises the frame first. */
+DXV_API int dxv_geodesic_download(dxv_ctx* ctx, void* host, size_t bytes);
+/* The selected frame's last geodesic as of the frame's last dxv_sync: device time in milliseconds from its first kernel to its last tally (HIP
+ * events, option events = 1; else 0), its rounds with the confirming one, and the tally.  `rounds` may differ from run to run: a tile reads its
+ * neighbours' words while they are being lowered, and how soon it sees them decides how many rounds are needed -- never what the map holds.
+ * Any pointer may be NULL; fails with a message before the frame's first geodesic or when the map is stale. */
+DXV_API int dxv_geodesic_info(dxv_ctx* ctx, float* ms, uint32_t* rounds, uint64_t* seeds_used, uint64_t* reached, uint64_t* unreached, uint32_t* farthest, uint32_t* farthest_voxel);
+/* ... and, for measurements, what its rounds did (one entry beyond the rule's list; as of the frame's last dxv_sync, under the same rules): the
+ * tiles they ran -- the sum over the rounds of the live 8^3 tiles, so tiles_run / rounds is the live tiles per round --, the most live tiles
+ * of one round, and the rounds with fewer than 1024 live tiles, which leave most of the device idle.  Like `rounds`, these differ from run to
+ * run. */
+DXV_API int dxv_geodesic_work_info(dxv_ctx* ctx, uint64_t* tiles_run, uint32_t* most_live_tiles, uint32_t* sparse_rounds);
+/* A shortest path of the selected frame's current map from `target` down to a seed, synchronous (the frame is synchronised first).  target must
+ * be in range and hold a value below DXV_GEO_UNREACHED, else an error with a message.  The path starts at p0 = target; the next voxel is the
+ * FIRST neighbour q of p_k with out(q) + w(q, p_k) == out(p_k), the neighbours taken in order of increasing index -- dz outermost and dx
+ * innermost, each over -1, 0, 1 -- and only the metric's neighbours inside the grid tried; it ends at the first voxel with value 0.  At a fixed
+ * point such a q always exists; if none is found the call fails with a message.  *length = the number of voxels on the whole path;
+ * min(length, capacity) indices are written to host_path; capacity 0 with a NULL buffer asks for the length alone.  The farthest voxel from
+ * the farthest voxel is the usual double sweep for a skeleton's length or a pore network's diameter. */
+DXV_API int dxv_geodesic_path(dxv_ctx* ctx, uint32_t target, uint32_t* host_path, uint32_t capacity, uint32_t* length);
+
 /* Multi-GPU: the built scene (nodes + triangle data) as one relocatable device blob, so that
  * rank 0 builds once and the host layer broadcasts it (RCCL over xGMI) to the other ranks.
  * export copies the blob into caller-provided DEVICE memory; import adopts a blob from DEVICE
@@ -911,6 +991,8 @@ DXV_API int dxv_get_stats(const dxv_ctx* ctx, dxv_stats* out);
  *                 where its frame is next synchronised.  Same grids.
  *   thinrounds 0..64  dxv_thin*: iterations of one batch (0, default: 16); a thin that needs more is continued where its frame is next
  *                 synchronised.  Same grids.
+ *   georounds 0..64  dxv_geodesic*: rounds of one batch (0, default: 16); a geodesic that needs more is continued where its frame is next
+ *                 synchronised.  Same map.
  *   morphform 0..2  dxv_morph*: 0 (default) = by the radius: bit planes up to radius_sq 1024, above it the distance field of the grid and its
  *                 threshold, per half; 1 / 2 = always the planes / always the field (measurement, cross-check).  Same grids.
  *   thickcull 0..3  dxv_thickness*: which centres are left out of the paint because their ball cannot raise anything: bit 0 = those whose ball
@@ -967,7 +1049,7 @@ DXV_API int dxv_debug_queue_order(dxv_ctx* ctx, uint64_t out[4]);
 
 /* Give back what the context keeps only to make the next build faster: the list build's scratch (up to 16 GiB per buffer
  * after a 10 M-triangle scene), the LBVH build's scratch when no refit can follow (imported scenes), the memory of prepared queues
- * whose lists are gone, the scratch of the frames' distance fields (the fields stay), of their flood fills, morphs, thins and thickness maps (the maps stay), of their isosurfaces (the
+ * whose lists are gone, the scratch of the frames' distance fields (the fields stay), of their flood fills, morphs, thins, thickness and geodesic maps (the maps stay), of their isosurfaces (the
  * meshes stay), of their octrees (the nodes stay) and of their connected components (labels and table stay).  Nothing a launch reads. */
 DXV_API int dxv_trim(dxv_ctx* ctx);
 

@@ -328,6 +328,47 @@ public:
 	bool ThicknessInfo(float& ms, uint64_t& centresPainted, uint64_t& workItems) { return m_ctx && dxv_thickness_info(m_ctx, &ms, &centresPainted, &workItems) == 0; }
 	static float ThicknessVoxels(uint32_t w) { return w ? 2.0f * sqrtf((float)w) - 1.0f : 0.0f; }
 
+	// The geodesic distance inside the selected frame's whole grid (dxv_geodesic / dxv_geodesic_async; include/dxv.h has the rule): per member voxel
+	// the length of the shortest path of member voxels to the nearest seed -- DXV_GEO_FACES over the face neighbours at weight 1, DXV_GEO_CHAMFER
+	// over the 26 neighbours at weights 3 / 4 / 5 --, DXV_GEO_NONE on the others, DXV_GEO_UNREACHED where no path exists or is longer than limit
+	// (0: no limit).  Seeds: the grid's border, a list of voxel indices, or a mask of N^3 bytes in device memory.  The grid and the frame's other
+	// products stay as they are.
+	bool Geodesic(int of = DXV_COMP_SOLID, int metric = DXV_GEO_CHAMFER, uint32_t limit = 0, bool sync = true)
+	{
+		return m_ctx && (sync ? dxv_geodesic(m_ctx, of, metric, DXV_GEO_SEEDS_BORDER, nullptr, 0, limit) : dxv_geodesic_async(m_ctx, of, metric, DXV_GEO_SEEDS_BORDER, nullptr, 0, limit)) == 0;
+	}
+	bool Geodesic(int of, int metric, const std::vector<uint32_t>& seeds, uint32_t limit = 0, bool sync = true)
+	{
+		const uint32_t count = static_cast<uint32_t>(seeds.size());
+		return m_ctx && (sync ? dxv_geodesic(m_ctx, of, metric, DXV_GEO_SEEDS_LIST, seeds.data(), count, limit) : dxv_geodesic_async(m_ctx, of, metric, DXV_GEO_SEEDS_LIST, seeds.data(), count, limit)) == 0;
+	}
+	bool GeodesicFromDeviceMask(int of, int metric, const void* deviceMask, uint32_t limit = 0, bool sync = true)
+	{
+		return m_ctx && (sync ? dxv_geodesic(m_ctx, of, metric, DXV_GEO_SEEDS_MASK, deviceMask, 0, limit) : dxv_geodesic_async(m_ctx, of, metric, DXV_GEO_SEEDS_MASK, deviceMask, 0, limit)) == 0;
+	}
+	const void* DeviceGeodesic() const { return m_ctx ? dxv_geodesic_device_ptr(m_ctx) : nullptr; }
+	bool GeodesicField(std::vector<uint32_t>& field)
+	{
+		if (!m_ctx) return setError("GeodesicField before Init");
+		const size_t bytes = dxv_geodesic_bytes(m_ctx);
+		if (!bytes) return false;
+		field.resize(bytes / sizeof(uint32_t));
+		return dxv_geodesic_download(m_ctx, field.data(), bytes) == 0;
+	}
+	struct GeodesicTally { float ms = 0.0f; uint32_t rounds = 0; uint64_t seedsUsed = 0, reached = 0, unreached = 0; uint32_t farthest = 0, farthestVoxel = 0xFFFFFFFFu; };
+	bool GeodesicInfo(GeodesicTally& t)
+	{
+		return m_ctx && dxv_geodesic_info(m_ctx, &t.ms, &t.rounds, &t.seedsUsed, &t.reached, &t.unreached, &t.farthest, &t.farthestVoxel) == 0;
+	}
+	// a shortest path from target down to a seed, as voxel indices (dxv_geodesic_path; synchronous)
+	bool GeodesicPath(uint32_t target, std::vector<uint32_t>& path)
+	{
+		uint32_t length = 0;
+		if (!m_ctx || dxv_geodesic_path(m_ctx, target, nullptr, 0, &length)) return false;
+		path.resize(length);
+		return dxv_geodesic_path(m_ctx, target, path.data(), length, &length) == 0 && length == path.size();
+	}
+
 	// The exterior flood fill of that frame's whole grid, in place (dxv_fill / dxv_fill_async): DXV_FILL_SOLID leaves the walls and everything
 	// they enclose, DXV_FILL_INTERIOR the enclosed voxels alone.  Voxelize(gridDim, SURFACE) && Fill() is the solid of a mesh whose
 	// normals and watertightness cannot be trusted.  Refers to the frame last selected; sync = false only enqueues (WaitFrame reports).
