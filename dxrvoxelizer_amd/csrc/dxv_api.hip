@@ -272,15 +272,7 @@ int dxv_trim(dxv_ctx* c)
     if (sync_frames(c)) return 1;
     DXV_HIP(c, hipStreamSynchronize(c->stream));
     c->listScratchA.release(); c->listScratchB.release();
-    for (auto& f : c->frames) f.distScratch.release();                  // (the passes' scratch, 6 bytes per voxel; a frame's field itself stays)
-    for (auto& f : c->frames) f.fillScratch.release();                  // (the masks of a flood fill, a quarter of a byte per voxel: sync_frames has settled every fill)
-    for (auto& f : c->frames) f.isoScratch.release();                   // (the bits, counts and sums of an isosurface extraction; a frame's mesh itself stays)
-    for (auto& f : c->frames) f.octScratch.release();                   // (the dense cell words, bits and counts of an octree build; a frame's nodes themselves stay)
-    for (auto& f : c->frames) { f.compScratch.release(); f.compWork.release(); }   // (the masks, counts and stats of a labelling; a frame's labels and table themselves stay)
-    for (auto& f : c->frames) f.morphScratch.release();                 // (the masks and planes of a morph: (R + 3) bits per voxel)
-    for (auto& f : c->frames) f.thinScratch.release();                  // (the masks of a thin, 3 1/8 bits per voxel: sync_frames has settled every thin)
-    for (auto& f : c->frames) f.thickScratch.release();                 // (the fields, bytes and passes of a thickness, 15 bytes per voxel; a frame's map and histogram themselves stay)
-    for (auto& f : c->frames) { f.geoScratch.release(); f.geoSeeds.release(); f.geoPath.release(); }   // (control block, flags and queue of a geodesic, 6 bytes per 8^3 tile, a list's seeds, a path's words; a frame's map itself stays)
+    for (auto& f : c->frames) f.trim_products();                        // (the scratch of every operator; what they made of the grid stays: Frame)
     c->specRes = 0;
     if (!c->haveHierarchy) c->scratch = BuildScratch{};                             // (a built scene keeps keys and links: dxv_refit reads them)
     // prepared queues of lists that are gone (their slots keep their memory for the next dxv_prepare_launch of the partition: 8 MB at
@@ -595,7 +587,7 @@ size_t dxv_grid_bytes(const dxv_ctx* c) { return c ? c->frames[c->cur].gridBytes
 // the download and count entries: an unchecked launch of the selected frame is finished (with its redo, if any) first ...
 static int finish_launch(dxv_ctx* c)
 {
-    if ((cur_frame(c).pending || cur_frame(c).fillPending || cur_frame(c).thinPending || cur_frame(c).octExpandPending) && dxv_sync(c)) return 1;       // (a fill or a thin whose verdict is not read yet: the grid may not be final)
+    if ((cur_frame(c).pending || cur_frame(c).grid_unsettled()) && dxv_sync(c)) return 1;     // (an edit in place whose verdict is not read yet: the grid may not be final)
     DXV_HIP(c, hipSetDevice(c->device));
     return 0;
 }

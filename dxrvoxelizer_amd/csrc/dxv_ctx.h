@@ -1,6 +1,6 @@
 // dxv_ctx.h -- the context of libdxv.so and what its translation units share: dxv_api.hip (context, mesh, build, options,
 // results), dxv_lists.hip (the candidate lists' policy and builds), dxv_frames.hip (frames, launches, work queues),
-// dxv_products.hip (what is made of a frame's grid: fields, mesh, tree, labels, and the edits in place), dxv_blob.hip (the
+// dxv_products.hip (what is made of a frame's grid and what edits it in place: one record of Frame per operator), dxv_blob.hip (the
 // scene blob that travels between GPUs), dxv_debug.hip (test hooks).  Nothing here is exported.
 #pragma once
 #include "../../include/dxv.h"
@@ -138,12 +138,14 @@ struct BuildScratch {
 struct Timer { hipEvent_t e0 = nullptr, e1 = nullptr; bool armed = false; float ms = 0; };
 // ... and what a frame times.  The launch's pair and its queue build's are here for their events alone: when they are read is the launch's
 // business (Frame::timed, lastRebuilt -> voxelize_ms, plan_ms), so they stand in front of kTimerFirstOperator: a synchronisation of the frame
-// reads the armed pairs from there on (sync_launch), and a new operator's slot goes behind it.
-enum TimerUse { kTimerLaunch, kTimerQueue, kTimerRender, kTimerDistance, kTimerMeshDistance, kTimerFill, kTimerIso, kTimerOctree, kTimerComponents, kTimerMorph, kTimerThin, kTimerMeasure, kTimerThickness,
+// reads the armed pairs from there on (sync_launch), and a new operator's slot goes behind it.  The operators that run in batches of rounds
+// form the tail from kTimerFirstBatched on: further batches move their second event, so their pairs are read where they are settled
+// (settle_batched), and sync_launch stops in front of them.
+enum TimerUse { kTimerLaunch, kTimerQueue, kTimerRender, kTimerDistance, kTimerMeshDistance, kTimerIso, kTimerOctree, kTimerComponents, kTimerMorph, kTimerMeasure, kTimerThickness,
                 kTimerThickStage0, kTimerThickStageLast = kTimerThickStage0 + dxv::THICK_STAGES - 1,     // the six stages of a thickness, each a pair of its own
-                kTimerGeodesic,
+                kTimerFill, kTimerThin, kTimerGeodesic,
                 kTimers,
-                kTimerFirstOperator = kTimerRender };
+                kTimerFirstOperator = kTimerRender, kTimerFirstBatched = kTimerFill };
 
 struct dxv_ctx {
     int device = 0;
@@ -190,8 +192,7 @@ struct dxv_ctx {
         bool lastCanFail = true;         // ... and it can report something (a walk's column can run out; the lists have no column)
         bool ready = false;              // status words, redo list, events and stream exist
         uint64_t gridVersion = 1;        // counts what rewrote the grid: launches and the edits in place (grid_rewritten).  What is made of the grid
-                                         // remembers the version it was made of (distVersion ...; 0: none, or being rebuilt) and is current exactly
-                                         // while the two are equal
+                                         // remembers the version it was made of (Made, below) and is current exactly while the two are equal
         uint64_t clearSig = 0;           // the partial launch whose memset this grid still carries (launch_shape, traverse.hip); 0 = none
         bool ptrExposed = false;         // dxv_grid_device_ptr handed this grid out for writing: the caller may write through the pointer at any
                                          // time, so no memset is ever kept for it again (until the grid is reallocated)
@@ -220,120 +221,160 @@ struct dxv_ctx {
         // surface modes (surface.hip): the large triangles' lists of the frame's surface pass, its own (never the work queue's
         // buffers: a kept queue of the reference rule is still needed by the frame's next mode-0 launch)
         DevBuf<uint8_t> surf;
-        // distance field (distance.hip; dxv_distance_async): the field of the frame's grid and the scratch of its three passes, the
-        // frame's own so that frames compute theirs side by side; the scratch goes with dxv_trim, the field stays
-        DevBuf<int32_t> dist;            // (cap: voxels) 4 bytes per voxel, int32 or float32
-        DevBuf<uint8_t> distScratch;     // (cap: bytes) distance_scratch_bytes: the x pass's 16-bit values, the y pass's squares
-        uint32_t distDim = 0;            // grid side of the frame's last field (0: none yet)
-        uint64_t distVersion = 0;        // ... and the grid version it was made of
-        int distFormat = 0;              // ... and its format (DXV_DIST_SQ_I32 / DXV_DIST_F32)
+        // What is made of the grid, and what edits it in place: one record per operator (dxv_products.hip), each the frame's own so that frames
+        // run theirs side by side.  A record's trim() releases what dxv_trim gives back -- the scratch of its making; what was made stays.
+        // Made: whether the frame has had the product made, and of which grid version.  have goes with the buffer's content (false while a
+        // product that is sized by the grid is being rebuilt: a failed allocation leaves "none yet"), version with the grid (0: being rebuilt).
+        struct Made {
+            bool have = false;
+            uint64_t version = 0;
+            bool current(const Frame& f) const { return have && version == f.gridVersion; }
+        };
+        // distance field (distance.hip; dxv_distance_async): the field of the frame's grid and the scratch of its three passes
+        struct Distance : Made {
+            DevBuf<int32_t> field;           // (cap: voxels) 4 bytes per voxel, int32 or float32
+            DevBuf<uint8_t> scratch;         // (cap: bytes) distance_scratch_bytes: the x pass's 16-bit values, the y pass's squares
+            uint32_t dim = 0;                // grid side of the frame's last field
+            int format = 0;                  // ... and its format (DXV_DIST_SQ_I32 / DXV_DIST_F32)
+            void trim() { scratch.release(); }   // (the passes' scratch, 6 bytes per voxel; the field itself stays)
+        } dist;
         // mesh distance field (mesh_distance.hip; dxv_mesh_distance_async): the field of the frame's last launch -- a slab's has nz slices --
-        // and, when asked for, the nearest triangles; the frame's own, kept by dxv_trim
-        DevBuf<float> mdist;             // (cap: voxels)
-        DevBuf<uint32_t> mdistTri;       // (cap: voxels)
-        uint32_t mdistDim = 0;           // grid side of the frame's last mesh distance field (0: none yet) ...
-        uint32_t mdistNz = 0;            // ... and its slices
-        int mdistFormat = 0;             // ... its format
-        bool mdistHasTri = false;        // ... and whether the nearest triangles were made with it
-        uint64_t mdistVersion = 0;       // ... and the grid version it was made of
+        // and, when asked for, the nearest triangles; kept by dxv_trim
+        struct MeshDistance : Made {
+            DevBuf<float> field;             // (cap: voxels)
+            DevBuf<uint32_t> tri;            // (cap: voxels)
+            uint32_t dim = 0;                // grid side of the frame's last mesh distance field ...
+            uint32_t nz = 0;                 // ... and its slices
+            int format = 0;                  // ... its format
+            bool hasTri = false;             // ... and whether the nearest triangles were made with it
+            void trim() {}                   // (it has no scratch)
+        } mdist;
         bool sceneReadPending = false;   // a mesh distance kernel that reads nodes and triangle records may still be running on the frame's stream: whatever
                                          // rewrites them on another stream (dxv_refit, ensure_nodes) waits for the frame's end event first; any
                                          // synchronisation of the frame clears it (the passes over the grid alone -- render, field, fill -- never set it)
-        // exterior flood fill (fill.hip; dxv_fill_async): the two bit masks and the control block of the frame's fill, its own so that
-        // frames fill side by side; goes with dxv_trim
-        DevBuf<uint8_t> fillScratch;     // (cap: bytes) fill_scratch_bytes
-        bool fillPending = false;        // a batch is in the stream whose verdict (converged or not) nobody has read yet: the frame can still
-                                         // report something, and its next synchronisation reads it and goes on if need be (settle_fill)
-        int fillWhat = 0;                // ... DXV_FILL_SOLID / DXV_FILL_INTERIOR, for the write-back of the batches that follow
-        uint32_t fillBatch = 0;          // ... rounds per batch (option fillrounds as it stood at dxv_fill_async)
-        uint32_t fillRounds = 0;         // rounds of the frame's last fill so far, the confirming one included
-                                         // (its timer's second event is recorded again behind every further batch, and settle_fill reads the pair)
+        // exterior flood fill (fill.hip; dxv_fill_async): the two bit masks and the control block of the frame's fill
+        struct Fill {
+            DevBuf<uint8_t> scratch;         // (cap: bytes) fill_scratch_bytes
+            bool pending = false;            // a batch is in the stream whose verdict (converged or not) nobody has read yet: the frame can still
+                                             // report something, and its next synchronisation reads it and goes on if need be (settle_fill)
+            int what = 0;                    // ... DXV_FILL_SOLID / DXV_FILL_INTERIOR, for the write-back of the batches that follow
+            uint32_t batch = 0;              // ... rounds per batch (option fillrounds as it stood at dxv_fill_async)
+            uint32_t rounds = 0;             // rounds of the frame's last fill so far, the confirming one included
+                                             // (its timer's second event is recorded again behind every further batch, and settle_fill reads the pair)
+            void trim() { scratch.release(); }   // (the masks, a quarter of a byte per voxel: sync_frames has settled every fill)
+        } fill;
         // isosurface (isosurface.hip; dxv_isosurface_async): the triangle mesh of one of the frame's fields and the scratch of its extraction
-        // (a bit per lattice cell, two counts per 64 cells, the scan's sums), the frame's own; the scratch goes with dxv_trim, the mesh stays
-        DevBuf<uint8_t> isoVb;           // (cap: vertices) 24 bytes each
-        DevBuf<uint32_t> isoIb;          // (cap: index words)
-        DevBuf<uint8_t> isoScratch;      // (cap: bytes) iso_scratch_bytes
-        uint32_t isoVertices = 0, isoTriangles = 0;   // of the frame's last mesh
-        bool isoHave = false;            // the frame has had a mesh extracted (an empty one counts) ...
-        uint64_t isoVersion = 0;         // ... of this grid version
+        // (a bit per lattice cell, two counts per 64 cells, the scan's sums)
+        struct Iso : Made {                  // (have: an empty mesh counts)
+            DevBuf<uint8_t> vb;              // (cap: vertices) 24 bytes each
+            DevBuf<uint32_t> ib;             // (cap: index words)
+            DevBuf<uint8_t> scratch;         // (cap: bytes) iso_scratch_bytes
+            uint32_t vertices = 0, triangles = 0;     // of the frame's last mesh
+            void trim() { scratch.release(); }   // (the bits, counts and sums of an extraction; the mesh itself stays)
+        } iso;
         // sparse voxel octree (octree.hip; dxv_octree_async): the nodes of the frame's grid and the scratch of their build (two bytes per cell of
-        // levels 0 .. L - 1, a bit per cell, a count per 64 cells, the scan's sums), the frame's own; the scratch goes with dxv_trim, the nodes stay
-        DevBuf<uint32_t> octNodes;       // (cap: nodes) 8 bytes each
-        DevBuf<uint8_t> octScratch;      // (cap: bytes) oct_scratch_bytes
-        uint32_t octLevels = 0, octCount = 0;         // L and the nodes of the frame's last tree ...
-        uint32_t octLevelFirst[12] = {}; // ... and the first node of every level, [L] the total
-        bool octHave = false;            // the frame has had a tree built ...
-        uint64_t octVersion = 0;         // ... of this grid version
-        bool octExpandPending = false;   // dxv_octree_expand_async read a CALLER's tree whose verdict (status word kOctStatusWord: an index that could not be
-                                         // followed) nobody has read yet: the frame can still report something, and its next synchronisation reads it
+        // levels 0 .. L - 1, a bit per cell, a count per 64 cells, the scan's sums)
+        struct Octree : Made {
+            DevBuf<uint32_t> nodes;          // (cap: nodes) 8 bytes each
+            DevBuf<uint8_t> scratch;         // (cap: bytes) oct_scratch_bytes
+            uint32_t levels = 0, count = 0;  // L and the nodes of the frame's last tree ...
+            uint32_t levelFirst[12] = {};    // ... and the first node of every level, [L] the total
+            bool expandPending = false;      // dxv_octree_expand_async read a CALLER's tree whose verdict (status word kOctStatusWord: an index that could not be
+                                             // followed) nobody has read yet: the frame can still report something, and its next synchronisation reads it
+            void trim() { scratch.release(); }   // (the dense cell words, bits and counts of a build; the nodes themselves stay)
+        } oct;
         // connected components (components.hip; dxv_components_async): labels and table of the frame's grid and the scratch of their build
-        // (two bits per voxel, a count per 64 voxels, the scan's sums; 32 bytes per component for the stats), the frame's own; the scratch
-        // goes with dxv_trim, labels and table stay
-        DevBuf<uint32_t> compLabels;     // (cap: voxels)
-        DevBuf<uint8_t> compTable;       // (cap: components) 24 bytes each
-        DevBuf<uint8_t> compScratch;     // (cap: bytes) comp_scratch_bytes
-        DevBuf<uint8_t> compWork;        // (cap: bytes) the stats of a build, then the counters and keep flags of a select
-        uint32_t compCount = 0, compDim = 0;          // K and the grid side of the frame's last labelling ...
-        int compOf = 0, compConnectivity = 0;         // ... and what it was asked for
-        bool compHave = false;           // the frame has had its grid labelled ...
-        uint64_t compVersion = 0;        // ... of this grid version
-        // the measures of that labelling (measure.hip; dxv_measure_async): K + 1 records of 96 bytes, the frame's own; stays with dxv_trim like the labels
-        DevBuf<uint8_t> measTable;       // (cap: records)
-        uint32_t measCount = 0;          // K of the labelling the table was made of
-        bool measHave = false;           // the frame has had a labelling measured ...
-        uint64_t measVersion = 0;        // ... of this grid version; 0 once the frame is labelled again
-        bool selPending = false;         // a select's four counters are on their way into page-locked words: the frame's next synchronisation reads them
-        int selRule = 0;
-        uint32_t selComponents = 0;      // K of the labels that select edited from
-        uint32_t selKept = 0, selDropped = 0;         // of the frame's last select, as of its last synchronisation
-        uint64_t selChanged = 0;
-        // morphology (morph.hip; dxv_morph_async): the bit masks and planes of the frame's morph, its own so that frames morph side by side;
-        // goes with dxv_trim
-        DevBuf<uint8_t> morphScratch;    // (cap: bytes) morph_scratch_bytes
-        bool morphPending = false;       // a morph's two counters are on their way into page-locked words: the frame's next synchronisation reads them
-        uint64_t morphSet = 0, morphCleared = 0;      // of the frame's last morph, as of its last synchronisation
-        // thinning (thin.hip; dxv_thin_async): the bit masks and the control block of the frame's thin, its own so that frames thin side by side;
-        // goes with dxv_trim
-        DevBuf<uint8_t> thinScratch;     // (cap: bytes) thin_scratch_bytes
-        bool thinPending = false;        // a batch is in the stream whose verdict (fixed point or not) nobody has read yet: the frame can still
-                                         // report something, and its next synchronisation reads it and goes on if need be (settle_thin)
-        int thinKind = 0;                // ... DXV_THIN_CURVE / DXV_THIN_KERNEL, for the batches that follow
-        uint32_t thinBatch = 0;          // ... iterations per batch (option thinrounds as it stood at dxv_thin_async)
-        uint32_t thinInBatch = 0;        // ... iterations of the batch in the stream (the last one of a bounded thin may be shorter)
-        uint32_t thinLeft = 0;           // ... iterations max_iterations still allows behind that batch (thinBounded)
-        bool thinBounded = false;        // ... max_iterations != 0
-        uint32_t thinIterations = 0;     // iterations of the frame's last thin so far, the confirming one included
-        uint64_t thinRemoved = 0;        // voxels it removed, as of the frame's last synchronisation
-        bool thinConverged = false;      // it stopped at an iteration that removed nothing (false: max_iterations stopped it first, or none yet)
+        // (two bits per voxel, a count per 64 voxels, the scan's sums; 32 bytes per component for the stats)
+        struct Components : Made {
+            DevBuf<uint32_t> labels;         // (cap: voxels)
+            DevBuf<uint8_t> table;           // (cap: components) 24 bytes each
+            DevBuf<uint8_t> scratch;         // (cap: bytes) comp_scratch_bytes
+            DevBuf<uint8_t> work;            // (cap: bytes) the stats of a build, then the counters and keep flags of a select
+            uint32_t count = 0, dim = 0;     // K and the grid side of the frame's last labelling ...
+            int of = 0, connectivity = 0;    // ... and what it was asked for
+            // the measures of that labelling (measure.hip; dxv_measure_async): K + 1 records of 96 bytes; stays with dxv_trim like the labels
+            struct Measure : Made {          // (version: 0 once the frame is labelled again)
+                DevBuf<uint8_t> table;       // (cap: records)
+                uint32_t count = 0;          // K of the labelling the table was made of
+            } measure;
+            // the edit from the labels (dxv_components_select_async)
+            struct Select {
+                bool pending = false;        // its four counters are on their way into page-locked words: the frame's next synchronisation reads them
+                int rule = 0;
+                uint32_t components = 0;     // K of the labels that select edited from
+                uint32_t kept = 0, dropped = 0;   // of the frame's last select, as of its last synchronisation
+                uint64_t changed = 0;
+            } select;
+            void trim() { scratch.release(); work.release(); }   // (the masks, counts and stats of a labelling; labels and tables themselves stay)
+        } comp;
+        // morphology (morph.hip; dxv_morph_async): the bit masks and planes of the frame's morph
+        struct Morph {
+            DevBuf<uint8_t> scratch;         // (cap: bytes) morph_scratch_bytes
+            bool pending = false;            // its two counters are on their way into page-locked words: the frame's next synchronisation reads them
+            uint64_t set = 0, cleared = 0;   // of the frame's last morph, as of its last synchronisation
+            void trim() { scratch.release(); }   // (the masks and planes: (R + 3) bits per voxel)
+        } morph;
+        // thinning (thin.hip; dxv_thin_async): the bit masks and the control block of the frame's thin
+        struct Thin {
+            DevBuf<uint8_t> scratch;         // (cap: bytes) thin_scratch_bytes
+            bool pending = false;            // a batch is in the stream whose verdict (fixed point or not) nobody has read yet: the frame can still
+                                             // report something, and its next synchronisation reads it and goes on if need be (settle_thin)
+            int kind = 0;                    // ... DXV_THIN_CURVE / DXV_THIN_KERNEL, for the batches that follow
+            uint32_t batch = 0;              // ... iterations per batch (option thinrounds as it stood at dxv_thin_async)
+            uint32_t inBatch = 0;            // ... iterations of the batch in the stream (the last one of a bounded thin may be shorter)
+            uint32_t left = 0;               // ... iterations max_iterations still allows behind that batch (bounded)
+            bool bounded = false;            // ... max_iterations != 0
+            uint32_t iterations = 0;         // iterations of the frame's last thin so far, the confirming one included
+            uint64_t removed = 0;            // voxels it removed, as of the frame's last synchronisation
+            bool converged = false;          // it stopped at an iteration that removed nothing (false: max_iterations stopped it first, or none yet)
+            void trim() { scratch.release(); }   // (the masks, 3 1/8 bits per voxel: sync_frames has settled every thin)
+        } thin;
         // local thickness (thickness.hip; dxv_thickness_async): the map and the histogram of the frame's grid and the scratch of their making (two
-        // fields, a byte per voxel, the fields' passes: 15 bytes per voxel), the frame's own; the scratch goes with dxv_trim, map and histogram stay
-        DevBuf<uint32_t> thick;          // (cap: voxels)
-        DevBuf<unsigned long long> thickHist;   // (cap: bins)
-        DevBuf<uint8_t> thickScratch;    // (cap: bytes) thickness_scratch_bytes
-        uint32_t thickDim = 0, thickCap = 0;    // grid side and cap_sq of the frame's last map (0: none yet) ...
-        uint64_t thickVersion = 0;       // ... and the grid version it was made of
-        bool thickPending = false;       // its four counters are on their way into page-locked words: the frame's next synchronisation reads them
-        uint64_t thickCentres = 0, thickItems = 0, thickTested = 0, thickSent = 0;   // of the frame's last thickness, as of its last synchronisation
+        // fields, a byte per voxel, the fields' passes)
+        struct Thickness : Made {
+            DevBuf<uint32_t> map;            // (cap: voxels)
+            DevBuf<unsigned long long> hist; // (cap: bins)
+            DevBuf<uint8_t> scratch;         // (cap: bytes) thickness_scratch_bytes
+            uint32_t dim = 0, cap = 0;       // grid side and cap_sq of the frame's last map
+            bool pending = false;            // its four counters are on their way into page-locked words: the frame's next synchronisation reads them
+            uint64_t centres = 0, items = 0, tested = 0, sent = 0;   // of the frame's last thickness, as of its last synchronisation
+            void trim() { scratch.release(); }   // (the fields, bytes and passes, 15 bytes per voxel; map and histogram themselves stay)
+        } thick;
         // geodesic distance (geodesic.hip; dxv_geodesic_async): the map of the frame's grid, and the scratch of its making -- control block, live
-        // flags, queue; the seeds of a list; the words of a path --, the frame's own so that frames run side by side; the scratch goes with
-        // dxv_trim, the map stays
-        DevBuf<uint32_t> geo;            // (cap: voxels)
-        DevBuf<uint8_t> geoScratch;      // (cap: bytes) geodesic_scratch_bytes
-        DevBuf<uint32_t> geoSeeds;       // (cap: indices) the seeds of a list
-        DevBuf<uint32_t> geoPath;        // (cap: words) dxv_geodesic_path: length, status, voxel indices
-        std::vector<uint32_t> geoList;   // the caller's list, copied before dxv_geodesic_async returns: what the upload reads
-        uint32_t geoDim = 0;             // grid side of the frame's last map (0: none yet) ...
-        uint64_t geoVersion = 0;         // ... and the grid version it was made of
-        int geoMetric = 0;               // ... DXV_GEO_FACES / DXV_GEO_CHAMFER, for the batches that follow and for the path
-        uint32_t geoLimit = 0;           // ... its limit (0: none)
-        bool geoPending = false;         // a batch is in the stream whose verdict (fixed point or not) nobody has read yet: the frame's next
-                                         // synchronisation reads it and goes on if need be (settle_geodesic)
-        uint32_t geoBatch = 0;           // ... rounds per batch (option georounds as it stood at dxv_geodesic_async)
-        uint32_t geoRounds = 0;          // rounds of the frame's last geodesic so far, the confirming one included
-        uint64_t geoTilesRun = 0;        // ... the tiles its rounds ran, the most of one round, and the rounds with fewer than kGeoSparseTiles
-        uint32_t geoMostLive = 0, geoSparseRounds = 0;
-        uint64_t geoSeedsUsed = 0, geoReached = 0, geoUnreached = 0;    // its tally, as of the frame's last synchronisation
-        uint32_t geoFarthest = 0, geoFarthestVoxel = 0xFFFFFFFFu;
+        // flags, queue; the seeds of a list; the words of a path
+        struct Geodesic : Made {
+            DevBuf<uint32_t> map;            // (cap: voxels)
+            DevBuf<uint8_t> scratch;         // (cap: bytes) geodesic_scratch_bytes
+            DevBuf<uint32_t> seeds;          // (cap: indices) the seeds of a list
+            DevBuf<uint32_t> path;           // (cap: words) dxv_geodesic_path: length, status, voxel indices
+            std::vector<uint32_t> list;      // the caller's list, copied before dxv_geodesic_async returns: what the upload reads
+            uint32_t dim = 0;                // grid side of the frame's last map
+            int metric = 0;                  // ... DXV_GEO_FACES / DXV_GEO_CHAMFER, for the batches that follow and for the path
+            uint32_t limit = 0;              // ... its limit (0: none)
+            bool pending = false;            // a batch is in the stream whose verdict (fixed point or not) nobody has read yet: the frame's next
+                                             // synchronisation reads it and goes on if need be (settle_geodesic)
+            uint32_t batch = 0;              // ... rounds per batch (option georounds as it stood at dxv_geodesic_async)
+            uint32_t rounds = 0;             // rounds of the frame's last geodesic so far, the confirming one included
+            uint64_t tilesRun = 0;           // ... the tiles its rounds ran, the most of one round, and the rounds with fewer than kGeoSparseTiles
+            uint32_t mostLive = 0, sparseRounds = 0;
+            uint64_t seedsUsed = 0, reached = 0, unreached = 0;     // its tally, as of the frame's last synchronisation
+            uint32_t farthest = 0, farthestVoxel = 0xFFFFFFFFu;
+            void trim() { scratch.release(); seeds.release(); path.release(); }   // (control block, flags and queue, 6 bytes per 8^3 tile, a list's seeds, a path's words; the map itself stays)
+        } geo;
+        // What a synchronisation of the frame and a launch need to know of all that, without naming an operator.
+        // grid_unsettled: the grid may not be final yet -- a fill or a thin whose verdict is not in, an expansion from a caller's tree that can
+        // still report; unsettled: ... or a geodesic, which only reads the grid, has further batches to go in front of whatever comes next.
+        bool grid_unsettled() const { return fill.pending || thin.pending || oct.expandPending; }
+        bool unsettled() const { return grid_unsettled() || geo.pending; }
+        // a launch replaces the grid: a fill of it that has not converged yet is dropped (its batch in the stream ends in front of the launch), a
+        // thin likewise (it stopped where that batch ended), and a geodesic map of it (stale from here on, nobody can read it)
+        void drop_unsettled()
+        {
+            fill.pending = false;
+            if (thin.pending) { thin.pending = false; thin.converged = false; }
+            geo.pending = false;
+        }
+        void trim_products() { dist.trim(); mdist.trim(); fill.trim(); iso.trim(); oct.trim(); comp.trim(); morph.trim(); thin.trim(); thick.trim(); geo.trim(); }
     };
     Frame frames[DXV_FRAME_COUNT];
     uint32_t cur = 0;                    // dxv_set_frame
@@ -359,18 +400,20 @@ struct dxv_ctx {
         uint32_t rootInfo[16];
         unsigned long long listTotal;
         uint32_t listLongest, pad;
-        uint32_t status[DXV_FRAME_COUNT][4];
-        uint32_t queueLens[DXV_FRAME_COUNT][16 * 64];    // the sixteen count words of a frame's queue (light and heavy bricks of the eight queues; each in a 256-byte line of its own)
-        uint32_t preparedLens[16 * 64];                  // ... of a queue that is being prepared
-        uint32_t fillCtl[DXV_FRAME_COUNT][64];           // the control block of a frame's last fill batch (kFillMaxRounds words)
-        unsigned long long isoTotals[DXV_FRAME_COUNT][2]; // vertices and quads of the mesh a frame is extracting: sizes its buffers
-        unsigned long long octTotals[DXV_FRAME_COUNT][12]; // level_first[0 .. L] of the tree a frame is building: sizes its node buffer
-        unsigned long long compTotal[DXV_FRAME_COUNT];    // K of the labelling a frame is building: sizes its table
-        unsigned long long compSel[DXV_FRAME_COUNT][4];   // kept, dropped, voxels changed and the largest component's key of a frame's last select
-        unsigned long long morphCount[DXV_FRAME_COUNT][2]; // voxels set and voxels cleared by a frame's last morph
-        dxv::ThinControl thinCtl[DXV_FRAME_COUNT];       // the control block of a frame's last thin batch and the voxels removed so far
-        unsigned long long thickCount[DXV_FRAME_COUNT][4]; // centres painted, work items, voxels tested and atomics sent of a frame's last thickness
-        dxv::GeoControl geoCtl[DXV_FRAME_COUNT];         // the control block of a frame's last geodesic batch and the tally behind it
+        uint32_t preparedLens[16 * 64];                  // the sixteen count words of a queue that is being prepared (as PerFrame::queueLens)
+        struct PerFrame {
+            uint32_t status[4];
+            uint32_t queueLens[16 * 64];                 // the sixteen count words of the frame's queue (light and heavy bricks of the eight queues; each in a 256-byte line of its own)
+            uint32_t fillCtl[64];                        // the control block of the frame's last fill batch (kFillMaxRounds words)
+            unsigned long long isoTotals[2];             // vertices and quads of the mesh the frame is extracting: sizes its buffers
+            unsigned long long octTotals[12];            // level_first[0 .. L] of the tree the frame is building: sizes its node buffer
+            unsigned long long compTotal;                // K of the labelling the frame is building: sizes its table
+            unsigned long long compSel[4];               // kept, dropped, voxels changed and the largest component's key of the frame's last select
+            unsigned long long morphCount[2];            // voxels set and voxels cleared by the frame's last morph
+            dxv::ThinControl thinCtl;                    // the control block of the frame's last thin batch and the voxels removed so far
+            unsigned long long thickCount[4];            // centres painted, work items, voxels tested and atomics sent of the frame's last thickness
+            dxv::GeoControl geoCtl;                      // the control block of the frame's last geodesic batch and the tally behind it
+        } frame[DXV_FRAME_COUNT];
     };
     Pinned* pin = nullptr;
     hipEvent_t evList[4] = {};       // around the counting pass, around the rest of the build
@@ -426,6 +469,7 @@ int fail(dxv_ctx* c, const char* fmt, ...);          // dxv_api.hip: message int
 
 using Frame = dxv_ctx::Frame;
 inline Frame& cur_frame(dxv_ctx* c) { return c->frames[c->cur]; }
+inline const Frame& cur_frame(const dxv_ctx* c) { return c->frames[c->cur]; }
 inline hipStream_t frame_stream(dxv_ctx* c, uint32_t i) { return i == 0 ? c->stream : c->frames[i].ownStream; }
 inline hipStream_t cur_stream(dxv_ctx* c) { return frame_stream(c, c->cur); }
 inline Node* scene_nodes(dxv_ctx* c) { return reinterpret_cast<Node*>(c->scene.p + c->hdr.offNodes); }
@@ -462,9 +506,12 @@ inline float elapsed(hipEvent_t a, hipEvent_t b)
     return ms;
 }
 
-// The grid of a frame was rewritten, by a launch or in place: whatever was made of it before is stale from here on.  (An edit in place
-// also drops the kept memset, clearSig = 0, next to this call; a launch keeps its own account of that.)
+// The grid of a frame was rewritten, by a launch or in place: whatever was made of it before -- fields, the mesh, the tree, labels, maps -- is
+// stale from here on.
 inline void grid_rewritten(Frame& f) { ++f.gridVersion; }
+// ... in place: the grid also stops being what the frame's last launch wrote, so a kept queue's zeros are gone (the next launch clears
+// everything; the caller holds no pointer because of this, so ptrExposed stays).  A launch keeps its own account of that.
+inline void edited_in_place(Frame& f) { f.clearSig = 0; grid_rewritten(f); }
 // A frame's timers.  begin: the pair is disarmed before its first event is recorded again -- a first event recorded again and an old second
 // one are no pair; end: armed once the second event is in the stream (whatever the caller enqueues behind it: both events can be read); read: what a synchronisation of the frame does with an armed pair.
 inline hipError_t timer_begin(Timer& t, bool timed, hipStream_t s)
@@ -514,7 +561,7 @@ int check_slab(dxv_ctx* c, const char* who, uint32_t N, uint32_t z0, uint32_t nz
 int check_interleave(dxv_ctx* c, const char* who, uint32_t N, uint32_t rank, uint32_t world, uint32_t zblock);
 // dxv_products.hip
 void read_products(dxv_ctx* c, uint32_t i);                // the counters of the frame's last select, morph and thickness, once its stream has been waited for
-int settle_fill(dxv_ctx* c, uint32_t i);                   // the verdict of the frame's last fill batch; further batches until one has converged
+int settle_fill(dxv_ctx* c, uint32_t i);                   // the verdict of the frame's last fill batch; further batches until one has converged (settle_batched)
 int settle_thin(dxv_ctx* c, uint32_t i);                   // ... of the frame's last thin batch; further batches until the fixed point or max_iterations
 int settle_geodesic(dxv_ctx* c, uint32_t i);               // ... of the frame's last geodesic batch; further batches until a round finds nothing live
 int settle_expand(dxv_ctx* c, uint32_t i);                 // the verdict of an expansion from a caller's tree

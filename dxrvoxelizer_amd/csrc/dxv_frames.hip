@@ -558,7 +558,7 @@ int voxelize_common(dxv_ctx* c, uint32_t N, int mode, uint32_t z0, uint32_t nzLo
     // the frame's previous launch is checked before its grid is reused -- when it can have anything to report: a launch
     // through the lists has no column to run out of, and the next launch simply queues behind it on the frame's stream
     // (no host round trip between back-to-back launches: 20 us of a 0.15 ms launch at 8 ranks)
-    if (((f.pending && f.lastCanFail) || f.octExpandPending) && sync_frame(c, c->cur)) return 1;
+    if (((f.pending && f.lastCanFail) || f.oct.expandPending) && sync_frame(c, c->cur)) return 1;
     const size_t bytes = (size_t)N * N * nzLocal;
     if (bytes > f.grid.cap) {
         DXV_HIP(c, f.grid.reserve(bytes, align256(bytes), fs));
@@ -573,9 +573,7 @@ int voxelize_common(dxv_ctx* c, uint32_t N, int mode, uint32_t z0, uint32_t nzLo
     f.grid_dim = N; f.z0 = z0; f.nz = nzLocal;
     f.lastMode = mode; f.lastZBlock = zBlock; f.lastZPeriod = zPeriod;
     grid_rewritten(f);                                                  // (whatever was made of the grid this launch replaces is stale)
-    f.fillPending = false;                                              // (... and a fill of it that has not converged yet is dropped: its batch in the stream ends in front of this launch)
-    if (f.thinPending) { f.thinPending = false; f.thinConverged = false; }      // (... and a thin of it likewise: it stopped where that batch ended)
-    f.geoPending = false;                                               // (... and a geodesic map of it: stale from here on, nobody can read it)
+    f.drop_unsettled();                                                 // (... and an operator in batches whose verdict nobody has read is dropped with it)
     return launch_now(c, c->cur);
 }
 
@@ -586,15 +584,15 @@ static int sync_launch(dxv_ctx* c, uint32_t i)
     const hipStream_t fs = frame_stream(c, i);
     for (int attempt = 0; attempt < 8; ++attempt) {
         // status words and the queue's header in one round trip, into page-locked words
-        uint32_t* words = c->pin->status[i];
+        dxv_ctx::Pinned::PerFrame& pin = c->pin->frame[i];
+        uint32_t* words = pin.status;
         const bool readQueue = f.pending && f.lastQueued;
         DXV_HIP(c, hipMemcpyAsync(words, f.status.p, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, fs));
-        if (readQueue) DXV_HIP(c, hipMemcpyAsync(c->pin->queueLens[i], f.queue.p + f.queueHdr * kQueueHeaderWords + queue_len_word(0), sizeof(c->pin->queueLens[i]), hipMemcpyDeviceToHost, fs));
-        if (f.octExpandPending) DXV_HIP(c, hipMemcpyAsync(words + kOctStatusWord, f.status.p + kOctStatusWord, sizeof(uint32_t), hipMemcpyDeviceToHost, fs));
+        if (readQueue) DXV_HIP(c, hipMemcpyAsync(pin.queueLens, f.queue.p + f.queueHdr * kQueueHeaderWords + queue_len_word(0), sizeof(pin.queueLens), hipMemcpyDeviceToHost, fs));
+        if (f.oct.expandPending) DXV_HIP(c, hipMemcpyAsync(words + kOctStatusWord, f.status.p + kOctStatusWord, sizeof(uint32_t), hipMemcpyDeviceToHost, fs));
         DXV_HIP(c, hipStreamSynchronize(fs));
         f.sceneReadPending = false;                                     // (whatever read the scene on this stream has finished)
-        for (int u = kTimerFirstOperator; u < kTimers; ++u)
-            if (u != kTimerFill && u != kTimerThin && u != kTimerGeodesic) timer_read(f.timers[u]);    // (the fill's pair is settle_fill's, the thin's settle_thin's, the geodesic's settle_geodesic's: further batches move their second event)
+        for (int u = kTimerFirstOperator; u < kTimerFirstBatched; ++u) timer_read(f.timers[u]);     // (the pairs behind them are read where their operators are settled: further batches move their second event)
         read_products(c, i);
         // lists this launch was queued behind without waiting for their verdict: withdrawn -> the launch again, through the tree
         if (settle_lists(c)) return 1;
@@ -608,7 +606,7 @@ static int sync_launch(dxv_ctx* c, uint32_t i)
             f.voxelize_ms = f.timed ? elapsed(f.timers[kTimerLaunch].e0, f.timers[kTimerLaunch].e1) : 0.0f;
             f.redo_rays = f.lastRedoParity < 0 ? 0u : words[1 + f.lastRedoParity];
             if (readQueue) {
-                f.plan_bricks = decode_queue_lens(c->pin->queueLens[i], f.queueLens);
+                f.plan_bricks = decode_queue_lens(pin.queueLens, f.queueLens);
                 f.queueLenSig = f.clearSig;                             // (the queue of this signature: 0 = none kept)
                 if (f.lastRebuilt) f.plan_ms = f.timed ? elapsed(f.timers[kTimerQueue].e0, f.timers[kTimerQueue].e1) : 0.0f;
             }
@@ -629,7 +627,7 @@ static int sync_launch(dxv_ctx* c, uint32_t i)
     return 0;
 }
 
-// ... then the fill's half and an expansion's verdict (dxv_products.hip)
+// ... then the halves of the operators that run in batches, and an expansion's verdict (dxv_products.hip)
 int sync_frame(dxv_ctx* c, uint32_t i)
 {
     if (sync_launch(c, i)) return 1;
@@ -664,9 +662,7 @@ int settle_frame_launch(dxv_ctx* c)
     if (settle_lists(c)) return 1;                                     // (waits for a list build's end, not for the launch behind it)
     Frame& f = cur_frame(c);
     if (f.pending && (f.lastCanFail || (f.usedLists && f.listEpochUsed == c->withdrawnEpoch))) return sync_frame(c, c->cur);
-    if (f.octExpandPending) return sync_frame(c, c->cur);               // an expansion from a caller's tree whose verdict is not in yet
-    if (f.fillPending || f.thinPending) return sync_frame(c, c->cur);   // a fill or a thin whose verdict is not in yet: what is behind it must see the final grid
-    if (f.geoPending) return sync_frame(c, c->cur);                     // a geodesic whose verdict is not in yet: its further batches go in front of whatever comes now
+    if (f.unsettled()) return sync_frame(c, c->cur);                    // an operator's verdict is not in yet: what is behind it must see the final grid, and further batches go in front of whatever comes now
     return 0;
 }
 

@@ -1,6 +1,9 @@
 // dxv_products.hip -- what is made of a frame's grid, and what edits it in place: distance field, mesh distance field, isosurface, octree and
-// its expansion, components, their measures and select, fill, morph, thin -- the host side of each (the kernels: distance.hip, mesh_distance.hip,
-// isosurface.hip, octree.hip, components.hip, measure.hip, thickness.hip, geodesic.hip, fill.hip, morph.hip, thin.hip), the accessors of what they made, and their halves of a frame's synchronisation.
+// its expansion, components, their measures and select, thickness, geodesic distance, fill, morph, thin -- the host side of each (the kernels:
+// distance.hip, mesh_distance.hip, isosurface.hip, octree.hip, components.hip, measure.hip, thickness.hip, geodesic.hip, fill.hip, morph.hip,
+// thin.hip), the accessors of what they made, and their halves of a frame's synchronisation.  Each operator has a record in Frame (dxv_ctx.h);
+// what they share is here, in front of them: the refusals (check_whole_grid, check_current), an operator's first and last steps (begin_operator,
+// end_operator, blocking), the download of a product (download_current) and the loop of the operators that run in batches (settle_batched).
 #include "dxv_ctx.h"
 #include "dxv_mesh_distance.h"
 #include "dxv_fill.h"
@@ -18,12 +21,39 @@ using namespace dxvhost;
 
 namespace dxvhost {
 
+using PinnedFrame = dxv_ctx::Pinned::PerFrame;
+static PinnedFrame& cur_pinned(dxv_ctx* c) { return c->pin->frame[c->cur]; }
+
 // the refusals of whatever works on the whole grid of the selected frame
 static int check_whole_grid(dxv_ctx* c, const char* who)
 {
     const Frame& f = cur_frame(c);
     if (!f.grid.p || !f.grid_dim) return fail(c, "%s: frame %u has no grid yet (call dxv_voxelize first)", who, c->cur);
     if (!frame_renderable(f)) return fail(c, "%s: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share", who);
+    return 0;
+}
+
+// What the refusals call a product: its noun, the call that makes it, and what is said once the grid has moved on.  The stale sentences
+// differ from family to family on purpose -- each names what could have rewritten the grid when its product was added -- and dxv_isosurface
+// speaks of a distance field in its own words.
+struct ProductText { const char *noun, *maker, *stale; };
+static const ProductText kDistanceText = {"distance field", "dxv_distance", "was launched again since its distance field was made: the field is stale"};
+static const ProductText kDistanceTextOfIso = {"distance field", "dxv_distance", "was launched or filled again since its distance field was made: the field is stale"};
+static const ProductText kMeshDistanceText = {"mesh distance field", "dxv_mesh_distance", "was launched or filled again since its mesh distance field was made: the field is stale"};
+static const ProductText kIsoText = {"isosurface", "dxv_isosurface", "was launched or filled again since its isosurface was made: the mesh is stale"};
+static const ProductText kOctreeText = {"octree", "dxv_octree", "was launched, filled or expanded again since its octree was made: the tree is stale"};
+static const ProductText kComponentsText = {"components", "dxv_components",
+                                            "was launched, filled, expanded or selected again since its components were labelled: labels and table are stale"};
+static const ProductText kMeasureText = {"measure", "dxv_measure", "was launched, edited or labelled again since its components were measured: the measure is stale"};
+static const ProductText kThicknessText = {"thickness map", "dxv_thickness", "was launched or edited again since its thickness map was made: map and histogram are stale"};
+static const ProductText kGeodesicText = {"geodesic map", "dxv_geodesic", "was launched or edited again since its geodesic map was made: the map is stale"};
+
+// whether the selected frame has this product to hand out: 0, or 1 with the reason as the message
+static int check_current(const dxv_ctx* c, const char* who, const Frame::Made& made, const ProductText& text)
+{
+    dxv_ctx* w = const_cast<dxv_ctx*>(c);                               // (the message is the one thing an accessor writes)
+    if (!made.have) return fail(w, "%s: frame %u has no %s yet (call %s first)", who, c->cur, text.noun, text.maker);
+    if (made.version != cur_frame(c).gridVersion) return fail(w, "%s: frame %u %s", who, c->cur, text.stale);
     return 0;
 }
 
@@ -49,142 +79,159 @@ static int timer_ms(dxv_ctx* c, const char* who, TimerUse use, float* ms)
     return 0;
 }
 
-// dxv_sync of one frame (sync_launch, once the stream has been waited for): the counters a select and a morph left in page-locked words
+// An operator's first step once it has refused what it must: the device, then dxv_render_async's host-wait rule -- the host waits for the
+// selected frame only while it can still report something (settle_frame_launch) --, then the frame's stream, behind whatever it holds.
+static int begin_operator(dxv_ctx* c, hipStream_t* fs)
+{
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (settle_frame_launch(c)) return 1;
+    *fs = cur_stream(c);
+    return 0;
+}
+// ... and its last: the second event of its timer (none: nullptr), what it reports into page-locked words for the frame's next
+// synchronisation (none: nullptr), and the frame's end event, which nobody waits for here
+static int end_operator(dxv_ctx* c, Frame& f, hipStream_t fs, Timer* t, void* words = nullptr, const void* counters = nullptr, size_t bytes = 0)
+{
+    if (t) DXV_HIP(c, timer_end(*t, c->opt.events != 0, fs));
+    if (words) DXV_HIP(c, hipMemcpyAsync(words, counters, bytes, hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    return 0;
+}
+// dxv_x(...) is dxv_x_async(...) and a synchronisation of the frame
+static int blocking(dxv_ctx* c, int enqueued) { return enqueued ? 1 : dxv_sync(c); }
+
+// dxv_sync of one frame (sync_launch, once the stream has been waited for): the counters a select, a morph and a thickness left in page-locked words
 void read_products(dxv_ctx* c, uint32_t i)
 {
     Frame& f = c->frames[i];
-    if (f.selPending) {                                                 // the counters of the frame's last select (k_comp_keep has the LARGEST case)
-        const unsigned long long* sel = c->pin->compSel[i];
-        const bool largest = f.selRule == DXV_SELECT_LARGEST && f.selComponents;
-        f.selKept = largest ? 1u : (uint32_t)sel[0];
-        f.selDropped = largest ? f.selComponents - 1u : (uint32_t)sel[1];
-        f.selChanged = largest ? sel[2] - (sel[3] >> 32) : sel[2];
-        f.selPending = false;
+    const PinnedFrame& pin = c->pin->frame[i];
+    if (Frame::Components::Select& sel = f.comp.select; sel.pending) {  // the counters of the frame's last select (k_comp_keep has the LARGEST case)
+        const bool largest = sel.rule == DXV_SELECT_LARGEST && sel.components;
+        sel.kept = largest ? 1u : (uint32_t)pin.compSel[0];
+        sel.dropped = largest ? sel.components - 1u : (uint32_t)pin.compSel[1];
+        sel.changed = largest ? pin.compSel[2] - (pin.compSel[3] >> 32) : pin.compSel[2];
+        sel.pending = false;
     }
-    if (f.morphPending) {                                               // the counters of the frame's last morph
-        f.morphSet = c->pin->morphCount[i][0];
-        f.morphCleared = c->pin->morphCount[i][1];
-        f.morphPending = false;
+    if (f.morph.pending) {                                              // the counters of the frame's last morph
+        f.morph.set = pin.morphCount[0];
+        f.morph.cleared = pin.morphCount[1];
+        f.morph.pending = false;
     }
-    if (f.thickPending) {                                               // the counters of the frame's last thickness
-        f.thickCentres = c->pin->thickCount[i][0];
-        f.thickItems = c->pin->thickCount[i][1];
-        f.thickTested = c->pin->thickCount[i][2];
-        f.thickSent = c->pin->thickCount[i][3];
-        f.thickPending = false;
+    if (f.thick.pending) {                                              // the counters of the frame's last thickness
+        f.thick.centres = pin.thickCount[0];
+        f.thick.items = pin.thickCount[1];
+        f.thick.tested = pin.thickCount[2];
+        f.thick.sent = pin.thickCount[3];
+        f.thick.pending = false;
     }
 }
 
-// ... and the fill's half, behind it (the stream has been waited for): the verdict of the frame's last fill batch.  A batch whose last
-// round still changed a word has not converged: further batches -- rounds and write-back, from the masks the frame's scratch still
-// holds -- are enqueued and waited for until one has (the pattern of settle_lists: what only the host can decide is decided where the
-// frame is synchronised anyway).  A flood over V voxels reaches at least one new voxel per live round: fewer than V rounds.
+// ... and the half of an operator that runs in batches of rounds, behind it (the stream has been waited for): the verdict of the frame's last
+// batch.  The batch's control block, in page-locked words by now, begins with a word per round: != 0, the round was live -- it still changed
+// something.  A batch one of whose rounds was not live has reached the fixed point, that round confirming it.  Otherwise a further batch --
+// from what the frame's scratch still holds -- is enqueued and waited for (the pattern of settle_lists: what only the host can decide is
+// decided where the frame is synchronised anyway), its control block copied behind it, the timer's second event moved behind it.  Every
+// live round reaches, removes or lowers at least one of the V voxels: the guard against an operator that never settles is V rounds.
+struct Batched {
+    const char *who, *unit;           // for the guard's message: "dxv_fill", "rounds"
+    TimerUse timer;
+    uint32_t N;                       // side of the grid the batches run on
+    bool* pending;                    // a batch is in the stream whose verdict nobody has read yet
+    uint32_t perBatch;                // rounds per batch ...
+    const uint32_t* inStream;         // ... and of the batch in the stream (a bounded run's last batch is shorter)
+    const uint32_t* done;             // rounds so far, for the guard's message
+    void* ctl;                        // the control block in page-locked words ...
+    const void* deviceCtl;            // ... and on the device, while a batch is pending
+    size_t ctlBytes;
+};
+// account(live, last): the batch in the stream had `live` live rounds (last: and then one that was not) -- adds them to the frame's counters and
+// says whether the operator is finished; launch(fs): sizes and enqueues the next batch.
+template <class Account, class Launch> static int settle_batched(dxv_ctx* c, uint32_t i, const Batched& b, Account account, Launch launch)
+{
+    Frame& f = c->frames[i];
+    const hipStream_t fs = frame_stream(c, i);
+    const uint32_t* words = static_cast<const uint32_t*>(b.ctl);
+    Timer& t = f.timers[b.timer];
+    const uint64_t most = b.perBatch ? (uint64_t)b.N * b.N * b.N / b.perBatch + 2u : 0u;
+    for (uint64_t batch = 0; *b.pending; ++batch) {
+        uint32_t live = 0;
+        while (live < *b.inStream && words[live]) ++live;
+        if (account(live, live < *b.inStream)) {
+            *b.pending = false;
+            break;
+        }
+        if (batch >= most) return fail(c, "%s: no fixed point after %u %s on a grid of %u^3 voxels", b.who, *b.done, b.unit, b.N);
+        DXV_HIP(c, launch(fs));
+        if (t.armed) DXV_HIP(c, hipEventRecord(t.e1, fs));
+        DXV_HIP(c, hipMemcpyAsync(b.ctl, b.deviceCtl, b.ctlBytes, hipMemcpyDeviceToHost, fs));
+        DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+        DXV_HIP(c, hipStreamSynchronize(fs));
+    }
+    timer_read(t);
+    return 0;
+}
+
+// the fill's: a batch whose last round still changed a word has not converged; a further batch is rounds and write-back from the masks
 int settle_fill(dxv_ctx* c, uint32_t i)
 {
     Frame& f = c->frames[i];
-    const hipStream_t fs = frame_stream(c, i);
-    const uint32_t* ctl = c->pin->fillCtl[i];
-    Timer& t = f.timers[kTimerFill];
+    Frame::Fill& o = f.fill;
+    uint32_t* ctl = c->pin->frame[i].fillCtl;
     const uint32_t N = f.grid_dim;
-    const uint64_t most = f.fillBatch ? (uint64_t)N * N * N / f.fillBatch + 2u : 0u;
-    for (uint64_t batch = 0; f.fillPending; ++batch) {
-        uint32_t live = 0;
-        while (live < f.fillBatch && ctl[live]) ++live;
-        if (live < f.fillBatch) {                                       // round `live` changed nothing: the confirming round
-            f.fillRounds += live + 1u;
-            f.fillPending = false;
-            break;
-        }
-        f.fillRounds += f.fillBatch;
-        if (batch >= most) return fail(c, "dxv_fill: no fixed point after %u rounds on a grid of %u^3 voxels", f.fillRounds, N);
-        DXV_HIP(c, launch_fill(f.grid.p, N, f.fillWhat, f.fillScratch.p, f.fillBatch, false, fs));
-        if (t.armed) DXV_HIP(c, hipEventRecord(t.e1, fs));
-        DXV_HIP(c, hipMemcpyAsync(c->pin->fillCtl[i], fill_control(f.fillScratch.p, N), sizeof(c->pin->fillCtl[i]), hipMemcpyDeviceToHost, fs));
-        DXV_HIP(c, hipEventRecord(f.evEnd, fs));
-        DXV_HIP(c, hipStreamSynchronize(fs));
-    }
-    timer_read(t);
-    return 0;
+    const Batched b{"dxv_fill", "rounds", kTimerFill, N, &o.pending, o.batch, &o.batch, &o.rounds, ctl, o.pending ? fill_control(o.scratch.p, N) : nullptr, sizeof(c->pin->frame[i].fillCtl)};
+    return settle_batched(c, i, b,
+        [&](uint32_t live, bool last) { o.rounds += last ? live + 1u : o.batch; return last; },
+        [&](hipStream_t fs) { return launch_fill(f.grid.p, N, o.what, o.scratch.p, o.batch, false, fs); });
 }
 
-// ... and the thin's, beside it (the stream has been waited for): the verdict of the frame's last thin batch, by the fill's discipline.  A batch all
-// of whose iterations removed something has not reached the fixed point: unless max_iterations has been used up, a further batch -- iterations and
-// write-back, from the masks the frame's scratch still holds -- is enqueued and waited for.  Every live iteration removes at least one of the
-// V voxels: fewer than V iterations.
+// the thin's: a batch all of whose iterations removed something has not reached the fixed point; unless max_iterations has been used up, a
+// further batch is iterations and write-back from the masks
 int settle_thin(dxv_ctx* c, uint32_t i)
 {
     Frame& f = c->frames[i];
-    const hipStream_t fs = frame_stream(c, i);
-    const ThinControl& ctl = c->pin->thinCtl[i];
-    Timer& t = f.timers[kTimerThin];
+    Frame::Thin& o = f.thin;
+    ThinControl& ctl = c->pin->frame[i].thinCtl;
     const uint32_t N = f.grid_dim;
-    const uint64_t most = f.thinBatch ? (uint64_t)N * N * N / f.thinBatch + 2u : 0u;
-    for (uint64_t batch = 0; f.thinPending; ++batch) {
-        uint32_t live = 0;
-        while (live < f.thinInBatch && ctl.live[live]) ++live;
-        f.thinRemoved = ctl.removed;
-        if (live < f.thinInBatch) {                                     // iteration `live` removed nothing: the confirming iteration
-            f.thinIterations += live + 1u;
-            f.thinConverged = true;
-            f.thinPending = false;
-            break;
-        }
-        f.thinIterations += f.thinInBatch;
-        if (f.thinBounded && !f.thinLeft) {                             // max_iterations stopped it first
-            f.thinPending = false;
-            break;
-        }
-        if (batch >= most) return fail(c, "dxv_thin: no fixed point after %u iterations on a grid of %u^3 voxels", f.thinIterations, N);
-        f.thinInBatch = thin_batch(f.thinBatch, f.thinBounded ? f.thinLeft : 0u);
-        if (f.thinBounded) f.thinLeft -= f.thinInBatch;
-        DXV_HIP(c, launch_thin(f.grid.p, N, f.thinKind, f.thinScratch.p, f.thinInBatch, false, fs));
-        if (t.armed) DXV_HIP(c, hipEventRecord(t.e1, fs));
-        DXV_HIP(c, hipMemcpyAsync(&c->pin->thinCtl[i], f.thinScratch.p, sizeof(ThinControl), hipMemcpyDeviceToHost, fs));
-        DXV_HIP(c, hipEventRecord(f.evEnd, fs));
-        DXV_HIP(c, hipStreamSynchronize(fs));
-    }
-    timer_read(t);
-    return 0;
+    const Batched b{"dxv_thin", "iterations", kTimerThin, N, &o.pending, o.batch, &o.inBatch, &o.iterations, &ctl, o.scratch.p, sizeof(ThinControl)};
+    return settle_batched(c, i, b,
+        [&](uint32_t live, bool last) {
+            o.removed = ctl.removed;
+            o.iterations += last ? live + 1u : o.inBatch;
+            if (last) o.converged = true;
+            return last || (o.bounded && !o.left);                      // (... or max_iterations stopped it first)
+        },
+        [&](hipStream_t fs) {
+            o.inBatch = thin_batch(o.batch, o.bounded ? o.left : 0u);
+            if (o.bounded) o.left -= o.inBatch;
+            return launch_thin(f.grid.p, N, o.kind, o.scratch.p, o.inBatch, false, fs);
+        });
 }
 
-// ... and the geodesic's (the stream has been waited for): the verdict of the frame's last geodesic batch, by the fill's discipline.  Word k of the
-// control block is the number of live tiles of round k: a batch all of whose rounds had some has not reached the fixed point, and a further batch
-// -- rounds from the flags the frame's scratch still holds, then the tally again -- is enqueued and waited for.  Every live round but the last
-// lowers at least one word; the guard against a map that never settles is V rounds.
+// the geodesic's: word k of the control block is the number of live tiles of round k; a further batch is rounds from the flags the frame's
+// scratch still holds, then the tally again, which is read behind the confirming round only
 int settle_geodesic(dxv_ctx* c, uint32_t i)
 {
     Frame& f = c->frames[i];
-    const hipStream_t fs = frame_stream(c, i);
-    const GeoControl& ctl = c->pin->geoCtl[i];
-    Timer& t = f.timers[kTimerGeodesic];
-    const uint32_t N = f.geoDim;
-    const uint64_t most = f.geoBatch ? (uint64_t)N * N * N / f.geoBatch + 2u : 0u;
-    for (uint64_t batch = 0; f.geoPending; ++batch) {
-        uint32_t live = 0;
-        while (live < f.geoBatch && ctl.live[live]) ++live;
-        for (uint32_t k = 0; k < live; ++k) {                           // what the batch's live rounds ran (dxv_geodesic_work_info)
-            f.geoTilesRun += ctl.live[k];
-            if (ctl.live[k] > f.geoMostLive) f.geoMostLive = ctl.live[k];
-            if (ctl.live[k] < kGeoSparseTiles) ++f.geoSparseRounds;
-        }
-        if (live < f.geoBatch) {                                        // round `live` found nothing live: the confirming round
-            GeoTally tally{ctl.tally[0], ctl.tally[1], ctl.tally[2], ctl.tally[3]};
-            f.geoRounds += live + 1u;
-            f.geoSeedsUsed = tally.seeds; f.geoReached = tally.reached; f.geoUnreached = tally.unreached;
-            f.geoFarthest = geo_tally_farthest(tally); f.geoFarthestVoxel = geo_tally_farthest_voxel(tally);
-            f.geoPending = false;
-            break;
-        }
-        f.geoRounds += f.geoBatch;
-        if (batch >= most) return fail(c, "dxv_geodesic: no fixed point after %u rounds on a grid of %u^3 voxels", f.geoRounds, N);
-        DXV_HIP(c, launch_geodesic_batch(f.geo.p, N, f.geoMetric, f.geoLimit, f.geoScratch.p, f.geoBatch, f.geoRounds, fs));
-        if (t.armed) DXV_HIP(c, hipEventRecord(t.e1, fs));
-        DXV_HIP(c, hipMemcpyAsync(&c->pin->geoCtl[i], f.geoScratch.p, sizeof(GeoControl), hipMemcpyDeviceToHost, fs));
-        DXV_HIP(c, hipEventRecord(f.evEnd, fs));
-        DXV_HIP(c, hipStreamSynchronize(fs));
-    }
-    timer_read(t);
-    return 0;
+    Frame::Geodesic& o = f.geo;
+    GeoControl& ctl = c->pin->frame[i].geoCtl;
+    const uint32_t N = o.dim;
+    const Batched b{"dxv_geodesic", "rounds", kTimerGeodesic, N, &o.pending, o.batch, &o.batch, &o.rounds, &ctl, o.scratch.p, sizeof(GeoControl)};
+    return settle_batched(c, i, b,
+        [&](uint32_t live, bool last) {
+            for (uint32_t k = 0; k < live; ++k) {                       // what the batch's live rounds ran (dxv_geodesic_work_info)
+                o.tilesRun += ctl.live[k];
+                if (ctl.live[k] > o.mostLive) o.mostLive = ctl.live[k];
+                if (ctl.live[k] < kGeoSparseTiles) ++o.sparseRounds;
+            }
+            o.rounds += last ? live + 1u : o.batch;
+            if (last) {
+                const GeoTally tally{ctl.tally[0], ctl.tally[1], ctl.tally[2], ctl.tally[3]};
+                o.seedsUsed = tally.seeds; o.reached = tally.reached; o.unreached = tally.unreached;
+                o.farthest = geo_tally_farthest(tally); o.farthestVoxel = geo_tally_farthest_voxel(tally);
+            }
+            return last;
+        },
+        [&](hipStream_t fs) { return launch_geodesic_batch(o.map.p, N, o.metric, o.limit, o.scratch.p, o.batch, o.rounds, fs); });
 }
 
 // ... and the verdict of an expansion from a caller's tree (sync_launch has read the word): an index that could not be followed left empty
@@ -192,9 +239,9 @@ int settle_geodesic(dxv_ctx* c, uint32_t i)
 int settle_expand(dxv_ctx* c, uint32_t i)
 {
     Frame& f = c->frames[i];
-    if (!f.octExpandPending) return 0;
-    f.octExpandPending = false;
-    if (!c->pin->status[i][kOctStatusWord]) return 0;
+    if (!f.oct.expandPending) return 0;
+    f.oct.expandPending = false;
+    if (!c->pin->frame[i].status[kOctStatusWord]) return 0;
     DXV_HIP(c, hipMemsetAsync(f.status.p + kOctStatusWord, 0, sizeof(uint32_t), frame_stream(c, i)));
     return fail(c, "dxv_octree_expand: the tree given for frame %u cannot be followed (a child index at or beyond its node count, or cells still mixed "
                    "after all its levels); the voxels behind such an index were left empty", i);
@@ -214,54 +261,37 @@ int dxv_distance_async(dxv_ctx* c, int format)
         return fail(c, "dxv_distance: unknown format %d (DXV_DIST_SQ_I32 = 0, DXV_DIST_F32 = 1)", format);
     if (check_whole_grid(c, "dxv_distance")) return 1;
     Frame& f = cur_frame(c);
-    DXV_HIP(c, hipSetDevice(c->device));
-    if (settle_frame_launch(c)) return 1;
-    const hipStream_t fs = cur_stream(c);
+    hipStream_t fs;
+    if (begin_operator(c, &fs)) return 1;
     const uint32_t N = f.grid_dim;
     const size_t voxels = (size_t)N * N * N, scratch = distance_scratch_bytes(N);
-    f.distVersion = 0; f.distDim = 0;
-    DXV_HIP(c, f.dist.reserve(voxels, align256(voxels * sizeof(int32_t)), fs));
-    DXV_HIP(c, f.distScratch.reserve(scratch, scratch, fs));
-    const bool timed = c->opt.events != 0;
-    DXV_HIP(c, timer_begin(f.timers[kTimerDistance], timed, fs));
-    DXV_HIP(c, launch_distance(f.grid.p, N, format, f.dist.p, f.distScratch.p, fs));
-    DXV_HIP(c, timer_end(f.timers[kTimerDistance], timed, fs));
-    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
-    f.distDim = N; f.distFormat = format; f.distVersion = f.gridVersion;
+    f.dist.version = 0; f.dist.have = false;
+    DXV_HIP(c, f.dist.field.reserve(voxels, align256(voxels * sizeof(int32_t)), fs));
+    DXV_HIP(c, f.dist.scratch.reserve(scratch, scratch, fs));
+    DXV_HIP(c, timer_begin(f.timers[kTimerDistance], c->opt.events != 0, fs));
+    DXV_HIP(c, launch_distance(f.grid.p, N, format, f.dist.field.p, f.dist.scratch.p, fs));
+    if (end_operator(c, f, fs, &f.timers[kTimerDistance])) return 1;
+    f.dist.dim = N; f.dist.format = format; f.dist.have = true; f.dist.version = f.gridVersion;
     return 0;
 }
 
-int dxv_distance(dxv_ctx* c, int format)
+int dxv_distance(dxv_ctx* c, int format) { return blocking(c, dxv_distance_async(c, format)); }
+
+const void* dxv_distance_device_ptr(const dxv_ctx* c)
 {
-    if (dxv_distance_async(c, format)) return 1;
-    return dxv_sync(c);
+    if (!c || check_current(c, "dxv_distance_device_ptr", cur_frame(c).dist, kDistanceText)) return nullptr;
+    return cur_frame(c).dist.field.p;
 }
-
-// the frame's field, or the reason there is none to hand out: NULL + message
-static const int32_t* current_field(const dxv_ctx* c, const char* who)
-{
-    const Frame& f = c->frames[c->cur];
-    dxv_ctx* w = const_cast<dxv_ctx*>(c);                               // (the message is the one thing an accessor writes)
-    if (!f.distDim || !f.dist.p) { (void)fail(w, "%s: frame %u has no distance field yet (call dxv_distance first)", who, c->cur); return nullptr; }
-    if (f.distVersion != f.gridVersion) { (void)fail(w, "%s: frame %u was launched again since its distance field was made: the field is stale", who, c->cur); return nullptr; }
-    return f.dist.p;
-}
-
-const void* dxv_distance_device_ptr(const dxv_ctx* c) { return c ? current_field(c, "dxv_distance_device_ptr") : nullptr; }
-
 size_t dxv_distance_bytes(const dxv_ctx* c)
 {
     if (!c) return 0;
-    const Frame& f = c->frames[c->cur];
-    return f.distVersion == f.gridVersion ? (size_t)f.distDim * f.distDim * f.distDim * sizeof(int32_t) : 0;
+    const Frame::Distance& d = cur_frame(c).dist;
+    return d.current(cur_frame(c)) ? (size_t)d.dim * d.dim * d.dim * sizeof(int32_t) : 0;
 }
-
 int dxv_distance_download(dxv_ctx* c, void* host, size_t bytes)
 {
-    if (!c) return 1;
-    const int32_t* field = current_field(c, "dxv_distance_download");
-    if (!field) return 1;
-    return download_current(c, "dxv_distance_download", field, dxv_distance_bytes(c), host, bytes);
+    if (!c || check_current(c, "dxv_distance_download", cur_frame(c).dist, kDistanceText)) return 1;
+    return download_current(c, "dxv_distance_download", cur_frame(c).dist.field.p, dxv_distance_bytes(c), host, bytes);
 }
 
 int dxv_distance_ms(dxv_ctx* c, float* ms) { return timer_ms(c, "dxv_distance_ms", kTimerDistance, ms); }
@@ -284,47 +314,38 @@ int dxv_mesh_distance_async(dxv_ctx* c, int format, uint32_t bandVoxels, int wan
     if (!c->haveScene) return fail(c, "dxv_mesh_distance: no scene with a built hierarchy (call dxv_build or dxv_scene_import first)");
     if (c->hdr.treeHeight > (uint32_t)kMdStack)
         return fail(c, "dxv_mesh_distance: tree height %u exceeds the walk's column of %d entries", c->hdr.treeHeight, kMdStack);
-    DXV_HIP(c, hipSetDevice(c->device));
-    if (settle_frame_launch(c)) return 1;
-    const hipStream_t fs = cur_stream(c);
+    hipStream_t fs;
+    if (begin_operator(c, &fs)) return 1;
     const bool walk = c->opt.mdistwalk != 0;
     if (walk && ensure_nodes(c, fs)) return 1;                          // after a refit that deferred the node boxes, as before a tree walk
     const uint32_t N = f.grid_dim;
     const size_t voxels = (size_t)N * N * f.nz;
-    f.mdistVersion = 0; f.mdistDim = 0;
-    DXV_HIP(c, f.mdist.reserve(voxels, align256(voxels * sizeof(float)), fs));
-    if (wantTriangles) DXV_HIP(c, f.mdistTri.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
+    f.mdist.version = 0; f.mdist.have = false;
+    DXV_HIP(c, f.mdist.field.reserve(voxels, align256(voxels * sizeof(float)), fs));
+    if (wantTriangles) DXV_HIP(c, f.mdist.tri.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
     MeshDistanceParams p{};
-    p.grid = f.grid.p; p.field = f.mdist.p; p.tris = wantTriangles ? f.mdistTri.p : nullptr;
+    p.grid = f.grid.p; p.field = f.mdist.field.p; p.tris = wantTriangles ? f.mdist.tri.p : nullptr;
     p.N = N; p.z0 = f.z0; p.nz = f.nz;
     p.format = format;
     p.cap = md_cap(N, bandVoxels);
     p.cullAbs = md_cull_abs(c->hdr.rootLo, c->hdr.rootHi);
-    const bool timed = c->opt.events != 0;
-    DXV_HIP(c, timer_begin(f.timers[kTimerMeshDistance], timed, fs));
+    DXV_HIP(c, timer_begin(f.timers[kTimerMeshDistance], c->opt.events != 0, fs));
     DXV_HIP(c, launch_mesh_distance(scene_nodes(c), scene_tripos(c), c->hdr.numTris, p, walk, fs));
-    DXV_HIP(c, timer_end(f.timers[kTimerMeshDistance], timed, fs));
-    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    if (end_operator(c, f, fs, &f.timers[kTimerMeshDistance])) return 1;
     f.sceneReadPending = true;
-    f.mdistDim = N; f.mdistNz = f.nz; f.mdistFormat = format; f.mdistHasTri = wantTriangles != 0; f.mdistVersion = f.gridVersion;
+    f.mdist.dim = N; f.mdist.nz = f.nz; f.mdist.format = format; f.mdist.hasTri = wantTriangles != 0; f.mdist.have = true; f.mdist.version = f.gridVersion;
     return 0;
 }
 
-int dxv_mesh_distance(dxv_ctx* c, int format, uint32_t bandVoxels, int wantTriangles)
-{
-    if (dxv_mesh_distance_async(c, format, bandVoxels, wantTriangles)) return 1;
-    return dxv_sync(c);
-}
+int dxv_mesh_distance(dxv_ctx* c, int format, uint32_t bandVoxels, int wantTriangles) { return blocking(c, dxv_mesh_distance_async(c, format, bandVoxels, wantTriangles)); }
 
 // the frame's mesh distance field (triangles: its nearest triangles), or the reason there is none to hand out: NULL + message
 static const void* current_mesh_field(const dxv_ctx* c, const char* who, bool triangles)
 {
-    const Frame& f = c->frames[c->cur];
-    dxv_ctx* w = const_cast<dxv_ctx*>(c);                               // (the message is the one thing an accessor writes)
-    if (!f.mdistDim || !f.mdist.p) { (void)fail(w, "%s: frame %u has no mesh distance field yet (call dxv_mesh_distance first)", who, c->cur); return nullptr; }
-    if (f.mdistVersion != f.gridVersion) { (void)fail(w, "%s: frame %u was launched or filled again since its mesh distance field was made: the field is stale", who, c->cur); return nullptr; }
-    if (triangles && !f.mdistHasTri) { (void)fail(w, "%s: frame %u's mesh distance field was made without triangles (want_triangles = 0)", who, c->cur); return nullptr; }
-    return triangles ? static_cast<const void*>(f.mdistTri.p) : static_cast<const void*>(f.mdist.p);
+    const Frame::MeshDistance& m = cur_frame(c).mdist;
+    if (check_current(c, who, m, kMeshDistanceText)) return nullptr;
+    if (triangles && !m.hasTri) { (void)fail(const_cast<dxv_ctx*>(c), "%s: frame %u's mesh distance field was made without triangles (want_triangles = 0)", who, c->cur); return nullptr; }
+    return triangles ? static_cast<const void*>(m.tri.p) : static_cast<const void*>(m.field.p);
 }
 
 const void* dxv_mesh_distance_device_ptr(const dxv_ctx* c) { return c ? current_mesh_field(c, "dxv_mesh_distance_device_ptr", false) : nullptr; }
@@ -333,8 +354,8 @@ const void* dxv_mesh_distance_triangles_device_ptr(const dxv_ctx* c) { return c 
 size_t dxv_mesh_distance_bytes(const dxv_ctx* c)
 {
     if (!c) return 0;
-    const Frame& f = c->frames[c->cur];
-    return f.mdistVersion == f.gridVersion ? (size_t)f.mdistDim * f.mdistDim * f.mdistNz * sizeof(float) : 0;
+    const Frame::MeshDistance& m = cur_frame(c).mdist;
+    return m.current(cur_frame(c)) ? (size_t)m.dim * m.dim * m.nz * sizeof(float) : 0;
 }
 
 static int mesh_field_download(dxv_ctx* c, const char* who, bool triangles, void* host, size_t bytes)
@@ -366,32 +387,28 @@ int dxv_isosurface_async(dxv_ctx* c, int source, float iso, int space)
     uint32_t N = 0;
     float P = 1.0f;
     if (source == DXV_ISO_MESH_DISTANCE) {
-        if (!f.mdistDim || !f.mdist.p) return fail(c, "dxv_isosurface: frame %u has no mesh distance field yet (call dxv_mesh_distance first)", c->cur);
-        if (f.mdistVersion != f.gridVersion) return fail(c, "dxv_isosurface: frame %u was launched or filled again since its mesh distance field was made: the field is stale", c->cur);
-        if (f.mdistNz != f.mdistDim)
-            return fail(c, "dxv_isosurface: the frame's mesh distance field is a slab's (%u of %u slices); needs the field of the whole grid", f.mdistNz, f.mdistDim);
-        field = f.mdist.p; N = f.mdistDim;
-        if (f.mdistFormat == DXV_MDIST_UNITS_F32) P = 2.0f / (float)N;
+        if (check_current(c, "dxv_isosurface", f.mdist, kMeshDistanceText)) return 1;
+        if (f.mdist.nz != f.mdist.dim)
+            return fail(c, "dxv_isosurface: the frame's mesh distance field is a slab's (%u of %u slices); needs the field of the whole grid", f.mdist.nz, f.mdist.dim);
+        field = f.mdist.field.p; N = f.mdist.dim;
+        if (f.mdist.format == DXV_MDIST_UNITS_F32) P = 2.0f / (float)N;
     } else {
-        if (!f.distDim || !f.dist.p) return fail(c, "dxv_isosurface: frame %u has no distance field yet (call dxv_distance first)", c->cur);
-        if (f.distVersion != f.gridVersion) return fail(c, "dxv_isosurface: frame %u was launched or filled again since its distance field was made: the field is stale", c->cur);
-        if (f.distFormat != DXV_DIST_F32) return fail(c, "dxv_isosurface: the frame's distance field is in the int32 format; needs DXV_DIST_F32");
-        field = reinterpret_cast<const float*>(f.dist.p); N = f.distDim;
+        if (check_current(c, "dxv_isosurface", f.dist, kDistanceTextOfIso)) return 1;
+        if (f.dist.format != DXV_DIST_F32) return fail(c, "dxv_isosurface: the frame's distance field is in the int32 format; needs DXV_DIST_F32");
+        field = reinterpret_cast<const float*>(f.dist.field.p); N = f.dist.dim;
     }
     if (space == DXV_ISO_SPACE_OBJECT && !c->haveScene)
         return fail(c, "dxv_isosurface: DXV_ISO_SPACE_OBJECT needs the scene's bound and the context has no scene (call dxv_build or dxv_scene_import, or ask for DXV_ISO_SPACE_VOXELS)");
-    DXV_HIP(c, hipSetDevice(c->device));
-    if (settle_frame_launch(c)) return 1;
-    const hipStream_t fs = cur_stream(c);
+    hipStream_t fs;
+    if (begin_operator(c, &fs)) return 1;
     const size_t scratch = iso_scratch_bytes(N);
-    DXV_HIP(c, f.isoScratch.reserve(scratch, scratch, fs));
+    DXV_HIP(c, f.iso.scratch.reserve(scratch, scratch, fs));
     IsoParams p{};
     p.field = field; p.N = N; p.iso = iso; p.P = P; p.object = space == DXV_ISO_SPACE_OBJECT;
     memcpy(p.bound, c->bound, sizeof(p.bound));
-    iso_scratch_layout(f.isoScratch.p, N, p);
-    const bool timed = c->opt.events != 0;
-    unsigned long long* totals = c->pin->isoTotals[c->cur];
-    DXV_HIP(c, timer_begin(f.timers[kTimerIso], timed, fs));
+    iso_scratch_layout(f.iso.scratch.p, N, p);
+    unsigned long long* totals = cur_pinned(c).isoTotals;
+    DXV_HIP(c, timer_begin(f.timers[kTimerIso], c->opt.events != 0, fs));
     DXV_HIP(c, launch_iso_count(p, fs));
     DXV_HIP(c, hipMemcpyAsync(totals, p.totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, fs));
     DXV_HIP(c, hipStreamSynchronize(fs));
@@ -399,65 +416,49 @@ int dxv_isosurface_async(dxv_ctx* c, int source, float iso, int space)
     if (vertices > kIsoMaxCount || quads > kIsoMaxCount / 6u)
         return fail(c, "dxv_isosurface: a mesh of %llu vertices and %llu index words; at most %llu of each (the frame's earlier mesh is kept)", vertices,
                     6u * quads, (unsigned long long)kIsoMaxCount);
-    f.isoVersion = 0;
+    f.iso.version = 0;
     if (vertices) {
-        DXV_HIP(c, f.isoVb.reserve((size_t)vertices, align256((size_t)vertices * sizeof(IsoVertex)), fs));
-        if (quads) DXV_HIP(c, f.isoIb.reserve(6 * (size_t)quads, align256(6 * (size_t)quads * sizeof(uint32_t)), fs));
-        p.vb = reinterpret_cast<IsoVertex*>(f.isoVb.p); p.ib = f.isoIb.p;
+        DXV_HIP(c, f.iso.vb.reserve((size_t)vertices, align256((size_t)vertices * sizeof(IsoVertex)), fs));
+        if (quads) DXV_HIP(c, f.iso.ib.reserve(6 * (size_t)quads, align256(6 * (size_t)quads * sizeof(uint32_t)), fs));
+        p.vb = reinterpret_cast<IsoVertex*>(f.iso.vb.p); p.ib = f.iso.ib.p;
         DXV_HIP(c, launch_iso_emit(p, fs));
     }
-    DXV_HIP(c, timer_end(f.timers[kTimerIso], timed, fs));
-    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
-    f.isoVertices = (uint32_t)vertices; f.isoTriangles = (uint32_t)(2u * quads);
-    f.isoHave = true; f.isoVersion = f.gridVersion;
+    if (end_operator(c, f, fs, &f.timers[kTimerIso])) return 1;
+    f.iso.vertices = (uint32_t)vertices; f.iso.triangles = (uint32_t)(2u * quads);
+    f.iso.have = true; f.iso.version = f.gridVersion;
     return 0;
 }
 
-int dxv_isosurface(dxv_ctx* c, int source, float iso, int space)
-{
-    if (dxv_isosurface_async(c, source, iso, space)) return 1;
-    return dxv_sync(c);
-}
-
-// whether the frame has a mesh to hand out: 0, or 1 with the reason as the message
-static int current_mesh(const dxv_ctx* c, const char* who)
-{
-    const Frame& f = c->frames[c->cur];
-    dxv_ctx* w = const_cast<dxv_ctx*>(c);                               // (the message is the one thing an accessor writes)
-    if (!f.isoHave) return fail(w, "%s: frame %u has no isosurface yet (call dxv_isosurface first)", who, c->cur);
-    if (f.isoVersion != f.gridVersion) return fail(w, "%s: frame %u was launched or filled again since its isosurface was made: the mesh is stale", who, c->cur);
-    return 0;
-}
+int dxv_isosurface(dxv_ctx* c, int source, float iso, int space) { return blocking(c, dxv_isosurface_async(c, source, iso, space)); }
 
 int dxv_isosurface_counts(dxv_ctx* c, uint32_t* vertices, uint32_t* triangles)
 {
-    if (!c) return 1;
-    if (current_mesh(c, "dxv_isosurface_counts")) return 1;
-    if (vertices) *vertices = cur_frame(c).isoVertices;
-    if (triangles) *triangles = cur_frame(c).isoTriangles;
+    if (!c || check_current(c, "dxv_isosurface_counts", cur_frame(c).iso, kIsoText)) return 1;
+    if (vertices) *vertices = cur_frame(c).iso.vertices;
+    if (triangles) *triangles = cur_frame(c).iso.triangles;
     return 0;
 }
 
 const void* dxv_isosurface_vertices_device_ptr(const dxv_ctx* c)
 {
-    if (!c || current_mesh(c, "dxv_isosurface_vertices_device_ptr")) return nullptr;
-    return c->frames[c->cur].isoVertices ? c->frames[c->cur].isoVb.p : nullptr;
+    if (!c || check_current(c, "dxv_isosurface_vertices_device_ptr", cur_frame(c).iso, kIsoText)) return nullptr;
+    return cur_frame(c).iso.vertices ? cur_frame(c).iso.vb.p : nullptr;
 }
 const void* dxv_isosurface_indices_device_ptr(const dxv_ctx* c)
 {
-    if (!c || current_mesh(c, "dxv_isosurface_indices_device_ptr")) return nullptr;
-    return c->frames[c->cur].isoTriangles ? c->frames[c->cur].isoIb.p : nullptr;
+    if (!c || check_current(c, "dxv_isosurface_indices_device_ptr", cur_frame(c).iso, kIsoText)) return nullptr;
+    return cur_frame(c).iso.triangles ? cur_frame(c).iso.ib.p : nullptr;
 }
 
 int dxv_isosurface_vertices_download(dxv_ctx* c, void* host, size_t bytes)
 {
-    if (!c || current_mesh(c, "dxv_isosurface_vertices_download")) return 1;
-    return download_current(c, "dxv_isosurface_vertices_download", cur_frame(c).isoVb.p, (size_t)cur_frame(c).isoVertices * sizeof(IsoVertex), host, bytes);
+    if (!c || check_current(c, "dxv_isosurface_vertices_download", cur_frame(c).iso, kIsoText)) return 1;
+    return download_current(c, "dxv_isosurface_vertices_download", cur_frame(c).iso.vb.p, (size_t)cur_frame(c).iso.vertices * sizeof(IsoVertex), host, bytes);
 }
 int dxv_isosurface_indices_download(dxv_ctx* c, void* host, size_t bytes)
 {
-    if (!c || current_mesh(c, "dxv_isosurface_indices_download")) return 1;
-    return download_current(c, "dxv_isosurface_indices_download", cur_frame(c).isoIb.p, (size_t)cur_frame(c).isoTriangles * 3u * sizeof(uint32_t), host, bytes);
+    if (!c || check_current(c, "dxv_isosurface_indices_download", cur_frame(c).iso, kIsoText)) return 1;
+    return download_current(c, "dxv_isosurface_indices_download", cur_frame(c).iso.ib.p, (size_t)cur_frame(c).iso.triangles * 3u * sizeof(uint32_t), host, bytes);
 }
 
 int dxv_isosurface_ms(dxv_ctx* c, float* ms) { return timer_ms(c, "dxv_isosurface_ms", kTimerIso, ms); }
@@ -471,19 +472,17 @@ int dxv_octree_async(dxv_ctx* c)
     if (!c) return 1;
     if (check_whole_grid(c, "dxv_octree")) return 1;
     Frame& f = cur_frame(c);
-    DXV_HIP(c, hipSetDevice(c->device));
-    if (settle_frame_launch(c)) return 1;
-    const hipStream_t fs = cur_stream(c);
+    hipStream_t fs;
+    if (begin_operator(c, &fs)) return 1;
     const uint32_t N = f.grid_dim;
     const size_t scratch = oct_scratch_bytes(N);
-    DXV_HIP(c, f.octScratch.reserve(scratch, scratch, fs));
+    DXV_HIP(c, f.oct.scratch.reserve(scratch, scratch, fs));
     OctParams p{};
     p.grid = f.grid.p;
-    oct_scratch_layout(f.octScratch.p, N, p);
+    oct_scratch_layout(f.oct.scratch.p, N, p);
     const uint32_t L = p.L;
-    const bool timed = c->opt.events != 0;
-    unsigned long long* totals = c->pin->octTotals[c->cur];
-    DXV_HIP(c, timer_begin(f.timers[kTimerOctree], timed, fs));
+    unsigned long long* totals = cur_pinned(c).octTotals;
+    DXV_HIP(c, timer_begin(f.timers[kTimerOctree], c->opt.events != 0, fs));
     DXV_HIP(c, launch_oct_count(p, fs));
     DXV_HIP(c, hipMemcpyAsync(totals, p.levelFirst, (L + 1u) * sizeof(unsigned long long), hipMemcpyDeviceToHost, fs));
     DXV_HIP(c, hipStreamSynchronize(fs));
@@ -491,62 +490,46 @@ int dxv_octree_async(dxv_ctx* c)
     if (!nodes || nodes > kOctMaxNodes)
         return fail(c, "dxv_octree: a tree of %llu nodes; at least the root and at most %llu (the frame's earlier tree is kept)", nodes,
                     (unsigned long long)kOctMaxNodes);
-    f.octVersion = 0;
-    DXV_HIP(c, f.octNodes.reserve((size_t)nodes, align256((size_t)nodes * 2u * sizeof(uint32_t)), fs));
-    p.nodes = f.octNodes.p;
+    f.oct.version = 0;
+    DXV_HIP(c, f.oct.nodes.reserve((size_t)nodes, align256((size_t)nodes * 2u * sizeof(uint32_t)), fs));
+    p.nodes = f.oct.nodes.p;
     DXV_HIP(c, launch_oct_emit(p, fs));
-    DXV_HIP(c, timer_end(f.timers[kTimerOctree], timed, fs));
-    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
-    f.octLevels = L; f.octCount = (uint32_t)nodes;
-    for (uint32_t l = 0; l < 12u; ++l) f.octLevelFirst[l] = l <= L ? (uint32_t)totals[l] : 0u;
-    f.octHave = true; f.octVersion = f.gridVersion;
+    if (end_operator(c, f, fs, &f.timers[kTimerOctree])) return 1;
+    f.oct.levels = L; f.oct.count = (uint32_t)nodes;
+    for (uint32_t l = 0; l < 12u; ++l) f.oct.levelFirst[l] = l <= L ? (uint32_t)totals[l] : 0u;
+    f.oct.have = true; f.oct.version = f.gridVersion;
     return 0;
 }
 
-int dxv_octree(dxv_ctx* c)
-{
-    if (dxv_octree_async(c)) return 1;
-    return dxv_sync(c);
-}
-
-// whether the frame has a tree to hand out: 0, or 1 with the reason as the message
-static int current_tree(const dxv_ctx* c, const char* who)
-{
-    const Frame& f = c->frames[c->cur];
-    dxv_ctx* w = const_cast<dxv_ctx*>(c);                               // (the message is the one thing an accessor writes)
-    if (!f.octHave) return fail(w, "%s: frame %u has no octree yet (call dxv_octree first)", who, c->cur);
-    if (f.octVersion != f.gridVersion) return fail(w, "%s: frame %u was launched, filled or expanded again since its octree was made: the tree is stale", who, c->cur);
-    return 0;
-}
+int dxv_octree(dxv_ctx* c) { return blocking(c, dxv_octree_async(c)); }
 
 int dxv_octree_info(dxv_ctx* c, uint32_t* levels, uint32_t* nodes, uint32_t level_first[12])
 {
-    if (!c) return 1;
-    if (current_tree(c, "dxv_octree_info")) return 1;
+    if (!c || check_current(c, "dxv_octree_info", cur_frame(c).oct, kOctreeText)) return 1;
     const Frame& f = cur_frame(c);
-    if (levels) *levels = f.octLevels;
-    if (nodes) *nodes = f.octCount;
-    if (level_first) memcpy(level_first, f.octLevelFirst, sizeof(f.octLevelFirst));
+    if (levels) *levels = f.oct.levels;
+    if (nodes) *nodes = f.oct.count;
+    if (level_first) memcpy(level_first, f.oct.levelFirst, sizeof(f.oct.levelFirst));
     return 0;
 }
 
 const void* dxv_octree_device_ptr(const dxv_ctx* c)
 {
-    if (!c || current_tree(c, "dxv_octree_device_ptr")) return nullptr;
-    return c->frames[c->cur].octNodes.p;
+    if (!c || check_current(c, "dxv_octree_device_ptr", cur_frame(c).oct, kOctreeText)) return nullptr;
+    return cur_frame(c).oct.nodes.p;
 }
 
 size_t dxv_octree_bytes(const dxv_ctx* c)
 {
     if (!c) return 0;
-    const Frame& f = c->frames[c->cur];
-    return f.octHave && f.octVersion == f.gridVersion ? (size_t)f.octCount * 2u * sizeof(uint32_t) : 0;
+    const Frame::Octree& o = cur_frame(c).oct;
+    return o.current(cur_frame(c)) ? (size_t)o.count * 2u * sizeof(uint32_t) : 0;
 }
 
 int dxv_octree_download(dxv_ctx* c, void* host, size_t bytes)
 {
-    if (!c || current_tree(c, "dxv_octree_download")) return 1;
-    return download_current(c, "dxv_octree_download", cur_frame(c).octNodes.p, dxv_octree_bytes(c), host, bytes);
+    if (!c || check_current(c, "dxv_octree_download", cur_frame(c).oct, kOctreeText)) return 1;
+    return download_current(c, "dxv_octree_download", cur_frame(c).oct.nodes.p, dxv_octree_bytes(c), host, bytes);
 }
 
 int dxv_octree_ms(dxv_ctx* c, float* ms) { return timer_ms(c, "dxv_octree_ms", kTimerOctree, ms); }
@@ -563,8 +546,8 @@ int dxv_octree_expand_async(dxv_ctx* c, const void* deviceNodes, uint32_t nodes,
     DXV_HIP(c, hipSetDevice(c->device));
     const bool own = deviceNodes == nullptr;
     if (own) {
-        if (current_tree(c, "dxv_octree_expand")) return 1;
-        deviceNodes = f.octNodes.p; nodes = f.octCount;                 // (a current tree is the tree of this grid: its levels are L)
+        if (check_current(c, "dxv_octree_expand", f.oct, kOctreeText)) return 1;
+        deviceNodes = f.oct.nodes.p; nodes = f.oct.count;               // (a current tree is the tree of this grid: its levels are L)
     } else {
         if (!nodes) return fail(c, "dxv_octree_expand: a tree of 0 nodes (the root is always there: nodes >= 1)");
         if (nodes > kOctMaxNodes) return fail(c, "dxv_octree_expand: a tree of %u nodes; at most %llu", nodes, (unsigned long long)kOctMaxNodes);
@@ -575,23 +558,16 @@ int dxv_octree_expand_async(dxv_ctx* c, const void* deviceNodes, uint32_t nodes,
         if (const int r = check_device_range(c, "dxv_octree_expand", deviceNodes, need, &room))
             return r == 1 ? 1 : fail(c, "dxv_octree_expand: %u nodes need %zu bytes, the allocation behind %p has %zu", nodes, need, deviceNodes, room);
     }
-    if (settle_frame_launch(c)) return 1;
+    if (settle_frame_launch(c)) return 1;                               // (begin_operator's steps, the device in front of the range check)
     const hipStream_t fs = cur_stream(c);
-    // the grid stops being what the frame's last launch wrote (dxv_fill_async's rules): a kept queue's zeros are gone, and whatever was made
-    // of the grid before -- fields, the mesh, the frame's own tree -- is stale
-    f.clearSig = 0;
-    grid_rewritten(f);
+    edited_in_place(f);                                                 // (the frame's own tree is stale with the rest)
     DXV_HIP(c, launch_oct_expand(f.grid.p, N, static_cast<const uint32_t*>(deviceNodes), nodes, f.status.p + kOctStatusWord, fs));
-    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
-    if (!own) f.octExpandPending = true;                                // (the frame's own tree was made by the build: it has nothing to report)
+    if (end_operator(c, f, fs, nullptr)) return 1;
+    if (!own) f.oct.expandPending = true;                               // (the frame's own tree was made by the build: it has nothing to report)
     return 0;
 }
 
-int dxv_octree_expand(dxv_ctx* c, const void* deviceNodes, uint32_t nodes, uint32_t levels)
-{
-    if (dxv_octree_expand_async(c, deviceNodes, nodes, levels)) return 1;
-    return dxv_sync(c);
-}
+int dxv_octree_expand(dxv_ctx* c, const void* deviceNodes, uint32_t nodes, uint32_t levels) { return blocking(c, dxv_octree_expand_async(c, deviceNodes, nodes, levels)); }
 
 // The connected components of the selected frame's grid (components.hip; dxv_components.h has the rule's routines), enqueued on the frame's
 // stream behind whatever it holds, under dxv_render_async's host-wait rule: pack, init, merge, compress and the numbering, K into a
@@ -606,98 +582,79 @@ int dxv_components_async(dxv_ctx* c, int of, int connectivity)
     Frame& f = cur_frame(c);
     const uint32_t N = f.grid_dim;
     if (N > kCompMaxN) return fail(c, "dxv_components: a grid of %u^3 voxels; at most %u^3 (a label and a linear index must fit 32 bits)", N, kCompMaxN);
-    DXV_HIP(c, hipSetDevice(c->device));
-    if (settle_frame_launch(c)) return 1;
-    const hipStream_t fs = cur_stream(c);
+    hipStream_t fs;
+    if (begin_operator(c, &fs)) return 1;
     const size_t voxels = (size_t)N * N * N, scratch = comp_scratch_bytes(N);
-    DXV_HIP(c, f.compScratch.reserve(scratch, scratch, fs));
-    f.compVersion = 0;                                                  // (the build writes into the frame's label buffer: what it held is gone)
-    f.measVersion = 0;                                                  // (... and a measure of the labels it held with it)
-    DXV_HIP(c, f.compLabels.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
+    DXV_HIP(c, f.comp.scratch.reserve(scratch, scratch, fs));
+    f.comp.version = 0;                                                 // (the build writes into the frame's label buffer: what it held is gone)
+    f.comp.measure.version = 0;                                         // (... and a measure of the labels it held with it)
+    DXV_HIP(c, f.comp.labels.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
     CompParams p{};
-    p.grid = f.grid.p; p.of = of; p.connectivity = (uint32_t)connectivity; p.labels = f.compLabels.p;
-    comp_scratch_layout(f.compScratch.p, N, p);
-    const bool timed = c->opt.events != 0;
-    unsigned long long* total = &c->pin->compTotal[c->cur];
-    DXV_HIP(c, timer_begin(f.timers[kTimerComponents], timed, fs));
+    p.grid = f.grid.p; p.of = of; p.connectivity = (uint32_t)connectivity; p.labels = f.comp.labels.p;
+    comp_scratch_layout(f.comp.scratch.p, N, p);
+    unsigned long long* total = &cur_pinned(c).compTotal;
+    DXV_HIP(c, timer_begin(f.timers[kTimerComponents], c->opt.events != 0, fs));
     DXV_HIP(c, launch_comp_label(p, fs));
     DXV_HIP(c, hipMemcpyAsync(total, p.total, sizeof(unsigned long long), hipMemcpyDeviceToHost, fs));
     DXV_HIP(c, hipStreamSynchronize(fs));
     const uint32_t K = (uint32_t)*total;
     if (K) {
-        DXV_HIP(c, f.compTable.reserve(K, align256((size_t)K * sizeof(CompRecord)), fs));
-        DXV_HIP(c, f.compWork.reserve((size_t)K * sizeof(CompStats), align256((size_t)K * sizeof(CompStats)), fs));
-        p.table = reinterpret_cast<CompRecord*>(f.compTable.p);
-        p.stats = reinterpret_cast<CompStats*>(f.compWork.p);
+        DXV_HIP(c, f.comp.table.reserve(K, align256((size_t)K * sizeof(CompRecord)), fs));
+        DXV_HIP(c, f.comp.work.reserve((size_t)K * sizeof(CompStats), align256((size_t)K * sizeof(CompStats)), fs));
+        p.table = reinterpret_cast<CompRecord*>(f.comp.table.p);
+        p.stats = reinterpret_cast<CompStats*>(f.comp.work.p);
         DXV_HIP(c, launch_comp_stats(p, K, fs));
     }
-    DXV_HIP(c, timer_end(f.timers[kTimerComponents], timed, fs));
-    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
-    f.compCount = K; f.compDim = N; f.compOf = of; f.compConnectivity = connectivity;
-    f.compHave = true; f.compVersion = f.gridVersion;
+    if (end_operator(c, f, fs, &f.timers[kTimerComponents])) return 1;
+    f.comp.count = K; f.comp.dim = N; f.comp.of = of; f.comp.connectivity = connectivity;
+    f.comp.have = true; f.comp.version = f.gridVersion;
     return 0;
 }
 
-int dxv_components(dxv_ctx* c, int of, int connectivity)
-{
-    if (dxv_components_async(c, of, connectivity)) return 1;
-    return dxv_sync(c);
-}
-
-// whether the frame has labels to hand out: 0, or 1 with the reason as the message
-static int current_labels(const dxv_ctx* c, const char* who)
-{
-    const Frame& f = c->frames[c->cur];
-    dxv_ctx* w = const_cast<dxv_ctx*>(c);                               // (the message is the one thing an accessor writes)
-    if (!f.compHave) return fail(w, "%s: frame %u has no components yet (call dxv_components first)", who, c->cur);
-    if (f.compVersion != f.gridVersion)
-        return fail(w, "%s: frame %u was launched, filled, expanded or selected again since its components were labelled: labels and table are stale", who, c->cur);
-    return 0;
-}
+int dxv_components(dxv_ctx* c, int of, int connectivity) { return blocking(c, dxv_components_async(c, of, connectivity)); }
 
 int dxv_components_info(dxv_ctx* c, uint32_t* count, int* of, int* connectivity)
 {
-    if (!c) return 1;
-    if (current_labels(c, "dxv_components_info")) return 1;
+    if (!c || check_current(c, "dxv_components_info", cur_frame(c).comp, kComponentsText)) return 1;
     const Frame& f = cur_frame(c);
-    if (count) *count = f.compCount;
-    if (of) *of = f.compOf;
-    if (connectivity) *connectivity = f.compConnectivity;
+    if (count) *count = f.comp.count;
+    if (of) *of = f.comp.of;
+    if (connectivity) *connectivity = f.comp.connectivity;
     return 0;
 }
 
 const void* dxv_components_labels_device_ptr(const dxv_ctx* c)
 {
-    if (!c || current_labels(c, "dxv_components_labels_device_ptr")) return nullptr;
-    return c->frames[c->cur].compLabels.p;
+    if (!c || check_current(c, "dxv_components_labels_device_ptr", cur_frame(c).comp, kComponentsText)) return nullptr;
+    return cur_frame(c).comp.labels.p;
 }
 size_t dxv_components_labels_bytes(const dxv_ctx* c)
 {
     if (!c) return 0;
-    const Frame& f = c->frames[c->cur];
-    return f.compHave && f.compVersion == f.gridVersion ? (size_t)f.compDim * f.compDim * f.compDim * sizeof(uint32_t) : 0;
+    const Frame::Components& k = cur_frame(c).comp;
+    return k.current(cur_frame(c)) ? (size_t)k.dim * k.dim * k.dim * sizeof(uint32_t) : 0;
 }
 const void* dxv_components_table_device_ptr(const dxv_ctx* c)
 {
-    if (!c || current_labels(c, "dxv_components_table_device_ptr")) return nullptr;
-    return c->frames[c->cur].compCount ? c->frames[c->cur].compTable.p : nullptr;
+    if (!c || check_current(c, "dxv_components_table_device_ptr", cur_frame(c).comp, kComponentsText)) return nullptr;
+    return cur_frame(c).comp.count ? cur_frame(c).comp.table.p : nullptr;
 }
 size_t dxv_components_table_bytes(const dxv_ctx* c)
 {
     if (!c) return 0;
-    const Frame& f = c->frames[c->cur];
-    return f.compHave && f.compVersion == f.gridVersion ? (size_t)f.compCount * sizeof(CompRecord) : 0;
+    const Frame::Components& k = cur_frame(c).comp;
+    return k.current(cur_frame(c)) ? (size_t)k.count * sizeof(CompRecord) : 0;
 }
 
 int dxv_components_labels_download(dxv_ctx* c, void* host, size_t bytes)
 {
-    if (!c || current_labels(c, "dxv_components_labels_download")) return 1;
-    return download_current(c, "dxv_components_labels_download", cur_frame(c).compLabels.p, dxv_components_labels_bytes(c), host, bytes);
+    if (!c || check_current(c, "dxv_components_labels_download", cur_frame(c).comp, kComponentsText)) return 1;
+    return download_current(c, "dxv_components_labels_download", cur_frame(c).comp.labels.p, dxv_components_labels_bytes(c), host, bytes);
 }
 int dxv_components_table_download(dxv_ctx* c, void* host, size_t bytes)
 {
-    if (!c || current_labels(c, "dxv_components_table_download")) return 1;
-    return download_current(c, "dxv_components_table_download", cur_frame(c).compTable.p, dxv_components_table_bytes(c), host, bytes);
+    if (!c || check_current(c, "dxv_components_table_download", cur_frame(c).comp, kComponentsText)) return 1;
+    return download_current(c, "dxv_components_table_download", cur_frame(c).comp.table.p, dxv_components_table_bytes(c), host, bytes);
 }
 
 int dxv_components_ms(dxv_ctx* c, float* ms) { return timer_ms(c, "dxv_components_ms", kTimerComponents, ms); }
@@ -709,61 +666,52 @@ int dxv_measure_async(dxv_ctx* c)
 {
     if (!c) return 1;
     if (check_whole_grid(c, "dxv_measure")) return 1;
-    if (current_labels(c, "dxv_measure")) return 1;
+    if (check_current(c, "dxv_measure", cur_frame(c).comp, kComponentsText)) return 1;
     Frame& f = cur_frame(c);
-    if (f.grid_dim != f.compDim) return fail(c, "dxv_measure: the labels of frame %u do not belong to its grid: they are stale", c->cur);
-    DXV_HIP(c, hipSetDevice(c->device));
-    if (settle_frame_launch(c)) return 1;
-    const hipStream_t fs = cur_stream(c);
-    const uint32_t N = f.compDim, K = f.compCount;
-    const bool packed = f.compScratch.p != nullptr;                     // (the mask of the frame's last labelling: this one, it is current)
+    if (f.grid_dim != f.comp.dim) return fail(c, "dxv_measure: the labels of frame %u do not belong to its grid: they are stale", c->cur);
+    hipStream_t fs;
+    if (begin_operator(c, &fs)) return 1;
+    const uint32_t N = f.comp.dim, K = f.comp.count;
+    const bool packed = f.comp.scratch.p != nullptr;                    // (the mask of the frame's last labelling: this one, it is current)
     const size_t scratch = comp_scratch_bytes(N);
-    DXV_HIP(c, f.compScratch.reserve(scratch, scratch, fs));
-    f.measVersion = 0;
-    DXV_HIP(c, f.measTable.reserve((size_t)K + 1u, align256(measure_table_bytes(K)), fs));
+    DXV_HIP(c, f.comp.scratch.reserve(scratch, scratch, fs));
+    f.comp.measure.version = 0;
+    DXV_HIP(c, f.comp.measure.table.reserve((size_t)K + 1u, align256(measure_table_bytes(K)), fs));
     CompParams p{};
-    comp_scratch_layout(f.compScratch.p, N, p);
-    const bool timed = c->opt.events != 0;
-    DXV_HIP(c, timer_begin(f.timers[kTimerMeasure], timed, fs));
-    if (!packed) DXV_HIP(c, launch_comp_pack(f.grid.p, N, f.compOf, p.mask, fs));
-    DXV_HIP(c, launch_measure(p.mask, N, (uint32_t)f.compConnectivity, f.compLabels.p, K, f.measTable.p, fs));
-    DXV_HIP(c, timer_end(f.timers[kTimerMeasure], timed, fs));
-    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
-    f.measCount = K; f.measHave = true; f.measVersion = f.gridVersion;
+    comp_scratch_layout(f.comp.scratch.p, N, p);
+    DXV_HIP(c, timer_begin(f.timers[kTimerMeasure], c->opt.events != 0, fs));
+    if (!packed) DXV_HIP(c, launch_comp_pack(f.grid.p, N, f.comp.of, p.mask, fs));
+    DXV_HIP(c, launch_measure(p.mask, N, (uint32_t)f.comp.connectivity, f.comp.labels.p, K, f.comp.measure.table.p, fs));
+    if (end_operator(c, f, fs, &f.timers[kTimerMeasure])) return 1;
+    f.comp.measure.count = K; f.comp.measure.have = true; f.comp.measure.version = f.gridVersion;
     return 0;
 }
 
-int dxv_measure(dxv_ctx* c)
-{
-    if (dxv_measure_async(c)) return 1;
-    return dxv_sync(c);
-}
+int dxv_measure(dxv_ctx* c) { return blocking(c, dxv_measure_async(c)); }
 
-// whether the frame has a measure to hand out: 0, or 1 with the reason as the message
+// whether the frame has a measure to hand out: its own version, and its labelling's -- a measure of labels that are stale is stale
 static int current_measure(const dxv_ctx* c, const char* who)
 {
-    const Frame& f = c->frames[c->cur];
-    dxv_ctx* w = const_cast<dxv_ctx*>(c);                               // (the message is the one thing an accessor writes)
-    if (!f.measHave) return fail(w, "%s: frame %u has no measure yet (call dxv_measure first)", who, c->cur);
-    if (f.measVersion != f.gridVersion || f.compVersion != f.gridVersion)
-        return fail(w, "%s: frame %u was launched, edited or labelled again since its components were measured: the measure is stale", who, c->cur);
-    return 0;
+    const Frame& f = cur_frame(c);
+    Frame::Made made = f.comp.measure;
+    if (f.comp.version != f.gridVersion) made.version = 0;
+    return check_current(c, who, made, kMeasureText);
 }
 
 const void* dxv_measure_table_device_ptr(const dxv_ctx* c)
 {
     if (!c || current_measure(c, "dxv_measure_table_device_ptr")) return nullptr;
-    return c->frames[c->cur].measTable.p;
+    return cur_frame(c).comp.measure.table.p;
 }
 size_t dxv_measure_table_bytes(const dxv_ctx* c)
 {
     if (!c || current_measure(c, "dxv_measure_table_bytes")) return 0;
-    return measure_table_bytes(c->frames[c->cur].measCount);
+    return measure_table_bytes(cur_frame(c).comp.measure.count);
 }
 int dxv_measure_table_download(dxv_ctx* c, void* host, size_t bytes)
 {
     if (!c || current_measure(c, "dxv_measure_table_download")) return 1;
-    return download_current(c, "dxv_measure_table_download", cur_frame(c).measTable.p, dxv_measure_table_bytes(c), host, bytes);
+    return download_current(c, "dxv_measure_table_download", cur_frame(c).comp.measure.table.p, dxv_measure_table_bytes(c), host, bytes);
 }
 
 int dxv_measure_ms(dxv_ctx* c, float* ms) { return timer_ms(c, "dxv_measure_ms", kTimerMeasure, ms); }
@@ -781,17 +729,16 @@ int dxv_thickness_async(dxv_ctx* c, int of, uint32_t cap_sq)
     Frame& f = cur_frame(c);
     const uint32_t N = f.grid_dim;
     if (N > kThickMaxN) return fail(c, "dxv_thickness: a grid of %u^3 voxels; at most %u^3 (a centre's linear index must fit 30 bits)", N, kThickMaxN);
-    DXV_HIP(c, hipSetDevice(c->device));
-    if (settle_frame_launch(c)) return 1;
-    const hipStream_t fs = cur_stream(c);
+    hipStream_t fs;
+    if (begin_operator(c, &fs)) return 1;
     const size_t voxels = (size_t)N * N * N, scratch = thickness_scratch_bytes(N);
-    f.thickVersion = 0; f.thickDim = 0;
-    DXV_HIP(c, f.thick.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
-    DXV_HIP(c, f.thickHist.reserve(kThickMaxCapSq + 1u, align256(thickness_histogram_bytes(kThickMaxCapSq)), fs));
-    DXV_HIP(c, f.thickScratch.reserve(scratch, scratch, fs));
+    f.thick.version = 0; f.thick.have = false;
+    DXV_HIP(c, f.thick.map.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
+    DXV_HIP(c, f.thick.hist.reserve(kThickMaxCapSq + 1u, align256(thickness_histogram_bytes(kThickMaxCapSq)), fs));
+    DXV_HIP(c, f.thick.scratch.reserve(scratch, scratch, fs));
     ThickParams p{};
-    p.of = of; p.cap = cap_sq; p.cull = (uint32_t)c->opt.thickcull; p.count = c->opt.thickstages ? 1u : 0u; p.W = f.thick.p; p.hist = f.thickHist.p;
-    thickness_layout(f.thickScratch.p, N, p);
+    p.of = of; p.cap = cap_sq; p.cull = (uint32_t)c->opt.thickcull; p.count = c->opt.thickstages ? 1u : 0u; p.W = f.thick.map.p; p.hist = f.thick.hist.p;
+    thickness_layout(f.thick.scratch.p, N, p);
     const bool timed = c->opt.events != 0, staged = timed && c->opt.thickstages != 0;      // (the stages' own pairs only for a caller that measures)
     DXV_HIP(c, timer_begin(f.timers[kTimerThickness], timed, fs));
     for (int stage = 0; stage < THICK_STAGES; ++stage) {
@@ -801,57 +748,41 @@ int dxv_thickness_async(dxv_ctx* c, int of, uint32_t cap_sq)
         DXV_HIP(c, launch_thickness_stage(f.grid.p, p, stage, fs));
         DXV_HIP(c, timer_end(t, staged, fs));
     }
-    DXV_HIP(c, timer_end(f.timers[kTimerThickness], timed, fs));
-    DXV_HIP(c, hipMemcpyAsync(c->pin->thickCount[c->cur], thickness_counters(p), sizeof(c->pin->thickCount[c->cur]), hipMemcpyDeviceToHost, fs));
-    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
-    f.thickPending = true;
-    f.thickDim = N; f.thickCap = cap_sq; f.thickVersion = f.gridVersion;
+    PinnedFrame& pin = cur_pinned(c);
+    if (end_operator(c, f, fs, &f.timers[kTimerThickness], pin.thickCount, thickness_counters(p), sizeof(pin.thickCount))) return 1;
+    f.thick.pending = true;
+    f.thick.dim = N; f.thick.cap = cap_sq; f.thick.have = true; f.thick.version = f.gridVersion;
     return 0;
 }
 
-int dxv_thickness(dxv_ctx* c, int of, uint32_t cap_sq)
-{
-    if (dxv_thickness_async(c, of, cap_sq)) return 1;
-    return dxv_sync(c);
-}
-
-// whether the frame has a thickness map to hand out: 0, or 1 with the reason as the message
-static int current_thickness(const dxv_ctx* c, const char* who)
-{
-    const Frame& f = c->frames[c->cur];
-    dxv_ctx* w = const_cast<dxv_ctx*>(c);                               // (the message is the one thing an accessor writes)
-    if (!f.thickDim || !f.thick.p) return fail(w, "%s: frame %u has no thickness map yet (call dxv_thickness first)", who, c->cur);
-    if (f.thickVersion != f.gridVersion)
-        return fail(w, "%s: frame %u was launched or edited again since its thickness map was made: map and histogram are stale", who, c->cur);
-    return 0;
-}
+int dxv_thickness(dxv_ctx* c, int of, uint32_t cap_sq) { return blocking(c, dxv_thickness_async(c, of, cap_sq)); }
 
 const void* dxv_thickness_device_ptr(const dxv_ctx* c)
 {
-    if (!c || current_thickness(c, "dxv_thickness_device_ptr")) return nullptr;
-    return c->frames[c->cur].thick.p;
+    if (!c || check_current(c, "dxv_thickness_device_ptr", cur_frame(c).thick, kThicknessText)) return nullptr;
+    return cur_frame(c).thick.map.p;
 }
 size_t dxv_thickness_bytes(const dxv_ctx* c)
 {
     if (!c) return 0;
-    const Frame& f = c->frames[c->cur];
-    return f.thickDim && f.thickVersion == f.gridVersion ? (size_t)f.thickDim * f.thickDim * f.thickDim * sizeof(uint32_t) : 0;
+    const Frame::Thickness& t = cur_frame(c).thick;
+    return t.current(cur_frame(c)) ? (size_t)t.dim * t.dim * t.dim * sizeof(uint32_t) : 0;
 }
 int dxv_thickness_download(dxv_ctx* c, void* host, size_t bytes)
 {
-    if (!c || current_thickness(c, "dxv_thickness_download")) return 1;
-    return download_current(c, "dxv_thickness_download", cur_frame(c).thick.p, dxv_thickness_bytes(c), host, bytes);
+    if (!c || check_current(c, "dxv_thickness_download", cur_frame(c).thick, kThicknessText)) return 1;
+    return download_current(c, "dxv_thickness_download", cur_frame(c).thick.map.p, dxv_thickness_bytes(c), host, bytes);
 }
 size_t dxv_thickness_histogram_bytes(const dxv_ctx* c)
 {
     if (!c) return 0;
-    const Frame& f = c->frames[c->cur];
-    return f.thickDim && f.thickVersion == f.gridVersion ? thickness_histogram_bytes(f.thickCap) : 0;
+    const Frame::Thickness& t = cur_frame(c).thick;
+    return t.current(cur_frame(c)) ? thickness_histogram_bytes(t.cap) : 0;
 }
 int dxv_thickness_histogram_download(dxv_ctx* c, void* host, size_t bytes)
 {
-    if (!c || current_thickness(c, "dxv_thickness_histogram_download")) return 1;
-    return download_current(c, "dxv_thickness_histogram_download", cur_frame(c).thickHist.p, dxv_thickness_histogram_bytes(c), host, bytes);
+    if (!c || check_current(c, "dxv_thickness_histogram_download", cur_frame(c).thick, kThicknessText)) return 1;
+    return download_current(c, "dxv_thickness_histogram_download", cur_frame(c).thick.hist.p, dxv_thickness_histogram_bytes(c), host, bytes);
 }
 
 int dxv_thickness_info(dxv_ctx* c, float* ms, uint64_t* centres_painted, uint64_t* work_items)
@@ -859,8 +790,8 @@ int dxv_thickness_info(dxv_ctx* c, float* ms, uint64_t* centres_painted, uint64_
     if (!c) return 1;
     const Frame& f = cur_frame(c);
     if (ms) *ms = f.timers[kTimerThickness].ms;
-    if (centres_painted) *centres_painted = f.thickCentres;
-    if (work_items) *work_items = f.thickItems;
+    if (centres_painted) *centres_painted = f.thick.centres;
+    if (work_items) *work_items = f.thick.items;
     return 0;
 }
 
@@ -870,8 +801,8 @@ int dxv_thickness_stage_info(dxv_ctx* c, float ms[6], uint64_t* voxels_tested, u
     if (!ms) return fail(c, "dxv_thickness_stage_info: ms is NULL");
     const Frame& f = cur_frame(c);
     for (int stage = 0; stage < THICK_STAGES; ++stage) ms[stage] = f.timers[kTimerThickStage0 + stage].ms;
-    if (voxels_tested) *voxels_tested = f.thickTested;
-    if (atomics_sent) *atomics_sent = f.thickSent;
+    if (voxels_tested) *voxels_tested = f.thick.tested;
+    if (atomics_sent) *atomics_sent = f.thick.sent;
     return 0;
 }
 
@@ -908,93 +839,76 @@ int dxv_geodesic_async(dxv_ctx* c, int of, int metric, int seeds_kind, const voi
         if (r == 2) return fail(c, "dxv_geodesic: the seed mask has %zu bytes from %p on, the grid has %zu voxels", room, seeds, voxels);
         if (r) return 1;
     }
-    if (settle_frame_launch(c)) return 1;                               // (a pending fill, thin, expansion or geodesic of the frame first)
+    if (settle_frame_launch(c)) return 1;                               // (begin_operator's steps, the device in front of the range check: a pending fill, thin, expansion or geodesic of the frame first)
     const hipStream_t fs = cur_stream(c);
     const size_t scratch = geodesic_scratch_bytes(N);
-    f.geoVersion = 0; f.geoDim = 0;
-    DXV_HIP(c, f.geo.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
-    DXV_HIP(c, f.geoScratch.reserve(scratch, scratch, fs));
+    f.geo.version = 0; f.geo.have = false;
+    DXV_HIP(c, f.geo.map.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
+    DXV_HIP(c, f.geo.scratch.reserve(scratch, scratch, fs));
     const void* deviceSeeds = seeds;
     if (seeds_kind == DXV_GEO_SEEDS_LIST) {
         // the frame's own copy of the list (no geodesic of the frame is in flight: settle_frame_launch), uploaded from there
         const uint32_t* list = static_cast<const uint32_t*>(seeds);
-        f.geoList.assign(list, list + seed_count);
+        f.geo.list.assign(list, list + seed_count);
         deviceSeeds = nullptr;
         if (seed_count) {
-            DXV_HIP(c, f.geoSeeds.reserve(seed_count, align256((size_t)seed_count * sizeof(uint32_t)), fs));
-            DXV_HIP(c, hipMemcpyAsync(f.geoSeeds.p, f.geoList.data(), (size_t)seed_count * sizeof(uint32_t), hipMemcpyHostToDevice, fs));
-            deviceSeeds = f.geoSeeds.p;
+            DXV_HIP(c, f.geo.seeds.reserve(seed_count, align256((size_t)seed_count * sizeof(uint32_t)), fs));
+            DXV_HIP(c, hipMemcpyAsync(f.geo.seeds.p, f.geo.list.data(), (size_t)seed_count * sizeof(uint32_t), hipMemcpyHostToDevice, fs));
+            deviceSeeds = f.geo.seeds.p;
         }
     }
-    const bool timed = c->opt.events != 0;
-    f.geoMetric = metric; f.geoLimit = limit;
-    f.geoBatch = c->opt.georounds ? (uint32_t)c->opt.georounds : kGeoRoundsDefault;
-    f.geoRounds = 0; f.geoTilesRun = 0; f.geoMostLive = 0; f.geoSparseRounds = 0;
-    DXV_HIP(c, timer_begin(f.timers[kTimerGeodesic], timed, fs));
-    DXV_HIP(c, launch_geodesic_init(f.grid.p, N, of, seeds_kind, deviceSeeds, seed_count, f.geo.p, f.geoScratch.p, fs));
-    DXV_HIP(c, launch_geodesic_batch(f.geo.p, N, metric, limit, f.geoScratch.p, f.geoBatch, 0u, fs));
-    DXV_HIP(c, timer_end(f.timers[kTimerGeodesic], timed, fs));
-    DXV_HIP(c, hipMemcpyAsync(&c->pin->geoCtl[c->cur], f.geoScratch.p, sizeof(GeoControl), hipMemcpyDeviceToHost, fs));
-    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
-    f.geoPending = true;
-    f.geoDim = N; f.geoVersion = f.gridVersion;
+    f.geo.metric = metric; f.geo.limit = limit;
+    f.geo.batch = c->opt.georounds ? (uint32_t)c->opt.georounds : kGeoRoundsDefault;
+    f.geo.rounds = 0; f.geo.tilesRun = 0; f.geo.mostLive = 0; f.geo.sparseRounds = 0;
+    DXV_HIP(c, timer_begin(f.timers[kTimerGeodesic], c->opt.events != 0, fs));
+    DXV_HIP(c, launch_geodesic_init(f.grid.p, N, of, seeds_kind, deviceSeeds, seed_count, f.geo.map.p, f.geo.scratch.p, fs));
+    DXV_HIP(c, launch_geodesic_batch(f.geo.map.p, N, metric, limit, f.geo.scratch.p, f.geo.batch, 0u, fs));
+    if (end_operator(c, f, fs, &f.timers[kTimerGeodesic], &cur_pinned(c).geoCtl, f.geo.scratch.p, sizeof(GeoControl))) return 1;
+    f.geo.pending = true;
+    f.geo.dim = N; f.geo.have = true; f.geo.version = f.gridVersion;
     return 0;
 }
 
-int dxv_geodesic(dxv_ctx* c, int of, int metric, int seeds_kind, const void* seeds, uint32_t seed_count, uint32_t limit)
-{
-    if (dxv_geodesic_async(c, of, metric, seeds_kind, seeds, seed_count, limit)) return 1;
-    return dxv_sync(c);
-}
-
-// whether the frame has a geodesic map to hand out: 0, or 1 with the reason as the message
-static int current_geodesic(const dxv_ctx* c, const char* who)
-{
-    const Frame& f = c->frames[c->cur];
-    dxv_ctx* w = const_cast<dxv_ctx*>(c);                               // (the message is the one thing an accessor writes)
-    if (!f.geoDim || !f.geo.p) return fail(w, "%s: frame %u has no geodesic map yet (call dxv_geodesic first)", who, c->cur);
-    if (f.geoVersion != f.gridVersion) return fail(w, "%s: frame %u was launched or edited again since its geodesic map was made: the map is stale", who, c->cur);
-    return 0;
-}
+int dxv_geodesic(dxv_ctx* c, int of, int metric, int seeds_kind, const void* seeds, uint32_t seed_count, uint32_t limit) { return blocking(c, dxv_geodesic_async(c, of, metric, seeds_kind, seeds, seed_count, limit)); }
 
 const void* dxv_geodesic_device_ptr(const dxv_ctx* c)
 {
-    if (!c || current_geodesic(c, "dxv_geodesic_device_ptr")) return nullptr;
-    return c->frames[c->cur].geo.p;
+    if (!c || check_current(c, "dxv_geodesic_device_ptr", cur_frame(c).geo, kGeodesicText)) return nullptr;
+    return cur_frame(c).geo.map.p;
 }
 size_t dxv_geodesic_bytes(const dxv_ctx* c)
 {
     if (!c) return 0;
-    const Frame& f = c->frames[c->cur];
-    return f.geoDim && f.geoVersion == f.gridVersion ? (size_t)f.geoDim * f.geoDim * f.geoDim * sizeof(uint32_t) : 0;
+    const Frame::Geodesic& g = cur_frame(c).geo;
+    return g.current(cur_frame(c)) ? (size_t)g.dim * g.dim * g.dim * sizeof(uint32_t) : 0;
 }
 int dxv_geodesic_download(dxv_ctx* c, void* host, size_t bytes)
 {
-    if (!c || current_geodesic(c, "dxv_geodesic_download")) return 1;
-    return download_current(c, "dxv_geodesic_download", cur_frame(c).geo.p, dxv_geodesic_bytes(c), host, bytes);
+    if (!c || check_current(c, "dxv_geodesic_download", cur_frame(c).geo, kGeodesicText)) return 1;
+    return download_current(c, "dxv_geodesic_download", cur_frame(c).geo.map.p, dxv_geodesic_bytes(c), host, bytes);
 }
 
 int dxv_geodesic_info(dxv_ctx* c, float* ms, uint32_t* rounds, uint64_t* seeds_used, uint64_t* reached, uint64_t* unreached, uint32_t* farthest, uint32_t* farthest_voxel)
 {
-    if (!c || current_geodesic(c, "dxv_geodesic_info")) return 1;
+    if (!c || check_current(c, "dxv_geodesic_info", cur_frame(c).geo, kGeodesicText)) return 1;
     const Frame& f = cur_frame(c);
     if (ms) *ms = f.timers[kTimerGeodesic].ms;
-    if (rounds) *rounds = f.geoRounds;
-    if (seeds_used) *seeds_used = f.geoSeedsUsed;
-    if (reached) *reached = f.geoReached;
-    if (unreached) *unreached = f.geoUnreached;
-    if (farthest) *farthest = f.geoFarthest;
-    if (farthest_voxel) *farthest_voxel = f.geoFarthestVoxel;
+    if (rounds) *rounds = f.geo.rounds;
+    if (seeds_used) *seeds_used = f.geo.seedsUsed;
+    if (reached) *reached = f.geo.reached;
+    if (unreached) *unreached = f.geo.unreached;
+    if (farthest) *farthest = f.geo.farthest;
+    if (farthest_voxel) *farthest_voxel = f.geo.farthestVoxel;
     return 0;
 }
 
 int dxv_geodesic_work_info(dxv_ctx* c, uint64_t* tiles_run, uint32_t* most_live_tiles, uint32_t* sparse_rounds)
 {
-    if (!c || current_geodesic(c, "dxv_geodesic_work_info")) return 1;
+    if (!c || check_current(c, "dxv_geodesic_work_info", cur_frame(c).geo, kGeodesicText)) return 1;
     const Frame& f = cur_frame(c);
-    if (tiles_run) *tiles_run = f.geoTilesRun;
-    if (most_live_tiles) *most_live_tiles = f.geoMostLive;
-    if (sparse_rounds) *sparse_rounds = f.geoSparseRounds;
+    if (tiles_run) *tiles_run = f.geo.tilesRun;
+    if (most_live_tiles) *most_live_tiles = f.geo.mostLive;
+    if (sparse_rounds) *sparse_rounds = f.geo.sparseRounds;
     return 0;
 }
 
@@ -1002,32 +916,32 @@ int dxv_geodesic_work_info(dxv_ctx* c, uint64_t* tiles_run, uint32_t* most_live_
 // one wave walks down (geodesic.hip: k_geo_path) into the frame's own words, and min(length, capacity) of them come back.
 int dxv_geodesic_path(dxv_ctx* c, uint32_t target, uint32_t* host_path, uint32_t capacity, uint32_t* length)
 {
-    if (!c || current_geodesic(c, "dxv_geodesic_path")) return 1;
+    if (!c || check_current(c, "dxv_geodesic_path", cur_frame(c).geo, kGeodesicText)) return 1;
     if (!length) return fail(c, "dxv_geodesic_path: length is NULL");
     if (capacity && !host_path) return fail(c, "dxv_geodesic_path: room for %u voxels at NULL", capacity);
     Frame& f = cur_frame(c);
-    const uint32_t N = f.geoDim;
+    const uint32_t N = f.geo.dim;
     const size_t voxels = (size_t)N * N * N;
     if (target >= voxels) return fail(c, "dxv_geodesic_path: target %u is outside the grid of %u^3 = %zu voxels", target, N, voxels);
     if (dxv_sync(c)) return 1;
     const hipStream_t fs = cur_stream(c);
     uint32_t word = 0;
-    DXV_HIP(c, hipMemcpyAsync(&word, f.geo.p + target, sizeof(word), hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipMemcpyAsync(&word, f.geo.map.p + target, sizeof(word), hipMemcpyDeviceToHost, fs));
     DXV_HIP(c, hipStreamSynchronize(fs));
     if (word >= kGeoUnreached)
         return fail(c, "dxv_geodesic_path: target %u holds no distance (%s)", target, word == kGeoNone ? "DXV_GEO_NONE: it is no member" : "DXV_GEO_UNREACHED: no path reaches it");
-    const uint64_t longest = (uint64_t)word / geo_min_weight(f.geoMetric) + 1u;     // (every step lowers the word by the least weight or more)
+    const uint64_t longest = (uint64_t)word / geo_min_weight(f.geo.metric) + 1u;     // (every step lowers the word by the least weight or more)
     const uint32_t room = (uint64_t)capacity < longest ? capacity : (uint32_t)longest;
-    DXV_HIP(c, f.geoPath.reserve((size_t)room + 2u, align256(((size_t)room + 2u) * sizeof(uint32_t)), fs));
-    DXV_HIP(c, launch_geodesic_path(f.geo.p, N, f.geoMetric, target, f.geoPath.p, room, fs));
+    DXV_HIP(c, f.geo.path.reserve((size_t)room + 2u, align256(((size_t)room + 2u) * sizeof(uint32_t)), fs));
+    DXV_HIP(c, launch_geodesic_path(f.geo.map.p, N, f.geo.metric, target, f.geo.path.p, room, fs));
     uint32_t head[2] = {0, 0};
-    DXV_HIP(c, hipMemcpyAsync(head, f.geoPath.p, sizeof(head), hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipMemcpyAsync(head, f.geo.path.p, sizeof(head), hipMemcpyDeviceToHost, fs));
     DXV_HIP(c, hipStreamSynchronize(fs));
     if (head[1] || head[0] > longest) return fail(c, "dxv_geodesic_path: no neighbour continues the path after %u voxels from target %u: the map is no fixed point", head[0], target);
     *length = head[0];
     const uint32_t give = head[0] < room ? head[0] : room;
     if (give) {
-        DXV_HIP(c, hipMemcpyAsync(host_path, f.geoPath.p + 2, (size_t)give * sizeof(uint32_t), hipMemcpyDeviceToHost, fs));
+        DXV_HIP(c, hipMemcpyAsync(host_path, f.geo.path.p + 2, (size_t)give * sizeof(uint32_t), hipMemcpyDeviceToHost, fs));
         DXV_HIP(c, hipStreamSynchronize(fs));
     }
     return 0;
@@ -1042,40 +956,32 @@ int dxv_components_select_async(dxv_ctx* c, int rule, uint32_t arg)
     if (rule != DXV_SELECT_LARGEST && rule != DXV_SELECT_MIN_VOXELS && rule != DXV_SELECT_BORDER)
         return fail(c, "dxv_components_select: unknown rule %d (DXV_SELECT_LARGEST = 0, DXV_SELECT_MIN_VOXELS = 1, DXV_SELECT_BORDER = 2)", rule);
     if (rule != DXV_SELECT_MIN_VOXELS && arg) return fail(c, "dxv_components_select: rule %d takes no argument (arg must be 0, got %u)", rule, arg);
-    if (current_labels(c, "dxv_components_select")) return 1;
+    if (check_current(c, "dxv_components_select", cur_frame(c).comp, kComponentsText)) return 1;
     Frame& f = cur_frame(c);
-    if (!f.grid.p || f.grid_dim != f.compDim || !frame_renderable(f))
+    if (!f.grid.p || f.grid_dim != f.comp.dim || !frame_renderable(f))
         return fail(c, "dxv_components_select: the labels of frame %u do not belong to its grid: they are stale", c->cur);
-    DXV_HIP(c, hipSetDevice(c->device));
-    if (settle_frame_launch(c)) return 1;
-    const hipStream_t fs = cur_stream(c);
-    const uint32_t K = f.compCount;
+    hipStream_t fs;
+    if (begin_operator(c, &fs)) return 1;
+    const uint32_t K = f.comp.count;
     const size_t work = comp_select_bytes(K);
-    DXV_HIP(c, f.compWork.reserve(work, work, fs));
-    // the grid stops being what the frame's last launch wrote (dxv_fill_async's rules): a kept queue's zeros are gone, and whatever was made
-    // of the grid before -- fields, the mesh, the tree, these labels -- is stale
-    f.clearSig = 0;
-    grid_rewritten(f);
-    DXV_HIP(c, launch_comp_select(f.grid.p, f.compDim, f.compOf, f.compLabels.p, reinterpret_cast<const CompRecord*>(f.compTable.p), K, rule, arg, f.compWork.p, fs));
-    DXV_HIP(c, hipMemcpyAsync(c->pin->compSel[c->cur], comp_select_counters(f.compWork.p), sizeof(c->pin->compSel[c->cur]), hipMemcpyDeviceToHost, fs));
-    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
-    f.selPending = true; f.selRule = rule; f.selComponents = K;
+    DXV_HIP(c, f.comp.work.reserve(work, work, fs));
+    edited_in_place(f);                                                 // (these labels are stale with the rest)
+    DXV_HIP(c, launch_comp_select(f.grid.p, f.comp.dim, f.comp.of, f.comp.labels.p, reinterpret_cast<const CompRecord*>(f.comp.table.p), K, rule, arg, f.comp.work.p, fs));
+    PinnedFrame& pin = cur_pinned(c);
+    if (end_operator(c, f, fs, nullptr, pin.compSel, comp_select_counters(f.comp.work.p), sizeof(pin.compSel))) return 1;
+    f.comp.select.pending = true; f.comp.select.rule = rule; f.comp.select.components = K;
     return 0;
 }
 
-int dxv_components_select(dxv_ctx* c, int rule, uint32_t arg)
-{
-    if (dxv_components_select_async(c, rule, arg)) return 1;
-    return dxv_sync(c);
-}
+int dxv_components_select(dxv_ctx* c, int rule, uint32_t arg) { return blocking(c, dxv_components_select_async(c, rule, arg)); }
 
 int dxv_components_select_info(dxv_ctx* c, uint32_t* kept, uint32_t* dropped, uint64_t* voxels_changed)
 {
     if (!c) return 1;
     const Frame& f = cur_frame(c);
-    if (kept) *kept = f.selKept;
-    if (dropped) *dropped = f.selDropped;
-    if (voxels_changed) *voxels_changed = f.selChanged;
+    if (kept) *kept = f.comp.select.kept;
+    if (dropped) *dropped = f.comp.select.dropped;
+    if (voxels_changed) *voxels_changed = f.comp.select.changed;
     return 0;
 }
 
@@ -1089,40 +995,30 @@ int dxv_fill_async(dxv_ctx* c, int what)
         return fail(c, "dxv_fill: unknown kind %d (DXV_FILL_SOLID = 0, DXV_FILL_INTERIOR = 1)", what);
     if (check_whole_grid(c, "dxv_fill")) return 1;
     Frame& f = cur_frame(c);
-    DXV_HIP(c, hipSetDevice(c->device));
-    if (settle_frame_launch(c)) return 1;
-    const hipStream_t fs = cur_stream(c);
+    hipStream_t fs;
+    if (begin_operator(c, &fs)) return 1;
     const uint32_t N = f.grid_dim;
     const size_t scratch = fill_scratch_bytes(N);
-    DXV_HIP(c, f.fillScratch.reserve(scratch, scratch, fs));
-    const bool timed = c->opt.events != 0;
-    f.fillWhat = what;
-    f.fillBatch = c->opt.fillrounds ? (uint32_t)c->opt.fillrounds : kFillRoundsDefault;
-    f.fillRounds = 0;
-    // the grid stops being what the frame's last launch wrote: a kept queue's zeros are gone (the next launch clears everything; the
-    // caller holds no pointer because of this, so ptrExposed stays), and a field made of the grid before is stale
-    f.clearSig = 0;
-    grid_rewritten(f);
-    DXV_HIP(c, timer_begin(f.timers[kTimerFill], timed, fs));
-    DXV_HIP(c, launch_fill(f.grid.p, N, what, f.fillScratch.p, f.fillBatch, true, fs));
-    DXV_HIP(c, timer_end(f.timers[kTimerFill], timed, fs));
-    DXV_HIP(c, hipMemcpyAsync(c->pin->fillCtl[c->cur], fill_control(f.fillScratch.p, N), sizeof(c->pin->fillCtl[c->cur]), hipMemcpyDeviceToHost, fs));
-    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
-    f.fillPending = true;
+    DXV_HIP(c, f.fill.scratch.reserve(scratch, scratch, fs));
+    f.fill.what = what;
+    f.fill.batch = c->opt.fillrounds ? (uint32_t)c->opt.fillrounds : kFillRoundsDefault;
+    f.fill.rounds = 0;
+    edited_in_place(f);
+    DXV_HIP(c, timer_begin(f.timers[kTimerFill], c->opt.events != 0, fs));
+    DXV_HIP(c, launch_fill(f.grid.p, N, what, f.fill.scratch.p, f.fill.batch, true, fs));
+    PinnedFrame& pin = cur_pinned(c);
+    if (end_operator(c, f, fs, &f.timers[kTimerFill], pin.fillCtl, fill_control(f.fill.scratch.p, N), sizeof(pin.fillCtl))) return 1;
+    f.fill.pending = true;
     return 0;
 }
 
-int dxv_fill(dxv_ctx* c, int what)
-{
-    if (dxv_fill_async(c, what)) return 1;
-    return dxv_sync(c);
-}
+int dxv_fill(dxv_ctx* c, int what) { return blocking(c, dxv_fill_async(c, what)); }
 
 int dxv_fill_info(dxv_ctx* c, float* ms, uint32_t* rounds)
 {
     if (!c) return 1;
     if (ms) *ms = cur_frame(c).timers[kTimerFill].ms;
-    if (rounds) *rounds = cur_frame(c).fillRounds;
+    if (rounds) *rounds = cur_frame(c).fill.rounds;
     return 0;
 }
 
@@ -1138,47 +1034,37 @@ int dxv_morph_async(dxv_ctx* c, int op, uint32_t radius_sq)
         return fail(c, "dxv_morph: radius_sq %u is not in [1, %u]", radius_sq, kMorphMaxRadiusSq);
     if (check_whole_grid(c, "dxv_morph")) return 1;
     Frame& f = cur_frame(c);
-    DXV_HIP(c, hipSetDevice(c->device));
-    if (settle_frame_launch(c)) return 1;
-    const hipStream_t fs = cur_stream(c);
+    hipStream_t fs;
+    if (begin_operator(c, &fs)) return 1;
     const uint32_t N = f.grid_dim;
     const int form = morph_form(radius_sq, c->opt.morphform);
     const size_t scratch = morph_scratch_bytes(N, op, radius_sq, form);
-    DXV_HIP(c, f.morphScratch.reserve(scratch, scratch, fs));
-    const bool timed = c->opt.events != 0;
-    // the grid stops being what the frame's last launch wrote (dxv_fill_async's rules): a kept queue's zeros are gone, and whatever was made
-    // of the grid before -- fields, the mesh, the tree, labels -- is stale
-    f.clearSig = 0;
-    grid_rewritten(f);
-    DXV_HIP(c, timer_begin(f.timers[kTimerMorph], timed, fs));
-    DXV_HIP(c, launch_morph(f.grid.p, N, op, radius_sq, form, f.morphScratch.p, fs));
-    DXV_HIP(c, timer_end(f.timers[kTimerMorph], timed, fs));
-    DXV_HIP(c, hipMemcpyAsync(c->pin->morphCount[c->cur], morph_counters(f.morphScratch.p), sizeof(c->pin->morphCount[c->cur]), hipMemcpyDeviceToHost, fs));
-    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
-    f.morphPending = true;
+    DXV_HIP(c, f.morph.scratch.reserve(scratch, scratch, fs));
+    edited_in_place(f);
+    DXV_HIP(c, timer_begin(f.timers[kTimerMorph], c->opt.events != 0, fs));
+    DXV_HIP(c, launch_morph(f.grid.p, N, op, radius_sq, form, f.morph.scratch.p, fs));
+    PinnedFrame& pin = cur_pinned(c);
+    if (end_operator(c, f, fs, &f.timers[kTimerMorph], pin.morphCount, morph_counters(f.morph.scratch.p), sizeof(pin.morphCount))) return 1;
+    f.morph.pending = true;
     return 0;
 }
 
-int dxv_morph(dxv_ctx* c, int op, uint32_t radius_sq)
-{
-    if (dxv_morph_async(c, op, radius_sq)) return 1;
-    return dxv_sync(c);
-}
+int dxv_morph(dxv_ctx* c, int op, uint32_t radius_sq) { return blocking(c, dxv_morph_async(c, op, radius_sq)); }
 
 int dxv_morph_info(dxv_ctx* c, float* ms, uint64_t* voxels_set, uint64_t* voxels_cleared)
 {
     if (!c) return 1;
     const Frame& f = cur_frame(c);
     if (ms) *ms = f.timers[kTimerMorph].ms;
-    if (voxels_set) *voxels_set = f.morphSet;
-    if (voxels_cleared) *voxels_cleared = f.morphCleared;
+    if (voxels_set) *voxels_set = f.morph.set;
+    if (voxels_cleared) *voxels_cleared = f.morph.cleared;
     return 0;
 }
 
 // Topology-preserving thinning of the selected frame's grid (thin.hip), in place, enqueued on the frame's stream behind whatever it holds -- under
 // dxv_render_async's host-wait rule and dxv_fill_async's rules for the grid: one batch of iterations, the write-back, the batch's control block
 // into page-locked words, the frame's end event.  Whether the batch reached the fixed point is read where the frame is next synchronised
-// (settle_thin).
+// (settle_thin).  Everything is refused before anything is enqueued or waited for.
 int dxv_thin_async(dxv_ctx* c, int kind, uint32_t max_iterations)
 {
     if (!c) return 1;
@@ -1186,49 +1072,38 @@ int dxv_thin_async(dxv_ctx* c, int kind, uint32_t max_iterations)
         return fail(c, "dxv_thin: unknown kind %d (DXV_THIN_CURVE = 0, DXV_THIN_KERNEL = 1)", kind);
     if (check_whole_grid(c, "dxv_thin")) return 1;
     Frame& f = cur_frame(c);
-    DXV_HIP(c, hipSetDevice(c->device));
-    if (settle_frame_launch(c)) return 1;
-    const hipStream_t fs = cur_stream(c);
     const uint32_t N = f.grid_dim;
     if (N > kThinMaxN || (N & 1u)) return fail(c, "dxv_thin: a grid of side %u (needs an even side of at most %u)", N, kThinMaxN);
+    hipStream_t fs;
+    if (begin_operator(c, &fs)) return 1;
     const size_t scratch = thin_scratch_bytes(N);
-    DXV_HIP(c, f.thinScratch.reserve(scratch, scratch, fs));
-    const bool timed = c->opt.events != 0;
-    f.thinKind = kind;
-    f.thinBatch = c->opt.thinrounds ? (uint32_t)c->opt.thinrounds : kThinRoundsDefault;
-    f.thinBounded = max_iterations != 0u;
-    f.thinInBatch = thin_batch(f.thinBatch, max_iterations);
-    f.thinLeft = f.thinBounded ? max_iterations - f.thinInBatch : 0u;
-    f.thinIterations = 0;
-    f.thinRemoved = 0;
-    f.thinConverged = false;
-    // the grid stops being what the frame's last launch wrote (dxv_fill_async's rules): a kept queue's zeros are gone, and whatever was made
-    // of the grid before -- fields, the mesh, the tree, labels -- is stale
-    f.clearSig = 0;
-    grid_rewritten(f);
-    DXV_HIP(c, timer_begin(f.timers[kTimerThin], timed, fs));
-    DXV_HIP(c, launch_thin(f.grid.p, N, kind, f.thinScratch.p, f.thinInBatch, true, fs));
-    DXV_HIP(c, timer_end(f.timers[kTimerThin], timed, fs));
-    DXV_HIP(c, hipMemcpyAsync(&c->pin->thinCtl[c->cur], f.thinScratch.p, sizeof(ThinControl), hipMemcpyDeviceToHost, fs));
-    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
-    f.thinPending = true;
+    DXV_HIP(c, f.thin.scratch.reserve(scratch, scratch, fs));
+    f.thin.kind = kind;
+    f.thin.batch = c->opt.thinrounds ? (uint32_t)c->opt.thinrounds : kThinRoundsDefault;
+    f.thin.bounded = max_iterations != 0u;
+    f.thin.inBatch = thin_batch(f.thin.batch, max_iterations);
+    f.thin.left = f.thin.bounded ? max_iterations - f.thin.inBatch : 0u;
+    f.thin.iterations = 0;
+    f.thin.removed = 0;
+    f.thin.converged = false;
+    edited_in_place(f);
+    DXV_HIP(c, timer_begin(f.timers[kTimerThin], c->opt.events != 0, fs));
+    DXV_HIP(c, launch_thin(f.grid.p, N, kind, f.thin.scratch.p, f.thin.inBatch, true, fs));
+    if (end_operator(c, f, fs, &f.timers[kTimerThin], &cur_pinned(c).thinCtl, f.thin.scratch.p, sizeof(ThinControl))) return 1;
+    f.thin.pending = true;
     return 0;
 }
 
-int dxv_thin(dxv_ctx* c, int kind, uint32_t max_iterations)
-{
-    if (dxv_thin_async(c, kind, max_iterations)) return 1;
-    return dxv_sync(c);
-}
+int dxv_thin(dxv_ctx* c, int kind, uint32_t max_iterations) { return blocking(c, dxv_thin_async(c, kind, max_iterations)); }
 
 int dxv_thin_info(dxv_ctx* c, float* ms, uint32_t* iterations, uint64_t* voxels_removed, int* converged)
 {
     if (!c) return 1;
     const Frame& f = cur_frame(c);
     if (ms) *ms = f.timers[kTimerThin].ms;
-    if (iterations) *iterations = f.thinIterations;
-    if (voxels_removed) *voxels_removed = f.thinRemoved;
-    if (converged) *converged = f.thinConverged ? 1 : 0;
+    if (iterations) *iterations = f.thin.iterations;
+    if (voxels_removed) *voxels_removed = f.thin.removed;
+    if (converged) *converged = f.thin.converged ? 1 : 0;
     return 0;
 }
 } // extern "C"

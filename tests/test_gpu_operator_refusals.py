@@ -1,7 +1,8 @@
 """What the operators on a frame's grid (include/dxv.h: dxv_distance*, dxv_mesh_distance*, dxv_isosurface*, dxv_octree*, dxv_components*,
-dxv_fill*, dxv_morph*, dxv_render_async) refuse, word for word: the WHOLE text of dxv_last_error against the sentence written out here, with
-==.  A frame without a grid, a slab, a product that was never made or went stale, a wrong byte count, a NULL ms, a caller's pointer the
-library cannot use.  One cube at 16^3 throughout; every call under test returns before it enqueues anything."""
+dxv_measure*, dxv_thickness*, dxv_geodesic*, dxv_fill*, dxv_morph*, dxv_thin*, dxv_render_async) refuse, word for word: the WHOLE text of
+dxv_last_error against the sentence written out here, with ==.  A frame without a grid, a slab, a product that was never made or went stale,
+a wrong byte count, a NULL ms, a caller's pointer the library cannot use.  One cube at 16^3 throughout; every call under test returns before
+it enqueues anything.  And what a launch does to a fill, a thin or a geodesic of its frame that nobody has settled yet: it drops it."""
 import ctypes as C
 
 import numpy as np
@@ -10,7 +11,9 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 N = 16
-FIELD = 4 * N ** 3                                                      # bytes of a 16^3 field, of the labels
+FIELD = 4 * N ** 3                                                      # bytes of a 16^3 field, of the labels, of a map
+CAP_SQ = 17                                                             # of the thickness the tests make ...
+HISTOGRAM = 8 * (CAP_SQ + 1)                                            # ... and the bytes of its histogram
 
 
 @pytest.fixture(scope="module")
@@ -53,7 +56,11 @@ def operators(v):
             ("dxv_octree_expand", lambda: lib.dxv_octree_expand_async(ctx, None, 0, 0)), ("dxv_octree_expand", lambda: lib.dxv_octree_expand(ctx, None, 0, 0)),
             ("dxv_components", lambda: lib.dxv_components_async(ctx, 0, 6)), ("dxv_components", lambda: lib.dxv_components(ctx, 0, 6)),
             ("dxv_fill", lambda: lib.dxv_fill_async(ctx, 0)), ("dxv_fill", lambda: lib.dxv_fill(ctx, 0)),
-            ("dxv_morph", lambda: lib.dxv_morph_async(ctx, 0, 1)), ("dxv_morph", lambda: lib.dxv_morph(ctx, 0, 1))]
+            ("dxv_morph", lambda: lib.dxv_morph_async(ctx, 0, 1)), ("dxv_morph", lambda: lib.dxv_morph(ctx, 0, 1)),
+            ("dxv_thin", lambda: lib.dxv_thin_async(ctx, 0, 0)), ("dxv_thin", lambda: lib.dxv_thin(ctx, 0, 0)),
+            ("dxv_thickness", lambda: lib.dxv_thickness_async(ctx, 0, CAP_SQ)), ("dxv_thickness", lambda: lib.dxv_thickness(ctx, 0, CAP_SQ)),
+            ("dxv_geodesic", lambda: lib.dxv_geodesic_async(ctx, 0, 0, 0, None, 0, 0)), ("dxv_geodesic", lambda: lib.dxv_geodesic(ctx, 0, 0, 0, None, 0, 0)),
+            ("dxv_measure", lambda: lib.dxv_measure_async(ctx)), ("dxv_measure", lambda: lib.dxv_measure(ctx))]
 
 
 NO_GRID = {"dxv_distance": "dxv_distance: frame 1 has no grid yet (call dxv_voxelize first)",
@@ -61,13 +68,21 @@ NO_GRID = {"dxv_distance": "dxv_distance: frame 1 has no grid yet (call dxv_voxe
            "dxv_octree_expand": "dxv_octree_expand: frame 1 has no grid yet (call dxv_voxelize first)",
            "dxv_components": "dxv_components: frame 1 has no grid yet (call dxv_voxelize first)",
            "dxv_fill": "dxv_fill: frame 1 has no grid yet (call dxv_voxelize first)",
-           "dxv_morph": "dxv_morph: frame 1 has no grid yet (call dxv_voxelize first)"}
+           "dxv_morph": "dxv_morph: frame 1 has no grid yet (call dxv_voxelize first)",
+           "dxv_thin": "dxv_thin: frame 1 has no grid yet (call dxv_voxelize first)",
+           "dxv_thickness": "dxv_thickness: frame 1 has no grid yet (call dxv_voxelize first)",
+           "dxv_geodesic": "dxv_geodesic: frame 1 has no grid yet (call dxv_voxelize first)",
+           "dxv_measure": "dxv_measure: frame 1 has no grid yet (call dxv_voxelize first)"}
 SLAB = {"dxv_distance": "dxv_distance: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share",
         "dxv_octree": "dxv_octree: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share",
         "dxv_octree_expand": "dxv_octree_expand: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share",
         "dxv_components": "dxv_components: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share",
         "dxv_fill": "dxv_fill: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share",
-        "dxv_morph": "dxv_morph: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share"}
+        "dxv_morph": "dxv_morph: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share",
+        "dxv_thin": "dxv_thin: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share",
+        "dxv_thickness": "dxv_thickness: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share",
+        "dxv_geodesic": "dxv_geodesic: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share",
+        "dxv_measure": "dxv_measure: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share"}
 
 
 def test_a_frame_without_a_grid(v):
@@ -134,6 +149,18 @@ def accessors(v):
                        ("dxv_components_table_download", lambda: lib.dxv_components_table_download(ctx, p, 24)),
                        ("dxv_components_select", lambda: lib.dxv_components_select_async(ctx, 0, 0)),
                        ("dxv_components_select", lambda: lib.dxv_components_select(ctx, 0, 0))],
+        # (dxv_measure_table_bytes is the one size that speaks: 0 and the message, which `refused` is given as None)
+        "measure": [("dxv_measure_table_device_ptr", lambda: lib.dxv_measure_table_device_ptr(ctx)),
+                    ("dxv_measure_table_bytes", lambda: lib.dxv_measure_table_bytes(ctx) or None),
+                    ("dxv_measure_table_download", lambda: lib.dxv_measure_table_download(ctx, p, 96))],
+        "thickness": [("dxv_thickness_device_ptr", lambda: lib.dxv_thickness_device_ptr(ctx)),
+                      ("dxv_thickness_download", lambda: lib.dxv_thickness_download(ctx, p, FIELD)),
+                      ("dxv_thickness_histogram_download", lambda: lib.dxv_thickness_histogram_download(ctx, p, HISTOGRAM))],
+        "geodesic": [("dxv_geodesic_device_ptr", lambda: lib.dxv_geodesic_device_ptr(ctx)),
+                     ("dxv_geodesic_download", lambda: lib.dxv_geodesic_download(ctx, p, FIELD)),
+                     ("dxv_geodesic_info", lambda: lib.dxv_geodesic_info(ctx, None, None, None, None, None, None, None)),
+                     ("dxv_geodesic_work_info", lambda: lib.dxv_geodesic_work_info(ctx, None, None, None)),
+                     ("dxv_geodesic_path", lambda: lib.dxv_geodesic_path(ctx, 0, None, 0, C.byref(C.c_uint32())))],
     }
 
 
@@ -141,12 +168,18 @@ NONE_YET = {"distance": "%s: frame 0 has no distance field yet (call dxv_distanc
             "mesh distance": "%s: frame 0 has no mesh distance field yet (call dxv_mesh_distance first)",
             "isosurface": "%s: frame 0 has no isosurface yet (call dxv_isosurface first)",
             "octree": "%s: frame 0 has no octree yet (call dxv_octree first)",
-            "components": "%s: frame 0 has no components yet (call dxv_components first)"}
+            "components": "%s: frame 0 has no components yet (call dxv_components first)",
+            "measure": "%s: frame 0 has no measure yet (call dxv_measure first)",
+            "thickness": "%s: frame 0 has no thickness map yet (call dxv_thickness first)",
+            "geodesic": "%s: frame 0 has no geodesic map yet (call dxv_geodesic first)"}
 STALE = {"distance": "%s: frame 0 was launched again since its distance field was made: the field is stale",
          "mesh distance": "%s: frame 0 was launched or filled again since its mesh distance field was made: the field is stale",
          "isosurface": "%s: frame 0 was launched or filled again since its isosurface was made: the mesh is stale",
          "octree": "%s: frame 0 was launched, filled or expanded again since its octree was made: the tree is stale",
-         "components": "%s: frame 0 was launched, filled, expanded or selected again since its components were labelled: labels and table are stale"}
+         "components": "%s: frame 0 was launched, filled, expanded or selected again since its components were labelled: labels and table are stale",
+         "measure": "%s: frame 0 was launched, edited or labelled again since its components were measured: the measure is stale",
+         "thickness": "%s: frame 0 was launched or edited again since its thickness map was made: map and histogram are stale",
+         "geodesic": "%s: frame 0 was launched or edited again since its geodesic map was made: the map is stale"}
 
 
 def make_every_product(v):
@@ -156,12 +189,19 @@ def make_every_product(v):
     assert lib.dxv_isosurface(ctx, 0, 0.0, 0) == 0
     assert lib.dxv_octree(ctx) == 0
     assert lib.dxv_components(ctx, 0, 6) == 0
+    assert lib.dxv_measure(ctx) == 0
+    assert lib.dxv_thickness(ctx, 0, CAP_SQ) == 0
+    assert lib.dxv_geodesic(ctx, 0, 0, 0, None, 0, 0) == 0
 
 
 def sizes(v):
     lib, ctx = v._lib, v._ctx
     return (lib.dxv_distance_bytes(ctx), lib.dxv_mesh_distance_bytes(ctx), lib.dxv_octree_bytes(ctx), lib.dxv_components_labels_bytes(ctx),
-            lib.dxv_components_table_bytes(ctx))
+            lib.dxv_components_table_bytes(ctx), lib.dxv_thickness_bytes(ctx), lib.dxv_thickness_histogram_bytes(ctx), lib.dxv_geodesic_bytes(ctx),
+            lib.dxv_measure_table_bytes(ctx))
+
+
+NO_SIZES = (0,) * 9
 
 
 def test_products_that_were_never_made_and_products_gone_stale(v):
@@ -172,10 +212,13 @@ def test_products_that_were_never_made_and_products_gone_stale(v):
             refused(v, call(), NONE_YET[family] % who)
     refused(v, lib.dxv_isosurface(ctx, 0, 0.0, 0), "dxv_isosurface: frame 0 has no mesh distance field yet (call dxv_mesh_distance first)")
     refused(v, lib.dxv_isosurface_async(ctx, 1, 0.0, 0), "dxv_isosurface: frame 0 has no distance field yet (call dxv_distance first)")
-    assert sizes(v) == (0, 0, 0, 0, 0)
+    for fn in (lib.dxv_measure_async, lib.dxv_measure):                 # a grid and no labels to measure
+        refused(v, fn(ctx), "dxv_measure: frame 0 has no components yet (call dxv_components first)")
+    assert sizes(v) == NO_SIZES
     make_every_product(v)
     got = sizes(v)
     assert got[:2] == (FIELD, FIELD) and got[2] >= 8 and got[3] == FIELD and got[4] % 24 == 0 and got[4] > 0
+    assert got[5:8] == (FIELD, HISTOGRAM, FIELD) and got[8] == 96 * (got[4] // 24 + 1)
     assert lib.dxv_distance_device_ptr(ctx) and lib.dxv_octree_info(ctx, None, None, None) == 0
     v.Voxelize(N)                                                       # launched again: every one of them is stale
     for family, calls in accessors(v).items():
@@ -185,7 +228,9 @@ def test_products_that_were_never_made_and_products_gone_stale(v):
             "dxv_isosurface: frame 0 was launched or filled again since its mesh distance field was made: the field is stale")
     refused(v, lib.dxv_isosurface_async(ctx, 1, 0.0, 0),
             "dxv_isosurface: frame 0 was launched or filled again since its distance field was made: the field is stale")
-    assert sizes(v) == (0, 0, 0, 0, 0)
+    for fn in (lib.dxv_measure_async, lib.dxv_measure):
+        refused(v, fn(ctx), "dxv_measure: frame 0 was launched, filled, expanded or selected again since its components were labelled: labels and table are stale")
+    assert sizes(v) == NO_SIZES
     make_every_product(v)                                               # ... and can be made again
     assert sizes(v) == got
 
@@ -334,3 +379,54 @@ def test_octree_expand_refuses_a_tree_it_cannot_use(v):
     assert np.array_equal(v.OctreeNodes()[0], nodes)                   # ... and the frame's own tree is still current
     assert lib.dxv_octree_expand(ctx, C.c_void_p(ptr), n, 4) == 0      # the same call with what it asks for
     assert np.array_equal(v.Grid(), (grid != 0).astype(np.uint8))
+
+
+def test_a_launch_drops_what_is_unsettled(v, dxv, cube):
+    """a fill, a thin and a geodesic in batches of one round, each followed at once by a launch of the same frame: the launch's grid is a fresh
+    context's, the operator's verdict is dropped with it, and the same operator afterwards gives what it gives in a fresh context"""
+    lib, ctx = v._lib, v._ctx
+    fresh = dxv.Voxelizer(0)
+    try:
+        fresh.InitFromArrays(*cube)
+        fresh.Voxelize(N)
+        launched = fresh.Grid()
+        fresh.Fill()
+        filled = fresh.Grid()
+        fresh.Voxelize(N)
+        fresh.Thin(dxv.THIN_CURVE)
+        thinned, thinned_info = fresh.Grid(), fresh.thin_info()[1:]
+        fresh.Voxelize(N)
+        geodesic = fresh.Geodesic(dxv.COMP_SOLID, dxv.GEO_CHAMFER, "border")
+    finally:
+        fresh.close()
+    try:
+        for key in ("fillrounds", "thinrounds", "georounds"):
+            v.set_option(key, 1)
+        v.Voxelize(N)
+        # fill
+        assert lib.dxv_fill_async(ctx, 0) == 0
+        v.Voxelize(N)
+        assert np.array_equal(v.Grid(), launched)
+        assert lib.dxv_fill(ctx, 0) == 0, last(v)
+        assert np.array_equal(v.Grid(), filled)
+        # thin
+        v.Voxelize(N)
+        assert lib.dxv_thin_async(ctx, 0, 0) == 0
+        v.Voxelize(N)
+        assert np.array_equal(v.Grid(), launched)
+        assert v.thin_info()[3] == 0
+        assert lib.dxv_thin(ctx, 0, 0) == 0, last(v)
+        assert np.array_equal(v.Grid(), thinned) and v.thin_info()[1:] == thinned_info and thinned_info[2] == 1
+        # geodesic
+        v.Voxelize(N)
+        assert lib.dxv_geodesic_async(ctx, 0, 1, 0, None, 0, 0) == 0
+        v.Voxelize(N)
+        assert np.array_equal(v.Grid(), launched)
+        refused(v, lib.dxv_geodesic_info(ctx, None, None, None, None, None, None, None),
+                "dxv_geodesic_info: frame 0 was launched or edited again since its geodesic map was made: the map is stale")
+        assert lib.dxv_geodesic(ctx, 0, 1, 0, None, 0, 0) == 0, last(v)
+        assert np.array_equal(v.GeodesicField(), geodesic)
+        assert np.array_equal(v.Grid(), launched)                      # (a geodesic only reads the grid)
+    finally:
+        for key in ("fillrounds", "thinrounds", "georounds"):
+            v.set_option(key, 0)
