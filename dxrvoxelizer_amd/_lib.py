@@ -130,6 +130,19 @@ SYMBOLS = {
     "dxv_thickness_histogram_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "dxv_thickness_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "dxv_thickness_stage_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "dxv_partition_async": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_int]),
+    "dxv_partition": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_int]),
+    "dxv_partition_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "dxv_partition_labels_device_ptr": (C.c_void_p, [C.c_void_p]),
+    "dxv_partition_labels_bytes": (C.c_size_t, [C.c_void_p]),
+    "dxv_partition_labels_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_partition_table_device_ptr": (C.c_void_p, [C.c_void_p]),
+    "dxv_partition_table_bytes": (C.c_size_t, [C.c_void_p]),
+    "dxv_partition_table_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_partition_throats_device_ptr": (C.c_void_p, [C.c_void_p]),
+    "dxv_partition_throats_bytes": (C.c_size_t, [C.c_void_p]),
+    "dxv_partition_throats_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_partition_stage_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "dxv_geodesic_async": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32]),
     "dxv_geodesic": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32]),
     "dxv_geodesic_device_ptr": (C.c_void_p, [C.c_void_p]),

@@ -143,6 +143,7 @@ struct Timer { hipEvent_t e0 = nullptr, e1 = nullptr; bool armed = false; float 
 // (settle_batched), and sync_launch stops in front of them.
 enum TimerUse { kTimerLaunch, kTimerQueue, kTimerRender, kTimerDistance, kTimerMeshDistance, kTimerIso, kTimerOctree, kTimerComponents, kTimerMorph, kTimerMeasure, kTimerThickness,
                 kTimerThickStage0, kTimerThickStageLast = kTimerThickStage0 + dxv::THICK_STAGES - 1,     // the six stages of a thickness, each a pair of its own
+                kTimerPartition, kTimerPartStage0, kTimerPartStageLast = kTimerPartStage0 + dxv::PART_STAGES - 1,      // a partition and its six stages, likewise
                 kTimerFill, kTimerThin, kTimerGeodesic,
                 kTimers,
                 kTimerFirstOperator = kTimerRender, kTimerFirstBatched = kTimerFill };
@@ -340,6 +341,23 @@ struct dxv_ctx {
             uint64_t centres = 0, items = 0, tested = 0, sent = 0;   // of the frame's last thickness, as of its last synchronisation
             void trim() { scratch.release(); }   // (the fields, bytes and passes, 15 bytes per voxel; map and histogram themselves stay)
         } thick;
+        // maximal-ball partition (partition.hip; dxv_partition_async): labels, table and throats of the frame's grid, the scratch of their making
+        // (field or parents, keys, roots, the mips, the passes) and the work sized by its counts (the regions' stats, the sort of the faces)
+        struct Partition : Made {
+            DevBuf<uint32_t> labels;         // (cap: voxels)
+            DevBuf<uint8_t> table;           // (cap: regions) 32 bytes each
+            DevBuf<uint32_t> throats;        // (cap: throats) 20 bytes each
+            DevBuf<uint8_t> scratch;         // (cap: bytes) partition_scratch_bytes
+            DevBuf<uint8_t> work;            // (cap: bytes) partition_work_bytes
+            uint32_t dim = 0, cap = 0;       // grid side and cap_sq of the frame's last partition ...
+            int of = 0;                      // ... what it was asked for ...
+            bool hasThroats = false;         // ... and whether the throats were made with it
+            uint32_t regions = 0, throatCount = 0;
+            uint64_t faces = 0;              // its interface faces (0 without throats)
+            bool pending = false;            // its two counters are on their way into page-locked words: the frame's next synchronisation reads them
+            uint64_t cellsTested = 0, voxelsTested = 0;   // of the frame's last partition, as of its last synchronisation (option partstages)
+            void trim() { scratch.release(); work.release(); }   // (22 bytes per voxel and the sort's buffers; labels, table and throats themselves stay)
+        } part;
         // geodesic distance (geodesic.hip; dxv_geodesic_async): the map of the frame's grid, and the scratch of its making -- control block, live
         // flags, queue; the seeds of a list; the words of a path
         struct Geodesic : Made {
@@ -374,7 +392,7 @@ struct dxv_ctx {
             if (thin.pending) { thin.pending = false; thin.converged = false; }
             geo.pending = false;
         }
-        void trim_products() { dist.trim(); mdist.trim(); fill.trim(); iso.trim(); oct.trim(); comp.trim(); morph.trim(); thin.trim(); thick.trim(); geo.trim(); }
+        void trim_products() { dist.trim(); mdist.trim(); fill.trim(); iso.trim(); oct.trim(); comp.trim(); morph.trim(); thin.trim(); thick.trim(); part.trim(); geo.trim(); }
     };
     Frame frames[DXV_FRAME_COUNT];
     uint32_t cur = 0;                    // dxv_set_frame
@@ -412,6 +430,9 @@ struct dxv_ctx {
             unsigned long long morphCount[2];            // voxels set and voxels cleared by the frame's last morph
             dxv::ThinControl thinCtl;                    // the control block of the frame's last thin batch and the voxels removed so far
             unsigned long long thickCount[4];            // centres painted, work items, voxels tested and atomics sent of the frame's last thickness
+            unsigned long long partTotals[2];            // K and the interface faces of the partition the frame is making: size its table and its sort
+            unsigned long long partPairs[2];             // T of that partition: sizes its throats
+            unsigned long long partCount[2];             // mip cells and voxels tested by the search of the frame's last partition
             dxv::GeoControl geoCtl;                      // the control block of the frame's last geodesic batch and the tally behind it
         } frame[DXV_FRAME_COUNT];
     };

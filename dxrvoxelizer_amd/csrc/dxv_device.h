@@ -356,6 +356,47 @@ void thickness_layout(uint8_t* scratch, uint32_t N, ThickParams& p);
 const unsigned long long* thickness_counters(const ThickParams& p);
 hipError_t launch_thickness_stage(const uint8_t* grid, const ThickParams& p, int stage, hipStream_t s);
 
+// partition.hip -- the maximal-ball partition of a whole N^3 grid (dxv_partition.h): labels = N^3 uint32, table = 32 K bytes, throats = 20 T bytes,
+// all the caller's.  scratch = partition_scratch_bytes(N), laid out by partition_layout; work = partition_work_bytes(K, faces), laid out by
+// partition_work_layout once the caller has waited for partition_totals = {K, interface faces} behind PART_STAGE_ROOTS.  The stages are enqueued
+// one by one so that the caller can put its events between them; the throats take launch_partition_pairs, a wait for partition_pair_total = T, and
+// launch_partition_throats.  partition_counters points at {mip cells tested, voxels tested} of the search (option partstages).  The grid is only read.
+struct PartRegion;
+struct PartStats;
+struct PartParams {
+    uint32_t N;
+    int of;                           // DXV_COMP_SOLID / DXV_COMP_EMPTY
+    uint32_t cap, prune;              // cap_sq; option partprune
+    uint32_t count;                   // 1: the search counts what it tests (option partstages)
+    uint32_t wantThroats;             // 1: the interface faces are counted with the roots
+    uint32_t K;                       // partition_work_layout fills these two and the work pointers below
+    unsigned long long faces;
+    uint32_t* labels;                 // the caller's, in place from PART_STAGE_REGIONS on
+    PartRegion* table;
+    int32_t* F;                       // partition_layout fills these: the grid's field, and in the same words ...
+    uint32_t *parent, *number;        // ... every member's parent, then the roots' numbers
+    uint32_t* rootOf;
+    uint64_t *keys, *mip4, *mip16;
+    unsigned long long *sums, *counters;
+    uint8_t* passes;                  // distance_scratch_bytes(N)
+    PartStats* stats;
+    uint64_t *sortA, *sortB, *sorted, *pairs;     // the sort's two buffers; which of them holds the sorted words, and the other: the unique pairs
+    uint32_t* hist;
+    unsigned long long* headSums;
+    uint32_t* pairCount;
+};
+enum { PART_STAGE_FIELD, PART_STAGE_KEYS, PART_STAGE_SEARCH, PART_STAGE_ROOTS, PART_STAGE_REGIONS, PART_STAGE_THROATS, PART_STAGES };
+size_t partition_scratch_bytes(uint32_t N);
+void partition_layout(uint8_t* scratch, uint32_t N, PartParams& p);
+const unsigned long long* partition_totals(const PartParams& p);
+const unsigned long long* partition_counters(const PartParams& p);
+size_t partition_work_bytes(uint32_t K, unsigned long long faces);
+void partition_work_layout(uint8_t* work, uint32_t K, unsigned long long faces, PartParams& p);
+const unsigned long long* partition_pair_total(const PartParams& p);
+hipError_t launch_partition_stage(const uint8_t* grid, const PartParams& p, int stage, hipStream_t s);     // PART_STAGE_FIELD .. PART_STAGE_REGIONS
+hipError_t launch_partition_pairs(PartParams& p, hipStream_t s);
+hipError_t launch_partition_throats(const PartParams& p, uint32_t T, uint32_t* throats, hipStream_t s);
+
 // geodesic.hip -- the geodesic distance inside a whole N^3 grid (dxv_geodesic.h): map = N^3 uint32, the caller's; everything else in scratch =
 // geodesic_scratch_bytes(N): the batch's control block -- word k = the live tiles of round k; the batch has reached the fixed point exactly when
 // one of its words is 0 --, the tally {seeds used, reached, unreached, key}, two sets of live flags (a byte per 8^3 tile) and the queue (a word

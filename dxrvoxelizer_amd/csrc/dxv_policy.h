@@ -200,6 +200,8 @@ struct Options {
     int morphform = 0;       // dxv_morph*: 0 = by the radius (dxv_morph.h: morph_form), 1 = bit planes, 2 = distance field + threshold.  Same grids.
     int thickcull = 3;       // dxv_thickness*: bit 0 = the Top cull, bit 1 = neighbour domination (dxv_thickness.h).  Same map, same histogram.
     int thickstages = 0;     // dxv_thickness*: 1 = every stage between events of its own and the paint counts its tests and atomics (dxv_thickness_stage_info); measurement
+    int partprune = 3;       // dxv_partition*: bit 0 = the 4^3 mip level of the parent search, bit 1 = the 16^3 level (dxv_partition.h); 0 = the plain ball walk.  Same bytes.
+    int partstages = 0;      // dxv_partition*: 1 = every stage between events of its own and the search counts the cells and voxels it tests (dxv_partition_stage_info); measurement
     int mdistwalk = 1;       // dxv_mesh_distance*: 1 = the nearest-triangle query over the hierarchy, 0 = every triangle for every voxel (cross-check; same field)
     int sortbits = 0;        // digit plan of the radix sort as last set through this context (the plan itself is the process's: radix_sort_set_plan)
 };
@@ -269,6 +271,8 @@ constexpr OptionRow kGridPassOptions[] = {
     {"georounds", in_range(0, 64), "not in [0, 64]", &Options::georounds, OptionEffect::none},
     {"thickcull", in_range(0, 3), "not in {0,1,2,3}", &Options::thickcull, OptionEffect::none},
     {"thickstages", kOnOff, "not in {0,1}", &Options::thickstages, OptionEffect::none},
+    {"partprune", in_range(0, 3), "not in {0,1,2,3}", &Options::partprune, OptionEffect::none},
+    {"partstages", kOnOff, "not in {0,1}", &Options::partstages, OptionEffect::none},
 };
 
 inline const OptionRow* find_option(const char* name)

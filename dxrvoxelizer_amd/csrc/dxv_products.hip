@@ -1,7 +1,7 @@
 // dxv_products.hip -- what is made of a frame's grid, and what edits it in place: distance field, mesh distance field, isosurface, octree and
-// its expansion, components, their measures and select, thickness, geodesic distance, fill, morph, thin -- the host side of each (the kernels:
-// distance.hip, mesh_distance.hip, isosurface.hip, octree.hip, components.hip, measure.hip, thickness.hip, geodesic.hip, fill.hip, morph.hip,
-// thin.hip), the accessors of what they made, and their halves of a frame's synchronisation.  Each operator has a record in Frame (dxv_ctx.h);
+// its expansion, components, their measures and select, thickness, partition, geodesic distance, fill, morph, thin -- the host side of each (the
+// kernels: distance.hip, mesh_distance.hip, isosurface.hip, octree.hip, components.hip, measure.hip, thickness.hip, partition.hip, geodesic.hip,
+// fill.hip, morph.hip, thin.hip), the accessors of what they made, and their halves of a frame's synchronisation.  Each operator has a record in Frame (dxv_ctx.h);
 // what they share is here, in front of them: the refusals (check_whole_grid, check_current), an operator's first and last steps (begin_operator,
 // end_operator, blocking), the download of a product (download_current) and the loop of the operators that run in batches (settle_batched).
 #include "dxv_ctx.h"
@@ -14,6 +14,7 @@
 #include "dxv_morph.h"
 #include "dxv_thin.h"
 #include "dxv_thickness.h"
+#include "dxv_partition.h"
 #include "dxv_geodesic.h"
 
 using namespace dxv;
@@ -46,6 +47,7 @@ static const ProductText kComponentsText = {"components", "dxv_components",
                                             "was launched, filled, expanded or selected again since its components were labelled: labels and table are stale"};
 static const ProductText kMeasureText = {"measure", "dxv_measure", "was launched, edited or labelled again since its components were measured: the measure is stale"};
 static const ProductText kThicknessText = {"thickness map", "dxv_thickness", "was launched or edited again since its thickness map was made: map and histogram are stale"};
+static const ProductText kPartitionText = {"partition", "dxv_partition", "was launched or edited again since its partition was made: labels, table and throats are stale"};
 static const ProductText kGeodesicText = {"geodesic map", "dxv_geodesic", "was launched or edited again since its geodesic map was made: the map is stale"};
 
 // whether the selected frame has this product to hand out: 0, or 1 with the reason as the message
@@ -123,6 +125,11 @@ void read_products(dxv_ctx* c, uint32_t i)
         f.thick.tested = pin.thickCount[2];
         f.thick.sent = pin.thickCount[3];
         f.thick.pending = false;
+    }
+    if (f.part.pending) {                                               // the counters of the frame's last partition
+        f.part.cellsTested = pin.partCount[0];
+        f.part.voxelsTested = pin.partCount[1];
+        f.part.pending = false;
     }
 }
 
@@ -803,6 +810,156 @@ int dxv_thickness_stage_info(dxv_ctx* c, float ms[6], uint64_t* voxels_tested, u
     for (int stage = 0; stage < THICK_STAGES; ++stage) ms[stage] = f.timers[kTimerThickStage0 + stage].ms;
     if (voxels_tested) *voxels_tested = f.thick.tested;
     if (atomics_sent) *atomics_sent = f.thick.sent;
+    return 0;
+}
+
+// The maximal-ball partition of the selected frame's grid (partition.hip; dxv_partition.h has the rule's routines), enqueued on the frame's stream
+// behind whatever it holds, under dxv_render_async's host-wait rule: field, keys, search, roots and their numbering, {K, interface faces} into
+// page-locked words and the one wait for them -- the pattern of dxv_components_async: table and sort cannot be sized without them --, then labels
+// and table; with throats the faces' words, their sort, T into a page-locked word and a second wait, then the throat records; the frame's end
+// event, which nobody waits for here.  Nothing the frame holds is touched before the refusals are through; the product's own buffers are written
+// behind the first wait only.  The field of the grid is made into the scratch, never into the frame's distance field.
+int dxv_partition_async(dxv_ctx* c, int of, uint32_t cap_sq, int want_throats)
+{
+    if (!c) return 1;
+    if (of != DXV_COMP_SOLID && of != DXV_COMP_EMPTY) return fail(c, "dxv_partition: unknown kind %d (DXV_COMP_SOLID = 0, DXV_COMP_EMPTY = 1)", of);
+    if (cap_sq < kPartMinCapSq || cap_sq > kPartMaxCapSq) return fail(c, "dxv_partition: cap_sq %u is not in [%u, %u]", cap_sq, kPartMinCapSq, kPartMaxCapSq);
+    if (check_whole_grid(c, "dxv_partition")) return 1;
+    Frame& f = cur_frame(c);
+    const uint32_t N = f.grid_dim;
+    if (N > kThickMaxN) return fail(c, "dxv_partition: a grid of %u^3 voxels; at most %u^3 (a voxel's linear index must fit 30 bits)", N, kThickMaxN);
+    hipStream_t fs;
+    if (begin_operator(c, &fs)) return 1;
+    Frame::Partition& o = f.part;
+    const size_t voxels = (size_t)N * N * N, scratch = partition_scratch_bytes(N);
+    o.version = 0; o.have = false;
+    DXV_HIP(c, o.scratch.reserve(scratch, scratch, fs));
+    PartParams p{};
+    p.of = of; p.cap = cap_sq; p.prune = (uint32_t)c->opt.partprune; p.count = c->opt.partstages ? 1u : 0u; p.wantThroats = want_throats ? 1u : 0u;
+    partition_layout(o.scratch.p, N, p);
+    PinnedFrame& pin = cur_pinned(c);
+    const bool timed = c->opt.events != 0, staged = timed && c->opt.partstages != 0;       // (the stages' own pairs only for a caller that measures)
+    auto stage_begin = [&](int stage) { Timer& t = f.timers[kTimerPartStage0 + stage]; if (!staged) t.ms = 0.0f; return timer_begin(t, staged, fs); };
+    auto stage_end = [&](int stage) { return timer_end(f.timers[kTimerPartStage0 + stage], staged, fs); };
+    DXV_HIP(c, timer_begin(f.timers[kTimerPartition], timed, fs));
+    for (int stage = PART_STAGE_FIELD; stage <= PART_STAGE_ROOTS; ++stage) {
+        DXV_HIP(c, stage_begin(stage));
+        DXV_HIP(c, launch_partition_stage(f.grid.p, p, stage, fs));
+        DXV_HIP(c, stage_end(stage));
+    }
+    DXV_HIP(c, hipMemcpyAsync(pin.partTotals, partition_totals(p), sizeof(pin.partTotals), hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipStreamSynchronize(fs));
+    const uint32_t K = (uint32_t)pin.partTotals[0];
+    const unsigned long long faces = want_throats && K ? pin.partTotals[1] : 0ull;
+    const size_t work = partition_work_bytes(K, faces);
+    DXV_HIP(c, o.labels.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
+    if (K) DXV_HIP(c, o.table.reserve(K, align256((size_t)K * sizeof(PartRegion)), fs));
+    DXV_HIP(c, o.work.reserve(work, work, fs));
+    p.labels = o.labels.p; p.table = reinterpret_cast<PartRegion*>(o.table.p);
+    partition_work_layout(o.work.p, K, faces, p);
+    DXV_HIP(c, stage_begin(PART_STAGE_REGIONS));
+    DXV_HIP(c, launch_partition_stage(f.grid.p, p, PART_STAGE_REGIONS, fs));
+    DXV_HIP(c, stage_end(PART_STAGE_REGIONS));
+    uint32_t T = 0;
+    DXV_HIP(c, stage_begin(PART_STAGE_THROATS));
+    if (faces) {
+        DXV_HIP(c, launch_partition_pairs(p, fs));
+        DXV_HIP(c, hipMemcpyAsync(pin.partPairs, partition_pair_total(p), sizeof(pin.partPairs), hipMemcpyDeviceToHost, fs));
+        DXV_HIP(c, hipStreamSynchronize(fs));
+        T = (uint32_t)pin.partPairs[0];
+        if (T) {
+            DXV_HIP(c, o.throats.reserve(T, align256((size_t)T * sizeof(PartThroat)), fs));
+            DXV_HIP(c, launch_partition_throats(p, T, o.throats.p, fs));
+        }
+    }
+    DXV_HIP(c, stage_end(PART_STAGE_THROATS));
+    if (end_operator(c, f, fs, &f.timers[kTimerPartition], pin.partCount, partition_counters(p), sizeof(pin.partCount))) return 1;
+    o.pending = true;
+    o.dim = N; o.cap = cap_sq; o.of = of; o.hasThroats = want_throats != 0; o.regions = K; o.throatCount = T; o.faces = faces;
+    o.have = true; o.version = f.gridVersion;
+    return 0;
+}
+
+int dxv_partition(dxv_ctx* c, int of, uint32_t cap_sq, int want_throats) { return blocking(c, dxv_partition_async(c, of, cap_sq, want_throats)); }
+
+int dxv_partition_info(dxv_ctx* c, float* ms, uint32_t* regions, uint32_t* throats, uint64_t* interface_faces)
+{
+    if (!c) return 1;
+    const Frame& f = cur_frame(c);
+    const bool current = f.part.current(f);
+    if (ms) *ms = f.timers[kTimerPartition].ms;
+    if (regions) *regions = current ? f.part.regions : 0u;
+    if (throats) *throats = current ? f.part.throatCount : 0u;
+    if (interface_faces) *interface_faces = current ? f.part.faces : 0u;
+    return 0;
+}
+
+// the frame's partition (throats: with its throats), or 1 with the reason there is none to hand out as the message
+static int current_partition(const dxv_ctx* c, const char* who, bool throats)
+{
+    const Frame::Partition& o = cur_frame(c).part;
+    if (check_current(c, who, o, kPartitionText)) return 1;
+    if (throats && !o.hasThroats) return fail(const_cast<dxv_ctx*>(c), "%s: frame %u's partition was made without throats (want_throats = 0)", who, c->cur);
+    return 0;
+}
+
+const void* dxv_partition_labels_device_ptr(const dxv_ctx* c)
+{
+    if (!c || current_partition(c, "dxv_partition_labels_device_ptr", false)) return nullptr;
+    return cur_frame(c).part.labels.p;
+}
+size_t dxv_partition_labels_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame::Partition& o = cur_frame(c).part;
+    return o.current(cur_frame(c)) ? (size_t)o.dim * o.dim * o.dim * sizeof(uint32_t) : 0;
+}
+int dxv_partition_labels_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || current_partition(c, "dxv_partition_labels_download", false)) return 1;
+    return download_current(c, "dxv_partition_labels_download", cur_frame(c).part.labels.p, dxv_partition_labels_bytes(c), host, bytes);
+}
+const void* dxv_partition_table_device_ptr(const dxv_ctx* c)
+{
+    if (!c || current_partition(c, "dxv_partition_table_device_ptr", false)) return nullptr;
+    return cur_frame(c).part.regions ? cur_frame(c).part.table.p : nullptr;
+}
+size_t dxv_partition_table_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame::Partition& o = cur_frame(c).part;
+    return o.current(cur_frame(c)) ? (size_t)o.regions * sizeof(PartRegion) : 0;
+}
+int dxv_partition_table_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || current_partition(c, "dxv_partition_table_download", false)) return 1;
+    return download_current(c, "dxv_partition_table_download", cur_frame(c).part.table.p, dxv_partition_table_bytes(c), host, bytes);
+}
+const void* dxv_partition_throats_device_ptr(const dxv_ctx* c)
+{
+    if (!c || current_partition(c, "dxv_partition_throats_device_ptr", true)) return nullptr;
+    return cur_frame(c).part.throatCount ? cur_frame(c).part.throats.p : nullptr;
+}
+size_t dxv_partition_throats_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame::Partition& o = cur_frame(c).part;
+    return o.current(cur_frame(c)) && o.hasThroats ? (size_t)o.throatCount * sizeof(PartThroat) : 0;
+}
+int dxv_partition_throats_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || current_partition(c, "dxv_partition_throats_download", true)) return 1;
+    return download_current(c, "dxv_partition_throats_download", cur_frame(c).part.throats.p, dxv_partition_throats_bytes(c), host, bytes);
+}
+
+int dxv_partition_stage_info(dxv_ctx* c, float ms[6], uint64_t* cells_tested, uint64_t* voxels_tested)
+{
+    if (!c) return 1;
+    if (!ms) return fail(c, "dxv_partition_stage_info: ms is NULL");
+    const Frame& f = cur_frame(c);
+    for (int stage = 0; stage < PART_STAGES; ++stage) ms[stage] = f.timers[kTimerPartStage0 + stage].ms;
+    if (cells_tested) *cells_tested = f.part.cellsTested;
+    if (voxels_tested) *voxels_tested = f.part.voxelsTested;
     return 0;
 }
 

@@ -25,6 +25,9 @@ SELECT_LARGEST, SELECT_MIN_VOXELS, SELECT_BORDER = 0, 1, 2   # which components 
 COMP_RECORD = np.dtype([("first", "<u4"), ("voxels", "<u4"), ("lo", "<u2", (3,)), ("hi", "<u2", (3,)), ("flags", "<u4")])   # a row of the components' table, 24 bytes
 # a row of the measures' table, 96 bytes (include/dxv.h over dxv_measure_async)
 MEASURE_RECORD = np.dtype([("voxels", "<u8"), ("sum", "<u8", (3,)), ("sum2", "<u8", (3,)), ("prod", "<u8", (3,)), ("faces", "<u8"), ("euler", "<i8")])
+# a row of a partition's table, 32 bytes, and one of its throats, 20 bytes (include/dxv.h over dxv_partition_async)
+PART_REGION = np.dtype([("root", "<u4"), ("radius_sq", "<u4"), ("voxels", "<u4"), ("throats", "<u4"), ("lo", "<u2", (3,)), ("hi", "<u2", (3,)), ("flags", "<u4")])
+PART_THROAT = np.dtype([("a", "<u4"), ("b", "<u4"), ("faces", "<u4"), ("neck_sq", "<u4"), ("neck_voxel", "<u4")])
 DBG_SORTED_KEYS, DBG_NODES, DBG_TRI_POS, DBG_TRI_NRM, DBG_PARENTS, DBG_NODES32, DBG_NODES64, DBG_LIST_CELLS, DBG_LIST_ENTRIES, DBG_LIST_MIP = range(10)
 DBG_BRICK_EMPTY, DBG_BRICK_SUMMARY = 10, 11         # the display pass's empty-brick flags and the summaries behind them
 
@@ -74,6 +77,16 @@ def mass_properties(table):
             cross = V * pr[a] - s[a] * s[b]                             # prod[a] pairs axis a with axis a + 1: xy, yz, zx
             out["inertia"][r, a, b] = out["inertia"][r, b, a] = -cross / V
     return out
+
+
+def pore_network(table, throats):
+    """A partition's table and throats (PartitionTable, PartitionThroats) as a network, in voxels: {"radius": float64 [K], sqrt(radius_sq) of every
+    region's largest ball; "voxels": int64 [K]; "coordination": int64 [K], the throats that name the region; "pairs": int64 [T, 2], the labels a < b
+    of every throat; "neck_radius": float64 [T], sqrt(neck_sq); "faces": int64 [T]}.  Labels count from 1: region k is row k - 1.  Pure numpy."""
+    table, throats = np.atleast_1d(np.asarray(table, PART_REGION)), np.atleast_1d(np.asarray(throats, PART_THROAT))
+    return {"radius": np.sqrt(table["radius_sq"].astype(np.float64)), "voxels": table["voxels"].astype(np.int64), "coordination": table["throats"].astype(np.int64),
+            "pairs": np.stack([throats["a"], throats["b"]], axis=1).astype(np.int64) if len(throats) else np.zeros((0, 2), np.int64),
+            "neck_radius": np.sqrt(throats["neck_sq"].astype(np.float64)), "faces": throats["faces"].astype(np.int64)}
 
 
 def thickness_voxels(field):
@@ -659,6 +672,68 @@ class Voxelizer:
         ms, tested, sent = (C.c_float * 6)(), C.c_uint64(), C.c_uint64()
         self._check(self._lib.dxv_thickness_stage_info(self._ctx, ms, C.byref(tested), C.byref(sent)))
         return dict(zip(("field", "top", "cull", "select", "paint", "histogram"), (float(m) for m in ms))), tested.value, sent.value
+
+    # ---- the maximal-ball partition of the frame's grid --------------------------------------------------
+    def Partition(self, of=COMP_SOLID, capSq=4096, throats=True, sync=True, frameIndex=None):
+        """The maximal-ball partition of the selected frame's whole grid on the device (dxv_partition / dxv_partition_async; include/dxv.h has
+        the rule): every member voxel -- of = COMP_SOLID the non-zero voxels, COMP_EMPTY the zero ones -- points to the highest voxel of its own
+        closed ball of radius^2 R = min(D2, capSq), by R and then by the smaller index; the roots of that forest are the bodies, a region is the
+        family of one root, a throat is where two families share faces; 1 <= capSq <= 4096.  With COMP_EMPTY pores and throats, with
+        COMP_SOLID lobes and necks.  The grid and the frame's other products stay as they are.  sync=True returns (PartitionLabels(),
+        PartitionTable(), PartitionThroats() or None without throats); sync=False only enqueues it -- the call still waits for its own counts."""
+        if frameIndex is not None:
+            self.SetFrame(frameIndex)
+        fn = self._lib.dxv_partition if sync else self._lib.dxv_partition_async
+        self._check(fn(self._ctx, int(of), int(capSq), 1 if throats else 0))
+        return (self.PartitionLabels(), self.PartitionTable(), self.PartitionThroats() if throats else None) if sync else True
+
+    def PartitionLabels(self):
+        """numpy copy uint32 [N, N, N] (z, y, x) of the selected frame's region labels, 0 off the members (dxv_partition_labels_download;
+        synchronises the frame)."""
+        nbytes = self._lib.dxv_partition_labels_bytes(self._ctx)
+        if not nbytes:
+            self._lib.dxv_partition_labels_device_ptr(self._ctx)       # (sets the message: none yet, or stale)
+            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
+        n = round((nbytes // 4) ** (1.0 / 3.0))
+        out = np.empty((n, n, n), np.uint32)
+        self._check(self._lib.dxv_partition_labels_download(self._ctx, out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+    def PartitionTable(self):
+        """numpy copy [K] of the selected frame's regions, dtype PART_REGION (dxv_partition_table_download; synchronises the frame)."""
+        if not self._lib.dxv_partition_labels_device_ptr(self._ctx):
+            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
+        table = np.empty(self._lib.dxv_partition_table_bytes(self._ctx) // PART_REGION.itemsize, PART_REGION)
+        self._check(self._lib.dxv_partition_table_download(self._ctx, table.ctypes.data_as(C.c_void_p), table.nbytes))
+        return table
+
+    def PartitionThroats(self):
+        """numpy copy [T] of the selected frame's throats, dtype PART_THROAT (dxv_partition_throats_download; synchronises the frame); an
+        error for a partition made without them."""
+        throats = np.empty(self._lib.dxv_partition_throats_bytes(self._ctx) // PART_THROAT.itemsize, PART_THROAT)
+        self._check(self._lib.dxv_partition_throats_download(self._ctx, throats.ctypes.data_as(C.c_void_p), throats.nbytes))
+        return throats
+
+    def partition_device_ptrs(self):
+        """(labels, table, throats) device pointers of the selected frame's partition, for consumers on the GPU; the table's is None when K = 0,
+        the throats' when T = 0 or when it was made without them."""
+        labels = self._lib.dxv_partition_labels_device_ptr(self._ctx)
+        if not labels:
+            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
+        return labels, self._lib.dxv_partition_table_device_ptr(self._ctx), self._lib.dxv_partition_throats_device_ptr(self._ctx)
+
+    def PartitionInfo(self):
+        """(ms, regions, throats, interface_faces) of the selected frame's last partition as of its last Sync (dxv_partition_info)."""
+        ms, regions, throats, faces = C.c_float(), C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self._check(self._lib.dxv_partition_info(self._ctx, C.byref(ms), C.byref(regions), C.byref(throats), C.byref(faces)))
+        return ms.value, regions.value, throats.value, faces.value
+
+    def partition_stage_info(self):
+        """({stage: ms}, cells_tested, voxels_tested) of the selected frame's last partition as of its last Sync (dxv_partition_stage_info): the
+        six stages' device times and the mip cells and voxels the parent search tested, under option partstages = 1 (else all 0)."""
+        ms, cells, voxels = (C.c_float * 6)(), C.c_uint64(), C.c_uint64()
+        self._check(self._lib.dxv_partition_stage_info(self._ctx, ms, C.byref(cells), C.byref(voxels)))
+        return dict(zip(("field", "keys", "search", "roots", "regions", "throats"), (float(m) for m in ms))), cells.value, voxels.value
 
     # ---- the geodesic distance inside the frame's grid ---------------------------------------------------
     def Geodesic(self, of=COMP_SOLID, metric=GEO_CHAMFER, seeds="border", limit=0, sync=True, frameIndex=None):

@@ -792,6 +792,73 @@ DXV_API int dxv_thickness_info(dxv_ctx* ctx, float* ms, uint64_t* centres_painte
  * The latter depends on the order the work items ran in and differs from run to run; the two pointers may be NULL. */
 DXV_API int dxv_thickness_stage_info(dxv_ctx* ctx, float ms[6], uint64_t* voxels_tested, uint64_t* atomics_sent);
 
+/* Maximal-ball partition: cut ONE connected piece at its necks (no reference counterpart).  dxv_components sees one component where the user sees
+ * a network; dxv_thickness gives the width per voxel.  This operator gives the bodies and what joins them -- of the EMPTY space the pores and the
+ * throats between them with each throat's width, of the SOLID the lobes of a part and the necks between them: the step from per-voxel maps to a
+ * graph (Silin & Patzek; Dong & Blunt 2009).
+ * Input: the WHOLE grid of the selected frame's last launch, in any mode.  Bytes written through dxv_grid_device_ptr count too.  solid(p) iff
+ * byte(p) != 0.  Only voxels inside the grid exist: its border is not "outside", as for dxv_thickness and dxv_distance.
+ * of = DXV_COMP_SOLID (0) or DXV_COMP_EMPTY (1) picks the members M; cap_sq is an integer, 1 <= cap_sq <= 4096.  Integers only, with
+ * index(v) = (z N + y) N + x and dxv_thickness's R:
+ *     R(v)      = min(D2(v), cap_sq) for v in M, 0 elsewhere                (D2: dxv_distance's d2; no voxel outside M: +infinity)
+ *     u above v   iff R(u) > R(v), or R(u) == R(v) and index(u) < index(v)  a strict total order on the grid's voxels
+ *     parent(c) = the highest voxel of the CLOSED ball { u in the grid : |u - c|^2 <= R(c) }     for c in M
+ *     root(c)   = where the chain c, parent(c), parent(parent(c)), ... ends (every step goes strictly up the order)
+ * One region per root, numbered 1 .. K by ascending index(root); label(v) = the number of root(v) on members, 0 elsewhere.  A face is a pair of
+ * members p, q = p + e, e in {+x, +y, +z}; it is an interface face iff label(p) != label(q).  One throat per unordered pair of labels that share
+ * at least one interface face, sorted ascending by (a, b), a < b.
+ * Output: labels, one uint32 per voxel, element (iz * N + iy) * N + ix like the grid, 4 N^3 bytes.  The table, K records of 32 bytes, little endian:
+ *     uint32 root, radius_sq (= R(root)), voxels, throats; uint16 lo[3], hi[3] (x, y, z); uint32 flags
+ * flags bit 0: the region has a voxel with a coordinate 0 or N - 1; throats: the throat records that name the region.  The throats, T records of
+ * 20 bytes:
+ *     uint32 a, b, faces, neck_sq, neck_voxel
+ * faces: the pair's interface faces; neck_sq: the maximum over them of min(R(p), R(q)); neck_voxel: the smallest index(p) among the faces that
+ * attain it.  Every step is a set function over the order: the device's bytes equal a restatement byte for byte, whatever ran first.
+ * Three properties of the rule, to know and not to "fix":
+ *  - A region is a family of balls.  It is 26-connected through its balls but need not be a 6-connected set.
+ *  - cap_sq bounds the search's reach.  A body thicker than the cap may fall into several regions: choose cap_sq at least the largest radius^2
+ *    of interest.
+ *  - A tube of constant width is cut into pieces about its diameter long, and a faceted corner of R = 1 can stay a region of one voxel.
+ * dxv_partition_async -- ENQUEUED on the frame's stream behind whatever it holds.  The host waits once in the middle, for K and the number of
+ * interface faces -- table and sort cannot be sized without them --, and with want_throats != 0 a second time, for T.  The grid is read and none
+ * of the frame's other products is written -- a current distance field, thickness map or labelling stays current and unchanged: the operator
+ * makes its field in its own scratch.
+ *  - want_throats = 0 skips the throats: the same labels and the same table except each record's `throats` word, which is 0 then; the throats'
+ *    pointer, size and download then fail with a message.
+ *  - The host waits before that only under dxv_render_async's rule; a pending fill or thin is settled first.
+ *  - Checked on the host before anything is enqueued, each an error with a message that leaves the frame's earlier partition and everything else
+ *    as it was: of is one of the two; 1 <= cap_sq <= 4096; the frame has been launched; its last launch was the whole grid; grid_dim <= 1024.
+ *    No count of regions is refused: a pair of labels is sorted as one word of twice the bits of K.
+ *  - Labels, table, throats, scratch (22 bytes per voxel) and the work of the sort belong to the frame: frames run side by side.  dxv_trim gives
+ *    scratch and work back.
+ *  - Labels, table and throats are STALE once the frame is launched, filled, morphed, thinned, expanded or selected again: pointers, sizes and
+ *    downloads then fail with a message.
+ *  - Option events = 1 (default): bracketed by the frame's own events, read at the frame's dxv_sync.
+ * dxv_partition -- the same + dxv_sync. */
+DXV_API int dxv_partition_async(dxv_ctx* ctx, int of, uint32_t cap_sq, int want_throats);
+DXV_API int dxv_partition(dxv_ctx* ctx, int of, uint32_t cap_sq, int want_throats);
+/* The selected frame's last partition as of the frame's last dxv_sync: device time in milliseconds from its first kernel to its last, the two
+ * waits included (HIP events, option events = 1; else 0); K, T and the interface faces of the frame's CURRENT partition (0 when none or stale).
+ * Any pointer may be NULL. */
+DXV_API int dxv_partition_info(dxv_ctx* ctx, float* ms, uint32_t* regions, uint32_t* throats, uint64_t* interface_faces);
+/* Labels, table and throats on the device (valid after dxv_sync or on the frame's stream), their sizes -- 4 * grid_dim^3, 32 K and 20 T bytes --
+ * and their copies to the host (bytes must be the size; synchronises the frame first).  NULL / 0 (pointer and download with a message) before the
+ * frame's first partition or when it is stale; the throats' also for a partition made with want_throats = 0.  With K = 0 (T = 0) the table's
+ * (throats') pointer is NULL and its size 0, without a message. */
+DXV_API const void* dxv_partition_labels_device_ptr(const dxv_ctx* ctx);
+DXV_API size_t dxv_partition_labels_bytes(const dxv_ctx* ctx);
+DXV_API int dxv_partition_labels_download(dxv_ctx* ctx, void* host, size_t bytes);
+DXV_API const void* dxv_partition_table_device_ptr(const dxv_ctx* ctx);
+DXV_API size_t dxv_partition_table_bytes(const dxv_ctx* ctx);
+DXV_API int dxv_partition_table_download(dxv_ctx* ctx, void* host, size_t bytes);
+DXV_API const void* dxv_partition_throats_device_ptr(const dxv_ctx* ctx);
+DXV_API size_t dxv_partition_throats_bytes(const dxv_ctx* ctx);
+DXV_API int dxv_partition_throats_download(dxv_ctx* ctx, void* host, size_t bytes);
+/* ... and, for measurements, under option partstages = 1 (else all 0): the times of its six stages, each between events of its own -- the grid's
+ * field; keys and mips; the parent search; chain walk, counts and numbering; labels, stats and table; throats -- with the mip cells and the voxels
+ * the search tested.  The two pointers may be NULL. */
+DXV_API int dxv_partition_stage_info(dxv_ctx* ctx, float ms[6], uint64_t* cells_tested, uint64_t* voxels_tested);
+
 /* Geodesic distance: how far one place is from another THROUGH the part, or through its empty space (no reference counterpart).  dxv_distance is
  * the straight-line distance to the other kind of voxel and dxv_fill knows only whether the border can be reached; this operator gives, per
  * member voxel, the length of the shortest path of member voxels to the nearest seed: the length of a dxv_thin skeleton branch, the path between
@@ -1000,6 +1067,10 @@ DXV_API int dxv_get_stats(const dxv_ctx* ctx, dxv_stats* out);
  *                 2 <= R < cap_sq is painted; measurement, cross-check).  Same map, same histogram.
  *   thickstages 0|1  dxv_thickness*: 1 = every stage stands between events of its own and the paint counts the voxels it tests and the atomics it
  *                 sends, for dxv_thickness_stage_info (measurement: twelve more event records per call); 0 (default): neither.  Same map.
+ *   partprune 0..3  dxv_partition*: which mip levels prune the parent search: bit 0 = the maxima over 4^3 bricks, bit 1 = those over 16^3 cells
+ *                 (3, default: both; 0: the plain walk over every ball, r^3 per voxel; measurement, cross-check).  Same labels, table, throats.
+ *   partstages 0|1  dxv_partition*: 1 = every stage stands between events of its own and the search counts the mip cells and the voxels it
+ *                 tests, for dxv_partition_stage_info (measurement: twelve more event records per call); 0 (default): neither.  Same bytes.
  *   mdistwalk 0|1 dxv_mesh_distance*: 1 (default) = nearest-triangle query over the hierarchy; 0 = every triangle for every voxel, the
  *                 on-device cross-check (seconds on large scenes).  Same field.
  *   morton 0|1, region 0..24, subbox 0|1   brick order, bricks per XCD region (log2), partial launch */
@@ -1049,7 +1120,7 @@ DXV_API int dxv_debug_queue_order(dxv_ctx* ctx, uint64_t out[4]);
 
 /* Give back what the context keeps only to make the next build faster: the list build's scratch (up to 16 GiB per buffer
  * after a 10 M-triangle scene), the LBVH build's scratch when no refit can follow (imported scenes), the memory of prepared queues
- * whose lists are gone, the scratch of the frames' distance fields (the fields stay), of their flood fills, morphs, thins, thickness and geodesic maps (the maps stay), of their isosurfaces (the
+ * whose lists are gone, the scratch of the frames' distance fields (the fields stay), of their flood fills, morphs, thins, thickness and geodesic maps and partitions (maps, labels and tables stay), of their isosurfaces (the
  * meshes stay), of their octrees (the nodes stay) and of their connected components (labels and table stay).  Nothing a launch reads. */
 DXV_API int dxv_trim(dxv_ctx* ctx);
 

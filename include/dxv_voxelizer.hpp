@@ -328,6 +328,43 @@ public:
 	bool ThicknessInfo(float& ms, uint64_t& centresPainted, uint64_t& workItems) { return m_ctx && dxv_thickness_info(m_ctx, &ms, &centresPainted, &workItems) == 0; }
 	static float ThicknessVoxels(uint32_t w) { return w ? 2.0f * sqrtf((float)w) - 1.0f : 0.0f; }
 
+	// The maximal-ball partition of the selected frame's whole grid (dxv_partition / dxv_partition_async; include/dxv.h has the rule and the two
+	// record layouts): regions -- pore bodies of the empty space, lobes of the solid -- as labels and a table of 32-byte records, and the throats
+	// between them as 20-byte records.  The grid and the frame's other products stay as they are.  A region is a family of balls and need not be
+	// 6-connected; choose capSq at least the largest radius^2 of interest; a tube of constant width is cut into pieces about its diameter long.
+	struct PartitionRegion { uint32_t root, radiusSq, voxels, throats; uint16_t lo[3], hi[3]; uint32_t flags; };
+	struct PartitionThroat { uint32_t a, b, faces, neckSq, neckVoxel; };
+	bool Partition(int of = DXV_COMP_SOLID, uint32_t capSq = 4096, bool throats = true, bool sync = true)
+	{
+		return m_ctx && (sync ? dxv_partition(m_ctx, of, capSq, throats ? 1 : 0) : dxv_partition_async(m_ctx, of, capSq, throats ? 1 : 0)) == 0;
+	}
+	const void* DevicePartitionLabels() const { return m_ctx ? dxv_partition_labels_device_ptr(m_ctx) : nullptr; }
+	bool PartitionLabels(std::vector<uint32_t>& labels)
+	{
+		if (!m_ctx) return setError("PartitionLabels before Init");
+		const size_t bytes = dxv_partition_labels_bytes(m_ctx);
+		if (!bytes) return dxv_partition_labels_device_ptr(m_ctx) != nullptr;      // (false, with the message: none yet, or stale)
+		labels.resize(bytes / sizeof(uint32_t));
+		return dxv_partition_labels_download(m_ctx, labels.data(), bytes) == 0;
+	}
+	bool PartitionTable(std::vector<PartitionRegion>& table)
+	{
+		if (!m_ctx) return setError("PartitionTable before Init");
+		static_assert(sizeof(PartitionRegion) == 32, "a region record is 32 bytes");
+		const size_t bytes = dxv_partition_table_bytes(m_ctx);
+		table.resize(bytes / sizeof(PartitionRegion));
+		return dxv_partition_table_download(m_ctx, table.data(), bytes) == 0;
+	}
+	bool PartitionThroats(std::vector<PartitionThroat>& throats)
+	{
+		if (!m_ctx) return setError("PartitionThroats before Init");
+		static_assert(sizeof(PartitionThroat) == 20, "a throat record is 20 bytes");
+		const size_t bytes = dxv_partition_throats_bytes(m_ctx);
+		throats.resize(bytes / sizeof(PartitionThroat));
+		return dxv_partition_throats_download(m_ctx, throats.data(), bytes) == 0;
+	}
+	bool PartitionInfo(float& ms, uint32_t& regions, uint32_t& throats, uint64_t& interfaceFaces) { return m_ctx && dxv_partition_info(m_ctx, &ms, &regions, &throats, &interfaceFaces) == 0; }
+
 	// The geodesic distance inside the selected frame's whole grid (dxv_geodesic / dxv_geodesic_async; include/dxv.h has the rule): per member voxel
 	// the length of the shortest path of member voxels to the nearest seed -- DXV_GEO_FACES over the face neighbours at weight 1, DXV_GEO_CHAMFER
 	// over the 26 neighbours at weights 3 / 4 / 5 --, DXV_GEO_NONE on the others, DXV_GEO_UNREACHED where no path exists or is longer than limit
