@@ -7,6 +7,7 @@
 #include "../../dxrvoxelizer_amd/csrc/dxv_raycast.h"
 
 #include <algorithm>
+#include <parallel/algorithm>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -59,6 +60,27 @@ static uint32_t refit(HcScene& s, int32_t link, float lo[3], float hi[3])
     set_child(n, 1, l1, h1, b);
     for (int k = 0; k < 3; ++k) { lo[k] = min_(l0[k], l1[k]); hi[k] = max_(h0[k], h1[k]); }
     return (a > b ? a : b) + 1;
+}
+
+// One voxel of a brick kernel of voxelize_lists.hip, behind the brick's set-up: the calls the kernel makes, in its order, on a
+// column of the kernel's size (a queue of 16 words; HITLDS 1: the hit's four words behind it).
+// HITLDS 1 = k_voxelize_listed<true> (the hit in the column, shade_reference_lds), 2 = both kernels with the texel image off (t and
+// the slot only, shade_reference_again: no texel).
+template <int HITLDS>
+static uint8_t voxel_listed(const SceneView& sc, uint32_t N, uint32_t ix, uint32_t iy, uint32_t iz, uint32_t& texel)
+{
+    int32_t column[HITLDS == 1 ? 20 : 16];
+    const StridedStack stk{column, 1};
+    Ray r;
+    ray_origin(N, ix, iy, iz, r.ox, r.oy, r.oz);
+    const DirMapView dm{static_cast<const DirCell*>(sc.dmCells), static_cast<const DirEntry*>(sc.dmEntries), sc.dmR, sc.dmCoop};
+    DirRayStart start = dm_ray_start(r.ox, r.oy, r.oz, dm);
+    if (origin_leaves_root(r.ox, r.oy, r.oz, sc.rootLo, sc.rootHi)) start.live = false;
+    Hit best;
+    float bestDet = 1.0f;
+    trace_reference_dm_from<StridedStack, 0, HITLDS>(r, dm, start, sc.triPos, stk, 16, best, bestDet);
+    texel = 0;
+    return HITLDS == 1 ? shade_reference_lds(sc, r, best.leaf, stk, 16, &texel) : shade_reference_again(sc, r, best.leaf);
 }
 
 extern "C" {
@@ -128,8 +150,14 @@ __attribute__((visibility("default"))) uint64_t hc_dirmap_build(void* p, uint32_
     std::vector<uint64_t> keys;
     std::vector<DirRecord> rec((size_t)s->T * 6);
     const DirKeyLayout lay = dm_key_layout(R);
-    for (uint32_t t = 0; t < s->T; ++t)
-        for (uint32_t f = 0; f < 6; ++f) {
+    // (a key per (texel, triangle), each made once: whichever thread makes it, the sorted list is the same -- cube-spanning triangles on a
+    // fine map are tens of millions of them)
+#pragma omp parallel
+    {
+        std::vector<uint64_t> mine;
+#pragma omp for schedule(dynamic, 4) nowait
+        for (int64_t t6 = 0; t6 < (int64_t)s->T * 6; ++t6) {
+            const uint32_t t = (uint32_t)(t6 / 6), f = (uint32_t)(t6 % 6);
             DirRecord e = dm_record(s->triPos[t], f);
             uint32_t i0, i1, j0, j1;
             const bool seen = dm_rect(e, R, i0, i1, j0, j1);
@@ -142,18 +170,24 @@ __attribute__((visibility("default"))) uint64_t hc_dirmap_build(void* p, uint32_
                     if (dm_texel_outside(tt, R, i, j)) continue;
                     uint32_t r0h, r1h;
                     dm_local_radial(e, R, i, j, r0h, r1h);
-                    keys.push_back(dm_key(lay, (f * R + j) * R + i, (uint16_t)r1h, t));
+                    mine.push_back(dm_key(lay, (f * R + j) * R + i, (uint16_t)r1h, t));
                 }
         }
-    std::sort(keys.begin(), keys.end());
+#pragma omp critical
+        keys.insert(keys.end(), mine.begin(), mine.end());
+    }
+    __gnu_parallel::sort(keys.begin(), keys.end());
     s->dmR = R;
     s->dmCells.assign((size_t)6 * R * R, DirCell{0, 0, 0, 0, 0, 0, 0});
     s->dmEntries.assign(keys.size() + 3, DirEntry{0, 0, 0, 0});          // (+ three spare ones: a scan round loads four)
-    for (size_t i = 0; i < keys.size(); ++i) {
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < (int64_t)keys.size(); ++i) {
         const uint32_t cell = dm_key_cell(lay, keys[i]), t = dm_key_tri(lay, keys[i]);
-        const DirRecord& rc = rec[(size_t)t * 6 + cell / (R * R)];
         const uint32_t inFace = cell % (R * R);
-        s->dmEntries[i] = dm_local_entry(rc, R, inFace % R, inFace / R, t);
+        s->dmEntries[i] = dm_local_entry(rec[(size_t)t * 6 + cell / (R * R)], R, inFace % R, inFace / R, t);
+    }
+    for (size_t i = 0; i < keys.size(); ++i) {
+        const uint32_t cell = dm_key_cell(lay, keys[i]);
         if (i == 0 || dm_key_cell(lay, keys[i - 1]) != cell) s->dmCells[cell].begin = (uint32_t)i;
         if (s->dmCells[cell].count == 0xffffu) return ~0ull;             // does not fit the 16-bit count
         s->dmCells[cell].count++;
@@ -161,7 +195,9 @@ __attribute__((visibility("default"))) uint64_t hc_dirmap_build(void* p, uint32_
         const uint32_t th = half_up(dm_entry_r1(s->dmEntries[i]) - dm_entry_r0(s->dmEntries[i]));
         if (th > s->dmCells[cell].thick) s->dmCells[cell].thick = (uint16_t)th;
     }
-    for (DirCell& cell : s->dmCells) {
+#pragma omp parallel for schedule(dynamic, 256)
+    for (int64_t ci = 0; ci < (int64_t)s->dmCells.size(); ++ci) {
+        DirCell& cell = s->dmCells[ci];
         const float step = dm_stop_step(half_bits_to_float(cell.thick));   // stop codes: from the far end, earliest start so far
         float smin = 3.0e38f;
         for (uint32_t k = cell.count; k-- > 0u;) {
@@ -424,7 +460,8 @@ __attribute__((visibility("default"))) int hc_voxelize(void* p, uint32_t N, int 
     int overflow = 0;
     SceneView sc{s->nodes32.data(), s->triPos.data(), s->triNrm.data(), {0, 0, 0}, {0, 0, 0}, s->nodes64.data(),
                  s->dmCells.data(), s->dmEntries.data(), s->dmR};
-    if (mode == 12 && !s->dmR) return -1;
+    if ((mode == 12 || mode == 14 || mode == 15) && !s->dmR) return -1;
+    if (mode == 15 && texels) return -1;           // (the kernels with the texel image off compute none)
     {   // root box = union of the root node's two child boxes (as k_root_info computes it)
         const float* w = reinterpret_cast<const float*>(&s->nodes[0]);
         for (int a = 0; a < 3; ++a) { sc.rootLo[a] = min_(w[a], w[6 + a]); sc.rootHi[a] = max_(w[3 + a], w[9 + a]); }
@@ -438,7 +475,10 @@ __attribute__((visibility("default"))) int hc_voxelize(void* p, uint32_t N, int 
             const size_t id = ((size_t)lz * N + iy) * N + ix;
             bool ovf = false;
             uint32_t texel = 0;
-            out[id] = mode == 0 ? voxel_reference<0>(sc, N, ix, iy, iz, stk, stackCap, texels ? &texel : nullptr, ovf)
+            // 14, 15: the brick kernels' own bodies (the hit in the column; t and the slot only), on a column of their size
+            out[id] = mode == 14 ? voxel_listed<1>(sc, N, ix, iy, iz, texel)
+                      : mode == 15 ? voxel_listed<2>(sc, N, ix, iy, iz, texel)
+                      : mode == 0 ? voxel_reference<0>(sc, N, ix, iy, iz, stk, stackCap, texels ? &texel : nullptr, ovf)
                       : mode == 2 ? voxel_reference<1>(sc, N, ix, iy, iz, stk, stackCap, texels ? &texel : nullptr, ovf)
                       : mode == 6 ? voxel_reference<2>(sc, N, ix, iy, iz, stk, stackCap, texels ? &texel : nullptr, ovf)
                       : mode == 12 ? voxel_reference<4>(sc, N, ix, iy, iz, stk, stackCap, texels ? &texel : nullptr, ovf)

@@ -83,10 +83,100 @@ def test_fuzz_host_code_vs_brute_force(orc, hostcheck, seed, n_tris):
         g, ovf = h.voxelize(N, mode)
         assert not ovf
         assert np.array_equal(g, want[0 if mode in (0, 2, 6) else 1]), (seed, mode)
+    # the texel image of the reference rule: the packed normal of every inside hit, nothing anywhere else
+    grid, tex = s.voxelize(N, algo=orc.ALGO_BRUTE, texels=True)
+    assert np.array_equal(grid, want[0]) and np.array_equal(tex != 0, grid != 0)
+    for mode in (0, 2, 6):
+        g, t, ovf = h.voxelize(N, mode, texels=True)
+        assert not ovf and np.array_equal(g, grid), (seed, mode)
+        assert np.array_equal(t, tex), (seed, mode)
     for z0, nz in ((3, 5), (10, 1)):                     # odd slabs: a block repeats its last slice
         for mode in (7, 8, 11):
             g, _ = h.voxelize(N, mode, z0, nz)
             assert np.array_equal(g, want[1][z0:z0 + nz]), (seed, mode, z0, nz)
+
+
+def doubled_sphere():
+    """A sphere whose every triangle is there twice, the copy's vertex normals turned by 0.3 rad about z: every hit is an exact tie
+    of t between a triangle and its copy, both answer the normal test alike nearly everywhere, and their packed normals differ.  So
+    the winner of the tie decides nothing the grid shows and nearly everything the texel image shows.  Returns the vertices and
+    the two index orders (the originals first; the copies first)."""
+    vb, ib = meshes.uv_sphere(48, 24, 0.7, (0.05, -0.03, 0.02))
+    V = len(vb)
+    c, sn = np.float32(np.cos(0.3)), np.float32(np.sin(0.3))
+    turned = vb.copy()
+    turned[:, 3] = c * vb[:, 3] - sn * vb[:, 4]
+    turned[:, 4] = sn * vb[:, 3] + c * vb[:, 4]
+    vb2 = np.concatenate([vb, turned]).astype(np.float32)
+    return vb2, (np.concatenate([ib, ib + V]).astype(np.uint32), np.concatenate([ib + V, ib]).astype(np.uint32))
+
+
+def doubled_sphere_wanted(orc, N):
+    """The oracle's (grid, texel image) of the doubled sphere in both index orders, and the conditions that make a comparison with
+    them a test of the tie: the same grid either way, texel images that differ in more than half of the solid voxels."""
+    vb2, orders = doubled_sphere()
+    want = [orc.Scene(vb2, ib2).voxelize(N, texels=True) for ib2 in orders]            # (the oracle's BVH: brute force takes seconds here)
+    solid = int(want[0][0].sum())
+    assert solid > 0 and np.array_equal(want[0][0], want[1][0])
+    for g, t in want:
+        assert np.array_equal(t != 0, g != 0)
+    differ = int((want[0][1] != want[1][1]).sum())
+    assert differ > solid // 2, (N, solid, differ)
+    return vb2, orders, want
+
+
+def host_lists_modes_vs(h, N, want, what):
+    """The three bodies that keep the closest hit of a scan of the lists, on the host: 12 = the hit in registers (k_voxelize_queue<true>),
+    14 = the hit in the column (k_voxelize_listed<true>), 15 = t and the slot only (both kernels, texel image off: grid only)."""
+    grid, tex = want
+    for mode in (12, 14):
+        g, t, ovf = h.voxelize(N, mode=mode, stack=16, texels=True)
+        assert ovf == 0 and np.array_equal(g, grid), what + (mode,)
+        assert np.array_equal(t, tex), what + (mode, int((t != tex).sum()))
+    g, ovf = h.voxelize(N, mode=15)
+    assert ovf == 0 and np.array_equal(g, grid), what + (15,)
+
+
+@pytest.mark.parametrize("seed,n_tris", CASES)
+def test_fuzz_host_lists_bodies_vs_brute_force(orc, hostcheck, seed, n_tris):
+    """The lattice meshes (vertices, edges, coplanar duplicates: exact ties of t) through the three closest-hit bodies of the lists'
+    kernels, coarse and fine map, grid AND texel image against the oracle's brute force."""
+    rng = np.random.default_rng(1000 + seed)
+    for N in (16, 32):
+        vb, ib = lattice_mesh(rng, n_tris, N)
+        s = orc.Scene(vb, ib)
+        want = s.voxelize(N, algo=orc.ALGO_BRUTE, texels=True)
+        assert np.array_equal(want[1] != 0, want[0] != 0)
+        h = hostcheck(vb, ib, s.bound)
+        assert h.voxelize(N, mode=14)[1] == -1 and h.voxelize(N, mode=15)[1] == -1     # no lists yet: refused, as mode 12 is
+        for R in (16, 256):
+            h.lists(R)
+            host_lists_modes_vs(h, N, want, (seed, N, R))
+        assert h.voxelize(N, mode=15, texels=True)[2] == -1                             # mode 15 computes no texel image
+
+
+def test_needles_host_lists_bodies_vs_brute_force(orc, hostcheck):
+    """... and the needles aimed at the rays (test_needles_host_lists_vs_brute_force), texel image included."""
+    rng = np.random.default_rng(4242)
+    for n_tris, N in ((40, 16), (200, 16), (120, 32)):
+        vb, ib = needle_mesh(rng, n_tris, N)
+        s = orc.Scene(vb, ib)
+        want = s.voxelize(N, algo=orc.ALGO_BRUTE, texels=True)
+        assert want[0].sum() > 0 and np.array_equal(want[1] != 0, want[0] != 0)
+        h = hostcheck(vb, ib, s.bound)
+        for R in (16, 256):
+            h.lists(R)
+            host_lists_modes_vs(h, N, want, (n_tris, N, R))
+
+
+@pytest.mark.parametrize("N", (16, 32))
+def test_doubled_sphere_host_lists_bodies_break_ties_like_the_oracle(orc, hostcheck, N):
+    """Every hit an exact tie that only the texel image can see (doubled_sphere), both index orders."""
+    vb2, orders, want = doubled_sphere_wanted(orc, N)
+    for first, ib2 in enumerate(orders):
+        h = hostcheck(vb2, ib2, orc.Scene(vb2, ib2).bound)
+        h.lists(64)
+        host_lists_modes_vs(h, N, want[first], (N, first))
 
 
 @pytest.mark.gpu

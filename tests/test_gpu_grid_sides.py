@@ -291,13 +291,22 @@ def test_isosurface_of_the_grid_distance_field(dxv, writer, N):
 
 
 # ---- the launches -----------------------------------------------------------------------------------------------------------------------------
-def launch_all_modes(v, dxv, N, want, what, prepared=None):
+def launch_all_modes(v, dxv, N, want, want_image, what, prepared=None):
+    """every mode over a poisoned grid; the reference launch with the texel image on (it exists in that mode only), compared as well: the image
+    the frame held before is the other mesh's or another way's, at the same side"""
     v.Voxelize(N)                                                       # (the frame's grid exists from the first launch on)
     for mode in (dxv.MODE_REFERENCE, dxv.MODE_PARITY, dxv.MODE_SURFACE, dxv.MODE_REFERENCE_SURFACE):
         poison(v, POISON)                                               # every voxel is written in every launch
-        v.Voxelize(N, mode)
-        got = v.Grid()
-        assert got.shape == want[mode].shape and np.array_equal(got, want[mode]), f"{what}, mode {mode}: {int((got != want[mode]).sum())} voxels differ"
+        v.EnableTexels(mode == dxv.MODE_REFERENCE)
+        try:
+            v.Voxelize(N, mode)
+            got = v.Grid()
+            assert got.shape == want[mode].shape and np.array_equal(got, want[mode]), f"{what}, mode {mode}: {int((got != want[mode]).sum())} voxels differ"
+            if mode == dxv.MODE_REFERENCE:
+                image = v.Texels()
+                assert image.shape == want_image.shape and np.array_equal(image, want_image), f"{what}: {int((image != want_image).sum())} texels differ"
+        finally:
+            v.EnableTexels(False)
         if prepared is not None and mode == dxv.MODE_REFERENCE:
             assert v.stats()["plan_prepared"] == prepared, (what, v.stats()["list_entries"])
 
@@ -305,26 +314,27 @@ def launch_all_modes(v, dxv, N, want, what, prepared=None):
 @pytest.mark.parametrize("N", gs.SWEEP)
 def test_launches_in_every_mode_three_ways(dxv, orc, bunny, N):
     from dxrvoxelizer_amd import meshes
-    for name, (vb, ib) in (("bunny", bunny[:2]), ("cube", meshes.cube())):
-        scene = orc.Scene(vb, ib)
-        solid, surface = scene.voxelize(N, mode=orc.MODE_REFERENCE), sr.surface_of_mesh(vb, ib, N)
-        want = {dxv.MODE_REFERENCE: solid, dxv.MODE_PARITY: scene.voxelize(N, mode=orc.MODE_PARITY), dxv.MODE_SURFACE: surface,
-                dxv.MODE_REFERENCE_SURFACE: solid | surface}
-        assert solid.any(), (name, N)
-        assert surface.any() or name == "cube", (name, N)             # (the cube's faces lie on the grid's outer voxel faces: at some sides float32 puts them outside, and the rule's surface is empty)
-        v, w = dxv.Voxelizer(0), dxv.Voxelizer(0)
-        try:
+    v, w = dxv.Voxelizer(0), dxv.Voxelizer(0)                           # (one pair for both meshes: the cube's launches find the bunny's texel image in the frame)
+    try:
+        w.set_option("lists", 0)                                        # w: every ray walks the tree
+        for name, (vb, ib) in (("bunny", bunny[:2]), ("cube", meshes.cube())):
+            scene = orc.Scene(vb, ib)
+            (solid, image), surface = scene.voxelize(N, mode=orc.MODE_REFERENCE, texels=True), sr.surface_of_mesh(vb, ib, N)
+            want = {dxv.MODE_REFERENCE: solid, dxv.MODE_PARITY: scene.voxelize(N, mode=orc.MODE_PARITY), dxv.MODE_SURFACE: surface,
+                    dxv.MODE_REFERENCE_SURFACE: solid | surface}
+            assert solid.any(), (name, N)
+            assert np.array_equal(image != 0, solid != 0), (name, N)
+            assert surface.any() or name == "cube", (name, N)         # (the cube's faces lie on the grid's outer voxel faces: at some sides float32 puts them outside, and the rule's surface is empty)
             v.InitFromArrays(vb, ib, gridDim=N)                         # Init with the grid hint: the launches run the prepared queue ...
-            launch_all_modes(v, dxv, N, want, f"{name} {N} prepared", prepared=1 if name == "bunny" and N >= 34 else None)
+            launch_all_modes(v, dxv, N, want, image, f"{name} {N} prepared", prepared=1 if name == "bunny" and N >= 34 else None)
             v.InitFromArrays(vb, ib)                                    # ... without it they build their own ...
-            launch_all_modes(v, dxv, N, want, f"{name} {N} unprepared", prepared=0)
-            w.set_option("lists", 0)                                    # ... and without lists every ray walks the tree
-            w.InitFromArrays(vb, ib)
-            launch_all_modes(w, dxv, N, want, f"{name} {N} tree walk", prepared=0)
+            launch_all_modes(v, dxv, N, want, image, f"{name} {N} unprepared", prepared=0)
+            w.InitFromArrays(vb, ib)                                    # ... and without lists every ray walks the tree
+            launch_all_modes(w, dxv, N, want, image, f"{name} {N} tree walk", prepared=0)
             assert w.stats()["list_entries"] == 0
-        finally:
-            v.close()
-            w.close()
+    finally:
+        v.close()
+        w.close()
 
 
 # ---- the mesh distance field ---------------------------------------------------------------------------------------------------------------
