@@ -180,6 +180,7 @@ SYMBOLS = {
     "dxv_debug_queue_order": (C.c_int, [C.c_void_p, C.c_void_p]),
     "dxv_debug_division_check": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "dxv_debug_far_check": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
+    "dxv_debug_scan": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
     "dxv_trim": (C.c_int, [C.c_void_p]),
     "dxv_api_version": (C.c_int, []),
 }

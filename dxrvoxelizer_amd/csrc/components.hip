@@ -13,8 +13,7 @@
 //   k_comp_compress    behind the kernel boundary: parent[p] = the root of p = first(C).  Plain accesses: other lanes write roots into
 //                      entries this lane reads, and whichever of the two values it sees is an ancestor of p.
 //   k_comp_roots       one bit per voxel in linear order, parent[p] == p, and their count per 64 voxels
-//   k_comp_block_sums, k_comp_scan_sums, k_comp_add
-//                      the exclusive scan of those counts (the three-kernel form of octree.hip); the total, K, is what the host reads
+//   scan.hip           the exclusive scan of those counts (launch_scan_words, one count per word); the total, K, is what the host reads
 //   k_comp_number      labels[p] = rank(root) + 1, in place (a lane reads only its own entry of the buffer it writes)
 //   k_comp_stats_init, k_comp_first, k_comp_stats, k_comp_table
 //                      behind the host's read of K: `first` from the root bits; voxels, lo, hi and flags by integer atomics into 32-bit words
@@ -25,16 +24,11 @@
 //                      dxv_components_select: one kernel over the table (keep flags, the 64-bit maximum of voxels << 32 | ~number, three
 //                      counters), one pass over labels and grid.
 // Every loop ends because an index strictly falls (comp_find, comp_root, comp_union) or bits leave a word (the run loops).  No loop waits for
-// another workgroup, no kernel uses scratch memory; the scan's kernels use 128 bytes of LDS per workgroup, the others none.
+// another workgroup, no kernel here uses scratch memory or LDS.
 #include "dxv_device.h"
 #include "dxv_components.h"
 
 namespace dxv {
-
-constexpr uint32_t kCompScanBlock = 256;                                // threads of a scan workgroup ...
-constexpr uint32_t kCompScanItems = 4;                                  // ... and the consecutive counts each of them takes
-constexpr uint32_t kCompScanWords = kCompScanBlock * kCompScanItems;
-constexpr uint32_t kCompSumsBlock = 1024;                               // threads of the one workgroup that scans the block sums
 
 // parent[] as the merge kernel sees it
 struct CompAtomic {
@@ -104,77 +98,6 @@ __global__ __launch_bounds__(256) void k_comp_roots(const uint32_t* __restrict__
     const size_t p = (size_t)word * 64u + lane;
     const uint64_t roots = __ballot(p < total && parent[p] == (uint32_t)p);
     if (lane == 0u) { rootMask[word] = roots; bases[word] = comp_popc(roots); }
-}
-
-// exclusive scan of one count per thread over the workgroup (blockDim.x a multiple of 64, at most 1024); total: the workgroup's sum
-__device__ __forceinline__ unsigned long long comp_block_scan(unsigned long long mine, unsigned long long& total)
-{
-    __shared__ unsigned long long waveSums[16];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
-    unsigned long long inc = mine;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const unsigned long long v = __shfl_up(inc, d);
-        if (lane >= d) inc += v;
-    }
-    if (lane == 63u) waveSums[wave] = inc;
-    __syncthreads();
-    unsigned long long before = 0;
-    total = 0;
-    for (uint32_t k = 0; k < waves; ++k) {
-        if (k < wave) before += waveSums[k];
-        total += waveSums[k];
-    }
-    __syncthreads();                                                    // (the sums may be written again by the caller's next scan)
-    return before + inc - mine;
-}
-
-__global__ __launch_bounds__(kCompScanBlock) void k_comp_block_sums(const uint32_t* __restrict__ counts, uint32_t words, unsigned long long* __restrict__ sums)
-{
-    const size_t first = ((size_t)blockIdx.x * kCompScanBlock + threadIdx.x) * kCompScanItems;
-    unsigned long long mine = 0;
-    for (uint32_t k = 0; k < kCompScanItems; ++k)
-        if (first + k < words) mine += counts[first + k];
-    unsigned long long total;
-    (void)comp_block_scan(mine, total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-// sums[b] -> the sum of the blocks in front of block b; *total = the sum of all blocks
-__global__ __launch_bounds__(kCompSumsBlock) void k_comp_scan_sums(unsigned long long* __restrict__ sums, uint32_t blocks, unsigned long long* __restrict__ total)
-{
-    const uint32_t chunk = (blocks + kCompSumsBlock - 1u) / kCompSumsBlock;
-    const uint32_t first = threadIdx.x * chunk < blocks ? threadIdx.x * chunk : blocks, last = first + chunk < blocks ? first + chunk : blocks;
-    unsigned long long mine = 0;
-    for (uint32_t b = first; b < last; ++b) mine += sums[b];
-    unsigned long long all;
-    unsigned long long run = comp_block_scan(mine, all);
-    for (uint32_t b = first; b < last; ++b) {
-        const unsigned long long v = sums[b];
-        sums[b] = run;
-        run += v;
-    }
-    if (threadIdx.x == 0) *total = all;
-}
-
-// counts -> what stands in front of every 64 voxels, in place (32-bit: there are fewer roots than voxels)
-__global__ __launch_bounds__(kCompScanBlock) void k_comp_add(uint32_t* __restrict__ counts, uint32_t words, const unsigned long long* __restrict__ sums)
-{
-    const size_t first = ((size_t)blockIdx.x * kCompScanBlock + threadIdx.x) * kCompScanItems;
-    uint32_t c[kCompScanItems];
-    unsigned long long mine = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kCompScanItems; ++k) {
-        c[k] = first + k < words ? counts[first + k] : 0u;
-        mine += c[k];
-    }
-    unsigned long long total;
-    unsigned long long run = comp_block_scan(mine, total) + sums[blockIdx.x];
-#pragma unroll
-    for (uint32_t k = 0; k < kCompScanItems; ++k) {
-        if (first + k < words) counts[first + k] = (uint32_t)run;
-        run += c[k];
-    }
 }
 
 __device__ __forceinline__ uint32_t comp_label_of(uint32_t root, const uint64_t* __restrict__ rootMask, const uint32_t* __restrict__ bases)
@@ -334,30 +257,28 @@ __global__ __launch_bounds__(256) void k_comp_edit(uint8_t* grid, const uint32_t
     if (after != before) *at = after;
 }
 
-static size_t comp_align(size_t v) { return (v + 255u) & ~(size_t)255u; }
 static uint32_t comp_total(uint32_t N) { return N * N * N; }
 static uint32_t comp_linear_words(uint32_t N) { return (comp_total(N) + 63u) / 64u; }
-static uint32_t comp_scan_blocks(uint32_t N) { return (comp_linear_words(N) + kCompScanWords - 1u) / kCompScanWords; }
 
 // scratch of one build: the member mask, the root bits and the roots in front of every 64 voxels, the scan's block sums, the total
 size_t comp_scratch_bytes(uint32_t N)
 {
     const size_t words = comp_linear_words(N);
-    return comp_align(fill_mask_words(N) * sizeof(uint64_t)) + comp_align(words * sizeof(uint64_t)) + comp_align(words * sizeof(uint32_t)) +
-           comp_align((size_t)comp_scan_blocks(N) * sizeof(unsigned long long)) + comp_align(sizeof(unsigned long long));
+    return align256(fill_mask_words(N) * sizeof(uint64_t)) + align256(words * sizeof(uint64_t)) + align256(words * sizeof(uint32_t)) +
+           align256((size_t)scan_blocks(words) * sizeof(unsigned long long)) + align256(sizeof(unsigned long long));
 }
 void comp_scratch_layout(uint8_t* scratch, uint32_t N, CompParams& p)
 {
     const size_t words = comp_linear_words(N);
     p.N = N;
     p.mask = reinterpret_cast<uint64_t*>(scratch);
-    scratch += comp_align(fill_mask_words(N) * sizeof(uint64_t));
+    scratch += align256(fill_mask_words(N) * sizeof(uint64_t));
     p.rootMask = reinterpret_cast<uint64_t*>(scratch);
-    scratch += comp_align(words * sizeof(uint64_t));
+    scratch += align256(words * sizeof(uint64_t));
     p.bases = reinterpret_cast<uint32_t*>(scratch);
-    scratch += comp_align(words * sizeof(uint32_t));
+    scratch += align256(words * sizeof(uint32_t));
     p.sums = reinterpret_cast<unsigned long long*>(scratch);
-    scratch += comp_align((size_t)comp_scan_blocks(N) * sizeof(unsigned long long));
+    scratch += align256((size_t)scan_blocks(words) * sizeof(unsigned long long));
     p.total = reinterpret_cast<unsigned long long*>(scratch);
 }
 
@@ -380,16 +301,15 @@ hipError_t launch_comp_pack(const uint8_t* grid, uint32_t N, int of, uint64_t* m
 hipError_t launch_comp_label(const CompParams& p, hipStream_t s)
 {
     if (!comp_params_ok(p)) return hipErrorInvalidValue;
-    const uint32_t N = p.N, W = fill_row_words(N), total = comp_total(N), maskWords = N * N * W, words = comp_linear_words(N), blocks = comp_scan_blocks(N);
+    const uint32_t N = p.N, W = fill_row_words(N), total = comp_total(N), maskWords = N * N * W, words = comp_linear_words(N);
     const size_t maskBytes = (size_t)maskWords * 8u;
     k_comp_pack<<<(uint32_t)((maskBytes + 255u) / 256u), 256, 0, s>>>(p.grid, N, p.of, reinterpret_cast<uint8_t*>(p.mask));
     k_comp_init<<<(total / 4u + 255u) / 256u, 256, 0, s>>>(p.mask, N, p.labels, total);
     k_comp_merge<<<(maskWords + 255u) / 256u, 256, 0, s>>>(p.mask, N, p.connectivity, p.labels, maskWords);
     k_comp_compress<<<(uint32_t)(((size_t)total + 255u) / 256u), 256, 0, s>>>(p.labels, total);
     k_comp_roots<<<(words + 3u) / 4u, 256, 0, s>>>(p.labels, total, p.rootMask, p.bases, words);
-    k_comp_block_sums<<<blocks, kCompScanBlock, 0, s>>>(p.bases, words, p.sums);
-    k_comp_scan_sums<<<1, kCompSumsBlock, 0, s>>>(p.sums, blocks, p.total);
-    k_comp_add<<<blocks, kCompScanBlock, 0, s>>>(p.bases, words, p.sums);
+    const hipError_t e = launch_scan_words(p.bases, 1, words, p.sums, p.total, s);
+    if (e != hipSuccess) return e;
     k_comp_number<<<(total / 4u + 255u) / 256u, 256, 0, s>>>(p.labels, total, p.rootMask, p.bases);
     return hipGetLastError();
 }
@@ -406,7 +326,7 @@ hipError_t launch_comp_stats(const CompParams& p, uint32_t K, hipStream_t s)
     return hipGetLastError();
 }
 
-size_t comp_select_bytes(uint32_t K) { return comp_align(4u * sizeof(unsigned long long)) + comp_align(K); }
+size_t comp_select_bytes(uint32_t K) { return align256(4u * sizeof(unsigned long long)) + align256(K); }
 unsigned long long* comp_select_counters(uint8_t* work) { return reinterpret_cast<unsigned long long*>(work); }
 
 // the grid edited from its labels: `work` holds the four counters, then K keep flags
@@ -415,7 +335,7 @@ hipError_t launch_comp_select(uint8_t* grid, uint32_t N, int of, const uint32_t*
 {
     if (N < 2u || N > kCompMaxN || (N & 1u) || !grid || !labels || !work || (K && !table)) return hipErrorInvalidValue;
     unsigned long long* counters = comp_select_counters(work);
-    uint8_t* keep = work + comp_align(4u * sizeof(unsigned long long));
+    uint8_t* keep = work + align256(4u * sizeof(unsigned long long));
     const hipError_t e = hipMemsetAsync(counters, 0, 4u * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
     if (!K) return hipSuccess;

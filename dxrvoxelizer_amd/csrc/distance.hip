@@ -44,7 +44,7 @@ __global__ __launch_bounds__(64) void k_dist_columns(const TIn* __restrict__ in,
     col.run();
 }
 
-size_t distance_rows_bytes(uint32_t N) { return ((size_t)N * N * N * sizeof(int16_t) + 255) & ~size_t(255); }
+size_t distance_rows_bytes(uint32_t N) { return align256((size_t)N * N * N * sizeof(int16_t)); }
 size_t distance_scratch_bytes(uint32_t N) { return distance_rows_bytes(N) + (size_t)N * N * N * sizeof(int32_t); }
 
 hipError_t launch_distance(const uint8_t* grid, uint32_t N, int format, void* field, uint8_t* scratch, hipStream_t s)

@@ -27,7 +27,6 @@ constexpr uint32_t kRedoCap = 1u << 21;   // (diagnostic build: the list doubles
 constexpr uint32_t kRedoCap = 1u << 16;   // rays per launch the redo pass takes before the column is grown instead
 #endif
 constexpr uint32_t kOctStatusWord = 3;    // the word of a frame's status block an octree expansion raises (words 0 .. 2 are the launch's)
-inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 }
 
 using namespace dxv;

@@ -1,5 +1,6 @@
 // dxv_debug.hip -- test hooks of the C-ABI: the exhaustive device checks of the lists' superset claim, of the triangle classes
-// and of the work queue -- each checker kernel in front of the one entry that calls it -- and the download of internal arrays.
+// and of the work queue -- each checker kernel in front of the one entry that calls it --, the grid operators' scan on the caller's numbers
+// and the download of internal arrays.
 // Not product paths.
 #include "dxv_ctx.h"
 #include "dxv_brick.h"
@@ -467,6 +468,34 @@ extern "C" int dxv_debug_queue_order(dxv_ctx* c, uint64_t out[4])
     if (e == hipSuccess) e = hipMemcpyAsync(out, dOut.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, fs);
     if (e == hipSuccess) e = hipStreamSynchronize(fs);
     if (e != hipSuccess) return fail(c, "dxv_debug_queue_order failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+// scan.hip's two entry points on the caller's numbers, in place: up, one launch_scan_*, down.  What the launchers refuse -- a lane count that is
+// neither 1 nor 2, nothing to scan, no buffer (host == NULL is handed on as it is) -- comes back as their error, and `host` is not written.
+// The hook itself admits up to 4 lanes, so that a lane count of 3 reaches the launchers and is refused THERE.
+extern "C" int dxv_debug_scan(dxv_ctx* c, int what, uint32_t lanes, void* host, size_t items, uint64_t totals[2])
+{
+    if (!c || !totals) return 1;
+    if (what != 0 && what != 1) return fail(c, "dxv_debug_scan: unknown selector %d", what);
+    if (lanes > 4u || items > (size_t(1) << 26)) return fail(c, "dxv_debug_scan: at most 4 lanes and 2^26 items");      // (a test hook's allocations stay small)
+    DXV_HIP(c, hipSetDevice(c->device));
+    const hipStream_t s = c->stream;
+    const size_t n = items * lanes, blocks = what == 0 ? scan_blocks(items) : 0;      // (block sums: the scratch of launch_scan_words alone)
+    const size_t bytes = what == 0 ? n * sizeof(uint32_t) : (n + lanes + 1u) * sizeof(unsigned long long);    // what = 1: sums, totals, a guard word
+    DevBuf<uint8_t> d;
+    DevBuf<unsigned long long> work;                                    // what = 0: the block sums, then the totals
+    if (host) DXV_HIP(c, d.reserve(bytes + 1u, align256(bytes + 1u)));  // (+ 1: items = 0 still gets a buffer, so that the launcher and not a null pointer refuses it)
+    if (what == 0) DXV_HIP(c, work.reserve(lanes * blocks + 2u, align256((lanes * blocks + 2u) * sizeof(unsigned long long))));
+    hipError_t e = d.p && bytes ? hipMemcpyAsync(d.p, host, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+    unsigned long long* sums = reinterpret_cast<unsigned long long*>(d.p);
+    unsigned long long* dTotals = what == 0 ? work.p + lanes * blocks : sums ? sums + n : nullptr;
+    if (e == hipSuccess) e = what == 0 ? launch_scan_words(reinterpret_cast<uint32_t*>(d.p), lanes, items, work.p, dTotals, s) : launch_scan_sums(sums, lanes, (uint32_t)items, dTotals, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(totals, dTotals, lanes * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(host, d.p, bytes, hipMemcpyDeviceToHost, s);
+    const hipError_t drained = hipStreamSynchronize(s);                 // (the buffers are freed when this returns)
+    if (e == hipSuccess) e = drained;
+    if (e != hipSuccess) return fail(c, "dxv_debug_scan failed: %s", hipGetErrorString(e));
     return 0;
 }
 

@@ -7,6 +7,9 @@
 
 namespace dxv {
 
+// device allocations and the blocks inside one are laid out in whole 256-byte lines
+inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
+
 // radix_sort.hip
 // plan: the diagnostic override (option sortbits) as ONE caller snapshot of radix_sort_plan(), -1: read it now
 hipError_t radix_sort_keys_bits(uint64_t* keys, uint64_t* tmp, uint32_t n, uint32_t* hist, int loBit, int numBits, uint64_t** result,
@@ -228,6 +231,14 @@ struct MeshDistanceParams {
     float cullAbs;          // md_cull_abs(root box)
 };
 hipError_t launch_mesh_distance(const Node* nodes, const TriPos* triPos, uint32_t T, const MeshDistanceParams& p, bool walk, hipStream_t s);
+
+// scan.hip -- the exclusive scan of the grid operators (dxv_scan.h has the workgroup's routine).  launch_scan_words: `words` words of C (1 or 2)
+// interleaved 32-bit counts each become what stands in front of them, in place; sums: C * scan_blocks(words) 64-bit words of scratch; totals: C
+// 64-bit words.  launch_scan_sums: the same for `blocks` entries of C 64-bit sums, by one workgroup; totals may stand right behind them.  Both
+// refuse a null pointer, a C that is neither 1 nor 2, and nothing to scan.
+uint32_t scan_blocks(size_t words);
+hipError_t launch_scan_words(uint32_t* counts, uint32_t C, size_t words, unsigned long long* sums, unsigned long long* totals, hipStream_t s);
+hipError_t launch_scan_sums(unsigned long long* sums, uint32_t C, uint32_t blocks, unsigned long long* totals, hipStream_t s);
 
 // isosurface.hip -- a triangle mesh from a float32 field of a whole N^3 grid by naive Surface Nets (dxv_isosurface.h): count + scan, ONE
 // read of the two totals by the caller, emit.  scratch: iso_scratch_bytes(N) -- one bit per lattice cell, two counts per 64 cells, the

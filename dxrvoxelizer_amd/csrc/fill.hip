@@ -12,7 +12,7 @@
 
 namespace dxv {
 
-static size_t fill_mask_bytes(uint32_t N) { return (fill_mask_words(N) * sizeof(uint64_t) + 255) & ~size_t(255); }
+static size_t fill_mask_bytes(uint32_t N) { return align256(fill_mask_words(N) * sizeof(uint64_t)); }
 size_t fill_scratch_bytes(uint32_t N) { return 2 * fill_mask_bytes(N) + sizeof(uint32_t) * kFillMaxRounds; }
 uint32_t* fill_control(uint8_t* scratch, uint32_t N) { return reinterpret_cast<uint32_t*>(scratch + 2 * fill_mask_bytes(N)); }
 

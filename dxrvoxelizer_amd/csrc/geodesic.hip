@@ -22,21 +22,20 @@ namespace dxv {
 constexpr uint32_t kGeoRoundBlocks = 8192;        // workgroups (of one wave) a round is launched with at the most, whatever its queue holds
 constexpr uint32_t kGeoTallyBlocks = 1024;        // ... the tally, of four waves
 
-static size_t geo_align(size_t v) { return (v + 255u) & ~(size_t)255u; }
 static uint32_t geo_tiles(uint32_t N) { return geo_tiles_side(N) * geo_tiles_side(N) * geo_tiles_side(N); }
 
 struct GeoLayout { GeoControl* ctl; uint8_t* flags[2]; uint32_t* queue; };
 static GeoLayout geo_layout(uint8_t* scratch, uint32_t N)
 {
-    const size_t flags = geo_align(geo_tiles(N));
+    const size_t flags = align256(geo_tiles(N));
     GeoLayout l;
     l.ctl = reinterpret_cast<GeoControl*>(scratch);
-    l.flags[0] = scratch + geo_align(sizeof(GeoControl));
+    l.flags[0] = scratch + align256(sizeof(GeoControl));
     l.flags[1] = l.flags[0] + flags;
     l.queue = reinterpret_cast<uint32_t*>(l.flags[1] + flags);
     return l;
 }
-size_t geodesic_scratch_bytes(uint32_t N) { return geo_align(sizeof(GeoControl)) + 2u * geo_align(geo_tiles(N)) + geo_align((size_t)geo_tiles(N) * sizeof(uint32_t)); }
+size_t geodesic_scratch_bytes(uint32_t N) { return align256(sizeof(GeoControl)) + 2u * align256(geo_tiles(N)) + align256((size_t)geo_tiles(N) * sizeof(uint32_t)); }
 
 // one thread per voxel
 __global__ __launch_bounds__(256) void k_geo_init(const uint8_t* __restrict__ grid, uint32_t N, int of, int seedsKind, const uint8_t* __restrict__ seedMask, uint32_t* __restrict__ map,
@@ -183,7 +182,7 @@ hipError_t launch_geodesic_init(const uint8_t* grid, uint32_t N, int of, int see
         return hipErrorInvalidValue;
     const GeoLayout l = geo_layout(scratch, N);
     const size_t voxels = (size_t)N * N * N;
-    const hipError_t e = hipMemsetAsync(l.flags[0], 0, 2u * geo_align(geo_tiles(N)), s);
+    const hipError_t e = hipMemsetAsync(l.flags[0], 0, 2u * align256(geo_tiles(N)), s);
     if (e != hipSuccess) return e;
     k_geo_init<<<(uint32_t)((voxels + 255u) / 256u), 256, 0, s>>>(grid, N, of, seedsKind, seedsKind == GEO_SEEDS_MASK ? static_cast<const uint8_t*>(seeds) : nullptr, map, l.flags[0]);
     if (seedsKind == GEO_SEEDS_LIST && seedCount) k_geo_seed_list<<<(seedCount + 255u) / 256u, 256, 0, s>>>(static_cast<const uint32_t*>(seeds), seedCount, N, map, l.flags[0]);

@@ -18,9 +18,8 @@
 
 namespace dxv {
 
-static size_t morph_align(size_t v) { return (v + 255u) & ~(size_t)255u; }
-static size_t morph_mask_bytes(uint32_t N) { return morph_align(fill_mask_words(N) * sizeof(uint64_t)); }
-static size_t morph_loose_bytes(uint32_t N) { return morph_align((fill_mask_words(N) * 8u + 63u) / 64u * sizeof(uint64_t)); }
+static size_t morph_mask_bytes(uint32_t N) { return align256(fill_mask_words(N) * sizeof(uint64_t)); }
+static size_t morph_loose_bytes(uint32_t N) { return align256((fill_mask_words(N) * 8u + 63u) / 64u * sizeof(uint64_t)); }
 
 // one thread per byte of a mask row (W * 8 of them, the ones behind the row's end are 0); every lane stays for the ballot
 __global__ __launch_bounds__(256) void k_morph_pack(const uint8_t* __restrict__ grid, uint32_t N, int complement, uint8_t* __restrict__ mask, uint64_t* __restrict__ loose)
@@ -154,7 +153,7 @@ void launch_morph_write(const uint8_t* was, const uint8_t* now, const uint64_t* 
 constexpr size_t kMorphCounterBytes = 256;
 size_t morph_scratch_bytes(uint32_t N, int op, uint32_t r2, int form)
 {
-    if (form == MORPH_FORM_FIELD) return kMorphCounterBytes + morph_align((size_t)N * N * N * sizeof(int32_t)) + distance_scratch_bytes(N);
+    if (form == MORPH_FORM_FIELD) return kMorphCounterBytes + align256((size_t)N * N * N * sizeof(int32_t)) + distance_scratch_bytes(N);
     return kMorphCounterBytes + (1u + morph_halves(op)) * morph_mask_bytes(N) + morph_loose_bytes(N) + (size_t)morph_isqrt(r2) * morph_mask_bytes(N);
 }
 unsigned long long* morph_counters(uint8_t* scratch) { return reinterpret_cast<unsigned long long*>(scratch); }
@@ -162,7 +161,7 @@ unsigned long long* morph_counters(uint8_t* scratch) { return reinterpret_cast<u
 static hipError_t launch_morph_field(uint8_t* grid, uint32_t N, int op, uint32_t r2, uint8_t* scratch, hipStream_t s)
 {
     int32_t* field = reinterpret_cast<int32_t*>(scratch + kMorphCounterBytes);
-    uint8_t* passes = scratch + kMorphCounterBytes + morph_align((size_t)N * N * N * sizeof(int32_t));
+    uint8_t* passes = scratch + kMorphCounterBytes + align256((size_t)N * N * N * sizeof(int32_t));
     const uint32_t groups = (uint32_t)((size_t)N * N * N / 8u);
     for (uint32_t half = 0; half < morph_halves(op); ++half) {
         const hipError_t e = launch_distance(grid, N, 0, field, passes, s);

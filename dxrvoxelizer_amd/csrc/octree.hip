@@ -8,25 +8,20 @@
 //                    read once, by this kernel.  (L < 3: the cube is part of one brick; the cells of a level are the first of that brick's.)
 //   k_oct_level      one per level above L - 3, from L - 4 up to the root: a thread per cell, eight consecutive child words -> its word.
 //   k_oct_flags      the "has a node" bits of levels 0 .. L - 2 (the root always has one), a wave per 64 cells.
-//   k_oct_block_sums, k_oct_scan_sums, k_oct_add, k_oct_level_first
-//                    the exclusive scan of the words' popcounts -- the three-kernel form of isosurface.hip with one count --, then the scan
-//                    value at the start of every level and the total: level_first, the L + 1 words the host reads.
+//   scan.hip, k_oct_level_first
+//                    the exclusive scan of the words' popcounts (launch_scan_words, one count per word), then the scan value at the start of
+//                    every level and the total: level_first, the L + 1 words the host reads.
 //   k_oct_emit       a wave per 64 cells: a flagged cell's node goes to its word's base + the set bits below its own; word0 is the scan value
 //                    at the dense position of its child 0.
 //   k_oct_expand     one wave per 8^3 brick of the GRID: a wave-uniform checked descent from the root to the brick's level-(L - 3) cell, with
 //                    early out for empty and full, then every lane finishes the last three levels for its x-run and stores its 8 voxels, 0
 //                    or 1 each.  Every index is compared with the node count before it is followed (oct_child); a tree that cannot be
 //                    followed gives empty voxels and sets the frame's status word.
-// No atomics, no workgroup waits for another, no kernel uses scratch memory; the scan's kernels use 128 bytes of LDS per workgroup.
+// No atomics, no workgroup waits for another, no kernel here uses scratch memory or LDS.
 #include "dxv_device.h"
 #include "dxv_octree.h"
 
 namespace dxv {
-
-constexpr uint32_t kOctScanBlock = 256;                                 // threads of a scan workgroup ...
-constexpr uint32_t kOctScanItems = 4;                                   // ... and the consecutive words each of them takes
-constexpr uint32_t kOctScanWords = kOctScanBlock * kOctScanItems;
-constexpr uint32_t kOctSumsBlock = 1024;                                // threads of the one workgroup that scans the block sums
 
 // the lane's x-run of brick (bx, by, bz): bit k set iff voxel (8 bx + k, 8 by + y, 8 bz + z) lies in the grid and its byte is non-zero
 __device__ __forceinline__ uint32_t oct_load_run(const uint8_t* __restrict__ grid, uint32_t N, uint32_t bx, uint32_t by, uint32_t bz, uint32_t lane)
@@ -103,77 +98,6 @@ __global__ __launch_bounds__(256) void k_oct_flags(OctParams p, size_t words)
     if (lane == 0u) { p.masks[word] = nodes; p.bases[word] = oct_popc(nodes); }
 }
 
-// exclusive scan of one count per thread over the workgroup (blockDim.x a multiple of 64, at most 1024); total: the workgroup's sum
-__device__ __forceinline__ unsigned long long oct_block_scan(unsigned long long mine, unsigned long long& total)
-{
-    __shared__ unsigned long long waveSums[16];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
-    unsigned long long inc = mine;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const unsigned long long v = __shfl_up(inc, d);
-        if (lane >= d) inc += v;
-    }
-    if (lane == 63u) waveSums[wave] = inc;
-    __syncthreads();
-    unsigned long long before = 0;
-    total = 0;
-    for (uint32_t k = 0; k < waves; ++k) {
-        if (k < wave) before += waveSums[k];
-        total += waveSums[k];
-    }
-    __syncthreads();                                                    // (the sums may be written again by the caller's next scan)
-    return before + inc - mine;
-}
-
-__global__ __launch_bounds__(kOctScanBlock) void k_oct_block_sums(const uint32_t* __restrict__ counts, size_t words, unsigned long long* __restrict__ sums)
-{
-    const size_t first = ((size_t)blockIdx.x * kOctScanBlock + threadIdx.x) * kOctScanItems;
-    unsigned long long mine = 0;
-    for (uint32_t k = 0; k < kOctScanItems; ++k)
-        if (first + k < words) mine += counts[first + k];
-    unsigned long long total;
-    (void)oct_block_scan(mine, total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-// sums[b] -> the sum of the blocks in front of block b; *total = the sum of all blocks
-__global__ __launch_bounds__(kOctSumsBlock) void k_oct_scan_sums(unsigned long long* __restrict__ sums, uint32_t blocks, unsigned long long* __restrict__ total)
-{
-    const uint32_t chunk = (blocks + kOctSumsBlock - 1u) / kOctSumsBlock;
-    const uint32_t first = threadIdx.x * chunk < blocks ? threadIdx.x * chunk : blocks, last = first + chunk < blocks ? first + chunk : blocks;
-    unsigned long long mine = 0;
-    for (uint32_t b = first; b < last; ++b) mine += sums[b];
-    unsigned long long all;
-    unsigned long long run = oct_block_scan(mine, all);
-    for (uint32_t b = first; b < last; ++b) {
-        const unsigned long long v = sums[b];
-        sums[b] = run;
-        run += v;
-    }
-    if (threadIdx.x == 0) *total = all;
-}
-
-// counts -> what stands in front of every word, in place (32-bit: a tree whose total passes the cap is refused before anything reads them)
-__global__ __launch_bounds__(kOctScanBlock) void k_oct_add(uint32_t* __restrict__ counts, size_t words, const unsigned long long* __restrict__ sums)
-{
-    const size_t first = ((size_t)blockIdx.x * kOctScanBlock + threadIdx.x) * kOctScanItems;
-    uint32_t c[kOctScanItems];
-    unsigned long long mine = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kOctScanItems; ++k) {
-        c[k] = first + k < words ? counts[first + k] : 0u;
-        mine += c[k];
-    }
-    unsigned long long total;
-    unsigned long long run = oct_block_scan(mine, total) + sums[blockIdx.x];
-#pragma unroll
-    for (uint32_t k = 0; k < kOctScanItems; ++k) {
-        if (first + k < words) counts[first + k] = (uint32_t)run;
-        run += c[k];
-    }
-}
-
 // level_first[l] = the nodes in front of level l (every level starts a word); level_first[L], the total, is in place
 __global__ __launch_bounds__(64) void k_oct_level_first(OctParams p)
 {
@@ -237,16 +161,14 @@ __global__ __launch_bounds__(256) void k_oct_expand(uint8_t* __restrict__ grid, 
 }
 
 static size_t oct_words(uint32_t L) { return oct_level_offset(L) >> 6; }
-static uint32_t oct_scan_blocks(uint32_t L) { return (uint32_t)((oct_words(L) + kOctScanWords - 1u) / kOctScanWords); }
-static size_t oct_align(size_t v) { return (v + 255u) & ~(size_t)255u; }
 
 // scratch of one build: the dense cell words, their "has a node" bits, the words' counts / bases, the scan's block sums, level_first
 size_t oct_scratch_bytes(uint32_t N)
 {
     const uint32_t L = oct_levels(N);
     const size_t words = oct_words(L);
-    return oct_align(words * 64u * sizeof(uint16_t)) + oct_align(words * sizeof(uint64_t)) + oct_align(words * sizeof(uint32_t)) +
-           oct_align((size_t)oct_scan_blocks(L) * sizeof(unsigned long long)) + oct_align((kOctMaxLevels + 1u) * sizeof(unsigned long long));
+    return align256(words * 64u * sizeof(uint16_t)) + align256(words * sizeof(uint64_t)) + align256(words * sizeof(uint32_t)) +
+           align256((size_t)scan_blocks(words) * sizeof(unsigned long long)) + align256((kOctMaxLevels + 1u) * sizeof(unsigned long long));
 }
 void oct_scratch_layout(uint8_t* scratch, uint32_t N, OctParams& p)
 {
@@ -254,13 +176,13 @@ void oct_scratch_layout(uint8_t* scratch, uint32_t N, OctParams& p)
     const size_t words = oct_words(L);
     p.N = N; p.L = L;
     p.cells = reinterpret_cast<uint16_t*>(scratch);
-    scratch += oct_align(words * 64u * sizeof(uint16_t));
+    scratch += align256(words * 64u * sizeof(uint16_t));
     p.masks = reinterpret_cast<uint64_t*>(scratch);
-    scratch += oct_align(words * sizeof(uint64_t));
+    scratch += align256(words * sizeof(uint64_t));
     p.bases = reinterpret_cast<uint32_t*>(scratch);
-    scratch += oct_align(words * sizeof(uint32_t));
+    scratch += align256(words * sizeof(uint32_t));
     p.sums = reinterpret_cast<unsigned long long*>(scratch);
-    scratch += oct_align((size_t)oct_scan_blocks(L) * sizeof(unsigned long long));
+    scratch += align256((size_t)scan_blocks(words) * sizeof(unsigned long long));
     p.levelFirst = reinterpret_cast<unsigned long long*>(scratch);
 }
 
@@ -272,16 +194,14 @@ hipError_t launch_oct_count(const OctParams& p, hipStream_t s)
     if (!oct_params_ok(p)) return hipErrorInvalidValue;
     const uint32_t L = p.L, bricks = L > 3u ? 1u << 3u * (L - 3u) : 1u;
     const size_t words = oct_words(L), upper = oct_level_offset(L - 1u) >> 6;
-    const uint32_t blocks = oct_scan_blocks(L);
     k_oct_reduce<<<(bricks + 3u) / 4u, 256, 0, s>>>(p, bricks);
     for (uint32_t l = L; l-- > 3u;) {                                   // levels L - 4 .. 0
         const uint32_t level = l - 3u;
         k_oct_level<<<(uint32_t)((oct_level_cells(level) + 255u) / 256u), 256, 0, s>>>(p.cells, level);
     }
     if (upper) k_oct_flags<<<(uint32_t)((upper + 3u) / 4u), 256, 0, s>>>(p, upper);
-    k_oct_block_sums<<<blocks, kOctScanBlock, 0, s>>>(p.bases, words, p.sums);
-    k_oct_scan_sums<<<1, kOctSumsBlock, 0, s>>>(p.sums, blocks, p.levelFirst + L);
-    k_oct_add<<<blocks, kOctScanBlock, 0, s>>>(p.bases, words, p.sums);
+    const hipError_t e = launch_scan_words(p.bases, 1, words, p.sums, p.levelFirst + L, s);
+    if (e != hipSuccess) return e;
     k_oct_level_first<<<1, 64, 0, s>>>(p);
     return hipGetLastError();
 }

@@ -7,21 +7,22 @@
 //   search     k_part_search: one wave per 4^3 brick, a lane per voxel of it as a centre: PartSearch, the argmax of the keys over the closed ball
 //              pruned by the two mip levels (option partprune).  The lanes of a wave stand on neighbouring centres of radii a few units apart, so
 //              they walk the same cells in the same order and their loads fall into the same lines.  parent goes where F was.
-//   roots      k_part_walk: every member follows its parents to its root, reading parent, writing rootOf.  k_part_count, k_part_scan,
-//              k_part_number: the roots -- rootOf[v] == v -- (and the interface faces, told by rootOf alone) per block of 1024 voxels, the
-//              exclusive scan of the blocks, the roots' numbers by ascending index (where parent was)
+//   roots      k_part_walk: every member follows its parents to its root, reading parent, writing rootOf.  k_part_count, scan.hip's
+//              launch_scan_sums, k_part_number: the roots -- rootOf[v] == v -- (and the interface faces, told by rootOf alone) per block of 1024
+//              voxels, two counts in one word, the second above bit 16 (a thread's four items count at most 4 and 12, a block's 1024 and 3072);
+//              the exclusive scan of the blocks; the roots' numbers by ascending index (where parent was)
 //   regions    k_part_labels; k_part_stats: voxels, box and border bit by 32-bit atomics per region, once per wave where the wave's voxels are of
 //              one region; k_part_table: the records
-//   throats    k_part_emit_faces: one word (a, b) per interface face, by the same scan; radix_sort.hip; k_part_count_heads, k_part_scan: the
+//   throats    k_part_emit_faces: one word (a, b) per interface face, by the same scan; radix_sort.hip; k_part_count_heads, launch_scan_sums: the
 //              run heads = the unique pairs, T; then k_part_emit_pairs, k_part_face_atomics: every face finds its pair by binary search --
 //              faces += 1, (neck, -voxel) = max as ONE 64-bit word --, k_part_throats: the records and the regions' throat counts
 // No kernel waits for another workgroup, every loop is bounded, nothing goes to scratch memory.
 #include "dxv_device.h"
 #include "dxv_partition.h"
+#include "dxv_scan.h"
 
 namespace dxv {
 
-static size_t part_align(size_t v) { return (v + 255u) & ~(size_t)255u; }
 static uint32_t part_blocks(size_t items) { return (uint32_t)((items + kPartBlock - 1u) / kPartBlock); }
 
 __global__ __launch_bounds__(256) void k_part_keys(const int32_t* __restrict__ F, uint32_t groups, int of, uint32_t cap, uint64_t* __restrict__ keys)
@@ -93,30 +94,6 @@ __global__ __launch_bounds__(256) void k_part_walk(const uint32_t* __restrict__ 
     rootOf[v] = parent[v] == kPartNone ? kPartNone : part_root(parent, v, voxels);
 }
 
-// two counts in one word, the second above bit 16 (a thread's four items count at most 4 and 12, a block's 1024 and 3072).  Exclusive scan
-// over the 256 threads; total: the block's sum
-__device__ __forceinline__ uint32_t part_block_scan(uint32_t mine, uint32_t& total)
-{
-    __shared__ uint32_t waveSums[4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = mine;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint32_t v = (uint32_t)__shfl_up((int)inc, d);
-        if (lane >= d) inc += v;
-    }
-    if (lane == 63u) waveSums[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0;
-    total = 0;
-    for (uint32_t k = 0; k < 4u; ++k) {
-        if (k < wave) before += waveSums[k];
-        total += waveSums[k];
-    }
-    __syncthreads();
-    return before + inc - mine;
-}
-
 // thread t of block b: voxels 1024 b + 4 t .. + 3 (N^3 is a multiple of 8: the four are all inside or all outside; a row may end after two of
 // them, so the coordinates step).  The roots among them, and under kFaces their interface faces above bit 16
 template <bool kFaces> __device__ __forceinline__ uint32_t part_count4(const uint32_t* __restrict__ id, uint32_t off, uint32_t N, uint32_t first, uint32_t voxels)
@@ -139,38 +116,8 @@ template <bool kFaces> __device__ __forceinline__ uint32_t part_count4(const uin
 template <bool kFaces> __global__ __launch_bounds__(256) void k_part_count(const uint32_t* __restrict__ rootOf, uint32_t N, uint32_t voxels, unsigned long long* __restrict__ sums)
 {
     uint32_t total;
-    (void)part_block_scan(part_count4<kFaces>(rootOf, kPartNone, N, blockIdx.x * kPartBlock + threadIdx.x * 4u, voxels), total);
+    (void)block_scan_exclusive<uint32_t, 4>(part_count4<kFaces>(rootOf, kPartNone, N, blockIdx.x * kPartBlock + threadIdx.x * 4u, voxels), total);
     if (threadIdx.x == 0) { sums[2 * (size_t)blockIdx.x] = total & 0xffffu; sums[2 * (size_t)blockIdx.x + 1] = total >> 16; }
-}
-
-// sums[2 b], sums[2 b + 1] -> the two counts of the blocks in front of block b; sums[2 blocks], sums[2 blocks + 1] = the totals
-__global__ __launch_bounds__(1024) void k_part_scan(unsigned long long* __restrict__ sums, uint32_t blocks)
-{
-    __shared__ unsigned long long waveSums[2][16];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t chunk = (blocks + 1023u) / 1024u;
-    const uint32_t first = threadIdx.x * chunk < blocks ? threadIdx.x * chunk : blocks, last = first + chunk < blocks ? first + chunk : blocks;
-    unsigned long long c = 0, i = 0;
-    for (uint32_t b = first; b < last; ++b) { c += sums[2 * (size_t)b]; i += sums[2 * (size_t)b + 1]; }
-    unsigned long long incC = c, incI = i;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const unsigned long long vc = __shfl_up(incC, d), vi = __shfl_up(incI, d);
-        if (lane >= d) { incC += vc; incI += vi; }
-    }
-    if (lane == 63u) { waveSums[0][wave] = incC; waveSums[1][wave] = incI; }
-    __syncthreads();
-    unsigned long long runC = incC - c, runI = incI - i, allC = 0, allI = 0;
-    for (uint32_t k = 0; k < 16u; ++k) {
-        if (k < wave) { runC += waveSums[0][k]; runI += waveSums[1][k]; }
-        allC += waveSums[0][k]; allI += waveSums[1][k];
-    }
-    for (uint32_t b = first; b < last; ++b) {
-        const unsigned long long vc = sums[2 * (size_t)b], vi = sums[2 * (size_t)b + 1];
-        sums[2 * (size_t)b] = runC; sums[2 * (size_t)b + 1] = runI;
-        runC += vc; runI += vi;
-    }
-    if (threadIdx.x == 0) { sums[2 * (size_t)blocks] = allC; sums[2 * (size_t)blocks + 1] = allI; }
 }
 
 // the roots' numbers, 1 .. K by ascending index, at the roots' own voxels (the other words of `number` are never read)
@@ -180,7 +127,7 @@ __global__ __launch_bounds__(256) void k_part_number(const uint32_t* __restrict_
     const uint32_t first = blockIdx.x * kPartBlock + threadIdx.x * 4u;
     const uint32_t mine = part_count4<false>(rootOf, kPartNone, N, first, voxels);
     uint32_t total;
-    uint32_t run = part_block_scan(mine, total) + (uint32_t)sums[2 * (size_t)blockIdx.x];
+    uint32_t run = block_scan_exclusive<uint32_t, 4>(mine, total) + (uint32_t)sums[2 * (size_t)blockIdx.x];
     if (!mine) return;
 #pragma unroll
     for (uint32_t k = 0; k < 4u; ++k)
@@ -262,7 +209,7 @@ __global__ __launch_bounds__(256) void k_part_emit_faces(const uint32_t* __restr
         }
     }
     uint32_t blockTotal;
-    unsigned long long at = sums[2 * (size_t)blockIdx.x + 1] + part_block_scan(mine, blockTotal);
+    unsigned long long at = sums[2 * (size_t)blockIdx.x + 1] + block_scan_exclusive<uint32_t, 4>(mine, blockTotal);
     if (!mine) return;
 #pragma unroll
     for (uint32_t k = 0; k < 4u; ++k)
@@ -288,7 +235,7 @@ __device__ __forceinline__ uint32_t part_heads4(const uint64_t* __restrict__ sor
 __global__ __launch_bounds__(256) void k_part_count_heads(const uint64_t* __restrict__ sorted, uint32_t n, unsigned long long* __restrict__ sums)
 {
     uint32_t total;
-    (void)part_block_scan((uint32_t)__popc(part_heads4(sorted, n, blockIdx.x * kPartBlock + threadIdx.x * 4u)), total);
+    (void)block_scan_exclusive<uint32_t, 4>((uint32_t)__popc(part_heads4(sorted, n, blockIdx.x * kPartBlock + threadIdx.x * 4u)), total);
     if (threadIdx.x == 0) { sums[2 * (size_t)blockIdx.x] = total; sums[2 * (size_t)blockIdx.x + 1] = 0; }
 }
 __global__ __launch_bounds__(256) void k_part_emit_pairs(const uint64_t* __restrict__ sorted, uint32_t n, const unsigned long long* __restrict__ sums, uint32_t T,
@@ -297,7 +244,7 @@ __global__ __launch_bounds__(256) void k_part_emit_pairs(const uint64_t* __restr
     const uint32_t first = blockIdx.x * kPartBlock + threadIdx.x * 4u;
     const uint32_t heads = part_heads4(sorted, n, first);
     uint32_t total;
-    uint32_t at = (uint32_t)sums[2 * (size_t)blockIdx.x] + part_block_scan((uint32_t)__popc(heads), total);
+    uint32_t at = (uint32_t)sums[2 * (size_t)blockIdx.x] + block_scan_exclusive<uint32_t, 4>((uint32_t)__popc(heads), total);
     if (!heads) return;
 #pragma unroll
     for (uint32_t k = 0; k < 4u; ++k)
@@ -343,23 +290,23 @@ __global__ __launch_bounds__(256) void k_part_throats(const uint64_t* __restrict
 
 // scratch of one call: F, then parent, then the roots' numbers (4 B per voxel); the keys (8 B); rootOf (4 B); the two mip levels; the blocks'
 // sums with the totals {K, interface faces} behind them; the search's two counters; the scratch of the field's passes (6 B per voxel)
-static size_t part_mip_bytes(uint32_t N, uint32_t side) { const size_t n = part_cells(N, side); return part_align(n * n * n * sizeof(uint64_t)); }
-static size_t part_sums_bytes(size_t items) { return part_align(2u * ((size_t)part_blocks(items) + 1u) * sizeof(unsigned long long)); }
+static size_t part_mip_bytes(uint32_t N, uint32_t side) { const size_t n = part_cells(N, side); return align256(n * n * n * sizeof(uint64_t)); }
+static size_t part_sums_bytes(size_t items) { return align256(2u * ((size_t)part_blocks(items) + 1u) * sizeof(unsigned long long)); }
 size_t partition_scratch_bytes(uint32_t N)
 {
     const size_t voxels = (size_t)N * N * N;
-    return 2u * part_align(voxels * sizeof(uint32_t)) + part_align(voxels * sizeof(uint64_t)) + part_mip_bytes(N, 4u) + part_mip_bytes(N, 16u) + part_sums_bytes(voxels) + 256u +
+    return 2u * align256(voxels * sizeof(uint32_t)) + align256(voxels * sizeof(uint64_t)) + part_mip_bytes(N, 4u) + part_mip_bytes(N, 16u) + part_sums_bytes(voxels) + 256u +
            distance_scratch_bytes(N);
 }
 void partition_layout(uint8_t* scratch, uint32_t N, PartParams& p)
 {
-    const size_t voxels = (size_t)N * N * N, word = part_align(voxels * sizeof(uint32_t));
+    const size_t voxels = (size_t)N * N * N, word = align256(voxels * sizeof(uint32_t));
     p.N = N;
     p.F = reinterpret_cast<int32_t*>(scratch);
     p.parent = p.number = reinterpret_cast<uint32_t*>(scratch);
     p.rootOf = reinterpret_cast<uint32_t*>(scratch + word);
     uint8_t* at = scratch + 2u * word;
-    p.keys = reinterpret_cast<uint64_t*>(at); at += part_align(voxels * sizeof(uint64_t));
+    p.keys = reinterpret_cast<uint64_t*>(at); at += align256(voxels * sizeof(uint64_t));
     p.mip4 = reinterpret_cast<uint64_t*>(at); at += part_mip_bytes(N, 4u);
     p.mip16 = reinterpret_cast<uint64_t*>(at); at += part_mip_bytes(N, 16u);
     p.sums = reinterpret_cast<unsigned long long*>(at); at += part_sums_bytes(voxels);
@@ -375,8 +322,8 @@ const unsigned long long* partition_counters(const PartParams& p) { return p.cou
 size_t partition_work_bytes(uint32_t K, unsigned long long faces)
 {
     const size_t n = (size_t)faces;
-    size_t bytes = part_align((size_t)K * sizeof(PartStats));
-    if (n) bytes += 2u * part_align(n * sizeof(uint64_t)) + part_align((size_t)radix_sort_hist_words((uint32_t)n) * sizeof(uint32_t)) + part_sums_bytes(n) + part_align(n * sizeof(uint32_t));
+    size_t bytes = align256((size_t)K * sizeof(PartStats));
+    if (n) bytes += 2u * align256(n * sizeof(uint64_t)) + align256((size_t)radix_sort_hist_words((uint32_t)n) * sizeof(uint32_t)) + part_sums_bytes(n) + align256(n * sizeof(uint32_t));
     return bytes ? bytes : 256u;
 }
 void partition_work_layout(uint8_t* work, uint32_t K, unsigned long long faces, PartParams& p)
@@ -384,10 +331,10 @@ void partition_work_layout(uint8_t* work, uint32_t K, unsigned long long faces, 
     const size_t n = (size_t)faces;
     p.K = K; p.faces = faces;
     p.stats = reinterpret_cast<PartStats*>(work);
-    uint8_t* at = work + part_align((size_t)K * sizeof(PartStats));
-    p.sortA = reinterpret_cast<uint64_t*>(at); at += part_align(n * sizeof(uint64_t));
-    p.sortB = reinterpret_cast<uint64_t*>(at); at += part_align(n * sizeof(uint64_t));
-    p.hist = reinterpret_cast<uint32_t*>(at); at += n ? part_align((size_t)radix_sort_hist_words((uint32_t)n) * sizeof(uint32_t)) : 0u;
+    uint8_t* at = work + align256((size_t)K * sizeof(PartStats));
+    p.sortA = reinterpret_cast<uint64_t*>(at); at += align256(n * sizeof(uint64_t));
+    p.sortB = reinterpret_cast<uint64_t*>(at); at += align256(n * sizeof(uint64_t));
+    p.hist = reinterpret_cast<uint32_t*>(at); at += n ? align256((size_t)radix_sort_hist_words((uint32_t)n) * sizeof(uint32_t)) : 0u;
     p.headSums = reinterpret_cast<unsigned long long*>(at); at += part_sums_bytes(n);
     p.pairCount = reinterpret_cast<uint32_t*>(at);
 }
@@ -422,7 +369,7 @@ hipError_t launch_partition_stage(const uint8_t* grid, const PartParams& p, int 
         k_part_walk<<<perVoxel, 256, 0, s>>>(p.parent, voxels, p.rootOf);
         if (p.wantThroats) k_part_count<true><<<blocks, 256, 0, s>>>(p.rootOf, N, voxels, p.sums);
         else k_part_count<false><<<blocks, 256, 0, s>>>(p.rootOf, N, voxels, p.sums);
-        k_part_scan<<<1, 1024, 0, s>>>(p.sums, blocks);
+        if ((e = launch_scan_sums(p.sums, 2, blocks, p.sums + 2 * (size_t)blocks, s)) != hipSuccess) return e;
         k_part_number<<<blocks, 256, 0, s>>>(p.rootOf, N, voxels, p.sums, p.number);
         break;
     case PART_STAGE_REGIONS:                                            // (behind the caller's wait for the totals: labels, table and work are in place)
@@ -450,8 +397,7 @@ hipError_t launch_partition_pairs(PartParams& p, hipStream_t s)
     p.sorted = sorted;
     p.pairs = sorted == p.sortA ? p.sortB : p.sortA;
     k_part_count_heads<<<part_blocks(n), 256, 0, s>>>(p.sorted, n, p.headSums);
-    k_part_scan<<<1, 1024, 0, s>>>(p.headSums, part_blocks(n));
-    return hipGetLastError();
+    return launch_scan_sums(p.headSums, 2, part_blocks(n), p.headSums + 2 * (size_t)part_blocks(n), s);
 }
 // ... and their second, with T known and `throats` (20 T bytes) in place
 hipError_t launch_partition_throats(const PartParams& p, uint32_t T, uint32_t* throats, hipStream_t s)

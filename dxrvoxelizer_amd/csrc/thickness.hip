@@ -4,23 +4,25 @@
 //   k_thick_members   F -> E = { R == cap } as bytes, four voxels per thread
 //   top        distance.hip of E, then k_thick_top: E and its field -> Top as bytes (in place) and the start of W: cap on Top, R elsewhere
 //   cull       distance.hip of Top (option thickcull bit 0)
-//   k_thick_select    per block of 1024 voxels: the work items of every voxel (0: no centre to paint) as a byte, the block's centres and items
-//   k_thick_scan      one workgroup: the exclusive scan of the blocks' two sums, 64-bit, and the totals behind them (then two words the paint counts in)
+//   k_thick_select    per block of 1024 voxels: the work items of every voxel (0: no centre to paint) as a byte, the block's centres and items;
+//                     it also zeroes the two words behind the totals that the paint counts in
+//   scan.hip          launch_scan_sums, one workgroup: the exclusive scan of the blocks' two sums, 64-bit, and the totals behind them
 //   k_thick_emit      the scan inside every block: the compacted centre list (voxel index) and every centre's first item within its block
 //   k_thick_paint     a fixed launch of waves striding over the items: item -> block -> centre by two binary searches (wave-uniform), then the
 //                     slice of the ball in row order, lanes along x: a plain load of W and a relaxed atomic max without return only where the
 //                     loaded value is lower.  W only grows, so a stale load costs a spare atomic and never loses one.
 //   k_thick_histogram W -> cap + 1 64-bit bins through 32-bit bins in LDS (16.4 KB), one 64-bit atomic per non-zero bin and workgroup
-// No kernel waits for another workgroup, no loop is unbounded, nothing goes to scratch memory; only the histogram uses LDS.
+// No kernel waits for another workgroup, no loop is unbounded, nothing goes to scratch memory; LDS: the histogram's bins and the four wave sums
+// of a block's scan (dxv_scan.h).
 #include "dxv_device.h"
 #include "dxv_thickness.h"
+#include "dxv_scan.h"
 
 namespace dxv {
 
 constexpr uint32_t kThickPaintBlocks = 2048;      // workgroups of four waves the paint is launched with, whatever the items
 constexpr uint32_t kThickHistBlocks = 1024;       // ... the histogram, at the most
 
-static size_t thick_align(size_t v) { return (v + 255u) & ~(size_t)255u; }
 static uint32_t thick_blocks(uint32_t N) { return (uint32_t)(((size_t)N * N * N + kThickBlock - 1u) / kThickBlock); }
 
 __global__ __launch_bounds__(256) void k_thick_members(const int32_t* __restrict__ F, uint32_t groups, int of, uint32_t cap, uint32_t* __restrict__ B)
@@ -45,32 +47,13 @@ __global__ __launch_bounds__(256) void k_thick_top(const int32_t* __restrict__ F
                                                 t3 ? cap : thick_radius(d.w, of, cap));
 }
 
-// a block's centres (above bit 20) and items (below it) in one word: at most 1024 and 1024 * 127.  Exclusive scan over the 256 threads; total: the block's sum
-__device__ __forceinline__ uint32_t thick_block_scan(uint32_t mine, uint32_t& total)
-{
-    __shared__ uint32_t waveSums[4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = mine;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint32_t v = (uint32_t)__shfl_up((int)inc, d);
-        if (lane >= d) inc += v;
-    }
-    if (lane == 63u) waveSums[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0;
-    total = 0;
-    for (uint32_t k = 0; k < 4u; ++k) {
-        if (k < wave) before += waveSums[k];
-        total += waveSums[k];
-    }
-    __syncthreads();
-    return before + inc - mine;
-}
-
-// thread t of block b: voxels 1024 b + 4 t .. + 3 (N^3 is a multiple of 8: the four are all inside or all outside)
+// thread t of block b: voxels 1024 b + 4 t .. + 3 (N^3 is a multiple of 8: the four are all inside or all outside).  A block's centres (above bit
+// 20) and items (below it) are scanned in one word: at most 1024 and 1024 * 127.  Thread 0 of block 0 also zeroes the two words behind the totals
+// that k_thick_paint<true> counts in: this kernel is the first of the select stage, the paint is a later stage of the same stream, and nothing
+// between the two -- the scan of the sums writes the blocks' entries and the two totals, k_thick_emit only reads the sums -- touches those words.
 __global__ __launch_bounds__(256) void k_thick_select(ThickParams p, uint32_t voxels)
 {
+    if (blockIdx.x == 0 && threadIdx.x == 0) { p.sums[2 * (size_t)gridDim.x + 2] = 0; p.sums[2 * (size_t)gridDim.x + 3] = 0; }
     const uint32_t first = blockIdx.x * kThickBlock + threadIdx.x * 4u;
     uint32_t bytes = 0, mine = 0;
     if (first < voxels) {
@@ -86,41 +69,8 @@ __global__ __launch_bounds__(256) void k_thick_select(ThickParams p, uint32_t vo
         p.B[first >> 2] = bytes;
     }
     uint32_t total;
-    (void)thick_block_scan(mine, total);
+    (void)block_scan_exclusive<uint32_t, 4>(mine, total);
     if (threadIdx.x == 0) { p.sums[2 * (size_t)blockIdx.x] = total >> 20; p.sums[2 * (size_t)blockIdx.x + 1] = total & 0xfffffu; }
-}
-
-// sums[2 b], sums[2 b + 1] -> the centres and items of the blocks in front of block b; sums[2 blocks], sums[2 blocks + 1] = the totals
-__global__ __launch_bounds__(1024) void k_thick_scan(unsigned long long* __restrict__ sums, uint32_t blocks)
-{
-    __shared__ unsigned long long waveSums[2][16];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t chunk = (blocks + 1023u) / 1024u;
-    const uint32_t first = threadIdx.x * chunk < blocks ? threadIdx.x * chunk : blocks, last = first + chunk < blocks ? first + chunk : blocks;
-    unsigned long long c = 0, i = 0;
-    for (uint32_t b = first; b < last; ++b) { c += sums[2 * (size_t)b]; i += sums[2 * (size_t)b + 1]; }
-    unsigned long long incC = c, incI = i;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const unsigned long long vc = __shfl_up(incC, d), vi = __shfl_up(incI, d);
-        if (lane >= d) { incC += vc; incI += vi; }
-    }
-    if (lane == 63u) { waveSums[0][wave] = incC; waveSums[1][wave] = incI; }
-    __syncthreads();
-    unsigned long long runC = incC - c, runI = incI - i, allC = 0, allI = 0;
-    for (uint32_t k = 0; k < 16u; ++k) {
-        if (k < wave) { runC += waveSums[0][k]; runI += waveSums[1][k]; }
-        allC += waveSums[0][k]; allI += waveSums[1][k];
-    }
-    for (uint32_t b = first; b < last; ++b) {
-        const unsigned long long vc = sums[2 * (size_t)b], vi = sums[2 * (size_t)b + 1];
-        sums[2 * (size_t)b] = runC; sums[2 * (size_t)b + 1] = runI;
-        runC += vc; runI += vi;
-    }
-    if (threadIdx.x == 0) {                                             // (... and the paint's two counters behind them start at 0)
-        sums[2 * (size_t)blocks] = allC; sums[2 * (size_t)blocks + 1] = allI;
-        sums[2 * (size_t)blocks + 2] = 0; sums[2 * (size_t)blocks + 3] = 0;
-    }
 }
 
 __global__ __launch_bounds__(256) void k_thick_emit(ThickParams p, uint32_t voxels)
@@ -134,7 +84,7 @@ __global__ __launch_bounds__(256) void k_thick_emit(ThickParams p, uint32_t voxe
         mine += items ? (1u << 20) + items : 0u;
     }
     uint32_t total;
-    uint32_t run = thick_block_scan(mine, total);
+    uint32_t run = block_scan_exclusive<uint32_t, 4>(mine, total);
     if (!mine) return;
     const size_t base = (size_t)p.sums[2 * (size_t)blockIdx.x];         // (at most N^3 centres: below 2^30)
 #pragma unroll
@@ -211,20 +161,20 @@ __global__ __launch_bounds__(256) void k_thick_histogram(const uint32_t* __restr
 size_t thickness_scratch_bytes(uint32_t N)
 {
     const size_t voxels = (size_t)N * N * N;
-    return 2u * thick_align(voxels * sizeof(int32_t)) + thick_align(voxels) + thick_align(2u * ((size_t)thick_blocks(N) + 2u) * sizeof(unsigned long long)) +
+    return 2u * align256(voxels * sizeof(int32_t)) + align256(voxels) + align256(2u * ((size_t)thick_blocks(N) + 2u) * sizeof(unsigned long long)) +
            distance_scratch_bytes(N);
 }
 size_t thickness_histogram_bytes(uint32_t cap) { return ((size_t)cap + 1u) * sizeof(unsigned long long); }
 
 void thickness_layout(uint8_t* scratch, uint32_t N, ThickParams& p)
 {
-    const size_t voxels = (size_t)N * N * N, field = thick_align(voxels * sizeof(int32_t));
+    const size_t voxels = (size_t)N * N * N, field = align256(voxels * sizeof(int32_t));
     p.N = N;
     p.F = reinterpret_cast<int32_t*>(scratch);
     p.G = reinterpret_cast<int32_t*>(scratch + field);
     p.B = reinterpret_cast<uint32_t*>(scratch + 2u * field);
-    p.sums = reinterpret_cast<unsigned long long*>(scratch + 2u * field + thick_align(voxels));
-    p.passes = scratch + 2u * field + thick_align(voxels) + thick_align(2u * ((size_t)thick_blocks(N) + 2u) * sizeof(unsigned long long));
+    p.sums = reinterpret_cast<unsigned long long*>(scratch + 2u * field + align256(voxels));
+    p.passes = scratch + 2u * field + align256(voxels) + align256(2u * ((size_t)thick_blocks(N) + 2u) * sizeof(unsigned long long));
     p.centres = reinterpret_cast<uint32_t*>(p.G);
     p.firstItem = reinterpret_cast<uint32_t*>(p.passes);
 }
@@ -254,7 +204,7 @@ hipError_t launch_thickness_stage(const uint8_t* grid, const ThickParams& p, int
         break;
     case THICK_STAGE_SELECT:
         k_thick_select<<<blocks, 256, 0, s>>>(p, voxels);
-        k_thick_scan<<<1, 1024, 0, s>>>(p.sums, blocks);
+        if ((e = launch_scan_sums(p.sums, 2, blocks, p.sums + 2 * (size_t)blocks, s)) != hipSuccess) return e;
         k_thick_emit<<<blocks, 256, 0, s>>>(p, voxels);
         break;
     case THICK_STAGE_PAINT:

@@ -22,9 +22,8 @@
 
 namespace dxv {
 
-static size_t thin_align(size_t v) { return (v + 255u) & ~(size_t)255u; }
-static size_t thin_mask_bytes(uint32_t N) { return thin_align(fill_mask_words(N) * sizeof(uint64_t)); }
-static size_t thin_loose_bytes(uint32_t N) { return thin_align((fill_mask_words(N) * 8u + 63u) / 64u * sizeof(uint64_t)); }
+static size_t thin_mask_bytes(uint32_t N) { return align256(fill_mask_words(N) * sizeof(uint64_t)); }
+static size_t thin_loose_bytes(uint32_t N) { return align256((fill_mask_words(N) * 8u + 63u) / 64u * sizeof(uint64_t)); }
 constexpr size_t kThinControlBytes = 512;
 static_assert(sizeof(ThinControl) <= kThinControlBytes && sizeof(ThinControl::live) == sizeof(uint32_t) * kThinMaxRounds, "the control block has a word per iteration of a batch");
 // the control block, S, S as it was, B, the loose bits: 3 1/8 bits per voxel

@@ -966,6 +966,14 @@ class Voxelizer:
         return {"bricks": int(out[0]), "dead_bricks": int(out[1]), "rays_walked": int(out[2]), "violations": int(out[3]),
                 "first": [int(v) for v in out[4:4 + int(min(out[3], 8))]]}
 
+    def debug_scan(self, what, lanes, buf, items):
+        """dxv_debug_scan: the grid operators' exclusive scan on the caller's numbers, in place in `buf` (a C-contiguous array, or None) --
+        what = 0: items x lanes uint32 counts; what = 1: items x lanes uint64 sums, then `lanes` words for the totals and one guard word.
+        Returns the `lanes` totals."""
+        totals = (C.c_uint64 * 2)()
+        self._check(self._lib.dxv_debug_scan(self._ctx, int(what), int(lanes), None if buf is None else buf.ctypes.data_as(C.c_void_p), int(items), totals))
+        return [int(totals[k]) for k in range(min(int(lanes), 2))]
+
     def trim(self):
         self._check(self._lib.dxv_trim(self._ctx))
 

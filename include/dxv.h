@@ -1118,6 +1118,15 @@ DXV_API int dxv_debug_plan_check(dxv_ctx* ctx, uint64_t out[16]);
  * the same for two builds of the same queue. */
 DXV_API int dxv_debug_queue_order(dxv_ctx* ctx, uint64_t out[4]);
 
+/* Test hook: the exclusive scan under the grid operators (octree, components, isosurface, thickness, partition; csrc/scan.hip) on the caller's
+ * numbers, in place, on the context's stream.  `lanes` (1 or 2) interleaved values per item.
+ *   what = 0: host_counts = items x lanes uint32 counts; each becomes the sum of its lane's counts in front of it, modulo 2^32;
+ *             totals[0 .. lanes) = the lanes' sums, 64-bit.
+ *   what = 1: host_counts = items x lanes uint64 sums, then `lanes` words the totals are written to -- right behind the sums, where thickness and
+ *             partition keep them -- and ONE more word that nothing writes: (items + 1) x lanes + 1 words in all; totals[] = the same totals.
+ * Another lane count, items = 0 or host_counts = NULL is refused by the scan's own entry points: non-zero, and host_counts is left as it was. */
+DXV_API int dxv_debug_scan(dxv_ctx* ctx, int what, uint32_t lanes, void* host_counts, size_t items, uint64_t totals[2]);
+
 /* Give back what the context keeps only to make the next build faster: the list build's scratch (up to 16 GiB per buffer
  * after a 10 M-triangle scene), the LBVH build's scratch when no refit can follow (imported scenes), the memory of prepared queues
  * whose lists are gone, the scratch of the frames' distance fields (the fields stay), of their flood fills, morphs, thins, thickness and geodesic maps and partitions (maps, labels and tables stay), of their isosurfaces (the

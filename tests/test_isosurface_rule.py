@@ -194,7 +194,7 @@ def test_isosurface_kernels_use_no_scratch_memory(dxvlib):
     if not os.path.exists(os.path.join(build.OBJDIR, "isosurface.usage")):
         build.build(force=True)
     res = {k: v for k, v in build.kernel_resources("isosurface").items() if "k_iso" in k}
-    assert len(res) == 5, sorted(res)                                  # count, the scan's three, emit
+    assert len(res) == 2, sorted(res)                                  # count, emit (the scan between them is csrc/scan.hip's: tests/test_scan_resources.py)
     for k, v in res.items():
         assert v["scratch"] == 0, k
-        assert v["lds"] <= 256, k                                      # the scan's wave sums; count and emit use none
+        assert v["lds"] == 0, k

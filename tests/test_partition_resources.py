@@ -1,11 +1,12 @@
 """The partition kernels (csrc/partition.hip) as the compiler made them for gfx950, from its resource remarks (build.kernel_resources): none uses
 scratch memory, their LDS is the few words of a block's scan, and their registers stay within the bounds DESIGN §4.16 states (read off the build;
-each bound the next multiple of eight).  The cross-compile needs no GPU."""
+each bound the next multiple of eight).  The scan of the blocks' sums is csrc/scan.hip's: tests/test_scan_resources.py.  The cross-compile needs
+no GPU."""
 import os
 
 # kernel -> (VGPR bound, waves per SIMD, LDS bytes at the most)
 BOUND = {"k_part_keys": (16, 8, 0), "k_part_mip": (16, 8, 0), "k_part_searchILb0E": (128, 4, 0), "k_part_searchILb1E": (152, 3, 0), "k_part_walk": (8, 8, 0),
-         "k_part_countILb0E": (16, 8, 16), "k_part_countILb1E": (24, 8, 16), "k_part_scan": (80, 6, 256), "k_part_number": (16, 8, 16), "k_part_labels": (8, 8, 0),
+         "k_part_countILb0E": (16, 8, 16), "k_part_countILb1E": (24, 8, 16), "k_part_number": (16, 8, 16), "k_part_labels": (8, 8, 0),
          "k_part_stats_init": (16, 8, 0), "k_part_statsE": (16, 8, 0), "k_part_table": (16, 8, 0), "k_part_emit_faces": (32, 8, 16), "k_part_count_heads": (16, 8, 16),
          "k_part_emit_pairs": (16, 8, 16), "k_part_face_atomics": (24, 8, 0), "k_part_throatsE": (16, 8, 0)}
 ROW = {"k_part_searchILb0E": "k_part_search<false>", "k_part_searchILb1E": "k_part_search<true>", "k_part_countILb0E": "k_part_count<false>", "k_part_countILb1E": "k_part_count<true>",
