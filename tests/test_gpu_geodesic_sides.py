@@ -34,6 +34,18 @@ def expectation(g, of, metric, seeds):
     return want, gr.tally(want)
 
 
+def check_kinds_metrics_and_seeds(v, N, name, g):
+    """map and tally of both kinds, both metrics and both seedings of the selected frame's grid, which holds g, against the expectation"""
+    for of in (gr.SOLID, gr.EMPTY):
+        for metric in (gr.FACES, gr.CHAMFER):
+            for seeds in (gr.smallest_member(g, of), "border"):
+                want, tally = expectation(g, of, metric, seeds)
+                got = v.Geodesic(of, metric, seeds)
+                assert got.dtype == want.dtype and got.shape == want.shape and got.tobytes() == want.tobytes(), (N, name, of, metric, type(seeds))
+                info = v.GeodesicInfo()
+                assert {k: info[k] for k in TALLY} == tally, (N, name, of, metric, type(seeds))
+
+
 @pytest.mark.parametrize("N", gs.SWEEP + gs.WIDE)
 def test_both_kinds_and_both_metrics_at_every_side(writer, N):
     v = writer
@@ -42,12 +54,5 @@ def test_both_kinds_and_both_metrics_at_every_side(writer, N):
     for name, g in gs.grids(N, ("all 0xFF", "ends") if N in gs.WIDE else None):
         seen += 1
         write_grid(v, g)
-        for of in (gr.SOLID, gr.EMPTY):
-            for metric in (gr.FACES, gr.CHAMFER):
-                for seeds in (gr.smallest_member(g, of), "border"):
-                    want, tally = expectation(g, of, metric, seeds)
-                    got = v.Geodesic(of, metric, seeds)
-                    assert got.dtype == want.dtype and got.shape == want.shape and got.tobytes() == want.tobytes(), (N, name, of, metric, type(seeds))
-                    info = v.GeodesicInfo()
-                    assert {k: info[k] for k in TALLY} == tally, (N, name, of, metric, type(seeds))
+        check_kinds_metrics_and_seeds(v, N, name, g)
     assert seen == (2 if N in gs.WIDE else 5 if N >= 6 else 4)

@@ -24,6 +24,15 @@ def writer(dxvlib, bunny):
     v.close()
 
 
+def check_both_kinds(v, N, name, g):
+    """labels, table and throats of both kinds of the selected frame's grid, which holds g, against the restatement"""
+    for of in (pr.SOLID, pr.EMPTY):
+        want = pr.partition(g, of, CAP)
+        got = v.Partition(of, CAP)
+        for a, b, what in zip(got, want, ("labels", "table", "throats")):
+            assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), (N, name, of, what)
+
+
 @pytest.mark.parametrize("N", gs.SWEEP)
 def test_both_kinds_at_every_side(writer, N):
     v = writer
@@ -32,9 +41,5 @@ def test_both_kinds_at_every_side(writer, N):
     for name, g in gs.grids(N):
         seen += 1
         write_grid(v, g)
-        for of in (pr.SOLID, pr.EMPTY):
-            want = pr.partition(g, of, CAP)
-            got = v.Partition(of, CAP)
-            for a, b, what in zip(got, want, ("labels", "table", "throats")):
-                assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), (N, name, of, what)
+        check_both_kinds(v, N, name, g)
     assert seen == (5 if N >= 6 else 4)

@@ -34,6 +34,15 @@ def expectation(g, of):
     return W, tr.histogram(W, CAP)
 
 
+def check_both_kinds(v, N, name, g):
+    """map and histogram of both kinds of the selected frame's grid, which holds g, against the expectation"""
+    for of in (tr.SOLID, tr.EMPTY):
+        want, hist = expectation(g, of)
+        got = v.Thickness(of, CAP)
+        assert got.dtype == want.dtype and got.shape == want.shape and got.tobytes() == want.tobytes(), (N, name, of)
+        assert v.ThicknessHistogram().tobytes() == hist.tobytes(), (N, name, of)
+
+
 @pytest.mark.parametrize("N", gs.SWEEP + gs.WIDE)
 def test_both_kinds_at_every_side(writer, N):
     v = writer
@@ -42,9 +51,5 @@ def test_both_kinds_at_every_side(writer, N):
     for name, g in gs.grids(N, ("all 0xFF", "ends") if N in gs.WIDE else None):
         seen += 1
         write_grid(v, g)
-        for of in (tr.SOLID, tr.EMPTY):
-            want, hist = expectation(g, of)
-            got = v.Thickness(of, CAP)
-            assert got.dtype == want.dtype and got.shape == want.shape and got.tobytes() == want.tobytes(), (N, name, of)
-            assert v.ThicknessHistogram().tobytes() == hist.tobytes(), (N, name, of)
+        check_both_kinds(v, N, name, g)
     assert seen == (2 if N in gs.WIDE else 5 if N >= 6 else 4)

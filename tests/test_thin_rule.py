@@ -122,12 +122,14 @@ def test_product_routines_equal_restatement_on_the_shapes(N):
 
 @pytest.mark.parametrize("N", gs.SWEEP + gs.WIDE)
 def test_product_routines_equal_restatement_at_every_side(N):
-    """every even side to 72 and the three longer rows.  The restatement of "all 0xFF" takes 0.15 s at side 72, 0.5 s at 130 and 2.0 s at 194 per
-    kind here, "ends" 0.03 s, 0.1 s and 0.3 s, so the longer rows are in (with the product's own runs a case takes 4 s at 126 and 130, 10 s at 194); the random grids take 1 s at 32 and 6 s at 72 (every distinct
-    neighbourhood is decided once), which is why they stop at 32."""
-    names = ("all 0xFF", "ends") if N in gs.WIDE else ("all 0xFF", "ends", "hollow box") + (("random 0.6", "random 0.3") if N <= 32 else ())
+    """every even side to 72 and the three longer rows.  The restatement of "all 0xFF" takes 1.4 s at side 72, 2.5 s at 130 and 5 s at 194 per
+    kind here, "ends" 0.4 s, 0.6 s and 1.1 s for KERNEL, so the longer rows are in (with the product's own runs a case takes 10 s at 126 and 130,
+    19 s at 194).  "random 0.3" runs at every side to 72: 2.3 s for both kinds at 72 (every distinct neighbourhood is decided once), a case there
+    9 s.  "random 0.6" takes 1 s at 32 and 6 s and more from 66 on, so it stops at 32 -- and runs once more at 66, two words with N % 8 != 0,
+    to the fixed point only (that case takes 18 s): tests/test_gpu_thin_sides.py takes the host library's word for that grid above 32."""
+    names = ("all 0xFF", "ends") if N in gs.WIDE else ("all 0xFF", "ends", "hollow box", "random 0.3") + (("random 0.6",) if N <= 32 or N == 66 else ())
     for what, g in gs.grids(N, names):
-        check_product(g, (N, what), limits=(0,) if N in gs.WIDE else (0, 2))
+        check_product(g, (N, what), limits=(0,) if N in gs.WIDE or (what, N) == ("random 0.6", 66) else (0, 2))
 
 
 def test_batches_split_a_bounded_run():
