@@ -386,6 +386,18 @@ __attribute__((visibility("default"))) void hc_scene_destroy(void* p) { delete s
 __attribute__((visibility("default"))) uint32_t hc_scene_height(void* p) { return static_cast<HcScene*>(p)->height; }
 __attribute__((visibility("default"))) void hc_scene_nodes64(void* p, void* out) { auto* s = static_cast<HcScene*>(p); memcpy(out, s->nodes64.data(), s->nodes64.size() * sizeof(Node64)); }
 __attribute__((visibility("default"))) void hc_scene_nodes(void* p, void* out) { auto* s = static_cast<HcScene*>(p); memcpy(out, s->nodes.data(), s->nodes.size() * sizeof(Node)); }
+// compress_node / widen_node of the caller's n exact nodes (a refit's boxes over a build's links): 32 and 64 bytes per node
+__attribute__((visibility("default"))) void hc_traversal_copies(const void* nodes, uint32_t n, void* out32, void* out64)
+{
+    std::vector<Node> in(n);                                            // (the caller's buffers need not be aligned like a Node)
+    memcpy(in.data(), nodes, sizeof(Node) * (size_t)n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const Node32 c = compress_node(in[i]);
+        const Node64 w = widen_node(in.data(), (int32_t)i);
+        memcpy(static_cast<char*>(out32) + sizeof(Node32) * (size_t)i, &c, sizeof(c));
+        memcpy(static_cast<char*>(out64) + sizeof(Node64) * (size_t)i, &w, sizeof(w));
+    }
+}
 __attribute__((visibility("default"))) void hc_scene_keys(void* p, void* out) { auto* s = static_cast<HcScene*>(p); memcpy(out, s->keys.data(), s->keys.size() * 8); }
 
 __attribute__((visibility("default"))) int hc_voxelize(void* p, uint32_t N, int mode, uint32_t z0, uint32_t nz, int stackCap,
