@@ -745,6 +745,35 @@ hipError_t dirmap_mip(const DirCell* cells, uint32_t R, uint16_t* mip, hipStream
     return hipGetLastError();
 }
 
+// The start table of the lists (dxv_dirmap.h: dm_start_word): one thread per texel, the buckets' edges by binary search in the texel's
+// sorted list -- a dozen loads per texel however long the list.
+__global__ __launch_bounds__(1024) void k_dm_starts(const DirCell* __restrict__ cells, uint32_t ncells, const DirEntry* __restrict__ entries,
+                                                   uint32_t* __restrict__ starts)
+{
+    const uint32_t k = blockIdx.x * 1024u + threadIdx.x;
+    uint32_t count = 0u;
+    if (k < ncells) {
+        const DirCell cell = cells[k];
+        starts[k] = dm_start_word(cell, entries + cell.begin);
+        count = cell.count;
+    }
+    // (the two counters behind the table: what the automatic setting of option starttable goes by -- start_table_pays)
+    // (one pair of additions per workgroup: per wave they were a quarter of the build's time on two words)
+    const int some = __syncthreads_count(count != 0u), many = __syncthreads_count(count > 8u);
+    if (threadIdx.x == 0u) {
+        if (some) atomicAdd(starts + ncells, (uint32_t)some);
+        if (many) atomicAdd(starts + ncells + 1u, (uint32_t)many);
+    }
+}
+hipError_t dirmap_starts(const DirCell* cells, uint32_t R, const DirEntry* entries, uint32_t* starts, hipStream_t s)
+{
+    const uint32_t n = 6u * R * R;
+    const hipError_t e = hipMemsetAsync(starts + n, 0, 2 * sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+    k_dm_starts<<<(n + 1023u) / 1024u, 1024, 0, s>>>(cells, n, entries, starts);
+    return hipGetLastError();
+}
+
 __global__ __launch_bounds__(kThreads) void k_dm_validate(const DirCell* __restrict__ cells, uint32_t ncells, const DirEntry* __restrict__ entries,
                                                           uint32_t n, uint32_t T, uint32_t* __restrict__ out)
 {

@@ -87,6 +87,8 @@ struct Lists {
     DevBuf<DirCell> cells;
     DevBuf<DirEntry> entries;
     DevBuf<uint16_t> mip;            // (cap: 16-bit words of the mip proper)
+    DevBuf<uint32_t> starts;         // start table (dxv_dirmap.h: dm_start_word): one word per texel, made with the mip wherever cells and entries are; two counters behind it
+    bool startsPay = false;          // what option starttable = 2 (automatic) does for these lists (dxv_policy.h: start_table_pays; false until the build is settled)
     uint32_t count = 0, res = 0;     // entries, texels per face side
     int state = 0;                   // 0: not built for this scene, 1: built, -1: over the cap for this scene (tree walk)
     int opt = 0;                     // the listres option these lists (or the decision against them) were made with
@@ -97,6 +99,7 @@ struct Lists {
         hipError_t e = cells.reserve(6 * (size_t)R * R, 6 * (size_t)R * R * sizeof(DirCell));
         if (e == hipSuccess) e = entries.reserve(n, (n + 4) * sizeof(DirEntry));
         if (e == hipSuccess) e = mip.reserve(dm_mip_words(R), sizeof(uint16_t) * (size_t)dm_mip_buffer_words(R));
+        if (e == hipSuccess) e = starts.reserve(6 * (size_t)R * R + 2, (6 * (size_t)R * R + 2) * sizeof(uint32_t));
         return e;
     }
 };
@@ -417,6 +420,7 @@ struct dxv_ctx {
         uint32_t rootInfo[16];
         unsigned long long listTotal;
         uint32_t listLongest, pad;
+        uint32_t listStarts[2];                          // non-empty texels, texels of more than 8 entries (dirmap_starts): start_table_pays
         uint32_t preparedLens[16 * 64];                  // the sixteen count words of a queue that is being prepared (as PerFrame::queueLens)
         struct PerFrame {
             uint32_t status[4];
@@ -505,7 +509,11 @@ inline void scene_params(dxv_ctx* c, SceneView& sc)
     memcpy(sc.rootHi, c->hdr.rootHi, 12);
 }
 // ... and about its direction-space lists
-inline void lists_params(const dxv_ctx* c, SceneView& sc) { sc.dmCells = c->lists.cells.p; sc.dmEntries = c->lists.entries.p; sc.dmR = c->lists.res; }
+inline void lists_params(const dxv_ctx* c, SceneView& sc)
+{
+    sc.dmCells = c->lists.cells.p; sc.dmEntries = c->lists.entries.p; sc.dmR = c->lists.res;
+    sc.dmStarts = start_table_used(c->opt.starttable, c->lists.startsPay) ? c->lists.starts.p : nullptr;
+}
 inline uint32_t z_shift(uint32_t zBlock)
 {
     uint32_t shift = 0;

@@ -19,7 +19,9 @@ namespace dxv {
 // watertight hit at 0 < t < TMax, box entry <= t) must be found in the ray's texel list and pass that entry's integer
 // test (box, edge, radial range) even with the radial cut already drawn at its own t, and lie in front of the point where a
 // scan holding a hit at that t stops -- then no order of scanning, no
-// cut by an earlier hit and no early stop can keep the closest hit out of the queue (dxv_dirmap.h).
+// cut by an earlier hit and no early stop can keep the closest hit out of the queue (dxv_dirmap.h).  The entry must also lie at or
+// behind the start the lists' start table gives this ray (dm_start_offset; the table as it stands in memory, whatever option
+// starttable says): a wrong or stale table shows up as violations.
 // out[0] accepted (ray, triangle) pairs, out[1] violations, out[2 + 2 k], out[3 + 2 k]: voxel id and triangle slot of the
 // first 16 violations.  Not a product path.
 // ---------------------------------------------------------------------------------------------
@@ -39,11 +41,12 @@ __global__ __launch_bounds__(64) void k_list_check(VoxelizeParams p, unsigned lo
     if (origin_leaves_root(r.ox, r.oy, r.oz, sc.rootLo, sc.rootHi)) return;
     finish_ray_reference(r);
     ray_shear(r);
-    const DirMapView dm{static_cast<const DirCell*>(sc.dmCells), static_cast<const DirEntry*>(sc.dmEntries), sc.dmR};
+    const DirMapView dm{static_cast<const DirCell*>(sc.dmCells), static_cast<const DirEntry*>(sc.dmEntries), sc.dmR, 0u, sc.dmStarts};
     const DirRayStart start = dm_ray_start(r.ox, r.oy, r.oz, dm);
     const DirCell cell = start.cell;
     const DirRayLocal loc = dm_ray_local(start.cx, start.cy);
     const float rho = start.rho, near = start.near;
+    const uint32_t from = cell.begin + dm_start_offset(start.startWord, cell.count, cell.r1max, near);
     const size_t id = ((size_t)lz * N + iy) * N + ix;
     auto leaf = [&](int32_t l) {
         const TriPos tp = load_tri(sc.triPos, l);
@@ -56,7 +59,7 @@ __global__ __launch_bounds__(64) void k_list_check(VoxelizeParams p, unsigned lo
         bool found = false;
         const float step = dm_stop_step(half_bits_to_float(cell.thick)), bound = (rho + t) * 1.001f + 1e-4f;
         if (start.live)
-            for (uint32_t k = cell.begin; k < cell.begin + cell.count && !found; ++k) {
+            for (uint32_t k = from; k < cell.begin + cell.count && !found; ++k) {
                 const DirEntry e = dm.entries[k];
                 if (dm_stop_radius(e, step) > bound) break;             // a scan with this hit in hand would stop here: the entry must come before
                 found = dm_entry_tri(e) == (uint32_t)l && dm_local_pass(e, loc, rc);
@@ -125,6 +128,7 @@ extern "C" int dxv_debug_list_check(dxv_ctx* c, uint32_t N, uint32_t z0, uint32_
     VoxelizeParams p{};
     scene_params(c, p.scene);
     lists_params(c, p.scene);
+    p.scene.dmStarts = c->lists.starts.p;
     p.N = N; p.z0 = z0; p.nz = nz;
     return run_check(c, "dxv_debug_list_check", 34, 34, out, c->stream, [&](unsigned long long* d) { return launch_list_check(p, d, c->stream); });
 }
@@ -529,6 +533,7 @@ extern "C" int dxv_debug_download(dxv_ctx* c, int what, void* host, size_t bytes
     case DXV_DBG_LIST_CELLS: if (c->haveScene && c->lists.state == 1) { src = c->lists.cells.p; want = sizeof(DirCell) * 6 * (size_t)c->lists.res * c->lists.res; } break;
     case DXV_DBG_LIST_ENTRIES: if (c->haveScene && c->lists.state == 1) { src = c->lists.entries.p; want = sizeof(DirEntry) * (size_t)c->lists.count; } break;
     case DXV_DBG_LIST_MIP: if (c->haveScene && c->lists.state == 1 && c->lists.mip.p) { src = c->lists.mip.p; want = sizeof(uint16_t) * (size_t)dm_mip_words(c->lists.res); } break;
+    case DXV_DBG_LIST_STARTS: if (c->haveScene && c->lists.state == 1 && c->lists.starts.p) { src = c->lists.starts.p; want = sizeof(uint32_t) * 6 * (size_t)c->lists.res * c->lists.res; } break;
     case DXV_DBG_BRICK_EMPTY:
     case DXV_DBG_BRICK_SUMMARY: {                                       // (written on the frame's stream by its last render with flags: launch_raycast)
         const Frame& f = cur_frame(c);

@@ -90,6 +90,7 @@ struct DirMapView {
     const DirEntry* entries;
     uint32_t R;                // texels per face side, a power of two
     uint32_t coop = 0u;        // device: 1 = a lone lane's long list is scanned by its whole wave (trace_reference_dm_from)
+    const uint32_t* starts = nullptr;   // 6 * R * R start words (dm_start_word), indexed like the cells; NULL: every scan begins where the search ends
 };
 
 constexpr float kDmDelta = 3.0517578125e-5f;        // 2^-15: dilation of the triangles
@@ -187,11 +188,67 @@ DXV_HD void dm_ray_point(float ox, float oy, float oz, uint32_t& face, float& u,
     rho = sqrt_in_range((ox * ox + oy * oy) + oz * oz);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Start table: one 32-bit word per texel, a pure function of the texel's cell and entries (like the max-mip: derived, never
+// exported; cells and entries stay as they are).  The start search narrows a list to a window of up to 8 entries and the scan
+// begins at the window's left edge: a texel that lists two shells (9 .. 35 entries: only q2 exists up to 17) sends a ray inside
+// the body to entry 0 or to n / 2 + 1, and the entries in front of the ray are fetched, four per round, to fail the radial test.
+// The word says how many entries a ray may skip, from the ray's start radius alone:
+//   key of an entry  ke = the half bits of its far radius r1;  key of a ray  kn = dm_half_down_pos(near);  top = cell.r1max
+//   bucket           d(k) = (top - k) >> sh, sh the smallest shift that puts the list's FIRST entry in bucket B - 1 or lower
+//   word             sh in bits 0 .. 3; then for d = 0 .. B - 2, in 8 bits each, S[d] = the number of entries with d(ke) > d
+//                    in units of ceil(count / 256) entries, rounded down (count <= 65,535: S <= 255)
+//   start of a ray   begin + S[d(kn)] * unit, begin itself for d(kn) >= B - 1
+// Why a ray loses nothing: d is non-increasing in k, so d(ke) > d(kn) implies ke < kn, i.e. r1 < half(kn) <= near -- the entry fails
+// the radial half of dm_local_pass for this ray.  The lists are sorted by r1, so those entries are a prefix of the list; rounding S
+// down only skips fewer of them.  The table skips only entries the scan would have looked at and rejected; the stop rule and the
+// flush rule do not depend on which entries were looked at before (the cooperative scan relies on the same).  A ray whose key lies
+// above `top` (not live) or outside the halfs' range gets no skip at all.
+// ---------------------------------------------------------------------------------------------
+constexpr uint32_t kDmStartBuckets = 4u;            // B: 4 bits + 3 x 8 bits of the word (the round replay: 8 buckets save 0.02 rounds more)
+DXV_HD uint32_t dm_entry_key(const DirEntry& e) { return (e.rr >> 16) & 0x7fffu; }
+DXV_HD uint32_t dm_start_unit(uint32_t count) { return (count + 255u) >> 8; }
+DXV_HD uint32_t dm_start_bucket(uint32_t top, uint32_t sh, uint32_t k) { return k < top ? (top - k) >> sh : 0u; }
+// the word of a texel; list = entries + cell.begin (O(B log count) loads: the buckets' edges by binary search in the sorted list)
+DXV_HD uint32_t dm_start_word(const DirCell& cell, const DirEntry* list)
+{
+    const uint32_t n = cell.count, top = cell.r1max;
+    if (n == 0u) return 0u;
+    const uint32_t k0 = dm_entry_key(list[0]);
+    uint32_t sh = 0u;
+    while (dm_start_bucket(top, sh, k0) > kDmStartBuckets - 1u) ++sh;   // (top - k0 < 2^15: sh <= 13)
+    const uint32_t unit = dm_start_unit(n);
+    uint32_t word = sh;
+    for (uint32_t d = 0u; d + 1u < kDmStartBuckets; ++d) {
+        uint32_t lo = 0u, hi = n;                                       // first entry with bucket <= d
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (dm_start_bucket(top, sh, dm_entry_key(list[mid])) > d) lo = mid + 1u; else hi = mid;
+        }
+        word |= (lo / unit) << (4u + 8u * d);                           // (the last entry's key is top, bucket 0: lo <= n - 1, lo / unit <= 255)
+    }
+    return word;
+}
+// entries a ray of start radius `near` may skip at the head of the texel's list (word 0: none)
+DXV_HD uint32_t dm_start_offset(uint32_t word, uint32_t count, uint32_t top, float near)
+{
+    const uint32_t kn = dm_half_down_pos(near);
+    uint32_t d = kn <= top ? (top - kn) >> (word & 15u) : kDmStartBuckets - 1u;
+    if (d > kDmStartBuckets - 1u) d = kDmStartBuckets - 1u;
+    return ((word >> (4u + 8u * d)) & 255u) * dm_start_unit(count);     // (d = B - 1 reads the word's four empty top bits: 0)
+}
+
 // The first step of a ray through the lists -- its texel, its cell inside the texel, and whether it has any candidate at
 // all: a ray whose texel is empty, or that starts beyond the far radius of its texel's last entry, is a miss after this
 // one load.  ONE definition: the kernel (trace_reference_dm), the plan's exact checker (k_plan_check, dxv_debug.hip) and
 // the exhaustive list check make this decision through it, and the brick test below bounds it from above.
-struct DirRayStart { DirCell cell; uint32_t cx, cy; float rho, near; bool live; };
+// (startWord: the texel's word of the start table, asked for with the cell -- two independent loads behind one wait; 0 without a table)
+// STARTS = false: a kernel compiled for launches WITHOUT a table (startWord is the constant 0 and everything made of it folds away: the
+// instruction stream of the kernel before there was a table).  The table's few instructions cost a launch that does not use them 5 - 6 %
+// (measured, profiles/start_table/: the body with them, pointer NULL, against the body without), so the brick kernels exist in both forms
+// and the launch picks by the pointer (voxelize_lists.hip).
+struct DirRayStart { DirCell cell; uint32_t cx, cy; float rho, near; bool live; uint32_t startWord; };
+template <bool STARTS = true>
 DXV_HD DirRayStart dm_ray_start(float ox, float oy, float oz, const DirMapView& dm)
 {
     DirRayStart s;
@@ -199,7 +256,17 @@ DXV_HD DirRayStart dm_ray_start(float ox, float oy, float oz, const DirMapView& 
     float u, v;
     dm_ray_point(ox, oy, oz, face, u, v, s.rho);
     dm_local(u, dm.R, ti, s.cx); dm_local(v, dm.R, tj, s.cy);
-    s.cell = dm.cells[(face * dm.R + tj) * dm.R + ti];
+    const uint32_t at = (face * dm.R + tj) * dm.R + ti;
+#if defined(DXV_NO_START_TABLE)                     // (A/B build from the same sources: the kernels as they were without the table)
+    s.startWord = 0u;
+#else
+    // The word is asked for IN FRONT of the cell, under the (wave-uniform) test of the pointer, and nothing looks at it before the cell
+    // has been asked for too: both loads are in flight behind one wait, no dependent trip -- and a launch without a table issues no
+    // load for it at all (asked for behind the cell, the compiler waits for the cell in front of the branch).
+    s.startWord = 0u;
+    if (STARTS && dm.starts) s.startWord = dm.starts[at];
+#endif
+    s.cell = dm.cells[at];
     s.near = s.rho * 0.999f;
     s.live = s.cell.count != 0u && !(half_bits_to_float(s.cell.r1max) < s.near);
     return s;
@@ -816,6 +883,12 @@ DXV_HD void trace_reference_dm_from(Ray& r, const DirMapView& dm, const DirRaySt
         const uint32_t mid = i + ((hi - i) >> 1);
         if (dm_entry_r1(dm.entries[mid]) < near) i = mid + 1u; else hi = mid;
     }
+    // ... and the start table moves the scan's first entry later, never earlier (hints and search name positions in the whole
+    // list and run as before; a ray that is not live stays at the end: the table's start never lies behind it)
+    {
+        const uint32_t from = cell.begin + dm_start_offset(start.startWord, cell.count, cell.r1max, near);
+        if (from > i) i = from;
+    }
     DXV_PHASE(1);
     int qn = 0;
     bestDet = 1.0f;                                                     // divisor of the closest hit's barycentrics (the caller's finish_hit)
@@ -974,7 +1047,7 @@ DXV_HD void trace_reference_dm(Ray& r, const DirMapView& dm, const TriPos* tris,
 template <class Stack, int ABL>
 DXV_HD void trace_reference_lists(Ray& r, const SceneView& sc, const Stack& stk, int cap, Hit& best, float& bestDet)
 {
-    const DirMapView dm{static_cast<const DirCell*>(sc.dmCells), static_cast<const DirEntry*>(sc.dmEntries), sc.dmR, sc.dmCoop};
+    const DirMapView dm{static_cast<const DirCell*>(sc.dmCells), static_cast<const DirEntry*>(sc.dmEntries), sc.dmR, sc.dmCoop, sc.dmStarts};
     trace_reference_dm<Stack, ABL>(r, dm, sc.triPos, stk, cap, best, bestDet);
 }
 

@@ -65,6 +65,7 @@ static int settle(dxv_ctx* c, Lists& l)
     DXV_HIP(c, hipEventSynchronize(c->evList[3]));
     c->listCheckPending = false;
     l.ms = elapsed(c->evList[0], c->evList[1]) + elapsed(c->evList[2], c->evList[3]);
+    l.startsPay = start_table_pays(c->pin->listStarts[0], c->pin->listStarts[1]);
     if (c->pin->listLongest > 0xffffu) {
         c->withdrawnEpoch = c->listEpoch;
         l.state = -1; l.count = 0; l.opt = c->opt.listres;
@@ -173,6 +174,12 @@ static int build_lists_into(dxv_ctx* c, Lists& l, hipStream_t stream, uint64_t f
 
     // the max-mip of the texels' far radii goes with the lists (a launch's work queue is probed against it)
     if ((e = dirmap_mip(l.cells.p, R, l.mip.p, stream)) != hipSuccess) return bail(e, "dirmap_mip");
+    // ... and so does the start table (a function of cells and entries: inside the build's second pair of events, list_ms)
+    // (one page-locked pair for every build and import: nothing else writes it between this copy and the settle() that reads it --
+    // builds beside working lists are never deferred, an import synchronises, and a deferred build is settled before the next one starts)
+    l.startsPay = false;
+    if ((e = dirmap_starts(l.cells.p, R, l.entries.p, l.starts.p, stream)) != hipSuccess) return bail(e, "dirmap_starts");
+    if ((e = hipMemcpyAsync(c->pin->listStarts, l.starts.p + 6 * (size_t)R * R, sizeof(c->pin->listStarts), hipMemcpyDeviceToHost, stream)) != hipSuccess) return bail(e, "hipMemcpyAsync");
     if ((e = hipEventRecord(c->evList[3], stream)) != hipSuccess) return bail(e, "hipEventRecord");
     // scratch that is not kept (over 16 GiB) is freed here: hipFree waits for the device
     onceA.release(); onceB.release();

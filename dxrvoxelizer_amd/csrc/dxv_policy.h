@@ -144,6 +144,17 @@ inline QueueLaunch queue_policy(const QueueState& q, uint64_t sig, uint64_t voxe
     return QueueLaunch::kept_persistent;
 }
 
+// Do the launches through the lists read the start table?  The word is one more load per ray in a kernel bound by the number of its
+// load instructions, and the brick kernels compiled with the table are 5 - 6 % slower than the plain ones before the table saves
+// anything (voxelize_lists.hip keeps both forms): it pays where it removes whole scan rounds from most waves, and a wave is as slow as
+// its worst lane.  What decides is how many texels hold more than 8 entries -- the lists the start search leaves a whole window of
+// entries in front of a ray in: at least a third of the non-empty texels (counted by the table's build).  Measured, table kernels with
+// the table against plain kernels, ms per prepared launch (profiles/start_table/option_ab_final_kernels.jsonl): torus-1M, 50 % of the
+// non-empty texels, 0.553 -> 0.518 (-6 %); dragon x9 at 1024^3, 16 %, 2.029 -> 2.086 (+3 %); bunny x16, 8 %, 0.602 -> 0.641 (+6 %) --
+// a line through the first two crosses zero at 28 %.  Option starttable: 0 / 1 as asked, 2 = by this rule.
+inline bool start_table_pays(uint32_t nonEmptyTexels, uint32_t texelsOver8) { return nonEmptyTexels != 0u && 3ull * texelsOver8 >= nonEmptyTexels; }
+inline bool start_table_used(int optStartTable, bool pays) { return optStartTable == 1 || (optStartTable == 2 && pays); }
+
 // ---------------------------------------------------------------------------------------------
 // options (dxv_set_option; include/dxv.h documents what they do): the values a context holds, and one row per key -- its name, the
 // values it accepts, the words a refusal ends in, where the value is stored and whether setting it does more than store it
@@ -168,6 +179,8 @@ struct Options {
                              // 1 = from a scene's second launch on (from the first when that launch is large: build_lists), 2 = from the first, 0 = tree walk
     int listres = 0;         // texels per face side; 0 = by triangle count (list_resolution)
     int listedwaves = 0;     // workgroups per CU of the hardware-dispatched lists kernel (8 .. 32), or 0 = by grid and map (voxelize_lists.hip: listed_lds_pad)
+    int starttable = 2;      // the lists' per-texel start table (dxv_dirmap.h: dm_start_word): 0 = scans begin where the start search ends, 1 = no earlier
+                             // than the table's start for the ray, 2 = automatic (default: where it pays -- start_table_pays)
     int coop = 1;            // 1: the lists kernel scans a lone lane's long list with its whole wave (dxv_dirmap.h: trace_reference_dm_from)
     int farmap = 1;          // 1: tree walks and brick-box launches of the reference rule skip the bricks none of whose rays can reach a triangle
     int plan = 2;            // work queue of the lists kernel (live bricks only, built on the device inside the stream): 0 = none (brick box
@@ -261,9 +274,10 @@ constexpr OptionRow kOptions[] = {
     {"morton", kOnOff, "not in {0,1}", &Options::morton, OptionEffect::none},
 };
 constexpr int kOptionCount = (int)(sizeof(kOptions) / sizeof(kOptions[0]));
-// kOptions is the set of keys of the strcmp chain it replaced, and tests/test_policy.py writes that set out key by key.  Keys of what
-// has been added since -- the passes over a frame's finished grid -- are rows of the same kind in a table of their own.
-constexpr OptionRow kGridPassOptions[] = {
+// kOptions is the set of keys of the strcmp chain it replaced, and tests/test_policy.py writes that set out key by key.  Keys added
+// since -- the start table of the lists, the passes over a frame's finished grid -- are rows of the same kind in a table of their own.
+constexpr OptionRow kLaterOptions[] = {
+    {"starttable", in_range(0, 2), "not in {0,1,2}", &Options::starttable, OptionEffect::none},
     {"fillrounds", in_range(0, 64), "not in [0, 64]", &Options::fillrounds, OptionEffect::none},
     {"mdistwalk", kOnOff, "not in {0,1}", &Options::mdistwalk, OptionEffect::none},
     {"morphform", in_range(0, 2), "not in {0,1,2}", &Options::morphform, OptionEffect::none},
@@ -279,7 +293,7 @@ inline const OptionRow* find_option(const char* name)
 {
     for (const OptionRow& row : kOptions)
         if (!strcmp(name, row.name)) return &row;
-    for (const OptionRow& row : kGridPassOptions)
+    for (const OptionRow& row : kLaterOptions)
         if (!strcmp(name, row.name)) return &row;
     return nullptr;
 }

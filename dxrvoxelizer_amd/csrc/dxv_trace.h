@@ -642,6 +642,7 @@ struct SceneView {
     const uint32_t* plCells;    // row lists of the parity rule (parity_lists.hip): (begin, count) per texel of the plR x plR grid over (y, z); NULL: none
     const uint32_t* plEntries;  // triangle slots
     uint32_t plR;
+    const uint32_t* dmStarts;   // start table of the direction-space lists (dxv_dirmap.h: dm_start_word), one word per texel; NULL: none (option starttable)
 };
 
 template <class Stack, int ABL = 0>

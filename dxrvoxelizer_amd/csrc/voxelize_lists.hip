@@ -97,8 +97,9 @@ __device__ __forceinline__ bool queue_item(const QueueLens& q, uint32_t cap, uin
 // k_voxelize<Brick<4,4,4>, 16, 0, TEXELS, 4>; the 64 result bytes of a brick leave as 16 dwords (one per 4-voxel row,
 // assembled from the wave's ballot) instead of 64 bytes.
 // ---------------------------------------------------------------------------------------------
-template <bool TEXELS>
-__global__ __launch_bounds__(64, 6) void k_voxelize_queue(VoxelizeParams p)
+// (the body; STARTS: compiled to read the lists' start table -- dm_ray_start, dxv_dirmap.h -- or as if there were none)
+template <bool TEXELS, bool STARTS>
+__device__ __forceinline__ void queue_bricks(const VoxelizeParams& p)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ int32_t stack[16 * 64];
@@ -181,7 +182,7 @@ __global__ __launch_bounds__(64, 6) void k_voxelize_queue(VoxelizeParams p)
             SceneView sc;                                               // (what the lists' path reads of it)
             sc.nodes = nullptr; sc.wide = nullptr; sc.plCells = nullptr; sc.plEntries = nullptr; sc.plR = 0;
             sc.triPos = pp->scene.triPos; sc.triNrm = pp->scene.triNrm;
-            sc.dmCells = pp->scene.dmCells; sc.dmEntries = pp->scene.dmEntries; sc.dmR = pp->scene.dmR; sc.dmCoop = pp->scene.dmCoop;
+            sc.dmCells = pp->scene.dmCells; sc.dmEntries = pp->scene.dmEntries; sc.dmR = pp->scene.dmR; sc.dmCoop = pp->scene.dmCoop; sc.dmStarts = pp->scene.dmStarts;
 #pragma unroll
             for (int a = 0; a < 3; ++a) { sc.rootLo[a] = pp->scene.rootLo[a]; sc.rootHi[a] = pp->scene.rootHi[a]; }
             // (the brick's set-up, down to origin_leaves_root: written out once more in k_voxelize_listed -- one helper for both changes both kernels' instruction streams)
@@ -199,8 +200,8 @@ __global__ __launch_bounds__(64, 6) void k_voxelize_queue(VoxelizeParams p)
             // raygenMain for the 64 voxels of the brick (voxel_reference<4>, dxv_trace.h, with its first step made by all lanes)
             Ray r;
             ray_origin(N, ix, iy, iz, r.ox, r.oy, r.oz);
-            const DirMapView dm{static_cast<const DirCell*>(sc.dmCells), static_cast<const DirEntry*>(sc.dmEntries), sc.dmR, sc.dmCoop};
-            DirRayStart start = dm_ray_start(r.ox, r.oy, r.oz, dm);
+            const DirMapView dm{static_cast<const DirCell*>(sc.dmCells), static_cast<const DirEntry*>(sc.dmEntries), sc.dmR, sc.dmCoop, sc.dmStarts};
+            DirRayStart start = dm_ray_start<STARTS>(r.ox, r.oy, r.oz, dm);
             wAhead = 0xffffffffu;
             if (ahead) {
                 next = (uint32_t)__builtin_amdgcn_readlane((int)jv, 0);  // the next brick's number
@@ -265,6 +266,9 @@ __global__ __launch_bounds__(64, 6) void k_voxelize_queue(VoxelizeParams p)
     (void)p;
 #endif
 }
+// ... as kernels: for launches whose lists have a start table the launch reads, and for launches without (_plain)
+template <bool TEXELS> __global__ __launch_bounds__(64, 6) void k_voxelize_queue(VoxelizeParams p) { queue_bricks<TEXELS, true>(p); }
+template <bool TEXELS> __global__ __launch_bounds__(64, 6) void k_voxelize_queue_plain(VoxelizeParams p) { queue_bricks<TEXELS, false>(p); }
 
 // The same brick body with one workgroup per queued brick, dispatched by the hardware: for a queue that is launched AGAIN and whose
 // eight lengths the host has read meanwhile (dxv_sync of an earlier launch of the same queue) -- the launch's size is then
@@ -332,8 +336,9 @@ __device__ __forceinline__ void clear_dead_bricks(const VoxelizeParams& p, const
     }
 }
 
-template <bool TEXELS>
-__global__ __launch_bounds__(64, 6) void k_voxelize_listed(VoxelizeParams p, QueueLens lens, ClearShare clr)
+// (the body; STARTS as in queue_bricks)
+template <bool TEXELS, bool STARTS>
+__device__ __forceinline__ void listed_brick(const VoxelizeParams& p, const QueueLens& lens, const ClearShare& clr)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ int32_t stack[(TEXELS ? 20 : 16) * 64];     // per lane: 8 queued triangles of two words (TEXELS: then the closest hit's V, W, det, index)
@@ -345,7 +350,7 @@ __global__ __launch_bounds__(64, 6) void k_voxelize_listed(VoxelizeParams p, Que
                  "s"(lens.heavy[0]), "s"(lens.heavy[1]), "s"(lens.heavy[2]), "s"(lens.heavy[3]), "s"(lens.heavy[4]), "s"(lens.heavy[5]), "s"(lens.heavy[6]),
                  "s"(lens.heavy[7]), "s"(clr.blocks), "s"(clr.where), "s"(clr.live), "s"(gridDim.x), "s"(p.queueSlots), "s"(p.queueCap));
     asm volatile("" :: "s"(p.N), "s"(p.z0), "s"(p.nz), "s"(p.zBlock), "s"(p.zPeriod), "s"(p.zShift), "s"(p.scene.dmCells), "s"(p.scene.dmEntries), "s"(p.scene.dmR),
-                 "s"(p.scene.dmCoop), "s"(p.scene.triPos), "s"(p.grid), "s"(p.scene.rootLo[0]), "s"(p.scene.rootLo[1]), "s"(p.scene.rootLo[2]),
+                 "s"(p.scene.dmCoop), "s"(p.scene.dmStarts), "s"(p.scene.triPos), "s"(p.grid), "s"(p.scene.rootLo[0]), "s"(p.scene.rootLo[1]), "s"(p.scene.rootLo[2]),
                  "s"(p.scene.rootHi[0]), "s"(p.scene.rootHi[1]), "s"(p.scene.rootHi[2]));
     uint32_t wg = blockIdx.x;
     if (clr.blocks) {
@@ -392,8 +397,8 @@ __global__ __launch_bounds__(64, 6) void k_voxelize_listed(VoxelizeParams p, Que
     const uint32_t iz = global_slice(p.z0, nz, p.zBlock, p.zShift, p.zPeriod, lz);
     Ray r;
     ray_origin(N, ix, iy, iz, r.ox, r.oy, r.oz);
-    const DirMapView dm{static_cast<const DirCell*>(sc.dmCells), static_cast<const DirEntry*>(sc.dmEntries), sc.dmR, sc.dmCoop};
-    DirRayStart start = dm_ray_start(r.ox, r.oy, r.oz, dm);
+    const DirMapView dm{static_cast<const DirCell*>(sc.dmCells), static_cast<const DirEntry*>(sc.dmEntries), sc.dmR, sc.dmCoop, sc.dmStarts};
+    DirRayStart start = dm_ray_start<STARTS>(r.ox, r.oy, r.oz, dm);
     if (origin_leaves_root(r.ox, r.oy, r.oz, sc.rootLo, sc.rootHi)) start.live = false;
     Hit best;
     float bestDet = 1.0f;
@@ -429,6 +434,9 @@ __global__ __launch_bounds__(64, 6) void k_voxelize_listed(VoxelizeParams p, Que
     (void)p;
 #endif
 }
+// ... as kernels, like the queue's
+template <bool TEXELS> __global__ __launch_bounds__(64, 6) void k_voxelize_listed(VoxelizeParams p, QueueLens lens, ClearShare clr) { listed_brick<TEXELS, true>(p, lens, clr); }
+template <bool TEXELS> __global__ __launch_bounds__(64, 6) void k_voxelize_listed_plain(VoxelizeParams p, QueueLens lens, ClearShare clr) { listed_brick<TEXELS, false>(p, lens, clr); }
 
 // persistent waves the current device holds at once (occupancy of the kernel x compute units), a multiple of 8.
 // An answer about (device, kernel): the context keeps it (ListsOccupancy, dxv_device.h), nothing here does.
@@ -471,6 +479,18 @@ static uint32_t listed_lds_pad(const VoxelizeParams& p, ListsOccupancy& occ)
     return pad > 0 ? (uint32_t)pad : 0u;
 }
 
+// one workgroup per queued brick (and the clearing ones): the kernel that reads the start table when the launch has one, else the plain one
+static hipError_t launch_listed(const VoxelizeParams& p, const QueueLens& lens, const ClearShare& clr, uint32_t wgs, ListsOccupancy& occ, hipStream_t s)
+{
+    const bool starts = p.scene.dmStarts != nullptr;
+    if (p.texels) { if (starts) k_voxelize_listed<true><<<dim3(wgs), dim3(64), 0, s>>>(p, lens, clr); else k_voxelize_listed_plain<true><<<dim3(wgs), dim3(64), 0, s>>>(p, lens, clr); }
+    else {
+        const uint32_t pad = listed_lds_pad(p, occ);
+        if (starts) k_voxelize_listed<false><<<dim3(wgs), dim3(64), pad, s>>>(p, lens, clr); else k_voxelize_listed_plain<false><<<dim3(wgs), dim3(64), pad, s>>>(p, lens, clr);
+    }
+    return hipGetLastError();
+}
+
 // the sixteen count words of a queue as the host read them (eight lengths, of which heavy) -> kernel argument; returns
 // listedLen = ceil(total / 8): the items of an XCD's equal share (queue_item)
 static uint32_t queue_lens_from(const uint32_t lens16[16], QueueLens& lens)
@@ -491,9 +511,7 @@ hipError_t launch_voxelize_queue(const VoxelizeParams& p, ListsOccupancy& occ, b
     if (!rebuild && listedLen) {
         // the queue as it stands, one workgroup per item of an XCD's equal share (listedLen = ceil(total / 8)) and per XCD
         if (wavesOut) *wavesOut = 8u * listedLen;
-        if (p.texels) k_voxelize_listed<true><<<dim3(8u * listedLen), dim3(64), 0, s>>>(p, lens, ClearShare{nullptr, 0u, 0u});
-        else k_voxelize_listed<false><<<dim3(8u * listedLen), dim3(64), listed_lds_pad(p, occ), s>>>(p, lens, ClearShare{nullptr, 0u, 0u});
-        return hipGetLastError();
+        return launch_listed(p, lens, ClearShare{nullptr, 0u, 0u}, 8u * listedLen, occ, s);
     }
     if (rebuild) {
         if (!p.planClear) {
@@ -509,8 +527,9 @@ hipError_t launch_voxelize_queue(const VoxelizeParams& p, ListsOccupancy& occ, b
     const uint32_t sevenths = p.queueSevenths && p.queueSevenths < 7u ? p.queueSevenths : 7u;
     const uint32_t waves = p.queueWaves ? (p.queueWaves + 7u) & ~7u : (held * sevenths / 7u + 7u) & ~7u;     // (a multiple of 8, at least 8: every head has a home wave)
     if (wavesOut) *wavesOut = waves;
-    if (p.texels) k_voxelize_queue<true><<<dim3(waves), dim3(64), 0, s>>>(p);
-    else k_voxelize_queue<false><<<dim3(waves), dim3(64), 0, s>>>(p);
+    const bool starts = p.scene.dmStarts != nullptr;
+    if (p.texels) { if (starts) k_voxelize_queue<true><<<dim3(waves), dim3(64), 0, s>>>(p); else k_voxelize_queue_plain<true><<<dim3(waves), dim3(64), 0, s>>>(p); }
+    else { if (starts) k_voxelize_queue<false><<<dim3(waves), dim3(64), 0, s>>>(p); else k_voxelize_queue_plain<false><<<dim3(waves), dim3(64), 0, s>>>(p); }
     return hipGetLastError();
 }
 
@@ -553,9 +572,7 @@ hipError_t launch_voxelize_prepared(const VoxelizeParams& p, ListsOccupancy& occ
         if (e != hipSuccess || !listedLen) return e;
     }
     const uint32_t wgs = 8u * listedLen + clr.blocks;
-    if (p.texels) k_voxelize_listed<true><<<dim3(wgs), dim3(64), 0, s>>>(p, lens, clr);
-    else k_voxelize_listed<false><<<dim3(wgs), dim3(64), listed_lds_pad(p, occ), s>>>(p, lens, clr);
-    return hipGetLastError();
+    return launch_listed(p, lens, clr, wgs, occ, s);
 }
 
 } // namespace dxv

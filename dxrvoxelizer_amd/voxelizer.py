@@ -30,6 +30,7 @@ PART_REGION = np.dtype([("root", "<u4"), ("radius_sq", "<u4"), ("voxels", "<u4")
 PART_THROAT = np.dtype([("a", "<u4"), ("b", "<u4"), ("faces", "<u4"), ("neck_sq", "<u4"), ("neck_voxel", "<u4")])
 DBG_SORTED_KEYS, DBG_NODES, DBG_TRI_POS, DBG_TRI_NRM, DBG_PARENTS, DBG_NODES32, DBG_NODES64, DBG_LIST_CELLS, DBG_LIST_ENTRIES, DBG_LIST_MIP = range(10)
 DBG_BRICK_EMPTY, DBG_BRICK_SUMMARY = 10, 11         # the display pass's empty-brick flags and the summaries behind them
+DBG_LIST_STARTS = 12                                # the lists' start table: one word per texel
 
 
 def obj_load(path):
@@ -985,6 +986,7 @@ class Voxelizer:
                   DBG_PARENTS: ((2 * T - 1,), np.uint32), DBG_NODES32: ((st["num_nodes"], 8), np.uint32),
                   DBG_NODES64: ((st["num_nodes"], 16), np.uint32),
                   DBG_LIST_CELLS: ((6 * st["list_res"] ** 2, 4), np.uint32), DBG_LIST_ENTRIES: ((st["list_entries"], 4), np.uint32),
+                  DBG_LIST_STARTS: ((6 * st["list_res"] ** 2,), np.uint32),
                   DBG_LIST_MIP: ((sum(6 * (st["list_res"] >> l) ** 2 for l in range(max(st["list_res"], 1).bit_length())),), np.uint16),
                   DBG_BRICK_EMPTY: (((st["grid_dim"] + 7) // 8,) * 3, np.uint8), DBG_BRICK_SUMMARY: (((st["grid_dim"] + 7) // 8,) * 3, np.uint8)}
         shape, dt = shapes[what]

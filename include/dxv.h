@@ -73,6 +73,9 @@ enum {
     DXV_DBG_BRICK_SUMMARY = 11 /* M^3 bytes behind them: bit0 any voxel of the brick, bit1 any on its x=0 face, bit2 z=0 face,
                                 * bit3 x=0,z=0 edge, bit4 y=0 face, bit5 x=0,y=0 edge, bit6 y=0,z=0 edge, bit7 its corner voxel */
 };
+/* ... and one selector more, of what is derived from the lists: 6 R R x uint32, the lists' start table, one word per texel (made with
+ * the lists, whatever option starttable says).  Named like the enum's members; a macro because the enum is a closed set of twelve. */
+#define DXV_DBG_LIST_STARTS 12
 
 typedef struct dxv_stats {
     uint32_t num_tris, num_verts, num_nodes, tree_height;
@@ -1024,7 +1027,13 @@ DXV_API int dxv_get_stats(const dxv_ctx* ctx, dxv_stats* out);
  *   coop   0|1    the lists kernel: when at most two lanes of a wave are still scanning and the first has 24 entries or more ahead, the whole
  *                 wave scans that ray's list, one entry per lane and round (1, default) -- a brick is as long as its longest list, and a
  *                 short launch (a rank's share) cannot end before its longest brick; 0: every lane scans alone
- *   listedwaves 0|8..32  the hardware-dispatched lists kernel (prepared and kept queues, no texel image) fits eight waves per SIMD: 32
+ *   starttable 0|1|2  the lists' start table, one word per texel made with the lists: from a ray's start radius it says how many entries
+ *                 at the head of the texel's list end in front of the ray, and the scan begins behind them (1); 0: the scan begins where
+ *                 the start search ends, up to 8 entries early; 2 (default): automatic -- 1 where at least a third of the lists'
+ *                 non-empty texels hold more than 8 entries (the word is one more load per ray: it pays where it removes whole scan
+ *                 rounds from most waves), else 0, and 0 for a launch queued behind a list build nobody has waited for yet.  A launch
+ *                 that reads the table runs brick kernels compiled with it, any other the kernels without.  Same grids either way
+ *   listedwaves 0|8..32 the hardware-dispatched lists kernel (prepared and kept queues, no texel image) fits eight waves per SIMD: 32
  *                 single-wave workgroups per CU.  0 (default): all 32 when the grid side is at least 3/4 of the lists' map side (a brick's rays
  *                 fall on neighbouring texels: 512^3 -9 %, 1024^3 -12 % against seven waves), else 28 (256^3 on the 512 map: a brick is spread
  *                 over many texels and the eighth wave costs 7 %); 8 .. 32: held at so many workgroups per CU by LDS the launch does not use
