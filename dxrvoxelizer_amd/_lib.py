@@ -152,6 +152,21 @@ SYMBOLS = {
                                     C.POINTER(C.c_uint32)]),
     "dxv_geodesic_work_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "dxv_geodesic_path": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "dxv_access_async": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_int]),
+    "dxv_access": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_int]),
+    "dxv_access_device_ptr": (C.c_void_p, [C.c_void_p]),
+    "dxv_access_bytes": (C.c_size_t, [C.c_void_p]),
+    "dxv_access_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_access_histogram_bytes": (C.c_size_t, [C.c_void_p]),
+    "dxv_access_histogram_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_intrusion_device_ptr": (C.c_void_p, [C.c_void_p]),
+    "dxv_intrusion_bytes": (C.c_size_t, [C.c_void_p]),
+    "dxv_intrusion_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_intrusion_histogram_bytes": (C.c_size_t, [C.c_void_p]),
+    "dxv_intrusion_histogram_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_access_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                  C.POINTER(C.c_uint32)]),
+    "dxv_access_work_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "dxv_components_select_async": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
     "dxv_components_select": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
     "dxv_components_select_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),

@@ -146,7 +146,7 @@ struct Timer { hipEvent_t e0 = nullptr, e1 = nullptr; bool armed = false; float 
 enum TimerUse { kTimerLaunch, kTimerQueue, kTimerRender, kTimerDistance, kTimerMeshDistance, kTimerIso, kTimerOctree, kTimerComponents, kTimerMorph, kTimerMeasure, kTimerThickness,
                 kTimerThickStage0, kTimerThickStageLast = kTimerThickStage0 + dxv::THICK_STAGES - 1,     // the six stages of a thickness, each a pair of its own
                 kTimerPartition, kTimerPartStage0, kTimerPartStageLast = kTimerPartStage0 + dxv::PART_STAGES - 1,      // a partition and its six stages, likewise
-                kTimerFill, kTimerThin, kTimerGeodesic,
+                kTimerFill, kTimerThin, kTimerGeodesic, kTimerAccess,
                 kTimers,
                 kTimerFirstOperator = kTimerRender, kTimerFirstBatched = kTimerFill };
 
@@ -381,11 +381,35 @@ struct dxv_ctx {
             uint32_t farthest = 0, farthestVoxel = 0xFFFFFFFFu;
             void trim() { scratch.release(); seeds.release(); path.release(); }   // (control block, flags and queue, 6 bytes per 8^3 tile, a list's seeds, a path's words; the map itself stays)
         } geo;
+        // access radius and intrusion map (access.hip; dxv_access_async): the two maps of the frame's grid and their histograms, and the scratch of
+        // their making -- control block, live flags, queue, the radius field and its passes, with the intrusion map a thickness's scratch; the
+        // seeds of a list
+        struct Access : Made {
+            DevBuf<uint32_t> map;            // (cap: voxels) A
+            DevBuf<uint32_t> intrusion;      // (cap: voxels) I, when asked for
+            DevBuf<unsigned long long> hist, histI;      // (cap: bins)
+            DevBuf<uint8_t> scratch;         // (cap: bytes) access_scratch_bytes
+            DevBuf<uint32_t> seeds;          // (cap: indices) the seeds of a list
+            std::vector<uint32_t> list;      // the caller's list, copied before dxv_access_async returns: what the upload reads
+            uint32_t dim = 0, cap = 0;       // grid side and cap_sq of the frame's last maps
+            int of = 0, connectivity = 0;    // ... what they were asked for, for the batches that follow
+            bool wantIntrusion = false;      // ... and whether the intrusion map is made with them
+            uint32_t cull = 0;               // ... option thickcull as it stood at dxv_access_async, for the paint
+            bool pending = false;            // a batch is in the stream whose verdict (fixed point or not) nobody has read yet: the frame's next
+                                             // synchronisation reads it, goes on if need be, and enqueues paint and histograms behind the last (settle_access)
+            uint32_t batch = 0;              // ... rounds per batch (option accessrounds as it stood at dxv_access_async)
+            uint32_t rounds = 0;             // rounds of the frame's last access so far, the confirming one included
+            uint64_t tilesRun = 0;           // ... the tiles its rounds ran, the most of one round, and the rounds with fewer than kGeoSparseTiles
+            uint32_t mostLive = 0, sparseRounds = 0;
+            uint64_t seedsUsed = 0, reached = 0, unreached = 0;     // its tally, as of the frame's last synchronisation
+            uint32_t widest = 0, widestVoxel = 0xFFFFFFFFu;
+            void trim() { scratch.release(); seeds.release(); }     // (control block, flags, queue, fields and passes; the maps and histograms themselves stay)
+        } acc;
         // What a synchronisation of the frame and a launch need to know of all that, without naming an operator.
         // grid_unsettled: the grid may not be final yet -- a fill or a thin whose verdict is not in, an expansion from a caller's tree that can
-        // still report; unsettled: ... or a geodesic, which only reads the grid, has further batches to go in front of whatever comes next.
+        // still report; unsettled: ... or a geodesic or an access, which only read the grid, has further batches to go in front of whatever comes next.
         bool grid_unsettled() const { return fill.pending || thin.pending || oct.expandPending; }
-        bool unsettled() const { return grid_unsettled() || geo.pending; }
+        bool unsettled() const { return grid_unsettled() || geo.pending || acc.pending; }
         // a launch replaces the grid: a fill of it that has not converged yet is dropped (its batch in the stream ends in front of the launch), a
         // thin likewise (it stopped where that batch ended), and a geodesic map of it (stale from here on, nobody can read it)
         void drop_unsettled()
@@ -393,8 +417,9 @@ struct dxv_ctx {
             fill.pending = false;
             if (thin.pending) { thin.pending = false; thin.converged = false; }
             geo.pending = false;
+            acc.pending = false;
         }
-        void trim_products() { dist.trim(); mdist.trim(); fill.trim(); iso.trim(); oct.trim(); comp.trim(); morph.trim(); thin.trim(); thick.trim(); part.trim(); geo.trim(); }
+        void trim_products() { dist.trim(); mdist.trim(); fill.trim(); iso.trim(); oct.trim(); comp.trim(); morph.trim(); thin.trim(); thick.trim(); part.trim(); geo.trim(); acc.trim(); }
     };
     Frame frames[DXV_FRAME_COUNT];
     uint32_t cur = 0;                    // dxv_set_frame
@@ -437,6 +462,7 @@ struct dxv_ctx {
             unsigned long long partPairs[2];             // T of that partition: sizes its throats
             unsigned long long partCount[2];             // mip cells and voxels tested by the search of the frame's last partition
             dxv::GeoControl geoCtl;                      // the control block of the frame's last geodesic batch and the tally behind it
+            dxv::GeoControl accCtl;                      // ... of the frame's last access batch, likewise
         } frame[DXV_FRAME_COUNT];
     };
     Pinned* pin = nullptr;
@@ -591,6 +617,7 @@ int check_interleave(dxv_ctx* c, const char* who, uint32_t N, uint32_t rank, uin
 void read_products(dxv_ctx* c, uint32_t i);                // the counters of the frame's last select, morph and thickness, once its stream has been waited for
 int settle_fill(dxv_ctx* c, uint32_t i);                   // the verdict of the frame's last fill batch; further batches until one has converged (settle_batched)
 int settle_thin(dxv_ctx* c, uint32_t i);                   // ... of the frame's last thin batch; further batches until the fixed point or max_iterations
+int settle_access(dxv_ctx* c, uint32_t i);                 // ... of the frame's last access batch; further batches, then the intrusion map and the histograms
 int settle_geodesic(dxv_ctx* c, uint32_t i);               // ... of the frame's last geodesic batch; further batches until a round finds nothing live
 int settle_expand(dxv_ctx* c, uint32_t i);                 // the verdict of an expansion from a caller's tree
 // dxv_lists.hip

@@ -425,6 +425,23 @@ hipError_t launch_geodesic_batch(uint32_t* map, uint32_t N, int metric, uint32_t
 // ... and the path from `target` down to a seed, by one wave: out = {voxels on the path, 0 or 1: no neighbour continued it}, then min(length,
 // capacity) voxel indices
 hipError_t launch_geodesic_path(const uint32_t* map, uint32_t N, int metric, uint32_t target, uint32_t* out, uint32_t capacity, hipStream_t s);
+// ... and the compaction of a round's live flags alone, for an operator with flags, queue and control block of the same shape (access.hip)
+hipError_t launch_geodesic_compact(uint8_t* live, uint32_t tiles, GeoControl* ctl, uint32_t round, uint32_t* queue, hipStream_t s);
+
+// access.hip -- the access radius inside a whole N^3 grid and its intrusion map (dxv_access.h): A = N^3 uint32, the caller's, and with
+// `intrusion` I likewise; the histograms cap + 1 uint64 each; everything else in scratch = access_scratch_bytes(N, intrusion): a control block,
+// live flags and a queue of the geodesic's shape (GeoControl: word k = the live tiles of round k, then the tally {seeds used, reached,
+// unreached, key}), the word the seeds are counted in, and behind them the radius field F with the scratch of its passes -- with `intrusion`
+// the whole of a thickness's scratch, which begins with F.  access_layout fills a ThickParams for that part (N, F and passes always; the rest
+// with `intrusion`).  launch_access_init: the field, A's first words and the live flags of round 0.  launch_access_batch: `rounds` rounds
+// (1 .. kAccMaxRounds), the first of them round `base` of the call, then the tally.  launch_access_radius, once A has settled: A into F in
+// thick_radius's encoding, for launch_thickness_stage TOP .. HISTOGRAM with W = I.  The grid is read by the field alone.
+size_t access_scratch_bytes(uint32_t N, bool intrusion);
+void access_layout(uint8_t* scratch, uint32_t N, bool intrusion, ThickParams& p);
+hipError_t launch_access_init(const uint8_t* grid, uint32_t N, int of, uint32_t cap, int seedsKind, const void* seeds, uint32_t seedCount, uint32_t* A, uint8_t* scratch, bool intrusion,
+                              hipStream_t s);
+hipError_t launch_access_batch(uint32_t* A, uint32_t N, int of, int connectivity, uint32_t cap, uint8_t* scratch, bool intrusion, uint32_t rounds, uint32_t base, hipStream_t s);
+hipError_t launch_access_radius(const uint32_t* A, uint32_t N, int of, uint8_t* scratch, bool intrusion, hipStream_t s);
 
 // raycast.hip
 struct RayCastCB;

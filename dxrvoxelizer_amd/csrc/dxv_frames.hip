@@ -634,6 +634,7 @@ int sync_frame(dxv_ctx* c, uint32_t i)
     if (settle_fill(c, i)) return 1;
     if (settle_thin(c, i)) return 1;
     if (settle_geodesic(c, i)) return 1;
+    if (settle_access(c, i)) return 1;
     return settle_expand(c, i);
 }
 

@@ -210,6 +210,8 @@ struct Options {
                              // continued where its frame is next synchronised
     int georounds = 0;       // dxv_geodesic*: rounds of one batch (1 .. 64); 0 = kGeoRoundsDefault (dxv_geodesic.h).  Same map: a geodesic that needs more is
                              // continued where its frame is next synchronised
+    int accessrounds = 0;    // dxv_access*: rounds of one batch (1 .. 64); 0 = kAccRoundsDefault (dxv_access.h).  Same maps: an access that needs more is
+                             // continued where its frame is next synchronised
     int morphform = 0;       // dxv_morph*: 0 = by the radius (dxv_morph.h: morph_form), 1 = bit planes, 2 = distance field + threshold.  Same grids.
     int thickcull = 3;       // dxv_thickness*: bit 0 = the Top cull, bit 1 = neighbour domination (dxv_thickness.h).  Same map, same histogram.
     int thickstages = 0;     // dxv_thickness*: 1 = every stage between events of its own and the paint counts its tests and atomics (dxv_thickness_stage_info); measurement
@@ -283,6 +285,7 @@ constexpr OptionRow kLaterOptions[] = {
     {"morphform", in_range(0, 2), "not in {0,1,2}", &Options::morphform, OptionEffect::none},
     {"thinrounds", in_range(0, 64), "not in [0, 64]", &Options::thinrounds, OptionEffect::none},
     {"georounds", in_range(0, 64), "not in [0, 64]", &Options::georounds, OptionEffect::none},
+    {"accessrounds", in_range(0, 64), "not in [0, 64]", &Options::accessrounds, OptionEffect::none},
     {"thickcull", in_range(0, 3), "not in {0,1,2,3}", &Options::thickcull, OptionEffect::none},
     {"thickstages", kOnOff, "not in {0,1}", &Options::thickstages, OptionEffect::none},
     {"partprune", in_range(0, 3), "not in {0,1,2,3}", &Options::partprune, OptionEffect::none},

@@ -1,7 +1,7 @@
 // dxv_products.hip -- what is made of a frame's grid, and what edits it in place: distance field, mesh distance field, isosurface, octree and
-// its expansion, components, their measures and select, thickness, partition, geodesic distance, fill, morph, thin -- the host side of each (the
+// its expansion, components, their measures and select, thickness, partition, geodesic distance, access radius, fill, morph, thin -- the host side of each (the
 // kernels: distance.hip, mesh_distance.hip, isosurface.hip, octree.hip, components.hip, measure.hip, thickness.hip, partition.hip, geodesic.hip,
-// fill.hip, morph.hip, thin.hip), the accessors of what they made, and their halves of a frame's synchronisation.  Each operator has a record in Frame (dxv_ctx.h);
+// access.hip, fill.hip, morph.hip, thin.hip), the accessors of what they made, and their halves of a frame's synchronisation.  Each operator has a record in Frame (dxv_ctx.h);
 // what they share is here, in front of them: the refusals (check_whole_grid, check_current), an operator's first and last steps (begin_operator,
 // end_operator, blocking), the download of a product (download_current) and the loop of the operators that run in batches (settle_batched).
 #include "dxv_ctx.h"
@@ -16,6 +16,7 @@
 #include "dxv_thickness.h"
 #include "dxv_partition.h"
 #include "dxv_geodesic.h"
+#include "dxv_access.h"
 
 using namespace dxv;
 using namespace dxvhost;
@@ -49,6 +50,7 @@ static const ProductText kMeasureText = {"measure", "dxv_measure", "was launched
 static const ProductText kThicknessText = {"thickness map", "dxv_thickness", "was launched or edited again since its thickness map was made: map and histogram are stale"};
 static const ProductText kPartitionText = {"partition", "dxv_partition", "was launched or edited again since its partition was made: labels, table and throats are stale"};
 static const ProductText kGeodesicText = {"geodesic map", "dxv_geodesic", "was launched or edited again since its geodesic map was made: the map is stale"};
+static const ProductText kAccessText = {"access map", "dxv_access", "was launched or edited again since its access map was made: maps and histograms are stale"};
 
 // whether the selected frame has this product to hand out: 0, or 1 with the reason as the message
 static int check_current(const dxv_ctx* c, const char* who, const Frame::Made& made, const ProductText& text)
@@ -239,6 +241,60 @@ int settle_geodesic(dxv_ctx* c, uint32_t i)
             return last;
         },
         [&](hipStream_t fs) { return launch_geodesic_batch(o.map.p, N, o.metric, o.limit, o.scratch.p, o.batch, o.rounds, fs); });
+}
+
+// the access's: the geodesic's loop; behind the confirming round A is final, and what is made of it -- A into the radius field, thickness's
+// stages TOP .. HISTOGRAM with W = the intrusion map, A's own histogram -- is enqueued here and waited for, the timer's second event behind it
+static ThickParams access_params(const Frame::Access& o, uint32_t* W, unsigned long long* hist)
+{
+    ThickParams p{};
+    p.of = o.of; p.cap = o.cap; p.cull = o.cull; p.count = 0u; p.W = W; p.hist = hist;
+    access_layout(o.scratch.p, o.dim, o.wantIntrusion, p);
+    return p;
+}
+static int finish_access(dxv_ctx* c, uint32_t i)
+{
+    Frame& f = c->frames[i];
+    Frame::Access& o = f.acc;
+    const hipStream_t fs = frame_stream(c, i);
+    Timer& t = f.timers[kTimerAccess];
+    DXV_HIP(c, launch_thickness_stage(f.grid.p, access_params(o, o.map.p, o.hist.p), THICK_STAGE_HISTOGRAM, fs));
+    if (o.wantIntrusion) {
+        const ThickParams p = access_params(o, o.intrusion.p, o.histI.p);
+        DXV_HIP(c, launch_access_radius(o.map.p, o.dim, o.of, o.scratch.p, true, fs));
+        for (int stage = THICK_STAGE_TOP; stage < THICK_STAGES; ++stage) DXV_HIP(c, launch_thickness_stage(f.grid.p, p, stage, fs));
+    }
+    if (t.armed) DXV_HIP(c, hipEventRecord(t.e1, fs));
+    DXV_HIP(c, hipEventRecord(f.evEnd, fs));
+    DXV_HIP(c, hipStreamSynchronize(fs));
+    return 0;
+}
+int settle_access(dxv_ctx* c, uint32_t i)
+{
+    Frame& f = c->frames[i];
+    Frame::Access& o = f.acc;
+    GeoControl& ctl = c->pin->frame[i].accCtl;
+    const uint32_t N = o.dim;
+    int finished = 0;
+    const Batched b{"dxv_access", "rounds", kTimerAccess, N, &o.pending, o.batch, &o.batch, &o.rounds, &ctl, o.scratch.p, sizeof(GeoControl)};
+    const int r = settle_batched(c, i, b,
+        [&](uint32_t live, bool last) {
+            for (uint32_t k = 0; k < live; ++k) {                       // what the batch's live rounds ran (dxv_access_work_info)
+                o.tilesRun += ctl.live[k];
+                if (ctl.live[k] > o.mostLive) o.mostLive = ctl.live[k];
+                if (ctl.live[k] < kGeoSparseTiles) ++o.sparseRounds;
+            }
+            o.rounds += last ? live + 1u : o.batch;
+            if (last) {
+                const AccTally tally{ctl.tally[0], ctl.tally[1], ctl.tally[2], ctl.tally[3]};
+                o.seedsUsed = tally.seeds; o.reached = tally.reached; o.unreached = tally.unreached;
+                o.widest = acc_tally_widest(tally); o.widestVoxel = acc_tally_widest_voxel(tally);
+                finished = finish_access(c, i);
+            }
+            return last;
+        },
+        [&](hipStream_t fs) { return launch_access_batch(o.map.p, N, o.of, o.connectivity, o.cap, o.scratch.p, o.wantIntrusion, o.batch, o.rounds, fs); });
+    return r ? r : finished;
 }
 
 // ... and the verdict of an expansion from a caller's tree (sync_launch has read the word): an index that could not be followed left empty
@@ -1066,6 +1122,168 @@ int dxv_geodesic_work_info(dxv_ctx* c, uint64_t* tiles_run, uint32_t* most_live_
     if (tiles_run) *tiles_run = f.geo.tilesRun;
     if (most_live_tiles) *most_live_tiles = f.geo.mostLive;
     if (sparse_rounds) *sparse_rounds = f.geo.sparseRounds;
+    return 0;
+}
+
+// The access radius inside the selected frame's grid and its intrusion map (access.hip; dxv_access.h has the rule's routines), enqueued on the
+// frame's stream behind whatever it holds, under dxv_render_async's host-wait rule and the geodesic's discipline: the radius field, the init,
+// ONE batch of rounds, the tally, the batch's control block into page-locked words, the frame's end event.  Whether the batch reached the fixed
+// point is read where the frame is next synchronised (settle_access), which also makes the intrusion map and the histograms behind the last
+// batch.  Everything is refused before anything is enqueued or allocated; the grid is only read.
+int dxv_access_async(dxv_ctx* c, int of, int connectivity, uint32_t cap_sq, int seeds_kind, const void* seeds, uint32_t seed_count, int want_intrusion)
+{
+    if (!c) return 1;
+    if (of != DXV_COMP_SOLID && of != DXV_COMP_EMPTY) return fail(c, "dxv_access: unknown kind %d (DXV_COMP_SOLID = 0, DXV_COMP_EMPTY = 1)", of);
+    if (!acc_connectivity(connectivity)) return fail(c, "dxv_access: connectivity %d is neither 6 nor 26", connectivity);
+    if (cap_sq < kThickMinCapSq || cap_sq > kThickMaxCapSq) return fail(c, "dxv_access: cap_sq %u is not in [%u, %u]", cap_sq, kThickMinCapSq, kThickMaxCapSq);
+    if (seeds_kind != DXV_GEO_SEEDS_BORDER && seeds_kind != DXV_GEO_SEEDS_LIST && seeds_kind != DXV_GEO_SEEDS_MASK)
+        return fail(c, "dxv_access: unknown seed kind %d (DXV_GEO_SEEDS_BORDER = 0, DXV_GEO_SEEDS_LIST = 1, DXV_GEO_SEEDS_MASK = 2)", seeds_kind);
+    if (seeds_kind == DXV_GEO_SEEDS_LIST && seed_count && !seeds) return fail(c, "dxv_access: a list of %u seeds at NULL", seed_count);
+    if (seeds_kind == DXV_GEO_SEEDS_MASK && !seeds) return fail(c, "dxv_access: the seed mask is NULL");
+    if (check_whole_grid(c, "dxv_access")) return 1;
+    Frame& f = cur_frame(c);
+    const uint32_t N = f.grid_dim;
+    if (N > kAccMaxN) return fail(c, "dxv_access: a grid of %u^3 voxels; at most %u^3 (a centre's linear index must fit 30 bits)", N, kAccMaxN);
+    const size_t voxels = (size_t)N * N * N;
+    if (seeds_kind == DXV_GEO_SEEDS_LIST) {
+        const uint32_t* list = static_cast<const uint32_t*>(seeds);
+        for (uint32_t k = 0; k < seed_count; ++k)
+            if (list[k] >= voxels) return fail(c, "dxv_access: seed %u is voxel %u, outside the grid of %u^3 = %zu voxels", k, list[k], N, voxels);
+    }
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (seeds_kind == DXV_GEO_SEEDS_MASK) {
+        size_t room = 0;
+        const int r = check_device_range(c, "dxv_access", seeds, voxels, &room);
+        if (r == 2) return fail(c, "dxv_access: the seed mask has %zu bytes from %p on, the grid has %zu voxels", room, seeds, voxels);
+        if (r) return 1;
+    }
+    if (settle_frame_launch(c)) return 1;                               // (begin_operator's steps, the device in front of the range check: a pending fill, thin, expansion, geodesic or access of the frame first)
+    const hipStream_t fs = cur_stream(c);
+    Frame::Access& o = f.acc;
+    const bool intrusion = want_intrusion != 0;
+    const size_t scratch = access_scratch_bytes(N, intrusion);
+    o.version = 0; o.have = false;
+    DXV_HIP(c, o.map.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
+    DXV_HIP(c, o.hist.reserve(kThickMaxCapSq + 1u, align256(thickness_histogram_bytes(kThickMaxCapSq)), fs));
+    if (intrusion) {
+        DXV_HIP(c, o.intrusion.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
+        DXV_HIP(c, o.histI.reserve(kThickMaxCapSq + 1u, align256(thickness_histogram_bytes(kThickMaxCapSq)), fs));
+    }
+    DXV_HIP(c, o.scratch.reserve(scratch, scratch, fs));
+    const void* deviceSeeds = seeds;
+    if (seeds_kind == DXV_GEO_SEEDS_LIST) {
+        // the frame's own copy of the list (no access of the frame is in flight: settle_frame_launch), uploaded from there
+        const uint32_t* list = static_cast<const uint32_t*>(seeds);
+        o.list.assign(list, list + seed_count);
+        deviceSeeds = nullptr;
+        if (seed_count) {
+            DXV_HIP(c, o.seeds.reserve(seed_count, align256((size_t)seed_count * sizeof(uint32_t)), fs));
+            DXV_HIP(c, hipMemcpyAsync(o.seeds.p, o.list.data(), (size_t)seed_count * sizeof(uint32_t), hipMemcpyHostToDevice, fs));
+            deviceSeeds = o.seeds.p;
+        }
+    }
+    o.dim = N; o.cap = cap_sq; o.of = of; o.connectivity = connectivity; o.wantIntrusion = intrusion; o.cull = (uint32_t)c->opt.thickcull;
+    o.batch = c->opt.accessrounds ? (uint32_t)c->opt.accessrounds : kAccRoundsDefault;
+    o.rounds = 0; o.tilesRun = 0; o.mostLive = 0; o.sparseRounds = 0;
+    DXV_HIP(c, timer_begin(f.timers[kTimerAccess], c->opt.events != 0, fs));
+    DXV_HIP(c, launch_access_init(f.grid.p, N, of, cap_sq, seeds_kind, deviceSeeds, seed_count, o.map.p, o.scratch.p, intrusion, fs));
+    DXV_HIP(c, launch_access_batch(o.map.p, N, of, connectivity, cap_sq, o.scratch.p, intrusion, o.batch, 0u, fs));
+    if (end_operator(c, f, fs, &f.timers[kTimerAccess], &cur_pinned(c).accCtl, o.scratch.p, sizeof(GeoControl))) return 1;
+    o.pending = true;
+    o.have = true; o.version = f.gridVersion;
+    return 0;
+}
+
+int dxv_access(dxv_ctx* c, int of, int connectivity, uint32_t cap_sq, int seeds_kind, const void* seeds, uint32_t seed_count, int want_intrusion)
+{
+    return blocking(c, dxv_access_async(c, of, connectivity, cap_sq, seeds_kind, seeds, seed_count, want_intrusion));
+}
+
+const void* dxv_access_device_ptr(const dxv_ctx* c)
+{
+    if (!c || check_current(c, "dxv_access_device_ptr", cur_frame(c).acc, kAccessText)) return nullptr;
+    return cur_frame(c).acc.map.p;
+}
+size_t dxv_access_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame::Access& a = cur_frame(c).acc;
+    return a.current(cur_frame(c)) ? (size_t)a.dim * a.dim * a.dim * sizeof(uint32_t) : 0;
+}
+int dxv_access_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || check_current(c, "dxv_access_download", cur_frame(c).acc, kAccessText)) return 1;
+    return download_current(c, "dxv_access_download", cur_frame(c).acc.map.p, dxv_access_bytes(c), host, bytes);
+}
+size_t dxv_access_histogram_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame::Access& a = cur_frame(c).acc;
+    return a.current(cur_frame(c)) ? thickness_histogram_bytes(a.cap) : 0;
+}
+int dxv_access_histogram_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || check_current(c, "dxv_access_histogram_download", cur_frame(c).acc, kAccessText)) return 1;
+    return download_current(c, "dxv_access_histogram_download", cur_frame(c).acc.hist.p, dxv_access_histogram_bytes(c), host, bytes);
+}
+
+// the intrusion map's accessors: the access map's refusals, and one more for a map made without it
+static int check_intrusion(const dxv_ctx* c, const char* who)
+{
+    if (check_current(c, who, cur_frame(c).acc, kAccessText)) return 1;
+    if (!cur_frame(c).acc.wantIntrusion)
+        return fail(const_cast<dxv_ctx*>(c), "%s: the access map of frame %u was made without its intrusion map (call dxv_access with want_intrusion != 0)", who, c->cur);
+    return 0;
+}
+const void* dxv_intrusion_device_ptr(const dxv_ctx* c)
+{
+    if (!c || check_intrusion(c, "dxv_intrusion_device_ptr")) return nullptr;
+    return cur_frame(c).acc.intrusion.p;
+}
+size_t dxv_intrusion_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame::Access& a = cur_frame(c).acc;
+    return a.current(cur_frame(c)) && a.wantIntrusion ? (size_t)a.dim * a.dim * a.dim * sizeof(uint32_t) : 0;
+}
+int dxv_intrusion_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || check_intrusion(c, "dxv_intrusion_download")) return 1;
+    return download_current(c, "dxv_intrusion_download", cur_frame(c).acc.intrusion.p, dxv_intrusion_bytes(c), host, bytes);
+}
+size_t dxv_intrusion_histogram_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame::Access& a = cur_frame(c).acc;
+    return a.current(cur_frame(c)) && a.wantIntrusion ? thickness_histogram_bytes(a.cap) : 0;
+}
+int dxv_intrusion_histogram_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || check_intrusion(c, "dxv_intrusion_histogram_download")) return 1;
+    return download_current(c, "dxv_intrusion_histogram_download", cur_frame(c).acc.histI.p, dxv_intrusion_histogram_bytes(c), host, bytes);
+}
+
+int dxv_access_info(dxv_ctx* c, float* ms, uint32_t* rounds, uint64_t* seeds_used, uint64_t* reached, uint64_t* unreached, uint32_t* widest, uint32_t* widest_voxel)
+{
+    if (!c || check_current(c, "dxv_access_info", cur_frame(c).acc, kAccessText)) return 1;
+    const Frame& f = cur_frame(c);
+    if (ms) *ms = f.timers[kTimerAccess].ms;
+    if (rounds) *rounds = f.acc.rounds;
+    if (seeds_used) *seeds_used = f.acc.seedsUsed;
+    if (reached) *reached = f.acc.reached;
+    if (unreached) *unreached = f.acc.unreached;
+    if (widest) *widest = f.acc.widest;
+    if (widest_voxel) *widest_voxel = f.acc.widestVoxel;
+    return 0;
+}
+
+int dxv_access_work_info(dxv_ctx* c, uint64_t* tiles_run, uint32_t* most_live_tiles, uint32_t* sparse_rounds)
+{
+    if (!c || check_current(c, "dxv_access_work_info", cur_frame(c).acc, kAccessText)) return 1;
+    const Frame& f = cur_frame(c);
+    if (tiles_run) *tiles_run = f.acc.tilesRun;
+    if (most_live_tiles) *most_live_tiles = f.acc.mostLive;
+    if (sparse_rounds) *sparse_rounds = f.acc.sparseRounds;
     return 0;
 }
 

@@ -213,6 +213,14 @@ hipError_t launch_geodesic_batch(uint32_t* map, uint32_t N, int metric, uint32_t
     return hipGetLastError();
 }
 
+// k_geo_compact for whoever keeps live flags, a queue and a control block of the same shape (access.hip)
+hipError_t launch_geodesic_compact(uint8_t* live, uint32_t tiles, GeoControl* ctl, uint32_t round, uint32_t* queue, hipStream_t s)
+{
+    if (!live || !ctl || !queue || !tiles || round >= kGeoMaxRounds) return hipErrorInvalidValue;
+    k_geo_compact<<<(tiles + 255u) / 256u, 256, 0, s>>>(live, tiles, ctl, round, queue);
+    return hipGetLastError();
+}
+
 hipError_t launch_geodesic_path(const uint32_t* map, uint32_t N, int metric, uint32_t target, uint32_t* out, uint32_t capacity, hipStream_t s)
 {
     if (!map || !out || !geo_valid(N, metric) || target >= N * N * N) return hipErrorInvalidValue;

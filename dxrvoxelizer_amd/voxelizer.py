@@ -98,6 +98,18 @@ def thickness_voxels(field):
     return np.where(W > 0, np.float32(2) * np.sqrt(W.astype(np.float32)) - np.float32(1), np.float32(0)).astype(np.float32)
 
 
+def intrusion_curve(histogram, members=None):
+    """The intrusion (drainage) curve of an IntrusionHistogram: (diameter float32 [capSq], share float64 [capSq]) -- for t = 1 .. capSq the
+    diameter in voxels of the ball of squared radius t (thickness_voxels) and the share of the members with I >= t: how much of the space a
+    ball that large gets into.  members: the members reached or not (AccessInfo: reached + unreached); by default the voxels the histogram
+    counts above 0, the members something gets to.  Pure numpy."""
+    h = np.asarray(histogram, np.uint64).astype(np.float64)
+    t = np.arange(1, len(h), dtype=np.uint32)
+    total = float(members) if members is not None else float(h[1:].sum())
+    at_least = np.cumsum(h[:0:-1])[::-1]                                # at_least[t - 1] = the voxels with I >= t
+    return thickness_voxels(t), (at_least / total if total else np.zeros(len(t)))
+
+
 class Voxelizer:
     """bool-returning calls of the reference become exceptions (DxvError) here."""
 
@@ -814,6 +826,100 @@ class Voxelizer:
         out = np.empty(length.value, np.uint32)
         self._check(self._lib.dxv_geodesic_path(self._ctx, int(target), out.ctypes.data_as(C.c_void_p), len(out), C.byref(length)))
         return out[:length.value]
+
+    # ---- what can get in: the access radius and the intrusion map of the frame's grid ---------------------
+    def _seed_args(self, who, seeds):
+        """(kind, pointer, count, what must stay alive until the call returns) of Geodesic's kinds of seeds, for Access"""
+        if isinstance(seeds, str):
+            if seeds != "border":
+                raise DxvError(f"{who}: unknown seeds {seeds!r} (\"border\", an index array, an [N, N, N] array or a device tensor)")
+            return GEO_SEEDS_BORDER, None, 0, None
+        if hasattr(seeds, "data_ptr"):                                  # a device tensor: a mask read in place
+            import torch
+            if not seeds.is_cuda or seeds.dtype not in (torch.uint8, torch.bool) or not seeds.is_contiguous():
+                raise DxvError(f"{who}: a seed tensor must be a contiguous uint8 or bool tensor on the device")
+            n = self.stats()["grid_dim"]
+            if seeds.numel() != n ** 3:
+                raise DxvError(f"{who}: the seed tensor has {seeds.numel()} elements, the grid has {n ** 3} voxels")
+            torch.cuda.current_stream(seeds.device).synchronize()       # (its writer is ordered before the frame's stream reads it)
+            return GEO_SEEDS_MASK, C.c_void_p(seeds.data_ptr()), 0, seeds
+        a = np.asarray(seeds)
+        if a.ndim == 3:
+            a = np.flatnonzero(a)
+        if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+            raise DxvError(f"{who}: a seed index is outside the grid")
+        a = np.ascontiguousarray(a.reshape(-1), np.uint32)
+        return GEO_SEEDS_LIST, a.ctypes.data_as(C.c_void_p) if a.size else None, int(a.size), a
+
+    def Access(self, of=COMP_EMPTY, connectivity=26, capSq=4096, seeds="border", intrusion=True, sync=True, frameIndex=None):
+        """The access radius inside the selected frame's whole grid on the device, and its intrusion map (dxv_access / dxv_access_async;
+        include/dxv.h has the rule): per member voxel -- of = COMP_SOLID the non-zero voxels, COMP_EMPTY the zero ones -- A = the squared radius
+        of the largest voxel-centred ball whose centre can travel from a seed to the voxel without leaving the members (steps over the 6 or the
+        26 neighbours; R = min(D2, capSq) as in Thickness), and with intrusion=True I = the largest such ball that covers the voxel; 0 on
+        the others and where nothing gets to; 2 <= capSq <= 4096.  seeds as in Geodesic.  The grid and the frame's other products stay as they
+        are.  sync=True returns (AccessField(), IntrusionField() or None); sync=False only enqueues one batch of rounds -- the intrusion map
+        is made where the frame is next synchronised, and a seed tensor is read on the frame's stream, as by Geodesic: with sync=False the
+        caller keeps it alive and unchanged until the frame has been synchronised (a list is copied before the call returns)."""
+        if frameIndex is not None:
+            self.SetFrame(frameIndex)
+        fn = self._lib.dxv_access if sync else self._lib.dxv_access_async
+        kind, ptr, count, keep = self._seed_args("Access", seeds)
+        self._check(fn(self._ctx, int(of), int(connectivity), int(capSq), kind, ptr, count, 1 if intrusion else 0))
+        del keep
+        return (self.AccessField(), self.IntrusionField() if intrusion else None) if sync else True
+
+    def _access_array(self, which, what, dtype):
+        nbytes = getattr(self._lib, f"dxv_{which}_bytes")(self._ctx)
+        if not nbytes:
+            getattr(self._lib, "dxv_intrusion_device_ptr" if which.startswith("intrusion") else "dxv_access_device_ptr")(self._ctx)   # (sets the message)
+            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
+        if what == "map":
+            n = round((nbytes // 4) ** (1.0 / 3.0))
+            out = np.empty((n, n, n), dtype)
+        else:
+            out = np.empty(nbytes // 8, dtype)
+        self._check(getattr(self._lib, f"dxv_{which}_download")(self._ctx, out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+    def AccessField(self):
+        """numpy copy uint32 [N, N, N] (z, y, x) of the selected frame's access map, squared radii (dxv_access_download; synchronises the frame)."""
+        return self._access_array("access", "map", np.uint32)
+
+    def AccessHistogram(self):
+        """numpy copy uint64 [capSq + 1] of the access map's histogram: bin v the voxels with A == v (dxv_access_histogram_download)."""
+        return self._access_array("access_histogram", "histogram", np.uint64)
+
+    def IntrusionField(self):
+        """numpy copy uint32 [N, N, N] (z, y, x) of the selected frame's intrusion map, squared radii (dxv_intrusion_download; synchronises the
+        frame); an error for an Access made with intrusion=False.  thickness_voxels turns it into voxels."""
+        return self._access_array("intrusion", "map", np.uint32)
+
+    def IntrusionHistogram(self):
+        """numpy copy uint64 [capSq + 1] of the intrusion map's histogram (dxv_intrusion_histogram_download); intrusion_curve reads it."""
+        return self._access_array("intrusion_histogram", "histogram", np.uint64)
+
+    def access_device_ptrs(self):
+        """(access map, intrusion map or None) device pointers of the selected frame, 4 * N^3 bytes each, for consumers on the GPU (exact after Sync)."""
+        ptr = self._lib.dxv_access_device_ptr(self._ctx)
+        if not ptr:
+            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
+        return ptr, self._lib.dxv_intrusion_device_ptr(self._ctx) if self._lib.dxv_intrusion_bytes(self._ctx) else None
+
+    def AccessInfo(self):
+        """{ms, rounds, seeds_used, reached, unreached, widest, widest_voxel} of the selected frame's last access as of its last Sync
+        (dxv_access_info).  rounds may differ from run to run; nothing reached: widest 0 at voxel 0xFFFFFFFF."""
+        ms, rounds, widest, voxel = C.c_float(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        used, reached, unreached = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self._lib.dxv_access_info(self._ctx, C.byref(ms), C.byref(rounds), C.byref(used), C.byref(reached), C.byref(unreached), C.byref(widest), C.byref(voxel)))
+        return {"ms": ms.value, "rounds": rounds.value, "seeds_used": used.value, "reached": reached.value, "unreached": unreached.value, "widest": widest.value,
+                "widest_voxel": voxel.value}
+
+    def access_work_info(self):
+        """{tiles_run, most_live_tiles, sparse_rounds} of the selected frame's last access as of its last Sync (dxv_access_work_info), as
+        geodesic_work_info.  They differ from run to run."""
+        tiles, most, sparse = C.c_uint64(), C.c_uint32(), C.c_uint32()
+        self._check(self._lib.dxv_access_work_info(self._ctx, C.byref(tiles), C.byref(most), C.byref(sparse)))
+        return {"tiles_run": tiles.value, "most_live_tiles": most.value, "sparse_rounds": sparse.value}
 
     def SelectComponents(self, rule, arg=0, sync=True):
         """Edit the selected frame's grid in place from its current labels (dxv_components_select / _async): the voxels of every component

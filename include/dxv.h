@@ -942,6 +942,80 @@ DXV_API int dxv_geodesic_work_info(dxv_ctx* ctx, uint64_t* tiles_run, uint32_t* 
  * the farthest voxel is the usual double sweep for a skeleton's length or a pore network's diameter. */
 DXV_API int dxv_geodesic_path(dxv_ctx* ctx, uint32_t target, uint32_t* host_path, uint32_t capacity, uint32_t* length);
 
+/* Access radius and intrusion map: what can reach a voxel from outside, and how large may it be (no reference counterpart).  dxv_thickness is
+ * not access-limited -- a wide chamber behind a narrow throat reads "wide", although nothing wider than the throat can get in.  This operator
+ * gives, per member voxel, the squared radius of the largest voxel-centred ball whose centre can travel from a seed to it without leaving the
+ * members, and the largest such ball that covers it: the mercury-intrusion / drainage curve of a porous sample, whether powder or a cleaning
+ * tool of a given radius reaches a cavity of a printed part, the percolation radius between two faces.  It replaces the host loop
+ * dxv_morph(ERODE, r), dxv_components, dxv_components_select, dxv_morph(DILATE, r) once per radius.
+ * Input: the WHOLE grid of the selected frame's last launch, in any mode.  Bytes written through dxv_grid_device_ptr count too.  solid(p) iff
+ * byte(p) != 0.  Only voxels inside the grid exist.
+ * of = DXV_COMP_SOLID (0) or DXV_COMP_EMPTY (1) picks the members M.  connectivity is 6 or 26, dxv_components' adjacency: an edge or corner
+ * step does not ask about the voxels it squeezes between.  2 <= cap_sq <= 4096 (dxv_thickness's range).  The seed set S is one of
+ * dxv_geodesic's three kinds -- DXV_GEO_SEEDS_BORDER, a host LIST of indices, a device MASK --, under the same checks and with the same
+ * lifetimes; seeds that are not members are ignored: seeds_used of dxv_access_info counts the others, |S n M|.
+ *     R(c) = min(D2(c), cap_sq) for c in M, 0 elsewhere                                        (dxv_thickness's R)
+ *     A(c) = max over paths s = p0, p1, ..., pk = c of members, p0 in S n M, consecutive voxels adjacent under `connectivity`,
+ *            of  min over the path of R(pi)                       (0 when no such path exists, and for c not in M)
+ *     I(p) = max { A(c) : c in M, |p - c|^2 < A(c) }             for p in M (0 when the set is empty), 0 for p not in M
+ * A is the access map, I the intrusion map: the access-limited counterpart of dxv_thickness's W.  On seeds A = R.  A <= R, and A <= I <= W on
+ * reached members.  Zero means "no member, or not reached"; the tally tells the two apart.  {A > 0} is the reached set of dxv_geodesic for the
+ * same seeds, 6 with DXV_GEO_FACES and 26 with DXV_GEO_CHAMFER.  With every member a seed, A == R and I == W, histogram included.
+ * The cap: A under cap_sq equals min(A under a larger cap, cap_sq).  This holds for A and NOT for I: a ball of the larger cap covers voxels
+ * that no ball of the smaller one does, so I under a cap is not the larger cap's I cut off.
+ * Second, independent statements of the same rule:
+ *     {A >= t} is the union of the components of {R >= t} under `connectivity` that hold a seed s with R(s) >= t
+ *     I(p) = 1 + max { r2 in 0 .. cap_sq - 1 : p in DILATE_r2({A >= r2 + 1}) }, with dxv_morph's closed ball and DILATE_0 the identity; 0 when
+ *            there is no such r2 -- the erode / keep-connected / dilate loop, stated once
+ * Output: the access map, one uint32 per voxel, element (iz * N + iy) * N + ix like the grid, 4 N^3 bytes; with want_intrusion != 0 the
+ * intrusion map, of the same shape; one histogram per map of cap_sq + 1 uint64, bin v the voxels with value v; and a tally by one
+ * deterministic reduction on the device: the seeds used, the members reached, the members unreached, `widest` = the greatest A and
+ * `widest_voxel` = the smallest index that holds it (nothing reached: 0 and 0xFFFFFFFF).  A is the least fixed point of a monotone relaxation
+ * from a fixed start and I is a set function of A: the device's bytes equal a restatement byte for byte, in whatever order its workgroups run.
+ * dxv_access_async -- ENQUEUED on the frame's stream behind whatever it holds; returns without waiting.  The grid is read and none of the
+ * frame's other products is written.
+ *  - The call enqueues the radius field, A's first words, ONE batch of rounds (option accessrounds) and the tally; whether the batch reached
+ *    the fixed point is read where the frame is next synchronised, further batches are enqueued and waited for there until a round finds
+ *    nothing to do, and the synchronisation that sees that round enqueues the intrusion map and the histograms and waits for them.  After
+ *    dxv_sync both maps are exact; on the frame's stream alone only A is, and only if one batch was enough -- the intrusion map and the
+ *    histograms do not exist before the frame is synchronised.  A map that has not settled after N^3 rounds is an error with a message.
+ *  - The host waits only under dxv_render_async's rule; a pending fill, thin, expansion, geodesic or access of the frame is settled first.
+ *  - Checked on the host before anything is enqueued, each an error with a message: of, connectivity, cap_sq and the seed kind are valid; a
+ *    LIST has a non-NULL pointer unless its count is 0, and no index is out of range; a MASK pointer is non-NULL and device memory of N^3
+ *    bytes; the frame has been launched; its last launch was the whole grid; grid_dim is even, 2 .. 1024.
+ *  - Maps, histograms and scratch belong to the frame: frames run side by side.  A map is 4 bytes per voxel; the scratch -- the geodesic's
+ *    control block, flags and queue, the radius field and its passes (10 bytes per voxel), with the intrusion map a thickness's scratch (15
+ *    bytes per voxel), the seeds of a list -- goes back with dxv_trim, maps and histograms stay.
+ *  - Maps and histograms are STALE once the frame's grid version moves -- it is launched, filled, morphed, thinned, expanded or selected
+ *    again: pointers, sizes, downloads and infos then fail with a message.
+ *  - Option events = 1 (default): bracketed by the frame's own events, read at the frame's dxv_sync.
+ * dxv_access -- the same + dxv_sync. */
+DXV_API int dxv_access_async(dxv_ctx* ctx, int of, int connectivity, uint32_t cap_sq, int seeds_kind, const void* seeds, uint32_t seed_count, int want_intrusion);
+DXV_API int dxv_access(dxv_ctx* ctx, int of, int connectivity, uint32_t cap_sq, int seeds_kind, const void* seeds, uint32_t seed_count, int want_intrusion);
+/* The access map on the device (exact after dxv_sync) and its size, 4 * grid_dim^3 bytes; its histogram, (cap_sq + 1) * 8 bytes.  NULL / 0
+ * (the pointer with a message) before the frame's first access or when it is stale.  The downloads synchronise the frame first; bytes must be
+ * the size above. */
+DXV_API const void* dxv_access_device_ptr(const dxv_ctx* ctx);
+DXV_API size_t dxv_access_bytes(const dxv_ctx* ctx);
+DXV_API int dxv_access_download(dxv_ctx* ctx, void* host, size_t bytes);
+DXV_API size_t dxv_access_histogram_bytes(const dxv_ctx* ctx);
+DXV_API int dxv_access_histogram_download(dxv_ctx* ctx, void* host, size_t bytes);
+/* ... and the intrusion map and its histogram, under the same rules; they also fail with a message (sizes: 0) when the frame's last access
+ * was made with want_intrusion = 0.  The map exists once the frame has been synchronised. */
+DXV_API const void* dxv_intrusion_device_ptr(const dxv_ctx* ctx);
+DXV_API size_t dxv_intrusion_bytes(const dxv_ctx* ctx);
+DXV_API int dxv_intrusion_download(dxv_ctx* ctx, void* host, size_t bytes);
+DXV_API size_t dxv_intrusion_histogram_bytes(const dxv_ctx* ctx);
+DXV_API int dxv_intrusion_histogram_download(dxv_ctx* ctx, void* host, size_t bytes);
+/* The selected frame's last access as of the frame's last dxv_sync: device time in milliseconds from its field to its last histogram (HIP
+ * events, option events = 1; else 0), its rounds with the confirming one, and the tally.  `rounds` may differ from run to run: a tile reads its
+ * neighbours' words while they are being raised -- never what the maps hold.  Any pointer may be NULL; fails with a message before the
+ * frame's first access or when the map is stale. */
+DXV_API int dxv_access_info(dxv_ctx* ctx, float* ms, uint32_t* rounds, uint64_t* seeds_used, uint64_t* reached, uint64_t* unreached, uint32_t* widest, uint32_t* widest_voxel);
+/* ... and, for measurements, what its rounds did, as dxv_geodesic_work_info: the live 8^3 tiles summed over the rounds, the most of one round,
+ * and the rounds with fewer than 1024 live tiles.  These differ from run to run. */
+DXV_API int dxv_access_work_info(dxv_ctx* ctx, uint64_t* tiles_run, uint32_t* most_live_tiles, uint32_t* sparse_rounds);
+
 /* Multi-GPU: the built scene (nodes + triangle data) as one relocatable device blob, so that
  * rank 0 builds once and the host layer broadcasts it (RCCL over xGMI) to the other ranks.
  * export copies the blob into caller-provided DEVICE memory; import adopts a blob from DEVICE
@@ -1069,6 +1143,8 @@ DXV_API int dxv_get_stats(const dxv_ctx* ctx, dxv_stats* out);
  *                 synchronised.  Same grids.
  *   georounds 0..64  dxv_geodesic*: rounds of one batch (0, default: 16); a geodesic that needs more is continued where its frame is next
  *                 synchronised.  Same map.
+ *   accessrounds 0..64  dxv_access*: rounds of one batch (0, default: 16); an access that needs more is continued where its frame is next
+ *                 synchronised.  Same maps.
  *   morphform 0..2  dxv_morph*: 0 (default) = by the radius: bit planes up to radius_sq 1024, above it the distance field of the grid and its
  *                 threshold, per half; 1 / 2 = always the planes / always the field (measurement, cross-check).  Same grids.
  *   thickcull 0..3  dxv_thickness*: which centres are left out of the paint because their ball cannot raise anything: bit 0 = those whose ball

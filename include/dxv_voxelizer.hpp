@@ -406,6 +406,63 @@ public:
 		return dxv_geodesic_path(m_ctx, target, path.data(), length, &length) == 0 && length == path.size();
 	}
 
+	// What can get in (dxv_access / dxv_access_async; include/dxv.h has the rule): per member voxel the access map A -- the squared radius of the
+	// largest voxel-centred ball whose centre can travel from a seed to the voxel without leaving the members, steps over the 6 or the 26
+	// neighbours -- and with intrusion the intrusion map I, the largest such ball that covers the voxel; 0 elsewhere and where nothing gets to.
+	// Seeds as for Geodesic.  sync = false only enqueues one batch of rounds: the intrusion map is made where the frame is next synchronised.
+	bool Access(int of = DXV_COMP_EMPTY, int connectivity = 26, uint32_t capSq = 4096, bool intrusion = true, bool sync = true)
+	{
+		return m_ctx && (sync ? dxv_access(m_ctx, of, connectivity, capSq, DXV_GEO_SEEDS_BORDER, nullptr, 0, intrusion) : dxv_access_async(m_ctx, of, connectivity, capSq, DXV_GEO_SEEDS_BORDER, nullptr, 0, intrusion)) == 0;
+	}
+	bool Access(int of, int connectivity, uint32_t capSq, const std::vector<uint32_t>& seeds, bool intrusion = true, bool sync = true)
+	{
+		const uint32_t count = static_cast<uint32_t>(seeds.size());
+		return m_ctx && (sync ? dxv_access(m_ctx, of, connectivity, capSq, DXV_GEO_SEEDS_LIST, seeds.data(), count, intrusion) : dxv_access_async(m_ctx, of, connectivity, capSq, DXV_GEO_SEEDS_LIST, seeds.data(), count, intrusion)) == 0;
+	}
+	bool AccessFromDeviceMask(int of, int connectivity, uint32_t capSq, const void* deviceMask, bool intrusion = true, bool sync = true)
+	{
+		return m_ctx && (sync ? dxv_access(m_ctx, of, connectivity, capSq, DXV_GEO_SEEDS_MASK, deviceMask, 0, intrusion) : dxv_access_async(m_ctx, of, connectivity, capSq, DXV_GEO_SEEDS_MASK, deviceMask, 0, intrusion)) == 0;
+	}
+	const void* DeviceAccess() const { return m_ctx ? dxv_access_device_ptr(m_ctx) : nullptr; }
+	const void* DeviceIntrusion() const { return m_ctx ? dxv_intrusion_device_ptr(m_ctx) : nullptr; }
+	bool AccessField(std::vector<uint32_t>& field)
+	{
+		if (!m_ctx) return setError("AccessField before Init");
+		const size_t bytes = dxv_access_bytes(m_ctx);
+		if (!bytes) return false;
+		field.resize(bytes / sizeof(uint32_t));
+		return dxv_access_download(m_ctx, field.data(), bytes) == 0;
+	}
+	bool AccessHistogram(std::vector<uint64_t>& histogram)
+	{
+		if (!m_ctx) return setError("AccessHistogram before Init");
+		const size_t bytes = dxv_access_histogram_bytes(m_ctx);
+		if (!bytes) return false;
+		histogram.resize(bytes / sizeof(uint64_t));
+		return dxv_access_histogram_download(m_ctx, histogram.data(), bytes) == 0;
+	}
+	bool IntrusionField(std::vector<uint32_t>& field)
+	{
+		if (!m_ctx) return setError("IntrusionField before Init");
+		const size_t bytes = dxv_intrusion_bytes(m_ctx);
+		if (!bytes) return false;
+		field.resize(bytes / sizeof(uint32_t));
+		return dxv_intrusion_download(m_ctx, field.data(), bytes) == 0;
+	}
+	bool IntrusionHistogram(std::vector<uint64_t>& histogram)
+	{
+		if (!m_ctx) return setError("IntrusionHistogram before Init");
+		const size_t bytes = dxv_intrusion_histogram_bytes(m_ctx);
+		if (!bytes) return false;
+		histogram.resize(bytes / sizeof(uint64_t));
+		return dxv_intrusion_histogram_download(m_ctx, histogram.data(), bytes) == 0;
+	}
+	struct AccessTally { float ms = 0.0f; uint32_t rounds = 0; uint64_t seedsUsed = 0, reached = 0, unreached = 0; uint32_t widest = 0, widestVoxel = 0xFFFFFFFFu; };
+	bool AccessInfo(AccessTally& t)
+	{
+		return m_ctx && dxv_access_info(m_ctx, &t.ms, &t.rounds, &t.seedsUsed, &t.reached, &t.unreached, &t.widest, &t.widestVoxel) == 0;
+	}
+
 	// The exterior flood fill of that frame's whole grid, in place (dxv_fill / dxv_fill_async): DXV_FILL_SOLID leaves the walls and everything
 	// they enclose, DXV_FILL_INTERIOR the enclosed voxels alone.  Voxelize(gridDim, SURFACE) && Fill() is the solid of a mesh whose
 	// normals and watertightness cannot be trusted.  Refers to the frame last selected; sync = false only enqueues (WaitFrame reports).
