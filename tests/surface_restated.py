@@ -4,11 +4,17 @@ Test helper, not collected.  `surface_grid(tris, N)` gives the uint8 [z, y, x] g
 least one closed triangle, decided by the float32 separating-axis test exactly as DESIGN §2 orders it (every intermediate is checked
 to be float32); `dtype=np.float64` is its twin for cross-checks.  The candidates are only a superset: each triangle's box in voxel
 units widened by one voxel; a triangle with a large box is walked column by column over its dominant axis plane, each column over
-the depths its plane reaches (widened by one voxel), so that 1024^3 grids with huge triangles stay cheap.
+the depths its plane reaches (widened by one voxel), so that 1024^3 grids with huge triangles stay cheap.  The walk follows the EXACT
+plane; the float32 test of a triangle with a vertex far outside the grid does not (its products are rounded at the far vertex's
+magnitude), so such a triangle (FAR_LIMIT) tests its whole box instead.
+
+`box_grid(tris, N)` is the truth for the candidate enumerations: the same test on every voxel of `kernel_box` (csrc/dxv_surface.h:
+surface_box restated), with no column walk and no plane reasoning.
 """
 import numpy as np
 
 F32 = np.float32
+FAR_LIMIT = 2.0 ** 17      # a triangle with |coordinate| * N above this tests its whole box (csrc/dxv_surface.h: kSurfaceFar, derived there)
 
 
 def bound_of(vb):
@@ -139,7 +145,8 @@ def surface_grid(tris, N, dtype=F32, chunk=1 << 22, large=4096):
     lo, hi, empty = _boxes(tris, N)
     ext = np.where(empty[:, None], 0, hi - lo + 1)
     cnt = ext.prod(1)
-    small = np.nonzero((cnt > 0) & (cnt <= large))[0]
+    far = np.abs(tris.astype(np.float64)).max((1, 2)) * N > FAR_LIMIT
+    small = np.nonzero((cnt > 0) & ((cnt <= large) | far))[0]
     # small boxes: every voxel of the box, a batch of triangles at a time
     ends = np.cumsum(cnt[small])
     start = 0
@@ -156,7 +163,7 @@ def surface_grid(tris, N, dtype=F32, chunk=1 << 22, large=4096):
         iz = lo[tid, 2] + off // (ex * ey)
         _test_and_set(grid, tris, tid, ix, iy, iz, N, dtype)
         start = stop
-    for t in np.nonzero(cnt > large)[0]:
+    for t in np.nonzero((cnt > large) & ~far)[0]:
         ix, iy, iz = _columns(tris[t], lo[t], hi[t], N)
         for s in range(0, len(ix), chunk):
             sl = slice(s, s + chunk)
@@ -171,6 +178,47 @@ def brute_grid(tris, N, dtype=F32):
     iz, iy, ix = (a.ravel() for a in np.meshgrid(np.arange(N), np.arange(N), np.arange(N), indexing="ij"))
     for t in range(len(tris)):
         _test_and_set(grid, tris, np.full(len(ix), t), ix, iy, iz, N, dtype)
+    return grid
+
+
+def kernel_box(tri, N):
+    """surface_box (csrc/dxv_surface.h) restated in float32: lo, hi per axis (x, y, z), or None when it is empty."""
+    tri = np.asarray(tri, F32)
+    if not np.isfinite(tri).all() or np.abs(tri).max() >= F32(1e30):
+        return None
+    half, m = F32(0.5) * F32(N), F32(0.0625)
+    lo, hi = [], []
+    for k in range(3):
+        mn, mx = tri[:, k].min(), tri[:, k].max()
+        u0 = (F32(1) - mx) * half if k == 1 else (mn + F32(1)) * half
+        u1 = (F32(1) - mn) * half if k == 1 else (mx + F32(1)) * half
+        u0 = min(max(np.floor(u0 - m), F32(-1)), F32(N))
+        u1 = min(max(np.floor(u1 + m), F32(-1)), F32(N))
+        lo.append(0 if u0 < 0 else int(u0))
+        hi.append(N - 1 if u1 > N - 1 else int(u1))
+        if lo[k] > hi[k]:
+            return None
+    return lo, hi
+
+
+def box_grid(tris, N, counts=None):
+    """uint8 [N, N, N] (z, y, x): the float32 test applied to EVERY voxel of every triangle's kernel_box -- no walk, no plane.
+    counts: a list that receives (voxels in the box, voxels accepted) per triangle."""
+    tris = np.ascontiguousarray(tris, F32).reshape(-1, 3, 3)
+    grid = np.zeros((N, N, N), np.uint8)
+    for t, tri in enumerate(tris):
+        box = kernel_box(tri, N)
+        if box is None:
+            if counts is not None:
+                counts.append((0, 0))
+            continue
+        lo, hi = box
+        iz, iy, ix = (a.ravel() for a in np.meshgrid(*(np.arange(lo[k], hi[k] + 1) for k in (2, 1, 0)), indexing="ij"))
+        one = np.zeros_like(grid)
+        _test_and_set(one, tris, np.full(len(ix), t), ix, iy, iz, N, F32)
+        grid |= one
+        if counts is not None:
+            counts.append((len(ix), int(one.sum())))
     return grid
 
 

@@ -150,24 +150,7 @@ def test_surface_kernels_use_no_scratch(dxvlib):
         assert v["vgprs"] <= 128, (k, v)
 
 
-# ---- the kernel's candidate box (csrc/dxv_surface.h: surface_box, 1/16 voxel of margin) ---------------------------------------
-def kernel_box(tri, N):
-    """surface_box restated in float32: lo, hi per axis (x, y, z), or None when it is empty."""
-    half, m = F(0.5) * F(N), F(0.0625)
-    lo, hi = [], []
-    for k in range(3):
-        mn, mx = tri[:, k].min(), tri[:, k].max()
-        u0 = (F(1) - mx) * half if k == 1 else (mn + F(1)) * half
-        u1 = (F(1) - mn) * half if k == 1 else (mx + F(1)) * half
-        u0 = min(max(np.floor(u0 - m), F(-1)), F(N))
-        u1 = min(max(np.floor(u1 + m), F(-1)), F(N))
-        lo.append(0 if u0 < 0 else int(u0))
-        hi.append(N - 1 if u1 > N - 1 else int(u1))
-        if lo[k] > hi[k]:
-            return None
-    return lo, hi
-
-
+# ---- the kernel's candidate box (csrc/dxv_surface.h: surface_box, 1/16 voxel of margin; restated as surface_restated.kernel_box) -------
 def near_face_triangles(rng, N, count):
     """triangles whose extreme coordinates sit on voxel faces or a float32 ulp either side of them, some with a vertex far outside
     the grid (a refitted mesh may leave its build's bound), some entirely outside"""
@@ -200,7 +183,7 @@ def test_kernel_candidate_box_holds_every_accepted_voxel(N):
     seen = 0
     for t in near_face_triangles(rng, N, 240):
         got = np.argwhere(sr.surface_grid(t[None], N))                       # (z, y, x) of the voxels the test accepts
-        box = kernel_box(t, N)
+        box = sr.kernel_box(t, N)
         if box is None:
             assert len(got) == 0, t
             continue
