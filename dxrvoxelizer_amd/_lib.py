@@ -143,6 +143,21 @@ SYMBOLS = {
     "dxv_partition_throats_bytes": (C.c_size_t, [C.c_void_p]),
     "dxv_partition_throats_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "dxv_partition_stage_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "dxv_skeleton_async": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "dxv_skeleton": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "dxv_skeleton_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "dxv_skeleton_labels_device_ptr": (C.c_void_p, [C.c_void_p]),
+    "dxv_skeleton_labels_bytes": (C.c_size_t, [C.c_void_p]),
+    "dxv_skeleton_labels_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_skeleton_nodes_device_ptr": (C.c_void_p, [C.c_void_p]),
+    "dxv_skeleton_nodes_bytes": (C.c_size_t, [C.c_void_p]),
+    "dxv_skeleton_nodes_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_skeleton_branches_device_ptr": (C.c_void_p, [C.c_void_p]),
+    "dxv_skeleton_branches_bytes": (C.c_size_t, [C.c_void_p]),
+    "dxv_skeleton_branches_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_skeleton_prune_async": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "dxv_skeleton_prune": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "dxv_skeleton_prune_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "dxv_geodesic_async": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32]),
     "dxv_geodesic": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32]),
     "dxv_geodesic_device_ptr": (C.c_void_p, [C.c_void_p]),

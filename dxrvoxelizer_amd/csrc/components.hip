@@ -23,6 +23,8 @@
 //   k_comp_keep, k_comp_edit
 //                      dxv_components_select: one kernel over the table (keep flags, the 64-bit maximum of voxels << 32 | ~number, three
 //                      counters), one pass over labels and grid.
+// launch_comp_merge and launch_comp_compress run k_comp_merge and k_comp_compress alone, for skeleton.hip, which labels two disjoint masks over one
+// parent array.
 // Every loop ends because an index strictly falls (comp_find, comp_root, comp_union) or bits leave a word (the run loops).  No loop waits for
 // another workgroup, no kernel here uses scratch memory or LDS.
 #include "dxv_device.h"
@@ -294,6 +296,23 @@ hipError_t launch_comp_pack(const uint8_t* grid, uint32_t N, int of, uint64_t* m
     if (N < 2u || N > kCompMaxN || (N & 1u) || (of != COMP_SOLID && of != COMP_EMPTY) || !grid || !mask) return hipErrorInvalidValue;
     const size_t maskBytes = fill_mask_words(N) * 8u;
     k_comp_pack<<<(uint32_t)((maskBytes + 255u) / 256u), 256, 0, s>>>(grid, N, of, reinterpret_cast<uint8_t*>(mask));
+    return hipGetLastError();
+}
+
+// the merge alone, and the compress alone: the unions of a mask over a parent array the caller has initialised from it (skeleton.hip: two
+// disjoint masks over one array), then every entry its root
+hipError_t launch_comp_merge(const uint64_t* mask, uint32_t N, uint32_t connectivity, uint32_t* parent, hipStream_t s)
+{
+    if (N < 2u || N > kCompMaxN || (N & 1u) || (connectivity != 6u && connectivity != 26u) || !mask || !parent) return hipErrorInvalidValue;
+    const uint32_t maskWords = N * N * fill_row_words(N);
+    k_comp_merge<<<(maskWords + 255u) / 256u, 256, 0, s>>>(mask, N, connectivity, parent, maskWords);
+    return hipGetLastError();
+}
+hipError_t launch_comp_compress(uint32_t* parent, uint32_t N, hipStream_t s)
+{
+    if (N < 2u || N > kCompMaxN || (N & 1u) || !parent) return hipErrorInvalidValue;
+    const uint32_t total = comp_total(N);
+    k_comp_compress<<<(uint32_t)(((size_t)total + 255u) / 256u), 256, 0, s>>>(parent, total);
     return hipGetLastError();
 }
 

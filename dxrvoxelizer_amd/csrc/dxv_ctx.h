@@ -146,6 +146,7 @@ struct Timer { hipEvent_t e0 = nullptr, e1 = nullptr; bool armed = false; float 
 enum TimerUse { kTimerLaunch, kTimerQueue, kTimerRender, kTimerDistance, kTimerMeshDistance, kTimerIso, kTimerOctree, kTimerComponents, kTimerMorph, kTimerMeasure, kTimerThickness,
                 kTimerThickStage0, kTimerThickStageLast = kTimerThickStage0 + dxv::THICK_STAGES - 1,     // the six stages of a thickness, each a pair of its own
                 kTimerPartition, kTimerPartStage0, kTimerPartStageLast = kTimerPartStage0 + dxv::PART_STAGES - 1,      // a partition and its six stages, likewise
+                kTimerSkeleton,
                 kTimerFill, kTimerThin, kTimerGeodesic, kTimerAccess,
                 kTimers,
                 kTimerFirstOperator = kTimerRender, kTimerFirstBatched = kTimerFill };
@@ -405,6 +406,25 @@ struct dxv_ctx {
             uint32_t widest = 0, widestVoxel = 0xFFFFFFFFu;
             void trim() { scratch.release(); seeds.release(); }     // (control block, flags, queue, fields and passes; the maps and histograms themselves stay)
         } acc;
+        // skeleton graph (skeleton.hip; dxv_skeleton_async): labels and the two tables of the frame's grid, the scratch of their making (four bits
+        // per voxel of masks, the root bits, the counts, the scan's sums) and the work sized by K and B (the nodes' stats, then a prune's flags)
+        struct Skeleton : Made {
+            DevBuf<uint32_t> labels;         // (cap: voxels)
+            DevBuf<uint8_t> nodes;           // (cap: nodes) 32 bytes each
+            DevBuf<uint8_t> branches;        // (cap: branches) 48 bytes each
+            DevBuf<uint8_t> scratch;         // (cap: bytes) skel_scratch_bytes
+            DevBuf<uint8_t> work;            // (cap: bytes) the nodes' stats of a build, then the counters and flags of a prune
+            uint32_t dim = 0;                // grid side of the frame's last skeleton
+            uint32_t nodeCount = 0, branchCount = 0;
+            uint64_t endVoxels = 0, curveVoxels = 0, junctionVoxels = 0;
+            // the edit from the tables (dxv_skeleton_prune_async)
+            struct Prune {
+                bool pending = false;        // its two counters are on their way into page-locked words: the frame's next synchronisation reads them
+                uint32_t branches = 0;       // of the frame's last prune, as of its last synchronisation
+                uint64_t voxels = 0;
+            } prune;
+            void trim() { scratch.release(); work.release(); }   // (the masks, bits, counts and stats; labels and tables themselves stay)
+        } skel;
         // What a synchronisation of the frame and a launch need to know of all that, without naming an operator.
         // grid_unsettled: the grid may not be final yet -- a fill or a thin whose verdict is not in, an expansion from a caller's tree that can
         // still report; unsettled: ... or a geodesic or an access, which only read the grid, has further batches to go in front of whatever comes next.
@@ -419,7 +439,7 @@ struct dxv_ctx {
             geo.pending = false;
             acc.pending = false;
         }
-        void trim_products() { dist.trim(); mdist.trim(); fill.trim(); iso.trim(); oct.trim(); comp.trim(); morph.trim(); thin.trim(); thick.trim(); part.trim(); geo.trim(); acc.trim(); }
+        void trim_products() { dist.trim(); mdist.trim(); fill.trim(); iso.trim(); oct.trim(); comp.trim(); morph.trim(); thin.trim(); thick.trim(); part.trim(); geo.trim(); acc.trim(); skel.trim(); }
     };
     Frame frames[DXV_FRAME_COUNT];
     uint32_t cur = 0;                    // dxv_set_frame
@@ -463,6 +483,8 @@ struct dxv_ctx {
             unsigned long long partCount[2];             // mip cells and voxels tested by the search of the frame's last partition
             dxv::GeoControl geoCtl;                      // the control block of the frame's last geodesic batch and the tally behind it
             dxv::GeoControl accCtl;                      // ... of the frame's last access batch, likewise
+            unsigned long long skelTotals[5];            // K, B and the end, curve and junction voxels of the skeleton the frame is making: K and B size its tables
+            unsigned long long skelPrune[2];             // branches and voxels removed by the frame's last prune
         } frame[DXV_FRAME_COUNT];
     };
     Pinned* pin = nullptr;

@@ -314,6 +314,41 @@ hipError_t launch_comp_select(uint8_t* grid, uint32_t N, int of, const uint32_t*
                               hipStream_t s);
 // ... its pack alone: grid -> the member mask (the first block of the scratch), for what reads the mask of a labelling after dxv_trim
 hipError_t launch_comp_pack(const uint8_t* grid, uint32_t N, int of, uint64_t* mask, hipStream_t s);
+// ... and its merge and its compress alone, for an operator that labels masks of its own over a parent array it has initialised (skeleton.hip)
+hipError_t launch_comp_merge(const uint64_t* mask, uint32_t N, uint32_t connectivity, uint32_t* parent, hipStream_t s);
+hipError_t launch_comp_compress(uint32_t* parent, uint32_t N, hipStream_t s);
+
+// skeleton.hip -- the skeleton graph of a whole N^3 grid (dxv_skeleton.h): pack, classify, init, merge and compress (the components'), number; ONE
+// read of {K, B} by the caller; the tables.  scratch: skel_scratch_bytes(N) -- four masks of a bit per voxel (member, node, curve, end), the two
+// kinds' root bits, a pair of counts per 64 voxels, the scan's block sums, {K, B, end voxels, curve voxels, junction voxels}.  labels: N^3 uint32;
+// nodes: 32 bytes each; branches: 48 bytes each; stats: 40 bytes per node of scratch.  The grid is only read.
+struct SkelNode;
+struct SkelBranch;
+struct SkelNodeStats;
+struct SkelParams {
+    const uint8_t* grid;    // N^3 bytes, element (iz * N + iy) * N + ix; a voxel is a member iff its byte is non-zero
+    uint32_t N;
+    const uint32_t* weights;      // N^3 uint32 of the caller's, or nullptr
+    uint32_t* labels;       // parent during the build, then the labels
+    uint64_t *member, *node, *curve, *ends;     // skel_scratch_layout fills these and the five below
+    uint64_t *nodeRoots, *curveRoots;
+    uint32_t* counts;
+    unsigned long long* sums;
+    unsigned long long* totals;   // {K, B, end voxels, curve voxels, junction voxels}
+    SkelNodeStats* stats;
+    SkelNode* nodes;
+    SkelBranch* branches;
+};
+size_t skel_scratch_bytes(uint32_t N);
+void skel_scratch_layout(uint8_t* scratch, uint32_t N, SkelParams& p);
+hipError_t launch_skel_classify(const SkelParams& p, hipStream_t s);
+hipError_t launch_skel_label(const SkelParams& p, hipStream_t s);
+hipError_t launch_skel_stats(const SkelParams& p, uint32_t K, uint32_t B, hipStream_t s);
+// dxv_skeleton_prune: `work` -- skel_prune_bytes(K, B) -- holds {branches removed, voxels removed}, then a flag per branch and per node
+size_t skel_prune_bytes(uint32_t K, uint32_t B);
+unsigned long long* skel_prune_counters(uint8_t* work);
+hipError_t launch_skel_prune(uint8_t* grid, uint32_t N, const uint32_t* labels, const SkelNode* nodes, uint32_t K, const SkelBranch* branches, uint32_t B, uint32_t maxLen345,
+                             uint8_t* work, hipStream_t s);
 
 // measure.hip -- the integral measures of the K components of a labelling (dxv_measure.h): table = measure_table_bytes(K) = (K + 1) * 96 bytes,
 // record 0 the sum of the others; mask: the labelling's member mask; labels: N^3 uint32.  Nothing but the table is written.

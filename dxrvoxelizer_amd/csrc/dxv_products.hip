@@ -1,7 +1,7 @@
 // dxv_products.hip -- what is made of a frame's grid, and what edits it in place: distance field, mesh distance field, isosurface, octree and
-// its expansion, components, their measures and select, thickness, partition, geodesic distance, access radius, fill, morph, thin -- the host side of each (the
+// its expansion, components, their measures and select, thickness, partition, skeleton graph and its prune, geodesic distance, access radius, fill, morph, thin -- the host side of each (the
 // kernels: distance.hip, mesh_distance.hip, isosurface.hip, octree.hip, components.hip, measure.hip, thickness.hip, partition.hip, geodesic.hip,
-// access.hip, fill.hip, morph.hip, thin.hip), the accessors of what they made, and their halves of a frame's synchronisation.  Each operator has a record in Frame (dxv_ctx.h);
+// access.hip, skeleton.hip, fill.hip, morph.hip, thin.hip), the accessors of what they made, and their halves of a frame's synchronisation.  Each operator has a record in Frame (dxv_ctx.h);
 // what they share is here, in front of them: the refusals (check_whole_grid, check_current), an operator's first and last steps (begin_operator,
 // end_operator, blocking), the download of a product (download_current) and the loop of the operators that run in batches (settle_batched).
 #include "dxv_ctx.h"
@@ -17,6 +17,7 @@
 #include "dxv_partition.h"
 #include "dxv_geodesic.h"
 #include "dxv_access.h"
+#include "dxv_skeleton.h"
 
 using namespace dxv;
 using namespace dxvhost;
@@ -50,6 +51,7 @@ static const ProductText kMeasureText = {"measure", "dxv_measure", "was launched
 static const ProductText kThicknessText = {"thickness map", "dxv_thickness", "was launched or edited again since its thickness map was made: map and histogram are stale"};
 static const ProductText kPartitionText = {"partition", "dxv_partition", "was launched or edited again since its partition was made: labels, table and throats are stale"};
 static const ProductText kGeodesicText = {"geodesic map", "dxv_geodesic", "was launched or edited again since its geodesic map was made: the map is stale"};
+static const ProductText kSkeletonText = {"skeleton", "dxv_skeleton", "was launched or edited again since its skeleton was made: labels and tables are stale"};
 static const ProductText kAccessText = {"access map", "dxv_access", "was launched or edited again since its access map was made: maps and histograms are stale"};
 
 // whether the selected frame has this product to hand out: 0, or 1 with the reason as the message
@@ -132,6 +134,11 @@ void read_products(dxv_ctx* c, uint32_t i)
         f.part.cellsTested = pin.partCount[0];
         f.part.voxelsTested = pin.partCount[1];
         f.part.pending = false;
+    }
+    if (f.skel.prune.pending) {                                         // the counters of the frame's last prune
+        f.skel.prune.branches = (uint32_t)pin.skelPrune[0];
+        f.skel.prune.voxels = pin.skelPrune[1];
+        f.skel.prune.pending = false;
     }
 }
 
@@ -1016,6 +1023,160 @@ int dxv_partition_stage_info(dxv_ctx* c, float ms[6], uint64_t* cells_tested, ui
     for (int stage = 0; stage < PART_STAGES; ++stage) ms[stage] = f.timers[kTimerPartStage0 + stage].ms;
     if (cells_tested) *cells_tested = f.part.cellsTested;
     if (voxels_tested) *voxels_tested = f.part.voxelsTested;
+    return 0;
+}
+
+// The skeleton graph of the selected frame's grid (skeleton.hip; dxv_skeleton.h has the rule's routines), enqueued on the frame's stream behind
+// whatever it holds, under dxv_render_async's host-wait rule: pack, classify, init, the components' merge over the node mask and over the curve
+// mask, compress and the numbering, {K, B} and the three voxel counts into page-locked words and the one wait for them -- the pattern of
+// dxv_components_async: the tables cannot be sized without them --, then the stats kernels and the frame's end event, which nobody waits for here.
+// Everything is refused before anything is enqueued or allocated; the grid and the caller's weights are only read.
+int dxv_skeleton_async(dxv_ctx* c, const void* device_weights)
+{
+    if (!c) return 1;
+    if (check_whole_grid(c, "dxv_skeleton")) return 1;
+    Frame& f = cur_frame(c);
+    const uint32_t N = f.grid_dim;
+    if (!skel_valid(N)) return fail(c, "dxv_skeleton: a grid of %u^3 voxels; at most %u^3 (bit 31 of a label is its kind)", N, kSkelMaxN);
+    const size_t voxels = (size_t)N * N * N;
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (device_weights) {
+        if (reinterpret_cast<uintptr_t>(device_weights) % 4) return fail(c, "dxv_skeleton: weights at %p: need a 4-byte aligned pointer", device_weights);
+        size_t room = 0;
+        if (const int r = check_device_range(c, "dxv_skeleton", device_weights, voxels * sizeof(uint32_t), &room))
+            return r == 1 ? 1 : fail(c, "dxv_skeleton: the weights of %u^3 voxels need %zu bytes, the allocation behind %p has %zu", N, voxels * sizeof(uint32_t), device_weights, room);
+    }
+    if (settle_frame_launch(c)) return 1;                               // (begin_operator's steps, the device in front of the range check: a pending fill or thin of the frame first)
+    const hipStream_t fs = cur_stream(c);
+    Frame::Skeleton& o = f.skel;
+    const size_t scratch = skel_scratch_bytes(N);
+    DXV_HIP(c, o.scratch.reserve(scratch, scratch, fs));
+    o.version = 0;                                                      // (the build writes into the frame's label buffer: what it held is gone)
+    DXV_HIP(c, o.labels.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
+    SkelParams p{};
+    p.grid = f.grid.p; p.weights = static_cast<const uint32_t*>(device_weights); p.labels = o.labels.p;
+    skel_scratch_layout(o.scratch.p, N, p);
+    unsigned long long* totals = cur_pinned(c).skelTotals;
+    DXV_HIP(c, timer_begin(f.timers[kTimerSkeleton], c->opt.events != 0, fs));
+    DXV_HIP(c, launch_skel_label(p, fs));
+    DXV_HIP(c, hipMemcpyAsync(totals, p.totals, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipStreamSynchronize(fs));
+    const uint32_t K = (uint32_t)totals[0], B = (uint32_t)totals[1];
+    if (K | B) {
+        if (K) {
+            DXV_HIP(c, o.nodes.reserve(K, align256((size_t)K * sizeof(SkelNode)), fs));
+            DXV_HIP(c, o.work.reserve((size_t)K * sizeof(SkelNodeStats), align256((size_t)K * sizeof(SkelNodeStats)), fs));
+        }
+        if (B) DXV_HIP(c, o.branches.reserve(B, align256((size_t)B * sizeof(SkelBranch)), fs));
+        p.nodes = reinterpret_cast<SkelNode*>(o.nodes.p);
+        p.branches = reinterpret_cast<SkelBranch*>(o.branches.p);
+        p.stats = reinterpret_cast<SkelNodeStats*>(o.work.p);
+        DXV_HIP(c, launch_skel_stats(p, K, B, fs));
+    }
+    if (end_operator(c, f, fs, &f.timers[kTimerSkeleton])) return 1;
+    o.dim = N; o.nodeCount = K; o.branchCount = B; o.endVoxels = totals[2]; o.curveVoxels = totals[3]; o.junctionVoxels = totals[4];
+    o.have = true; o.version = f.gridVersion;
+    return 0;
+}
+
+int dxv_skeleton(dxv_ctx* c, const void* device_weights) { return blocking(c, dxv_skeleton_async(c, device_weights)); }
+
+int dxv_skeleton_info(dxv_ctx* c, float* ms, uint32_t* nodes, uint32_t* branches, uint64_t* end_voxels, uint64_t* curve_voxels, uint64_t* junction_voxels)
+{
+    if (!c) return 1;
+    const Frame& f = cur_frame(c);
+    const bool current = f.skel.current(f);
+    if (ms) *ms = f.timers[kTimerSkeleton].ms;
+    if (nodes) *nodes = current ? f.skel.nodeCount : 0u;
+    if (branches) *branches = current ? f.skel.branchCount : 0u;
+    if (end_voxels) *end_voxels = current ? f.skel.endVoxels : 0u;
+    if (curve_voxels) *curve_voxels = current ? f.skel.curveVoxels : 0u;
+    if (junction_voxels) *junction_voxels = current ? f.skel.junctionVoxels : 0u;
+    return 0;
+}
+
+const void* dxv_skeleton_labels_device_ptr(const dxv_ctx* c)
+{
+    if (!c || check_current(c, "dxv_skeleton_labels_device_ptr", cur_frame(c).skel, kSkeletonText)) return nullptr;
+    return cur_frame(c).skel.labels.p;
+}
+size_t dxv_skeleton_labels_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame::Skeleton& o = cur_frame(c).skel;
+    return o.current(cur_frame(c)) ? (size_t)o.dim * o.dim * o.dim * sizeof(uint32_t) : 0;
+}
+int dxv_skeleton_labels_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || check_current(c, "dxv_skeleton_labels_download", cur_frame(c).skel, kSkeletonText)) return 1;
+    return download_current(c, "dxv_skeleton_labels_download", cur_frame(c).skel.labels.p, dxv_skeleton_labels_bytes(c), host, bytes);
+}
+const void* dxv_skeleton_nodes_device_ptr(const dxv_ctx* c)
+{
+    if (!c || check_current(c, "dxv_skeleton_nodes_device_ptr", cur_frame(c).skel, kSkeletonText)) return nullptr;
+    return cur_frame(c).skel.nodeCount ? cur_frame(c).skel.nodes.p : nullptr;
+}
+size_t dxv_skeleton_nodes_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame::Skeleton& o = cur_frame(c).skel;
+    return o.current(cur_frame(c)) ? (size_t)o.nodeCount * sizeof(SkelNode) : 0;
+}
+int dxv_skeleton_nodes_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || check_current(c, "dxv_skeleton_nodes_download", cur_frame(c).skel, kSkeletonText)) return 1;
+    return download_current(c, "dxv_skeleton_nodes_download", cur_frame(c).skel.nodes.p, dxv_skeleton_nodes_bytes(c), host, bytes);
+}
+const void* dxv_skeleton_branches_device_ptr(const dxv_ctx* c)
+{
+    if (!c || check_current(c, "dxv_skeleton_branches_device_ptr", cur_frame(c).skel, kSkeletonText)) return nullptr;
+    return cur_frame(c).skel.branchCount ? cur_frame(c).skel.branches.p : nullptr;
+}
+size_t dxv_skeleton_branches_bytes(const dxv_ctx* c)
+{
+    if (!c) return 0;
+    const Frame::Skeleton& o = cur_frame(c).skel;
+    return o.current(cur_frame(c)) ? (size_t)o.branchCount * sizeof(SkelBranch) : 0;
+}
+int dxv_skeleton_branches_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || check_current(c, "dxv_skeleton_branches_download", cur_frame(c).skel, kSkeletonText)) return 1;
+    return download_current(c, "dxv_skeleton_branches_download", cur_frame(c).skel.branches.p, dxv_skeleton_branches_bytes(c), host, bytes);
+}
+
+// The selected frame's grid edited from its skeleton (skeleton.hip: k_skel_prune_mark, k_skel_prune_edit), in place, enqueued on the frame's
+// stream behind whatever it holds -- under dxv_render_async's host-wait rule and dxv_fill_async's rules for the grid.  Labels and tables are what
+// it reads: dxv_trim has left them.  The two counters go into page-locked words and are read where the frame is next synchronised.
+int dxv_skeleton_prune_async(dxv_ctx* c, uint32_t max_len345)
+{
+    if (!c) return 1;
+    if (check_current(c, "dxv_skeleton_prune", cur_frame(c).skel, kSkeletonText)) return 1;
+    Frame& f = cur_frame(c);
+    if (!f.grid.p || f.grid_dim != f.skel.dim || !frame_renderable(f))
+        return fail(c, "dxv_skeleton_prune: the skeleton of frame %u does not belong to its grid: it is stale", c->cur);
+    hipStream_t fs;
+    if (begin_operator(c, &fs)) return 1;
+    Frame::Skeleton& o = f.skel;
+    const uint32_t K = o.nodeCount, B = o.branchCount;
+    const size_t work = skel_prune_bytes(K, B);
+    DXV_HIP(c, o.work.reserve(work, work, fs));
+    edited_in_place(f);                                                 // (this skeleton is stale with the rest)
+    DXV_HIP(c, launch_skel_prune(f.grid.p, o.dim, o.labels.p, reinterpret_cast<const SkelNode*>(o.nodes.p), K, reinterpret_cast<const SkelBranch*>(o.branches.p), B, max_len345,
+                                 o.work.p, fs));
+    PinnedFrame& pin = cur_pinned(c);
+    if (end_operator(c, f, fs, nullptr, pin.skelPrune, skel_prune_counters(o.work.p), sizeof(pin.skelPrune))) return 1;
+    o.prune.pending = true;
+    return 0;
+}
+
+int dxv_skeleton_prune(dxv_ctx* c, uint32_t max_len345) { return blocking(c, dxv_skeleton_prune_async(c, max_len345)); }
+
+int dxv_skeleton_prune_info(dxv_ctx* c, uint32_t* branches_removed, uint64_t* voxels_removed)
+{
+    if (!c) return 1;
+    const Frame& f = cur_frame(c);
+    if (branches_removed) *branches_removed = f.skel.prune.branches;
+    if (voxels_removed) *voxels_removed = f.skel.prune.voxels;
     return 0;
 }
 

@@ -28,6 +28,12 @@ MEASURE_RECORD = np.dtype([("voxels", "<u8"), ("sum", "<u8", (3,)), ("sum2", "<u
 # a row of a partition's table, 32 bytes, and one of its throats, 20 bytes (include/dxv.h over dxv_partition_async)
 PART_REGION = np.dtype([("root", "<u4"), ("radius_sq", "<u4"), ("voxels", "<u4"), ("throats", "<u4"), ("lo", "<u2", (3,)), ("hi", "<u2", (3,)), ("flags", "<u4")])
 PART_THROAT = np.dtype([("a", "<u4"), ("b", "<u4"), ("faces", "<u4"), ("neck_sq", "<u4"), ("neck_voxel", "<u4")])
+# a node and a branch of a skeleton graph, 32 and 48 bytes (include/dxv.h over dxv_skeleton_async)
+SKELETON_NODE = np.dtype([("first", "<u4"), ("voxels", "<u4"), ("degree", "<u4"), ("flags", "<u4"), ("lo", "<u2", (3,)), ("hi", "<u2", (3,)), ("w_max", "<u4")])
+SKELETON_BRANCH = np.dtype([("a", "<u4"), ("b", "<u4"), ("first", "<u4"), ("voxels", "<u4"), ("steps", "<u4", (3,)), ("flags", "<u4"), ("w_min", "<u4"), ("w_max", "<u4"),
+                            ("w_sum", "<u8")])
+SKELETON_BRANCH_BIT = 0x80000000                    # labels: 0 no member, k node k, SKELETON_BRANCH_BIT | b branch b
+SKELETON_CLOSED, SKELETON_BORDER, SKELETON_SPUR = 1, 2, 4     # flags of a branch
 DBG_SORTED_KEYS, DBG_NODES, DBG_TRI_POS, DBG_TRI_NRM, DBG_PARENTS, DBG_NODES32, DBG_NODES64, DBG_LIST_CELLS, DBG_LIST_ENTRIES, DBG_LIST_MIP = range(10)
 DBG_BRICK_EMPTY, DBG_BRICK_SUMMARY = 10, 11         # the display pass's empty-brick flags and the summaries behind them
 DBG_LIST_STARTS = 12                                # the lists' start table: one word per texel
@@ -88,6 +94,27 @@ def pore_network(table, throats):
     return {"radius": np.sqrt(table["radius_sq"].astype(np.float64)), "voxels": table["voxels"].astype(np.int64), "coordination": table["throats"].astype(np.int64),
             "pairs": np.stack([throats["a"], throats["b"]], axis=1).astype(np.int64) if len(throats) else np.zeros((0, 2), np.int64),
             "neck_radius": np.sqrt(throats["neck_sq"].astype(np.float64)), "faces": throats["faces"].astype(np.int64)}
+
+
+def skeleton_graph(nodes, branches, h=1.0):
+    """A skeleton's tables (Voxelizer.Skeleton) as a graph: {"length": float64 [B], steps[0] + sqrt(2) steps[1] + sqrt(3) steps[2] times h, the
+    voxel's edge in object units; "len345": int64 [B], the same in SkeletonPrune's integer weights; "pairs": int64 [B, 2], the nodes a <= b of every
+    branch (0, 0: a closed cycle); "closed", "spur": bool [B]; "mean_radius", "min_radius": float64 [B], sqrt of w_sum / voxels and of w_min -- for
+    weights that are squared radii, a Thickness map's -- times h, NaN where no weights were given (w_max == 0); "degree": int64 [K]; "tip": bool
+    [K]}.  Numbers count from 1: node k is row k - 1.  Pure numpy."""
+    nodes, branches = np.atleast_1d(np.asarray(nodes, SKELETON_NODE)), np.atleast_1d(np.asarray(branches, SKELETON_BRANCH))
+    steps = branches["steps"].astype(np.float64).reshape(-1, 3)
+    isteps = branches["steps"].astype(np.int64).reshape(-1, 3)
+    voxels = branches["voxels"].astype(np.float64)
+    given = branches["w_max"] > 0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.where(given, np.sqrt(branches["w_sum"].astype(np.float64) / voxels), np.nan)
+    return {"length": (steps[:, 0] + np.sqrt(2.0) * steps[:, 1] + np.sqrt(3.0) * steps[:, 2]) * float(h),
+            "len345": 3 * isteps[:, 0] + 4 * isteps[:, 1] + 5 * isteps[:, 2],
+            "pairs": np.stack([branches["a"], branches["b"]], axis=1).astype(np.int64) if len(branches) else np.zeros((0, 2), np.int64),
+            "closed": (branches["flags"] & SKELETON_CLOSED) != 0, "spur": (branches["flags"] & SKELETON_SPUR) != 0,
+            "mean_radius": mean * float(h), "min_radius": np.where(given, np.sqrt(branches["w_min"].astype(np.float64)), np.nan) * float(h),
+            "degree": nodes["degree"].astype(np.int64), "tip": (nodes["voxels"] == 1) & (nodes["degree"] == 1)}
 
 
 def thickness_voxels(field):
@@ -747,6 +774,94 @@ class Voxelizer:
         ms, cells, voxels = (C.c_float * 6)(), C.c_uint64(), C.c_uint64()
         self._check(self._lib.dxv_partition_stage_info(self._ctx, ms, C.byref(cells), C.byref(voxels)))
         return dict(zip(("field", "keys", "search", "roots", "regions", "throats"), (float(m) for m in ms))), cells.value, voxels.value
+
+    # ---- the skeleton graph of the frame's grid ------------------------------------------------------------
+    def Skeleton(self, weights=None, sync=True, frameIndex=None):
+        """The skeleton graph of the selected frame's whole grid on the device (dxv_skeleton / dxv_skeleton_async; include/dxv.h has the rule):
+        the members with two members among their 26 neighbours are curve voxels, the others node voxels; a node is a 26-connected cluster of node
+        voxels, a branch one of curve voxels -- a path between two attachments to nodes, or a closed cycle.  weights: None, or N^3 uint32 on the
+        device laid out like the grid -- a torch tensor of a 4-byte integer dtype or a pointer, for example another frame's
+        thickness_device_ptr() -- whose minimum, maximum and sum along every branch go into its record.  A graph of the shape for a grid Thin has
+        left.  The grid and the frame's other products stay as they are.  sync=True returns (SkeletonLabels(), SkeletonNodes(),
+        SkeletonBranches()); sync=False only enqueues it -- the call still waits for its own counts, and the caller keeps the weights alive and
+        unchanged until the frame has been synchronised."""
+        if frameIndex is not None:
+            self.SetFrame(frameIndex)
+        ptr, keep = None, None
+        if weights is not None:
+            if hasattr(weights, "data_ptr"):
+                import torch
+                if not weights.is_cuda or weights.element_size() != 4 or weights.is_floating_point() or not weights.is_contiguous():
+                    raise DxvError("Skeleton: a weight tensor must be a contiguous 4-byte integer tensor on the device")
+                n = self.stats()["grid_dim"]
+                if weights.numel() != n ** 3:
+                    raise DxvError(f"Skeleton: the weight tensor has {weights.numel()} elements, the grid has {n ** 3} voxels")
+                torch.cuda.current_stream(weights.device).synchronize()   # (its writer is ordered before the frame's stream reads it)
+                ptr, keep = C.c_void_p(weights.data_ptr()), weights
+            else:
+                ptr = C.c_void_p(int(weights))
+        fn = self._lib.dxv_skeleton if sync else self._lib.dxv_skeleton_async
+        self._check(fn(self._ctx, ptr))
+        del keep
+        return (self.SkeletonLabels(), self.SkeletonNodes(), self.SkeletonBranches()) if sync else True
+
+    def SkeletonLabels(self):
+        """numpy copy uint32 [N, N, N] (z, y, x) of the selected frame's skeleton labels: 0 off the members, k on node k, SKELETON_BRANCH_BIT | b on
+        branch b (dxv_skeleton_labels_download; synchronises the frame)."""
+        nbytes = self._lib.dxv_skeleton_labels_bytes(self._ctx)
+        if not nbytes:
+            self._lib.dxv_skeleton_labels_device_ptr(self._ctx)        # (sets the message: none yet, or stale)
+            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
+        n = round((nbytes // 4) ** (1.0 / 3.0))
+        out = np.empty((n, n, n), np.uint32)
+        self._check(self._lib.dxv_skeleton_labels_download(self._ctx, out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
+    def SkeletonNodes(self):
+        """numpy copy [K] of the selected frame's nodes, dtype SKELETON_NODE (dxv_skeleton_nodes_download; synchronises the frame)."""
+        if not self._lib.dxv_skeleton_labels_device_ptr(self._ctx):
+            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
+        table = np.empty(self._lib.dxv_skeleton_nodes_bytes(self._ctx) // SKELETON_NODE.itemsize, SKELETON_NODE)
+        self._check(self._lib.dxv_skeleton_nodes_download(self._ctx, table.ctypes.data_as(C.c_void_p), table.nbytes))
+        return table
+
+    def SkeletonBranches(self):
+        """numpy copy [B] of the selected frame's branches, dtype SKELETON_BRANCH (dxv_skeleton_branches_download; synchronises the frame)."""
+        if not self._lib.dxv_skeleton_labels_device_ptr(self._ctx):
+            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
+        table = np.empty(self._lib.dxv_skeleton_branches_bytes(self._ctx) // SKELETON_BRANCH.itemsize, SKELETON_BRANCH)
+        self._check(self._lib.dxv_skeleton_branches_download(self._ctx, table.ctypes.data_as(C.c_void_p), table.nbytes))
+        return table
+
+    def skeleton_device_ptrs(self):
+        """(labels, nodes, branches) device pointers of the selected frame's skeleton, for consumers on the GPU; the nodes' is None when K = 0, the
+        branches' when B = 0."""
+        labels = self._lib.dxv_skeleton_labels_device_ptr(self._ctx)
+        if not labels:
+            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
+        return labels, self._lib.dxv_skeleton_nodes_device_ptr(self._ctx), self._lib.dxv_skeleton_branches_device_ptr(self._ctx)
+
+    def SkeletonInfo(self):
+        """{ms, nodes, branches, end_voxels, curve_voxels, junction_voxels} of the selected frame's last skeleton as of its last Sync
+        (dxv_skeleton_info): the members with at most one, with two and with three or more members among their 26 neighbours."""
+        ms, nodes, branches = C.c_float(), C.c_uint32(), C.c_uint32()
+        ends, curve, junctions = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self._lib.dxv_skeleton_info(self._ctx, C.byref(ms), C.byref(nodes), C.byref(branches), C.byref(ends), C.byref(curve), C.byref(junctions)))
+        return {"ms": ms.value, "nodes": nodes.value, "branches": branches.value, "end_voxels": ends.value, "curve_voxels": curve.value, "junction_voxels": junctions.value}
+
+    def SkeletonPrune(self, max_len345, sync=True):
+        """Remove short spurs from the selected frame's grid in place, from its current skeleton (dxv_skeleton_prune / _async): every branch with
+        exactly one tip -- a node of one voxel and degree 1 -- at an end and 3 steps[0] + 4 steps[1] + 5 steps[2] <= max_len345 goes, with that
+        tip.  The skeleton is stale afterwards; the recipe is Thin; Skeleton; SkeletonPrune(L); Thin; Skeleton."""
+        fn = self._lib.dxv_skeleton_prune if sync else self._lib.dxv_skeleton_prune_async
+        self._check(fn(self._ctx, int(max_len345)))
+        return True
+
+    def SkeletonPruneInfo(self):
+        """(branches_removed, voxels_removed) of the selected frame's last SkeletonPrune as of its last Sync (dxv_skeleton_prune_info)."""
+        branches, voxels = C.c_uint32(), C.c_uint64()
+        self._check(self._lib.dxv_skeleton_prune_info(self._ctx, C.byref(branches), C.byref(voxels)))
+        return branches.value, voxels.value
 
     # ---- the geodesic distance inside the frame's grid ---------------------------------------------------
     def Geodesic(self, of=COMP_SOLID, metric=GEO_CHAMFER, seeds="border", limit=0, sync=True, frameIndex=None):

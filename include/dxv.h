@@ -862,6 +862,86 @@ DXV_API int dxv_partition_throats_download(dxv_ctx* ctx, void* host, size_t byte
  * the search tested.  The two pointers may be NULL. */
 DXV_API int dxv_partition_stage_info(dxv_ctx* ctx, float ms[6], uint64_t* cells_tested, uint64_t* voxels_tested);
 
+/* Skeleton graph: the nodes and branches of a curve skeleton (no reference counterpart).  dxv_thin leaves centre lines as a grid of bytes; this
+ * operator gives the graph they draw -- a label per voxel, a table of nodes (ends and junctions, clustered) and a table of branches (the curves
+ * between nodes) with each branch's end nodes, voxel count, exact step counts and, optionally, the minimum, maximum and sum of a caller's
+ * per-voxel map along it: the step from a per-voxel map to a graph, as dxv_partition is for pores.
+ * Input: the WHOLE grid of the selected frame's last launch, in any mode.  Bytes written through dxv_grid_device_ptr count too.  member(p) iff
+ * byte(p) != 0.  Voxels outside the grid are non-members, as for dxv_thin.  Adjacency is dxv_components' at connectivity 26.  Integers only, with
+ * index(p) = (z N + y) N + x:
+ *     deg(p)     = the members among the 26 neighbours of p                       for a member p
+ *     curve(p)   iff deg(p) == 2;   node voxel iff deg(p) != 2   (0: isolated, 1: end, >= 3: junction)
+ *     node       a 26-connected component of the node voxels;   numbered 1 .. K by ascending smallest index
+ *     branch     a 26-connected component of the curve voxels;  numbered 1 .. B by ascending smallest index
+ *     step       an unordered pair {p, q} of adjacent members with at least one of them a curve voxel;
+ *                it belongs to the branch of its curve voxel(s); its type is |dx|+|dy|+|dz| - 1  (0 face, 1 edge, 2 corner)
+ *     attachment a step whose other voxel is a node voxel: it joins the branch to that voxel's node
+ * What deg == 2 gives: a branch is a simple path or a simple closed cycle of curve voxels; two curve voxels that are adjacent are always in the
+ * same branch; a path has exactly two attachments (a one-voxel path has both of them) and steps = voxels + 1; a cycle has no attachment, at least
+ * 3 voxels, and steps = voxels.  The numbering is scipy.ndimage.label's with the full 3x3x3 structure, as for dxv_components.
+ * Output: labels, one uint32 per voxel, element (iz * N + iy) * N + ix like the grid, 4 N^3 bytes: 0 for a non-member, k for a voxel of node k,
+ * 0x80000000 | b for a voxel of branch b.  The nodes, K records of 32 bytes, little endian:
+ *     uint32 first, voxels, degree, flags; uint16 lo[3], hi[3] (x, y, z); uint32 w_max
+ * first: the node's smallest index; degree: the attachments that name the node (a branch from a node back to itself counts 2); flags bit 0: a
+ * voxel with a coordinate 0 or N - 1, bit 1: a voxel with deg <= 1, bit 2: a voxel with deg >= 3.  The branches, B records of 48 bytes:
+ *     uint32 a, b, first, voxels, steps[3], flags; uint32 w_min, w_max; uint64 w_sum
+ * a <= b: the nodes of its two attachments; a == b != 0 is a loop at one node, a == b == 0 a closed cycle.  steps[t]: its steps of type t,
+ * attachments included.  flags bit 0: closed, bit 1: a curve voxel with a coordinate 0 or N - 1, bit 2: spur.  A tip is a node with voxels == 1
+ * and degree == 1; a spur is a branch of which exactly one of a, b is a tip (with both it is a free segment, not a spur).  w_* are taken over the
+ * voxels of the node, or over the curve voxels of the branch, of the caller's uint32 map; all 0 without one.  Length and mean radius are host
+ * arithmetic: steps[0] + sqrt(2) steps[1] + sqrt(3) steps[2], and w_sum / voxels.  Every step is a set function of the grid: the device's bytes
+ * equal a restatement byte for byte, whatever ran first.
+ * Two properties of the rule, to know and not to "fix":
+ *  - The rule reads any grid, but it is a graph of the shape only for a grid dxv_thin has left.  A voxel dxv_thin would remove reads as a node or
+ *    as a one-voxel loop: the corner voxel of an axis-aligned right angle, whose two neighbours touch each other diagonally, is one.  A square
+ *    ring drawn by hand gives 4 nodes of 2 voxels and 4 such loops beside its 4 sides; dxv_thin(DXV_THIN_CURVE) first gives one closed branch.
+ *  - A solid blob is one big node.
+ * dxv_skeleton_async -- ENQUEUED on the frame's stream behind whatever it holds.  The host waits once in the middle, for K and B -- the tables
+ * cannot be sized without them --; then the stats kernels are enqueued.  The grid is read and none of the frame's other products is written -- a
+ * current distance field, thickness map or labelling stays current and unchanged.
+ *  - device_weights: NULL, or N^3 uint32 on the device laid out like the grid -- another frame's thickness map, for the radius along a branch.
+ *    The caller orders whatever wrote it in front of the frame's stream.
+ *  - The host waits before that only under dxv_render_async's rule; a pending fill or thin is settled first.
+ *  - Checked on the host before anything is enqueued, each an error with a message that leaves the frame's earlier skeleton and everything else
+ *    as it was: the frame has been launched; its last launch was the whole grid; grid_dim <= 1024 (bit 31 of a label is the kind);
+ *    device_weights is NULL or 4-byte aligned device memory of this context's device with 4 N^3 bytes inside its allocation.
+ *  - Labels, tables and scratch (5 bytes per voxel beside the labels) belong to the frame: frames run side by side.  dxv_trim gives the scratch
+ *    back and keeps labels and tables.
+ *  - Labels and tables are STALE once the frame is launched, filled, morphed, thinned, expanded, selected or pruned again: pointers, sizes and
+ *    downloads then fail with a message.
+ *  - Option events = 1 (default): bracketed by the frame's own events, read at the frame's dxv_sync.
+ * dxv_skeleton -- the same + dxv_sync. */
+DXV_API int dxv_skeleton_async(dxv_ctx* ctx, const void* device_weights);
+DXV_API int dxv_skeleton(dxv_ctx* ctx, const void* device_weights);
+/* The selected frame's last skeleton as of the frame's last dxv_sync: device time in milliseconds from its first kernel to its last, the wait
+ * included (HIP events, option events = 1; else 0); K, B and the members with deg <= 1, deg == 2 and deg >= 3 of the frame's CURRENT skeleton (0
+ * when none or stale).  Any pointer may be NULL. */
+DXV_API int dxv_skeleton_info(dxv_ctx* ctx, float* ms, uint32_t* nodes, uint32_t* branches, uint64_t* end_voxels, uint64_t* curve_voxels, uint64_t* junction_voxels);
+/* Labels, nodes and branches on the device (valid after dxv_sync or on the frame's stream), their sizes -- 4 * grid_dim^3, 32 K and 48 B bytes --
+ * and their copies to the host (bytes must be the size; synchronises the frame first).  NULL / 0 (pointer and download with a message) before the
+ * frame's first skeleton or when it is stale.  With K = 0 (B = 0) the nodes' (branches') pointer is NULL and its size 0, without a message. */
+DXV_API const void* dxv_skeleton_labels_device_ptr(const dxv_ctx* ctx);
+DXV_API size_t dxv_skeleton_labels_bytes(const dxv_ctx* ctx);
+DXV_API int dxv_skeleton_labels_download(dxv_ctx* ctx, void* host, size_t bytes);
+DXV_API const void* dxv_skeleton_nodes_device_ptr(const dxv_ctx* ctx);
+DXV_API size_t dxv_skeleton_nodes_bytes(const dxv_ctx* ctx);
+DXV_API int dxv_skeleton_nodes_download(dxv_ctx* ctx, void* host, size_t bytes);
+DXV_API const void* dxv_skeleton_branches_device_ptr(const dxv_ctx* ctx);
+DXV_API size_t dxv_skeleton_branches_bytes(const dxv_ctx* ctx);
+DXV_API int dxv_skeleton_branches_download(dxv_ctx* ctx, void* host, size_t bytes);
+/* dxv_skeleton_prune_async -- removes short spurs from the frame's grid IN PLACE; needs a current skeleton.  For every spur with
+ * 3 steps[0] + 4 steps[1] + 5 steps[2] <= max_len345 (dxv_geodesic's chamfer weights, integers) the bytes of the branch's curve voxels and of its
+ * tip's one voxel become 0; all such spurs go in one pass, nothing else is touched.  A curve voxel has deg 2 and a tip deg 1, so the removal is a
+ * collapse: no piece, tunnel or cavity appears or disappears.  ENQUEUED on the frame's stream under dxv_fill_async's rules for the grid.  It makes
+ * stale everything dxv_components_select makes stale, and the skeleton itself.  The recipe:
+ *     dxv_thin; dxv_skeleton; dxv_skeleton_prune(L); dxv_thin; dxv_skeleton
+ * (the second thin takes what the removal left of a junction).
+ * dxv_skeleton_prune -- the same + dxv_sync. */
+DXV_API int dxv_skeleton_prune_async(dxv_ctx* ctx, uint32_t max_len345);
+DXV_API int dxv_skeleton_prune(dxv_ctx* ctx, uint32_t max_len345);
+/* The spurs and the voxels the selected frame's last prune removed, as of the frame's last dxv_sync.  Either pointer may be NULL. */
+DXV_API int dxv_skeleton_prune_info(dxv_ctx* ctx, uint32_t* branches_removed, uint64_t* voxels_removed);
+
 /* Geodesic distance: how far one place is from another THROUGH the part, or through its empty space (no reference counterpart).  dxv_distance is
  * the straight-line distance to the other kind of voxel and dxv_fill knows only whether the border can be reached; this operator gives, per
  * member voxel, the length of the shortest path of member voxels to the nearest seed: the length of a dxv_thin skeleton branch, the path between

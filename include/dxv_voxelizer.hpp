@@ -365,6 +365,52 @@ public:
 	}
 	bool PartitionInfo(float& ms, uint32_t& regions, uint32_t& throats, uint64_t& interfaceFaces) { return m_ctx && dxv_partition_info(m_ctx, &ms, &regions, &throats, &interfaceFaces) == 0; }
 
+	// The skeleton graph of the selected frame's whole grid (dxv_skeleton / dxv_skeleton_async; include/dxv.h has the rule and the two record
+	// layouts): a label per voxel -- 0, k for node k, 0x80000000 | b for branch b --, the nodes as 32-byte records and the branches as 48-byte
+	// records.  deviceWeights: nullptr, or N^3 uint32 on the device laid out like the grid (another frame's DeviceThickness()): their minimum,
+	// maximum and sum along every branch.  A graph of the shape for a grid Thin has left; a solid blob is one big node.  The grid and the frame's
+	// other products stay as they are.  SkeletonPrune removes from the grid, in place, every spur with 3 steps[0] + 4 steps[1] + 5 steps[2] <=
+	// maxLen345, with its tip; the recipe is Thin; Skeleton; SkeletonPrune(L); Thin; Skeleton.
+	struct SkeletonNode { uint32_t first, voxels, degree, flags; uint16_t lo[3], hi[3]; uint32_t wMax; };
+	struct SkeletonBranch { uint32_t a, b, first, voxels, steps[3], flags, wMin, wMax; uint64_t wSum; };
+	struct SkeletonCounts { float ms; uint32_t nodes, branches; uint64_t endVoxels, curveVoxels, junctionVoxels; };
+	bool Skeleton(const void* deviceWeights = nullptr, bool sync = true)
+	{
+		return m_ctx && (sync ? dxv_skeleton(m_ctx, deviceWeights) : dxv_skeleton_async(m_ctx, deviceWeights)) == 0;
+	}
+	const void* DeviceSkeletonLabels() const { return m_ctx ? dxv_skeleton_labels_device_ptr(m_ctx) : nullptr; }
+	bool SkeletonLabels(std::vector<uint32_t>& labels)
+	{
+		if (!m_ctx) return setError("SkeletonLabels before Init");
+		const size_t bytes = dxv_skeleton_labels_bytes(m_ctx);
+		if (!bytes) return dxv_skeleton_labels_device_ptr(m_ctx) != nullptr;       // (false, with the message: none yet, or stale)
+		labels.resize(bytes / sizeof(uint32_t));
+		return dxv_skeleton_labels_download(m_ctx, labels.data(), bytes) == 0;
+	}
+	bool SkeletonNodes(std::vector<SkeletonNode>& nodes)
+	{
+		if (!m_ctx) return setError("SkeletonNodes before Init");
+		static_assert(sizeof(SkeletonNode) == 32, "a node record is 32 bytes");
+		const size_t bytes = dxv_skeleton_nodes_bytes(m_ctx);
+		nodes.resize(bytes / sizeof(SkeletonNode));
+		return dxv_skeleton_nodes_download(m_ctx, nodes.data(), bytes) == 0;
+	}
+	bool SkeletonBranches(std::vector<SkeletonBranch>& branches)
+	{
+		if (!m_ctx) return setError("SkeletonBranches before Init");
+		static_assert(sizeof(SkeletonBranch) == 48, "a branch record is 48 bytes");
+		const size_t bytes = dxv_skeleton_branches_bytes(m_ctx);
+		branches.resize(bytes / sizeof(SkeletonBranch));
+		return dxv_skeleton_branches_download(m_ctx, branches.data(), bytes) == 0;
+	}
+	bool SkeletonInfo(SkeletonCounts& c)
+	{
+		return m_ctx && dxv_skeleton_info(m_ctx, &c.ms, &c.nodes, &c.branches, &c.endVoxels, &c.curveVoxels, &c.junctionVoxels) == 0;
+	}
+	bool SkeletonPrune(uint32_t maxLen345, bool sync = true) { return m_ctx && (sync ? dxv_skeleton_prune(m_ctx, maxLen345) : dxv_skeleton_prune_async(m_ctx, maxLen345)) == 0; }
+	bool SkeletonPruneInfo(uint32_t& branchesRemoved, uint64_t& voxelsRemoved) { return m_ctx && dxv_skeleton_prune_info(m_ctx, &branchesRemoved, &voxelsRemoved) == 0; }
+	static double SkeletonLength(const SkeletonBranch& b) { return b.steps[0] + 1.4142135623730951 * b.steps[1] + 1.7320508075688772 * b.steps[2]; }
+
 	// The geodesic distance inside the selected frame's whole grid (dxv_geodesic / dxv_geodesic_async; include/dxv.h has the rule): per member voxel
 	// the length of the shortest path of member voxels to the nearest seed -- DXV_GEO_FACES over the face neighbours at weight 1, DXV_GEO_CHAMFER
 	// over the 26 neighbours at weights 3 / 4 / 5 --, DXV_GEO_NONE on the others, DXV_GEO_UNREACHED where no path exists or is longer than limit
