@@ -748,13 +748,15 @@ hipError_t dirmap_mip(const DirCell* cells, uint32_t R, uint16_t* mip, hipStream
 // The start table of the lists (dxv_dirmap.h: dm_start_word): one thread per texel, the buckets' edges by binary search in the texel's
 // sorted list -- a dozen loads per texel however long the list.
 __global__ __launch_bounds__(1024) void k_dm_starts(const DirCell* __restrict__ cells, uint32_t ncells, const DirEntry* __restrict__ entries,
-                                                   uint32_t* __restrict__ starts)
+                                                   uint32_t* __restrict__ starts, DirCell* __restrict__ startCells)
 {
     const uint32_t k = blockIdx.x * 1024u + threadIdx.x;
     uint32_t count = 0u;
     if (k < ncells) {
         const DirCell cell = cells[k];
-        starts[k] = dm_start_word(cell, entries + cell.begin);
+        const uint32_t word = dm_start_word(cell, entries + cell.begin);
+        starts[k] = word;
+        startCells[k] = dm_start_cell(cell, word);                      // (the cell the kernels that read the table read: one 16-byte store more)
         count = cell.count;
     }
     // (the two counters behind the table: what the automatic setting of option starttable goes by -- start_table_pays)
@@ -765,12 +767,12 @@ __global__ __launch_bounds__(1024) void k_dm_starts(const DirCell* __restrict__ 
         if (many) atomicAdd(starts + ncells + 1u, (uint32_t)many);
     }
 }
-hipError_t dirmap_starts(const DirCell* cells, uint32_t R, const DirEntry* entries, uint32_t* starts, hipStream_t s)
+hipError_t dirmap_starts(const DirCell* cells, uint32_t R, const DirEntry* entries, uint32_t* starts, DirCell* startCells, hipStream_t s)
 {
     const uint32_t n = 6u * R * R;
     const hipError_t e = hipMemsetAsync(starts + n, 0, 2 * sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
-    k_dm_starts<<<(n + 1023u) / 1024u, 1024, 0, s>>>(cells, n, entries, starts);
+    k_dm_starts<<<(n + 1023u) / 1024u, 1024, 0, s>>>(cells, n, entries, starts, startCells);
     return hipGetLastError();
 }
 

@@ -138,8 +138,8 @@ int dxv_scene_import(dxv_ctx* c, const void* src, size_t bytes)
                         bad[0], h.listCount, bad[1], h.numTris);
         // the max-mip of the far radii is a function of the cells: made here, not carried in the blob
         DXV_HIP(c, dirmap_mip(c->lists.cells.p, h.listRes, c->lists.mip.p, c->stream));
-        // ... and so is the start table (of the validated cells and entries)
-        DXV_HIP(c, dirmap_starts(c->lists.cells.p, h.listRes, c->lists.entries.p, c->lists.starts.p, c->stream));
+        // ... and so are the start table and the start cells (of the validated cells and entries)
+        DXV_HIP(c, dirmap_starts(c->lists.cells.p, h.listRes, c->lists.entries.p, c->lists.starts.p, c->lists.startCells.p, c->stream));
         DXV_HIP(c, hipMemcpyAsync(c->pin->listStarts, c->lists.starts.p + 6 * (size_t)h.listRes * h.listRes, sizeof(c->pin->listStarts), hipMemcpyDeviceToHost, c->stream));
         DXV_HIP(c, hipStreamSynchronize(c->stream));
         c->lists.startsPay = start_table_pays(c->pin->listStarts[0], c->pin->listStarts[1]);

@@ -88,6 +88,7 @@ struct Lists {
     DevBuf<DirEntry> entries;
     DevBuf<uint16_t> mip;            // (cap: 16-bit words of the mip proper)
     DevBuf<uint32_t> starts;         // start table (dxv_dirmap.h: dm_start_word): one word per texel, made with the mip wherever cells and entries are; two counters behind it
+    DevBuf<DirCell> startCells;      // start cells (dxv_dirmap.h: dm_start_cell): the cells with the table's word where the hints are, made with the table by dirmap_starts; never exported
     bool startsPay = false;          // what option starttable = 2 (automatic) does for these lists (dxv_policy.h: start_table_pays; false until the build is settled)
     uint32_t count = 0, res = 0;     // entries, texels per face side
     int state = 0;                   // 0: not built for this scene, 1: built, -1: over the cap for this scene (tree walk)
@@ -100,6 +101,7 @@ struct Lists {
         if (e == hipSuccess) e = entries.reserve(n, (n + 4) * sizeof(DirEntry));
         if (e == hipSuccess) e = mip.reserve(dm_mip_words(R), sizeof(uint16_t) * (size_t)dm_mip_buffer_words(R));
         if (e == hipSuccess) e = starts.reserve(6 * (size_t)R * R + 2, (6 * (size_t)R * R + 2) * sizeof(uint32_t));
+        if (e == hipSuccess) e = startCells.reserve(6 * (size_t)R * R, 6 * (size_t)R * R * sizeof(DirCell));
         return e;
     }
 };
@@ -561,6 +563,7 @@ inline void lists_params(const dxv_ctx* c, SceneView& sc)
 {
     sc.dmCells = c->lists.cells.p; sc.dmEntries = c->lists.entries.p; sc.dmR = c->lists.res;
     sc.dmStarts = start_table_used(c->opt.starttable, c->lists.startsPay) ? c->lists.starts.p : nullptr;
+    sc.dmStartCells = sc.dmStarts ? c->lists.startCells.p : nullptr;
 }
 inline uint32_t z_shift(uint32_t zBlock)
 {

@@ -534,8 +534,9 @@ extern "C" int dxv_debug_download(dxv_ctx* c, int what, void* host, size_t bytes
     case DXV_DBG_LIST_ENTRIES: if (c->haveScene && c->lists.state == 1) { src = c->lists.entries.p; want = sizeof(DirEntry) * (size_t)c->lists.count; } break;
     case DXV_DBG_LIST_MIP: if (c->haveScene && c->lists.state == 1 && c->lists.mip.p) { src = c->lists.mip.p; want = sizeof(uint16_t) * (size_t)dm_mip_words(c->lists.res); } break;
     case DXV_DBG_LIST_STARTS: if (c->haveScene && c->lists.state == 1 && c->lists.starts.p) { src = c->lists.starts.p; want = sizeof(uint32_t) * 6 * (size_t)c->lists.res * c->lists.res; } break;
+    case DXV_DBG_LIST_START_CELLS: if (c->haveScene && c->lists.state == 1 && c->lists.startCells.p) { src = c->lists.startCells.p; want = sizeof(DirCell) * 6 * (size_t)c->lists.res * c->lists.res; } break;
     case DXV_DBG_BRICK_EMPTY:
-    case DXV_DBG_BRICK_SUMMARY: {                                       // (written on the frame's stream by its last render with flags: launch_raycast)
+    case DXV_DBG_BRICK_SUMMARY: {                                    // (written on the frame's stream by its last render with flags: launch_raycast)
         const Frame& f = cur_frame(c);
         if (!f.emptyDim || !f.empty.p) return fail(c, "dxv_debug_download: frame %u has not been rendered with empty-brick flags (option skipempty = 1)", c->cur);
         if (f.emptyDim != f.grid_dim) return fail(c, "dxv_debug_download: frame %u's flags are of a %u^3 grid, its grid is %u^3 now (render it again)", c->cur, f.emptyDim, f.grid_dim);

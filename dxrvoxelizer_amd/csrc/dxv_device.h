@@ -61,7 +61,7 @@ hipError_t dirmap_fill(uint32_t T, uint32_t R, const DirRecord* rec, const uint3
 
 // max-mips of the texels' far radii and entry counts (dxv_dirmap.h: dm_mip_max), dm_mip_buffer_words(R) 16-bit words: what the launch's work queue is probed against
 hipError_t dirmap_mip(const DirCell* cells, uint32_t R, uint16_t* mip, hipStream_t s);
-hipError_t dirmap_starts(const DirCell* cells, uint32_t R, const DirEntry* entries, uint32_t* starts, hipStream_t s);   // starts: 6 R R words (dm_start_word) + two counters: non-empty texels, texels of more than 8 entries
+hipError_t dirmap_starts(const DirCell* cells, uint32_t R, const DirEntry* entries, uint32_t* starts, DirCell* startCells, hipStream_t s);   // starts: 6 R R words (dm_start_word) + two counters: non-empty texels, texels of more than 8 entries; startCells: 6 R R cells (dm_start_cell)
 
 // the far-radius map of a scene WITHOUT lists (a tree walk's brick test): far32 = 6 R R words of scratch, cells = 6 R R, mip = dm_mip_buffer_words(R)
 hipError_t dirmap_far(const TriPos* triPos, uint32_t T, uint32_t R, uint32_t* far32, DirCell* cells, uint16_t* mip, hipStream_t s);

@@ -91,6 +91,7 @@ struct DirMapView {
     uint32_t R;                // texels per face side, a power of two
     uint32_t coop = 0u;        // device: 1 = a lone lane's long list is scanned by its whole wave (trace_reference_dm_from)
     const uint32_t* starts = nullptr;   // 6 * R * R start words (dm_start_word), indexed like the cells; NULL: every scan begins where the search ends
+    const DirCell* startCells = nullptr;    // 6 * R * R start cells (dm_start_cell): a texel's cell with its start word where the hints are; NULL: none
 };
 
 constexpr float kDmDelta = 3.0517578125e-5f;        // 2^-15: dilation of the triangles
@@ -237,6 +238,49 @@ DXV_HD uint32_t dm_start_offset(uint32_t word, uint32_t count, uint32_t top, flo
     if (d > kDmStartBuckets - 1u) d = kDmStartBuckets - 1u;
     return ((word >> (4u + 8u * d)) & 255u) * dm_start_unit(count);     // (d = B - 1 reads the word's four empty top bits: 0)
 }
+// Start cells: a third array beside cells and table (derived like the table, never exported), a texel's cell with the texel's start word
+// where the search hints are -- q1 | q2 << 16 = dm_start_word, q3 = 0; begin, count, r1max and thick byte for byte the canonical cell's, so
+// a ray's `live` decision and its stop step come out of either cell alike.  A kernel that reads the table reads THIS cell and nothing else:
+// one 16-byte gather per ray instead of a 16-byte and a 4-byte one to the same texel index.  The hints are what it gives up: a list of up to
+// kDmStartCellDirect entries begins its scan at the table's start with no search at all, a longer one runs the loaded binary search over
+// the whole list (two trips more than behind the hints) and then takes the later of the two starts, as before.  Either way a skipped
+// entry has r1 < near (the table's argument above; the search's own invariant): only which rejected entries are looked at changes.
+constexpr uint32_t kDmStartCellDirect = 35u;        // (the hints' reach: the lists that take a search load stay the ones that took one)
+DXV_HD DirCell dm_start_cell(const DirCell& cell, uint32_t word)
+{
+    DirCell s = cell;
+    s.q1 = (uint16_t)(word & 0xffffu); s.q2 = (uint16_t)(word >> 16); s.q3 = 0u;
+    return s;
+}
+#if defined(DXV_START_WORD_ZERO)                    // (timing-only build: the body that reads start cells with every word 0 -- no skip -- against the _plain body)
+DXV_HD uint32_t dm_start_cell_word(const DirCell&)
+{
+    uint32_t w = 0u;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(w));                              // (a zero the compiler cannot see: the word's arithmetic stays in the body)
+#endif
+    return w;
+}
+#else
+DXV_HD uint32_t dm_start_cell_word(const DirCell& startCell) { return (uint32_t)startCell.q1 | ((uint32_t)startCell.q2 << 16); }
+#endif
+// where the scan of a ray that read a START cell begins (absolute entry index; a ray that is not live: the list's end)
+// direct: lists of up to so many entries take no search (kDmStartCellDirect; a parameter for the host's replay); loads: search loads, counted
+DXV_HD uint32_t dm_start_cell_begin(const DirCell& sc, const DirEntry* entries, bool live, float near, uint32_t direct = kDmStartCellDirect,
+                                    uint32_t* loads = nullptr)
+{
+    const uint32_t end = sc.begin + sc.count;
+    if (!live) return end;
+    const uint32_t from = sc.begin + dm_start_offset(dm_start_cell_word(sc), sc.count, sc.r1max, near);
+    if (sc.count <= direct) return from;
+    uint32_t i = sc.begin, hi = end;
+    while (hi - i > 8u) {
+        const uint32_t mid = i + ((hi - i) >> 1);
+        if (loads) ++*loads;
+        if (dm_entry_r1(entries[mid]) < near) i = mid + 1u; else hi = mid;
+    }
+    return from > i ? from : i;
+}
 
 // The first step of a ray through the lists -- its texel, its cell inside the texel, and whether it has any candidate at
 // all: a ray whose texel is empty, or that starts beyond the far radius of its texel's last entry, is a miss after this
@@ -247,8 +291,16 @@ DXV_HD uint32_t dm_start_offset(uint32_t word, uint32_t count, uint32_t top, flo
 // instruction stream of the kernel before there was a table).  The table's few instructions cost a launch that does not use them 5 - 6 %
 // (measured, profiles/start_table/: the body with them, pointer NULL, against the body without), so the brick kernels exist in both forms
 // and the launch picks by the pointer (voxelize_lists.hip).
+// STARTS = 2: a kernel compiled to read START cells (dm.startCells: the one load; its scan begins by dm_start_cell_begin, startWord stays 0);
+// STARTS = 3: start cells where the view has them, else as STARTS = 1 (a wave-uniform choice: the brick-box body, the host).
 struct DirRayStart { DirCell cell; uint32_t cx, cy; float rho, near; bool live; uint32_t startWord; };
-template <bool STARTS = true>
+#if defined(DXV_NO_START_TABLE)
+constexpr int dm_starts_form(int) { return 0; }
+#else
+constexpr int dm_starts_form(int starts) { return starts; }
+#endif
+template <int FORM> DXV_HD bool dm_reads_start_cells(const DirMapView& dm) { return FORM == 2 || (FORM == 3 && dm.startCells != nullptr); }
+template <int STARTS = 1>
 DXV_HD DirRayStart dm_ray_start(float ox, float oy, float oz, const DirMapView& dm)
 {
     DirRayStart s;
@@ -257,16 +309,27 @@ DXV_HD DirRayStart dm_ray_start(float ox, float oy, float oz, const DirMapView& 
     dm_ray_point(ox, oy, oz, face, u, v, s.rho);
     dm_local(u, dm.R, ti, s.cx); dm_local(v, dm.R, tj, s.cy);
     const uint32_t at = (face * dm.R + tj) * dm.R + ti;
-#if defined(DXV_NO_START_TABLE)                     // (A/B build from the same sources: the kernels as they were without the table)
+    constexpr int FORM = dm_starts_form(STARTS);    // (DXV_NO_START_TABLE, an A/B build from the same sources: 0, the kernels as they were without the table)
     s.startWord = 0u;
+    if (dm_reads_start_cells<FORM>(dm)) {                               // (wave-uniform)
+#if defined(__HIP_DEVICE_COMPILE__)
+        // ONE 16-byte load: nothing reads q3 of a start cell, and left to itself the compiler asks for the cell's first twelve bytes and for
+        // q2 in two load instructions -- as many as cell and word were.  The empty statement may have changed all four words for all it knows.
+        typedef uint32_t Words4 __attribute__((ext_vector_type(4)));
+        Words4 w = *reinterpret_cast<const Words4*>(dm.startCells + at);
+        asm("" : "+v"(w));
+        s.cell = __builtin_bit_cast(DirCell, w);
 #else
-    // The word is asked for IN FRONT of the cell, under the (wave-uniform) test of the pointer, and nothing looks at it before the cell
-    // has been asked for too: both loads are in flight behind one wait, no dependent trip -- and a launch without a table issues no
-    // load for it at all (asked for behind the cell, the compiler waits for the cell in front of the branch).
-    s.startWord = 0u;
-    if (STARTS && dm.starts) s.startWord = dm.starts[at];
+        s.cell = dm.startCells[at];
 #endif
-    s.cell = dm.cells[at];
+    }
+    else {
+        // The word is asked for IN FRONT of the cell, under the (wave-uniform) test of the pointer, and nothing looks at it before the cell
+        // has been asked for too: both loads are in flight behind one wait, no dependent trip -- and a launch without a table issues no
+        // load for it at all (asked for behind the cell, the compiler waits for the cell in front of the branch).
+        if (FORM && dm.starts) s.startWord = dm.starts[at];
+        s.cell = dm.cells[at];
+    }
     s.near = s.rho * 0.999f;
     s.live = s.cell.count != 0u && !(half_bits_to_float(s.cell.r1max) < s.near);
     return s;
@@ -853,7 +916,9 @@ static __device__ unsigned long long g_dxvPhase[kPhaseSlots * 16u];
 // HITLDS: the closest hit's V, W, det and index live in column words cap .. cap + 3 (leaf_reference_deferred_lds); best.t and best.leaf are
 // all of `best` that is meaningful then (best.leaf == -1: miss), bestDet is untouched.
 // HITLDS 2: nothing but best.t and best.leaf is kept at all (leaf_reference_min, shade_reference_again).
-template <class Stack, int ABL = 0, int HITLDS = 0>
+// STARTS: what dm_ray_start<STARTS> read for `start` -- 2 (or 3 with start cells in the view): a START cell, whose scan begins by
+// dm_start_cell_begin (no hint steps; the words where the hints were are the start word); else the canonical cell and start.startWord.
+template <class Stack, int ABL = 0, int HITLDS = 0, int STARTS = 1>
 DXV_HD void trace_reference_dm_from(Ray& r, const DirMapView& dm, const DirRayStart& start, const TriPos* tris, const Stack& stk, int cap, Hit& best,
                                     float& bestDet)
 {
@@ -869,25 +934,28 @@ DXV_HD void trace_reference_dm_from(Ray& r, const DirMapView& dm, const DirRaySt
     uint32_t i = cell.begin, hi = end;
     if (!start.live) i = hi;
     if (ABL & 1) { if (i == 0xffffffffu) best.k = 0u; return; }
-    if (hi - i > 8u) {                                                  // the first two steps of the search from the texel's own words
-        const uint32_t mid = i + ((hi - i) >> 1);
-        const bool right = half_bits_to_float(cell.q2) < near;
-        const float q = half_bits_to_float(right ? cell.q3 : cell.q1);
-        if (right) i = mid + 1u; else hi = mid;
-        if (hi - i > 8u) {
-            const uint32_t mid2 = i + ((hi - i) >> 1);
-            if (q < near) i = mid2 + 1u; else hi = mid2;
+    if (dm_reads_start_cells<dm_starts_form(STARTS)>(dm)) i = dm_start_cell_begin(cell, dm.entries, start.live, near);
+    else {
+        if (hi - i > 8u) {                                                  // the first two steps of the search from the texel's own words
+            const uint32_t mid = i + ((hi - i) >> 1);
+            const bool right = half_bits_to_float(cell.q2) < near;
+            const float q = half_bits_to_float(right ? cell.q3 : cell.q1);
+            if (right) i = mid + 1u; else hi = mid;
+            if (hi - i > 8u) {
+                const uint32_t mid2 = i + ((hi - i) >> 1);
+                if (q < near) i = mid2 + 1u; else hi = mid2;
+            }
         }
-    }
-    while (hi - i > 8u) {
-        const uint32_t mid = i + ((hi - i) >> 1);
-        if (dm_entry_r1(dm.entries[mid]) < near) i = mid + 1u; else hi = mid;
-    }
-    // ... and the start table moves the scan's first entry later, never earlier (hints and search name positions in the whole
-    // list and run as before; a ray that is not live stays at the end: the table's start never lies behind it)
-    {
-        const uint32_t from = cell.begin + dm_start_offset(start.startWord, cell.count, cell.r1max, near);
-        if (from > i) i = from;
+        while (hi - i > 8u) {
+            const uint32_t mid = i + ((hi - i) >> 1);
+            if (dm_entry_r1(dm.entries[mid]) < near) i = mid + 1u; else hi = mid;
+        }
+        // ... and the start table moves the scan's first entry later, never earlier (hints and search name positions in the whole
+        // list and run as before; a ray that is not live stays at the end: the table's start never lies behind it)
+        {
+            const uint32_t from = cell.begin + dm_start_offset(start.startWord, cell.count, cell.r1max, near);
+            if (from > i) i = from;
+        }
     }
     DXV_PHASE(1);
     int qn = 0;
@@ -1040,14 +1108,15 @@ template <class Stack, int ABL = 0>
 DXV_HD void trace_reference_dm(Ray& r, const DirMapView& dm, const TriPos* tris, const Stack& stk, int cap, Hit& best, float& bestDet)
 {
     if (ABL & 8) { best.t = kTMax; best.b1 = 0.0f; best.b2 = 0.0f; best.k = 0xffffffffu; best.leaf = -1; return; }
-    const DirRayStart start = dm_ray_start(r.ox, r.oy, r.oz, dm);
-    trace_reference_dm_from<Stack, ABL>(r, dm, start, tris, stk, cap, best, bestDet);
+    // (start cells where the view has them -- a launch that reads the table --, else the canonical cell and the table's word, if any)
+    const DirRayStart start = dm_ray_start<3>(r.ox, r.oy, r.oz, dm);
+    trace_reference_dm_from<Stack, ABL, 0, 3>(r, dm, start, tris, stk, cap, best, bestDet);
 }
 
 template <class Stack, int ABL>
 DXV_HD void trace_reference_lists(Ray& r, const SceneView& sc, const Stack& stk, int cap, Hit& best, float& bestDet)
 {
-    const DirMapView dm{static_cast<const DirCell*>(sc.dmCells), static_cast<const DirEntry*>(sc.dmEntries), sc.dmR, sc.dmCoop, sc.dmStarts};
+    const DirMapView dm{static_cast<const DirCell*>(sc.dmCells), static_cast<const DirEntry*>(sc.dmEntries), sc.dmR, sc.dmCoop, sc.dmStarts, static_cast<const DirCell*>(sc.dmStartCells)};
     trace_reference_dm<Stack, ABL>(r, dm, sc.triPos, stk, cap, best, bestDet);
 }
 

@@ -174,11 +174,11 @@ static int build_lists_into(dxv_ctx* c, Lists& l, hipStream_t stream, uint64_t f
 
     // the max-mip of the texels' far radii goes with the lists (a launch's work queue is probed against it)
     if ((e = dirmap_mip(l.cells.p, R, l.mip.p, stream)) != hipSuccess) return bail(e, "dirmap_mip");
-    // ... and so does the start table (a function of cells and entries: inside the build's second pair of events, list_ms)
+    // ... and so do the start table and the start cells (a function of cells and entries: inside the build's second pair of events, list_ms)
     // (one page-locked pair for every build and import: nothing else writes it between this copy and the settle() that reads it --
     // builds beside working lists are never deferred, an import synchronises, and a deferred build is settled before the next one starts)
     l.startsPay = false;
-    if ((e = dirmap_starts(l.cells.p, R, l.entries.p, l.starts.p, stream)) != hipSuccess) return bail(e, "dirmap_starts");
+    if ((e = dirmap_starts(l.cells.p, R, l.entries.p, l.starts.p, l.startCells.p, stream)) != hipSuccess) return bail(e, "dirmap_starts");
     if ((e = hipMemcpyAsync(c->pin->listStarts, l.starts.p + 6 * (size_t)R * R, sizeof(c->pin->listStarts), hipMemcpyDeviceToHost, stream)) != hipSuccess) return bail(e, "hipMemcpyAsync");
     if ((e = hipEventRecord(c->evList[3], stream)) != hipSuccess) return bail(e, "hipEventRecord");
     // scratch that is not kept (over 16 GiB) is freed here: hipFree waits for the device

@@ -643,6 +643,7 @@ struct SceneView {
     const uint32_t* plEntries;  // triangle slots
     uint32_t plR;
     const uint32_t* dmStarts;   // start table of the direction-space lists (dxv_dirmap.h: dm_start_word), one word per texel; NULL: none (option starttable)
+    const void* dmStartCells;   // ... and their start cells (dxv_dirmap.h: dm_start_cell), DirCell[6 R R]: set and NULL with dmStarts; what the kernels that read the table read
 };
 
 template <class Stack, int ABL = 0>

@@ -97,7 +97,8 @@ __device__ __forceinline__ bool queue_item(const QueueLens& q, uint32_t cap, uin
 // k_voxelize<Brick<4,4,4>, 16, 0, TEXELS, 4>; the 64 result bytes of a brick leave as 16 dwords (one per 4-voxel row,
 // assembled from the wave's ballot) instead of 64 bytes.
 // ---------------------------------------------------------------------------------------------
-// (the body; STARTS: compiled to read the lists' start table -- dm_ray_start, dxv_dirmap.h -- or as if there were none)
+// (the body; STARTS: compiled to read the lists' START CELLS -- the cells with the start table's word in them: dm_ray_start<2>, dxv_dirmap.h --
+// or the canonical cells, as if there were no table)
 template <bool TEXELS, bool STARTS>
 __device__ __forceinline__ void queue_bricks(const VoxelizeParams& p)
 {
@@ -183,6 +184,7 @@ __device__ __forceinline__ void queue_bricks(const VoxelizeParams& p)
             sc.nodes = nullptr; sc.wide = nullptr; sc.plCells = nullptr; sc.plEntries = nullptr; sc.plR = 0;
             sc.triPos = pp->scene.triPos; sc.triNrm = pp->scene.triNrm;
             sc.dmCells = pp->scene.dmCells; sc.dmEntries = pp->scene.dmEntries; sc.dmR = pp->scene.dmR; sc.dmCoop = pp->scene.dmCoop; sc.dmStarts = pp->scene.dmStarts;
+            sc.dmStartCells = STARTS ? pp->scene.dmStartCells : nullptr;
 #pragma unroll
             for (int a = 0; a < 3; ++a) { sc.rootLo[a] = pp->scene.rootLo[a]; sc.rootHi[a] = pp->scene.rootHi[a]; }
             // (the brick's set-up, down to origin_leaves_root: written out once more in k_voxelize_listed -- one helper for both changes both kernels' instruction streams)
@@ -200,8 +202,8 @@ __device__ __forceinline__ void queue_bricks(const VoxelizeParams& p)
             // raygenMain for the 64 voxels of the brick (voxel_reference<4>, dxv_trace.h, with its first step made by all lanes)
             Ray r;
             ray_origin(N, ix, iy, iz, r.ox, r.oy, r.oz);
-            const DirMapView dm{static_cast<const DirCell*>(sc.dmCells), static_cast<const DirEntry*>(sc.dmEntries), sc.dmR, sc.dmCoop, sc.dmStarts};
-            DirRayStart start = dm_ray_start<STARTS>(r.ox, r.oy, r.oz, dm);
+            const DirMapView dm{static_cast<const DirCell*>(sc.dmCells), static_cast<const DirEntry*>(sc.dmEntries), sc.dmR, sc.dmCoop, sc.dmStarts, static_cast<const DirCell*>(sc.dmStartCells)};
+            DirRayStart start = dm_ray_start<STARTS ? 2 : 0>(r.ox, r.oy, r.oz, dm);
             wAhead = 0xffffffffu;
             if (ahead) {
                 next = (uint32_t)__builtin_amdgcn_readlane((int)jv, 0);  // the next brick's number
@@ -218,7 +220,7 @@ __device__ __forceinline__ void queue_bricks(const VoxelizeParams& p)
             Hit best;
             float bestDet = 1.0f;
             const StridedStack stk{stack + tid, 64};
-            trace_reference_dm_from<StridedStack, 0, TEXELS ? 0 : 2>(r, dm, start, sc.triPos, stk, 16, best, bestDet);
+            trace_reference_dm_from<StridedStack, 0, TEXELS ? 0 : 2, STARTS ? 2 : 0>(r, dm, start, sc.triPos, stk, 16, best, bestDet);
             // The add for the brick AFTER the next one, here: vector memory answers in order, so an add asked for right in front of a
             // brick's first load makes that load wait for the add's 1.1 - 1.3 us instead of its own 0.8 -- asked for behind the scan,
             // it has the predicate, the stores and the next brick's ray set-up (nine divisions) to come back in.
@@ -266,7 +268,7 @@ __device__ __forceinline__ void queue_bricks(const VoxelizeParams& p)
     (void)p;
 #endif
 }
-// ... as kernels: for launches whose lists have a start table the launch reads, and for launches without (_plain)
+// ... as kernels: for launches whose lists have a start table the launch reads (through the start cells), and for launches without (_plain)
 template <bool TEXELS> __global__ __launch_bounds__(64, 6) void k_voxelize_queue(VoxelizeParams p) { queue_bricks<TEXELS, true>(p); }
 template <bool TEXELS> __global__ __launch_bounds__(64, 6) void k_voxelize_queue_plain(VoxelizeParams p) { queue_bricks<TEXELS, false>(p); }
 
@@ -349,8 +351,8 @@ __device__ __forceinline__ void listed_brick(const VoxelizeParams& p, const Queu
     asm volatile("" :: "s"(lens.len[0]), "s"(lens.len[1]), "s"(lens.len[2]), "s"(lens.len[3]), "s"(lens.len[4]), "s"(lens.len[5]), "s"(lens.len[6]), "s"(lens.len[7]),
                  "s"(lens.heavy[0]), "s"(lens.heavy[1]), "s"(lens.heavy[2]), "s"(lens.heavy[3]), "s"(lens.heavy[4]), "s"(lens.heavy[5]), "s"(lens.heavy[6]),
                  "s"(lens.heavy[7]), "s"(clr.blocks), "s"(clr.where), "s"(clr.live), "s"(gridDim.x), "s"(p.queueSlots), "s"(p.queueCap));
-    asm volatile("" :: "s"(p.N), "s"(p.z0), "s"(p.nz), "s"(p.zBlock), "s"(p.zPeriod), "s"(p.zShift), "s"(p.scene.dmCells), "s"(p.scene.dmEntries), "s"(p.scene.dmR),
-                 "s"(p.scene.dmCoop), "s"(p.scene.dmStarts), "s"(p.scene.triPos), "s"(p.grid), "s"(p.scene.rootLo[0]), "s"(p.scene.rootLo[1]), "s"(p.scene.rootLo[2]),
+    asm volatile("" :: "s"(p.N), "s"(p.z0), "s"(p.nz), "s"(p.zBlock), "s"(p.zPeriod), "s"(p.zShift), "s"(STARTS ? p.scene.dmStartCells : p.scene.dmCells), "s"(p.scene.dmEntries), "s"(p.scene.dmR),
+                 "s"(p.scene.dmCoop), "s"(STARTS ? p.scene.dmStartCells : static_cast<const void*>(p.scene.dmStarts)), "s"(p.scene.triPos), "s"(p.grid), "s"(p.scene.rootLo[0]), "s"(p.scene.rootLo[1]), "s"(p.scene.rootLo[2]),
                  "s"(p.scene.rootHi[0]), "s"(p.scene.rootHi[1]), "s"(p.scene.rootHi[2]));
     uint32_t wg = blockIdx.x;
     if (clr.blocks) {
@@ -397,8 +399,8 @@ __device__ __forceinline__ void listed_brick(const VoxelizeParams& p, const Queu
     const uint32_t iz = global_slice(p.z0, nz, p.zBlock, p.zShift, p.zPeriod, lz);
     Ray r;
     ray_origin(N, ix, iy, iz, r.ox, r.oy, r.oz);
-    const DirMapView dm{static_cast<const DirCell*>(sc.dmCells), static_cast<const DirEntry*>(sc.dmEntries), sc.dmR, sc.dmCoop, sc.dmStarts};
-    DirRayStart start = dm_ray_start<STARTS>(r.ox, r.oy, r.oz, dm);
+    const DirMapView dm{static_cast<const DirCell*>(sc.dmCells), static_cast<const DirEntry*>(sc.dmEntries), sc.dmR, sc.dmCoop, sc.dmStarts, static_cast<const DirCell*>(STARTS ? sc.dmStartCells : nullptr)};
+    DirRayStart start = dm_ray_start<STARTS ? 2 : 0>(r.ox, r.oy, r.oz, dm);
     if (origin_leaves_root(r.ox, r.oy, r.oz, sc.rootLo, sc.rootHi)) start.live = false;
     Hit best;
     float bestDet = 1.0f;
@@ -408,7 +410,7 @@ __device__ __forceinline__ void listed_brick(const VoxelizeParams& p, const Queu
 #endif
     // (with the texel image on, the closest hit's V, W, det and index wait in the LDS column: four registers that cost that variant its
     // seventh wave per SIMD; without it the allocator does better with them in registers: 68 against 74)
-    trace_reference_dm_from<StridedStack, 0, TEXELS ? 1 : 2>(r, dm, start, sc.triPos, stk, 16, best, bestDet);
+    trace_reference_dm_from<StridedStack, 0, TEXELS ? 1 : 2, STARTS ? 2 : 0>(r, dm, start, sc.triPos, stk, 16, best, bestDet);
 #if defined(DXV_PHASE_TIMES)
     const unsigned long long tPhase5_ = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -479,10 +481,10 @@ static uint32_t listed_lds_pad(const VoxelizeParams& p, ListsOccupancy& occ)
     return pad > 0 ? (uint32_t)pad : 0u;
 }
 
-// one workgroup per queued brick (and the clearing ones): the kernel that reads the start table when the launch has one, else the plain one
+// one workgroup per queued brick (and the clearing ones): the kernel that reads the start cells when the launch has a table, else the plain one
 static hipError_t launch_listed(const VoxelizeParams& p, const QueueLens& lens, const ClearShare& clr, uint32_t wgs, ListsOccupancy& occ, hipStream_t s)
 {
-    const bool starts = p.scene.dmStarts != nullptr;
+    const bool starts = p.scene.dmStartCells != nullptr;
     if (p.texels) { if (starts) k_voxelize_listed<true><<<dim3(wgs), dim3(64), 0, s>>>(p, lens, clr); else k_voxelize_listed_plain<true><<<dim3(wgs), dim3(64), 0, s>>>(p, lens, clr); }
     else {
         const uint32_t pad = listed_lds_pad(p, occ);
@@ -527,7 +529,7 @@ hipError_t launch_voxelize_queue(const VoxelizeParams& p, ListsOccupancy& occ, b
     const uint32_t sevenths = p.queueSevenths && p.queueSevenths < 7u ? p.queueSevenths : 7u;
     const uint32_t waves = p.queueWaves ? (p.queueWaves + 7u) & ~7u : (held * sevenths / 7u + 7u) & ~7u;     // (a multiple of 8, at least 8: every head has a home wave)
     if (wavesOut) *wavesOut = waves;
-    const bool starts = p.scene.dmStarts != nullptr;
+    const bool starts = p.scene.dmStartCells != nullptr;
     if (p.texels) { if (starts) k_voxelize_queue<true><<<dim3(waves), dim3(64), 0, s>>>(p); else k_voxelize_queue_plain<true><<<dim3(waves), dim3(64), 0, s>>>(p); }
     else { if (starts) k_voxelize_queue<false><<<dim3(waves), dim3(64), 0, s>>>(p); else k_voxelize_queue_plain<false><<<dim3(waves), dim3(64), 0, s>>>(p); }
     return hipGetLastError();

@@ -37,6 +37,7 @@ SKELETON_CLOSED, SKELETON_BORDER, SKELETON_SPUR = 1, 2, 4     # flags of a branc
 DBG_SORTED_KEYS, DBG_NODES, DBG_TRI_POS, DBG_TRI_NRM, DBG_PARENTS, DBG_NODES32, DBG_NODES64, DBG_LIST_CELLS, DBG_LIST_ENTRIES, DBG_LIST_MIP = range(10)
 DBG_BRICK_EMPTY, DBG_BRICK_SUMMARY = 10, 11         # the display pass's empty-brick flags and the summaries behind them
 DBG_LIST_STARTS = 12                                # the lists' start table: one word per texel
+DBG_LIST_START_CELLS = 13                           # the lists' start cells: the cells with that word in place of the search hints
 
 
 def obj_load(path):
@@ -1207,7 +1208,7 @@ class Voxelizer:
                   DBG_PARENTS: ((2 * T - 1,), np.uint32), DBG_NODES32: ((st["num_nodes"], 8), np.uint32),
                   DBG_NODES64: ((st["num_nodes"], 16), np.uint32),
                   DBG_LIST_CELLS: ((6 * st["list_res"] ** 2, 4), np.uint32), DBG_LIST_ENTRIES: ((st["list_entries"], 4), np.uint32),
-                  DBG_LIST_STARTS: ((6 * st["list_res"] ** 2,), np.uint32),
+                  DBG_LIST_STARTS: ((6 * st["list_res"] ** 2,), np.uint32), DBG_LIST_START_CELLS: ((6 * st["list_res"] ** 2, 4), np.uint32),
                   DBG_LIST_MIP: ((sum(6 * (st["list_res"] >> l) ** 2 for l in range(max(st["list_res"], 1).bit_length())),), np.uint16),
                   DBG_BRICK_EMPTY: (((st["grid_dim"] + 7) // 8,) * 3, np.uint8), DBG_BRICK_SUMMARY: (((st["grid_dim"] + 7) // 8,) * 3, np.uint8)}
         shape, dt = shapes[what]

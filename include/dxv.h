@@ -76,6 +76,9 @@ enum {
 /* ... and one selector more, of what is derived from the lists: 6 R R x uint32, the lists' start table, one word per texel (made with
  * the lists, whatever option starttable says).  Named like the enum's members; a macro because the enum is a closed set of twelve. */
 #define DXV_DBG_LIST_STARTS 12
+/* ... and the lists' start cells, 6 R R x 16 B: every texel's cell of DXV_DBG_LIST_CELLS with its word of the start table in place of the
+ * three search hints (bytes 10 .. 13; bytes 14, 15 zero) -- what the kernels that read the table read.  Made with the table. */
+#define DXV_DBG_LIST_START_CELLS 13
 
 typedef struct dxv_stats {
     uint32_t num_tris, num_verts, num_nodes, tree_height;

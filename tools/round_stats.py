@@ -2,7 +2,11 @@
 """Host replay of the lists kernel's loop per 4x4x4 brick (tests/hostcheck/start_table_check.cpp: the product's own __host__ __device__
 code, in lockstep for the 64 rays of a brick): what a wave issues -- scan rounds and scan load instructions, search loads, triangle
 rounds, flushes -- with the scan beginning where the start search ends ("shipped") and no earlier than the start table's start
-("table").  CPU only.   usage: round_stats.py MESH N R [every n-th brick layer = 16]"""
+("table").  CPU only.   usage: round_stats.py MESH N R [every n-th brick layer = 16]
+       round_stats.py --cells MESH N R [every n-th brick layer = 16] [DIRECT ...]
+--cells: the table kernels' two bodies side by side (tests/hostcheck/start_cells_check.cpp) -- "table": canonical cell, hints, search and the
+table's word; "cells_DIRECT": the start cell alone, lists of up to DIRECT entries (default: the product's kDmStartCellDirect) begin without
+a search -- with scan + search load instructions per brick summed for each."""
 import ctypes as C
 import json
 import os
@@ -19,12 +23,16 @@ NAMES = ["bricks", "scan_rounds", "scan_rounds_with_loads", "scan_load_instructi
          "live_rays"]
 
 
-def library():
-    """the check library, built like tests/conftest.py builds libhostcheck.so"""
+def library(cells=False):
+    """the check library, built like tests/conftest.py builds libhostcheck.so (cells: the one of start_cells_check.cpp, which holds the other's
+    functions too)"""
     d = os.path.join(ROOT, "tests", "hostcheck")
     src, so = os.path.join(d, "start_table_check.cpp"), os.path.join(d, "libstartcheck.so")
     deps = [src, os.path.join(d, "hostcheck.cpp")] + [os.path.join(ROOT, "dxrvoxelizer_amd", "csrc", h)
                                                        for h in ("dxv_math.h", "dxv_trace.h", "dxv_types.h", "dxv_dirmap.h", "dxv_raycast.h", "dxv_policy.h")]
+    if cells:
+        src, so = os.path.join(d, "start_cells_check.cpp"), os.path.join(d, "libstartcells.so")
+        deps.append(src)
     if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(p) for p in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fopenmp", "-ffp-contract=off", "-mavx2", "-mfma",
                                "-Wno-unknown-pragmas", "-o", so, src])
@@ -44,7 +52,42 @@ def library():
     L.st_probe_raw.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, u32p, C.c_void_p]
     L.st_voxelize.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, np.ctypeslib.ndpointer(np.uint8, flags="C"), C.c_void_p]
     L.st_round_stats.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]
+    if cells:
+        L.sc_direct.restype = C.c_uint32
+        L.sc_cells.argtypes = [C.c_void_p, C.c_void_p]
+        L.sc_cells_raw.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.sc_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.sc_probe_raw.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.sc_voxelize.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, np.ctypeslib.ndpointer(np.uint8, flags="C"), C.c_void_p]
+        L.sc_round_stats.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
     return L
+
+
+def main_cells(argv):
+    name, N, R = argv[0], int(argv[1]), int(argv[2])
+    bstep = int(argv[3]) if len(argv) > 3 else 16
+    from oracle import orc
+    from bench import make_mesh
+    L = library(cells=True)
+    directs = [int(a) for a in argv[4:]] or [int(L.sc_direct())]
+    vb, ib, _ = make_mesh(name)
+    _, b = orc.bound(vb)
+    h = L.hc_scene_create(np.ascontiguousarray(vb, np.float32), len(vb), np.ascontiguousarray(ib, np.uint32), len(ib) // 3, b)
+    n = L.hc_dirmap_build(h, R)
+    starts = np.zeros(6 * R * R, np.uint32)
+    L.st_table(h, starts)
+    cells = np.zeros((6 * R * R, 4), np.uint32)
+    L.sc_cells(h, cells.ctypes.data_as(C.c_void_p))
+    res = {"mesh": name, "N": N, "R": R, "entries": int(n), "every_nth_brick_layer": bstep, "buckets": int(L.st_buckets())}
+    for which, ptr, direct in [("table", None, 0)] + [("cells_%d" % d, cells.ctypes.data_as(C.c_void_p), d) for d in directs]:
+        out = np.zeros(len(NAMES), np.uint64)
+        L.sc_round_stats(h, N, bstep, starts.ctypes.data_as(C.c_void_p), ptr, direct, 1, out.ctypes.data_as(C.c_void_p))
+        w = float(out[0]) or 1.0
+        per = {k: round(float(out[i]) / w, 3) for i, k in enumerate(NAMES) if i}
+        per["scan_plus_search_load_instructions"] = round(per["scan_load_instructions"] + per["search_load_instructions"], 3)
+        res[which] = {"per_brick": per, "bricks": int(out[0])}
+    L.hc_scene_destroy(h)
+    print(json.dumps(res))
 
 
 def main():
@@ -70,4 +113,7 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) > 1 and sys.argv[1] == "--cells":
+        main_cells(sys.argv[2:])
+    else:
+        main()
