@@ -231,6 +231,9 @@ struct dxv_ctx {
         // run theirs side by side.  A record's trim() releases what dxv_trim gives back -- the scratch of its making; what was made stays.
         // Made: whether the frame has had the product made, and of which grid version.  have goes with the buffer's content (false while a
         // product that is sized by the grid is being rebuilt: a failed allocation leaves "none yet"), version with the grid (0: being rebuilt).
+        // How a caller reads a buffer of a product -- pointer, byte count, download -- is not the record's business: dxv_products.hip has a
+        // descriptor per buffer (Readable) that names the record which guards it.  Flood, further down, is the part of a record that the two
+        // flood operators share.
         struct Made {
             bool have = false;
             uint64_t version = 0;
@@ -363,49 +366,44 @@ struct dxv_ctx {
             uint64_t cellsTested = 0, voxelsTested = 0;   // of the frame's last partition, as of its last synchronisation (option partstages)
             void trim() { scratch.release(); work.release(); }   // (22 bytes per voxel and the sort's buffers; labels, table and throats themselves stay)
         } part;
-        // geodesic distance (geodesic.hip; dxv_geodesic_async): the map of the frame's grid, and the scratch of its making -- control block, live
-        // flags, queue; the seeds of a list; the words of a path
-        struct Geodesic : Made {
-            DevBuf<uint32_t> map;            // (cap: voxels)
-            DevBuf<uint8_t> scratch;         // (cap: bytes) geodesic_scratch_bytes
+        // Flood: what the two operators that flood the members from seeds in batches of rounds keep alike (geodesic and access, below; their
+        // host side shares its seed handling, its accounting and its work-info getter: dxv_products.hip)
+        struct Flood : Made {
             DevBuf<uint32_t> seeds;          // (cap: indices) the seeds of a list
-            DevBuf<uint32_t> path;           // (cap: words) dxv_geodesic_path: length, status, voxel indices
-            std::vector<uint32_t> list;      // the caller's list, copied before dxv_geodesic_async returns: what the upload reads
-            uint32_t dim = 0;                // grid side of the frame's last map
-            int metric = 0;                  // ... DXV_GEO_FACES / DXV_GEO_CHAMFER, for the batches that follow and for the path
-            uint32_t limit = 0;              // ... its limit (0: none)
+            std::vector<uint32_t> list;      // the caller's list, copied before the operator's _async returns: what the upload reads
             bool pending = false;            // a batch is in the stream whose verdict (fixed point or not) nobody has read yet: the frame's next
-                                             // synchronisation reads it and goes on if need be (settle_geodesic)
-            uint32_t batch = 0;              // ... rounds per batch (option georounds as it stood at dxv_geodesic_async)
-            uint32_t rounds = 0;             // rounds of the frame's last geodesic so far, the confirming one included
+                                             // synchronisation reads it and goes on if need be (settle_geodesic, settle_access)
+            uint32_t batch = 0;              // ... rounds per batch (option georounds / accessrounds as it stood at the operator's _async)
+            uint32_t rounds = 0;             // rounds of the frame's last flood so far, the confirming one included
             uint64_t tilesRun = 0;           // ... the tiles its rounds ran, the most of one round, and the rounds with fewer than kGeoSparseTiles
             uint32_t mostLive = 0, sparseRounds = 0;
             uint64_t seedsUsed = 0, reached = 0, unreached = 0;     // its tally, as of the frame's last synchronisation
-            uint32_t farthest = 0, farthestVoxel = 0xFFFFFFFFu;
+        };
+        // geodesic distance (geodesic.hip; dxv_geodesic_async): the map of the frame's grid, and the scratch of its making -- control block, live
+        // flags, queue; the seeds of a list; the words of a path
+        struct Geodesic : Flood {
+            DevBuf<uint32_t> map;            // (cap: voxels)
+            DevBuf<uint8_t> scratch;         // (cap: bytes) geodesic_scratch_bytes
+            DevBuf<uint32_t> path;           // (cap: words) dxv_geodesic_path: length, status, voxel indices
+            uint32_t dim = 0;                // grid side of the frame's last map
+            int metric = 0;                  // ... DXV_GEO_FACES / DXV_GEO_CHAMFER, for the batches that follow and for the path
+            uint32_t limit = 0;              // ... its limit (0: none)
+            uint32_t farthest = 0, farthestVoxel = 0xFFFFFFFFu;     // the rest of its tally
             void trim() { scratch.release(); seeds.release(); path.release(); }   // (control block, flags and queue, 6 bytes per 8^3 tile, a list's seeds, a path's words; the map itself stays)
         } geo;
         // access radius and intrusion map (access.hip; dxv_access_async): the two maps of the frame's grid and their histograms, and the scratch of
         // their making -- control block, live flags, queue, the radius field and its passes, with the intrusion map a thickness's scratch; the
-        // seeds of a list
-        struct Access : Made {
+        // seeds of a list.  Behind its last batch the frame's synchronisation also enqueues paint and histograms (settle_access).
+        struct Access : Flood {
             DevBuf<uint32_t> map;            // (cap: voxels) A
             DevBuf<uint32_t> intrusion;      // (cap: voxels) I, when asked for
             DevBuf<unsigned long long> hist, histI;      // (cap: bins)
             DevBuf<uint8_t> scratch;         // (cap: bytes) access_scratch_bytes
-            DevBuf<uint32_t> seeds;          // (cap: indices) the seeds of a list
-            std::vector<uint32_t> list;      // the caller's list, copied before dxv_access_async returns: what the upload reads
             uint32_t dim = 0, cap = 0;       // grid side and cap_sq of the frame's last maps
             int of = 0, connectivity = 0;    // ... what they were asked for, for the batches that follow
             bool wantIntrusion = false;      // ... and whether the intrusion map is made with them
             uint32_t cull = 0;               // ... option thickcull as it stood at dxv_access_async, for the paint
-            bool pending = false;            // a batch is in the stream whose verdict (fixed point or not) nobody has read yet: the frame's next
-                                             // synchronisation reads it, goes on if need be, and enqueues paint and histograms behind the last (settle_access)
-            uint32_t batch = 0;              // ... rounds per batch (option accessrounds as it stood at dxv_access_async)
-            uint32_t rounds = 0;             // rounds of the frame's last access so far, the confirming one included
-            uint64_t tilesRun = 0;           // ... the tiles its rounds ran, the most of one round, and the rounds with fewer than kGeoSparseTiles
-            uint32_t mostLive = 0, sparseRounds = 0;
-            uint64_t seedsUsed = 0, reached = 0, unreached = 0;     // its tally, as of the frame's last synchronisation
-            uint32_t widest = 0, widestVoxel = 0xFFFFFFFFu;
+            uint32_t widest = 0, widestVoxel = 0xFFFFFFFFu;         // the rest of its tally
             void trim() { scratch.release(); seeds.release(); }     // (control block, flags, queue, fields and passes; the maps and histograms themselves stay)
         } acc;
         // skeleton graph (skeleton.hip; dxv_skeleton_async): labels and the two tables of the frame's grid, the scratch of their making (four bits

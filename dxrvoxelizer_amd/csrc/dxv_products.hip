@@ -3,7 +3,11 @@
 // kernels: distance.hip, mesh_distance.hip, isosurface.hip, octree.hip, components.hip, measure.hip, thickness.hip, partition.hip, geodesic.hip,
 // access.hip, skeleton.hip, fill.hip, morph.hip, thin.hip), the accessors of what they made, and their halves of a frame's synchronisation.  Each operator has a record in Frame (dxv_ctx.h);
 // what they share is here, in front of them: the refusals (check_whole_grid, check_current), an operator's first and last steps (begin_operator,
-// end_operator, blocking), the download of a product (download_current) and the loop of the operators that run in batches (settle_batched).
+// end_operator, blocking), a stage's own timer pair (StageTimer), the loop of the operators that run in batches (settle_batched), and what the two
+// floods from seeds -- geodesic and access -- have alike: the seeds' refusals, their upload, the account of a batch, the work-info getter
+// (check_seed_args, begin_seeded, upload_seeds, begin_flood, account_flood, flood_work_info).  What a caller READS of a product is a table: one
+// descriptor per buffer (Readable) and three routines (product_ptr, product_bytes, product_download); every dxv_*_device_ptr, dxv_*_bytes and
+// dxv_*_download entry is one line over them.  A new product's buffer is a descriptor and its three entries.
 #include "dxv_ctx.h"
 #include "dxv_mesh_distance.h"
 #include "dxv_fill.h"
@@ -76,6 +80,84 @@ static int download_current(dxv_ctx* c, const char* who, const void* src, size_t
     return 0;
 }
 
+// What a caller reads of a product, one descriptor per buffer.  view: the record that guards the buffer, where the buffer is, its bytes as the
+// record counts them, and whether the product was made with this part of it (the nearest triangles, the throats, the intrusion map are made on
+// request) -- if not, `without` is the refusal, a format of (who, frame).  A buffer sized by a count is handed out as NULL, without a message,
+// when the count is 0 (nullIfEmpty).  The measure alone is stale when another record, its labelling, is (ofLabels), and its size alone says why
+// it is 0 (sizeSpeaks).
+struct View { const Frame::Made* made; const void* p; size_t bytes; bool part = true; };
+struct Readable {
+    const ProductText& text;
+    View (*view)(const Frame&);
+    bool nullIfEmpty = false;
+    const char* without = nullptr;
+    bool ofLabels = false, sizeSpeaks = false;
+};
+static size_t cube(uint32_t n) { return (size_t)n * n * n; }
+static const char kNoTriangles[] = "%s: frame %u's mesh distance field was made without triangles (want_triangles = 0)";
+static const char kNoThroats[] = "%s: frame %u's partition was made without throats (want_throats = 0)";
+static const char kNoIntrusion[] = "%s: the access map of frame %u was made without its intrusion map (call dxv_access with want_intrusion != 0)";
+
+static const Readable kDistanceField = {kDistanceText, [](const Frame& f) { return View{&f.dist, f.dist.field.p, cube(f.dist.dim) * sizeof(int32_t)}; }};
+static const Readable kMeshField = {kMeshDistanceText, [](const Frame& f) { return View{&f.mdist, f.mdist.field.p, (size_t)f.mdist.dim * f.mdist.dim * f.mdist.nz * sizeof(float)}; }};
+static const Readable kMeshTriangles = {kMeshDistanceText, [](const Frame& f) { return View{&f.mdist, f.mdist.tri.p, (size_t)f.mdist.dim * f.mdist.dim * f.mdist.nz * sizeof(uint32_t), f.mdist.hasTri}; },
+                                        false, kNoTriangles};
+static const Readable kIsoVertices = {kIsoText, [](const Frame& f) { return View{&f.iso, f.iso.vb.p, (size_t)f.iso.vertices * sizeof(IsoVertex)}; }, true};
+static const Readable kIsoIndices = {kIsoText, [](const Frame& f) { return View{&f.iso, f.iso.ib.p, (size_t)f.iso.triangles * 3u * sizeof(uint32_t)}; }, true};
+static const Readable kOctreeNodes = {kOctreeText, [](const Frame& f) { return View{&f.oct, f.oct.nodes.p, (size_t)f.oct.count * 2u * sizeof(uint32_t)}; }};
+static const Readable kCompLabels = {kComponentsText, [](const Frame& f) { return View{&f.comp, f.comp.labels.p, cube(f.comp.dim) * sizeof(uint32_t)}; }};
+static const Readable kCompTable = {kComponentsText, [](const Frame& f) { return View{&f.comp, f.comp.table.p, (size_t)f.comp.count * sizeof(CompRecord)}; }, true};
+static const Readable kMeasureTable = {kMeasureText, [](const Frame& f) { return View{&f.comp.measure, f.comp.measure.table.p, measure_table_bytes(f.comp.measure.count)}; },
+                                       false, nullptr, true, true};
+static const Readable kThickMap = {kThicknessText, [](const Frame& f) { return View{&f.thick, f.thick.map.p, cube(f.thick.dim) * sizeof(uint32_t)}; }};
+static const Readable kThickHistogram = {kThicknessText, [](const Frame& f) { return View{&f.thick, f.thick.hist.p, thickness_histogram_bytes(f.thick.cap)}; }};
+static const Readable kPartLabels = {kPartitionText, [](const Frame& f) { return View{&f.part, f.part.labels.p, cube(f.part.dim) * sizeof(uint32_t)}; }};
+static const Readable kPartTable = {kPartitionText, [](const Frame& f) { return View{&f.part, f.part.table.p, (size_t)f.part.regions * sizeof(PartRegion)}; }, true};
+static const Readable kPartThroats = {kPartitionText, [](const Frame& f) { return View{&f.part, f.part.throats.p, (size_t)f.part.throatCount * sizeof(PartThroat), f.part.hasThroats}; },
+                                      true, kNoThroats};
+static const Readable kSkelLabels = {kSkeletonText, [](const Frame& f) { return View{&f.skel, f.skel.labels.p, cube(f.skel.dim) * sizeof(uint32_t)}; }};
+static const Readable kSkelNodes = {kSkeletonText, [](const Frame& f) { return View{&f.skel, f.skel.nodes.p, (size_t)f.skel.nodeCount * sizeof(SkelNode)}; }, true};
+static const Readable kSkelBranches = {kSkeletonText, [](const Frame& f) { return View{&f.skel, f.skel.branches.p, (size_t)f.skel.branchCount * sizeof(SkelBranch)}; }, true};
+static const Readable kGeoMap = {kGeodesicText, [](const Frame& f) { return View{&f.geo, f.geo.map.p, cube(f.geo.dim) * sizeof(uint32_t)}; }};
+static const Readable kAccMap = {kAccessText, [](const Frame& f) { return View{&f.acc, f.acc.map.p, cube(f.acc.dim) * sizeof(uint32_t)}; }};
+static const Readable kAccHistogram = {kAccessText, [](const Frame& f) { return View{&f.acc, f.acc.hist.p, thickness_histogram_bytes(f.acc.cap)}; }};
+static const Readable kIntrusionMap = {kAccessText, [](const Frame& f) { return View{&f.acc, f.acc.intrusion.p, cube(f.acc.dim) * sizeof(uint32_t), f.acc.wantIntrusion}; },
+                                       false, kNoIntrusion};
+static const Readable kIntrusionHistogram = {kAccessText, [](const Frame& f) { return View{&f.acc, f.acc.histI.p, thickness_histogram_bytes(f.acc.cap), f.acc.wantIntrusion}; },
+                                             false, kNoIntrusion};
+
+// whether the selected frame has this buffer to hand out, and *v, what it is: 0, or 1 -- with the reason as the message where an entry asks in
+// its own name, without a word for who = nullptr
+static int readable(const dxv_ctx* c, const char* who, const Readable& d, View* v)
+{
+    const Frame& f = cur_frame(c);
+    *v = d.view(f);
+    Frame::Made made = *v->made;
+    if (d.ofLabels && f.comp.version != f.gridVersion) made.version = 0;    // (a measure of labels that are stale is stale)
+    if (!who) return made.current(f) && v->part ? 0 : 1;
+    if (check_current(c, who, made, d.text)) return 1;
+    if (!v->part) return fail(const_cast<dxv_ctx*>(c), d.without, who, c->cur);
+    return 0;
+}
+// dxv_*_device_ptr, dxv_*_bytes and dxv_*_download.  A download refuses in this order: the product, the part, the byte count (download_current).
+static const void* product_ptr(const dxv_ctx* c, const char* who, const Readable& d)
+{
+    View v;
+    if (!c || readable(c, who, d, &v)) return nullptr;
+    return d.nullIfEmpty && !v.bytes ? nullptr : v.p;
+}
+static size_t product_bytes(const dxv_ctx* c, const char* who, const Readable& d)
+{
+    View v;
+    return !c || readable(c, d.sizeSpeaks ? who : nullptr, d, &v) ? 0 : v.bytes;
+}
+static int product_download(dxv_ctx* c, const char* who, const Readable& d, void* host, size_t bytes)
+{
+    View v;
+    if (!c || readable(c, who, d, &v)) return 1;
+    return download_current(c, who, v.p, v.bytes, host, bytes);
+}
+
 // dxv_*_ms: the time the selected frame's last synchronisation read from one of its timers
 static int timer_ms(dxv_ctx* c, const char* who, TimerUse use, float* ms)
 {
@@ -105,6 +187,17 @@ static int end_operator(dxv_ctx* c, Frame& f, hipStream_t fs, Timer* t, void* wo
 }
 // dxv_x(...) is dxv_x_async(...) and a synchronisation of the frame
 static int blocking(dxv_ctx* c, int enqueued) { return enqueued ? 1 : dxv_sync(c); }
+
+// A stage's own timer pair inside an operator that times the whole as well (options thickstages, partstages): recorded only for a caller that
+// measures -- events on and the option set; for everybody else the stage reads 0 ms
+struct StageTimer {
+    Timer& t;
+    bool staged;
+    hipStream_t fs;
+    hipError_t begin() const { if (!staged) t.ms = 0.0f; return timer_begin(t, staged, fs); }
+    hipError_t end() const { return timer_end(t, staged, fs); }
+};
+static StageTimer stage_timer(const dxv_ctx* c, Frame& f, int slot, int option, hipStream_t fs) { return {f.timers[slot], c->opt.events != 0 && option != 0, fs}; }
 
 // dxv_sync of one frame (sync_launch, once the stream has been waited for): the counters a select, a morph and a thickness left in page-locked words
 void read_products(dxv_ctx* c, uint32_t i)
@@ -223,8 +316,21 @@ int settle_thin(dxv_ctx* c, uint32_t i)
         });
 }
 
-// the geodesic's: word k of the control block is the number of live tiles of round k; a further batch is rounds from the flags the frame's
-// scratch still holds, then the tally again, which is read behind the confirming round only
+// The two floods from seeds, geodesic and access: word k of a batch's control block is the number of live tiles of round k, and the tally
+// behind the rounds -- {seeds used, reached, unreached, the operator's own key} -- is read behind the confirming round only.  What the batch's
+// live rounds ran (dxv_*_work_info), the rounds so far, and behind the last one the three counts of the tally that both keep:
+static void account_flood(Frame::Flood& o, const GeoControl& ctl, uint32_t live, bool last)
+{
+    for (uint32_t k = 0; k < live; ++k) {
+        o.tilesRun += ctl.live[k];
+        if (ctl.live[k] > o.mostLive) o.mostLive = ctl.live[k];
+        if (ctl.live[k] < kGeoSparseTiles) ++o.sparseRounds;
+    }
+    o.rounds += last ? live + 1u : o.batch;
+    if (last) { o.seedsUsed = ctl.tally[0]; o.reached = ctl.tally[1]; o.unreached = ctl.tally[2]; }
+}
+
+// the geodesic's: a further batch is rounds from the flags the frame's scratch still holds, then the tally again
 int settle_geodesic(dxv_ctx* c, uint32_t i)
 {
     Frame& f = c->frames[i];
@@ -234,15 +340,9 @@ int settle_geodesic(dxv_ctx* c, uint32_t i)
     const Batched b{"dxv_geodesic", "rounds", kTimerGeodesic, N, &o.pending, o.batch, &o.batch, &o.rounds, &ctl, o.scratch.p, sizeof(GeoControl)};
     return settle_batched(c, i, b,
         [&](uint32_t live, bool last) {
-            for (uint32_t k = 0; k < live; ++k) {                       // what the batch's live rounds ran (dxv_geodesic_work_info)
-                o.tilesRun += ctl.live[k];
-                if (ctl.live[k] > o.mostLive) o.mostLive = ctl.live[k];
-                if (ctl.live[k] < kGeoSparseTiles) ++o.sparseRounds;
-            }
-            o.rounds += last ? live + 1u : o.batch;
+            account_flood(o, ctl, live, last);
             if (last) {
                 const GeoTally tally{ctl.tally[0], ctl.tally[1], ctl.tally[2], ctl.tally[3]};
-                o.seedsUsed = tally.seeds; o.reached = tally.reached; o.unreached = tally.unreached;
                 o.farthest = geo_tally_farthest(tally); o.farthestVoxel = geo_tally_farthest_voxel(tally);
             }
             return last;
@@ -286,15 +386,9 @@ int settle_access(dxv_ctx* c, uint32_t i)
     const Batched b{"dxv_access", "rounds", kTimerAccess, N, &o.pending, o.batch, &o.batch, &o.rounds, &ctl, o.scratch.p, sizeof(GeoControl)};
     const int r = settle_batched(c, i, b,
         [&](uint32_t live, bool last) {
-            for (uint32_t k = 0; k < live; ++k) {                       // what the batch's live rounds ran (dxv_access_work_info)
-                o.tilesRun += ctl.live[k];
-                if (ctl.live[k] > o.mostLive) o.mostLive = ctl.live[k];
-                if (ctl.live[k] < kGeoSparseTiles) ++o.sparseRounds;
-            }
-            o.rounds += last ? live + 1u : o.batch;
+            account_flood(o, ctl, live, last);
             if (last) {
                 const AccTally tally{ctl.tally[0], ctl.tally[1], ctl.tally[2], ctl.tally[3]};
-                o.seedsUsed = tally.seeds; o.reached = tally.reached; o.unreached = tally.unreached;
                 o.widest = acc_tally_widest(tally); o.widestVoxel = acc_tally_widest_voxel(tally);
                 finished = finish_access(c, i);
             }
@@ -315,6 +409,69 @@ int settle_expand(dxv_ctx* c, uint32_t i)
     DXV_HIP(c, hipMemsetAsync(f.status.p + kOctStatusWord, 0, sizeof(uint32_t), frame_stream(c, i)));
     return fail(c, "dxv_octree_expand: the tree given for frame %u cannot be followed (a child index at or beyond its node count, or cells still mixed "
                    "after all its levels); the voxels behind such an index were left empty", i);
+}
+
+// The seeds of a flood, as dxv_geodesic_async and dxv_access_async take them.  What is refused of them in front of check_whole_grid ...
+static int check_seed_args(dxv_ctx* c, const char* who, int kind, const void* seeds, uint32_t count)
+{
+    if (kind != DXV_GEO_SEEDS_BORDER && kind != DXV_GEO_SEEDS_LIST && kind != DXV_GEO_SEEDS_MASK)
+        return fail(c, "%s: unknown seed kind %d (DXV_GEO_SEEDS_BORDER = 0, DXV_GEO_SEEDS_LIST = 1, DXV_GEO_SEEDS_MASK = 2)", who, kind);
+    if (kind == DXV_GEO_SEEDS_LIST && count && !seeds) return fail(c, "%s: a list of %u seeds at NULL", who, count);
+    if (kind == DXV_GEO_SEEDS_MASK && !seeds) return fail(c, "%s: the seed mask is NULL", who);
+    return 0;
+}
+// ... and behind the refusals of the grid's size, as the operator's first step: begin_operator's steps with the device in front of the range
+// check of a mask -- a list's values against the grid, the device, a mask's range, then the host-wait rule (a pending fill, thin, expansion or
+// flood of the frame first) and the frame's stream
+static int begin_seeded(dxv_ctx* c, const char* who, int kind, const void* seeds, uint32_t count, uint32_t N, hipStream_t* fs)
+{
+    const size_t voxels = cube(N);
+    if (kind == DXV_GEO_SEEDS_LIST) {
+        const uint32_t* list = static_cast<const uint32_t*>(seeds);
+        for (uint32_t k = 0; k < count; ++k)
+            if (list[k] >= voxels) return fail(c, "%s: seed %u is voxel %u, outside the grid of %u^3 = %zu voxels", who, k, list[k], N, voxels);
+    }
+    DXV_HIP(c, hipSetDevice(c->device));
+    if (kind == DXV_GEO_SEEDS_MASK) {
+        size_t room = 0;
+        const int r = check_device_range(c, who, seeds, voxels, &room);
+        if (r == 2) return fail(c, "%s: the seed mask has %zu bytes from %p on, the grid has %zu voxels", who, room, seeds, voxels);
+        if (r) return 1;
+    }
+    if (settle_frame_launch(c)) return 1;
+    *fs = cur_stream(c);
+    return 0;
+}
+// ... and what the init kernel is given: a mask as it is; a list as the frame's own copy (no flood of the frame is in flight:
+// settle_frame_launch), uploaded from there -- nullptr for an empty one
+static int upload_seeds(dxv_ctx* c, Frame::Flood& o, int kind, const void* seeds, uint32_t count, hipStream_t fs, const void** deviceSeeds)
+{
+    *deviceSeeds = seeds;
+    if (kind != DXV_GEO_SEEDS_LIST) return 0;
+    const uint32_t* list = static_cast<const uint32_t*>(seeds);
+    o.list.assign(list, list + count);
+    *deviceSeeds = nullptr;
+    if (count) {
+        DXV_HIP(c, o.seeds.reserve(count, align256((size_t)count * sizeof(uint32_t)), fs));
+        DXV_HIP(c, hipMemcpyAsync(o.seeds.p, o.list.data(), (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, fs));
+        *deviceSeeds = o.seeds.p;
+    }
+    return 0;
+}
+// a flood starts: rounds per batch from its option (0: the operator's default), nothing run yet
+static void begin_flood(Frame::Flood& o, int option, uint32_t roundsDefault)
+{
+    o.batch = option ? (uint32_t)option : roundsDefault;
+    o.rounds = 0; o.tilesRun = 0; o.mostLive = 0; o.sparseRounds = 0;
+}
+// dxv_geodesic_work_info, dxv_access_work_info
+static int flood_work_info(dxv_ctx* c, const char* who, const Frame::Flood& o, const ProductText& text, uint64_t* tiles_run, uint32_t* most_live_tiles, uint32_t* sparse_rounds)
+{
+    if (check_current(c, who, o, text)) return 1;
+    if (tiles_run) *tiles_run = o.tilesRun;
+    if (most_live_tiles) *most_live_tiles = o.mostLive;
+    if (sparse_rounds) *sparse_rounds = o.sparseRounds;
+    return 0;
 }
 
 } // namespace dxvhost
@@ -347,22 +504,9 @@ int dxv_distance_async(dxv_ctx* c, int format)
 
 int dxv_distance(dxv_ctx* c, int format) { return blocking(c, dxv_distance_async(c, format)); }
 
-const void* dxv_distance_device_ptr(const dxv_ctx* c)
-{
-    if (!c || check_current(c, "dxv_distance_device_ptr", cur_frame(c).dist, kDistanceText)) return nullptr;
-    return cur_frame(c).dist.field.p;
-}
-size_t dxv_distance_bytes(const dxv_ctx* c)
-{
-    if (!c) return 0;
-    const Frame::Distance& d = cur_frame(c).dist;
-    return d.current(cur_frame(c)) ? (size_t)d.dim * d.dim * d.dim * sizeof(int32_t) : 0;
-}
-int dxv_distance_download(dxv_ctx* c, void* host, size_t bytes)
-{
-    if (!c || check_current(c, "dxv_distance_download", cur_frame(c).dist, kDistanceText)) return 1;
-    return download_current(c, "dxv_distance_download", cur_frame(c).dist.field.p, dxv_distance_bytes(c), host, bytes);
-}
+const void* dxv_distance_device_ptr(const dxv_ctx* c) { return product_ptr(c, "dxv_distance_device_ptr", kDistanceField); }
+size_t dxv_distance_bytes(const dxv_ctx* c) { return product_bytes(c, "dxv_distance_bytes", kDistanceField); }
+int dxv_distance_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_distance_download", kDistanceField, host, bytes); }
 
 int dxv_distance_ms(dxv_ctx* c, float* ms) { return timer_ms(c, "dxv_distance_ms", kTimerDistance, ms); }
 
@@ -409,34 +553,12 @@ int dxv_mesh_distance_async(dxv_ctx* c, int format, uint32_t bandVoxels, int wan
 
 int dxv_mesh_distance(dxv_ctx* c, int format, uint32_t bandVoxels, int wantTriangles) { return blocking(c, dxv_mesh_distance_async(c, format, bandVoxels, wantTriangles)); }
 
-// the frame's mesh distance field (triangles: its nearest triangles), or the reason there is none to hand out: NULL + message
-static const void* current_mesh_field(const dxv_ctx* c, const char* who, bool triangles)
-{
-    const Frame::MeshDistance& m = cur_frame(c).mdist;
-    if (check_current(c, who, m, kMeshDistanceText)) return nullptr;
-    if (triangles && !m.hasTri) { (void)fail(const_cast<dxv_ctx*>(c), "%s: frame %u's mesh distance field was made without triangles (want_triangles = 0)", who, c->cur); return nullptr; }
-    return triangles ? static_cast<const void*>(m.tri.p) : static_cast<const void*>(m.field.p);
-}
-
-const void* dxv_mesh_distance_device_ptr(const dxv_ctx* c) { return c ? current_mesh_field(c, "dxv_mesh_distance_device_ptr", false) : nullptr; }
-const void* dxv_mesh_distance_triangles_device_ptr(const dxv_ctx* c) { return c ? current_mesh_field(c, "dxv_mesh_distance_triangles_device_ptr", true) : nullptr; }
-
-size_t dxv_mesh_distance_bytes(const dxv_ctx* c)
-{
-    if (!c) return 0;
-    const Frame::MeshDistance& m = cur_frame(c).mdist;
-    return m.current(cur_frame(c)) ? (size_t)m.dim * m.dim * m.nz * sizeof(float) : 0;
-}
-
-static int mesh_field_download(dxv_ctx* c, const char* who, bool triangles, void* host, size_t bytes)
-{
-    if (!c) return 1;
-    const void* field = current_mesh_field(c, who, triangles);
-    if (!field) return 1;
-    return download_current(c, who, field, dxv_mesh_distance_bytes(c), host, bytes);
-}
-int dxv_mesh_distance_download(dxv_ctx* c, void* host, size_t bytes) { return mesh_field_download(c, "dxv_mesh_distance_download", false, host, bytes); }
-int dxv_mesh_distance_triangles_download(dxv_ctx* c, void* host, size_t bytes) { return mesh_field_download(c, "dxv_mesh_distance_triangles_download", true, host, bytes); }
+// (the nearest triangles have the field's size: there is no size of their own)
+const void* dxv_mesh_distance_device_ptr(const dxv_ctx* c) { return product_ptr(c, "dxv_mesh_distance_device_ptr", kMeshField); }
+const void* dxv_mesh_distance_triangles_device_ptr(const dxv_ctx* c) { return product_ptr(c, "dxv_mesh_distance_triangles_device_ptr", kMeshTriangles); }
+size_t dxv_mesh_distance_bytes(const dxv_ctx* c) { return product_bytes(c, "dxv_mesh_distance_bytes", kMeshField); }
+int dxv_mesh_distance_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_mesh_distance_download", kMeshField, host, bytes); }
+int dxv_mesh_distance_triangles_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_mesh_distance_triangles_download", kMeshTriangles, host, bytes); }
 
 int dxv_mesh_distance_ms(dxv_ctx* c, float* ms) { return timer_ms(c, "dxv_mesh_distance_ms", kTimerMeshDistance, ms); }
 
@@ -509,27 +631,11 @@ int dxv_isosurface_counts(dxv_ctx* c, uint32_t* vertices, uint32_t* triangles)
     return 0;
 }
 
-const void* dxv_isosurface_vertices_device_ptr(const dxv_ctx* c)
-{
-    if (!c || check_current(c, "dxv_isosurface_vertices_device_ptr", cur_frame(c).iso, kIsoText)) return nullptr;
-    return cur_frame(c).iso.vertices ? cur_frame(c).iso.vb.p : nullptr;
-}
-const void* dxv_isosurface_indices_device_ptr(const dxv_ctx* c)
-{
-    if (!c || check_current(c, "dxv_isosurface_indices_device_ptr", cur_frame(c).iso, kIsoText)) return nullptr;
-    return cur_frame(c).iso.triangles ? cur_frame(c).iso.ib.p : nullptr;
-}
-
-int dxv_isosurface_vertices_download(dxv_ctx* c, void* host, size_t bytes)
-{
-    if (!c || check_current(c, "dxv_isosurface_vertices_download", cur_frame(c).iso, kIsoText)) return 1;
-    return download_current(c, "dxv_isosurface_vertices_download", cur_frame(c).iso.vb.p, (size_t)cur_frame(c).iso.vertices * sizeof(IsoVertex), host, bytes);
-}
-int dxv_isosurface_indices_download(dxv_ctx* c, void* host, size_t bytes)
-{
-    if (!c || check_current(c, "dxv_isosurface_indices_download", cur_frame(c).iso, kIsoText)) return 1;
-    return download_current(c, "dxv_isosurface_indices_download", cur_frame(c).iso.ib.p, (size_t)cur_frame(c).iso.triangles * 3u * sizeof(uint32_t), host, bytes);
-}
+// (dxv_isosurface_counts gives the sizes: the mesh has no dxv_*_bytes)
+const void* dxv_isosurface_vertices_device_ptr(const dxv_ctx* c) { return product_ptr(c, "dxv_isosurface_vertices_device_ptr", kIsoVertices); }
+const void* dxv_isosurface_indices_device_ptr(const dxv_ctx* c) { return product_ptr(c, "dxv_isosurface_indices_device_ptr", kIsoIndices); }
+int dxv_isosurface_vertices_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_isosurface_vertices_download", kIsoVertices, host, bytes); }
+int dxv_isosurface_indices_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_isosurface_indices_download", kIsoIndices, host, bytes); }
 
 int dxv_isosurface_ms(dxv_ctx* c, float* ms) { return timer_ms(c, "dxv_isosurface_ms", kTimerIso, ms); }
 
@@ -583,24 +689,9 @@ int dxv_octree_info(dxv_ctx* c, uint32_t* levels, uint32_t* nodes, uint32_t leve
     return 0;
 }
 
-const void* dxv_octree_device_ptr(const dxv_ctx* c)
-{
-    if (!c || check_current(c, "dxv_octree_device_ptr", cur_frame(c).oct, kOctreeText)) return nullptr;
-    return cur_frame(c).oct.nodes.p;
-}
-
-size_t dxv_octree_bytes(const dxv_ctx* c)
-{
-    if (!c) return 0;
-    const Frame::Octree& o = cur_frame(c).oct;
-    return o.current(cur_frame(c)) ? (size_t)o.count * 2u * sizeof(uint32_t) : 0;
-}
-
-int dxv_octree_download(dxv_ctx* c, void* host, size_t bytes)
-{
-    if (!c || check_current(c, "dxv_octree_download", cur_frame(c).oct, kOctreeText)) return 1;
-    return download_current(c, "dxv_octree_download", cur_frame(c).oct.nodes.p, dxv_octree_bytes(c), host, bytes);
-}
+const void* dxv_octree_device_ptr(const dxv_ctx* c) { return product_ptr(c, "dxv_octree_device_ptr", kOctreeNodes); }
+size_t dxv_octree_bytes(const dxv_ctx* c) { return product_bytes(c, "dxv_octree_bytes", kOctreeNodes); }
+int dxv_octree_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_octree_download", kOctreeNodes, host, bytes); }
 
 int dxv_octree_ms(dxv_ctx* c, float* ms) { return timer_ms(c, "dxv_octree_ms", kTimerOctree, ms); }
 
@@ -693,39 +784,12 @@ int dxv_components_info(dxv_ctx* c, uint32_t* count, int* of, int* connectivity)
     return 0;
 }
 
-const void* dxv_components_labels_device_ptr(const dxv_ctx* c)
-{
-    if (!c || check_current(c, "dxv_components_labels_device_ptr", cur_frame(c).comp, kComponentsText)) return nullptr;
-    return cur_frame(c).comp.labels.p;
-}
-size_t dxv_components_labels_bytes(const dxv_ctx* c)
-{
-    if (!c) return 0;
-    const Frame::Components& k = cur_frame(c).comp;
-    return k.current(cur_frame(c)) ? (size_t)k.dim * k.dim * k.dim * sizeof(uint32_t) : 0;
-}
-const void* dxv_components_table_device_ptr(const dxv_ctx* c)
-{
-    if (!c || check_current(c, "dxv_components_table_device_ptr", cur_frame(c).comp, kComponentsText)) return nullptr;
-    return cur_frame(c).comp.count ? cur_frame(c).comp.table.p : nullptr;
-}
-size_t dxv_components_table_bytes(const dxv_ctx* c)
-{
-    if (!c) return 0;
-    const Frame::Components& k = cur_frame(c).comp;
-    return k.current(cur_frame(c)) ? (size_t)k.count * sizeof(CompRecord) : 0;
-}
-
-int dxv_components_labels_download(dxv_ctx* c, void* host, size_t bytes)
-{
-    if (!c || check_current(c, "dxv_components_labels_download", cur_frame(c).comp, kComponentsText)) return 1;
-    return download_current(c, "dxv_components_labels_download", cur_frame(c).comp.labels.p, dxv_components_labels_bytes(c), host, bytes);
-}
-int dxv_components_table_download(dxv_ctx* c, void* host, size_t bytes)
-{
-    if (!c || check_current(c, "dxv_components_table_download", cur_frame(c).comp, kComponentsText)) return 1;
-    return download_current(c, "dxv_components_table_download", cur_frame(c).comp.table.p, dxv_components_table_bytes(c), host, bytes);
-}
+const void* dxv_components_labels_device_ptr(const dxv_ctx* c) { return product_ptr(c, "dxv_components_labels_device_ptr", kCompLabels); }
+size_t dxv_components_labels_bytes(const dxv_ctx* c) { return product_bytes(c, "dxv_components_labels_bytes", kCompLabels); }
+int dxv_components_labels_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_components_labels_download", kCompLabels, host, bytes); }
+const void* dxv_components_table_device_ptr(const dxv_ctx* c) { return product_ptr(c, "dxv_components_table_device_ptr", kCompTable); }
+size_t dxv_components_table_bytes(const dxv_ctx* c) { return product_bytes(c, "dxv_components_table_bytes", kCompTable); }
+int dxv_components_table_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_components_table_download", kCompTable, host, bytes); }
 
 int dxv_components_ms(dxv_ctx* c, float* ms) { return timer_ms(c, "dxv_components_ms", kTimerComponents, ms); }
 
@@ -759,30 +823,10 @@ int dxv_measure_async(dxv_ctx* c)
 
 int dxv_measure(dxv_ctx* c) { return blocking(c, dxv_measure_async(c)); }
 
-// whether the frame has a measure to hand out: its own version, and its labelling's -- a measure of labels that are stale is stale
-static int current_measure(const dxv_ctx* c, const char* who)
-{
-    const Frame& f = cur_frame(c);
-    Frame::Made made = f.comp.measure;
-    if (f.comp.version != f.gridVersion) made.version = 0;
-    return check_current(c, who, made, kMeasureText);
-}
-
-const void* dxv_measure_table_device_ptr(const dxv_ctx* c)
-{
-    if (!c || current_measure(c, "dxv_measure_table_device_ptr")) return nullptr;
-    return cur_frame(c).comp.measure.table.p;
-}
-size_t dxv_measure_table_bytes(const dxv_ctx* c)
-{
-    if (!c || current_measure(c, "dxv_measure_table_bytes")) return 0;
-    return measure_table_bytes(cur_frame(c).comp.measure.count);
-}
-int dxv_measure_table_download(dxv_ctx* c, void* host, size_t bytes)
-{
-    if (!c || current_measure(c, "dxv_measure_table_download")) return 1;
-    return download_current(c, "dxv_measure_table_download", cur_frame(c).comp.measure.table.p, dxv_measure_table_bytes(c), host, bytes);
-}
+// (the one size that says why it is 0: kMeasureTable)
+const void* dxv_measure_table_device_ptr(const dxv_ctx* c) { return product_ptr(c, "dxv_measure_table_device_ptr", kMeasureTable); }
+size_t dxv_measure_table_bytes(const dxv_ctx* c) { return product_bytes(c, "dxv_measure_table_bytes", kMeasureTable); }
+int dxv_measure_table_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_measure_table_download", kMeasureTable, host, bytes); }
 
 int dxv_measure_ms(dxv_ctx* c, float* ms) { return timer_ms(c, "dxv_measure_ms", kTimerMeasure, ms); }
 
@@ -809,14 +853,12 @@ int dxv_thickness_async(dxv_ctx* c, int of, uint32_t cap_sq)
     ThickParams p{};
     p.of = of; p.cap = cap_sq; p.cull = (uint32_t)c->opt.thickcull; p.count = c->opt.thickstages ? 1u : 0u; p.W = f.thick.map.p; p.hist = f.thick.hist.p;
     thickness_layout(f.thick.scratch.p, N, p);
-    const bool timed = c->opt.events != 0, staged = timed && c->opt.thickstages != 0;      // (the stages' own pairs only for a caller that measures)
-    DXV_HIP(c, timer_begin(f.timers[kTimerThickness], timed, fs));
+    DXV_HIP(c, timer_begin(f.timers[kTimerThickness], c->opt.events != 0, fs));
     for (int stage = 0; stage < THICK_STAGES; ++stage) {
-        Timer& t = f.timers[kTimerThickStage0 + stage];
-        if (!staged) t.ms = 0.0f;
-        DXV_HIP(c, timer_begin(t, staged, fs));
+        const StageTimer t = stage_timer(c, f, kTimerThickStage0 + stage, c->opt.thickstages, fs);
+        DXV_HIP(c, t.begin());
         DXV_HIP(c, launch_thickness_stage(f.grid.p, p, stage, fs));
-        DXV_HIP(c, timer_end(t, staged, fs));
+        DXV_HIP(c, t.end());
     }
     PinnedFrame& pin = cur_pinned(c);
     if (end_operator(c, f, fs, &f.timers[kTimerThickness], pin.thickCount, thickness_counters(p), sizeof(pin.thickCount))) return 1;
@@ -827,33 +869,11 @@ int dxv_thickness_async(dxv_ctx* c, int of, uint32_t cap_sq)
 
 int dxv_thickness(dxv_ctx* c, int of, uint32_t cap_sq) { return blocking(c, dxv_thickness_async(c, of, cap_sq)); }
 
-const void* dxv_thickness_device_ptr(const dxv_ctx* c)
-{
-    if (!c || check_current(c, "dxv_thickness_device_ptr", cur_frame(c).thick, kThicknessText)) return nullptr;
-    return cur_frame(c).thick.map.p;
-}
-size_t dxv_thickness_bytes(const dxv_ctx* c)
-{
-    if (!c) return 0;
-    const Frame::Thickness& t = cur_frame(c).thick;
-    return t.current(cur_frame(c)) ? (size_t)t.dim * t.dim * t.dim * sizeof(uint32_t) : 0;
-}
-int dxv_thickness_download(dxv_ctx* c, void* host, size_t bytes)
-{
-    if (!c || check_current(c, "dxv_thickness_download", cur_frame(c).thick, kThicknessText)) return 1;
-    return download_current(c, "dxv_thickness_download", cur_frame(c).thick.map.p, dxv_thickness_bytes(c), host, bytes);
-}
-size_t dxv_thickness_histogram_bytes(const dxv_ctx* c)
-{
-    if (!c) return 0;
-    const Frame::Thickness& t = cur_frame(c).thick;
-    return t.current(cur_frame(c)) ? thickness_histogram_bytes(t.cap) : 0;
-}
-int dxv_thickness_histogram_download(dxv_ctx* c, void* host, size_t bytes)
-{
-    if (!c || check_current(c, "dxv_thickness_histogram_download", cur_frame(c).thick, kThicknessText)) return 1;
-    return download_current(c, "dxv_thickness_histogram_download", cur_frame(c).thick.hist.p, dxv_thickness_histogram_bytes(c), host, bytes);
-}
+const void* dxv_thickness_device_ptr(const dxv_ctx* c) { return product_ptr(c, "dxv_thickness_device_ptr", kThickMap); }
+size_t dxv_thickness_bytes(const dxv_ctx* c) { return product_bytes(c, "dxv_thickness_bytes", kThickMap); }
+int dxv_thickness_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_thickness_download", kThickMap, host, bytes); }
+size_t dxv_thickness_histogram_bytes(const dxv_ctx* c) { return product_bytes(c, "dxv_thickness_histogram_bytes", kThickHistogram); }
+int dxv_thickness_histogram_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_thickness_histogram_download", kThickHistogram, host, bytes); }
 
 int dxv_thickness_info(dxv_ctx* c, float* ms, uint64_t* centres_painted, uint64_t* work_items)
 {
@@ -901,14 +921,12 @@ int dxv_partition_async(dxv_ctx* c, int of, uint32_t cap_sq, int want_throats)
     p.of = of; p.cap = cap_sq; p.prune = (uint32_t)c->opt.partprune; p.count = c->opt.partstages ? 1u : 0u; p.wantThroats = want_throats ? 1u : 0u;
     partition_layout(o.scratch.p, N, p);
     PinnedFrame& pin = cur_pinned(c);
-    const bool timed = c->opt.events != 0, staged = timed && c->opt.partstages != 0;       // (the stages' own pairs only for a caller that measures)
-    auto stage_begin = [&](int stage) { Timer& t = f.timers[kTimerPartStage0 + stage]; if (!staged) t.ms = 0.0f; return timer_begin(t, staged, fs); };
-    auto stage_end = [&](int stage) { return timer_end(f.timers[kTimerPartStage0 + stage], staged, fs); };
-    DXV_HIP(c, timer_begin(f.timers[kTimerPartition], timed, fs));
+    auto timer_of = [&](int stage) { return stage_timer(c, f, kTimerPartStage0 + stage, c->opt.partstages, fs); };
+    DXV_HIP(c, timer_begin(f.timers[kTimerPartition], c->opt.events != 0, fs));
     for (int stage = PART_STAGE_FIELD; stage <= PART_STAGE_ROOTS; ++stage) {
-        DXV_HIP(c, stage_begin(stage));
+        DXV_HIP(c, timer_of(stage).begin());
         DXV_HIP(c, launch_partition_stage(f.grid.p, p, stage, fs));
-        DXV_HIP(c, stage_end(stage));
+        DXV_HIP(c, timer_of(stage).end());
     }
     DXV_HIP(c, hipMemcpyAsync(pin.partTotals, partition_totals(p), sizeof(pin.partTotals), hipMemcpyDeviceToHost, fs));
     DXV_HIP(c, hipStreamSynchronize(fs));
@@ -920,11 +938,11 @@ int dxv_partition_async(dxv_ctx* c, int of, uint32_t cap_sq, int want_throats)
     DXV_HIP(c, o.work.reserve(work, work, fs));
     p.labels = o.labels.p; p.table = reinterpret_cast<PartRegion*>(o.table.p);
     partition_work_layout(o.work.p, K, faces, p);
-    DXV_HIP(c, stage_begin(PART_STAGE_REGIONS));
+    DXV_HIP(c, timer_of(PART_STAGE_REGIONS).begin());
     DXV_HIP(c, launch_partition_stage(f.grid.p, p, PART_STAGE_REGIONS, fs));
-    DXV_HIP(c, stage_end(PART_STAGE_REGIONS));
+    DXV_HIP(c, timer_of(PART_STAGE_REGIONS).end());
     uint32_t T = 0;
-    DXV_HIP(c, stage_begin(PART_STAGE_THROATS));
+    DXV_HIP(c, timer_of(PART_STAGE_THROATS).begin());
     if (faces) {
         DXV_HIP(c, launch_partition_pairs(p, fs));
         DXV_HIP(c, hipMemcpyAsync(pin.partPairs, partition_pair_total(p), sizeof(pin.partPairs), hipMemcpyDeviceToHost, fs));
@@ -935,7 +953,7 @@ int dxv_partition_async(dxv_ctx* c, int of, uint32_t cap_sq, int want_throats)
             DXV_HIP(c, launch_partition_throats(p, T, o.throats.p, fs));
         }
     }
-    DXV_HIP(c, stage_end(PART_STAGE_THROATS));
+    DXV_HIP(c, timer_of(PART_STAGE_THROATS).end());
     if (end_operator(c, f, fs, &f.timers[kTimerPartition], pin.partCount, partition_counters(p), sizeof(pin.partCount))) return 1;
     o.pending = true;
     o.dim = N; o.cap = cap_sq; o.of = of; o.hasThroats = want_throats != 0; o.regions = K; o.throatCount = T; o.faces = faces;
@@ -957,63 +975,15 @@ int dxv_partition_info(dxv_ctx* c, float* ms, uint32_t* regions, uint32_t* throa
     return 0;
 }
 
-// the frame's partition (throats: with its throats), or 1 with the reason there is none to hand out as the message
-static int current_partition(const dxv_ctx* c, const char* who, bool throats)
-{
-    const Frame::Partition& o = cur_frame(c).part;
-    if (check_current(c, who, o, kPartitionText)) return 1;
-    if (throats && !o.hasThroats) return fail(const_cast<dxv_ctx*>(c), "%s: frame %u's partition was made without throats (want_throats = 0)", who, c->cur);
-    return 0;
-}
-
-const void* dxv_partition_labels_device_ptr(const dxv_ctx* c)
-{
-    if (!c || current_partition(c, "dxv_partition_labels_device_ptr", false)) return nullptr;
-    return cur_frame(c).part.labels.p;
-}
-size_t dxv_partition_labels_bytes(const dxv_ctx* c)
-{
-    if (!c) return 0;
-    const Frame::Partition& o = cur_frame(c).part;
-    return o.current(cur_frame(c)) ? (size_t)o.dim * o.dim * o.dim * sizeof(uint32_t) : 0;
-}
-int dxv_partition_labels_download(dxv_ctx* c, void* host, size_t bytes)
-{
-    if (!c || current_partition(c, "dxv_partition_labels_download", false)) return 1;
-    return download_current(c, "dxv_partition_labels_download", cur_frame(c).part.labels.p, dxv_partition_labels_bytes(c), host, bytes);
-}
-const void* dxv_partition_table_device_ptr(const dxv_ctx* c)
-{
-    if (!c || current_partition(c, "dxv_partition_table_device_ptr", false)) return nullptr;
-    return cur_frame(c).part.regions ? cur_frame(c).part.table.p : nullptr;
-}
-size_t dxv_partition_table_bytes(const dxv_ctx* c)
-{
-    if (!c) return 0;
-    const Frame::Partition& o = cur_frame(c).part;
-    return o.current(cur_frame(c)) ? (size_t)o.regions * sizeof(PartRegion) : 0;
-}
-int dxv_partition_table_download(dxv_ctx* c, void* host, size_t bytes)
-{
-    if (!c || current_partition(c, "dxv_partition_table_download", false)) return 1;
-    return download_current(c, "dxv_partition_table_download", cur_frame(c).part.table.p, dxv_partition_table_bytes(c), host, bytes);
-}
-const void* dxv_partition_throats_device_ptr(const dxv_ctx* c)
-{
-    if (!c || current_partition(c, "dxv_partition_throats_device_ptr", true)) return nullptr;
-    return cur_frame(c).part.throatCount ? cur_frame(c).part.throats.p : nullptr;
-}
-size_t dxv_partition_throats_bytes(const dxv_ctx* c)
-{
-    if (!c) return 0;
-    const Frame::Partition& o = cur_frame(c).part;
-    return o.current(cur_frame(c)) && o.hasThroats ? (size_t)o.throatCount * sizeof(PartThroat) : 0;
-}
-int dxv_partition_throats_download(dxv_ctx* c, void* host, size_t bytes)
-{
-    if (!c || current_partition(c, "dxv_partition_throats_download", true)) return 1;
-    return download_current(c, "dxv_partition_throats_download", cur_frame(c).part.throats.p, dxv_partition_throats_bytes(c), host, bytes);
-}
+const void* dxv_partition_labels_device_ptr(const dxv_ctx* c) { return product_ptr(c, "dxv_partition_labels_device_ptr", kPartLabels); }
+size_t dxv_partition_labels_bytes(const dxv_ctx* c) { return product_bytes(c, "dxv_partition_labels_bytes", kPartLabels); }
+int dxv_partition_labels_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_partition_labels_download", kPartLabels, host, bytes); }
+const void* dxv_partition_table_device_ptr(const dxv_ctx* c) { return product_ptr(c, "dxv_partition_table_device_ptr", kPartTable); }
+size_t dxv_partition_table_bytes(const dxv_ctx* c) { return product_bytes(c, "dxv_partition_table_bytes", kPartTable); }
+int dxv_partition_table_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_partition_table_download", kPartTable, host, bytes); }
+const void* dxv_partition_throats_device_ptr(const dxv_ctx* c) { return product_ptr(c, "dxv_partition_throats_device_ptr", kPartThroats); }
+size_t dxv_partition_throats_bytes(const dxv_ctx* c) { return product_bytes(c, "dxv_partition_throats_bytes", kPartThroats); }
+int dxv_partition_throats_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_partition_throats_download", kPartThroats, host, bytes); }
 
 int dxv_partition_stage_info(dxv_ctx* c, float ms[6], uint64_t* cells_tested, uint64_t* voxels_tested)
 {
@@ -1095,54 +1065,15 @@ int dxv_skeleton_info(dxv_ctx* c, float* ms, uint32_t* nodes, uint32_t* branches
     return 0;
 }
 
-const void* dxv_skeleton_labels_device_ptr(const dxv_ctx* c)
-{
-    if (!c || check_current(c, "dxv_skeleton_labels_device_ptr", cur_frame(c).skel, kSkeletonText)) return nullptr;
-    return cur_frame(c).skel.labels.p;
-}
-size_t dxv_skeleton_labels_bytes(const dxv_ctx* c)
-{
-    if (!c) return 0;
-    const Frame::Skeleton& o = cur_frame(c).skel;
-    return o.current(cur_frame(c)) ? (size_t)o.dim * o.dim * o.dim * sizeof(uint32_t) : 0;
-}
-int dxv_skeleton_labels_download(dxv_ctx* c, void* host, size_t bytes)
-{
-    if (!c || check_current(c, "dxv_skeleton_labels_download", cur_frame(c).skel, kSkeletonText)) return 1;
-    return download_current(c, "dxv_skeleton_labels_download", cur_frame(c).skel.labels.p, dxv_skeleton_labels_bytes(c), host, bytes);
-}
-const void* dxv_skeleton_nodes_device_ptr(const dxv_ctx* c)
-{
-    if (!c || check_current(c, "dxv_skeleton_nodes_device_ptr", cur_frame(c).skel, kSkeletonText)) return nullptr;
-    return cur_frame(c).skel.nodeCount ? cur_frame(c).skel.nodes.p : nullptr;
-}
-size_t dxv_skeleton_nodes_bytes(const dxv_ctx* c)
-{
-    if (!c) return 0;
-    const Frame::Skeleton& o = cur_frame(c).skel;
-    return o.current(cur_frame(c)) ? (size_t)o.nodeCount * sizeof(SkelNode) : 0;
-}
-int dxv_skeleton_nodes_download(dxv_ctx* c, void* host, size_t bytes)
-{
-    if (!c || check_current(c, "dxv_skeleton_nodes_download", cur_frame(c).skel, kSkeletonText)) return 1;
-    return download_current(c, "dxv_skeleton_nodes_download", cur_frame(c).skel.nodes.p, dxv_skeleton_nodes_bytes(c), host, bytes);
-}
-const void* dxv_skeleton_branches_device_ptr(const dxv_ctx* c)
-{
-    if (!c || check_current(c, "dxv_skeleton_branches_device_ptr", cur_frame(c).skel, kSkeletonText)) return nullptr;
-    return cur_frame(c).skel.branchCount ? cur_frame(c).skel.branches.p : nullptr;
-}
-size_t dxv_skeleton_branches_bytes(const dxv_ctx* c)
-{
-    if (!c) return 0;
-    const Frame::Skeleton& o = cur_frame(c).skel;
-    return o.current(cur_frame(c)) ? (size_t)o.branchCount * sizeof(SkelBranch) : 0;
-}
-int dxv_skeleton_branches_download(dxv_ctx* c, void* host, size_t bytes)
-{
-    if (!c || check_current(c, "dxv_skeleton_branches_download", cur_frame(c).skel, kSkeletonText)) return 1;
-    return download_current(c, "dxv_skeleton_branches_download", cur_frame(c).skel.branches.p, dxv_skeleton_branches_bytes(c), host, bytes);
-}
+const void* dxv_skeleton_labels_device_ptr(const dxv_ctx* c) { return product_ptr(c, "dxv_skeleton_labels_device_ptr", kSkelLabels); }
+size_t dxv_skeleton_labels_bytes(const dxv_ctx* c) { return product_bytes(c, "dxv_skeleton_labels_bytes", kSkelLabels); }
+int dxv_skeleton_labels_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_skeleton_labels_download", kSkelLabels, host, bytes); }
+const void* dxv_skeleton_nodes_device_ptr(const dxv_ctx* c) { return product_ptr(c, "dxv_skeleton_nodes_device_ptr", kSkelNodes); }
+size_t dxv_skeleton_nodes_bytes(const dxv_ctx* c) { return product_bytes(c, "dxv_skeleton_nodes_bytes", kSkelNodes); }
+int dxv_skeleton_nodes_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_skeleton_nodes_download", kSkelNodes, host, bytes); }
+const void* dxv_skeleton_branches_device_ptr(const dxv_ctx* c) { return product_ptr(c, "dxv_skeleton_branches_device_ptr", kSkelBranches); }
+size_t dxv_skeleton_branches_bytes(const dxv_ctx* c) { return product_bytes(c, "dxv_skeleton_branches_bytes", kSkelBranches); }
+int dxv_skeleton_branches_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_skeleton_branches_download", kSkelBranches, host, bytes); }
 
 // The selected frame's grid edited from its skeleton (skeleton.hip: k_skel_prune_mark, k_skel_prune_edit), in place, enqueued on the frame's
 // stream behind whatever it holds -- under dxv_render_async's host-wait rule and dxv_fill_async's rules for the grid.  Labels and tables are what
@@ -1189,10 +1120,7 @@ int dxv_geodesic_async(dxv_ctx* c, int of, int metric, int seeds_kind, const voi
     if (!c) return 1;
     if (of != DXV_COMP_SOLID && of != DXV_COMP_EMPTY) return fail(c, "dxv_geodesic: unknown kind %d (DXV_COMP_SOLID = 0, DXV_COMP_EMPTY = 1)", of);
     if (metric != DXV_GEO_FACES && metric != DXV_GEO_CHAMFER) return fail(c, "dxv_geodesic: unknown metric %d (DXV_GEO_FACES = 0, DXV_GEO_CHAMFER = 1)", metric);
-    if (seeds_kind != DXV_GEO_SEEDS_BORDER && seeds_kind != DXV_GEO_SEEDS_LIST && seeds_kind != DXV_GEO_SEEDS_MASK)
-        return fail(c, "dxv_geodesic: unknown seed kind %d (DXV_GEO_SEEDS_BORDER = 0, DXV_GEO_SEEDS_LIST = 1, DXV_GEO_SEEDS_MASK = 2)", seeds_kind);
-    if (seeds_kind == DXV_GEO_SEEDS_LIST && seed_count && !seeds) return fail(c, "dxv_geodesic: a list of %u seeds at NULL", seed_count);
-    if (seeds_kind == DXV_GEO_SEEDS_MASK && !seeds) return fail(c, "dxv_geodesic: the seed mask is NULL");
+    if (check_seed_args(c, "dxv_geodesic", seeds_kind, seeds, seed_count)) return 1;
     if (check_whole_grid(c, "dxv_geodesic")) return 1;
     Frame& f = cur_frame(c);
     const uint32_t N = f.grid_dim;
@@ -1200,40 +1128,16 @@ int dxv_geodesic_async(dxv_ctx* c, int of, int metric, int seeds_kind, const voi
     if (!geo_fits(N, metric))
         return fail(c, "dxv_geodesic: a grid of %u^3 voxels under metric %d: a path of weight %u per step can reach the codes of the map (wmax (N^3 - 1) must stay below 0xFFFFFFFE)", N,
                     metric, geo_max_weight(metric));
-    const size_t voxels = (size_t)N * N * N;
-    if (seeds_kind == DXV_GEO_SEEDS_LIST) {
-        const uint32_t* list = static_cast<const uint32_t*>(seeds);
-        for (uint32_t k = 0; k < seed_count; ++k)
-            if (list[k] >= voxels) return fail(c, "dxv_geodesic: seed %u is voxel %u, outside the grid of %u^3 = %zu voxels", k, list[k], N, voxels);
-    }
-    DXV_HIP(c, hipSetDevice(c->device));
-    if (seeds_kind == DXV_GEO_SEEDS_MASK) {
-        size_t room = 0;
-        const int r = check_device_range(c, "dxv_geodesic", seeds, voxels, &room);
-        if (r == 2) return fail(c, "dxv_geodesic: the seed mask has %zu bytes from %p on, the grid has %zu voxels", room, seeds, voxels);
-        if (r) return 1;
-    }
-    if (settle_frame_launch(c)) return 1;                               // (begin_operator's steps, the device in front of the range check: a pending fill, thin, expansion or geodesic of the frame first)
-    const hipStream_t fs = cur_stream(c);
-    const size_t scratch = geodesic_scratch_bytes(N);
+    hipStream_t fs;
+    if (begin_seeded(c, "dxv_geodesic", seeds_kind, seeds, seed_count, N, &fs)) return 1;
+    const size_t voxels = cube(N), scratch = geodesic_scratch_bytes(N);
     f.geo.version = 0; f.geo.have = false;
     DXV_HIP(c, f.geo.map.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
     DXV_HIP(c, f.geo.scratch.reserve(scratch, scratch, fs));
-    const void* deviceSeeds = seeds;
-    if (seeds_kind == DXV_GEO_SEEDS_LIST) {
-        // the frame's own copy of the list (no geodesic of the frame is in flight: settle_frame_launch), uploaded from there
-        const uint32_t* list = static_cast<const uint32_t*>(seeds);
-        f.geo.list.assign(list, list + seed_count);
-        deviceSeeds = nullptr;
-        if (seed_count) {
-            DXV_HIP(c, f.geo.seeds.reserve(seed_count, align256((size_t)seed_count * sizeof(uint32_t)), fs));
-            DXV_HIP(c, hipMemcpyAsync(f.geo.seeds.p, f.geo.list.data(), (size_t)seed_count * sizeof(uint32_t), hipMemcpyHostToDevice, fs));
-            deviceSeeds = f.geo.seeds.p;
-        }
-    }
+    const void* deviceSeeds;
+    if (upload_seeds(c, f.geo, seeds_kind, seeds, seed_count, fs, &deviceSeeds)) return 1;
     f.geo.metric = metric; f.geo.limit = limit;
-    f.geo.batch = c->opt.georounds ? (uint32_t)c->opt.georounds : kGeoRoundsDefault;
-    f.geo.rounds = 0; f.geo.tilesRun = 0; f.geo.mostLive = 0; f.geo.sparseRounds = 0;
+    begin_flood(f.geo, c->opt.georounds, kGeoRoundsDefault);
     DXV_HIP(c, timer_begin(f.timers[kTimerGeodesic], c->opt.events != 0, fs));
     DXV_HIP(c, launch_geodesic_init(f.grid.p, N, of, seeds_kind, deviceSeeds, seed_count, f.geo.map.p, f.geo.scratch.p, fs));
     DXV_HIP(c, launch_geodesic_batch(f.geo.map.p, N, metric, limit, f.geo.scratch.p, f.geo.batch, 0u, fs));
@@ -1245,22 +1149,9 @@ int dxv_geodesic_async(dxv_ctx* c, int of, int metric, int seeds_kind, const voi
 
 int dxv_geodesic(dxv_ctx* c, int of, int metric, int seeds_kind, const void* seeds, uint32_t seed_count, uint32_t limit) { return blocking(c, dxv_geodesic_async(c, of, metric, seeds_kind, seeds, seed_count, limit)); }
 
-const void* dxv_geodesic_device_ptr(const dxv_ctx* c)
-{
-    if (!c || check_current(c, "dxv_geodesic_device_ptr", cur_frame(c).geo, kGeodesicText)) return nullptr;
-    return cur_frame(c).geo.map.p;
-}
-size_t dxv_geodesic_bytes(const dxv_ctx* c)
-{
-    if (!c) return 0;
-    const Frame::Geodesic& g = cur_frame(c).geo;
-    return g.current(cur_frame(c)) ? (size_t)g.dim * g.dim * g.dim * sizeof(uint32_t) : 0;
-}
-int dxv_geodesic_download(dxv_ctx* c, void* host, size_t bytes)
-{
-    if (!c || check_current(c, "dxv_geodesic_download", cur_frame(c).geo, kGeodesicText)) return 1;
-    return download_current(c, "dxv_geodesic_download", cur_frame(c).geo.map.p, dxv_geodesic_bytes(c), host, bytes);
-}
+const void* dxv_geodesic_device_ptr(const dxv_ctx* c) { return product_ptr(c, "dxv_geodesic_device_ptr", kGeoMap); }
+size_t dxv_geodesic_bytes(const dxv_ctx* c) { return product_bytes(c, "dxv_geodesic_bytes", kGeoMap); }
+int dxv_geodesic_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_geodesic_download", kGeoMap, host, bytes); }
 
 int dxv_geodesic_info(dxv_ctx* c, float* ms, uint32_t* rounds, uint64_t* seeds_used, uint64_t* reached, uint64_t* unreached, uint32_t* farthest, uint32_t* farthest_voxel)
 {
@@ -1278,12 +1169,7 @@ int dxv_geodesic_info(dxv_ctx* c, float* ms, uint32_t* rounds, uint64_t* seeds_u
 
 int dxv_geodesic_work_info(dxv_ctx* c, uint64_t* tiles_run, uint32_t* most_live_tiles, uint32_t* sparse_rounds)
 {
-    if (!c || check_current(c, "dxv_geodesic_work_info", cur_frame(c).geo, kGeodesicText)) return 1;
-    const Frame& f = cur_frame(c);
-    if (tiles_run) *tiles_run = f.geo.tilesRun;
-    if (most_live_tiles) *most_live_tiles = f.geo.mostLive;
-    if (sparse_rounds) *sparse_rounds = f.geo.sparseRounds;
-    return 0;
+    return c ? flood_work_info(c, "dxv_geodesic_work_info", cur_frame(c).geo, kGeodesicText, tiles_run, most_live_tiles, sparse_rounds) : 1;
 }
 
 // The access radius inside the selected frame's grid and its intrusion map (access.hip; dxv_access.h has the rule's routines), enqueued on the
@@ -1297,32 +1183,16 @@ int dxv_access_async(dxv_ctx* c, int of, int connectivity, uint32_t cap_sq, int 
     if (of != DXV_COMP_SOLID && of != DXV_COMP_EMPTY) return fail(c, "dxv_access: unknown kind %d (DXV_COMP_SOLID = 0, DXV_COMP_EMPTY = 1)", of);
     if (!acc_connectivity(connectivity)) return fail(c, "dxv_access: connectivity %d is neither 6 nor 26", connectivity);
     if (cap_sq < kThickMinCapSq || cap_sq > kThickMaxCapSq) return fail(c, "dxv_access: cap_sq %u is not in [%u, %u]", cap_sq, kThickMinCapSq, kThickMaxCapSq);
-    if (seeds_kind != DXV_GEO_SEEDS_BORDER && seeds_kind != DXV_GEO_SEEDS_LIST && seeds_kind != DXV_GEO_SEEDS_MASK)
-        return fail(c, "dxv_access: unknown seed kind %d (DXV_GEO_SEEDS_BORDER = 0, DXV_GEO_SEEDS_LIST = 1, DXV_GEO_SEEDS_MASK = 2)", seeds_kind);
-    if (seeds_kind == DXV_GEO_SEEDS_LIST && seed_count && !seeds) return fail(c, "dxv_access: a list of %u seeds at NULL", seed_count);
-    if (seeds_kind == DXV_GEO_SEEDS_MASK && !seeds) return fail(c, "dxv_access: the seed mask is NULL");
+    if (check_seed_args(c, "dxv_access", seeds_kind, seeds, seed_count)) return 1;
     if (check_whole_grid(c, "dxv_access")) return 1;
     Frame& f = cur_frame(c);
     const uint32_t N = f.grid_dim;
     if (N > kAccMaxN) return fail(c, "dxv_access: a grid of %u^3 voxels; at most %u^3 (a centre's linear index must fit 30 bits)", N, kAccMaxN);
-    const size_t voxels = (size_t)N * N * N;
-    if (seeds_kind == DXV_GEO_SEEDS_LIST) {
-        const uint32_t* list = static_cast<const uint32_t*>(seeds);
-        for (uint32_t k = 0; k < seed_count; ++k)
-            if (list[k] >= voxels) return fail(c, "dxv_access: seed %u is voxel %u, outside the grid of %u^3 = %zu voxels", k, list[k], N, voxels);
-    }
-    DXV_HIP(c, hipSetDevice(c->device));
-    if (seeds_kind == DXV_GEO_SEEDS_MASK) {
-        size_t room = 0;
-        const int r = check_device_range(c, "dxv_access", seeds, voxels, &room);
-        if (r == 2) return fail(c, "dxv_access: the seed mask has %zu bytes from %p on, the grid has %zu voxels", room, seeds, voxels);
-        if (r) return 1;
-    }
-    if (settle_frame_launch(c)) return 1;                               // (begin_operator's steps, the device in front of the range check: a pending fill, thin, expansion, geodesic or access of the frame first)
-    const hipStream_t fs = cur_stream(c);
+    hipStream_t fs;
+    if (begin_seeded(c, "dxv_access", seeds_kind, seeds, seed_count, N, &fs)) return 1;
     Frame::Access& o = f.acc;
     const bool intrusion = want_intrusion != 0;
-    const size_t scratch = access_scratch_bytes(N, intrusion);
+    const size_t voxels = cube(N), scratch = access_scratch_bytes(N, intrusion);
     o.version = 0; o.have = false;
     DXV_HIP(c, o.map.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
     DXV_HIP(c, o.hist.reserve(kThickMaxCapSq + 1u, align256(thickness_histogram_bytes(kThickMaxCapSq)), fs));
@@ -1331,21 +1201,10 @@ int dxv_access_async(dxv_ctx* c, int of, int connectivity, uint32_t cap_sq, int 
         DXV_HIP(c, o.histI.reserve(kThickMaxCapSq + 1u, align256(thickness_histogram_bytes(kThickMaxCapSq)), fs));
     }
     DXV_HIP(c, o.scratch.reserve(scratch, scratch, fs));
-    const void* deviceSeeds = seeds;
-    if (seeds_kind == DXV_GEO_SEEDS_LIST) {
-        // the frame's own copy of the list (no access of the frame is in flight: settle_frame_launch), uploaded from there
-        const uint32_t* list = static_cast<const uint32_t*>(seeds);
-        o.list.assign(list, list + seed_count);
-        deviceSeeds = nullptr;
-        if (seed_count) {
-            DXV_HIP(c, o.seeds.reserve(seed_count, align256((size_t)seed_count * sizeof(uint32_t)), fs));
-            DXV_HIP(c, hipMemcpyAsync(o.seeds.p, o.list.data(), (size_t)seed_count * sizeof(uint32_t), hipMemcpyHostToDevice, fs));
-            deviceSeeds = o.seeds.p;
-        }
-    }
+    const void* deviceSeeds;
+    if (upload_seeds(c, o, seeds_kind, seeds, seed_count, fs, &deviceSeeds)) return 1;
     o.dim = N; o.cap = cap_sq; o.of = of; o.connectivity = connectivity; o.wantIntrusion = intrusion; o.cull = (uint32_t)c->opt.thickcull;
-    o.batch = c->opt.accessrounds ? (uint32_t)c->opt.accessrounds : kAccRoundsDefault;
-    o.rounds = 0; o.tilesRun = 0; o.mostLive = 0; o.sparseRounds = 0;
+    begin_flood(o, c->opt.accessrounds, kAccRoundsDefault);
     DXV_HIP(c, timer_begin(f.timers[kTimerAccess], c->opt.events != 0, fs));
     DXV_HIP(c, launch_access_init(f.grid.p, N, of, cap_sq, seeds_kind, deviceSeeds, seed_count, o.map.p, o.scratch.p, intrusion, fs));
     DXV_HIP(c, launch_access_batch(o.map.p, N, of, connectivity, cap_sq, o.scratch.p, intrusion, o.batch, 0u, fs));
@@ -1360,69 +1219,17 @@ int dxv_access(dxv_ctx* c, int of, int connectivity, uint32_t cap_sq, int seeds_
     return blocking(c, dxv_access_async(c, of, connectivity, cap_sq, seeds_kind, seeds, seed_count, want_intrusion));
 }
 
-const void* dxv_access_device_ptr(const dxv_ctx* c)
-{
-    if (!c || check_current(c, "dxv_access_device_ptr", cur_frame(c).acc, kAccessText)) return nullptr;
-    return cur_frame(c).acc.map.p;
-}
-size_t dxv_access_bytes(const dxv_ctx* c)
-{
-    if (!c) return 0;
-    const Frame::Access& a = cur_frame(c).acc;
-    return a.current(cur_frame(c)) ? (size_t)a.dim * a.dim * a.dim * sizeof(uint32_t) : 0;
-}
-int dxv_access_download(dxv_ctx* c, void* host, size_t bytes)
-{
-    if (!c || check_current(c, "dxv_access_download", cur_frame(c).acc, kAccessText)) return 1;
-    return download_current(c, "dxv_access_download", cur_frame(c).acc.map.p, dxv_access_bytes(c), host, bytes);
-}
-size_t dxv_access_histogram_bytes(const dxv_ctx* c)
-{
-    if (!c) return 0;
-    const Frame::Access& a = cur_frame(c).acc;
-    return a.current(cur_frame(c)) ? thickness_histogram_bytes(a.cap) : 0;
-}
-int dxv_access_histogram_download(dxv_ctx* c, void* host, size_t bytes)
-{
-    if (!c || check_current(c, "dxv_access_histogram_download", cur_frame(c).acc, kAccessText)) return 1;
-    return download_current(c, "dxv_access_histogram_download", cur_frame(c).acc.hist.p, dxv_access_histogram_bytes(c), host, bytes);
-}
-
-// the intrusion map's accessors: the access map's refusals, and one more for a map made without it
-static int check_intrusion(const dxv_ctx* c, const char* who)
-{
-    if (check_current(c, who, cur_frame(c).acc, kAccessText)) return 1;
-    if (!cur_frame(c).acc.wantIntrusion)
-        return fail(const_cast<dxv_ctx*>(c), "%s: the access map of frame %u was made without its intrusion map (call dxv_access with want_intrusion != 0)", who, c->cur);
-    return 0;
-}
-const void* dxv_intrusion_device_ptr(const dxv_ctx* c)
-{
-    if (!c || check_intrusion(c, "dxv_intrusion_device_ptr")) return nullptr;
-    return cur_frame(c).acc.intrusion.p;
-}
-size_t dxv_intrusion_bytes(const dxv_ctx* c)
-{
-    if (!c) return 0;
-    const Frame::Access& a = cur_frame(c).acc;
-    return a.current(cur_frame(c)) && a.wantIntrusion ? (size_t)a.dim * a.dim * a.dim * sizeof(uint32_t) : 0;
-}
-int dxv_intrusion_download(dxv_ctx* c, void* host, size_t bytes)
-{
-    if (!c || check_intrusion(c, "dxv_intrusion_download")) return 1;
-    return download_current(c, "dxv_intrusion_download", cur_frame(c).acc.intrusion.p, dxv_intrusion_bytes(c), host, bytes);
-}
-size_t dxv_intrusion_histogram_bytes(const dxv_ctx* c)
-{
-    if (!c) return 0;
-    const Frame::Access& a = cur_frame(c).acc;
-    return a.current(cur_frame(c)) && a.wantIntrusion ? thickness_histogram_bytes(a.cap) : 0;
-}
-int dxv_intrusion_histogram_download(dxv_ctx* c, void* host, size_t bytes)
-{
-    if (!c || check_intrusion(c, "dxv_intrusion_histogram_download")) return 1;
-    return download_current(c, "dxv_intrusion_histogram_download", cur_frame(c).acc.histI.p, dxv_intrusion_histogram_bytes(c), host, bytes);
-}
+const void* dxv_access_device_ptr(const dxv_ctx* c) { return product_ptr(c, "dxv_access_device_ptr", kAccMap); }
+size_t dxv_access_bytes(const dxv_ctx* c) { return product_bytes(c, "dxv_access_bytes", kAccMap); }
+int dxv_access_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_access_download", kAccMap, host, bytes); }
+size_t dxv_access_histogram_bytes(const dxv_ctx* c) { return product_bytes(c, "dxv_access_histogram_bytes", kAccHistogram); }
+int dxv_access_histogram_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_access_histogram_download", kAccHistogram, host, bytes); }
+// (the intrusion map's: the access map's refusals, and one more for a map made without it)
+const void* dxv_intrusion_device_ptr(const dxv_ctx* c) { return product_ptr(c, "dxv_intrusion_device_ptr", kIntrusionMap); }
+size_t dxv_intrusion_bytes(const dxv_ctx* c) { return product_bytes(c, "dxv_intrusion_bytes", kIntrusionMap); }
+int dxv_intrusion_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_intrusion_download", kIntrusionMap, host, bytes); }
+size_t dxv_intrusion_histogram_bytes(const dxv_ctx* c) { return product_bytes(c, "dxv_intrusion_histogram_bytes", kIntrusionHistogram); }
+int dxv_intrusion_histogram_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_intrusion_histogram_download", kIntrusionHistogram, host, bytes); }
 
 int dxv_access_info(dxv_ctx* c, float* ms, uint32_t* rounds, uint64_t* seeds_used, uint64_t* reached, uint64_t* unreached, uint32_t* widest, uint32_t* widest_voxel)
 {
@@ -1440,12 +1247,7 @@ int dxv_access_info(dxv_ctx* c, float* ms, uint32_t* rounds, uint64_t* seeds_use
 
 int dxv_access_work_info(dxv_ctx* c, uint64_t* tiles_run, uint32_t* most_live_tiles, uint32_t* sparse_rounds)
 {
-    if (!c || check_current(c, "dxv_access_work_info", cur_frame(c).acc, kAccessText)) return 1;
-    const Frame& f = cur_frame(c);
-    if (tiles_run) *tiles_run = f.acc.tilesRun;
-    if (most_live_tiles) *most_live_tiles = f.acc.mostLive;
-    if (sparse_rounds) *sparse_rounds = f.acc.sparseRounds;
-    return 0;
+    return c ? flood_work_info(c, "dxv_access_work_info", cur_frame(c).acc, kAccessText, tiles_run, most_live_tiles, sparse_rounds) : 1;
 }
 
 // The path from `target` down to a seed of the selected frame's current map, synchronous: the frame is synchronised, the target's word is read,

@@ -175,6 +175,37 @@ class Voxelizer:
         if rc:
             raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
 
+    def _pointer(self, entry):
+        """what the entry `entry` hands out for the selected frame (a dxv_*_device_ptr), or the library's refusal as a DxvError"""
+        p = getattr(self._lib, entry)(self._ctx)
+        if not p:
+            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
+        return p
+
+    def _download(self, name, dtype, shape="records", speaks=None, size=None):
+        """numpy copy of a product of the selected frame through dxv_<name>_download, sized by dxv_<size or name>_bytes.  shape: "cube", a field
+        [n, n, n] of side n = round(cbrt(elements)); "slab", the mesh distance field's [nz, N, N]; "records", a flat array.  A size of 0 does
+        not say why: `speaks` is the entry that is called for the message then (a dxv_*_device_ptr, or the one size that speaks), and what it
+        refuses is raised; where it refuses nothing the product is an empty table.  Without one the download's own refusal is raised."""
+        nbytes = getattr(self._lib, f"dxv_{size or name}_bytes")(self._ctx)
+        if not nbytes and speaks:
+            self._pointer(speaks)
+        count = nbytes // np.dtype(dtype).itemsize
+        if shape == "cube":
+            n = round(count ** (1.0 / 3.0))
+            out = np.empty((n, n, n), dtype)
+        elif shape == "slab":
+            # the library's own record of the frame's last launch (dxv_get_stats: grid_dim, nz), which is the field's while the field is current
+            st = self.stats()
+            n, nz = (st["grid_dim"], st["nz"]) if nbytes else (0, 0)
+            if n * n * nz != count:
+                raise DxvError(f"mesh distance field of {nbytes} bytes does not belong to the frame's last launch ({n}^2 x {nz} voxels)")
+            out = np.empty((nz, n, n), dtype)
+        else:
+            out = np.empty(count, dtype)
+        self._check(getattr(self._lib, f"dxv_{name}_download")(self._ctx, out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
+
     # ---- reference surface ------------------------------------------------------------------
     def Init(self, fileName, posScale=(0.0, 0.0, 0.0, 1.0), dynamicMesh=False, gridDim=0):
         """Voxelizer::Init (Content/Voxelizer.cpp:30-79) minus the D3D12 arguments."""
@@ -382,19 +413,12 @@ class Voxelizer:
 
     def Distance(self):
         """numpy copy of the selected frame's field (dxv_distance_download; synchronises the frame)."""
-        nbytes = self._lib.dxv_distance_bytes(self._ctx)
-        n = round((nbytes // 4) ** (1.0 / 3.0))
-        out = np.empty((n, n, n), np.float32 if self._dist_formats.get(self._frame) == DIST_F32 else np.int32)
-        self._check(self._lib.dxv_distance_download(self._ctx, out.ctypes.data_as(C.c_void_p), out.nbytes))
-        return out
+        return self._download("distance", np.float32 if self._dist_formats.get(self._frame) == DIST_F32 else np.int32, "cube")
 
     def distance_device_ptr(self):
         """Device pointer of the selected frame's field (dxv_distance_device_ptr), for consumers on the GPU; raises where the
         library refuses (no field yet, or the frame was launched again since)."""
-        p = self._lib.dxv_distance_device_ptr(self._ctx)
-        if not p:
-            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
-        return p
+        return self._pointer("dxv_distance_device_ptr")
 
     def distance_ms(self):
         """Device time of the selected frame's last field, read at the frame's Sync (dxv_distance_ms)."""
@@ -417,36 +441,19 @@ class Voxelizer:
         self._check(fn(self._ctx, int(format), int(band), 1 if triangles else 0))
         return self.MeshDistance() if sync else True
 
-    def _mdist_array(self, dtype):
-        """an empty array of the selected frame's field: the library's own record of the frame's last launch (dxv_get_stats: grid_dim, nz),
-        which is the field's while the field is current"""
-        nbytes = self._lib.dxv_mesh_distance_bytes(self._ctx)
-        st = self.stats()
-        n, nz = (st["grid_dim"], st["nz"]) if nbytes else (0, 0)
-        if n * n * nz * 4 != nbytes:
-            raise DxvError(f"mesh distance field of {nbytes} bytes does not belong to the frame's last launch ({n}^2 x {nz} voxels)")
-        return np.empty((nz, n, n), dtype)
-
     def MeshDistance(self):
         """numpy copy of the selected frame's mesh distance field (dxv_mesh_distance_download; synchronises the frame)."""
-        out = self._mdist_array(np.float32)
-        self._check(self._lib.dxv_mesh_distance_download(self._ctx, out.ctypes.data_as(C.c_void_p), out.nbytes))
-        return out
+        return self._download("mesh_distance", np.float32, "slab")
 
     def MeshDistanceTriangles(self):
         """numpy copy (uint32) of the nearest triangle per voxel, 0xffffffff beyond the band (dxv_mesh_distance_triangles_download); raises
         when the field was made without them."""
-        out = self._mdist_array(np.uint32)
-        self._check(self._lib.dxv_mesh_distance_triangles_download(self._ctx, out.ctypes.data_as(C.c_void_p), out.nbytes))
-        return out
+        return self._download("mesh_distance_triangles", np.uint32, "slab", size="mesh_distance")
 
     def mesh_distance_device_ptr(self):
         """Device pointer of the selected frame's mesh distance field (dxv_mesh_distance_device_ptr); raises where the library refuses
         (no field yet, or the frame was launched or filled again since)."""
-        p = self._lib.dxv_mesh_distance_device_ptr(self._ctx)
-        if not p:
-            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
-        return p
+        return self._pointer("dxv_mesh_distance_device_ptr")
 
     def mesh_distance_ms(self):
         """Device time of the selected frame's last mesh distance field, read at the frame's Sync (dxv_mesh_distance_ms)."""
@@ -519,17 +526,12 @@ class Voxelizer:
 
     def OctreeNodes(self):
         """numpy copy (nodes [n, 2] uint32, level_first) of the selected frame's tree (dxv_octree_download; synchronises the frame)."""
-        _, n, first = self.OctreeInfo()
-        nodes = np.empty((n, 2), np.uint32)
-        self._check(self._lib.dxv_octree_download(self._ctx, nodes.ctypes.data_as(C.c_void_p), nodes.nbytes))
-        return nodes, first
+        _, _, first = self.OctreeInfo()
+        return self._download("octree", np.uint32).reshape(-1, 2), first
 
     def octree_device_ptr(self):
         """Device pointer of the selected frame's nodes (dxv_octree_device_ptr), for consumers on the GPU; raises where the library refuses."""
-        p = self._lib.dxv_octree_device_ptr(self._ctx)
-        if not p:
-            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
-        return p
+        return self._pointer("dxv_octree_device_ptr")
 
     def octree_bytes(self):
         return self._lib.dxv_octree_bytes(self._ctx)
@@ -584,28 +586,17 @@ class Voxelizer:
 
     def ComponentLabels(self):
         """numpy copy [N, N, N] uint32 of the selected frame's labels (dxv_components_labels_download; synchronises the frame)."""
-        self.components_info()
-        nbytes = self._lib.dxv_components_labels_bytes(self._ctx)
-        side = self.stats()["grid_dim"]                                 # labels are current: made of the grid of the frame's last launch
-        if side ** 3 * 4 != nbytes:
-            raise DxvError(f"component labels of {nbytes} bytes do not belong to the frame's last launch ({side}^3 voxels)")
-        labels = np.empty((side, side, side), np.uint32)
-        self._check(self._lib.dxv_components_labels_download(self._ctx, labels.ctypes.data_as(C.c_void_p), labels.nbytes))
-        return labels
+        self.components_info()                                          # (raises where there are none, or stale ones)
+        return self._download("components_labels", np.uint32, "cube")
 
     def ComponentTable(self):
         """numpy copy [K] of the selected frame's table, dtype COMP_RECORD (dxv_components_table_download; synchronises the frame)."""
-        count, _, _ = self.components_info()
-        table = np.empty(count, COMP_RECORD)
-        self._check(self._lib.dxv_components_table_download(self._ctx, table.ctypes.data_as(C.c_void_p), table.nbytes))
-        return table
+        self.components_info()
+        return self._download("components_table", COMP_RECORD)
 
     def component_device_ptrs(self):
         """(labels, table) device pointers of the selected frame's labelling, for consumers on the GPU; the table's is None when K = 0."""
-        labels = self._lib.dxv_components_labels_device_ptr(self._ctx)
-        if not labels:
-            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
-        return labels, self._lib.dxv_components_table_device_ptr(self._ctx)
+        return self._pointer("dxv_components_labels_device_ptr"), self._lib.dxv_components_table_device_ptr(self._ctx)
 
     def components_ms(self):
         """Device time of the selected frame's last labelling, read at the frame's Sync (dxv_components_ms)."""
@@ -626,19 +617,11 @@ class Voxelizer:
 
     def MeasureTable(self):
         """numpy copy [K + 1] of the selected frame's measures, dtype MEASURE_RECORD (dxv_measure_table_download; synchronises the frame)."""
-        nbytes = self._lib.dxv_measure_table_bytes(self._ctx)
-        if not nbytes:
-            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
-        table = np.empty(nbytes // MEASURE_RECORD.itemsize, MEASURE_RECORD)
-        self._check(self._lib.dxv_measure_table_download(self._ctx, table.ctypes.data_as(C.c_void_p), table.nbytes))
-        return table
+        return self._download("measure_table", MEASURE_RECORD, speaks="dxv_measure_table_bytes")
 
     def measure_device_ptr(self):
         """Device pointer of the selected frame's measures, (K + 1) * 96 bytes, for consumers on the GPU."""
-        ptr = self._lib.dxv_measure_table_device_ptr(self._ctx)
-        if not ptr:
-            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
-        return ptr
+        return self._pointer("dxv_measure_table_device_ptr")
 
     def measure_ms(self):
         """Device time of the selected frame's last measure, read at the frame's Sync (dxv_measure_ms)."""
@@ -674,32 +657,16 @@ class Voxelizer:
     def ThicknessField(self):
         """numpy copy uint32 [N, N, N] (z, y, x) of the selected frame's thickness map, squared radii (dxv_thickness_download; synchronises
         the frame); thickness_voxels turns it into voxels."""
-        nbytes = self._lib.dxv_thickness_bytes(self._ctx)
-        if not nbytes:
-            self._lib.dxv_thickness_device_ptr(self._ctx)              # (sets the message: none yet, or stale)
-            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
-        n = round((nbytes // 4) ** (1.0 / 3.0))
-        out = np.empty((n, n, n), np.uint32)
-        self._check(self._lib.dxv_thickness_download(self._ctx, out.ctypes.data_as(C.c_void_p), out.nbytes))
-        return out
+        return self._download("thickness", np.uint32, "cube", speaks="dxv_thickness_device_ptr")
 
     def ThicknessHistogram(self):
         """numpy copy uint64 [capSq + 1] of the selected frame's thickness histogram: bin v the voxels with W == v, bin 0 those that are no
         members (dxv_thickness_histogram_download; synchronises the frame).  Its first non-zero bin above 0 is the minimum wall."""
-        nbytes = self._lib.dxv_thickness_histogram_bytes(self._ctx)
-        if not nbytes:
-            self._lib.dxv_thickness_device_ptr(self._ctx)
-            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
-        out = np.empty(nbytes // 8, np.uint64)
-        self._check(self._lib.dxv_thickness_histogram_download(self._ctx, out.ctypes.data_as(C.c_void_p), out.nbytes))
-        return out
+        return self._download("thickness_histogram", np.uint64, speaks="dxv_thickness_device_ptr")
 
     def thickness_device_ptr(self):
         """Device pointer of the selected frame's thickness map, 4 * N^3 bytes, for consumers on the GPU."""
-        ptr = self._lib.dxv_thickness_device_ptr(self._ctx)
-        if not ptr:
-            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
-        return ptr
+        return self._pointer("dxv_thickness_device_ptr")
 
     def ThicknessInfo(self):
         """(ms, centres_painted, work_items) of the selected frame's last thickness as of its last Sync (dxv_thickness_info)."""
@@ -731,37 +698,22 @@ class Voxelizer:
     def PartitionLabels(self):
         """numpy copy uint32 [N, N, N] (z, y, x) of the selected frame's region labels, 0 off the members (dxv_partition_labels_download;
         synchronises the frame)."""
-        nbytes = self._lib.dxv_partition_labels_bytes(self._ctx)
-        if not nbytes:
-            self._lib.dxv_partition_labels_device_ptr(self._ctx)       # (sets the message: none yet, or stale)
-            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
-        n = round((nbytes // 4) ** (1.0 / 3.0))
-        out = np.empty((n, n, n), np.uint32)
-        self._check(self._lib.dxv_partition_labels_download(self._ctx, out.ctypes.data_as(C.c_void_p), out.nbytes))
-        return out
+        return self._download("partition_labels", np.uint32, "cube", speaks="dxv_partition_labels_device_ptr")
 
     def PartitionTable(self):
         """numpy copy [K] of the selected frame's regions, dtype PART_REGION (dxv_partition_table_download; synchronises the frame)."""
-        if not self._lib.dxv_partition_labels_device_ptr(self._ctx):
-            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
-        table = np.empty(self._lib.dxv_partition_table_bytes(self._ctx) // PART_REGION.itemsize, PART_REGION)
-        self._check(self._lib.dxv_partition_table_download(self._ctx, table.ctypes.data_as(C.c_void_p), table.nbytes))
-        return table
+        return self._download("partition_table", PART_REGION, speaks="dxv_partition_labels_device_ptr")
 
     def PartitionThroats(self):
         """numpy copy [T] of the selected frame's throats, dtype PART_THROAT (dxv_partition_throats_download; synchronises the frame); an
         error for a partition made without them."""
-        throats = np.empty(self._lib.dxv_partition_throats_bytes(self._ctx) // PART_THROAT.itemsize, PART_THROAT)
-        self._check(self._lib.dxv_partition_throats_download(self._ctx, throats.ctypes.data_as(C.c_void_p), throats.nbytes))
-        return throats
+        return self._download("partition_throats", PART_THROAT)
 
     def partition_device_ptrs(self):
         """(labels, table, throats) device pointers of the selected frame's partition, for consumers on the GPU; the table's is None when K = 0,
         the throats' when T = 0 or when it was made without them."""
-        labels = self._lib.dxv_partition_labels_device_ptr(self._ctx)
-        if not labels:
-            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
-        return labels, self._lib.dxv_partition_table_device_ptr(self._ctx), self._lib.dxv_partition_throats_device_ptr(self._ctx)
+        return (self._pointer("dxv_partition_labels_device_ptr"), self._lib.dxv_partition_table_device_ptr(self._ctx),
+                self._lib.dxv_partition_throats_device_ptr(self._ctx))
 
     def PartitionInfo(self):
         """(ms, regions, throats, interface_faces) of the selected frame's last partition as of its last Sync (dxv_partition_info)."""
@@ -809,38 +761,21 @@ class Voxelizer:
     def SkeletonLabels(self):
         """numpy copy uint32 [N, N, N] (z, y, x) of the selected frame's skeleton labels: 0 off the members, k on node k, SKELETON_BRANCH_BIT | b on
         branch b (dxv_skeleton_labels_download; synchronises the frame)."""
-        nbytes = self._lib.dxv_skeleton_labels_bytes(self._ctx)
-        if not nbytes:
-            self._lib.dxv_skeleton_labels_device_ptr(self._ctx)        # (sets the message: none yet, or stale)
-            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
-        n = round((nbytes // 4) ** (1.0 / 3.0))
-        out = np.empty((n, n, n), np.uint32)
-        self._check(self._lib.dxv_skeleton_labels_download(self._ctx, out.ctypes.data_as(C.c_void_p), out.nbytes))
-        return out
+        return self._download("skeleton_labels", np.uint32, "cube", speaks="dxv_skeleton_labels_device_ptr")
 
     def SkeletonNodes(self):
         """numpy copy [K] of the selected frame's nodes, dtype SKELETON_NODE (dxv_skeleton_nodes_download; synchronises the frame)."""
-        if not self._lib.dxv_skeleton_labels_device_ptr(self._ctx):
-            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
-        table = np.empty(self._lib.dxv_skeleton_nodes_bytes(self._ctx) // SKELETON_NODE.itemsize, SKELETON_NODE)
-        self._check(self._lib.dxv_skeleton_nodes_download(self._ctx, table.ctypes.data_as(C.c_void_p), table.nbytes))
-        return table
+        return self._download("skeleton_nodes", SKELETON_NODE, speaks="dxv_skeleton_labels_device_ptr")
 
     def SkeletonBranches(self):
         """numpy copy [B] of the selected frame's branches, dtype SKELETON_BRANCH (dxv_skeleton_branches_download; synchronises the frame)."""
-        if not self._lib.dxv_skeleton_labels_device_ptr(self._ctx):
-            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
-        table = np.empty(self._lib.dxv_skeleton_branches_bytes(self._ctx) // SKELETON_BRANCH.itemsize, SKELETON_BRANCH)
-        self._check(self._lib.dxv_skeleton_branches_download(self._ctx, table.ctypes.data_as(C.c_void_p), table.nbytes))
-        return table
+        return self._download("skeleton_branches", SKELETON_BRANCH, speaks="dxv_skeleton_labels_device_ptr")
 
     def skeleton_device_ptrs(self):
         """(labels, nodes, branches) device pointers of the selected frame's skeleton, for consumers on the GPU; the nodes' is None when K = 0, the
         branches' when B = 0."""
-        labels = self._lib.dxv_skeleton_labels_device_ptr(self._ctx)
-        if not labels:
-            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
-        return labels, self._lib.dxv_skeleton_nodes_device_ptr(self._ctx), self._lib.dxv_skeleton_branches_device_ptr(self._ctx)
+        return (self._pointer("dxv_skeleton_labels_device_ptr"), self._lib.dxv_skeleton_nodes_device_ptr(self._ctx),
+                self._lib.dxv_skeleton_branches_device_ptr(self._ctx))
 
     def SkeletonInfo(self):
         """{ms, nodes, branches, end_voxels, curve_voxels, junction_voxels} of the selected frame's last skeleton as of its last Sync
@@ -865,6 +800,29 @@ class Voxelizer:
         return branches.value, voxels.value
 
     # ---- the geodesic distance inside the frame's grid ---------------------------------------------------
+    def _seed_args(self, who, seeds):
+        """(kind, pointer, count, what must stay alive until the call returns) of the kinds of seeds that Geodesic and Access take"""
+        if isinstance(seeds, str):
+            if seeds != "border":
+                raise DxvError(f"{who}: unknown seeds {seeds!r} (\"border\", an index array, an [N, N, N] array or a device tensor)")
+            return GEO_SEEDS_BORDER, None, 0, None
+        if hasattr(seeds, "data_ptr"):                                  # a device tensor: a mask read in place
+            import torch
+            if not seeds.is_cuda or seeds.dtype not in (torch.uint8, torch.bool) or not seeds.is_contiguous():
+                raise DxvError(f"{who}: a seed tensor must be a contiguous uint8 or bool tensor on the device")
+            n = self.stats()["grid_dim"]
+            if seeds.numel() != n ** 3:
+                raise DxvError(f"{who}: the seed tensor has {seeds.numel()} elements, the grid has {n ** 3} voxels")
+            torch.cuda.current_stream(seeds.device).synchronize()       # (its writer is ordered before the frame's stream reads it)
+            return GEO_SEEDS_MASK, C.c_void_p(seeds.data_ptr()), 0, seeds
+        a = np.asarray(seeds)
+        if a.ndim == 3:
+            a = np.flatnonzero(a)
+        if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+            raise DxvError(f"{who}: a seed index is outside the grid")
+        a = np.ascontiguousarray(a.reshape(-1), np.uint32)
+        return GEO_SEEDS_LIST, a.ctypes.data_as(C.c_void_p) if a.size else None, int(a.size), a
+
     def Geodesic(self, of=COMP_SOLID, metric=GEO_CHAMFER, seeds="border", limit=0, sync=True, frameIndex=None):
         """The geodesic distance inside the selected frame's whole grid on the device (dxv_geodesic / dxv_geodesic_async; include/dxv.h has the
         rule): per member voxel -- of = COMP_SOLID the non-zero voxels, COMP_EMPTY the zero ones -- the length of the shortest path of member
@@ -876,47 +834,18 @@ class Voxelizer:
         if frameIndex is not None:
             self.SetFrame(frameIndex)
         fn = self._lib.dxv_geodesic if sync else self._lib.dxv_geodesic_async
-        if isinstance(seeds, str):
-            if seeds != "border":
-                raise DxvError(f"Geodesic: unknown seeds {seeds!r} (\"border\", an index array, an [N, N, N] array or a device tensor)")
-            rc = fn(self._ctx, int(of), int(metric), GEO_SEEDS_BORDER, None, 0, int(limit))
-        elif hasattr(seeds, "data_ptr"):                                # a device tensor: a mask read in place
-            import torch
-            if not seeds.is_cuda or seeds.dtype not in (torch.uint8, torch.bool) or not seeds.is_contiguous():
-                raise DxvError("Geodesic: a seed tensor must be a contiguous uint8 or bool tensor on the device")
-            n = self.stats()["grid_dim"]
-            if seeds.numel() != n ** 3:
-                raise DxvError(f"Geodesic: the seed tensor has {seeds.numel()} elements, the grid has {n ** 3} voxels")
-            torch.cuda.current_stream(seeds.device).synchronize()       # (its writer is ordered before the frame's stream reads it)
-            rc = fn(self._ctx, int(of), int(metric), GEO_SEEDS_MASK, C.c_void_p(seeds.data_ptr()), 0, int(limit))
-        else:
-            a = np.asarray(seeds)
-            if a.ndim == 3:
-                a = np.flatnonzero(a)
-            if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
-                raise DxvError("Geodesic: a seed index is outside the grid")
-            a = np.ascontiguousarray(a.reshape(-1), np.uint32)
-            rc = fn(self._ctx, int(of), int(metric), GEO_SEEDS_LIST, a.ctypes.data_as(C.c_void_p) if a.size else None, int(a.size), int(limit))
-        self._check(rc)
+        kind, ptr, count, keep = self._seed_args("Geodesic", seeds)
+        self._check(fn(self._ctx, int(of), int(metric), kind, ptr, count, int(limit)))
+        del keep
         return self.GeodesicField() if sync else True
 
     def GeodesicField(self):
         """numpy copy uint32 [N, N, N] (z, y, x) of the selected frame's geodesic map (dxv_geodesic_download; synchronises the frame)."""
-        nbytes = self._lib.dxv_geodesic_bytes(self._ctx)
-        if not nbytes:
-            self._lib.dxv_geodesic_device_ptr(self._ctx)               # (sets the message: none yet, or stale)
-            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
-        n = round((nbytes // 4) ** (1.0 / 3.0))
-        out = np.empty((n, n, n), np.uint32)
-        self._check(self._lib.dxv_geodesic_download(self._ctx, out.ctypes.data_as(C.c_void_p), out.nbytes))
-        return out
+        return self._download("geodesic", np.uint32, "cube", speaks="dxv_geodesic_device_ptr")
 
     def geodesic_device_ptr(self):
         """Device pointer of the selected frame's geodesic map, 4 * N^3 bytes, for consumers on the GPU (exact after Sync)."""
-        ptr = self._lib.dxv_geodesic_device_ptr(self._ctx)
-        if not ptr:
-            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
-        return ptr
+        return self._pointer("dxv_geodesic_device_ptr")
 
     def GeodesicInfo(self):
         """{ms, rounds, seeds_used, reached, unreached, farthest, farthest_voxel} of the selected frame's last geodesic as of its last Sync
@@ -944,29 +873,6 @@ class Voxelizer:
         return out[:length.value]
 
     # ---- what can get in: the access radius and the intrusion map of the frame's grid ---------------------
-    def _seed_args(self, who, seeds):
-        """(kind, pointer, count, what must stay alive until the call returns) of Geodesic's kinds of seeds, for Access"""
-        if isinstance(seeds, str):
-            if seeds != "border":
-                raise DxvError(f"{who}: unknown seeds {seeds!r} (\"border\", an index array, an [N, N, N] array or a device tensor)")
-            return GEO_SEEDS_BORDER, None, 0, None
-        if hasattr(seeds, "data_ptr"):                                  # a device tensor: a mask read in place
-            import torch
-            if not seeds.is_cuda or seeds.dtype not in (torch.uint8, torch.bool) or not seeds.is_contiguous():
-                raise DxvError(f"{who}: a seed tensor must be a contiguous uint8 or bool tensor on the device")
-            n = self.stats()["grid_dim"]
-            if seeds.numel() != n ** 3:
-                raise DxvError(f"{who}: the seed tensor has {seeds.numel()} elements, the grid has {n ** 3} voxels")
-            torch.cuda.current_stream(seeds.device).synchronize()       # (its writer is ordered before the frame's stream reads it)
-            return GEO_SEEDS_MASK, C.c_void_p(seeds.data_ptr()), 0, seeds
-        a = np.asarray(seeds)
-        if a.ndim == 3:
-            a = np.flatnonzero(a)
-        if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
-            raise DxvError(f"{who}: a seed index is outside the grid")
-        a = np.ascontiguousarray(a.reshape(-1), np.uint32)
-        return GEO_SEEDS_LIST, a.ctypes.data_as(C.c_void_p) if a.size else None, int(a.size), a
-
     def Access(self, of=COMP_EMPTY, connectivity=26, capSq=4096, seeds="border", intrusion=True, sync=True, frameIndex=None):
         """The access radius inside the selected frame's whole grid on the device, and its intrusion map (dxv_access / dxv_access_async;
         include/dxv.h has the rule): per member voxel -- of = COMP_SOLID the non-zero voxels, COMP_EMPTY the zero ones -- A = the squared radius
@@ -984,42 +890,26 @@ class Voxelizer:
         del keep
         return (self.AccessField(), self.IntrusionField() if intrusion else None) if sync else True
 
-    def _access_array(self, which, what, dtype):
-        nbytes = getattr(self._lib, f"dxv_{which}_bytes")(self._ctx)
-        if not nbytes:
-            getattr(self._lib, "dxv_intrusion_device_ptr" if which.startswith("intrusion") else "dxv_access_device_ptr")(self._ctx)   # (sets the message)
-            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
-        if what == "map":
-            n = round((nbytes // 4) ** (1.0 / 3.0))
-            out = np.empty((n, n, n), dtype)
-        else:
-            out = np.empty(nbytes // 8, dtype)
-        self._check(getattr(self._lib, f"dxv_{which}_download")(self._ctx, out.ctypes.data_as(C.c_void_p), out.nbytes))
-        return out
-
     def AccessField(self):
         """numpy copy uint32 [N, N, N] (z, y, x) of the selected frame's access map, squared radii (dxv_access_download; synchronises the frame)."""
-        return self._access_array("access", "map", np.uint32)
+        return self._download("access", np.uint32, "cube", speaks="dxv_access_device_ptr")
 
     def AccessHistogram(self):
         """numpy copy uint64 [capSq + 1] of the access map's histogram: bin v the voxels with A == v (dxv_access_histogram_download)."""
-        return self._access_array("access_histogram", "histogram", np.uint64)
+        return self._download("access_histogram", np.uint64, speaks="dxv_access_device_ptr")
 
     def IntrusionField(self):
         """numpy copy uint32 [N, N, N] (z, y, x) of the selected frame's intrusion map, squared radii (dxv_intrusion_download; synchronises the
         frame); an error for an Access made with intrusion=False.  thickness_voxels turns it into voxels."""
-        return self._access_array("intrusion", "map", np.uint32)
+        return self._download("intrusion", np.uint32, "cube", speaks="dxv_intrusion_device_ptr")
 
     def IntrusionHistogram(self):
         """numpy copy uint64 [capSq + 1] of the intrusion map's histogram (dxv_intrusion_histogram_download); intrusion_curve reads it."""
-        return self._access_array("intrusion_histogram", "histogram", np.uint64)
+        return self._download("intrusion_histogram", np.uint64, speaks="dxv_intrusion_device_ptr")
 
     def access_device_ptrs(self):
         """(access map, intrusion map or None) device pointers of the selected frame, 4 * N^3 bytes each, for consumers on the GPU (exact after Sync)."""
-        ptr = self._lib.dxv_access_device_ptr(self._ctx)
-        if not ptr:
-            raise DxvError(self._lib.dxv_last_error(self._ctx).decode())
-        return ptr, self._lib.dxv_intrusion_device_ptr(self._ctx) if self._lib.dxv_intrusion_bytes(self._ctx) else None
+        return self._pointer("dxv_access_device_ptr"), self._lib.dxv_intrusion_device_ptr(self._ctx) if self._lib.dxv_intrusion_bytes(self._ctx) else None
 
     def AccessInfo(self):
         """{ms, rounds, seeds_used, reached, unreached, widest, widest_voxel} of the selected frame's last access as of its last Sync

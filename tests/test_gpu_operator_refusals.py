@@ -1,8 +1,9 @@
 """What the operators on a frame's grid (include/dxv.h: dxv_distance*, dxv_mesh_distance*, dxv_isosurface*, dxv_octree*, dxv_components*,
-dxv_measure*, dxv_thickness*, dxv_geodesic*, dxv_fill*, dxv_morph*, dxv_thin*, dxv_render_async) refuse, word for word: the WHOLE text of
-dxv_last_error against the sentence written out here, with ==.  A frame without a grid, a slab, a product that was never made or went stale,
-a wrong byte count, a NULL ms, a caller's pointer the library cannot use.  One cube at 16^3 throughout; every call under test returns before
-it enqueues anything.  And what a launch does to a fill, a thin or a geodesic of its frame that nobody has settled yet: it drops it."""
+dxv_measure*, dxv_thickness*, dxv_partition*, dxv_skeleton*, dxv_geodesic*, dxv_access*, dxv_intrusion*, dxv_fill*, dxv_morph*, dxv_thin*,
+dxv_render_async) refuse, word for word: the WHOLE text of dxv_last_error against the sentence written out here, with ==.  A frame without a
+grid, a slab, a product that was never made or went stale or was made without the part asked for, a wrong byte count, a NULL ms, a caller's
+pointer the library cannot use -- and what is NOT said: a size never speaks (the measure's does), an empty table is NULL without a word.  One
+cube at 16^3 throughout; every call under test returns before it enqueues anything, or works on 16^3.  And what a launch does to a fill, a thin or a geodesic of its frame that nobody has settled yet: it drops it."""
 import ctypes as C
 
 import numpy as np
@@ -60,7 +61,10 @@ def operators(v):
             ("dxv_thin", lambda: lib.dxv_thin_async(ctx, 0, 0)), ("dxv_thin", lambda: lib.dxv_thin(ctx, 0, 0)),
             ("dxv_thickness", lambda: lib.dxv_thickness_async(ctx, 0, CAP_SQ)), ("dxv_thickness", lambda: lib.dxv_thickness(ctx, 0, CAP_SQ)),
             ("dxv_geodesic", lambda: lib.dxv_geodesic_async(ctx, 0, 0, 0, None, 0, 0)), ("dxv_geodesic", lambda: lib.dxv_geodesic(ctx, 0, 0, 0, None, 0, 0)),
-            ("dxv_measure", lambda: lib.dxv_measure_async(ctx)), ("dxv_measure", lambda: lib.dxv_measure(ctx))]
+            ("dxv_measure", lambda: lib.dxv_measure_async(ctx)), ("dxv_measure", lambda: lib.dxv_measure(ctx)),
+            ("dxv_partition", lambda: lib.dxv_partition_async(ctx, 0, CAP_SQ, 1)), ("dxv_partition", lambda: lib.dxv_partition(ctx, 0, CAP_SQ, 1)),
+            ("dxv_skeleton", lambda: lib.dxv_skeleton_async(ctx, None)), ("dxv_skeleton", lambda: lib.dxv_skeleton(ctx, None)),
+            ("dxv_access", lambda: lib.dxv_access_async(ctx, 0, 6, CAP_SQ, 0, None, 0, 1)), ("dxv_access", lambda: lib.dxv_access(ctx, 0, 6, CAP_SQ, 0, None, 0, 1))]
 
 
 NO_GRID = {"dxv_distance": "dxv_distance: frame 1 has no grid yet (call dxv_voxelize first)",
@@ -72,7 +76,10 @@ NO_GRID = {"dxv_distance": "dxv_distance: frame 1 has no grid yet (call dxv_voxe
            "dxv_thin": "dxv_thin: frame 1 has no grid yet (call dxv_voxelize first)",
            "dxv_thickness": "dxv_thickness: frame 1 has no grid yet (call dxv_voxelize first)",
            "dxv_geodesic": "dxv_geodesic: frame 1 has no grid yet (call dxv_voxelize first)",
-           "dxv_measure": "dxv_measure: frame 1 has no grid yet (call dxv_voxelize first)"}
+           "dxv_measure": "dxv_measure: frame 1 has no grid yet (call dxv_voxelize first)",
+           "dxv_partition": "dxv_partition: frame 1 has no grid yet (call dxv_voxelize first)",
+           "dxv_skeleton": "dxv_skeleton: frame 1 has no grid yet (call dxv_voxelize first)",
+           "dxv_access": "dxv_access: frame 1 has no grid yet (call dxv_voxelize first)"}
 SLAB = {"dxv_distance": "dxv_distance: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share",
         "dxv_octree": "dxv_octree: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share",
         "dxv_octree_expand": "dxv_octree_expand: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share",
@@ -82,7 +89,10 @@ SLAB = {"dxv_distance": "dxv_distance: needs the whole grid of the frame's last 
         "dxv_thin": "dxv_thin: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share",
         "dxv_thickness": "dxv_thickness: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share",
         "dxv_geodesic": "dxv_geodesic: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share",
-        "dxv_measure": "dxv_measure: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share"}
+        "dxv_measure": "dxv_measure: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share",
+        "dxv_partition": "dxv_partition: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share",
+        "dxv_skeleton": "dxv_skeleton: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share",
+        "dxv_access": "dxv_access: needs the whole grid of the frame's last launch (z0 = 0, nz = grid_dim), not a slab or a share"}
 
 
 def test_a_frame_without_a_grid(v):
@@ -161,6 +171,28 @@ def accessors(v):
                      ("dxv_geodesic_info", lambda: lib.dxv_geodesic_info(ctx, None, None, None, None, None, None, None)),
                      ("dxv_geodesic_work_info", lambda: lib.dxv_geodesic_work_info(ctx, None, None, None)),
                      ("dxv_geodesic_path", lambda: lib.dxv_geodesic_path(ctx, 0, None, 0, C.byref(C.c_uint32())))],
+        "partition": [("dxv_partition_labels_device_ptr", lambda: lib.dxv_partition_labels_device_ptr(ctx)),
+                      ("dxv_partition_labels_download", lambda: lib.dxv_partition_labels_download(ctx, p, FIELD)),
+                      ("dxv_partition_table_device_ptr", lambda: lib.dxv_partition_table_device_ptr(ctx)),
+                      ("dxv_partition_table_download", lambda: lib.dxv_partition_table_download(ctx, p, 32)),
+                      ("dxv_partition_throats_device_ptr", lambda: lib.dxv_partition_throats_device_ptr(ctx)),
+                      ("dxv_partition_throats_download", lambda: lib.dxv_partition_throats_download(ctx, p, 20))],
+        "skeleton": [("dxv_skeleton_labels_device_ptr", lambda: lib.dxv_skeleton_labels_device_ptr(ctx)),
+                     ("dxv_skeleton_labels_download", lambda: lib.dxv_skeleton_labels_download(ctx, p, FIELD)),
+                     ("dxv_skeleton_nodes_device_ptr", lambda: lib.dxv_skeleton_nodes_device_ptr(ctx)),
+                     ("dxv_skeleton_nodes_download", lambda: lib.dxv_skeleton_nodes_download(ctx, p, 32)),
+                     ("dxv_skeleton_branches_device_ptr", lambda: lib.dxv_skeleton_branches_device_ptr(ctx)),
+                     ("dxv_skeleton_branches_download", lambda: lib.dxv_skeleton_branches_download(ctx, p, 48)),
+                     ("dxv_skeleton_prune", lambda: lib.dxv_skeleton_prune_async(ctx, 0)),
+                     ("dxv_skeleton_prune", lambda: lib.dxv_skeleton_prune(ctx, 0))],
+        "access": [("dxv_access_device_ptr", lambda: lib.dxv_access_device_ptr(ctx)),
+                   ("dxv_access_download", lambda: lib.dxv_access_download(ctx, p, FIELD)),
+                   ("dxv_access_histogram_download", lambda: lib.dxv_access_histogram_download(ctx, p, HISTOGRAM)),
+                   ("dxv_access_info", lambda: lib.dxv_access_info(ctx, None, None, None, None, None, None, None)),
+                   ("dxv_access_work_info", lambda: lib.dxv_access_work_info(ctx, None, None, None))],
+        "intrusion": [("dxv_intrusion_device_ptr", lambda: lib.dxv_intrusion_device_ptr(ctx)),
+                      ("dxv_intrusion_download", lambda: lib.dxv_intrusion_download(ctx, p, FIELD)),
+                      ("dxv_intrusion_histogram_download", lambda: lib.dxv_intrusion_histogram_download(ctx, p, HISTOGRAM))],
     }
 
 
@@ -171,7 +203,11 @@ NONE_YET = {"distance": "%s: frame 0 has no distance field yet (call dxv_distanc
             "components": "%s: frame 0 has no components yet (call dxv_components first)",
             "measure": "%s: frame 0 has no measure yet (call dxv_measure first)",
             "thickness": "%s: frame 0 has no thickness map yet (call dxv_thickness first)",
-            "geodesic": "%s: frame 0 has no geodesic map yet (call dxv_geodesic first)"}
+            "geodesic": "%s: frame 0 has no geodesic map yet (call dxv_geodesic first)",
+            "partition": "%s: frame 0 has no partition yet (call dxv_partition first)",
+            "skeleton": "%s: frame 0 has no skeleton yet (call dxv_skeleton first)",
+            "access": "%s: frame 0 has no access map yet (call dxv_access first)",
+            "intrusion": "%s: frame 0 has no access map yet (call dxv_access first)"}
 STALE = {"distance": "%s: frame 0 was launched again since its distance field was made: the field is stale",
          "mesh distance": "%s: frame 0 was launched or filled again since its mesh distance field was made: the field is stale",
          "isosurface": "%s: frame 0 was launched or filled again since its isosurface was made: the mesh is stale",
@@ -179,7 +215,11 @@ STALE = {"distance": "%s: frame 0 was launched again since its distance field wa
          "components": "%s: frame 0 was launched, filled, expanded or selected again since its components were labelled: labels and table are stale",
          "measure": "%s: frame 0 was launched, edited or labelled again since its components were measured: the measure is stale",
          "thickness": "%s: frame 0 was launched or edited again since its thickness map was made: map and histogram are stale",
-         "geodesic": "%s: frame 0 was launched or edited again since its geodesic map was made: the map is stale"}
+         "geodesic": "%s: frame 0 was launched or edited again since its geodesic map was made: the map is stale",
+         "partition": "%s: frame 0 was launched or edited again since its partition was made: labels, table and throats are stale",
+         "skeleton": "%s: frame 0 was launched or edited again since its skeleton was made: labels and tables are stale",
+         "access": "%s: frame 0 was launched or edited again since its access map was made: maps and histograms are stale",
+         "intrusion": "%s: frame 0 was launched or edited again since its access map was made: maps and histograms are stale"}
 
 
 def make_every_product(v):
@@ -192,16 +232,28 @@ def make_every_product(v):
     assert lib.dxv_measure(ctx) == 0
     assert lib.dxv_thickness(ctx, 0, CAP_SQ) == 0
     assert lib.dxv_geodesic(ctx, 0, 0, 0, None, 0, 0) == 0
+    assert lib.dxv_partition(ctx, 0, CAP_SQ, 1) == 0
+    assert lib.dxv_skeleton(ctx, None) == 0
+    assert lib.dxv_access(ctx, 0, 6, CAP_SQ, 0, None, 0, 1) == 0
 
 
-def sizes(v):
+def silent_sizes(v):
+    """every size that never speaks (all of them but the measure's)"""
     lib, ctx = v._lib, v._ctx
     return (lib.dxv_distance_bytes(ctx), lib.dxv_mesh_distance_bytes(ctx), lib.dxv_octree_bytes(ctx), lib.dxv_components_labels_bytes(ctx),
             lib.dxv_components_table_bytes(ctx), lib.dxv_thickness_bytes(ctx), lib.dxv_thickness_histogram_bytes(ctx), lib.dxv_geodesic_bytes(ctx),
-            lib.dxv_measure_table_bytes(ctx))
+            lib.dxv_partition_labels_bytes(ctx), lib.dxv_partition_table_bytes(ctx), lib.dxv_partition_throats_bytes(ctx),
+            lib.dxv_skeleton_labels_bytes(ctx), lib.dxv_skeleton_nodes_bytes(ctx), lib.dxv_skeleton_branches_bytes(ctx),
+            lib.dxv_access_bytes(ctx), lib.dxv_access_histogram_bytes(ctx), lib.dxv_intrusion_bytes(ctx), lib.dxv_intrusion_histogram_bytes(ctx))
 
 
-NO_SIZES = (0,) * 9
+def sizes(v):
+    """[0 .. 7] distance .. geodesic, [8] the measure's, [9 .. 18] partition .. intrusion"""
+    silent = silent_sizes(v)
+    return silent[:8] + (v._lib.dxv_measure_table_bytes(v._ctx),) + silent[8:]
+
+
+NO_SIZES = (0,) * 19
 
 
 def test_products_that_were_never_made_and_products_gone_stale(v):
@@ -219,6 +271,9 @@ def test_products_that_were_never_made_and_products_gone_stale(v):
     got = sizes(v)
     assert got[:2] == (FIELD, FIELD) and got[2] >= 8 and got[3] == FIELD and got[4] % 24 == 0 and got[4] > 0
     assert got[5:8] == (FIELD, HISTOGRAM, FIELD) and got[8] == 96 * (got[4] // 24 + 1)
+    assert got[9] == FIELD and got[10] % 32 == 0 and got[10] > 0 and got[11] % 20 == 0                 # partition: labels, table, throats
+    assert got[12] == FIELD and got[13] % 32 == 0 and got[14] % 48 == 0 and got[13] + got[14] > 0      # skeleton: labels, nodes, branches
+    assert got[15:19] == (FIELD, HISTOGRAM, FIELD, HISTOGRAM)                                          # access and intrusion: map, histogram
     assert lib.dxv_distance_device_ptr(ctx) and lib.dxv_octree_info(ctx, None, None, None) == 0
     v.Voxelize(N)                                                       # launched again: every one of them is stale
     for family, calls in accessors(v).items():
@@ -248,15 +303,100 @@ def test_a_field_without_triangles_and_a_field_in_the_int32_format(v):
     refused(v, lib.dxv_isosurface(ctx, 1, 0.0, 0), "dxv_isosurface: the frame's distance field is in the int32 format; needs DXV_DIST_F32")
 
 
+def test_a_partition_without_throats_and_an_access_without_intrusion(v):
+    lib, ctx = v._lib, v._ctx
+    buf = np.empty(FIELD, np.uint8)
+    p = buf.ctypes.data_as(C.c_void_p)
+    v.Voxelize(N)
+    assert lib.dxv_partition(ctx, 0, CAP_SQ, 0) == 0
+    refused(v, lib.dxv_partition_throats_device_ptr(ctx), "dxv_partition_throats_device_ptr: frame 0's partition was made without throats (want_throats = 0)")
+    refused(v, lib.dxv_partition_throats_download(ctx, p, 0), "dxv_partition_throats_download: frame 0's partition was made without throats (want_throats = 0)")
+    assert lib.dxv_partition_throats_bytes(ctx) == 0
+    assert lib.dxv_partition_labels_device_ptr(ctx) and lib.dxv_partition_labels_bytes(ctx) == FIELD        # (the rest of it is handed out)
+    assert lib.dxv_access(ctx, 0, 6, CAP_SQ, 0, None, 0, 0) == 0
+    refused(v, lib.dxv_intrusion_device_ptr(ctx),
+            "dxv_intrusion_device_ptr: the access map of frame 0 was made without its intrusion map (call dxv_access with want_intrusion != 0)")
+    refused(v, lib.dxv_intrusion_download(ctx, p, FIELD),
+            "dxv_intrusion_download: the access map of frame 0 was made without its intrusion map (call dxv_access with want_intrusion != 0)")
+    refused(v, lib.dxv_intrusion_download(ctx, p, 0),
+            "dxv_intrusion_download: the access map of frame 0 was made without its intrusion map (call dxv_access with want_intrusion != 0)")
+    refused(v, lib.dxv_intrusion_histogram_download(ctx, p, HISTOGRAM),
+            "dxv_intrusion_histogram_download: the access map of frame 0 was made without its intrusion map (call dxv_access with want_intrusion != 0)")
+    assert lib.dxv_intrusion_bytes(ctx) == 0 and lib.dxv_intrusion_histogram_bytes(ctx) == 0
+    assert lib.dxv_access_device_ptr(ctx) and lib.dxv_access_bytes(ctx) == FIELD and lib.dxv_access_histogram_bytes(ctx) == HISTOGRAM
+
+
+def test_sizes_are_silent_except_the_one_that_speaks(v):
+    lib, ctx = v._lib, v._ctx
+    buf = np.empty(FIELD, np.uint8)
+    p = buf.ctypes.data_as(C.c_void_p)
+    v.Voxelize(N)
+    # none yet
+    said = "dxv_distance_download: frame 0 has no distance field yet (call dxv_distance first)"
+    refused(v, lib.dxv_distance_download(ctx, p, FIELD), said)
+    for size in silent_sizes(v):
+        assert size == 0 and last(v) == said
+    assert lib.dxv_measure_table_bytes(ctx) == 0
+    assert last(v) == "dxv_measure_table_bytes: frame 0 has no measure yet (call dxv_measure first)"
+    # stale
+    make_every_product(v)
+    v.Voxelize(N)
+    said = "dxv_distance_download: frame 0 was launched again since its distance field was made: the field is stale"
+    refused(v, lib.dxv_distance_download(ctx, p, FIELD), said)
+    for size in silent_sizes(v):
+        assert size == 0 and last(v) == said
+    assert lib.dxv_measure_table_bytes(ctx) == 0
+    assert last(v) == "dxv_measure_table_bytes: frame 0 was launched, edited or labelled again since its components were measured: the measure is stale"
+
+
+def test_an_empty_table_is_null_without_a_word(v):
+    from raycast_restated import write_grid
+    lib, ctx = v._lib, v._ctx
+    v.Voxelize(N)
+    write_grid(v, np.zeros((N, N, N), np.uint8))
+    assert lib.dxv_components(ctx, 0, 6) == 0, last(v)                  # (DXV_COMP_SOLID: no component)
+    assert lib.dxv_skeleton(ctx, None) == 0, last(v)
+    assert lib.dxv_partition(ctx, 0, CAP_SQ, 1) == 0, last(v)
+    said = "dxv_distance_device_ptr: frame 0 has no distance field yet (call dxv_distance first)"
+    refused(v, lib.dxv_distance_device_ptr(ctx), said)
+    for ptr in (lib.dxv_components_table_device_ptr, lib.dxv_skeleton_nodes_device_ptr, lib.dxv_skeleton_branches_device_ptr,
+                lib.dxv_partition_table_device_ptr, lib.dxv_partition_throats_device_ptr):
+        assert ptr(ctx) is None and last(v) == said
+    for size in (lib.dxv_components_table_bytes, lib.dxv_skeleton_nodes_bytes, lib.dxv_skeleton_branches_bytes, lib.dxv_partition_table_bytes,
+                 lib.dxv_partition_throats_bytes):
+        assert size(ctx) == 0
+    for download in (lib.dxv_components_table_download, lib.dxv_skeleton_nodes_download, lib.dxv_skeleton_branches_download,
+                     lib.dxv_partition_table_download, lib.dxv_partition_throats_download):
+        assert download(ctx, None, 0) == 0, last(v)
+    for ptr in (lib.dxv_components_labels_device_ptr, lib.dxv_skeleton_labels_device_ptr, lib.dxv_partition_labels_device_ptr):
+        assert ptr(ctx)
+    assert last(v) == said
+
+
 def test_downloads_given_a_wrong_byte_count_or_no_buffer(v):
     lib, ctx = v._lib, v._ctx
     v.Voxelize(N)
     make_every_product(v)
     nv, nt, nodes, K = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+    regions, throats, skel_nodes, skel_branches = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
     assert lib.dxv_isosurface_counts(ctx, C.byref(nv), C.byref(nt)) == 0 and nv.value and nt.value
     assert lib.dxv_octree_info(ctx, None, C.byref(nodes), None) == 0 and nodes.value
     assert lib.dxv_components_info(ctx, C.byref(K), None, None) == 0 and K.value
-    buf = np.empty(max(FIELD, 24 * nv.value, 12 * nt.value, 8 * nodes.value, 24 * K.value) + 8, np.uint8)
+    assert lib.dxv_partition_info(ctx, None, C.byref(regions), C.byref(throats), None) == 0 and regions.value
+    assert lib.dxv_skeleton_info(ctx, None, C.byref(skel_nodes), C.byref(skel_branches), None, None, None) == 0 and skel_nodes.value + skel_branches.value
+    # every download the checks above leave out: (its name, its call, what it asks for)
+    others = (("dxv_measure_table_download", lib.dxv_measure_table_download, 96 * (K.value + 1)),
+              ("dxv_thickness_download", lib.dxv_thickness_download, FIELD), ("dxv_thickness_histogram_download", lib.dxv_thickness_histogram_download, HISTOGRAM),
+              ("dxv_geodesic_download", lib.dxv_geodesic_download, FIELD),
+              ("dxv_partition_labels_download", lib.dxv_partition_labels_download, FIELD),
+              ("dxv_partition_table_download", lib.dxv_partition_table_download, 32 * regions.value),
+              ("dxv_partition_throats_download", lib.dxv_partition_throats_download, 20 * throats.value),
+              ("dxv_skeleton_labels_download", lib.dxv_skeleton_labels_download, FIELD),
+              ("dxv_skeleton_nodes_download", lib.dxv_skeleton_nodes_download, 32 * skel_nodes.value),
+              ("dxv_skeleton_branches_download", lib.dxv_skeleton_branches_download, 48 * skel_branches.value),
+              ("dxv_access_download", lib.dxv_access_download, FIELD), ("dxv_access_histogram_download", lib.dxv_access_histogram_download, HISTOGRAM),
+              ("dxv_intrusion_download", lib.dxv_intrusion_download, FIELD), ("dxv_intrusion_histogram_download", lib.dxv_intrusion_histogram_download, HISTOGRAM))
+    buf = np.empty(max(FIELD, 24 * nv.value, 12 * nt.value, 8 * nodes.value, 24 * K.value, max(want for _, _, want in others)) + 8, np.uint8)
     p = buf.ctypes.data_as(C.c_void_p)
     refused(v, lib.dxv_distance_download(ctx, p, 16385), "dxv_distance_download: expected 16384 bytes, got 16385")
     refused(v, lib.dxv_distance_download(ctx, None, 16384), "dxv_distance_download: expected 16384 bytes, got 16384")
@@ -278,7 +418,15 @@ def test_downloads_given_a_wrong_byte_count_or_no_buffer(v):
     want = 24 * K.value
     refused(v, lib.dxv_components_table_download(ctx, p, want + 1), f"dxv_components_table_download: expected {want} bytes, got {want + 1}")
     refused(v, lib.dxv_components_table_download(ctx, None, want), f"dxv_components_table_download: expected {want} bytes, got {want}")
+    for who, fn, want in others:
+        refused(v, fn(ctx, p, want + 1), f"{who}: expected {want} bytes, got {want + 1}")
+        if want:                                                       # (a table without records has nothing to copy: NULL with 0 is served, below)
+            refused(v, fn(ctx, None, want), f"{who}: expected {want} bytes, got {want}")
+        else:
+            assert fn(ctx, None, 0) == 0, last(v)
     # the same calls with what they ask for
+    for who, fn, want in others:
+        assert fn(ctx, p, want) == 0, last(v)
     for fn, want in ((lib.dxv_distance_download, FIELD), (lib.dxv_mesh_distance_download, FIELD), (lib.dxv_mesh_distance_triangles_download, FIELD),
                      (lib.dxv_isosurface_vertices_download, 24 * nv.value), (lib.dxv_isosurface_indices_download, 12 * nt.value),
                      (lib.dxv_octree_download, 8 * nodes.value), (lib.dxv_components_labels_download, FIELD),
