@@ -13,6 +13,7 @@ import pytest
 
 import access_host as ah
 import access_restated as ar
+import flood_seeds as fs
 import grid_sides as gs
 import thickness_host as th
 
@@ -44,6 +45,26 @@ def test_host_library_equals_the_restatements_at_every_side(N):
                     other = ah.access(g, of, connectivity, 65, seeds, cull=0, shuffle=N + connectivity)
                     assert other["A"].tobytes() == A.tobytes() and other["I"].tobytes() == got["I"].tobytes() and other["tally"] == got["tally"], key
     assert seen == (5 if N >= 6 else 4)
+
+
+@pytest.mark.parametrize("connectivity", [6, 26])
+@pytest.mark.parametrize("of", [ar.SOLID, ar.EMPTY])
+def test_host_library_equals_the_restatement_with_a_seed_in_every_tile(of, connectivity):
+    """The seeding of tests/test_gpu_flood_wide_rounds.py, which takes the host library for its expectation at side 162: one member of every
+    8^3 tile of "random 0.3" (tests/flood_seeds.py), so round 0 runs every tile.  Side 66 (729 tiles, rows of two words, partial last tiles) is
+    the largest of the sweep's residues at which the widest-path search stays within seconds -- measured: solid 0.5 s (6) and 2.5 s (26),
+    empty 2.3 s and 5.9 s; at 50 it takes 0.2 .. 2.6 s, and the host library 0.8 .. 1.5 s at 162.  The items take 0.7 .. 5.0 s."""
+    N = 66
+    g = dict(gs.grids(N, ("random 0.3",)))["random 0.3"]
+    seeds = fs.tile_seeds(g, of, 3 + connectivity)
+    assert len(np.unique(fs.tile_of(seeds, N))) == len(seeds) == 9 ** 3 and ar.members(g, of).reshape(-1)[seeds].all()
+    got = ah.access(g, of, connectivity, 65, seeds)
+    A = ar.access(g, of, connectivity, 65, seeds)
+    assert got["A"].tobytes() == A.tobytes() and got["I"].tobytes() == ar.intrusion(g, of, A).tobytes(), (of, connectivity)
+    assert got["hist_a"].tobytes() == ar.histogram(A, 65).tobytes() and got["hist_i"].tobytes() == ar.histogram(got["I"], 65).tobytes()
+    assert got["tally"] == ar.tally(g, of, A, seeds) and got["tally"]["seeds_used"] == 9 ** 3 and got["tiles_run"] >= 9 ** 3
+    masked = ah.access(g, of, connectivity, 65, fs.seed_mask(seeds, N), shuffle=connectivity)
+    assert masked["A"].tobytes() == A.tobytes() and masked["I"].tobytes() == got["I"].tobytes() and masked["tally"] == got["tally"]
 
 
 @pytest.mark.parametrize("name", [b[0] for b in ar.builders()])

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import flood_seeds as fs
 import geodesic_host as gh
 import geodesic_restated as gr
 import grid_sides as gs
@@ -83,6 +84,28 @@ def test_seed_lists_and_masks():
             assert out.tobytes() == want.tobytes() and tally["seeds_used"] == 3
     out, tally, (rounds, tiles) = gh.geodesic(g, gr.EMPTY, gr.FACES, np.zeros(0, np.uint32))
     assert (rounds, tiles) == (1, 0) and tally["reached"] == 0 and tally["unreached"] == len(inside)
+
+
+@pytest.mark.parametrize("N, of", [(66, gr.SOLID), (66, gr.EMPTY), (162, gr.SOLID)])
+def test_host_library_equals_dijkstra_with_a_seed_in_every_tile(N, of):
+    """The seeding of tests/test_gpu_flood_wide_rounds.py, which takes the host library for its expectation at side 162: one member of every
+    8^3 tile of "random 0.3" (tests/flood_seeds.py), so round 0 runs every tile -- 9261 at 162, more than the 8192 workgroups of a round's
+    launch; 729 at 66.  Measured: at 162 the solid kind takes the host library 1.9 s (FACES) and 2.4 s (CHAMFER) and Dijkstra 0.8 s and 2.5 s;
+    the empty kind takes Dijkstra 3.7 s and 8.2 s there (host library 2.7 s and 4.6 s), so it is held at side 66.  The items take 6.7 s (162, solid), 0.6 s
+    (66, solid) and 1.4 s (66, empty)."""
+    g = dict(gs.grids(N, ("random 0.3",)))["random 0.3"]
+    tiles = ((N + 7) // 8) ** 3
+    for metric in (gr.FACES, gr.CHAMFER):
+        seeds = fs.tile_seeds(g, of, 1 + metric)
+        assert len(np.unique(fs.tile_of(seeds, N))) == len(seeds) == tiles and gr.members(g, of).reshape(-1)[seeds].all()
+        assert (tiles > fs.ROUND_BLOCKS) == (N == 162)
+        assert (fs.tile_seeds(g, of, 7) != seeds).any() and fs.tile_seeds(g, of, 1 + metric).tobytes() == seeds.tobytes()
+        got, tally, (rounds, run) = gh.geodesic(g, of, metric, seeds)
+        want = gr.geodesic_dijkstra(g, of, metric, seeds)
+        assert got.tobytes() == want.tobytes() and tally == gr.tally(want), (N, of, metric)
+        assert tally["seeds_used"] == tiles and run >= tiles
+        if N == 66:
+            assert gh.geodesic(g, of, metric, fs.seed_mask(seeds, N))[0].tobytes() == want.tobytes()
 
 
 def test_a_changed_voxel_flags_the_tiles_that_hold_a_neighbour_of_it():

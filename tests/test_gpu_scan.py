@@ -4,8 +4,11 @@ isosurface call it --, what = 1 launch_scan_sums alone with the totals right beh
 
 The sizes are the ones at which the code takes another path: one word, less than a wave, one word less than / exactly / one word more than a
 block of 1024, several blocks with a ragged end, and 1024 * 1024 + 5 words = 1025 block sums, where a thread of the one workgroup that scans
-the sums takes TWO of them (chunk = 2), thread 512 takes the one that is left and threads 513 .. 1023 an empty, clamped range -- the path
-that no operator test reaches (it needs more than 2^20 words, or a grid side of 102 for thickness and partition)."""
+the sums takes TWO of them (chunk = 2), thread 512 takes the one that is left and threads 513 .. 1023 an empty, clamped range.  Of the
+operator tests that path (more than 2^20 words, or a grid side of 102 for thickness and partition) is reached by test_gpu_thickness_sides.py at
+126, 130 and 194, by test_gpu_access_sides.py at the same sides out of access's own scratch layout, by test_gpu_partition_sides.py at 102,
+126, 130 and 194 -- there also under the heads' scan, with more than 2^20 interface faces -- and by test_gpu_flood_wide_rounds.py at 160 and
+162 through the intrusion map."""
 import numpy as np
 import pytest
 

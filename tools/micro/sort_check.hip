@@ -18,7 +18,11 @@ int main(int argc, char** argv)
 {
     const bool timing = argc > 1 && !strncmp(argv[1], "time", 4);
     struct Case { uint32_t n; int loBit, numBits; };
-    std::vector<Case> cases = {{1, 32, 30}, {63, 32, 30}, {4097, 32, 30}, {70000, 32, 30}, {1000000, 32, 30}, {6403636, 27, 37}, {5000000, 29, 35}};
+    // the LBVH's field, the lists' two; then the partition's (partition.hip: loBit 0, a pair of region labels of numBits / 2 bits each, the
+    // smaller one on top) at the label widths from 17 bits up, with a key count on each side of the small shape's last (2 * 2^20): 4 passes of
+    // the small shape, 5 of the medium one and of 8-bit digits; at 21-bit labels 6
+    std::vector<Case> cases = {{1, 32, 30}, {63, 32, 30}, {4097, 32, 30}, {70000, 32, 30}, {1000000, 32, 30}, {6403636, 27, 37}, {5000000, 29, 35},
+                               {2097152, 0, 34}, {2097153, 0, 34}, {1052426, 0, 36}, {3521131, 0, 36}, {423304, 0, 40}, {2200000, 0, 40}, {2000003, 0, 42}, {2300001, 0, 42}};
     if (timing) cases = {{1000000, 32, 30}, {10000000, 32, 30}, {6403636, 27, 37}, {150000000, 29, 35}};
     std::vector<int> plans = {0, 8, 9, 10, 11, 16 + 10, 32 + 10, 32 + 8, 16 + 8, 48 + 11};
     if (argc > 2) { plans.clear(); for (int a = 2; a < argc; ++a) plans.push_back(atoi(argv[a])); if (!strcmp(argv[1], "time1")) cases.resize(1); else if (!strcmp(argv[1], "time6")) cases = {cases[2]}; }
@@ -26,7 +30,13 @@ int main(int argc, char** argv)
     for (const Case& c : cases) {
         std::vector<uint64_t> h(c.n);
         const uint64_t fieldMask = (c.numBits >= 64 ? ~0ull : ((1ull << c.numBits) - 1ull)) << c.loBit;
-        for (uint32_t i = 0; i < c.n; ++i) {
+        for (uint32_t i = 0; i < c.n && c.loBit == 0; ++i) {
+            // the partition's words: two different labels >= 1 of the full width, the smaller on top, the other one of its next eight (pairs repeat:
+            // a throat has many faces)
+            const uint64_t half = (uint64_t)c.numBits / 2u, a = 1ull + rng() % ((1ull << half) - 9ull), b = a + 1ull + rng() % 8ull;
+            h[i] = a << half | b;
+        }
+        for (uint32_t i = 0; i < c.n && c.loBit != 0; ++i) {
             // clustered like Morton codes of a surface: a random field from a small set of high parts + the index below
             const uint64_t f = ((rng() % 4096ull) * 0x100000ull + (rng() & 0xfffffull)) * 0x9e3779b1ull;
             h[i] = ((f << c.loBit) & fieldMask) | (uint64_t)i;
