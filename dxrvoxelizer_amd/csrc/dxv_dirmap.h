@@ -32,8 +32,10 @@ namespace dxv {
 //         128 x 128 cells).  A ray in cell (x, y) passes iff every byte of (x, y, 127 - x, 127 - y) is >= this word's
 //         byte: one subtraction of packed bytes (dm_local_pass).
 //   edge  signed bytes (a, b, c1, c2): the ONE edge of the projected, dilated triangle that cuts most off that box.
-//         The ray passes iff a x + b y + 127 c1 + c2 >= 0 (one v_dot4c_i32_i8); 0 = no edge (clipped polygons, or no
-//         edge crosses the box).  A triangle fills at most half of its box: this halves the triangle tests.
+//         The ray passes iff a (x - 64) + b (y - 64) + 127 c1 + c2 >= 0 (one v_dot4c_i32_i8; cells from the texel's
+//         centre, so that every line through the texel has a constant the two bytes hold: dm_local_entry); 0 = no edge
+//         (clipped polygons, or no edge crosses the box).  A triangle fills at most half of its box: this halves the
+//         triangle tests.
 //   rr    (0x7fff - r0) | r1 << 16 | 0x80008000, r0 / r1 the outward-rounded radial range as halfs: positive halfs
 //         order like integers, so r1 >= near and r0 <= (start + closest hit) are one packed subtraction as well.
 //   tri   position in the scene's triangle order (TriPos index) in the low 26 bits; the high 6 bits say how far behind this
@@ -131,14 +133,32 @@ DXV_HD int32_t dm_dot4(uint32_t a, uint32_t b)
 #endif
 }
 
-// The ray's side of an entry test: q = bytes (x, y, 127 - x, 127 - y) | 0x80808080, p = bytes (x, y, 127, 1),
-// rc = (0x7fff - half_down(bound)) | half_up(near) << 16 (dm_radial_word)
+// The ray's side of an entry test: q = bytes (x, y, 127 - x, 127 - y) | 0x80808080, p = signed bytes (x - 64, y - 64, 127, 1)
+// -- the edge word counts cells from the texel's CENTRE --, rc = (0x7fff - half_down(bound)) | half_up(near) << 16 (dm_radial_word)
 struct DirRayLocal { uint32_t q, p; };
 DXV_HD DirRayLocal dm_ray_local(uint32_t x, uint32_t y)
 {
     DirRayLocal l;
-    l.q = (x | (y << 8) | ((kDmCells - 1u - x) << 16) | ((kDmCells - 1u - y) << 24)) | 0x80808080u;
-    l.p = x | (y << 8) | (127u << 16) | (1u << 24);
+    // q in three instructions from w = x | y << 8 where the sum of four shifted bytes took four: the upper bytes (127 - x) | 0x80 =
+    // 255 - x = x ^ 0xff are w's complement, shifted.  That pays for the instruction the centred p costs more than the corner's: the
+    // kernels' instruction counts stay what they were.  (The empty asm statements pin the three steps: left alone the compiler
+    // moves y's shift into the branches y comes out of, builds the complement from x and y again, or adds all three parts at once
+    // with the constant in a scalar register -- an instruction more each way.)
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(y));
+#endif
+    uint32_t w = x | (y << 8);
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(w));
+#endif
+    uint32_t lo = w + 0x8080u;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(lo));
+#endif
+    l.q = ((~w) << 16) + lo;
+    // x - 64 in each of the two low bytes: adding 64 cannot carry out of a byte, and flipping bit 7 of the sum is adding 128 more,
+    // 192 = -64 in all -- one add and one xor where the corner's word took one or
+    l.p = (w + ((127u << 16) | (1u << 24) | 0x4040u)) ^ 0x8080u;
     return l;
 }
 // Directed float -> half for the values a ray brings to the integer radial test: positive, inside the half's normal
@@ -804,10 +824,16 @@ DXV_HD void dm_local_radial(const DirRecord& rec, uint32_t R, uint32_t i, uint32
 // the edge of the projected triangle that removes most of that box.
 // Edge arithmetic (builder side, double): inside the dilated triangle means (p - P_k) . n_k + pad >= 0 for the unit inward
 // normal n_k of every edge k.  With texel-local coordinates X, Y (u = 2 i / R - 1 + X / (64 R)) that is A X + B Y + C >= 0;
-// scaled so that the larger of |A|, |B| is 127 and rounded to bytes a, b.  For a ray in integer cell (x, y), i.e. anywhere
-// in [x, x + 1) x [y, y + 1), a x + b y differs from the scaled A X + B Y by at most |A| + |B| (position inside the cell)
-// + 127 (rounding of a and b, x, y <= 127) + a little for the ray's own float arithmetic: c takes all of that, so the
-// byte test passes wherever the real one does (it gives away two to three cells of 128, 2 % of a texel).
+// scaled so that the larger of |A|, |B| is 127 (ka, kb) and rounded to bytes a, b.  The bytes multiply cells counted from the
+// texel's CENTRE: a ray in integer cell (x, y) is anywhere in [x, x + 1) x [y, y + 1), X = 64 + x' + fx with x' = x - 64 in
+// [-64, 63] and fx in [0, 1), so the scaled function is  ka x' + kb y' + (C + 64 (ka + kb)) + ka fx + kb fy:  the constant is the
+// edge function AT THE CENTRE, ka fx + kb fy is at most |ka| + |kb| (position inside the cell), and a x' + b y' falls short of
+// ka x' + kb y' by at most 0.5 (|x'| + |y'|) <= 64 (rounding of a and b) -- half of what cells counted from the corner, up to
+// 127 each way, cost.  c takes all of that + 13 for the ray's own float arithmetic, so the byte test passes wherever the real
+// one does (it gives away one and a half to three cells of 128).  Centred, |a x' + b y'| <= 2 * 127 * 64 = 16,256: every line
+// that crosses the texel has a c the two bytes (127 c1 + c2) hold -- from the corner a diagonal edge beyond the centre, a quad's
+// hypotenuse, had none and was clamped or dropped.  What is still out of range cuts nothing (c >= 16,256: dropped) or all of
+// the texel (c < -16,256: clamped, never stricter).
 DXV_HD DirEntry dm_local_entry(const DirRecord& rec, uint32_t R, uint32_t i, uint32_t j, uint32_t tri)
 {
     DirEntry e;
@@ -842,18 +868,20 @@ DXV_HD DirEntry dm_local_entry(const DirRecord& rec, uint32_t R, uint32_t i, uin
         const double sc = (double)(127.0f / (float)big);                // (one scale for A, B and C: its last bits do not matter)
         const double ka = A * sc, kb = B * sc;
         const int a = (int)__builtin_floor(ka + 0.5), b = (int)__builtin_floor(kb + 0.5);
-        double cd = __builtin_ceil(C * sc + __builtin_fabs(ka) + __builtin_fabs(kb) + 127.0 + 13.0);
-        if (!(cd < 16256.0)) continue;                                   // this edge cuts nothing representable off the texel
-        if (cd < -16256.0) cd = -16256.0;                               // (more permissive: safe)
+        double cd = __builtin_ceil(C * sc + 64.0 * (ka + kb) + __builtin_fabs(ka) + __builtin_fabs(kb) + 64.0 + 13.0);
+        if (!(cd < 16256.0)) continue;                                   // this edge cuts nothing off the texel
+        if (cd < -16256.0) cd = -16256.0;                               // (never stricter: safe)
         const int c = (int)cd;
         const int c1b = c / 127, c2b = c - 127 * c1b;                   // truncation: |c2b| < 127
         // how much of the box does it remove?  Nothing when the box's corner farthest outside is still inside; else 3 x 3 samples
-        const int worst = a * (int)(a < 0 ? x1 : x0) + b * (int)(b < 0 ? y1 : y0) + c;
+        // (cells from the centre, as the ray brings them)
+        const int half = (int)(kDmCells / 2u);
+        const int worst = a * ((int)(a < 0 ? x1 : x0) - half) + b * ((int)(b < 0 ? y1 : y0) - half) + c;
         if (worst >= 0) continue;
         int cut = 1;
         for (int sy = 0; sy < 3; ++sy)
             for (int sx = 0; sx < 3; ++sx) {
-                const int x = (int)x0 + (int)((x1 - x0) * (2 * sx + 1) / 6), y = (int)y0 + (int)((y1 - y0) * (2 * sy + 1) / 6);
+                const int x = (int)x0 + (int)((x1 - x0) * (2 * sx + 1) / 6) - half, y = (int)y0 + (int)((y1 - y0) * (2 * sy + 1) / 6) - half;
                 if (a * x + b * y + c < 0) ++cut;
             }
         if (cut > bestCut) {

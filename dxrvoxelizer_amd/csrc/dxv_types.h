@@ -90,7 +90,7 @@ struct SceneHeader {
 static_assert(sizeof(SceneHeader) % 16 == 0, "header alignment");
 
 constexpr uint32_t kSceneMagic = 0x53565844u; // "DXVS"
-constexpr uint32_t kSceneVersion = 8;
+constexpr uint32_t kSceneVersion = 9;          // 9: the lists' edge words count cells from the texel's centre (dxv_dirmap.h: dm_ray_local); an older blob's count them from its corner
 
 // canonical constants (hlsl:5, :76-77)
 constexpr float kThreshold = 0.12f;
