@@ -44,7 +44,7 @@ template <bool PER_FACE>
 __global__ __launch_bounds__(kThreads) void k_dm_records(const TriPos* __restrict__ triPos, uint32_t T, uint32_t R,
                                                          DirRecord* __restrict__ rec, uint32_t* __restrict__ counts,
                                                          unsigned long long* __restrict__ total, uint32_t* __restrict__ pairs,
-                                                         uint32_t* __restrict__ wideList, uint32_t stride)
+                                                         uint32_t* __restrict__ wideList, uint32_t stride, bool lateral)
 {
     // (stride > 1: every stride-th triangle only -- dirmap_count's estimate of a scene's entries on a map)
     const uint32_t t = blockIdx.x * kThreads + threadIdx.x, tri = (PER_FACE ? t / 6u : t) * stride;
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(kThreads) void k_dm_records(const TriPos* __restric
         uint32_t c = 0, i0 = 0, i1 = 0, j0 = 0, j1 = 0;
         DirTexelTest tt{};
         bool wide = false;
-        if (tri < T && dm_footprint(tp, face, f)) {
+        if (tri < T && dm_footprint(tp, face, f, lateral)) {     // (lateral: option lateralpad)
             DirRecord e = dm_record(f);
             if (dm_rect(e, R, i0, i1, j0, j1)) {
                 c = (i1 - i0 + 1u) * (j1 - j0 + 1u);
@@ -634,13 +634,13 @@ hipError_t scan_exclusive(const uint32_t* counts, uint32_t n, uint32_t* sums, ui
 // wideList: 6T words of scratch (the offsets of pass 2, not made yet)
 // stride > 1: every stride-th triangle only (an estimate: total x stride; what it leaves in the arrays is of no use to pass 2)
 hipError_t dirmap_count(const TriPos* triPos, uint32_t T, uint32_t R, DirRecord* rec, uint32_t* counts, uint32_t* pairs, uint32_t* wideList,
-                        unsigned long long* total, hipStream_t s, uint32_t stride)
+                        unsigned long long* total, bool lateral, hipStream_t s, uint32_t stride)
 {
     hipError_t e = hipMemsetAsync(total, 0, 4 * sizeof(unsigned long long), s);      // (entries, pairs; three list lengths)
     if (e != hipSuccess) return e;
     const uint32_t Ts = (T + stride - 1u) / stride;
-    if (T <= kDmFewTriangles) k_dm_records<true><<<(6u * Ts + kThreads - 1) / kThreads, kThreads, 0, s>>>(triPos, T, R, rec, counts, total, pairs, wideList, stride);
-    else k_dm_records<false><<<(Ts + kThreads - 1) / kThreads, kThreads, 0, s>>>(triPos, T, R, rec, counts, total, pairs, wideList, stride);
+    if (T <= kDmFewTriangles) k_dm_records<true><<<(6u * Ts + kThreads - 1) / kThreads, kThreads, 0, s>>>(triPos, T, R, rec, counts, total, pairs, wideList, stride, lateral);
+    else k_dm_records<false><<<(Ts + kThreads - 1) / kThreads, kThreads, 0, s>>>(triPos, T, R, rec, counts, total, pairs, wideList, stride, lateral);
     if (T > kDmFewTriangles) k_dm_count_waves<<<2048, kThreads, 0, s>>>(rec, R, wideList, counts, total);
     return hipGetLastError();
 }
@@ -701,7 +701,7 @@ __global__ __launch_bounds__(kThreads) void k_dm_far(const TriPos* __restrict__ 
 #pragma unroll 1
     for (uint32_t face = 0; face < 6u; ++face) {
         DirFootprint f;
-        if (!dm_footprint(tp, face, f)) continue;
+        if (!dm_footprint(tp, face, f, false)) continue;                // (the 2^-15 pad: a coarse map that only has to be a superset)
         const DirRecord e = dm_record(f);
         uint32_t i0, i1, j0, j1;
         if (!dm_rect(e, R, i0, i1, j0, j1)) continue;

@@ -508,7 +508,7 @@ int dxv_refit(dxv_ctx* c)
         spec = c->opt.listres ? (uint32_t)c->opt.listres : list_resolution(c);     // (the base map: a mesh that is being refitted gets its lists built for one launch)
         const ListScratchA sa = list_scratch_a(c->listScratchA.p, c->hdr.numTris);
         DXV_HIP(c, hipEventRecord(c->evList[0], c->stream));
-        DXV_HIP(c, dirmap_count(scene_tripos(c), c->hdr.numTris, spec, sa.rec, sa.counts, sa.pairs, sa.offsets, sa.total, c->stream));
+        DXV_HIP(c, dirmap_count(scene_tripos(c), c->hdr.numTris, spec, sa.rec, sa.counts, sa.pairs, sa.offsets, sa.total, c->opt.lateralpad != 0, c->stream));
         DXV_HIP(c, hipEventRecord(c->evList[1], c->stream));
         DXV_HIP(c, hipMemcpyAsync(&c->pin->listTotal, sa.total, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     }
@@ -689,6 +689,16 @@ int dxv_set_option(dxv_ctx* c, const char* key, int64_t value)
         break;
     case OptionEffect::listres:
         if (slot != (int)value && sync_frames(c)) return 1;             // the next launch rebuilds the lists: nothing may still read them
+        break;
+    case OptionEffect::lateralpad:
+        // the lists are made with it: they go, with everything made of them (start table and start cells are rebuilt with them, the
+        // prepared queues were probed against their mip, a counting pass dxv_refit left behind counted the other pad's records)
+        if (slot != (int)value) {
+            if (sync_frames(c) || settle_lists(c)) return 1;
+            drop_prepared(c);
+            c->lists.state = 0; c->specRes = 0;
+            ++c->listEpoch;
+        }
         break;
     default: break;
     }

@@ -13,14 +13,66 @@
 // Identical results need only one property: every triangle that leaf_reference would accept for a
 // ray is listed in that ray's texel with a footprint containing the ray and a radial range that
 // passes.  leaf_reference accepts a triangle when the ray passes the slab test of its box padded by
-// 2^-16 AND the fp32 watertight test: the edge functions of a triangle that is not degenerate only
-// agree in sign within ~1e-6 of it (inputs are differences of coordinates in [-1, 1], rounding
-// ~1e-7), and for a degenerate sliver, whose edge functions all vanish along its line, the padded
-// box keeps the ray within sqrt(3) 2^-16 = 2.64e-5 of it.  Footprints are those of the triangle
-// dilated by kDmDelta = 2^-15 = 3.05e-5, clipped against face frusta widened by 2^-10, and then
-// rounded outward to halfs; triangles closer than 64 kDmDelta to the centre along the face axis
-// take the whole face.  tests/ (fuzz against the oracle, lattice-snapped adversarial meshes) and the GPU
-// soak check the claim the same way they check the padded leaf boxes.
+// 2^-16 AND the fp32 watertight test (tri_test, dxv_math.h).
+//
+// THE WIDE PAD.  For a degenerate sliver, whose edge functions all vanish along its line, only the padded
+// box keeps the ray within sqrt(3) 2^-16 = 2.64e-5 of it: footprints are those of the triangle dilated by
+// kDmDelta = 2^-15 = 3.05e-5 (in face coordinates 2.25 delta / dmin, dm_footprint_finish), clipped against
+// face frusta widened by 2^-10, and then rounded outward to halfs; triangles closer than 64 kDmDelta to
+// the centre along the face axis take the whole face.  Radial margins (+-4 delta), `thick`, the 64 delta
+// rule and the frustum planes are all made with this delta, for every triangle.
+//
+// THE TRIANGLE'S OWN LATERAL BOUND (dm_lateral_pad; option lateralpad).  A whole projected triangle that is
+// not degenerate is held by the watertight test itself, far closer than by its box; sideways -- and only
+// sideways -- its record is dilated by the smaller of the wide pad and the bound below.  u = 2^-24: a rounded
+// fp32 result r is within u |r| of the exact one.  All coordinates lie in [-1, 1].
+//  1  Sheared coordinates.  tri_test computes A = fl(v - o) per axis (|v - o| <= 2: off by <= 2 u each) and
+//     Ax = fma(-Sx, akz, akx) with |Sx| <= 1, |Ax| <= 4: one rounding, <= 4 u, plus the two inherited ones,
+//     2 u + 2 u.  Every sheared coordinate is within E = 8 u of the exact projection of v - o along the
+//     line L' through o with direction D = (Sx, Sy, 1) (in the ray's kx, ky, kz).
+//  2  Size.  An accepted ray has passed the slab test of the padded box; taken as 2^-15 per axis that also
+//     pays for the slab's own roundings (its t values are <= 3.5 where it decides, off by a few u) and for
+//     the slab's line against L'.  So some point of L' lies within diag + 2 sqrt(3) 2^-15 of every vertex
+//     (diag: the diagonal of the triangle's box), and the projection along D stretches by at most
+//     sqrt(1 + Sx^2 + Sy^2) <= sqrt(3): every sheared vertex lies within Dm = sqrt(3) (diag + 2 sqrt(3) 2^-15)
+//     of the ray.
+//  3  Edge functions.  U = fl(fl(Cx By) - fl(Cy Bx)) (no contraction).  Against the exact U^ of the exact
+//     sheared vertices: the coordinates' E through the products, E (|B|_1 + |C|_1) + 2 E^2 <= 2 sqrt(2) E Dm
+//     + 2 E^2; the three roundings, u (|Cx By| + |Cy Bx|) + u |U| <= 2.01 u Dm^2.  An exact zero is evaluated
+//     again in double: exact products, an exact sign -- inside the same bound.
+//  4  The line.  L' is not the radial line: Sx = fl(fl(ox / len) / fl(oz / len)), three roundings of which
+//     `len`'s own cancel, is within 3.01 u of ox / oz, so D = D0 + dD with D0 = o / o_kz and |dD| <= 4.26 u.
+//     U^ is the triple product [D, C - o, B - o]; the share of dD is at most |dD| |C - o| |B - C| <=
+//     4.26 u * 2 sqrt(3) * diag <= 15 u diag.  In all a computed edge function is within
+//         e1 = 2 sqrt(2) E Dm + 2 E^2 + 2.01 u Dm^2 + 15 u diag
+//     of [D0, C - o, B - o] = [D0, C, B] (o is parallel to D0), the edge function of the TRUE radial line.
+//  5  Face coordinates.  With o = |o_a| (u_r, v_r, 1), C = d_C (u_C, v_C, 1), B = d_B (u_B, v_B, 1) on the
+//     ray's face (a: the face axis, d: depths >= dmin >= 64 delta), [D0, C, B] = +- (|o_a| / |o_kz|) d_C d_B
+//     e_CB (u_r, v_r), e_CB the edge function of the PROJECTED triangle, |o_a| / |o_kz| >= 1 (a is o's
+//     largest axis).  tri_test accepts when the three computed signs agree.  All three >= 0 (with the
+//     triangle's orientation): every e_k (u_r, v_r) >= -e1', e1' = e1 / dmin^2.  All three <= 0: every e_k
+//     <= e1', but the three sum to twice the projected area -- impossible once 2 area > 3 e1'.
+//  6  Shape.  e_k >= -e1' puts the ray within e1' / l_k of edge k's line (l_k: its projected length), and
+//     inside the triangle of the three lines so moved, whose corner at the vertex between edges a and b
+//     lies at most (e1' / l_a + e1' / l_b) / sin(angle) = e1' (l_a + l_b) / (2 area) <= 2 e1' / hmin from it,
+//     hmin = 2 area / l_max the projected triangle's smallest altitude (no edge is shorter than hmin).  So
+//         pad = 2 e1 / (dmin^2 hmin)
+//     holds the ray inside every edge pushed out by pad AND inside the box of the projected vertices widened
+//     by pad: what dm_rect, dm_texel_test and dm_local_entry ask.  Beyond the end of a short edge the second
+//     edge function is definitely negative from this distance on.  Shape enters through the PROJECTED
+//     triangle: a well-shaped triangle seen at a grazing angle has a small hmin and gets a large pad or none.
+//     The bound is used where pad < hmin / 2 (then e1' < hmin^2 / 4 <= area / 2: step 5's second case is
+//     excluded).
+//  7  The other roundings, as before: + 1e-6 for the ray's own dm_ray_point / dm_local (u and the cell are
+//     within 2 u of exact), + 1e-6 for the record's fp32 vertices; dm_lateral_pad's own double arithmetic
+//     takes 1 %.
+// The wide pad stays, explicitly, for records without a projected triangle (hasTri 0: a vertex within
+// 64 delta of the face plane), clipped polygons, a box cut to the face, coordinates beyond the unit cube,
+// projections (nearly) edge-on (twice the area <= 1e-3 of the squared edges: the threshold of dm_texel_test
+// and dm_local_radial) and altitudes below 2 pad.  At the headline's scale (triangles of 0.008 at depth 0.6
+// on the 512 map) the lateral band falls from 3.8 cells of a texel's 128 to about 0.5.
+// tests/test_lateral_pad.py casts millions of rays at and around every edge of seeded families of
+// triangles through this very code and finds every accepted ray listed -- and with the pad at zero does not.
 #pragma once
 #include "dxv_trace.h"
 
@@ -53,12 +105,29 @@ constexpr uint32_t kDmCells = 128u;                 // cells per texel side (7 b
 struct alignas(16) DirRecord {
     float u0, u1, v0, v1;      // footprint box in face coordinates, rounded outward; u0 > u1: no footprint
     uint32_t rr;               // radial range of the whole footprint, halfs rounded outward: r0 | r1 << 16
-    uint32_t hasTri;           // bit 0: px / py / pw hold the projected triangle (all three vertices in front of the face plane); bit 1: dm_record_on_map
-    float pad;                 // dilation of the projected triangle in face coordinates
+    uint32_t hasTri;           // bit 0: px / py / pw hold the projected triangle (all three vertices in front of the face plane); bit 1: dm_record_on_map;
+                               // bit 2 (kDmRecLateral): made with the per-record lateral bound, bits 3 .. 31 = the low 29 bits of the 2^-15 pad (dm_wide_pad)
+    float pad;                 // dilation of the projected triangle in face coordinates: the smaller of the 2^-15 pad and the triangle's own bound (dm_lateral_pad)
     float px[3], py[3];        // projected vertices
     float pw[3];               // 1 / depth of the vertices along the face axis: linear over the projected triangle's plane (dm_local_radial)
 };
 static_assert(sizeof(DirRecord) == 64, "record layout");
+constexpr uint32_t kDmRecLateral = 4u;
+struct DirBox { float u0, u1, v0, v1; };
+// the 2^-15 pad of a record (what `pad` was before triangles had a bound of their own): which EDGE an entry stores is still chosen
+// with it, so that an entry made with the smaller pad stores the same edge with a smaller constant -- its cells a subset
+DXV_HD float dm_wide_pad(const DirRecord& r) { return (r.hasTri & kDmRecLateral) ? __builtin_bit_cast(float, 0x20000000u | (r.hasTri >> 3)) : r.pad; }
+// the footprint box of a record: u0 .. v1 are the box of the 2^-15 pad; a record with a bound of its own takes back 99 % of the
+// difference on every side (the last per cent: this subtraction's and the two pads' own rounding, 1e-7 against the 1e-6 both pads carry)
+DXV_HD DirBox dm_record_box(const DirRecord& r)
+{
+    DirBox b{r.u0, r.u1, r.v0, r.v1};
+    if (r.hasTri & kDmRecLateral) {
+        const float s = 0.99f * (dm_wide_pad(r) - r.pad);
+        b.u0 += s; b.u1 -= s; b.v0 += s; b.v1 -= s;
+    }
+    return b;
+}
 
 struct alignas(16) DirCell {                        // one 16-byte load per ray
     uint32_t begin;                                 // the texel's entries: [begin, begin + count)
@@ -502,16 +571,57 @@ DXV_HD float dm_up(float x)
 }
 DXV_HD float dm_down(float x) { return -dm_up(-x); }
 
+// The lateral bound of ONE whole projected triangle (the header's derivation, steps 1 - 6): how far outside an edge line, and how
+// far outside the bounding box of its projected vertices, the direction point of a ray that leaf_reference accepts can lie, in
+// face coordinates.  tri: the triangle in the face's coordinates (b, c, depth), all depths >= dmin >= 64 delta.  Returns 1e30
+// where the derivation does not hold (coordinates beyond the unit cube, a projection that is (nearly) edge-on or degenerate, a
+// smallest projected altitude below twice the bound): the caller keeps the 2^-15 pad there.
+DXV_HD double dm_lateral_pad(const double (*tri)[3], double dmin)
+{
+    const double none = 1e30, u = 5.9604644775390625e-8;                 // (u = 2^-24: a rounded fp32 result is within u of its size)
+    double lo[3], hi[3], big = 0.0;
+    for (int k = 0; k < 3; ++k) { lo[k] = hi[k] = tri[0][k]; }
+    for (int i = 0; i < 3; ++i)
+        for (int k = 0; k < 3; ++k) {
+            const double x = tri[i][k];
+            if (x < lo[k]) lo[k] = x;
+            if (x > hi[k]) hi[k] = x;
+            if (__builtin_fabs(x) > big) big = __builtin_fabs(x);
+        }
+    if (!(big <= 1.0)) return none;                                     // step 1 takes |v - o| <= 2 per axis
+    const double diag = __builtin_sqrt((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) + (hi[2] - lo[2]) * (hi[2] - lo[2]));
+    // step 2: sheared vertices within Dm of the ray (slab test of the box padded by 2^-16, taken as 2^-15 for the slab's own roundings)
+    const double Dm = 1.7321 * (diag + 3.4642 * (double)kDmDelta);
+    // step 1: one sheared coordinate -- two differences of at most 2 each, one fused step of at most 4: the sizes the unit cube allows
+    const double E = 8.0 * u;
+    // steps 3, 4: what a computed edge function can differ by from the exact one of the true radial line
+    const double e1 = 2.8285 * E * Dm + 2.0 * E * E + 2.01 * u * Dm * Dm + 15.0 * u * diag;
+    // step 5: face coordinates
+    double pu[3], pv[3];
+    for (int i = 0; i < 3; ++i) { pu[i] = tri[i][0] / tri[i][2]; pv[i] = tri[i][1] / tri[i][2]; }
+    const double ax = pu[1] - pu[0], ay = pv[1] - pv[0], bx = pu[2] - pu[0], by = pv[2] - pv[0], cx = pu[2] - pu[1], cy = pv[2] - pv[1];
+    const double area2 = __builtin_fabs(ax * by - ay * bx);
+    const double la = ax * ax + ay * ay, lb = bx * bx + by * by, lc = cx * cx + cy * cy;
+    if (!(area2 > 1e-3 * (la + lb)) || !(la + lb > 1e-24)) return none;  // (nearly) edge-on: the threshold of dm_texel_test and dm_local_radial
+    double l2 = la > lb ? la : lb;
+    if (lc > l2) l2 = lc;
+    const double hmin = area2 / __builtin_sqrt(l2);                      // smallest altitude of the projected triangle
+    // step 6: the corner of the pushed-out edges, 1 % for this function's own double arithmetic
+    const double own = 1.01 * 2.0 * e1 / (dmin * dmin * hmin);
+    if (!(own < 0.5 * hmin)) return none;                               // below this altitude all three signs could flip together
+    return own;
+}
+
 // Footprint of triangle tp on one face, or false when it cannot be seen through that face.
 // Builder side only (one call per triangle and face): double precision, nothing canonical here --
 // the result only has to be a superset.
-struct DirFootprint { float u0, u1, v0, v1, r0, r1, pad, px[3], py[3], pw[3]; bool hasTri; };
+struct DirFootprint { float u0, u1, v0, v1, r0, r1, pad, px[3], py[3], pw[3]; bool hasTri; float padWide; bool lateral; };   // (padWide: the 2^-15 pad; lateral: made with option lateralpad on)
 
 // The polygon a face sees of a triangle (its vertices in the face's own coordinates b, c, +-a) -> footprint.  FIXED = 3: the
 // triangle itself, whole inside the face's frustum -- by far the common case; all loops have constant bounds then and the
 // polygon stays in registers (the general case indexes it dynamically: scratch memory on the device).
 template <int FIXED>
-DXV_HD void dm_footprint_finish(const double (*poly)[3], int n, const double (*tri)[3], DirFootprint& out)
+DXV_HD void dm_footprint_finish(const double (*poly)[3], int n, const double (*tri)[3], DirFootprint& out, bool lateral = true)
 {
     const int m = FIXED ? FIXED : n;
     const double delta = (double)kDmDelta;
@@ -524,7 +634,7 @@ DXV_HD void dm_footprint_finish(const double (*poly)[3], int n, const double (*t
     }
     const double full = kDmFrustum + 1.0 / 256.0;
     double u0 = -full, u1 = full, v0 = -full, v1 = full;
-    out.hasTri = false; out.pad = 0.0f;
+    out.hasTri = false; out.pad = 0.0f; out.padWide = 0.0f; out.lateral = lateral;
     for (int i = 0; i < 3; ++i) out.px[i] = out.py[i] = out.pw[i] = 0.0f;
     if (dmin >= 64.0 * delta) {
         u0 = v0 = 1e300; u1 = v1 = -1e300;
@@ -538,8 +648,13 @@ DXV_HD void dm_footprint_finish(const double (*poly)[3], int n, const double (*t
         }
         // a point moved by delta sideways and in depth at depth >= dmin >= 64 delta, |u| <= 1.006:
         // du <= (1 + |u|) delta / (dmin - delta) <= 2.04 delta / dmin
-        const double pad = 2.25 * delta / dmin + 1e-6;
-        u0 -= pad; u1 += pad; v0 -= pad; v1 += pad;
+        const double wide = 2.25 * delta / dmin + 1e-6;
+        // ... and a whole, well-shaped projected triangle is held by its own bound instead (dm_lateral_pad; never the larger).  The box
+        // stays the wide pad's: the record carries both pads and hands out the narrow box (dm_record_box)
+        double pad = wide;
+        if (FIXED == 3 && lateral) { const double own = dm_lateral_pad(tri, dmin) + 1e-6; if (own < pad) pad = own; }
+        u0 -= wide; u1 += wide; v0 -= wide; v1 += wide;
+        const bool cut = u0 < -full || v0 < -full || u1 > full || v1 > full;    // (a box cut to the face has no pad to take back)
         // the projected triangle itself, when all of it lies in front of the face plane: its edges, pushed out by the same
         // pad, bound the footprint too (the part cut off by the frustum's side planes only makes the polygon smaller)
         const double d0 = tri[0][2], d1 = tri[1][2], d2 = tri[2][2];           // (tri: the unclipped triangle in the face's coordinates)
@@ -547,8 +662,11 @@ DXV_HD void dm_footprint_finish(const double (*poly)[3], int n, const double (*t
             const double dd[3] = {d0, d1, d2};
             for (int i = 0; i < 3; ++i) { out.px[i] = (float)(tri[i][0] / dd[i]); out.py[i] = (float)(tri[i][1] / dd[i]); out.pw[i] = (float)(1.0 / dd[i]); }
             out.hasTri = true;
-            out.pad = (float)(pad + 1e-6);                      // (+ the rounding of the stored vertices)
+            out.padWide = (float)(wide + 1e-6);                 // (+ the rounding of the stored vertices)
+            out.pad = cut ? out.padWide : (float)(pad + 1e-6);
+            if (!(out.pad < out.padWide)) { out.pad = out.padWide; out.lateral = false; }
         }
+        else out.lateral = false;
         if (u0 < -full) u0 = -full;
         if (v0 < -full) v0 = -full;
         if (u1 > full) u1 = full;
@@ -615,7 +733,7 @@ DXV_HD void dm_footprint_finish(const double (*poly)[3], int n, const double (*t
 }
 
 
-DXV_HD bool dm_footprint(const TriPos& tp, uint32_t face, DirFootprint& out)
+DXV_HD bool dm_footprint(const TriPos& tp, uint32_t face, DirFootprint& out, bool lateral = true)
 {
     const uint32_t a = face >> 1, b = (a + 1u) % 3u, c = (a + 2u) % 3u;
     const double s = (face & 1u) ? -1.0 : 1.0;
@@ -643,7 +761,7 @@ DXV_HD bool dm_footprint(const TriPos& tp, uint32_t face, DirFootprint& out)
         if (!anyIn) return false;
     }
     if (allIn) {                                                        // nothing to clip: the polygon is the triangle
-        dm_footprint_finish<3>(tri, 3, tri, out);
+        dm_footprint_finish<3>(tri, 3, tri, out, lateral);
         return true;
     }
     double poly[2][10][3];
@@ -668,7 +786,7 @@ DXV_HD bool dm_footprint(const TriPos& tp, uint32_t face, DirFootprint& out)
         n = m;
     }
     if (n == 0) return false;
-    dm_footprint_finish<0>(poly[cur], n, tri, out);
+    dm_footprint_finish<0>(poly[cur], n, tri, out, lateral);
     return true;
 }
 
@@ -679,13 +797,16 @@ DXV_HD DirRecord dm_record(const DirFootprint& f)
     r.u0 = f.u0; r.u1 = f.u1; r.v0 = f.v0; r.v1 = f.v1;
     r.rr = (uint32_t)half_down(f.r0) | ((uint32_t)half_up(f.r1) << 16);
     r.hasTri = f.hasTri ? 1u : 0u; r.pad = f.pad;
+    // (made with the per-record bound: the 2^-15 pad rides along -- a pad is a float in [2^-63, 2): its top three bits are 001)
+    const uint32_t wideBits = __builtin_bit_cast(uint32_t, f.padWide);
+    if (f.hasTri && f.lateral && (wideBits >> 29) == 1u) r.hasTri |= kDmRecLateral | (wideBits << 3);
     for (int i = 0; i < 3; ++i) { r.px[i] = f.px[i]; r.py[i] = f.py[i]; r.pw[i] = f.pw[i]; }
     return r;
 }
-DXV_HD DirRecord dm_record(const TriPos& tp, uint32_t face)
+DXV_HD DirRecord dm_record(const TriPos& tp, uint32_t face, bool lateral = true)
 {
     DirFootprint f;
-    if (!dm_footprint(tp, face, f)) {
+    if (!dm_footprint(tp, face, f, lateral)) {
         DirRecord r;
         r.u0 = 1.0f; r.u1 = 0.0f; r.v0 = 1.0f; r.v1 = 0.0f; r.rr = 0u; r.hasTri = 0u; r.pad = 0.0f;
         for (int i = 0; i < 3; ++i) r.px[i] = r.py[i] = r.pw[i] = 0.0f;
@@ -698,8 +819,9 @@ DXV_HD DirRecord dm_record(const TriPos& tp, uint32_t face)
 DXV_HD bool dm_rect(const DirRecord& e, uint32_t R, uint32_t& i0, uint32_t& i1, uint32_t& j0, uint32_t& j1)
 {
     if (e.u0 > e.u1) return false;
-    if (e.u1 < -1.0f || e.u0 > 1.0f || e.v1 < -1.0f || e.v0 > 1.0f) return false;      // rays only have |u|, |v| <= 1
-    i0 = dm_texel(e.u0, R); i1 = dm_texel(e.u1, R); j0 = dm_texel(e.v0, R); j1 = dm_texel(e.v1, R);
+    const DirBox b = dm_record_box(e);
+    if (b.u1 < -1.0f || b.u0 > 1.0f || b.v1 < -1.0f || b.v0 > 1.0f) return false;      // rays only have |u|, |v| <= 1
+    i0 = dm_texel(b.u0, R); i1 = dm_texel(b.u1, R); j0 = dm_texel(b.v0, R); j1 = dm_texel(b.v1, R);
     return true;
 }
 
@@ -728,7 +850,10 @@ DXV_HD DirTexelTest dm_texel_test(const DirRecord& rec, uint32_t texels)
     DirTexelTest t;
     t.on = false;
     for (int k = 0; k < 3; ++k) { t.nx[k] = 0.0f; t.ny[k] = 0.0f; t.c[k] = 0.0f; }
-    if (!(rec.hasTri & 1u) || texels < 4u || texels > kDmTexelTestMax) return t;   // (a strip of two or three texels is touched in all of them)
+    // (a strip of two or three texels is touched in all of them -- by the 2^-15 pad.  A record with a bound of its own is tested whatever
+    // its rectangle: the smaller pad's rectangle is the smaller one, and a test that came on with the area would let the wide pad
+    // drop a texel the narrow pad keeps)
+    if (!(rec.hasTri & 1u) || texels < ((rec.hasTri & kDmRecLateral) ? 1u : 4u) || texels > kDmTexelTestMax) return t;
     const float ax = rec.px[1] - rec.px[0], ay = rec.py[1] - rec.py[0], bx = rec.px[2] - rec.px[0], by = rec.py[2] - rec.py[0];
     const float area2 = ax * by - ay * bx;
     const float scale = (ax * ax + ay * ay) + (bx * bx + by * by);
@@ -788,10 +913,11 @@ DXV_HD void dm_local_radial(const DirRecord& rec, uint32_t R, uint32_t i, uint32
     const float eps = rec.pad + 4e-6f;
     float ua = 2.0f * (float)i / (float)R - 1.0f, ub = 2.0f * (float)(i + 1u) / (float)R - 1.0f;
     float va = 2.0f * (float)j / (float)R - 1.0f, vb = 2.0f * (float)(j + 1u) / (float)R - 1.0f;
-    if (rec.u0 > ua) ua = rec.u0;
-    if (rec.u1 < ub) ub = rec.u1;
-    if (rec.v0 > va) va = rec.v0;
-    if (rec.v1 < vb) vb = rec.v1;
+    const DirBox box = dm_record_box(rec);
+    if (box.u0 > ua) ua = box.u0;
+    if (box.u1 < ub) ub = box.u1;
+    if (box.v0 > va) va = box.v0;
+    if (box.v1 < vb) vb = box.v1;
     ua -= eps; ub += eps; va -= eps; vb += eps;
     if (!(ua <= ub && va <= vb)) return;
     const float w0 = w00 + gu * ua + gv * va, w1 = w00 + gu * ub + gv * va, w2 = w00 + gu * ua + gv * vb, w3 = w00 + gu * ub + gv * vb;
@@ -842,10 +968,20 @@ DXV_HD DirEntry dm_local_entry(const DirRecord& rec, uint32_t R, uint32_t i, uin
     dm_local_radial(rec, R, i, j, r0h, r1h);
     e.rr = ((0x7fffu - r0h) | (r1h << 16)) | 0x80008000u;
     uint32_t t0, c0, t1, c1, x0, x1, y0, y1;
-    dm_local(rec.u0, R, t0, c0); dm_local(rec.u1, R, t1, c1);
+    const DirBox box = dm_record_box(rec);
+    dm_local(box.u0, R, t0, c0); dm_local(box.u1, R, t1, c1);
     x0 = t0 < i ? 0u : c0; x1 = t1 > i ? kDmCells - 1u : c1;
-    dm_local(rec.v0, R, t0, c0); dm_local(rec.v1, R, t1, c1);
+    dm_local(box.v0, R, t0, c0); dm_local(box.v1, R, t1, c1);
     y0 = t0 < j ? 0u : c0; y1 = t1 > j ? kDmCells - 1u : c1;
+    // (the 2^-15 pad and its box cut to the texel: what the choice of the edge below goes by -- the record's own where it has no other)
+    const double wide = (double)dm_wide_pad(rec);
+    uint32_t wx0 = x0, wx1 = x1, wy0 = y0, wy1 = y1;
+    if (rec.hasTri & kDmRecLateral) {
+        dm_local(rec.u0, R, t0, c0); dm_local(rec.u1, R, t1, c1);
+        wx0 = t0 < i ? 0u : c0; wx1 = t1 > i ? kDmCells - 1u : c1;
+        dm_local(rec.v0, R, t0, c0); dm_local(rec.v1, R, t1, c1);
+        wy0 = t0 < j ? 0u : c0; wy1 = t1 > j ? kDmCells - 1u : c1;
+    }
     e.box = x0 | (y0 << 8) | ((kDmCells - 1u - x1) << 16) | ((kDmCells - 1u - y1) << 24);
     e.edge = 0u;
     if (!(rec.hasTri & 1u)) return e;
@@ -863,26 +999,28 @@ DXV_HD DirEntry dm_local_entry(const DirRecord& rec, uint32_t R, uint32_t i, uin
         const double rl = (double)(1.0f / __builtin_sqrtf((float)len2)) * sgn;
         const double nx = -ey * rl, ny = ex * rl;
         const double A = nx * perCell, B = ny * perCell;
-        const double C = (ou - rec.px[k]) * nx + (ov - rec.py[k]) * ny + rec.pad;
+        const double C0 = (ou - rec.px[k]) * nx + (ov - rec.py[k]) * ny, C = C0 + rec.pad, Cwide = C0 + wide;
         const double big = __builtin_fabs(A) > __builtin_fabs(B) ? __builtin_fabs(A) : __builtin_fabs(B);
         const double sc = (double)(127.0f / (float)big);                // (one scale for A, B and C: its last bits do not matter)
         const double ka = A * sc, kb = B * sc;
         const int a = (int)__builtin_floor(ka + 0.5), b = (int)__builtin_floor(kb + 0.5);
         double cd = __builtin_ceil(C * sc + 64.0 * (ka + kb) + __builtin_fabs(ka) + __builtin_fabs(kb) + 64.0 + 13.0);
-        if (!(cd < 16256.0)) continue;                                   // this edge cuts nothing off the texel
+        const double cdWide = __builtin_ceil(Cwide * sc + 64.0 * (ka + kb) + __builtin_fabs(ka) + __builtin_fabs(kb) + 64.0 + 13.0);
+        if (!(cdWide < 16256.0)) continue;                               // this edge cuts nothing off the texel
         if (cd < -16256.0) cd = -16256.0;                               // (never stricter: safe)
-        const int c = (int)cd;
+        const int c = (int)cd, cw = (int)(cdWide < -16256.0 ? -16256.0 : cdWide);
         const int c1b = c / 127, c2b = c - 127 * c1b;                   // truncation: |c2b| < 127
         // how much of the box does it remove?  Nothing when the box's corner farthest outside is still inside; else 3 x 3 samples
-        // (cells from the centre, as the ray brings them)
-        const int half = (int)(kDmCells / 2u);
-        const int worst = a * ((int)(a < 0 ? x1 : x0) - half) + b * ((int)(b < 0 ? y1 : y0) - half) + c;
+        // (cells from the centre, as the ray brings them).  Asked of the constant of the 2^-15 pad and of that pad's box: the edge stored
+        // is the same whichever pad the record was made with (dm_wide_pad)
+        const int half = (int)kDmCells / 2;
+        const int worst = a * ((int)(a < 0 ? wx1 : wx0) - half) + b * ((int)(b < 0 ? wy1 : wy0) - half) + cw;
         if (worst >= 0) continue;
         int cut = 1;
         for (int sy = 0; sy < 3; ++sy)
             for (int sx = 0; sx < 3; ++sx) {
-                const int x = (int)x0 + (int)((x1 - x0) * (2 * sx + 1) / 6) - half, y = (int)y0 + (int)((y1 - y0) * (2 * sy + 1) / 6) - half;
-                if (a * x + b * y + c < 0) ++cut;
+                const int x = (int)wx0 + (int)((wx1 - wx0) * (2 * sx + 1) / 6) - half, y = (int)wy0 + (int)((wy1 - wy0) * (2 * sy + 1) / 6) - half;
+                if (a * x + b * y + cw < 0) ++cut;
             }
         if (cut > bestCut) {
             bestCut = cut;

@@ -118,7 +118,7 @@ static int build_lists_into(dxv_ctx* c, Lists& l, hipStream_t stream, uint64_t f
     unsigned long long total = 0;
     auto recount = [&](uint32_t res, uint32_t stride = 1u) -> int {
         R = res;
-        if ((e = dirmap_count(scene_tripos(c), T, R, rec, counts, sa.pairs, offsets, dTotal, stream, stride)) != hipSuccess) return bail(e, "dirmap_count");
+        if ((e = dirmap_count(scene_tripos(c), T, R, rec, counts, sa.pairs, offsets, dTotal, c->opt.lateralpad != 0, stream, stride)) != hipSuccess) return bail(e, "dirmap_count");
         (void)hipEventRecord(c->evList[1], stream);
         if ((e = hipMemcpyAsync(&c->pin->listTotal, dTotal, sizeof(total), hipMemcpyDeviceToHost, stream)) != hipSuccess) return bail(e, "hipMemcpyAsync");
         if ((e = hipStreamSynchronize(stream)) != hipSuccess) return bail(e, "hipStreamSynchronize");

@@ -181,6 +181,8 @@ struct Options {
     int listedwaves = 0;     // workgroups per CU of the hardware-dispatched lists kernel (8 .. 32), or 0 = by grid and map (voxelize_lists.hip: listed_lds_pad)
     int starttable = 2;      // the lists' per-texel start table (dxv_dirmap.h: dm_start_word): 0 = scans begin where the start search ends, 1 = no earlier
                              // than the table's start for the ray, 2 = automatic (default: where it pays -- start_table_pays)
+    int lateralpad = 1;      // the lists' lateral dilation (dxv_dirmap.h: dm_lateral_pad): 1 = every whole, well-shaped projected triangle by its own bound, 0 = all by 2^-15.
+                             // Read by the list build; a change drops lists, start table, start cells and prepared queues.  Same grids.
     int coop = 1;            // 1: the lists kernel scans a lone lane's long list with its whole wave (dxv_dirmap.h: trace_reference_dm_from)
     int farmap = 1;          // 1: tree walks and brick-box launches of the reference rule skip the bricks none of whose rays can reach a triangle
     int plan = 2;            // work queue of the lists kernel (live bricks only, built on the device inside the stream): 0 = none (brick box
@@ -235,7 +237,7 @@ constexpr OptionRule kOnOff = in_range(0, 1);
 constexpr OptionRule kSortBits = {OptionRule::sortbits, false, 0, 63, {}};    // 0 or 8..11 bits per digit, + 16 / + 32 / + 48
 
 // what dxv_set_option does for a key beyond checking and storing its value
-enum class OptionEffect { none, brick, wide, listres, plistres, stack0, sortbits, ablate };
+enum class OptionEffect { none, brick, wide, listres, plistres, stack0, sortbits, ablate, lateralpad };
 struct OptionRow { const char* name; OptionRule rule; const char* refusal; int Options::*where; OptionEffect effect; };
 
 // (stack, stack0: the column depths the brick kernels are compiled for -- stack_round_up, traverse.hip)
@@ -280,6 +282,7 @@ constexpr int kOptionCount = (int)(sizeof(kOptions) / sizeof(kOptions[0]));
 // since -- the start table of the lists, the passes over a frame's finished grid -- are rows of the same kind in a table of their own.
 constexpr OptionRow kLaterOptions[] = {
     {"starttable", in_range(0, 2), "not in {0,1,2}", &Options::starttable, OptionEffect::none},
+    {"lateralpad", kOnOff, "not in {0,1}", &Options::lateralpad, OptionEffect::lateralpad},
     {"fillrounds", in_range(0, 64), "not in [0, 64]", &Options::fillrounds, OptionEffect::none},
     {"mdistwalk", kOnOff, "not in {0,1}", &Options::mdistwalk, OptionEffect::none},
     {"morphform", in_range(0, 2), "not in {0,1,2}", &Options::morphform, OptionEffect::none},

@@ -1190,6 +1190,10 @@ DXV_API int dxv_get_stats(const dxv_ctx* ctx, dxv_stats* out);
  *                 non-empty texels hold more than 8 entries (the word is one more load per ray: it pays where it removes whole scan
  *                 rounds from most waves), else 0, and 0 for a launch queued behind a list build nobody has waited for yet.  A launch
  *                 that reads the table runs brick kernels compiled with it, any other the kernels without.  Same grids either way
+ *   lateralpad 0|1  the lists' builder: how far a projected triangle is dilated sideways before its texels and cells are listed.  1 (default):
+ *                 a whole, well-shaped projected triangle by the bound derived from the triangle test's own rounding (dxv_dirmap.h:
+ *                 dm_lateral_pad), everything else by 2^-15; 0: everything by 2^-15.  Read by the next list build: a change drops the
+ *                 lists, their start table and start cells and the prepared queues.  Not part of an exported scene.  Same grids either way
  *   listedwaves 0|8..32 the hardware-dispatched lists kernel (prepared and kept queues, no texel image) fits eight waves per SIMD: 32
  *                 single-wave workgroups per CU.  0 (default): all 32 when the grid side is at least 3/4 of the lists' map side (a brick's rays
  *                 fall on neighbouring texels: 512^3 -9 %, 1024^3 -12 % against seven waves), else 28 (256^3 on the 512 map: a brick is spread
