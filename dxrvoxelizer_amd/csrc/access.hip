@@ -19,7 +19,8 @@
 // exceeds A (each is a real path's), and at a fixed point none is below it (induction along a best path).  Of the voxels whose word is not
 // final yet, the one with the highest A whose path predecessor is final becomes final in the next round that runs its tile -- and that tile is
 // flagged, by the round that made the predecessor final or by the seeds --, so V live rounds bound the call.
-// No workgroup waits for another, every loop is bounded, launch sizes depend on N alone; no scratch memory.
+// No workgroup waits for another, every loop is bounded, launch sizes depend on N alone; no scratch memory.  The flood's blocks and, behind them,
+// the field's or the whole thickness's are laid out by access_carve (dxv_access.h).
 #include "dxv_device.h"
 #include "dxv_access.h"
 
@@ -27,37 +28,6 @@ namespace dxv {
 
 constexpr uint32_t kAccRoundBlocks = 8192;        // workgroups (of one wave) a round is launched with at the most, whatever its queue holds
 constexpr uint32_t kAccTallyBlocks = 1024;        // ... the tally, of four waves
-
-static uint32_t acc_tiles(uint32_t N) { return geo_tiles_side(N) * geo_tiles_side(N) * geo_tiles_side(N); }
-
-struct AccLayout { GeoControl* ctl; unsigned long long* seedsUsed; uint8_t* flags[2]; uint32_t* queue; uint8_t* rest; };
-static size_t acc_front_bytes(uint32_t N) { return align256(sizeof(GeoControl)) + 256u + 2u * align256(acc_tiles(N)) + align256((size_t)acc_tiles(N) * sizeof(uint32_t)); }
-static AccLayout acc_layout(uint8_t* scratch, uint32_t N)
-{
-    const size_t flags = align256(acc_tiles(N));
-    AccLayout l;
-    l.ctl = reinterpret_cast<GeoControl*>(scratch);
-    l.seedsUsed = reinterpret_cast<unsigned long long*>(scratch + align256(sizeof(GeoControl)));
-    l.flags[0] = scratch + align256(sizeof(GeoControl)) + 256u;
-    l.flags[1] = l.flags[0] + flags;
-    l.queue = reinterpret_cast<uint32_t*>(l.flags[1] + flags);
-    l.rest = scratch + acc_front_bytes(N);
-    return l;
-}
-size_t access_scratch_bytes(uint32_t N, bool intrusion)
-{
-    const size_t voxels = (size_t)N * N * N;
-    return acc_front_bytes(N) + (intrusion ? thickness_scratch_bytes(N) : align256(voxels * sizeof(int32_t)) + distance_scratch_bytes(N));
-}
-void access_layout(uint8_t* scratch, uint32_t N, bool intrusion, ThickParams& p)
-{
-    uint8_t* rest = acc_layout(scratch, N).rest;
-    if (intrusion) { thickness_layout(rest, N, p); return; }
-    p.N = N;
-    p.F = reinterpret_cast<int32_t*>(rest);
-    p.passes = rest + align256((size_t)N * N * N * sizeof(int32_t));
-    p.G = nullptr; p.B = nullptr; p.sums = nullptr; p.centres = nullptr; p.firstItem = nullptr;
-}
 
 // one thread per voxel; a wave counts its seeds with one atomic
 __global__ __launch_bounds__(256) void k_acc_init(const int32_t* __restrict__ F, uint32_t N, int of, uint32_t cap, int seedsKind, const uint8_t* __restrict__ seedMask,
@@ -184,19 +154,16 @@ __global__ __launch_bounds__(256) void k_acc_radius(const uint32_t* __restrict__
     reinterpret_cast<int4*>(F)[t] = make_int4(acc_radius_word(a.x, of), acc_radius_word(a.y, of), acc_radius_word(a.z, of), acc_radius_word(a.w, of));
 }
 
-hipError_t launch_access_init(const uint8_t* grid, uint32_t N, int of, uint32_t cap, int seedsKind, const void* seeds, uint32_t seedCount, uint32_t* A, uint8_t* scratch, bool intrusion,
-                              hipStream_t s)
+hipError_t launch_access_init(const uint8_t* grid, uint32_t N, int of, uint32_t cap, int seedsKind, const void* seeds, uint32_t seedCount, uint32_t* A, const AccScratch& l, hipStream_t s)
 {
-    if (!grid || !A || !scratch || !acc_valid(N, of, 6, cap) || seedsKind < GEO_SEEDS_BORDER || seedsKind > GEO_SEEDS_MASK ||
+    if (!grid || !A || !l.seedsUsed || !l.flags[0] || !l.thick.F || !l.thick.passes || !acc_valid(N, of, 6, cap) || seedsKind < GEO_SEEDS_BORDER || seedsKind > GEO_SEEDS_MASK ||
         (seedsKind != GEO_SEEDS_BORDER && !seeds && (seedsKind == GEO_SEEDS_MASK || seedCount)))
         return hipErrorInvalidValue;
-    const AccLayout l = acc_layout(scratch, N);
-    ThickParams p{};
-    access_layout(scratch, N, intrusion, p);
+    const ThickParams& p = l.thick;
     const size_t voxels = (size_t)N * N * N;
     hipError_t e = launch_distance(grid, N, 0, p.F, p.passes, s);
     if (e != hipSuccess) return e;
-    if ((e = hipMemsetAsync(l.seedsUsed, 0, 256u + 2u * align256(acc_tiles(N)), s)) != hipSuccess) return e;     // (the seeds' word and both sets of flags)
+    if ((e = hipMemsetAsync(l.seedsUsed, 0, l.clearBytes, s)) != hipSuccess) return e;     // (the seeds' word and both sets of flags)
     k_acc_init<<<(uint32_t)((voxels + 255u) / 256u), 256, 0, s>>>(p.F, N, of, cap, seedsKind, seedsKind == GEO_SEEDS_MASK ? static_cast<const uint8_t*>(seeds) : nullptr, A, l.flags[0],
                                                                   l.seedsUsed);
     if (seedsKind == GEO_SEEDS_LIST && seedCount)
@@ -206,13 +173,11 @@ hipError_t launch_access_init(const uint8_t* grid, uint32_t N, int of, uint32_t 
 
 // One batch: `rounds` rounds, the first of them round `base` of the call (the flags a round reads are those of its number's parity), then the
 // tally.  Control block and tally are cleared in front of the rounds.
-hipError_t launch_access_batch(uint32_t* A, uint32_t N, int of, int connectivity, uint32_t cap, uint8_t* scratch, bool intrusion, uint32_t rounds, uint32_t base, hipStream_t s)
+hipError_t launch_access_batch(uint32_t* A, uint32_t N, int of, int connectivity, uint32_t cap, const AccScratch& l, uint32_t rounds, uint32_t base, hipStream_t s)
 {
-    if (!A || !scratch || !acc_valid(N, of, connectivity, cap)) return hipErrorInvalidValue;
-    const AccLayout l = acc_layout(scratch, N);
-    ThickParams p{};
-    access_layout(scratch, N, intrusion, p);
-    const uint32_t tiles = acc_tiles(N), voxels = N * N * N;
+    if (!A || !l.ctl || !l.flags[0] || !l.flags[1] || !l.queue || !l.thick.F || !acc_valid(N, of, connectivity, cap)) return hipErrorInvalidValue;
+    const ThickParams& p = l.thick;
+    const uint32_t tiles = geo_tiles(N), voxels = N * N * N;
     if (rounds < 1u) rounds = 1u;
     if (rounds > kAccMaxRounds) rounds = kAccMaxRounds;
     hipError_t e = hipMemsetAsync(l.ctl, 0, sizeof(GeoControl), s);
@@ -230,13 +195,11 @@ hipError_t launch_access_batch(uint32_t* A, uint32_t N, int of, int connectivity
     return hipGetLastError();
 }
 
-hipError_t launch_access_radius(const uint32_t* A, uint32_t N, int of, uint8_t* scratch, bool intrusion, hipStream_t s)
+hipError_t launch_access_radius(const uint32_t* A, uint32_t N, int of, const AccScratch& l, hipStream_t s)
 {
-    if (!A || !scratch || !acc_valid(N, of, 6, kThickMinCapSq)) return hipErrorInvalidValue;
-    ThickParams p{};
-    access_layout(scratch, N, intrusion, p);
+    if (!A || !l.thick.F || !acc_valid(N, of, 6, kThickMinCapSq)) return hipErrorInvalidValue;
     const uint32_t groups = N * N * N / 4u;
-    k_acc_radius<<<(groups + 255u) / 256u, 256, 0, s>>>(A, groups, of, p.F);
+    k_acc_radius<<<(groups + 255u) / 256u, 256, 0, s>>>(A, groups, of, l.thick.F);
     return hipGetLastError();
 }
 

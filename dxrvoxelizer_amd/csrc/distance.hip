@@ -5,7 +5,8 @@
 //   k_dist_columns  along z: 32-bit -> the field (4 B read, 4 B written)
 // A column scan is one lane per column, adjacent lanes on adjacent x: every lane of a wave is at the same u, so the loads of the input
 // and the stores of the result are whole 256-byte (128-byte for the 16-bit input) wave accesses; only the stack's slots, a + q per
-// lane, spread -- over neighbouring lines of the same x range.  No LDS in the column scans, no scratch memory.
+// lane, spread -- over neighbouring lines of the same x range.  No LDS in the column scans, no scratch memory.  The two intermediate fields are
+// laid out by distance_carve (dxv_distance.h).
 #include "dxv_device.h"
 #include "dxv_distance.h"
 
@@ -44,13 +45,14 @@ __global__ __launch_bounds__(64) void k_dist_columns(const TIn* __restrict__ in,
     col.run();
 }
 
-size_t distance_rows_bytes(uint32_t N) { return align256((size_t)N * N * N * sizeof(int16_t)); }
-size_t distance_scratch_bytes(uint32_t N) { return distance_rows_bytes(N) + (size_t)N * N * N * sizeof(int32_t); }
-
+// scratch: distance_scratch_bytes(N) bytes (dxv_distance.h: distance_carve), which whoever embeds them has taken from its own carve
 hipError_t launch_distance(const uint8_t* grid, uint32_t N, int format, void* field, uint8_t* scratch, hipStream_t s)
 {
-    int16_t* rows = reinterpret_cast<int16_t*>(scratch);
-    int32_t* squares = reinterpret_cast<int32_t*>(scratch + distance_rows_bytes(N));
+    Carve c(scratch, distance_scratch_bytes(N));
+    DistScratch l;
+    distance_carve(c, N, l);
+    int16_t* rows = l.rows;
+    int32_t* squares = l.squares;
     const size_t n2 = (size_t)N * N;
     const uint32_t columns = (uint32_t)((n2 + 63) / 64);
     k_dist_rows<<<(uint32_t)(n2 / kDistRowWaves), 64 * kDistRowWaves, 0, s>>>(grid, N, rows);

@@ -97,4 +97,24 @@ DXV_HD void acc_tally_combine(AccTally& a, const AccTally& b)
 DXV_HD uint32_t acc_tally_widest(const AccTally& t) { return (uint32_t)(t.key >> 32); }
 DXV_HD uint32_t acc_tally_widest_voxel(const AccTally& t) { return 0xFFFFFFFFu - (uint32_t)(t.key & 0xFFFFFFFFu); }
 
+// ---- scratch of one call: a control block, live flags and a queue of the geodesic's shape with the word the seeds are counted in between them
+// (clearBytes: that word and both sets of flags, cleared together), and behind them the radius field F with the scratch of its passes -- with
+// `intrusion` the whole of a thickness's scratch, which begins with F.  thick: N, F and passes always; the rest with `intrusion`. ----
+struct AccScratch { GeoControl* ctl; unsigned long long* seedsUsed; uint8_t* flags[2]; size_t clearBytes; uint32_t* queue; ThickParams thick; };
+inline void access_carve(Carve& c, uint32_t N, bool intrusion, AccScratch& l)
+{
+    l.ctl = c.take<GeoControl>(1);
+    const size_t from = c.used();
+    l.seedsUsed = reinterpret_cast<unsigned long long*>(c.take_bytes(256u));
+    l.flags[0] = c.take<uint8_t>(geo_tiles(N));
+    l.flags[1] = c.take<uint8_t>(geo_tiles(N));
+    l.clearBytes = c.used() - from;
+    l.queue = c.take<uint32_t>(geo_tiles(N));
+    if (intrusion) { thickness_carve(c, N, l.thick); return; }
+    l.thick.N = N;
+    l.thick.F = c.take<int32_t>((size_t)N * N * N);
+    l.thick.passes = c.take_bytes(distance_scratch_bytes(N));
+}
+inline size_t access_scratch_bytes(uint32_t N, bool intrusion) { return carved_bytes<AccScratch>(access_carve, N, intrusion); }
+
 } // namespace dxv

@@ -45,7 +45,7 @@ struct CompRecord {
 static_assert(sizeof(CompRecord) == 24, "the table's record is 24 bytes");
 
 // what the stats pass gathers per component with 32-bit integer atomics before the table is packed
-struct CompStats { uint32_t voxels, lo[3], hi[3], flags; };
+using CompStats = BoxStats;
 
 DXV_HD uint32_t comp_ctz(uint64_t v)              // v != 0
 {
@@ -213,5 +213,43 @@ DXV_HD bool comp_keep(int rule, uint32_t arg, uint32_t number, uint32_t voxels, 
     if (rule == COMP_SELECT_MIN_VOXELS) return voxels >= arg;
     return (flags & 1u) != 0u;
 }
+
+// ---- what components.hip's launches work on: labels = N^3 uint32 and table = 24 K bytes are the caller's, stats = K CompStats of work ----
+struct CompParams {
+    const uint8_t* grid;    // N^3 bytes, element (iz * N + iy) * N + ix; a voxel is solid iff its byte is non-zero
+    uint32_t N;
+    int of;                 // DXV_COMP_SOLID / DXV_COMP_EMPTY
+    uint32_t connectivity;  // 6 / 26
+    uint32_t* labels;       // parent during the build, then the labels
+    uint64_t* mask;         // comp_carve fills these five
+    uint64_t* rootMask;
+    uint32_t* bases;
+    unsigned long long* sums;
+    unsigned long long* total;    // K
+    CompStats* stats;
+    CompRecord* table;
+};
+inline size_t comp_linear_words(uint32_t N) { return ((size_t)N * N * N + 63u) / 64u; }
+// scratch of one build: the member mask, the root bits and the roots in front of every 64 voxels, the scan's block sums, the total
+inline void comp_carve(Carve& c, uint32_t N, CompParams& p)
+{
+    const size_t words = comp_linear_words(N);
+    p.N = N;
+    p.mask = c.take<uint64_t>(fill_mask_words(N));
+    p.rootMask = c.take<uint64_t>(words);
+    p.bases = c.take<uint32_t>(words);
+    p.sums = c.take<unsigned long long>(scan_blocks(words));
+    p.total = c.take<unsigned long long>(1);
+}
+inline size_t comp_scratch_bytes(uint32_t N) { return carved_bytes<CompParams>(comp_carve, N); }
+
+// work of dxv_components_select: {kept, dropped, voxels changed, the maximum of comp_best_key}, then K keep flags
+struct CompSelectWork { unsigned long long* counters; uint8_t* keep; };
+inline void comp_select_carve(Carve& c, uint32_t K, CompSelectWork& w)
+{
+    w.counters = c.take<unsigned long long>(4);
+    w.keep = c.take<uint8_t>(K);
+}
+inline size_t comp_select_bytes(uint32_t K) { return carved_bytes<CompSelectWork>(comp_select_carve, K); }
 
 } // namespace dxv

@@ -8,6 +8,8 @@
 #include "dxv_raycast.h"
 #include "dxv_dirmap.h"
 #include "dxv_policy.h"
+#include "dxv_geodesic.h"       // GeoControl and ThinControl, which the page-locked words of a frame hold whole
+#include "dxv_thin.h"
 
 #include <cmath>
 #include <cstdarg>

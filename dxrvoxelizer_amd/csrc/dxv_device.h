@@ -4,11 +4,13 @@
 #include <stdint.h>
 #include "dxv_types.h"
 #include "dxv_trace.h"
+#include "dxv_scratch.h"
 
 namespace dxv {
 
-// device allocations and the blocks inside one are laid out in whole 256-byte lines
-inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
+// The grid operators (distance.hip .. partition.hip below) describe their scratch memory ONCE, in the carve function beside their params in
+// their rule header (dxv_scratch.h has the Carve; dxv_distance.h, dxv_fill.h, ... the functions): X_scratch_bytes is that function over a null
+// base, the layout the same function over the allocation.  Here stand the launches alone.
 
 // radix_sort.hip
 // plan: the diagnostic override (option sortbits) as ONE caller snapshot of radix_sort_plan(), -1: read it now
@@ -16,7 +18,6 @@ hipError_t radix_sort_keys_bits(uint64_t* keys, uint64_t* tmp, uint32_t n, uint3
                                 hipStream_t s, int plan = -1);
 int radix_sort_passes(uint32_t n, int numBits, int plan = -1);     // how many times that sort swaps keys and tmp
 int radix_sort_plan();                              // the process-wide override as it stands (a build asks once)
-uint32_t radix_sort_hist_words(uint32_t n);
 void radix_sort_set_plan(int v);                    // diagnostic (option sortbits)
 
 // lbvh.hip -- device-side build of the scene blob.
@@ -207,17 +208,15 @@ size_t surface_scratch_bytes(uint32_t T);
 hipError_t launch_surface(const SurfaceParams& p, hipStream_t s);
 
 // distance.hip -- the exact signed distance field of a whole N^3 grid (dxv_distance.h): format 0 = int32 s * d2, 1 = float32 s * sqrt(d2);
-// field: 4 * N^3 bytes, scratch: distance_scratch_bytes(N); grid, field and scratch are three different allocations
-size_t distance_scratch_bytes(uint32_t N);
+// field: 4 * N^3 bytes, scratch: distance_scratch_bytes(N) (dxv_distance.h); grid, field and scratch are three different allocations
 hipError_t launch_distance(const uint8_t* grid, uint32_t N, int format, void* field, uint8_t* scratch, hipStream_t s);
 
 // fill.hip -- the exterior flood fill of a whole N^3 grid (dxv_fill.h), in place: one batch = (first: the grid packed into the free and
 // reached masks,) `rounds` rounds (1 .. kFillMaxRounds), the write-back of what = 0 (walls and what they enclose) or 1 (the enclosed voxels
-// alone).  scratch: fill_scratch_bytes(N), the two masks and the batch's control block -- word k != 0: round k changed something; the
+// alone).  scratch: fill_carve (dxv_fill.h), the two masks and the batch's control block -- word k != 0: round k changed something; the
 // batch has converged exactly when the word of its last round is 0.  A batch with first = false goes on from the masks of the one before.
-size_t fill_scratch_bytes(uint32_t N);
-uint32_t* fill_control(uint8_t* scratch, uint32_t N);
-hipError_t launch_fill(uint8_t* grid, uint32_t N, int what, uint8_t* scratch, uint32_t rounds, bool first, hipStream_t s);
+struct FillScratch;
+hipError_t launch_fill(uint8_t* grid, uint32_t N, int what, const FillScratch& scratch, uint32_t rounds, bool first, hipStream_t s);
 
 // mesh_distance.hip -- the exact distance from the voxel centres of slices [z0, z0 + nz) of an N^3 grid to the mesh, signed by the grid's
 // bytes (dxv_mesh_distance.h): walk = the nearest-triangle query over the two-box nodes (a tree no higher than kMdStack), else every
@@ -234,84 +233,38 @@ struct MeshDistanceParams {
 hipError_t launch_mesh_distance(const Node* nodes, const TriPos* triPos, uint32_t T, const MeshDistanceParams& p, bool walk, hipStream_t s);
 
 // scan.hip -- the exclusive scan of the grid operators (dxv_scan.h has the workgroup's routine).  launch_scan_words: `words` words of C (1 or 2)
-// interleaved 32-bit counts each become what stands in front of them, in place; sums: C * scan_blocks(words) 64-bit words of scratch; totals: C
+// interleaved 32-bit counts each become what stands in front of them, in place; sums: C * scan_blocks(words) (dxv_scratch.h) 64-bit words of scratch; totals: C
 // 64-bit words.  launch_scan_sums: the same for `blocks` entries of C 64-bit sums, by one workgroup; totals may stand right behind them.  Both
 // refuse a null pointer, a C that is neither 1 nor 2, and nothing to scan.
-uint32_t scan_blocks(size_t words);
 hipError_t launch_scan_words(uint32_t* counts, uint32_t C, size_t words, unsigned long long* sums, unsigned long long* totals, hipStream_t s);
 hipError_t launch_scan_sums(unsigned long long* sums, uint32_t C, uint32_t blocks, unsigned long long* totals, hipStream_t s);
 
 // isosurface.hip -- a triangle mesh from a float32 field of a whole N^3 grid by naive Surface Nets (dxv_isosurface.h): count + scan, ONE
-// read of the two totals by the caller, emit.  scratch: iso_scratch_bytes(N) -- one bit per lattice cell, two counts per 64 cells, the
-// scan's block sums, the totals.  vb: 24 bytes per vertex, ib: three uint32 per triangle, two triangles per quad.
-struct IsoVertex;
-struct IsoCounts;
-struct IsoParams {
-    const float* field;     // N^3 floats, element (iz * N + iy) * N + ix
-    uint32_t N;
-    float iso, P;           // the level, and one voxel in the field's unit: what a sample outside the grid is worth
-    int object;             // 0: vertices in voxel index space, 1: in object space through `bound` (triangles turned round: y is mirrored)
-    float bound[4];
-    uint64_t* masks;        // iso_scratch_layout fills these four
-    IsoCounts* bases;
-    unsigned long long* sums;
-    unsigned long long* totals;   // {vertices, quads} of the whole mesh
-    IsoVertex* vb;
-    uint32_t* ib;
-};
-size_t iso_scratch_bytes(uint32_t N);
-void iso_scratch_layout(uint8_t* scratch, uint32_t N, IsoParams& p);
+// read of the two totals by the caller, emit.  scratch: iso_carve (dxv_isosurface.h).  vb: 24 bytes per vertex, ib: three uint32 per triangle, two
+// triangles per quad.
+struct IsoParams;
 hipError_t launch_iso_count(const IsoParams& p, hipStream_t s);
 hipError_t launch_iso_emit(const IsoParams& p, hipStream_t s);
 
 // octree.hip -- the sparse voxel octree of a whole N^3 grid (dxv_octree.h): reduce + scan, ONE read of the L + 1 level totals by the caller,
-// emit; and the way back, a grid from a tree.  scratch: oct_scratch_bytes(N) -- 2 bytes per cell of levels 0 .. L - 1, one bit per cell, one
-// count per 64 cells, the scan's block sums, level_first.  nodes: 8 bytes each.
-struct OctParams {
-    const uint8_t* grid;    // N^3 bytes, element (iz * N + iy) * N + ix; a voxel is solid iff its byte is non-zero
-    uint32_t N, L;          // oct_scratch_layout fills L and the five below
-    uint16_t* cells;        // the dense cell words
-    uint64_t* masks;        // "has a node", one bit per dense cell
-    uint32_t* bases;        // per 64 cells: the nodes among them, then the nodes in front of them
-    unsigned long long* sums;
-    unsigned long long* levelFirst;   // [0 .. L]: the nodes in front of every level, and the total
-    uint32_t* nodes;
-};
-size_t oct_scratch_bytes(uint32_t N);
-void oct_scratch_layout(uint8_t* scratch, uint32_t N, OctParams& p);
+// emit; and the way back, a grid from a tree.  scratch: oct_carve (dxv_octree.h).  nodes: 8 bytes each.
+struct OctParams;
 hipError_t launch_oct_count(const OctParams& p, hipStream_t s);
 hipError_t launch_oct_emit(const OctParams& p, hipStream_t s);
 // every voxel of the grid of side N becomes 0 or 1 from a tree of `count` nodes (4-byte aligned, not trusted); *bad = 1 if it cannot be followed
 hipError_t launch_oct_expand(uint8_t* grid, uint32_t N, const uint32_t* nodes, uint32_t count, uint32_t* bad, hipStream_t s);
 
 // components.hip -- the connected components of a whole N^3 grid (dxv_components.h): pack, init, merge, compress, number; ONE read of K by the
-// caller; the table.  scratch: comp_scratch_bytes(N) -- the member mask (a bit per voxel), the root bits (a bit per voxel), a count per 64
-// voxels, the scan's block sums, the total.  labels: N^3 uint32; table: 24 bytes per component; stats: 32 bytes per component of scratch.
+// caller; the table.  scratch: comp_carve (dxv_components.h).  labels: N^3 uint32; table: 24 bytes per component; stats: 32 bytes per component
+// of work.
 struct CompRecord;
-struct CompStats;
-struct CompParams {
-    const uint8_t* grid;    // N^3 bytes, element (iz * N + iy) * N + ix; a voxel is solid iff its byte is non-zero
-    uint32_t N;
-    int of;                 // DXV_COMP_SOLID / DXV_COMP_EMPTY
-    uint32_t connectivity;  // 6 / 26
-    uint32_t* labels;       // parent during the build, then the labels
-    uint64_t* mask;         // comp_scratch_layout fills these five
-    uint64_t* rootMask;
-    uint32_t* bases;
-    unsigned long long* sums;
-    unsigned long long* total;    // K
-    CompStats* stats;
-    CompRecord* table;
-};
-size_t comp_scratch_bytes(uint32_t N);
-void comp_scratch_layout(uint8_t* scratch, uint32_t N, CompParams& p);
+struct CompParams;
+struct CompSelectWork;
 hipError_t launch_comp_label(const CompParams& p, hipStream_t s);
 hipError_t launch_comp_stats(const CompParams& p, uint32_t K, hipStream_t s);
-// dxv_components_select: `work` -- comp_select_bytes(K) -- holds {kept, dropped, voxels changed, the maximum of comp_best_key}, then K keep flags
-size_t comp_select_bytes(uint32_t K);
-unsigned long long* comp_select_counters(uint8_t* work);
-hipError_t launch_comp_select(uint8_t* grid, uint32_t N, int of, const uint32_t* labels, const CompRecord* table, uint32_t K, int rule, uint32_t arg, uint8_t* work,
-                              hipStream_t s);
+// dxv_components_select: `work` -- comp_select_carve -- holds {kept, dropped, voxels changed, the maximum of comp_best_key}, then K keep flags
+hipError_t launch_comp_select(uint8_t* grid, uint32_t N, int of, const uint32_t* labels, const CompRecord* table, uint32_t K, int rule, uint32_t arg,
+                              const CompSelectWork& work, hipStream_t s);
 // ... its pack alone: grid -> the member mask (the first block of the scratch), for what reads the mask of a labelling after dxv_trim
 hipError_t launch_comp_pack(const uint8_t* grid, uint32_t N, int of, uint64_t* mask, hipStream_t s);
 // ... and its merge and its compress alone, for an operator that labels masks of its own over a parent array it has initialised (skeleton.hip)
@@ -319,36 +272,18 @@ hipError_t launch_comp_merge(const uint64_t* mask, uint32_t N, uint32_t connecti
 hipError_t launch_comp_compress(uint32_t* parent, uint32_t N, hipStream_t s);
 
 // skeleton.hip -- the skeleton graph of a whole N^3 grid (dxv_skeleton.h): pack, classify, init, merge and compress (the components'), number; ONE
-// read of {K, B} by the caller; the tables.  scratch: skel_scratch_bytes(N) -- four masks of a bit per voxel (member, node, curve, end), the two
-// kinds' root bits, a pair of counts per 64 voxels, the scan's block sums, {K, B, end voxels, curve voxels, junction voxels}.  labels: N^3 uint32;
-// nodes: 32 bytes each; branches: 48 bytes each; stats: 40 bytes per node of scratch.  The grid is only read.
+// read of {K, B} by the caller; the tables.  scratch: skel_carve (dxv_skeleton.h).  labels: N^3 uint32; nodes: 32 bytes each; branches: 48 bytes
+// each; stats: 40 bytes per node of work.  The grid is only read.
 struct SkelNode;
 struct SkelBranch;
-struct SkelNodeStats;
-struct SkelParams {
-    const uint8_t* grid;    // N^3 bytes, element (iz * N + iy) * N + ix; a voxel is a member iff its byte is non-zero
-    uint32_t N;
-    const uint32_t* weights;      // N^3 uint32 of the caller's, or nullptr
-    uint32_t* labels;       // parent during the build, then the labels
-    uint64_t *member, *node, *curve, *ends;     // skel_scratch_layout fills these and the five below
-    uint64_t *nodeRoots, *curveRoots;
-    uint32_t* counts;
-    unsigned long long* sums;
-    unsigned long long* totals;   // {K, B, end voxels, curve voxels, junction voxels}
-    SkelNodeStats* stats;
-    SkelNode* nodes;
-    SkelBranch* branches;
-};
-size_t skel_scratch_bytes(uint32_t N);
-void skel_scratch_layout(uint8_t* scratch, uint32_t N, SkelParams& p);
+struct SkelParams;
+struct SkelPruneWork;
 hipError_t launch_skel_classify(const SkelParams& p, hipStream_t s);
 hipError_t launch_skel_label(const SkelParams& p, hipStream_t s);
 hipError_t launch_skel_stats(const SkelParams& p, uint32_t K, uint32_t B, hipStream_t s);
-// dxv_skeleton_prune: `work` -- skel_prune_bytes(K, B) -- holds {branches removed, voxels removed}, then a flag per branch and per node
-size_t skel_prune_bytes(uint32_t K, uint32_t B);
-unsigned long long* skel_prune_counters(uint8_t* work);
+// dxv_skeleton_prune: `work` -- skel_prune_carve -- holds {branches removed, voxels removed}, then a flag per branch and per node
 hipError_t launch_skel_prune(uint8_t* grid, uint32_t N, const uint32_t* labels, const SkelNode* nodes, uint32_t K, const SkelBranch* branches, uint32_t B, uint32_t maxLen345,
-                             uint8_t* work, hipStream_t s);
+                             const SkelPruneWork& work, hipStream_t s);
 
 // measure.hip -- the integral measures of the K components of a labelling (dxv_measure.h): table = measure_table_bytes(K) = (K + 1) * 96 bytes,
 // record 0 the sum of the others; mask: the labelling's member mask; labels: N^3 uint32.  Nothing but the table is written.
@@ -357,10 +292,9 @@ hipError_t launch_measure(const uint64_t* mask, uint32_t N, uint32_t connectivit
 
 // morph.hip -- DILATE / ERODE / OPEN / CLOSE (0 .. 3) of a whole N^3 grid by the Euclidean ball of squared radius r2 (1 .. 4096; dxv_morph.h), in
 // place, bytes 0 / 1.  form 1: word-parallel on bit masks and R = floor(sqrt(r2)) planes; form 2: the distance field and its threshold, per
-// half.  scratch: morph_scratch_bytes(N, op, r2, form); it begins with {voxels set, voxels cleared}
-size_t morph_scratch_bytes(uint32_t N, int op, uint32_t r2, int form);
-unsigned long long* morph_counters(uint8_t* scratch);
-hipError_t launch_morph(uint8_t* grid, uint32_t N, int op, uint32_t r2, int form, uint8_t* scratch, hipStream_t s);
+// half.  scratch: morph_carve(N, op, r2, form) (dxv_morph.h); it begins with {voxels set, voxels cleared}
+struct MorphScratch;
+hipError_t launch_morph(uint8_t* grid, uint32_t N, int op, uint32_t r2, int form, const MorphScratch& scratch, hipStream_t s);
 // ... its pack (grid -> the solid mask and the "a byte here is neither 0 nor 1" bits, one per eight voxels) and its write-back (was, now: the solid
 // masks before and after; counters: {voxels set, voxels cleared}, added to) for the operators that work on the same masks
 void launch_morph_pack(const uint8_t* grid, uint32_t N, uint8_t* mask, uint64_t* loose, hipStream_t s);
@@ -368,95 +302,43 @@ void launch_morph_write(const uint8_t* was, const uint8_t* now, const uint64_t* 
 
 // thin.hip -- topology-preserving thinning of a whole N^3 grid (dxv_thin.h), kind 0 = CURVE, 1 = KERNEL, in place, bytes 0 / 1: one batch =
 // (first: the grid packed into the solid mask,) `iterations` iterations (1 .. kThinMaxRounds) of border + eight sub-iterations, the write-back.
-// scratch: thin_scratch_bytes(N); it begins with the batch's control block -- word k != 0: iteration k removed something; the batch has reached
+// scratch: thin_carve (dxv_thin.h); it begins with the batch's control block -- word k != 0: iteration k removed something; the batch has reached
 // the fixed point exactly when one of its words is 0 -- and the voxels removed since the first batch.  A batch with first = false goes on from
 // the masks of the one before.
-struct ThinControl {
-    uint32_t live[64];                // (kThinMaxRounds)
-    unsigned long long removed;
-    unsigned long long written[2];    // the write-back's own counters: nobody reads them
-};
-size_t thin_scratch_bytes(uint32_t N);
-hipError_t launch_thin(uint8_t* grid, uint32_t N, int kind, uint8_t* scratch, uint32_t iterations, bool first, hipStream_t s);
+struct ThinScratch;
+hipError_t launch_thin(uint8_t* grid, uint32_t N, int kind, const ThinScratch& scratch, uint32_t iterations, bool first, hipStream_t s);
 
 // thickness.hip -- the exact local thickness of a whole N^3 grid (dxv_thickness.h): W = N^3 uint32, hist = cap + 1 uint64, both the caller's;
-// everything else in scratch = thickness_scratch_bytes(N), laid out by thickness_layout.  Six stages, enqueued one by one so that the caller can
-// put its events between them; nothing is read back: thickness_counters points at {centres painted, work items, voxels the paint tested, atomics it
+// everything else in scratch, laid out by thickness_carve (dxv_thickness.h, with ThickParams).  Six stages, enqueued one by one so that the caller
+// can put its events between them; nothing is read back: p.counters points at {centres painted, work items, voxels the paint tested, atomics it
 // sent} in the scratch, the first two valid behind the select.  The grid is only read.
-struct ThickParams {
-    uint32_t N;
-    int of;                           // DXV_COMP_SOLID / DXV_COMP_EMPTY
-    uint32_t cap, cull;               // cap_sq; option thickcull
-    uint32_t count;                   // 1: the paint counts what it tests and sends (option thickstages)
-    uint32_t* W;
-    unsigned long long* hist;
-    int32_t *F, *G;                   // thickness_layout fills these and the ones below: the grid's field; E's field, then Top's
-    uint32_t* B;                      // a byte per voxel: E, then Top, then the work items of the voxel as a centre
-    unsigned long long* sums;         // per block of 1024 voxels {centres, items} in front of it, then the two totals and the paint's two counters
-    uint8_t* passes;                  // distance_scratch_bytes(N)
-    uint32_t *centres, *firstItem;    // the compacted centres (in G) and every centre's first item within its block (in the passes' scratch)
-};
+struct ThickParams;
 enum { THICK_STAGE_FIELD, THICK_STAGE_TOP, THICK_STAGE_CULL, THICK_STAGE_SELECT, THICK_STAGE_PAINT, THICK_STAGE_HISTOGRAM, THICK_STAGES };
-size_t thickness_scratch_bytes(uint32_t N);
 size_t thickness_histogram_bytes(uint32_t cap);
-void thickness_layout(uint8_t* scratch, uint32_t N, ThickParams& p);
-const unsigned long long* thickness_counters(const ThickParams& p);
 hipError_t launch_thickness_stage(const uint8_t* grid, const ThickParams& p, int stage, hipStream_t s);
 
 // partition.hip -- the maximal-ball partition of a whole N^3 grid (dxv_partition.h): labels = N^3 uint32, table = 32 K bytes, throats = 20 T bytes,
-// all the caller's.  scratch = partition_scratch_bytes(N), laid out by partition_layout; work = partition_work_bytes(K, faces), laid out by
-// partition_work_layout once the caller has waited for partition_totals = {K, interface faces} behind PART_STAGE_ROOTS.  The stages are enqueued
-// one by one so that the caller can put its events between them; the throats take launch_partition_pairs, a wait for partition_pair_total = T, and
-// launch_partition_throats.  partition_counters points at {mip cells tested, voxels tested} of the search (option partstages).  The grid is only read.
-struct PartRegion;
-struct PartStats;
-struct PartParams {
-    uint32_t N;
-    int of;                           // DXV_COMP_SOLID / DXV_COMP_EMPTY
-    uint32_t cap, prune;              // cap_sq; option partprune
-    uint32_t count;                   // 1: the search counts what it tests (option partstages)
-    uint32_t wantThroats;             // 1: the interface faces are counted with the roots
-    uint32_t K;                       // partition_work_layout fills these two and the work pointers below
-    unsigned long long faces;
-    uint32_t* labels;                 // the caller's, in place from PART_STAGE_REGIONS on
-    PartRegion* table;
-    int32_t* F;                       // partition_layout fills these: the grid's field, and in the same words ...
-    uint32_t *parent, *number;        // ... every member's parent, then the roots' numbers
-    uint32_t* rootOf;
-    uint64_t *keys, *mip4, *mip16;
-    unsigned long long *sums, *counters;
-    uint8_t* passes;                  // distance_scratch_bytes(N)
-    PartStats* stats;
-    uint64_t *sortA, *sortB, *sorted, *pairs;     // the sort's two buffers; which of them holds the sorted words, and the other: the unique pairs
-    uint32_t* hist;
-    unsigned long long* headSums;
-    uint32_t* pairCount;
-};
+// all the caller's.  scratch is laid out by partition_carve, work by partition_work_carve (dxv_partition.h, with PartParams) once the caller has
+// waited for p.totals = {K, interface faces} behind PART_STAGE_ROOTS.  The stages are enqueued one by one so that the caller can put its events
+// between them; the throats take launch_partition_pairs, a wait for p.pairTotal = T, and launch_partition_throats.  p.counters points at {mip
+// cells tested, voxels tested} of the search (option partstages).  The grid is only read.
+struct PartParams;
 enum { PART_STAGE_FIELD, PART_STAGE_KEYS, PART_STAGE_SEARCH, PART_STAGE_ROOTS, PART_STAGE_REGIONS, PART_STAGE_THROATS, PART_STAGES };
-size_t partition_scratch_bytes(uint32_t N);
-void partition_layout(uint8_t* scratch, uint32_t N, PartParams& p);
-const unsigned long long* partition_totals(const PartParams& p);
-const unsigned long long* partition_counters(const PartParams& p);
-size_t partition_work_bytes(uint32_t K, unsigned long long faces);
-void partition_work_layout(uint8_t* work, uint32_t K, unsigned long long faces, PartParams& p);
-const unsigned long long* partition_pair_total(const PartParams& p);
 hipError_t launch_partition_stage(const uint8_t* grid, const PartParams& p, int stage, hipStream_t s);     // PART_STAGE_FIELD .. PART_STAGE_REGIONS
 hipError_t launch_partition_pairs(PartParams& p, hipStream_t s);
 hipError_t launch_partition_throats(const PartParams& p, uint32_t T, uint32_t* throats, hipStream_t s);
 
 // geodesic.hip -- the geodesic distance inside a whole N^3 grid (dxv_geodesic.h): map = N^3 uint32, the caller's; everything else in scratch =
-// geodesic_scratch_bytes(N): the batch's control block -- word k = the live tiles of round k; the batch has reached the fixed point exactly when
-// one of its words is 0 --, the tally {seeds used, reached, unreached, key}, two sets of live flags (a byte per 8^3 tile) and the queue (a word
-// per tile).  launch_geodesic_init: the map's first words and the live flags of round 0 from the grid and the seeds -- `seeds` is a device
-// pointer, N^3 bytes for GEO_SEEDS_MASK, seedCount voxel indices for GEO_SEEDS_LIST.  launch_geodesic_batch: `rounds` rounds (1 .. kGeoMaxRounds),
-// the first of them round `base` of the call, then the tally.  The grid is read by the init alone.
-struct GeoControl {
-    uint32_t live[64];                // (kGeoMaxRounds)
-    unsigned long long tally[4];      // GeoTally
-};
-size_t geodesic_scratch_bytes(uint32_t N);
-hipError_t launch_geodesic_init(const uint8_t* grid, uint32_t N, int of, int seedsKind, const void* seeds, uint32_t seedCount, uint32_t* map, uint8_t* scratch, hipStream_t s);
-hipError_t launch_geodesic_batch(uint32_t* map, uint32_t N, int metric, uint32_t limit, uint8_t* scratch, uint32_t rounds, uint32_t base, hipStream_t s);
+// geodesic_carve (dxv_geodesic.h, with GeoControl): the batch's control block -- word k = the live tiles of round k; the batch has reached the fixed
+// point exactly when one of its words is 0 --, the tally {seeds used, reached, unreached, key}, two sets of live flags (a byte per 8^3 tile) and
+// the queue (a word per tile).  launch_geodesic_init: the map's first words and the live flags of round 0 from the grid and the seeds -- `seeds`
+// is a device pointer, N^3 bytes for GEO_SEEDS_MASK, seedCount voxel indices for GEO_SEEDS_LIST.  launch_geodesic_batch: `rounds` rounds
+// (1 .. kGeoMaxRounds), the first of them round `base` of the call, then the tally.  The grid is read by the init alone.
+struct GeoControl;
+struct GeoScratch;
+hipError_t launch_geodesic_init(const uint8_t* grid, uint32_t N, int of, int seedsKind, const void* seeds, uint32_t seedCount, uint32_t* map, const GeoScratch& scratch,
+                                hipStream_t s);
+hipError_t launch_geodesic_batch(uint32_t* map, uint32_t N, int metric, uint32_t limit, const GeoScratch& scratch, uint32_t rounds, uint32_t base, hipStream_t s);
 // ... and the path from `target` down to a seed, by one wave: out = {voxels on the path, 0 or 1: no neighbour continued it}, then min(length,
 // capacity) voxel indices
 hipError_t launch_geodesic_path(const uint32_t* map, uint32_t N, int metric, uint32_t target, uint32_t* out, uint32_t capacity, hipStream_t s);
@@ -464,19 +346,17 @@ hipError_t launch_geodesic_path(const uint32_t* map, uint32_t N, int metric, uin
 hipError_t launch_geodesic_compact(uint8_t* live, uint32_t tiles, GeoControl* ctl, uint32_t round, uint32_t* queue, hipStream_t s);
 
 // access.hip -- the access radius inside a whole N^3 grid and its intrusion map (dxv_access.h): A = N^3 uint32, the caller's, and with
-// `intrusion` I likewise; the histograms cap + 1 uint64 each; everything else in scratch = access_scratch_bytes(N, intrusion): a control block,
-// live flags and a queue of the geodesic's shape (GeoControl: word k = the live tiles of round k, then the tally {seeds used, reached,
-// unreached, key}), the word the seeds are counted in, and behind them the radius field F with the scratch of its passes -- with `intrusion`
-// the whole of a thickness's scratch, which begins with F.  access_layout fills a ThickParams for that part (N, F and passes always; the rest
-// with `intrusion`).  launch_access_init: the field, A's first words and the live flags of round 0.  launch_access_batch: `rounds` rounds
-// (1 .. kAccMaxRounds), the first of them round `base` of the call, then the tally.  launch_access_radius, once A has settled: A into F in
-// thick_radius's encoding, for launch_thickness_stage TOP .. HISTOGRAM with W = I.  The grid is read by the field alone.
-size_t access_scratch_bytes(uint32_t N, bool intrusion);
-void access_layout(uint8_t* scratch, uint32_t N, bool intrusion, ThickParams& p);
-hipError_t launch_access_init(const uint8_t* grid, uint32_t N, int of, uint32_t cap, int seedsKind, const void* seeds, uint32_t seedCount, uint32_t* A, uint8_t* scratch, bool intrusion,
+// `intrusion` I likewise; the histograms cap + 1 uint64 each; everything else in scratch, laid out by access_carve (dxv_access.h): a control block,
+// live flags and a queue of the geodesic's shape, the word the seeds are counted in, and behind them the radius field F with the scratch of its
+// passes -- with `intrusion` the whole of a thickness's scratch, which begins with F.  launch_access_init: the field, A's first words and the live
+// flags of round 0.  launch_access_batch: `rounds` rounds (1 .. kAccMaxRounds), the first of them round `base` of the call, then the tally.
+// launch_access_radius, once A has settled: A into F in thick_radius's encoding, for launch_thickness_stage TOP .. HISTOGRAM with W = I.  The grid
+// is read by the field alone.
+struct AccScratch;
+hipError_t launch_access_init(const uint8_t* grid, uint32_t N, int of, uint32_t cap, int seedsKind, const void* seeds, uint32_t seedCount, uint32_t* A, const AccScratch& scratch,
                               hipStream_t s);
-hipError_t launch_access_batch(uint32_t* A, uint32_t N, int of, int connectivity, uint32_t cap, uint8_t* scratch, bool intrusion, uint32_t rounds, uint32_t base, hipStream_t s);
-hipError_t launch_access_radius(const uint32_t* A, uint32_t N, int of, uint8_t* scratch, bool intrusion, hipStream_t s);
+hipError_t launch_access_batch(uint32_t* A, uint32_t N, int of, int connectivity, uint32_t cap, const AccScratch& scratch, uint32_t rounds, uint32_t base, hipStream_t s);
+hipError_t launch_access_radius(const uint32_t* A, uint32_t N, int of, const AccScratch& scratch, hipStream_t s);
 
 // raycast.hip
 struct RayCastCB;

@@ -22,11 +22,23 @@
 #pragma once
 #include <math.h>
 #include "dxv_types.h"
+#include "dxv_scratch.h"
 
 namespace dxv {
 
 constexpr int32_t kDistNone = 0x7fffffff;     // magnitude where no voxel of the other kind exists (the int32 format's own sentinel)
 constexpr int32_t kDistRowNone = 0x7fff;      // ... in the 16-bit values of the x pass
+
+// scratch of the three passes: the x pass's 16-bit values in whole lines, the y pass's squares as they are (the one block of the operators
+// that does not end on a line: what embeds these passes puts them last)
+struct DistScratch { int16_t* rows; int32_t* squares; };
+inline void distance_carve(Carve& c, uint32_t N, DistScratch& l)
+{
+    const size_t voxels = (size_t)N * N * N;
+    l.rows = c.take<int16_t>(voxels);
+    l.squares = reinterpret_cast<int32_t*>(c.take_bytes(voxels * sizeof(int32_t)));
+}
+inline size_t distance_scratch_bytes(uint32_t N) { return carved_bytes<DistScratch>(distance_carve, N); }
 
 // ---- x: the nearest voxel of the other kind in the row.  bits: the row's voxels, bit x % 64 of word x / 64 set = solid ----
 DXV_HD uint64_t dist_row_other(const uint64_t* bits, uint32_t N, uint32_t w, bool solid)

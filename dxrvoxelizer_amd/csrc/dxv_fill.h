@@ -10,6 +10,7 @@
 #include <stddef.h>
 #include "dxv_types.h"
 #include "dxv_solid.h"
+#include "dxv_scratch.h"
 
 namespace dxv {
 
@@ -19,6 +20,20 @@ constexpr uint32_t kFillBlock = 8;                // steps of a column pass whos
 
 DXV_HD uint32_t fill_row_words(uint32_t N) { return (N + 63u) / 64u; }
 DXV_HD size_t fill_mask_words(uint32_t N) { return (size_t)N * N * fill_row_words(N); }
+// such a mask in whole lines of device memory, and beside it one bit per eight voxels of it (morph.hip's pack: "a byte here is neither 0 nor 1")
+inline size_t fill_loose_words(uint32_t N) { return (fill_mask_words(N) * 8u + 63u) / 64u; }
+inline size_t fill_mask_bytes(uint32_t N) { return align256(fill_mask_words(N) * sizeof(uint64_t)); }
+inline size_t fill_loose_bytes(uint32_t N) { return align256(fill_loose_words(N) * sizeof(uint64_t)); }
+
+// scratch of the fill: the free mask, the reached mask, the batch's control block (a word per round)
+struct FillScratch { uint64_t *freeMask, *reached; uint32_t* ctl; };
+inline void fill_carve(Carve& c, uint32_t N, FillScratch& l)
+{
+    l.freeMask = c.take<uint64_t>(fill_mask_words(N));
+    l.reached = c.take<uint64_t>(fill_mask_words(N));
+    l.ctl = reinterpret_cast<uint32_t*>(c.take_bytes(sizeof(uint32_t) * kFillMaxRounds));
+}
+inline size_t fill_scratch_bytes(uint32_t N) { return carved_bytes<FillScratch>(fill_carve, N); }
 
 DXV_HD uint64_t fill_reverse(uint64_t v)
 {

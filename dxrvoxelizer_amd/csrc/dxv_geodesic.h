@@ -11,6 +11,7 @@
 #pragma once
 #include <stddef.h>
 #include "dxv_types.h"
+#include "dxv_scratch.h"
 
 namespace dxv {
 
@@ -163,5 +164,26 @@ DXV_HD void geo_tally_combine(GeoTally& a, const GeoTally& b)
 // nothing reached: key 0 reads farthest 0 at voxel 0xFFFFFFFF
 DXV_HD uint32_t geo_tally_farthest(const GeoTally& t) { return (uint32_t)(t.key >> 32); }
 DXV_HD uint32_t geo_tally_farthest_voxel(const GeoTally& t) { return 0xFFFFFFFFu - (uint32_t)(t.key & 0xFFFFFFFFu); }
+
+// ---- scratch of a flood in tiles (geodesic.hip, access.hip) ----
+// the batch's control block -- word k = the live tiles of round k; the batch has reached the fixed point exactly when one of its words is 0 --
+// and the tally behind the rounds: {seeds used, reached, unreached, the operator's own key}
+struct GeoControl {
+    uint32_t live[64];                // (kGeoMaxRounds)
+    unsigned long long tally[4];      // GeoTally
+};
+inline uint32_t geo_tiles(uint32_t N) { return geo_tiles_side(N) * geo_tiles_side(N) * geo_tiles_side(N); }
+// the control block, two sets of live flags (a byte per 8^3 tile; flagBytes: both, cleared together) and the queue (a word per tile)
+struct GeoScratch { GeoControl* ctl; uint8_t* flags[2]; size_t flagBytes; uint32_t* queue; };
+inline void geodesic_carve(Carve& c, uint32_t N, GeoScratch& l)
+{
+    l.ctl = c.take<GeoControl>(1);
+    const size_t from = c.used();
+    l.flags[0] = c.take<uint8_t>(geo_tiles(N));
+    l.flags[1] = c.take<uint8_t>(geo_tiles(N));
+    l.flagBytes = c.used() - from;
+    l.queue = c.take<uint32_t>(geo_tiles(N));
+}
+inline size_t geodesic_scratch_bytes(uint32_t N) { return carved_bytes<GeoScratch>(geodesic_carve, N); }
 
 } // namespace dxv

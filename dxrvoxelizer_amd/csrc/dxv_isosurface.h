@@ -10,6 +10,7 @@
 #include <math.h>
 #include <stddef.h>
 #include "dxv_types.h"
+#include "dxv_scratch.h"
 
 namespace dxv {
 
@@ -135,5 +136,31 @@ DXV_HD void iso_quad(uint32_t out[6], const uint64_t* masks, const IsoCounts* ba
     if (!object) { out[0] = v0; out[1] = v1; out[2] = v2; out[3] = v0; out[4] = v2; out[5] = v3; }
     else { out[0] = v2; out[1] = v1; out[2] = v0; out[3] = v3; out[4] = v2; out[5] = v0; }
 }
+
+// ---- what isosurface.hip's launches work on: vb (24 bytes per vertex) and ib (three uint32 per triangle) are the caller's ----
+struct IsoParams {
+    const float* field;     // N^3 floats, element (iz * N + iy) * N + ix
+    uint32_t N;
+    float iso, P;           // the level, and one voxel in the field's unit: what a sample outside the grid is worth
+    int object;             // 0: vertices in voxel index space, 1: in object space through `bound` (triangles turned round: y is mirrored)
+    float bound[4];
+    uint64_t* masks;        // iso_carve fills these four
+    IsoCounts* bases;
+    unsigned long long* sums;
+    unsigned long long* totals;   // {vertices, quads} of the whole mesh
+    IsoVertex* vb;
+    uint32_t* ib;
+};
+// scratch of one extraction: one bit per lattice cell, two counts per 64 cells, the scan's block sums, the two totals -- 8-byte words one
+// behind the other, not in lines of their own
+inline void iso_carve(Carve& c, uint32_t N, IsoParams& p)
+{
+    const size_t words = iso_words(N);
+    p.masks = reinterpret_cast<uint64_t*>(c.take_bytes(words * sizeof(uint64_t)));
+    p.bases = reinterpret_cast<IsoCounts*>(c.take_bytes(words * sizeof(IsoCounts)));
+    p.sums = reinterpret_cast<unsigned long long*>(c.take_bytes(2u * (size_t)scan_blocks(words) * sizeof(unsigned long long)));
+    p.totals = reinterpret_cast<unsigned long long*>(c.take_bytes(2u * sizeof(unsigned long long)));
+}
+inline size_t iso_scratch_bytes(uint32_t N) { return carved_bytes<IsoParams>(iso_carve, N); }
 
 } // namespace dxv

@@ -16,6 +16,7 @@
 #include "dxv_types.h"
 #include "dxv_solid.h"
 #include "dxv_fill.h"
+#include "dxv_distance.h"
 
 namespace dxv {
 
@@ -111,5 +112,29 @@ DXV_HD uint64_t morph_ball_word(const uint64_t* m0, const uint64_t* planes, size
 
 // ---- write-back: one byte of the masks -> eight result bytes of 0 / 1 (fill_spread_byte), and what it counts ----
 DXV_HD uint32_t morph_popc8(uint32_t b) { return solid_popc((uint64_t)(b & 0xffu)); }
+
+// ---- scratch of one call: {voxels set, voxels cleared} in a line of their own, then
+//   planes: the packed mask, one result mask per half, the "neither 0 nor 1" bits, the R planes (a mask each)
+//   field:  the field (4 B per voxel) and the scratch of its passes (distance_scratch_bytes, 6 B per voxel) ----
+struct MorphScratch {
+    unsigned long long* counters;
+    uint64_t *packed, *half[2], *loose, *planes;
+    int32_t* field;
+    uint8_t* passes;
+};
+inline void morph_carve(Carve& c, uint32_t N, int op, uint32_t r2, int form, MorphScratch& l)
+{
+    l.counters = reinterpret_cast<unsigned long long*>(c.take_bytes(256u));
+    if (form == MORPH_FORM_FIELD) {
+        l.field = c.take<int32_t>((size_t)N * N * N);
+        l.passes = c.take_bytes(distance_scratch_bytes(N));
+        return;
+    }
+    l.packed = c.take<uint64_t>(fill_mask_words(N));
+    for (uint32_t half = 0; half < morph_halves(op); ++half) l.half[half] = c.take<uint64_t>(fill_mask_words(N));
+    l.loose = c.take<uint64_t>(fill_loose_words(N));
+    l.planes = reinterpret_cast<uint64_t*>(c.take_bytes((size_t)morph_isqrt(r2) * fill_mask_bytes(N)));
+}
+inline size_t morph_scratch_bytes(uint32_t N, int op, uint32_t r2, int form) { return carved_bytes<MorphScratch>(morph_carve, N, op, r2, form); }
 
 } // namespace dxv

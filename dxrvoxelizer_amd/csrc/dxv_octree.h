@@ -11,6 +11,7 @@
 #pragma once
 #include <stddef.h>
 #include "dxv_types.h"
+#include "dxv_scratch.h"
 
 namespace dxv {
 
@@ -131,5 +132,32 @@ DXV_HD int oct_lookup(const uint32_t* nodes, uint32_t count, uint32_t levels, ui
     }
     return OCT_BAD;
 }
+
+// ---- what octree.hip's launches work on: nodes (8 bytes each) is the caller's ----
+struct OctParams {
+    const uint8_t* grid;    // N^3 bytes, element (iz * N + iy) * N + ix; a voxel is solid iff its byte is non-zero
+    uint32_t N, L;          // oct_carve fills L and the five below
+    uint16_t* cells;        // the dense cell words
+    uint64_t* masks;        // "has a node", one bit per dense cell
+    uint32_t* bases;        // per 64 cells: the nodes among them, then the nodes in front of them
+    unsigned long long* sums;
+    unsigned long long* levelFirst;   // [0 .. L]: the nodes in front of every level, and the total
+    uint32_t* nodes;
+};
+inline size_t oct_words(uint32_t L) { return oct_level_offset(L) >> 6; }
+// scratch of one build: the dense cell words (2 bytes per cell of levels 0 .. L - 1), their "has a node" bits, the words' counts / bases, the
+// scan's block sums, level_first
+inline void oct_carve(Carve& c, uint32_t N, OctParams& p)
+{
+    const uint32_t L = oct_levels(N);
+    const size_t words = oct_words(L);
+    p.N = N; p.L = L;
+    p.cells = c.take<uint16_t>(words * 64u);
+    p.masks = c.take<uint64_t>(words);
+    p.bases = c.take<uint32_t>(words);
+    p.sums = c.take<unsigned long long>(scan_blocks(words));
+    p.levelFirst = c.take<unsigned long long>(kOctMaxLevels + 1u);
+}
+inline size_t oct_scratch_bytes(uint32_t N) { return carved_bytes<OctParams>(oct_carve, N); }
 
 } // namespace dxv

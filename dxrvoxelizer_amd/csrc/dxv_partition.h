@@ -39,7 +39,7 @@ struct PartRegion {
 struct PartThroat { uint32_t a, b, faces, neck_sq, neck_voxel; };
 static_assert(sizeof(PartRegion) == 32 && sizeof(PartThroat) == 20, "record layouts");
 // what the atomics of a region's voxels work on
-struct PartStats { uint32_t voxels, lo[3], hi[3], flags; };
+using PartStats = BoxStats;
 
 DXV_HD uint64_t part_key(uint32_t R, uint32_t index) { return R ? (uint64_t)R << 32 | (uint64_t)(0xFFFFFFFFu - index) : 0ull; }
 DXV_HD uint32_t part_key_radius(uint64_t key) { return (uint32_t)(key >> 32); }
@@ -220,7 +220,7 @@ DXV_HD uint32_t part_find_pair(const uint64_t* pairs, uint32_t T, uint64_t pair)
 DXV_HD uint64_t part_neck_word(uint32_t neck, uint32_t p) { return (uint64_t)neck << 32 | (uint64_t)(0xFFFFFFFFu - p); }
 
 DXV_HD uint32_t part_border(uint32_t x, uint32_t y, uint32_t z, uint32_t N) { return !x || !y || !z || x == N - 1u || y == N - 1u || z == N - 1u ? 1u : 0u; }
-DXV_HD PartStats part_stats_none() { return PartStats{0u, {kPartNone, kPartNone, kPartNone}, {0u, 0u, 0u}, 0u}; }
+DXV_HD PartStats part_stats_none() { return box_stats_none(); }          // (the one init of dxv_scratch.h, under the name the host check calls)
 DXV_HD PartRegion part_region(uint32_t root, uint32_t radius, const PartStats& s)
 {
     return PartRegion{root, radius, s.voxels, 0u, {(uint16_t)s.lo[0], (uint16_t)s.lo[1], (uint16_t)s.lo[2]}, {(uint16_t)s.hi[0], (uint16_t)s.hi[1], (uint16_t)s.hi[2]}, s.flags};
@@ -229,5 +229,74 @@ DXV_HD PartThroat part_throat(uint64_t pair, uint32_t shift, uint32_t faces, uin
 {
     return PartThroat{part_pair_a(pair, shift), part_pair_b(pair, shift), faces, (uint32_t)(neckWord >> 32), 0xFFFFFFFFu - (uint32_t)neckWord};
 }
+
+// What partition.hip's stages work on: labels = N^3 uint32, table = 32 K bytes (and throats = 20 T bytes) are the caller's; scratch and work are
+// carved below.
+struct PartParams {
+    uint32_t N;
+    int of;                           // DXV_COMP_SOLID / DXV_COMP_EMPTY
+    uint32_t cap, prune;              // cap_sq; option partprune
+    uint32_t count;                   // 1: the search counts what it tests (option partstages)
+    uint32_t wantThroats;             // 1: the interface faces are counted with the roots
+    uint32_t K;                       // partition_work_carve fills these two and the work pointers below
+    unsigned long long faces;
+    uint32_t* labels;                 // the caller's, in place from PART_STAGE_REGIONS on
+    PartRegion* table;
+    int32_t* F;                       // partition_carve fills these: the grid's field, and in the same words ...
+    uint32_t *parent, *number;        // ... every member's parent, then the roots' numbers
+    uint32_t* rootOf;
+    uint64_t *keys, *mip4, *mip16;
+    unsigned long long *sums, *counters;          // the blocks' sums; {mip cells tested, voxels tested} of the search (option partstages)
+    uint8_t* passes;                  // distance_scratch_bytes(N)
+    PartStats* stats;
+    uint64_t *sortA, *sortB, *sorted, *pairs;     // the sort's two buffers; which of them holds the sorted words, and the other: the unique pairs
+    uint32_t* hist;
+    unsigned long long* headSums;
+    uint32_t* pairCount;
+    const unsigned long long *totals, *pairTotal; // for the host, behind the sums and behind the head sums: {K, interface faces}, and T
+};
+inline uint32_t part_blocks(size_t items) { return (uint32_t)((items + kPartBlock - 1u) / kPartBlock); }
+// the sums of the blocks of a scan of `items` items, two per block, with the two totals behind them
+inline size_t part_sums_words(size_t items) { return 2u * ((size_t)part_blocks(items) + 1u); }
+
+// scratch of one call: F, then parent, then the roots' numbers (4 B per voxel); rootOf (4 B); the keys (8 B); the two mip levels; the blocks'
+// sums with the totals {K, interface faces} behind them; the search's two counters; the scratch of the field's passes (6 B per voxel)
+inline void partition_carve(Carve& c, uint32_t N, PartParams& p)
+{
+    const size_t voxels = (size_t)N * N * N, n4 = part_cells(N, 4u), n16 = part_cells(N, 16u);
+    p.N = N;
+    p.parent = p.number = c.take<uint32_t>(voxels);
+    p.F = reinterpret_cast<int32_t*>(p.parent);
+    p.rootOf = c.take<uint32_t>(voxels);
+    p.keys = c.take<uint64_t>(voxels);
+    p.mip4 = c.take<uint64_t>(n4 * n4 * n4);
+    p.mip16 = c.take<uint64_t>(n16 * n16 * n16);
+    p.sums = c.take<unsigned long long>(part_sums_words(voxels));
+    p.totals = carve_at<const unsigned long long>(p.sums, 2u * (size_t)part_blocks(voxels));
+    p.counters = reinterpret_cast<unsigned long long*>(c.take_bytes(256u));
+    p.passes = c.take_bytes(distance_scratch_bytes(N));
+}
+inline size_t partition_scratch_bytes(uint32_t N) { return carved_bytes<PartParams>(partition_carve, N); }
+
+// work of one call, sized once {K, interface faces} are known: the regions' stats; for the throats the two buffers of the sort, its histogram, the
+// sums of the run heads with T behind them, and a count per pair.  The unique pairs go into the buffer the sort did not end in, the pairs' 64-bit
+// neck words to the front of the one it did.  Without faces nothing of the throats is allocated -- their pointers stand where they would begin and
+// nothing is launched that reads them --, and an allocation is never empty.
+inline void partition_work_carve(Carve& c, uint32_t K, unsigned long long faces, PartParams& p)
+{
+    const size_t n = (size_t)faces;
+    p.K = K; p.faces = faces;
+    p.stats = c.take<PartStats>(K);
+    const size_t throatsAt = c.used();
+    p.sortA = c.take<uint64_t>(n);
+    p.sortB = c.take<uint64_t>(n);
+    p.hist = c.take<uint32_t>(n ? radix_sort_hist_words((uint32_t)n) : 0u);
+    p.headSums = c.take<unsigned long long>(part_sums_words(n));
+    p.pairTotal = carve_at<const unsigned long long>(p.headSums, 2u * (size_t)part_blocks(n));
+    p.pairCount = c.take<uint32_t>(n);
+    if (!n) c.at = throatsAt;
+    if (!c.used()) (void)c.take_bytes(256u);
+}
+inline size_t partition_work_bytes(uint32_t K, unsigned long long faces) { return carved_bytes<PartParams>(partition_work_carve, K, faces); }
 
 } // namespace dxv

@@ -31,6 +31,15 @@ namespace dxvhost {
 using PinnedFrame = dxv_ctx::Pinned::PerFrame;
 static PinnedFrame& cur_pinned(dxv_ctx* c) { return c->pin->frame[c->cur]; }
 
+// An operator's scratch laid out in the buffer it was reserved in: carve = the operator's own description (X_carve, args ..., params), the one
+// its X_scratch_bytes sized the buffer with.  A buffer that does not hold what was taken fails the call here, in front of every launch.
+template <class P, class F, class... A> static hipError_t carve_buffer(const DevBuf<uint8_t>& b, P& p, F carve, A... args)
+{
+    Carve c(b.p, b.cap);
+    carve(c, args..., p);
+    return b.p && c.fits() ? hipSuccess : hipErrorInvalidValue;
+}
+
 // the refusals of whatever works on the whole grid of the selected frame
 static int check_whole_grid(dxv_ctx* c, const char* who)
 {
@@ -287,10 +296,13 @@ int settle_fill(dxv_ctx* c, uint32_t i)
     Frame::Fill& o = f.fill;
     uint32_t* ctl = c->pin->frame[i].fillCtl;
     const uint32_t N = f.grid_dim;
-    const Batched b{"dxv_fill", "rounds", kTimerFill, N, &o.pending, o.batch, &o.batch, &o.rounds, ctl, o.pending ? fill_control(o.scratch.p, N) : nullptr, sizeof(c->pin->frame[i].fillCtl)};
+    Carve carve(o.scratch.p, o.scratch.cap);                            // (as dxv_fill_async laid it out; all null without a scratch)
+    FillScratch l{};
+    fill_carve(carve, N, l);
+    const Batched b{"dxv_fill", "rounds", kTimerFill, N, &o.pending, o.batch, &o.batch, &o.rounds, ctl, l.ctl, sizeof(c->pin->frame[i].fillCtl)};
     return settle_batched(c, i, b,
         [&](uint32_t live, bool last) { o.rounds += last ? live + 1u : o.batch; return last; },
-        [&](hipStream_t fs) { return launch_fill(f.grid.p, N, o.what, o.scratch.p, o.batch, false, fs); });
+        [&](hipStream_t fs) { return launch_fill(f.grid.p, N, o.what, l, o.batch, false, fs); });
 }
 
 // the thin's: a batch all of whose iterations removed something has not reached the fixed point; unless max_iterations has been used up, a
@@ -301,7 +313,10 @@ int settle_thin(dxv_ctx* c, uint32_t i)
     Frame::Thin& o = f.thin;
     ThinControl& ctl = c->pin->frame[i].thinCtl;
     const uint32_t N = f.grid_dim;
-    const Batched b{"dxv_thin", "iterations", kTimerThin, N, &o.pending, o.batch, &o.inBatch, &o.iterations, &ctl, o.scratch.p, sizeof(ThinControl)};
+    Carve carve(o.scratch.p, o.scratch.cap);                            // (as dxv_thin_async laid it out; all null without a scratch)
+    ThinScratch l{};
+    thin_carve(carve, N, l);
+    const Batched b{"dxv_thin", "iterations", kTimerThin, N, &o.pending, o.batch, &o.inBatch, &o.iterations, &ctl, l.ctl, sizeof(ThinControl)};
     return settle_batched(c, i, b,
         [&](uint32_t live, bool last) {
             o.removed = ctl.removed;
@@ -312,7 +327,7 @@ int settle_thin(dxv_ctx* c, uint32_t i)
         [&](hipStream_t fs) {
             o.inBatch = thin_batch(o.batch, o.bounded ? o.left : 0u);
             if (o.bounded) o.left -= o.inBatch;
-            return launch_thin(f.grid.p, N, o.kind, o.scratch.p, o.inBatch, false, fs);
+            return launch_thin(f.grid.p, N, o.kind, l, o.inBatch, false, fs);
         });
 }
 
@@ -337,7 +352,10 @@ int settle_geodesic(dxv_ctx* c, uint32_t i)
     Frame::Geodesic& o = f.geo;
     GeoControl& ctl = c->pin->frame[i].geoCtl;
     const uint32_t N = o.dim;
-    const Batched b{"dxv_geodesic", "rounds", kTimerGeodesic, N, &o.pending, o.batch, &o.batch, &o.rounds, &ctl, o.scratch.p, sizeof(GeoControl)};
+    Carve carve(o.scratch.p, o.scratch.cap);                            // (as dxv_geodesic_async laid it out; all null without a scratch)
+    GeoScratch l{};
+    geodesic_carve(carve, N, l);
+    const Batched b{"dxv_geodesic", "rounds", kTimerGeodesic, N, &o.pending, o.batch, &o.batch, &o.rounds, &ctl, l.ctl, sizeof(GeoControl)};
     return settle_batched(c, i, b,
         [&](uint32_t live, bool last) {
             account_flood(o, ctl, live, last);
@@ -347,16 +365,22 @@ int settle_geodesic(dxv_ctx* c, uint32_t i)
             }
             return last;
         },
-        [&](hipStream_t fs) { return launch_geodesic_batch(o.map.p, N, o.metric, o.limit, o.scratch.p, o.batch, o.rounds, fs); });
+        [&](hipStream_t fs) { return launch_geodesic_batch(o.map.p, N, o.metric, o.limit, l, o.batch, o.rounds, fs); });
 }
 
 // the access's: the geodesic's loop; behind the confirming round A is final, and what is made of it -- A into the radius field, thickness's
 // stages TOP .. HISTOGRAM with W = the intrusion map, A's own histogram -- is enqueued here and waited for, the timer's second event behind it
+static AccScratch access_scratch(const Frame::Access& o)
+{
+    Carve carve(o.scratch.p, o.scratch.cap);                            // (as dxv_access_async laid it out; all null without a scratch)
+    AccScratch l{};
+    access_carve(carve, o.dim, o.wantIntrusion, l);
+    return l;
+}
 static ThickParams access_params(const Frame::Access& o, uint32_t* W, unsigned long long* hist)
 {
-    ThickParams p{};
+    ThickParams p = access_scratch(o).thick;
     p.of = o.of; p.cap = o.cap; p.cull = o.cull; p.count = 0u; p.W = W; p.hist = hist;
-    access_layout(o.scratch.p, o.dim, o.wantIntrusion, p);
     return p;
 }
 static int finish_access(dxv_ctx* c, uint32_t i)
@@ -368,7 +392,7 @@ static int finish_access(dxv_ctx* c, uint32_t i)
     DXV_HIP(c, launch_thickness_stage(f.grid.p, access_params(o, o.map.p, o.hist.p), THICK_STAGE_HISTOGRAM, fs));
     if (o.wantIntrusion) {
         const ThickParams p = access_params(o, o.intrusion.p, o.histI.p);
-        DXV_HIP(c, launch_access_radius(o.map.p, o.dim, o.of, o.scratch.p, true, fs));
+        DXV_HIP(c, launch_access_radius(o.map.p, o.dim, o.of, access_scratch(o), fs));
         for (int stage = THICK_STAGE_TOP; stage < THICK_STAGES; ++stage) DXV_HIP(c, launch_thickness_stage(f.grid.p, p, stage, fs));
     }
     if (t.armed) DXV_HIP(c, hipEventRecord(t.e1, fs));
@@ -383,7 +407,8 @@ int settle_access(dxv_ctx* c, uint32_t i)
     GeoControl& ctl = c->pin->frame[i].accCtl;
     const uint32_t N = o.dim;
     int finished = 0;
-    const Batched b{"dxv_access", "rounds", kTimerAccess, N, &o.pending, o.batch, &o.batch, &o.rounds, &ctl, o.scratch.p, sizeof(GeoControl)};
+    const AccScratch l = access_scratch(o);
+    const Batched b{"dxv_access", "rounds", kTimerAccess, N, &o.pending, o.batch, &o.batch, &o.rounds, &ctl, l.ctl, sizeof(GeoControl)};
     const int r = settle_batched(c, i, b,
         [&](uint32_t live, bool last) {
             account_flood(o, ctl, live, last);
@@ -394,7 +419,7 @@ int settle_access(dxv_ctx* c, uint32_t i)
             }
             return last;
         },
-        [&](hipStream_t fs) { return launch_access_batch(o.map.p, N, o.of, o.connectivity, o.cap, o.scratch.p, o.wantIntrusion, o.batch, o.rounds, fs); });
+        [&](hipStream_t fs) { return launch_access_batch(o.map.p, N, o.of, o.connectivity, o.cap, l, o.batch, o.rounds, fs); });
     return r ? r : finished;
 }
 
@@ -598,7 +623,7 @@ int dxv_isosurface_async(dxv_ctx* c, int source, float iso, int space)
     IsoParams p{};
     p.field = field; p.N = N; p.iso = iso; p.P = P; p.object = space == DXV_ISO_SPACE_OBJECT;
     memcpy(p.bound, c->bound, sizeof(p.bound));
-    iso_scratch_layout(f.iso.scratch.p, N, p);
+    DXV_HIP(c, carve_buffer(f.iso.scratch, p, iso_carve, N));
     unsigned long long* totals = cur_pinned(c).isoTotals;
     DXV_HIP(c, timer_begin(f.timers[kTimerIso], c->opt.events != 0, fs));
     DXV_HIP(c, launch_iso_count(p, fs));
@@ -655,7 +680,7 @@ int dxv_octree_async(dxv_ctx* c)
     DXV_HIP(c, f.oct.scratch.reserve(scratch, scratch, fs));
     OctParams p{};
     p.grid = f.grid.p;
-    oct_scratch_layout(f.oct.scratch.p, N, p);
+    DXV_HIP(c, carve_buffer(f.oct.scratch, p, oct_carve, N));
     const uint32_t L = p.L;
     unsigned long long* totals = cur_pinned(c).octTotals;
     DXV_HIP(c, timer_begin(f.timers[kTimerOctree], c->opt.events != 0, fs));
@@ -752,7 +777,7 @@ int dxv_components_async(dxv_ctx* c, int of, int connectivity)
     DXV_HIP(c, f.comp.labels.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
     CompParams p{};
     p.grid = f.grid.p; p.of = of; p.connectivity = (uint32_t)connectivity; p.labels = f.comp.labels.p;
-    comp_scratch_layout(f.comp.scratch.p, N, p);
+    DXV_HIP(c, carve_buffer(f.comp.scratch, p, comp_carve, N));
     unsigned long long* total = &cur_pinned(c).compTotal;
     DXV_HIP(c, timer_begin(f.timers[kTimerComponents], c->opt.events != 0, fs));
     DXV_HIP(c, launch_comp_label(p, fs));
@@ -812,7 +837,7 @@ int dxv_measure_async(dxv_ctx* c)
     f.comp.measure.version = 0;
     DXV_HIP(c, f.comp.measure.table.reserve((size_t)K + 1u, align256(measure_table_bytes(K)), fs));
     CompParams p{};
-    comp_scratch_layout(f.comp.scratch.p, N, p);
+    DXV_HIP(c, carve_buffer(f.comp.scratch, p, comp_carve, N));
     DXV_HIP(c, timer_begin(f.timers[kTimerMeasure], c->opt.events != 0, fs));
     if (!packed) DXV_HIP(c, launch_comp_pack(f.grid.p, N, f.comp.of, p.mask, fs));
     DXV_HIP(c, launch_measure(p.mask, N, (uint32_t)f.comp.connectivity, f.comp.labels.p, K, f.comp.measure.table.p, fs));
@@ -852,7 +877,7 @@ int dxv_thickness_async(dxv_ctx* c, int of, uint32_t cap_sq)
     DXV_HIP(c, f.thick.scratch.reserve(scratch, scratch, fs));
     ThickParams p{};
     p.of = of; p.cap = cap_sq; p.cull = (uint32_t)c->opt.thickcull; p.count = c->opt.thickstages ? 1u : 0u; p.W = f.thick.map.p; p.hist = f.thick.hist.p;
-    thickness_layout(f.thick.scratch.p, N, p);
+    DXV_HIP(c, carve_buffer(f.thick.scratch, p, thickness_carve, N));
     DXV_HIP(c, timer_begin(f.timers[kTimerThickness], c->opt.events != 0, fs));
     for (int stage = 0; stage < THICK_STAGES; ++stage) {
         const StageTimer t = stage_timer(c, f, kTimerThickStage0 + stage, c->opt.thickstages, fs);
@@ -861,7 +886,7 @@ int dxv_thickness_async(dxv_ctx* c, int of, uint32_t cap_sq)
         DXV_HIP(c, t.end());
     }
     PinnedFrame& pin = cur_pinned(c);
-    if (end_operator(c, f, fs, &f.timers[kTimerThickness], pin.thickCount, thickness_counters(p), sizeof(pin.thickCount))) return 1;
+    if (end_operator(c, f, fs, &f.timers[kTimerThickness], pin.thickCount, p.counters, sizeof(pin.thickCount))) return 1;
     f.thick.pending = true;
     f.thick.dim = N; f.thick.cap = cap_sq; f.thick.have = true; f.thick.version = f.gridVersion;
     return 0;
@@ -919,7 +944,7 @@ int dxv_partition_async(dxv_ctx* c, int of, uint32_t cap_sq, int want_throats)
     DXV_HIP(c, o.scratch.reserve(scratch, scratch, fs));
     PartParams p{};
     p.of = of; p.cap = cap_sq; p.prune = (uint32_t)c->opt.partprune; p.count = c->opt.partstages ? 1u : 0u; p.wantThroats = want_throats ? 1u : 0u;
-    partition_layout(o.scratch.p, N, p);
+    DXV_HIP(c, carve_buffer(o.scratch, p, partition_carve, N));
     PinnedFrame& pin = cur_pinned(c);
     auto timer_of = [&](int stage) { return stage_timer(c, f, kTimerPartStage0 + stage, c->opt.partstages, fs); };
     DXV_HIP(c, timer_begin(f.timers[kTimerPartition], c->opt.events != 0, fs));
@@ -928,7 +953,7 @@ int dxv_partition_async(dxv_ctx* c, int of, uint32_t cap_sq, int want_throats)
         DXV_HIP(c, launch_partition_stage(f.grid.p, p, stage, fs));
         DXV_HIP(c, timer_of(stage).end());
     }
-    DXV_HIP(c, hipMemcpyAsync(pin.partTotals, partition_totals(p), sizeof(pin.partTotals), hipMemcpyDeviceToHost, fs));
+    DXV_HIP(c, hipMemcpyAsync(pin.partTotals, p.totals, sizeof(pin.partTotals), hipMemcpyDeviceToHost, fs));
     DXV_HIP(c, hipStreamSynchronize(fs));
     const uint32_t K = (uint32_t)pin.partTotals[0];
     const unsigned long long faces = want_throats && K ? pin.partTotals[1] : 0ull;
@@ -937,7 +962,7 @@ int dxv_partition_async(dxv_ctx* c, int of, uint32_t cap_sq, int want_throats)
     if (K) DXV_HIP(c, o.table.reserve(K, align256((size_t)K * sizeof(PartRegion)), fs));
     DXV_HIP(c, o.work.reserve(work, work, fs));
     p.labels = o.labels.p; p.table = reinterpret_cast<PartRegion*>(o.table.p);
-    partition_work_layout(o.work.p, K, faces, p);
+    DXV_HIP(c, carve_buffer(o.work, p, partition_work_carve, K, faces));
     DXV_HIP(c, timer_of(PART_STAGE_REGIONS).begin());
     DXV_HIP(c, launch_partition_stage(f.grid.p, p, PART_STAGE_REGIONS, fs));
     DXV_HIP(c, timer_of(PART_STAGE_REGIONS).end());
@@ -945,7 +970,7 @@ int dxv_partition_async(dxv_ctx* c, int of, uint32_t cap_sq, int want_throats)
     DXV_HIP(c, timer_of(PART_STAGE_THROATS).begin());
     if (faces) {
         DXV_HIP(c, launch_partition_pairs(p, fs));
-        DXV_HIP(c, hipMemcpyAsync(pin.partPairs, partition_pair_total(p), sizeof(pin.partPairs), hipMemcpyDeviceToHost, fs));
+        DXV_HIP(c, hipMemcpyAsync(pin.partPairs, p.pairTotal, sizeof(pin.partPairs), hipMemcpyDeviceToHost, fs));
         DXV_HIP(c, hipStreamSynchronize(fs));
         T = (uint32_t)pin.partPairs[0];
         if (T) {
@@ -954,7 +979,7 @@ int dxv_partition_async(dxv_ctx* c, int of, uint32_t cap_sq, int want_throats)
         }
     }
     DXV_HIP(c, timer_of(PART_STAGE_THROATS).end());
-    if (end_operator(c, f, fs, &f.timers[kTimerPartition], pin.partCount, partition_counters(p), sizeof(pin.partCount))) return 1;
+    if (end_operator(c, f, fs, &f.timers[kTimerPartition], pin.partCount, p.counters, sizeof(pin.partCount))) return 1;
     o.pending = true;
     o.dim = N; o.cap = cap_sq; o.of = of; o.hasThroats = want_throats != 0; o.regions = K; o.throatCount = T; o.faces = faces;
     o.have = true; o.version = f.gridVersion;
@@ -1025,7 +1050,7 @@ int dxv_skeleton_async(dxv_ctx* c, const void* device_weights)
     DXV_HIP(c, o.labels.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
     SkelParams p{};
     p.grid = f.grid.p; p.weights = static_cast<const uint32_t*>(device_weights); p.labels = o.labels.p;
-    skel_scratch_layout(o.scratch.p, N, p);
+    DXV_HIP(c, carve_buffer(o.scratch, p, skel_carve, N));
     unsigned long long* totals = cur_pinned(c).skelTotals;
     DXV_HIP(c, timer_begin(f.timers[kTimerSkeleton], c->opt.events != 0, fs));
     DXV_HIP(c, launch_skel_label(p, fs));
@@ -1075,7 +1100,7 @@ const void* dxv_skeleton_branches_device_ptr(const dxv_ctx* c) { return product_
 size_t dxv_skeleton_branches_bytes(const dxv_ctx* c) { return product_bytes(c, "dxv_skeleton_branches_bytes", kSkelBranches); }
 int dxv_skeleton_branches_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_skeleton_branches_download", kSkelBranches, host, bytes); }
 
-// The selected frame's grid edited from its skeleton (skeleton.hip: k_skel_prune_mark, k_skel_prune_edit), in place, enqueued on the frame's
+// The selected frame's grid edited from its skeleton (skeleton.hip: k_skel_prune_mark; dxv_label.h: k_label_edit), in place, enqueued on the frame's
 // stream behind whatever it holds -- under dxv_render_async's host-wait rule and dxv_fill_async's rules for the grid.  Labels and tables are what
 // it reads: dxv_trim has left them.  The two counters go into page-locked words and are read where the frame is next synchronised.
 int dxv_skeleton_prune_async(dxv_ctx* c, uint32_t max_len345)
@@ -1091,11 +1116,13 @@ int dxv_skeleton_prune_async(dxv_ctx* c, uint32_t max_len345)
     const uint32_t K = o.nodeCount, B = o.branchCount;
     const size_t work = skel_prune_bytes(K, B);
     DXV_HIP(c, o.work.reserve(work, work, fs));
+    SkelPruneWork w{};
+    DXV_HIP(c, carve_buffer(o.work, w, skel_prune_carve, K, B));
     edited_in_place(f);                                                 // (this skeleton is stale with the rest)
-    DXV_HIP(c, launch_skel_prune(f.grid.p, o.dim, o.labels.p, reinterpret_cast<const SkelNode*>(o.nodes.p), K, reinterpret_cast<const SkelBranch*>(o.branches.p), B, max_len345,
-                                 o.work.p, fs));
+    DXV_HIP(c, launch_skel_prune(f.grid.p, o.dim, o.labels.p, reinterpret_cast<const SkelNode*>(o.nodes.p), K, reinterpret_cast<const SkelBranch*>(o.branches.p), B, max_len345, w,
+                                 fs));
     PinnedFrame& pin = cur_pinned(c);
-    if (end_operator(c, f, fs, nullptr, pin.skelPrune, skel_prune_counters(o.work.p), sizeof(pin.skelPrune))) return 1;
+    if (end_operator(c, f, fs, nullptr, pin.skelPrune, w.counters, sizeof(pin.skelPrune))) return 1;
     o.prune.pending = true;
     return 0;
 }
@@ -1134,14 +1161,16 @@ int dxv_geodesic_async(dxv_ctx* c, int of, int metric, int seeds_kind, const voi
     f.geo.version = 0; f.geo.have = false;
     DXV_HIP(c, f.geo.map.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
     DXV_HIP(c, f.geo.scratch.reserve(scratch, scratch, fs));
+    GeoScratch l{};
+    DXV_HIP(c, carve_buffer(f.geo.scratch, l, geodesic_carve, N));
     const void* deviceSeeds;
     if (upload_seeds(c, f.geo, seeds_kind, seeds, seed_count, fs, &deviceSeeds)) return 1;
     f.geo.metric = metric; f.geo.limit = limit;
     begin_flood(f.geo, c->opt.georounds, kGeoRoundsDefault);
     DXV_HIP(c, timer_begin(f.timers[kTimerGeodesic], c->opt.events != 0, fs));
-    DXV_HIP(c, launch_geodesic_init(f.grid.p, N, of, seeds_kind, deviceSeeds, seed_count, f.geo.map.p, f.geo.scratch.p, fs));
-    DXV_HIP(c, launch_geodesic_batch(f.geo.map.p, N, metric, limit, f.geo.scratch.p, f.geo.batch, 0u, fs));
-    if (end_operator(c, f, fs, &f.timers[kTimerGeodesic], &cur_pinned(c).geoCtl, f.geo.scratch.p, sizeof(GeoControl))) return 1;
+    DXV_HIP(c, launch_geodesic_init(f.grid.p, N, of, seeds_kind, deviceSeeds, seed_count, f.geo.map.p, l, fs));
+    DXV_HIP(c, launch_geodesic_batch(f.geo.map.p, N, metric, limit, l, f.geo.batch, 0u, fs));
+    if (end_operator(c, f, fs, &f.timers[kTimerGeodesic], &cur_pinned(c).geoCtl, l.ctl, sizeof(GeoControl))) return 1;
     f.geo.pending = true;
     f.geo.dim = N; f.geo.have = true; f.geo.version = f.gridVersion;
     return 0;
@@ -1201,14 +1230,16 @@ int dxv_access_async(dxv_ctx* c, int of, int connectivity, uint32_t cap_sq, int 
         DXV_HIP(c, o.histI.reserve(kThickMaxCapSq + 1u, align256(thickness_histogram_bytes(kThickMaxCapSq)), fs));
     }
     DXV_HIP(c, o.scratch.reserve(scratch, scratch, fs));
+    AccScratch l{};
+    DXV_HIP(c, carve_buffer(o.scratch, l, access_carve, N, intrusion));
     const void* deviceSeeds;
     if (upload_seeds(c, o, seeds_kind, seeds, seed_count, fs, &deviceSeeds)) return 1;
     o.dim = N; o.cap = cap_sq; o.of = of; o.connectivity = connectivity; o.wantIntrusion = intrusion; o.cull = (uint32_t)c->opt.thickcull;
     begin_flood(o, c->opt.accessrounds, kAccRoundsDefault);
     DXV_HIP(c, timer_begin(f.timers[kTimerAccess], c->opt.events != 0, fs));
-    DXV_HIP(c, launch_access_init(f.grid.p, N, of, cap_sq, seeds_kind, deviceSeeds, seed_count, o.map.p, o.scratch.p, intrusion, fs));
-    DXV_HIP(c, launch_access_batch(o.map.p, N, of, connectivity, cap_sq, o.scratch.p, intrusion, o.batch, 0u, fs));
-    if (end_operator(c, f, fs, &f.timers[kTimerAccess], &cur_pinned(c).accCtl, o.scratch.p, sizeof(GeoControl))) return 1;
+    DXV_HIP(c, launch_access_init(f.grid.p, N, of, cap_sq, seeds_kind, deviceSeeds, seed_count, o.map.p, l, fs));
+    DXV_HIP(c, launch_access_batch(o.map.p, N, of, connectivity, cap_sq, l, o.batch, 0u, fs));
+    if (end_operator(c, f, fs, &f.timers[kTimerAccess], &cur_pinned(c).accCtl, l.ctl, sizeof(GeoControl))) return 1;
     o.pending = true;
     o.have = true; o.version = f.gridVersion;
     return 0;
@@ -1285,7 +1316,7 @@ int dxv_geodesic_path(dxv_ctx* c, uint32_t target, uint32_t* host_path, uint32_t
     return 0;
 }
 
-// The selected frame's grid edited from its labels (components.hip: k_comp_keep, k_comp_edit), in place, enqueued on the frame's stream behind
+// The selected frame's grid edited from its labels (components.hip: k_comp_keep; dxv_label.h: k_label_edit), in place, enqueued on the frame's stream behind
 // whatever it holds -- under dxv_render_async's host-wait rule and dxv_fill_async's rules for the grid.  The four counters go into page-locked
 // words and are read where the frame is next synchronised.
 int dxv_components_select_async(dxv_ctx* c, int rule, uint32_t arg)
@@ -1303,10 +1334,12 @@ int dxv_components_select_async(dxv_ctx* c, int rule, uint32_t arg)
     const uint32_t K = f.comp.count;
     const size_t work = comp_select_bytes(K);
     DXV_HIP(c, f.comp.work.reserve(work, work, fs));
+    CompSelectWork w{};
+    DXV_HIP(c, carve_buffer(f.comp.work, w, comp_select_carve, K));
     edited_in_place(f);                                                 // (these labels are stale with the rest)
-    DXV_HIP(c, launch_comp_select(f.grid.p, f.comp.dim, f.comp.of, f.comp.labels.p, reinterpret_cast<const CompRecord*>(f.comp.table.p), K, rule, arg, f.comp.work.p, fs));
+    DXV_HIP(c, launch_comp_select(f.grid.p, f.comp.dim, f.comp.of, f.comp.labels.p, reinterpret_cast<const CompRecord*>(f.comp.table.p), K, rule, arg, w, fs));
     PinnedFrame& pin = cur_pinned(c);
-    if (end_operator(c, f, fs, nullptr, pin.compSel, comp_select_counters(f.comp.work.p), sizeof(pin.compSel))) return 1;
+    if (end_operator(c, f, fs, nullptr, pin.compSel, w.counters, sizeof(pin.compSel))) return 1;
     f.comp.select.pending = true; f.comp.select.rule = rule; f.comp.select.components = K;
     return 0;
 }
@@ -1338,14 +1371,16 @@ int dxv_fill_async(dxv_ctx* c, int what)
     const uint32_t N = f.grid_dim;
     const size_t scratch = fill_scratch_bytes(N);
     DXV_HIP(c, f.fill.scratch.reserve(scratch, scratch, fs));
+    FillScratch l{};
+    DXV_HIP(c, carve_buffer(f.fill.scratch, l, fill_carve, N));
     f.fill.what = what;
     f.fill.batch = c->opt.fillrounds ? (uint32_t)c->opt.fillrounds : kFillRoundsDefault;
     f.fill.rounds = 0;
     edited_in_place(f);
     DXV_HIP(c, timer_begin(f.timers[kTimerFill], c->opt.events != 0, fs));
-    DXV_HIP(c, launch_fill(f.grid.p, N, what, f.fill.scratch.p, f.fill.batch, true, fs));
+    DXV_HIP(c, launch_fill(f.grid.p, N, what, l, f.fill.batch, true, fs));
     PinnedFrame& pin = cur_pinned(c);
-    if (end_operator(c, f, fs, &f.timers[kTimerFill], pin.fillCtl, fill_control(f.fill.scratch.p, N), sizeof(pin.fillCtl))) return 1;
+    if (end_operator(c, f, fs, &f.timers[kTimerFill], pin.fillCtl, l.ctl, sizeof(pin.fillCtl))) return 1;
     f.fill.pending = true;
     return 0;
 }
@@ -1378,11 +1413,13 @@ int dxv_morph_async(dxv_ctx* c, int op, uint32_t radius_sq)
     const int form = morph_form(radius_sq, c->opt.morphform);
     const size_t scratch = morph_scratch_bytes(N, op, radius_sq, form);
     DXV_HIP(c, f.morph.scratch.reserve(scratch, scratch, fs));
+    MorphScratch l{};
+    DXV_HIP(c, carve_buffer(f.morph.scratch, l, morph_carve, N, op, radius_sq, form));
     edited_in_place(f);
     DXV_HIP(c, timer_begin(f.timers[kTimerMorph], c->opt.events != 0, fs));
-    DXV_HIP(c, launch_morph(f.grid.p, N, op, radius_sq, form, f.morph.scratch.p, fs));
+    DXV_HIP(c, launch_morph(f.grid.p, N, op, radius_sq, form, l, fs));
     PinnedFrame& pin = cur_pinned(c);
-    if (end_operator(c, f, fs, &f.timers[kTimerMorph], pin.morphCount, morph_counters(f.morph.scratch.p), sizeof(pin.morphCount))) return 1;
+    if (end_operator(c, f, fs, &f.timers[kTimerMorph], pin.morphCount, l.counters, sizeof(pin.morphCount))) return 1;
     f.morph.pending = true;
     return 0;
 }
@@ -1416,6 +1453,8 @@ int dxv_thin_async(dxv_ctx* c, int kind, uint32_t max_iterations)
     if (begin_operator(c, &fs)) return 1;
     const size_t scratch = thin_scratch_bytes(N);
     DXV_HIP(c, f.thin.scratch.reserve(scratch, scratch, fs));
+    ThinScratch l{};
+    DXV_HIP(c, carve_buffer(f.thin.scratch, l, thin_carve, N));
     f.thin.kind = kind;
     f.thin.batch = c->opt.thinrounds ? (uint32_t)c->opt.thinrounds : kThinRoundsDefault;
     f.thin.bounded = max_iterations != 0u;
@@ -1426,8 +1465,8 @@ int dxv_thin_async(dxv_ctx* c, int kind, uint32_t max_iterations)
     f.thin.converged = false;
     edited_in_place(f);
     DXV_HIP(c, timer_begin(f.timers[kTimerThin], c->opt.events != 0, fs));
-    DXV_HIP(c, launch_thin(f.grid.p, N, kind, f.thin.scratch.p, f.thin.inBatch, true, fs));
-    if (end_operator(c, f, fs, &f.timers[kTimerThin], &cur_pinned(c).thinCtl, f.thin.scratch.p, sizeof(ThinControl))) return 1;
+    DXV_HIP(c, launch_thin(f.grid.p, N, kind, l, f.thin.inBatch, true, fs));
+    if (end_operator(c, f, fs, &f.timers[kTimerThin], &cur_pinned(c).thinCtl, l.ctl, sizeof(ThinControl))) return 1;
     f.thin.pending = true;
     return 0;
 }

@@ -40,7 +40,7 @@ struct SkelBranch {
 };
 static_assert(sizeof(SkelNode) == 32 && sizeof(SkelBranch) == 48, "the tables' records are 32 and 48 bytes");
 // what the stats pass gathers per node with 32-bit integer atomics before the table is packed (a branch gathers into its own record)
-struct SkelNodeStats { uint32_t voxels, degree, flags, lo[3], hi[3], w_max; };
+struct SkelNodeStats : BoxStats { uint32_t degree, w_max; };
 
 DXV_HD bool skel_valid(uint32_t N) { return N >= 2u && N <= kSkelMaxN && !(N & 1u); }
 
@@ -158,5 +158,51 @@ DXV_HD uint64_t skel_len345(const SkelBranch& r) { return 3ull * r.steps[0] + 4u
 DXV_HD bool skel_pruned(const SkelBranch& r, uint32_t maxLen345) { return (r.flags & SKEL_BRANCH_SPUR) && skel_len345(r) <= maxLen345; }
 // the tip of a spur (exactly one of a, b is one)
 DXV_HD uint32_t skel_spur_tip(const SkelBranch& r, const SkelNode* nodes) { return skel_tip(nodes[r.a - 1u]) ? r.a : r.b; }
+
+// ---- what skeleton.hip's launches work on: labels = N^3 uint32, nodes = 32 K bytes and branches = 48 B bytes are the caller's, stats = K
+// SkelNodeStats of work.  The grid is only read. ----
+struct SkelParams {
+    const uint8_t* grid;    // N^3 bytes, element (iz * N + iy) * N + ix; a voxel is a member iff its byte is non-zero
+    uint32_t N;
+    const uint32_t* weights;      // N^3 uint32 of the caller's, or nullptr
+    uint32_t* labels;       // parent during the build, then the labels
+    uint64_t *member, *node, *curve, *ends;     // skel_carve fills these and the five below
+    uint64_t *nodeRoots, *curveRoots;
+    uint32_t* counts;
+    unsigned long long* sums;
+    unsigned long long* totals;   // {K, B, end voxels, curve voxels, junction voxels}
+    SkelNodeStats* stats;
+    SkelNode* nodes;
+    SkelBranch* branches;
+};
+// scratch of one build: the member, node, curve and end masks (a bit per voxel each; node, curve and ends one behind the other: one clear), the two
+// kinds' root bits in linear order, a pair of counts per 64 voxels, the scan's block sums, {K, B, end voxels, curve voxels, junction voxels}
+inline void skel_carve(Carve& c, uint32_t N, SkelParams& p)
+{
+    const size_t words = comp_linear_words(N);
+    p.N = N;
+    p.member = c.take<uint64_t>(fill_mask_words(N));
+    p.node = c.take<uint64_t>(fill_mask_words(N));
+    p.curve = c.take<uint64_t>(fill_mask_words(N));
+    p.ends = c.take<uint64_t>(fill_mask_words(N));
+    p.nodeRoots = c.take<uint64_t>(words);
+    p.curveRoots = c.take<uint64_t>(words);
+    p.counts = c.take<uint32_t>(2u * words);
+    p.sums = c.take<unsigned long long>(2u * (size_t)scan_blocks(words));
+    p.totals = c.take<unsigned long long>(5);
+}
+inline size_t skel_scratch_bytes(uint32_t N) { return carved_bytes<SkelParams>(skel_carve, N); }
+
+// work of dxv_skeleton_prune: {branches removed, voxels removed}, then a flag per branch and per node; bytes: all of it, cleared by the launch
+struct SkelPruneWork { unsigned long long* counters; uint8_t *goB, *goN; size_t bytes; };
+inline void skel_prune_carve(Carve& c, uint32_t K, uint32_t B, SkelPruneWork& w)
+{
+    const size_t from = c.used();
+    w.counters = c.take<unsigned long long>(2);
+    w.goB = c.take<uint8_t>(B);
+    w.goN = c.take<uint8_t>(K);
+    w.bytes = c.used() - from;
+}
+inline size_t skel_prune_bytes(uint32_t K, uint32_t B) { return carved_bytes<SkelPruneWork>(skel_prune_carve, K, B); }
 
 } // namespace dxv

@@ -17,6 +17,7 @@
 #include <math.h>
 #include <stddef.h>
 #include "dxv_types.h"
+#include "dxv_distance.h"
 
 namespace dxv {
 
@@ -100,5 +101,39 @@ template <class Raise> DXV_HD void thick_paint_disc(uint32_t N, uint32_t x, uint
         if (rx >= side) { rx -= side; ++ry; }
     }
 }
+
+// What thickness.hip's stages work on: W = N^3 uint32 and hist = cap + 1 uint64 are the caller's, everything below them is scratch.
+struct ThickParams {
+    uint32_t N;
+    int of;                           // DXV_COMP_SOLID / DXV_COMP_EMPTY
+    uint32_t cap, cull;               // cap_sq; option thickcull
+    uint32_t count;                   // 1: the paint counts what it tests and sends (option thickstages)
+    uint32_t* W;
+    unsigned long long* hist;
+    int32_t *F, *G;                   // thickness_carve fills these and the ones below: the grid's field; E's field, then Top's
+    uint32_t* B;                      // a byte per voxel: E, then Top, then the work items of the voxel as a centre
+    unsigned long long* sums;         // per block of 1024 voxels {centres, items} in front of it, then the two totals and the paint's two counters
+    uint8_t* passes;                  // distance_scratch_bytes(N)
+    uint32_t *centres, *firstItem;    // the compacted centres (in G) and every centre's first item within its block (in the passes' scratch)
+    const unsigned long long* counters;         // those four words behind the sums, for the host: {centres painted, work items, voxels tested, atomics sent},
+                                                // the first two valid behind the select
+};
+inline uint32_t thick_blocks(uint32_t N) { return (uint32_t)(((size_t)N * N * N + kThickBlock - 1u) / kThickBlock); }
+// scratch of one call: F and G (4 B per voxel each), B (1 B), the blocks' sums and the totals, the scratch of the fields' passes (6 B per voxel) --
+// whose front holds the centres' first items once the last field is made; the centre list goes into G once the select has read it
+inline void thickness_carve(Carve& c, uint32_t N, ThickParams& p)
+{
+    const size_t voxels = (size_t)N * N * N;
+    p.N = N;
+    p.F = c.take<int32_t>(voxels);
+    p.G = c.take<int32_t>(voxels);
+    p.centres = reinterpret_cast<uint32_t*>(p.G);
+    p.B = reinterpret_cast<uint32_t*>(c.take<uint8_t>(voxels));
+    p.sums = c.take<unsigned long long>(2u * ((size_t)thick_blocks(N) + 2u));
+    p.counters = carve_at<const unsigned long long>(p.sums, 2u * (size_t)thick_blocks(N));
+    p.passes = c.take_bytes(distance_scratch_bytes(N));
+    p.firstItem = reinterpret_cast<uint32_t*>(p.passes);
+}
+inline size_t thickness_scratch_bytes(uint32_t N) { return carved_bytes<ThickParams>(thickness_carve, N); }
 
 } // namespace dxv

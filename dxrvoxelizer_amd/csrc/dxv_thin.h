@@ -160,4 +160,26 @@ DXV_HD uint32_t thin_batch(uint32_t rounds, uint32_t left)
     return left && left < rounds ? left : rounds;
 }
 
+// ---- scratch of thin.hip ----
+// the batch's control block -- word k != 0: iteration k removed something; the batch has reached the fixed point exactly when one of its words is
+// 0 -- and the voxels removed since the first batch
+struct ThinControl {
+    uint32_t live[64];                // (kThinMaxRounds)
+    unsigned long long removed;
+    unsigned long long written[2];    // the write-back's own counters: nobody reads them
+};
+constexpr size_t kThinControlBytes = 512;
+static_assert(sizeof(ThinControl) <= kThinControlBytes && sizeof(ThinControl::live) == sizeof(uint32_t) * kThinMaxRounds, "the control block has a word per iteration of a batch");
+// the control block, S, S as it was, B, the loose bits: 3 1/8 bits per voxel
+struct ThinScratch { ThinControl* ctl; uint64_t *S, *was, *B, *loose; };
+inline void thin_carve(Carve& c, uint32_t N, ThinScratch& l)
+{
+    l.ctl = reinterpret_cast<ThinControl*>(c.take_bytes(kThinControlBytes));
+    l.S = c.take<uint64_t>(fill_mask_words(N));
+    l.was = c.take<uint64_t>(fill_mask_words(N));
+    l.B = c.take<uint64_t>(fill_mask_words(N));
+    l.loose = c.take<uint64_t>(fill_loose_words(N));
+}
+inline size_t thin_scratch_bytes(uint32_t N) { return carved_bytes<ThinScratch>(thin_carve, N); }
+
 } // namespace dxv

@@ -6,15 +6,11 @@
 // A batch is `rounds` rounds behind one another.  Whether a round changed a word is word `round` of the batch's control block; the
 // kernels of a round return at once when the round before them left its word 0, so a batch costs what its live rounds cost, and the
 // host reads the block where the frame is next synchronised (dxv_products.hip: settle_fill).  No workgroup waits for another, every
-// loop is bounded by N; no LDS, no scratch memory.
+// loop is bounded by N; no LDS, no scratch memory.  The masks and the control block are laid out by fill_carve (dxv_fill.h).
 #include "dxv_device.h"
 #include "dxv_fill.h"
 
 namespace dxv {
-
-static size_t fill_mask_bytes(uint32_t N) { return align256(fill_mask_words(N) * sizeof(uint64_t)); }
-size_t fill_scratch_bytes(uint32_t N) { return 2 * fill_mask_bytes(N) + sizeof(uint32_t) * kFillMaxRounds; }
-uint32_t* fill_control(uint8_t* scratch, uint32_t N) { return reinterpret_cast<uint32_t*>(scratch + 2 * fill_mask_bytes(N)); }
 
 // one thread per byte of a mask row (W * 8 of them, the ones behind the row's end are 0)
 __global__ __launch_bounds__(256) void k_fill_pack(const uint8_t* __restrict__ grid, uint32_t N, uint8_t* __restrict__ freeMask, uint8_t* __restrict__ reached)
@@ -71,14 +67,14 @@ __global__ __launch_bounds__(256) void k_fill_write(const uint8_t* __restrict__ 
 }
 
 // One batch: (first: the pack,) `rounds` rounds, the write-back.  The control block is cleared in front of the rounds.
-hipError_t launch_fill(uint8_t* grid, uint32_t N, int what, uint8_t* scratch, uint32_t rounds, bool first, hipStream_t s)
+hipError_t launch_fill(uint8_t* grid, uint32_t N, int what, const FillScratch& l, uint32_t rounds, bool first, hipStream_t s)
 {
     const uint32_t W = fill_row_words(N);
-    uint8_t* freeMask = scratch;
-    uint8_t* reached = scratch + fill_mask_bytes(N);
-    uint32_t* ctl = fill_control(scratch, N);
-    const uint64_t* f = reinterpret_cast<const uint64_t*>(freeMask);
-    uint64_t* r = reinterpret_cast<uint64_t*>(reached);
+    const uint64_t* f = l.freeMask;
+    uint64_t* r = l.reached;
+    uint8_t* freeMask = reinterpret_cast<uint8_t*>(l.freeMask);
+    uint8_t* reached = reinterpret_cast<uint8_t*>(l.reached);
+    uint32_t* ctl = l.ctl;
     const size_t maskBytes = (size_t)N * N * W * 8u, rows = (size_t)N * N;
     const uint32_t byteBlocks = (uint32_t)((maskBytes + 255) / 256), columns = N * W;
     if (rounds < 1u) rounds = 1u;

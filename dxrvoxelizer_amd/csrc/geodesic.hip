@@ -13,7 +13,7 @@
 // A tile reads its neighbours' words while they may be lowering them: every word ever stored is the length of a real path and words only fall,
 // so a stale word is a valid upper bound, and whoever lowers a word on a tile's border flags the tiles beyond it for the next round -- the
 // chain stops only at the fixed point, which is unique.  No workgroup waits for another, every loop is bounded, launch sizes
-// depend on N alone; no scratch memory.
+// depend on N alone; no scratch memory.  Control block, flags and queue are laid out by geodesic_carve (dxv_geodesic.h).
 #include "dxv_device.h"
 #include "dxv_geodesic.h"
 
@@ -21,21 +21,6 @@ namespace dxv {
 
 constexpr uint32_t kGeoRoundBlocks = 8192;        // workgroups (of one wave) a round is launched with at the most, whatever its queue holds
 constexpr uint32_t kGeoTallyBlocks = 1024;        // ... the tally, of four waves
-
-static uint32_t geo_tiles(uint32_t N) { return geo_tiles_side(N) * geo_tiles_side(N) * geo_tiles_side(N); }
-
-struct GeoLayout { GeoControl* ctl; uint8_t* flags[2]; uint32_t* queue; };
-static GeoLayout geo_layout(uint8_t* scratch, uint32_t N)
-{
-    const size_t flags = align256(geo_tiles(N));
-    GeoLayout l;
-    l.ctl = reinterpret_cast<GeoControl*>(scratch);
-    l.flags[0] = scratch + align256(sizeof(GeoControl));
-    l.flags[1] = l.flags[0] + flags;
-    l.queue = reinterpret_cast<uint32_t*>(l.flags[1] + flags);
-    return l;
-}
-size_t geodesic_scratch_bytes(uint32_t N) { return align256(sizeof(GeoControl)) + 2u * align256(geo_tiles(N)) + align256((size_t)geo_tiles(N) * sizeof(uint32_t)); }
 
 // one thread per voxel
 __global__ __launch_bounds__(256) void k_geo_init(const uint8_t* __restrict__ grid, uint32_t N, int of, int seedsKind, const uint8_t* __restrict__ seedMask, uint32_t* __restrict__ map,
@@ -175,14 +160,13 @@ __global__ __launch_bounds__(64) void k_geo_path(const uint32_t* __restrict__ ma
 
 static bool geo_valid(uint32_t N, int metric) { return N >= 1u && N <= kGeoMaxN && (metric == GEO_FACES || metric == GEO_CHAMFER) && geo_fits(N, metric); }
 
-hipError_t launch_geodesic_init(const uint8_t* grid, uint32_t N, int of, int seedsKind, const void* seeds, uint32_t seedCount, uint32_t* map, uint8_t* scratch, hipStream_t s)
+hipError_t launch_geodesic_init(const uint8_t* grid, uint32_t N, int of, int seedsKind, const void* seeds, uint32_t seedCount, uint32_t* map, const GeoScratch& l, hipStream_t s)
 {
-    if (!grid || !map || !scratch || N < 1u || N > kGeoMaxN || (of != GEO_SOLID && of != GEO_EMPTY) || seedsKind < GEO_SEEDS_BORDER || seedsKind > GEO_SEEDS_MASK ||
+    if (!grid || !map || !l.flags[0] || N < 1u || N > kGeoMaxN || (of != GEO_SOLID && of != GEO_EMPTY) || seedsKind < GEO_SEEDS_BORDER || seedsKind > GEO_SEEDS_MASK ||
         (seedsKind != GEO_SEEDS_BORDER && !seeds && (seedsKind == GEO_SEEDS_MASK || seedCount)))
         return hipErrorInvalidValue;
-    const GeoLayout l = geo_layout(scratch, N);
     const size_t voxels = (size_t)N * N * N;
-    const hipError_t e = hipMemsetAsync(l.flags[0], 0, 2u * align256(geo_tiles(N)), s);
+    const hipError_t e = hipMemsetAsync(l.flags[0], 0, l.flagBytes, s);
     if (e != hipSuccess) return e;
     k_geo_init<<<(uint32_t)((voxels + 255u) / 256u), 256, 0, s>>>(grid, N, of, seedsKind, seedsKind == GEO_SEEDS_MASK ? static_cast<const uint8_t*>(seeds) : nullptr, map, l.flags[0]);
     if (seedsKind == GEO_SEEDS_LIST && seedCount) k_geo_seed_list<<<(seedCount + 255u) / 256u, 256, 0, s>>>(static_cast<const uint32_t*>(seeds), seedCount, N, map, l.flags[0]);
@@ -191,10 +175,9 @@ hipError_t launch_geodesic_init(const uint8_t* grid, uint32_t N, int of, int see
 
 // One batch: `rounds` rounds, the first of them round `base` of the call (the flags a round reads are those of its number's parity), then the
 // tally.  Control block and tally are cleared in front of the rounds.
-hipError_t launch_geodesic_batch(uint32_t* map, uint32_t N, int metric, uint32_t limit, uint8_t* scratch, uint32_t rounds, uint32_t base, hipStream_t s)
+hipError_t launch_geodesic_batch(uint32_t* map, uint32_t N, int metric, uint32_t limit, const GeoScratch& l, uint32_t rounds, uint32_t base, hipStream_t s)
 {
-    if (!map || !scratch || !geo_valid(N, metric)) return hipErrorInvalidValue;
-    const GeoLayout l = geo_layout(scratch, N);
+    if (!map || !l.ctl || !l.flags[0] || !l.flags[1] || !l.queue || !geo_valid(N, metric)) return hipErrorInvalidValue;
     const uint32_t tiles = geo_tiles(N), voxels = N * N * N;
     if (rounds < 1u) rounds = 1u;
     if (rounds > kGeoMaxRounds) rounds = kGeoMaxRounds;

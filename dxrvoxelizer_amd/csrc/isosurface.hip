@@ -9,7 +9,8 @@
 //   k_iso_emit       the count kernel's mapping again: a cell's vertex goes to the word's base + the popcount of the lower lanes' bits,
 //                    a neighbour cell's number comes from that cell's word and base, the cell's up to three quads go to the word's quad
 //                    base + the lane's rank among the wave's owned crossing edges.
-// No kernel here uses scratch memory or LDS, every loop is bounded and no workgroup waits for another.
+// No kernel here uses scratch memory or LDS, every loop is bounded and no workgroup waits for another.  The scratch is laid out by iso_carve
+// (dxv_isosurface.h).
 #include "dxv_device.h"
 #include "dxv_isosurface.h"
 
@@ -86,21 +87,6 @@ __global__ __launch_bounds__(256) void k_iso_emit(IsoParams p, size_t words)
         for (int k = 0; k < 6; ++k) dst[k] = out[k];
         ++quad;
     }
-}
-
-// scratch of one extraction: the words' masks, their counts / bases, the scan's block sums, the two totals
-size_t iso_scratch_bytes(uint32_t N)
-{
-    const size_t words = iso_words(N);
-    return words * sizeof(uint64_t) + words * sizeof(IsoCounts) + 2 * (size_t)scan_blocks(words) * sizeof(unsigned long long) + 2 * sizeof(unsigned long long);
-}
-void iso_scratch_layout(uint8_t* scratch, uint32_t N, IsoParams& p)
-{
-    const size_t words = iso_words(N);
-    p.masks = reinterpret_cast<uint64_t*>(scratch);
-    p.bases = reinterpret_cast<IsoCounts*>(scratch + words * sizeof(uint64_t));
-    p.sums = reinterpret_cast<unsigned long long*>(scratch + words * (sizeof(uint64_t) + sizeof(IsoCounts)));
-    p.totals = p.sums + 2 * (size_t)scan_blocks(words);
 }
 
 // count + scan: p.masks and p.bases (what stands in front of every word) and p.totals = {vertices, quads} of the whole mesh

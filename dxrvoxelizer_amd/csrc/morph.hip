@@ -12,14 +12,11 @@
 //   k_morph_threshold  field and grid -> bytes 0 / 1 in place, eight voxels per thread, a store only where a byte changes, the same counters
 // Lanes of a wave sit on adjacent words -- adjacent x, then adjacent y -- in every kernel, and the offsets of the ball are the same in every
 // lane, so every load and store is a whole-wave access of consecutive words.  No loop waits for another workgroup, every loop is bounded
-// by the radius; no LDS, no scratch memory.
+// by the radius; no LDS, no scratch memory.  The counters and either form's buffers are laid out by morph_carve (dxv_morph.h).
 #include "dxv_device.h"
 #include "dxv_morph.h"
 
 namespace dxv {
-
-static size_t morph_mask_bytes(uint32_t N) { return align256(fill_mask_words(N) * sizeof(uint64_t)); }
-static size_t morph_loose_bytes(uint32_t N) { return align256((fill_mask_words(N) * 8u + 63u) / 64u * sizeof(uint64_t)); }
 
 // one thread per byte of a mask row (W * 8 of them, the ones behind the row's end are 0); every lane stays for the ballot
 __global__ __launch_bounds__(256) void k_morph_pack(const uint8_t* __restrict__ grid, uint32_t N, int complement, uint8_t* __restrict__ mask, uint64_t* __restrict__ loose)
@@ -147,55 +144,38 @@ void launch_morph_write(const uint8_t* was, const uint8_t* now, const uint64_t* 
     k_morph_write<<<(uint32_t)((fill_mask_words(N) * 8u + 255u) / 256u), 256, 0, s>>>(was, 0, now, loose, N, grid, counters);
 }
 
-// scratch of one call: {voxels set, voxels cleared} in a line of their own, then
-//   planes: the packed mask, one result mask per half, the "neither 0 nor 1" bits, the R planes
-//   field:  the field (4 B per voxel) and the scratch of its passes (distance_scratch_bytes, 6 B per voxel)
-constexpr size_t kMorphCounterBytes = 256;
-size_t morph_scratch_bytes(uint32_t N, int op, uint32_t r2, int form)
+static hipError_t launch_morph_field(uint8_t* grid, uint32_t N, int op, uint32_t r2, const MorphScratch& l, hipStream_t s)
 {
-    if (form == MORPH_FORM_FIELD) return kMorphCounterBytes + align256((size_t)N * N * N * sizeof(int32_t)) + distance_scratch_bytes(N);
-    return kMorphCounterBytes + (1u + morph_halves(op)) * morph_mask_bytes(N) + morph_loose_bytes(N) + (size_t)morph_isqrt(r2) * morph_mask_bytes(N);
-}
-unsigned long long* morph_counters(uint8_t* scratch) { return reinterpret_cast<unsigned long long*>(scratch); }
-
-static hipError_t launch_morph_field(uint8_t* grid, uint32_t N, int op, uint32_t r2, uint8_t* scratch, hipStream_t s)
-{
-    int32_t* field = reinterpret_cast<int32_t*>(scratch + kMorphCounterBytes);
-    uint8_t* passes = scratch + kMorphCounterBytes + align256((size_t)N * N * N * sizeof(int32_t));
     const uint32_t groups = (uint32_t)((size_t)N * N * N / 8u);
     for (uint32_t half = 0; half < morph_halves(op); ++half) {
-        const hipError_t e = launch_distance(grid, N, 0, field, passes, s);
+        const hipError_t e = launch_distance(grid, N, 0, l.field, l.passes, s);
         if (e != hipSuccess) return e;
-        k_morph_threshold<<<(groups + 255u) / 256u, 256, 0, s>>>(grid, field, groups, r2, morph_half_erodes(op, half) ? 1 : 0, (int)half, morph_counters(scratch));
+        k_morph_threshold<<<(groups + 255u) / 256u, 256, 0, s>>>(grid, l.field, groups, r2, morph_half_erodes(op, half) ? 1 : 0, (int)half, l.counters);
     }
     return hipGetLastError();
 }
 
-hipError_t launch_morph(uint8_t* grid, uint32_t N, int op, uint32_t r2, int form, uint8_t* scratch, hipStream_t s)
+// l: morph_carve(N, op, r2, form) over the call's scratch
+hipError_t launch_morph(uint8_t* grid, uint32_t N, int op, uint32_t r2, int form, const MorphScratch& l, hipStream_t s)
 {
-    if (!grid || !scratch || N < 2u || N > kMorphMaxN || (N & 1u) || op < MORPH_DILATE || op > MORPH_CLOSE || r2 < 1u || r2 > kMorphMaxRadiusSq ||
-        (form != MORPH_FORM_PLANES && form != MORPH_FORM_FIELD))
+    if (!grid || !l.counters || N < 2u || N > kMorphMaxN || (N & 1u) || op < MORPH_DILATE || op > MORPH_CLOSE || r2 < 1u || r2 > kMorphMaxRadiusSq ||
+        (form != MORPH_FORM_PLANES && form != MORPH_FORM_FIELD) || (form == MORPH_FORM_FIELD ? !l.field || !l.passes : !l.packed || !l.loose || !l.planes))
         return hipErrorInvalidValue;
-    const hipError_t e = hipMemsetAsync(morph_counters(scratch), 0, 2u * sizeof(unsigned long long), s);
+    const hipError_t e = hipMemsetAsync(l.counters, 0, 2u * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
-    if (form == MORPH_FORM_FIELD) return launch_morph_field(grid, N, op, r2, scratch, s);
+    if (form == MORPH_FORM_FIELD) return launch_morph_field(grid, N, op, r2, l, s);
     const uint32_t W = fill_row_words(N), words = N * N * W, R = morph_isqrt(r2), halves = morph_halves(op);     // (N <= kMorphMaxN: 2^27 words at the most)
-    const size_t maskBytes = (size_t)words * 8u, stride = morph_mask_bytes(N);
-    uint8_t* packed = scratch + kMorphCounterBytes;
-    uint64_t* loose = reinterpret_cast<uint64_t*>(packed + (1u + halves) * stride);
-    uint64_t* planes = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(loose) + morph_loose_bytes(N));
+    const size_t maskBytes = (size_t)words * 8u;
     const uint32_t byteBlocks = (uint32_t)((maskBytes + 255u) / 256u), wordBlocks = (words + 255u) / 256u;
     const bool complement = morph_packs_complement(op);
-    k_morph_pack<<<byteBlocks, 256, 0, s>>>(grid, N, complement ? 1 : 0, packed, loose);
-    const uint8_t* from = packed;
+    k_morph_pack<<<byteBlocks, 256, 0, s>>>(grid, N, complement ? 1 : 0, reinterpret_cast<uint8_t*>(l.packed), l.loose);
+    const uint64_t* from = l.packed;
     for (uint32_t half = 0; half < halves; ++half) {
-        uint8_t* to = packed + (1u + half) * stride;
-        k_morph_spread<<<wordBlocks, 256, 0, s>>>(reinterpret_cast<const uint64_t*>(from), N, R, planes, words);
-        k_morph_ball<<<wordBlocks, 256, 0, s>>>(reinterpret_cast<const uint64_t*>(from), planes, N, r2, morph_half_complements(op, half) ? 1 : 0,
-                                                reinterpret_cast<uint64_t*>(to), words);
-        from = to;
+        k_morph_spread<<<wordBlocks, 256, 0, s>>>(from, N, R, l.planes, words);
+        k_morph_ball<<<wordBlocks, 256, 0, s>>>(from, l.planes, N, r2, morph_half_complements(op, half) ? 1 : 0, l.half[half], words);
+        from = l.half[half];
     }
-    k_morph_write<<<byteBlocks, 256, 0, s>>>(packed, complement ? 1 : 0, from, loose, N, grid, morph_counters(scratch));
+    k_morph_write<<<byteBlocks, 256, 0, s>>>(reinterpret_cast<const uint8_t*>(l.packed), complement ? 1 : 0, reinterpret_cast<const uint8_t*>(from), l.loose, N, grid, l.counters);
     return hipGetLastError();
 }
 

@@ -17,7 +17,7 @@
 //                    early out for empty and full, then every lane finishes the last three levels for its x-run and stores its 8 voxels, 0
 //                    or 1 each.  Every index is compared with the node count before it is followed (oct_child); a tree that cannot be
 //                    followed gives empty voxels and sets the frame's status word.
-// No atomics, no workgroup waits for another, no kernel here uses scratch memory or LDS.
+// No atomics, no workgroup waits for another, no kernel here uses scratch memory or LDS.  The scratch is laid out by oct_carve (dxv_octree.h).
 #include "dxv_device.h"
 #include "dxv_octree.h"
 
@@ -158,32 +158,6 @@ __global__ __launch_bounds__(256) void k_oct_expand(uint8_t* __restrict__ grid, 
         for (uint32_t k = 0; k < 8u; ++k)
             if (gx + k < N) row[k] = (uint8_t)(run >> k & 1u);
     }
-}
-
-static size_t oct_words(uint32_t L) { return oct_level_offset(L) >> 6; }
-
-// scratch of one build: the dense cell words, their "has a node" bits, the words' counts / bases, the scan's block sums, level_first
-size_t oct_scratch_bytes(uint32_t N)
-{
-    const uint32_t L = oct_levels(N);
-    const size_t words = oct_words(L);
-    return align256(words * 64u * sizeof(uint16_t)) + align256(words * sizeof(uint64_t)) + align256(words * sizeof(uint32_t)) +
-           align256((size_t)scan_blocks(words) * sizeof(unsigned long long)) + align256((kOctMaxLevels + 1u) * sizeof(unsigned long long));
-}
-void oct_scratch_layout(uint8_t* scratch, uint32_t N, OctParams& p)
-{
-    const uint32_t L = oct_levels(N);
-    const size_t words = oct_words(L);
-    p.N = N; p.L = L;
-    p.cells = reinterpret_cast<uint16_t*>(scratch);
-    scratch += align256(words * 64u * sizeof(uint16_t));
-    p.masks = reinterpret_cast<uint64_t*>(scratch);
-    scratch += align256(words * sizeof(uint64_t));
-    p.bases = reinterpret_cast<uint32_t*>(scratch);
-    scratch += align256(words * sizeof(uint32_t));
-    p.sums = reinterpret_cast<unsigned long long*>(scratch);
-    scratch += align256((size_t)scan_blocks(words) * sizeof(unsigned long long));
-    p.levelFirst = reinterpret_cast<unsigned long long*>(scratch);
 }
 
 static bool oct_params_ok(const OctParams& p) { return p.N >= 2u && p.N <= 2048u && !(p.N & 1u) && p.L == oct_levels(p.N) && p.grid && p.cells; }

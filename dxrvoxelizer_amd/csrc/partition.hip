@@ -16,14 +16,13 @@
 //   throats    k_part_emit_faces: one word (a, b) per interface face, by the same scan; radix_sort.hip; k_part_count_heads, launch_scan_sums: the
 //              run heads = the unique pairs, T; then k_part_emit_pairs, k_part_face_atomics: every face finds its pair by binary search --
 //              faces += 1, (neck, -voxel) = max as ONE 64-bit word --, k_part_throats: the records and the regions' throat counts
-// No kernel waits for another workgroup, every loop is bounded, nothing goes to scratch memory.
+// No kernel waits for another workgroup, every loop is bounded, nothing goes to scratch memory.  Scratch and work are described once, by
+// partition_carve and partition_work_carve (dxv_partition.h).
 #include "dxv_device.h"
 #include "dxv_partition.h"
 #include "dxv_scan.h"
 
 namespace dxv {
-
-static uint32_t part_blocks(size_t items) { return (uint32_t)((items + kPartBlock - 1u) / kPartBlock); }
 
 __global__ __launch_bounds__(256) void k_part_keys(const int32_t* __restrict__ F, uint32_t groups, int of, uint32_t cap, uint64_t* __restrict__ keys)
 {
@@ -288,58 +287,6 @@ __global__ __launch_bounds__(256) void k_part_throats(const uint64_t* __restrict
     if (r.b - 1u < K) atomicAdd(&table[r.b - 1u].throats, 1u);
 }
 
-// scratch of one call: F, then parent, then the roots' numbers (4 B per voxel); the keys (8 B); rootOf (4 B); the two mip levels; the blocks'
-// sums with the totals {K, interface faces} behind them; the search's two counters; the scratch of the field's passes (6 B per voxel)
-static size_t part_mip_bytes(uint32_t N, uint32_t side) { const size_t n = part_cells(N, side); return align256(n * n * n * sizeof(uint64_t)); }
-static size_t part_sums_bytes(size_t items) { return align256(2u * ((size_t)part_blocks(items) + 1u) * sizeof(unsigned long long)); }
-size_t partition_scratch_bytes(uint32_t N)
-{
-    const size_t voxels = (size_t)N * N * N;
-    return 2u * align256(voxels * sizeof(uint32_t)) + align256(voxels * sizeof(uint64_t)) + part_mip_bytes(N, 4u) + part_mip_bytes(N, 16u) + part_sums_bytes(voxels) + 256u +
-           distance_scratch_bytes(N);
-}
-void partition_layout(uint8_t* scratch, uint32_t N, PartParams& p)
-{
-    const size_t voxels = (size_t)N * N * N, word = align256(voxels * sizeof(uint32_t));
-    p.N = N;
-    p.F = reinterpret_cast<int32_t*>(scratch);
-    p.parent = p.number = reinterpret_cast<uint32_t*>(scratch);
-    p.rootOf = reinterpret_cast<uint32_t*>(scratch + word);
-    uint8_t* at = scratch + 2u * word;
-    p.keys = reinterpret_cast<uint64_t*>(at); at += align256(voxels * sizeof(uint64_t));
-    p.mip4 = reinterpret_cast<uint64_t*>(at); at += part_mip_bytes(N, 4u);
-    p.mip16 = reinterpret_cast<uint64_t*>(at); at += part_mip_bytes(N, 16u);
-    p.sums = reinterpret_cast<unsigned long long*>(at); at += part_sums_bytes(voxels);
-    p.counters = reinterpret_cast<unsigned long long*>(at); at += 256u;
-    p.passes = at;
-}
-const unsigned long long* partition_totals(const PartParams& p) { return p.sums + 2u * (size_t)part_blocks((size_t)p.N * p.N * p.N); }
-const unsigned long long* partition_counters(const PartParams& p) { return p.counters; }
-
-// work of one call, sized once {K, interface faces} are known: the regions' stats; for the throats the two buffers of the sort, its histogram, the
-// sums of the run heads with T behind them, and a count per pair.  The unique pairs go into the buffer the sort did not end in, the pairs' 64-bit
-// neck words to the front of the one it did.
-size_t partition_work_bytes(uint32_t K, unsigned long long faces)
-{
-    const size_t n = (size_t)faces;
-    size_t bytes = align256((size_t)K * sizeof(PartStats));
-    if (n) bytes += 2u * align256(n * sizeof(uint64_t)) + align256((size_t)radix_sort_hist_words((uint32_t)n) * sizeof(uint32_t)) + part_sums_bytes(n) + align256(n * sizeof(uint32_t));
-    return bytes ? bytes : 256u;
-}
-void partition_work_layout(uint8_t* work, uint32_t K, unsigned long long faces, PartParams& p)
-{
-    const size_t n = (size_t)faces;
-    p.K = K; p.faces = faces;
-    p.stats = reinterpret_cast<PartStats*>(work);
-    uint8_t* at = work + align256((size_t)K * sizeof(PartStats));
-    p.sortA = reinterpret_cast<uint64_t*>(at); at += align256(n * sizeof(uint64_t));
-    p.sortB = reinterpret_cast<uint64_t*>(at); at += align256(n * sizeof(uint64_t));
-    p.hist = reinterpret_cast<uint32_t*>(at); at += n ? align256((size_t)radix_sort_hist_words((uint32_t)n) * sizeof(uint32_t)) : 0u;
-    p.headSums = reinterpret_cast<unsigned long long*>(at); at += part_sums_bytes(n);
-    p.pairCount = reinterpret_cast<uint32_t*>(at);
-}
-const unsigned long long* partition_pair_total(const PartParams& p) { return p.headSums + 2u * (size_t)part_blocks((size_t)p.faces); }
-
 static bool part_valid(const uint8_t* grid, const PartParams& p)
 {
     return grid && p.F && p.N >= 2u && p.N <= kThickMaxN && !(p.N & 1u) && (p.of == PART_SOLID || p.of == PART_EMPTY) && p.cap >= kPartMinCapSq && p.cap <= kPartMaxCapSq &&
@@ -385,7 +332,7 @@ hipError_t launch_partition_stage(const uint8_t* grid, const PartParams& p, int 
     return hipGetLastError();
 }
 
-// the throats' first half: the faces' words, sorted, and the count of their run heads -- T, at partition_pair_total -- for the caller to wait for
+// the throats' first half: the faces' words, sorted, and the count of their run heads -- T, at p.pairTotal -- for the caller to wait for
 hipError_t launch_partition_pairs(PartParams& p, hipStream_t s)
 {
     if (!p.faces || p.faces > 0xFFFFFFFFull || !p.K || !p.labels || !p.sortA) return hipErrorInvalidValue;

@@ -20,8 +20,7 @@
 
 namespace dxv {
 
-constexpr uint32_t kSortSmall = 2u << 20;           // up to here: tiles of 4 waves x 8 keys per lane, digits of up to 11 bits (fewest passes)
-constexpr uint32_t kSortMedium = 16u << 20;         // up to here: tiles of 4 waves x 16 keys per lane, digits of 8 bits; beyond: 16 waves, 10 bits
+// (kSortSmall, kSortMedium -- where the three shapes change -- and radix_sort_hist_words: dxv_scratch.h)
 // TW waves per tile, ITEMS keys per lane: a wave owns 64 x ITEMS consecutive keys
 template <int TW, int ITEMS> struct SortShape {
     static constexpr int waves = TW, items = ITEMS, threads = 64 * TW, waveKeys = 64 * ITEMS, tile = waveKeys * TW;
@@ -234,13 +233,5 @@ hipError_t radix_sort_keys_bits(uint64_t* keys, uint64_t* tmp, uint32_t n, uint3
 }
 
 int radix_sort_passes(uint32_t n, int numBits, int plan) { return sort_plan(n, numBits, plan).passes; }
-
-// words of the histogram scratch of a sort of n keys, whatever its plan: bins x tiles + bins of the shape with the most of them
-uint32_t radix_sort_hist_words(uint32_t n)
-{
-    if (n <= kSortSmall) return 2048u * ((n + 2047u) / 2048u) + 2048u;
-    if (n <= kSortMedium) return 2048u * ((n + 4095u) / 4096u) + 2048u;
-    return 1024u * (uint32_t)(((uint64_t)n + 16383ull) / 16384ull) + 1024u;
-}
 
 } // namespace dxv

@@ -15,7 +15,7 @@ namespace dxv {
 
 constexpr uint32_t kScanBlock = 256;                                    // threads of a workgroup of the two outer kernels ...
 constexpr uint32_t kScanItems = 4;                                      // ... and the consecutive words each of them takes
-constexpr uint32_t kScanWords = kScanBlock * kScanItems;
+static_assert(kScanWords == kScanBlock * kScanItems, "scan_blocks (dxv_scratch.h) counts the words of one such workgroup");
 constexpr uint32_t kScanSumsBlock = 1024;                               // threads of the one workgroup that scans the block sums
 
 // what C interleaved counts add up to, and C consecutive words (counts or sums) <-> that
@@ -89,8 +89,6 @@ template <uint32_t C> __global__ __launch_bounds__(kScanBlock) void k_scan_add(u
         run = run + v;
     }
 }
-
-uint32_t scan_blocks(size_t words) { return (uint32_t)((words + kScanWords - 1u) / kScanWords); }
 
 template <uint32_t C> static hipError_t scan_words(uint32_t* counts, size_t words, unsigned long long* sums, unsigned long long* totals, hipStream_t s)
 {

@@ -13,7 +13,7 @@
 //                     loaded value is lower.  W only grows, so a stale load costs a spare atomic and never loses one.
 //   k_thick_histogram W -> cap + 1 64-bit bins through 32-bit bins in LDS (16.4 KB), one 64-bit atomic per non-zero bin and workgroup
 // No kernel waits for another workgroup, no loop is unbounded, nothing goes to scratch memory; LDS: the histogram's bins and the four wave sums
-// of a block's scan (dxv_scan.h).
+// of a block's scan (dxv_scan.h).  The scratch is laid out by thickness_carve (dxv_thickness.h).
 #include "dxv_device.h"
 #include "dxv_thickness.h"
 #include "dxv_scan.h"
@@ -22,8 +22,6 @@ namespace dxv {
 
 constexpr uint32_t kThickPaintBlocks = 2048;      // workgroups of four waves the paint is launched with, whatever the items
 constexpr uint32_t kThickHistBlocks = 1024;       // ... the histogram, at the most
-
-static uint32_t thick_blocks(uint32_t N) { return (uint32_t)(((size_t)N * N * N + kThickBlock - 1u) / kThickBlock); }
 
 __global__ __launch_bounds__(256) void k_thick_members(const int32_t* __restrict__ F, uint32_t groups, int of, uint32_t cap, uint32_t* __restrict__ B)
 {
@@ -156,29 +154,7 @@ __global__ __launch_bounds__(256) void k_thick_histogram(const uint32_t* __restr
         if (bins[t]) (void)__hip_atomic_fetch_add(hist + t, (unsigned long long)bins[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// scratch of one call: F and G (4 B per voxel each), B (1 B), the blocks' sums and the totals, the scratch of the fields' passes (6 B per voxel) --
-// whose front holds the centres' first items once the last field is made; the centre list goes into G once the select has read it
-size_t thickness_scratch_bytes(uint32_t N)
-{
-    const size_t voxels = (size_t)N * N * N;
-    return 2u * align256(voxels * sizeof(int32_t)) + align256(voxels) + align256(2u * ((size_t)thick_blocks(N) + 2u) * sizeof(unsigned long long)) +
-           distance_scratch_bytes(N);
-}
 size_t thickness_histogram_bytes(uint32_t cap) { return ((size_t)cap + 1u) * sizeof(unsigned long long); }
-
-void thickness_layout(uint8_t* scratch, uint32_t N, ThickParams& p)
-{
-    const size_t voxels = (size_t)N * N * N, field = align256(voxels * sizeof(int32_t));
-    p.N = N;
-    p.F = reinterpret_cast<int32_t*>(scratch);
-    p.G = reinterpret_cast<int32_t*>(scratch + field);
-    p.B = reinterpret_cast<uint32_t*>(scratch + 2u * field);
-    p.sums = reinterpret_cast<unsigned long long*>(scratch + 2u * field + align256(voxels));
-    p.passes = scratch + 2u * field + align256(voxels) + align256(2u * ((size_t)thick_blocks(N) + 2u) * sizeof(unsigned long long));
-    p.centres = reinterpret_cast<uint32_t*>(p.G);
-    p.firstItem = reinterpret_cast<uint32_t*>(p.passes);
-}
-const unsigned long long* thickness_counters(const ThickParams& p) { return p.sums + 2u * (size_t)thick_blocks(p.N); }
 
 static bool thick_valid(const uint8_t* grid, const ThickParams& p)
 {

@@ -16,18 +16,12 @@
 // A batch is `iterations` iterations behind one another, nine launches each.  Whether an iteration removed a voxel is word `iteration` of the
 // batch's control block; the kernels of an iteration return at once when the iteration before left its word 0, so a batch costs what its live
 // iterations cost, and the host reads the block where the frame is next synchronised (dxv_products.hip: settle_thin).  No workgroup waits
-// for another, every loop is bounded by 64 candidates and 26 flood steps; no LDS, no scratch memory.
+// for another, every loop is bounded by 64 candidates and 26 flood steps; no LDS, no scratch memory.  The control block and the masks are laid
+// out by thin_carve (dxv_thin.h).
 #include "dxv_device.h"
 #include "dxv_thin.h"
 
 namespace dxv {
-
-static size_t thin_mask_bytes(uint32_t N) { return align256(fill_mask_words(N) * sizeof(uint64_t)); }
-static size_t thin_loose_bytes(uint32_t N) { return align256((fill_mask_words(N) * 8u + 63u) / 64u * sizeof(uint64_t)); }
-constexpr size_t kThinControlBytes = 512;
-static_assert(sizeof(ThinControl) <= kThinControlBytes && sizeof(ThinControl::live) == sizeof(uint32_t) * kThinMaxRounds, "the control block has a word per iteration of a batch");
-// the control block, S, S as it was, B, the loose bits: 3 1/8 bits per voxel
-size_t thin_scratch_bytes(uint32_t N) { return kThinControlBytes + 3u * thin_mask_bytes(N) + thin_loose_bytes(N); }
 
 __global__ __launch_bounds__(256) void k_thin_border(const uint64_t* __restrict__ S, uint32_t N, uint64_t* __restrict__ B, uint32_t words, const ThinControl* ctl, uint32_t iteration)
 {
@@ -78,16 +72,13 @@ __global__ __launch_bounds__(256) void k_thin_sub(uint64_t* S, const uint64_t* _
 
 // One batch: (first: the pack and the copy of S,) `iterations` iterations, the write-back.  The words of the control block are cleared in front of
 // the iterations; the count of removed voxels runs on from batch to batch.
-hipError_t launch_thin(uint8_t* grid, uint32_t N, int kind, uint8_t* scratch, uint32_t iterations, bool first, hipStream_t s)
+hipError_t launch_thin(uint8_t* grid, uint32_t N, int kind, const ThinScratch& l, uint32_t iterations, bool first, hipStream_t s)
 {
-    if (!grid || !scratch || N < 2u || N > kThinMaxN || (N & 1u) || (kind != THIN_CURVE && kind != THIN_KERNEL)) return hipErrorInvalidValue;
+    if (!grid || !l.ctl || !l.S || !l.was || !l.B || !l.loose || N < 2u || N > kThinMaxN || (N & 1u) || (kind != THIN_CURVE && kind != THIN_KERNEL)) return hipErrorInvalidValue;
     const uint32_t W = fill_row_words(N), words = N * N * W, lanes = (N >> 1) * (N >> 1) * W;    // (N <= kThinMaxN: 2^27 words at the most)
-    const size_t stride = thin_mask_bytes(N);
-    ThinControl* ctl = reinterpret_cast<ThinControl*>(scratch);
-    uint64_t* S = reinterpret_cast<uint64_t*>(scratch + kThinControlBytes);
-    uint8_t* was = scratch + kThinControlBytes + stride;
-    uint64_t* B = reinterpret_cast<uint64_t*>(scratch + kThinControlBytes + 2u * stride);
-    uint64_t* loose = reinterpret_cast<uint64_t*>(scratch + kThinControlBytes + 3u * stride);
+    ThinControl* ctl = l.ctl;
+    uint64_t *S = l.S, *B = l.B, *loose = l.loose;
+    uint8_t* was = reinterpret_cast<uint8_t*>(l.was);
     iterations = thin_batch(iterations, 0u);
     hipError_t e = hipMemsetAsync(ctl, 0, first ? sizeof(ThinControl) : sizeof(ctl->live), s);
     if (e != hipSuccess) return e;
