@@ -182,6 +182,15 @@ SYMBOLS = {
     "dxv_access_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                                   C.POINTER(C.c_uint32)]),
     "dxv_access_work_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "dxv_sight_async": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
+    "dxv_sight": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
+    "dxv_sight_device_ptr": (C.c_void_p, [C.c_void_p]),
+    "dxv_sight_bytes": (C.c_size_t, [C.c_void_p]),
+    "dxv_sight_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_sight_tally_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "dxv_sight_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
+    "dxv_sight_fill_async": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "dxv_sight_fill": (C.c_int, [C.c_void_p, C.c_uint32]),
     "dxv_components_select_async": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
     "dxv_components_select": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
     "dxv_components_select_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),

@@ -17,8 +17,8 @@ OBJDIR = os.path.join(HERE, "csrc", "build")
 LIB = os.path.join(HERE, "libdxv.so")
 
 SOURCES = ["dxv_api.hip", "dxv_lists.hip", "dxv_frames.hip", "dxv_products.hip", "dxv_blob.hip", "dxv_debug.hip", "lbvh.hip", "radix_sort.hip", "traverse.hip", "plan_bricks.hip", "queue_order.hip", "voxelize_lists.hip", "parity_rows.hip", "grid_utils.hip",
-           "raycast.hip", "dirmap.hip", "parity_lists.hip", "surface.hip", "distance.hip", "fill.hip", "mesh_distance.hip", "scan.hip", "isosurface.hip", "octree.hip", "components.hip", "measure.hip", "morph.hip", "thin.hip", "thickness.hip", "geodesic.hip", "access.hip", "skeleton.hip", "partition.hip", "obj_ingest.cpp"]
-HEADERS = ["dxv_device.h", "dxv_math.h", "dxv_trace.h", "dxv_types.h", "dxv_raycast.h", "dxv_dirmap.h", "dxv_ctx.h", "dxv_policy.h", "dxv_surface.h", "dxv_brick.h", "dxv_distance.h", "dxv_fill.h", "dxv_solid.h", "dxv_mesh_distance.h", "dxv_scan.h", "dxv_scratch.h", "dxv_label.h", "dxv_isosurface.h", "dxv_octree.h", "dxv_components.h", "dxv_measure.h", "dxv_morph.h", "dxv_thin.h", "dxv_thickness.h", "dxv_geodesic.h", "dxv_access.h", "dxv_skeleton.h", "dxv_partition.h", os.path.join("..", "..", "include", "dxv.h")]
+           "raycast.hip", "dirmap.hip", "parity_lists.hip", "surface.hip", "distance.hip", "fill.hip", "mesh_distance.hip", "scan.hip", "isosurface.hip", "octree.hip", "components.hip", "measure.hip", "morph.hip", "thin.hip", "thickness.hip", "geodesic.hip", "access.hip", "sight.hip", "skeleton.hip", "partition.hip", "obj_ingest.cpp"]
+HEADERS = ["dxv_device.h", "dxv_math.h", "dxv_trace.h", "dxv_types.h", "dxv_raycast.h", "dxv_dirmap.h", "dxv_ctx.h", "dxv_policy.h", "dxv_surface.h", "dxv_brick.h", "dxv_distance.h", "dxv_fill.h", "dxv_solid.h", "dxv_mesh_distance.h", "dxv_scan.h", "dxv_scratch.h", "dxv_label.h", "dxv_isosurface.h", "dxv_octree.h", "dxv_components.h", "dxv_measure.h", "dxv_morph.h", "dxv_thin.h", "dxv_thickness.h", "dxv_geodesic.h", "dxv_access.h", "dxv_sight.h", "dxv_skeleton.h", "dxv_partition.h", os.path.join("..", "..", "include", "dxv.h")]
 
 # -ffp-contract=off: the arithmetic of the path has a fixed operation order; the only fused
 # operations are the explicit fmaf calls in dxv_math.h (hipcc contracts by default).

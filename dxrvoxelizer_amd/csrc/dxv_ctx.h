@@ -150,7 +150,7 @@ struct Timer { hipEvent_t e0 = nullptr, e1 = nullptr; bool armed = false; float 
 enum TimerUse { kTimerLaunch, kTimerQueue, kTimerRender, kTimerDistance, kTimerMeshDistance, kTimerIso, kTimerOctree, kTimerComponents, kTimerMorph, kTimerMeasure, kTimerThickness,
                 kTimerThickStage0, kTimerThickStageLast = kTimerThickStage0 + dxv::THICK_STAGES - 1,     // the six stages of a thickness, each a pair of its own
                 kTimerPartition, kTimerPartStage0, kTimerPartStageLast = kTimerPartStage0 + dxv::PART_STAGES - 1,      // a partition and its six stages, likewise
-                kTimerSkeleton,
+                kTimerSkeleton, kTimerSight,
                 kTimerFill, kTimerThin, kTimerGeodesic, kTimerAccess,
                 kTimers,
                 kTimerFirstOperator = kTimerRender, kTimerFirstBatched = kTimerFill };
@@ -427,6 +427,18 @@ struct dxv_ctx {
             } prune;
             void trim() { scratch.release(); work.release(); }   // (the masks, bits, counts and stats; labels and tables themselves stay)
         } skel;
+        // line-of-sight map (sight.hip; dxv_sight_async): the map of the frame's grid and its tally, and the scratch of their making -- the member
+        // mask and a bit plane per requested direction
+        struct Sight : Made {
+            DevBuf<uint32_t> map;            // (cap: voxels)
+            DevBuf<uint8_t> scratch;         // (cap: bytes) sight_scratch_bytes
+            uint32_t dim = 0;                // grid side of the frame's last map
+            int of = 0;                      // ... what it was asked for
+            uint32_t directions = 0;         // ... and the directions it was made with
+            bool pending = false;            // its tally is on its way into page-locked words: the frame's next synchronisation reads it
+            unsigned long long tally[68] = {};   // of the frame's last map, as of its last synchronisation (dxv_sight.h: SightTally)
+            void trim() { scratch.release(); }   // (the mask and the planes, up to 27 bits per voxel; the map itself stays)
+        } sight;
         // What a synchronisation of the frame and a launch need to know of all that, without naming an operator.
         // grid_unsettled: the grid may not be final yet -- a fill or a thin whose verdict is not in, an expansion from a caller's tree that can
         // still report; unsettled: ... or a geodesic or an access, which only read the grid, has further batches to go in front of whatever comes next.
@@ -441,7 +453,7 @@ struct dxv_ctx {
             geo.pending = false;
             acc.pending = false;
         }
-        void trim_products() { dist.trim(); mdist.trim(); fill.trim(); iso.trim(); oct.trim(); comp.trim(); morph.trim(); thin.trim(); thick.trim(); part.trim(); geo.trim(); acc.trim(); skel.trim(); }
+        void trim_products() { dist.trim(); mdist.trim(); fill.trim(); iso.trim(); oct.trim(); comp.trim(); morph.trim(); thin.trim(); thick.trim(); part.trim(); geo.trim(); acc.trim(); skel.trim(); sight.trim(); }
     };
     Frame frames[DXV_FRAME_COUNT];
     uint32_t cur = 0;                    // dxv_set_frame
@@ -486,6 +498,7 @@ struct dxv_ctx {
             dxv::GeoControl geoCtl;                      // the control block of the frame's last geodesic batch and the tally behind it
             dxv::GeoControl accCtl;                      // ... of the frame's last access batch, likewise
             unsigned long long skelTotals[5];            // K, B and the end, curve and junction voxels of the skeleton the frame is making: K and B size its tables
+            unsigned long long sightTally[68];           // the tally of the frame's last line-of-sight map
             unsigned long long skelPrune[2];             // branches and voxels removed by the frame's last prune
         } frame[DXV_FRAME_COUNT];
     };

@@ -358,6 +358,14 @@ hipError_t launch_access_init(const uint8_t* grid, uint32_t N, int of, uint32_t 
 hipError_t launch_access_batch(uint32_t* A, uint32_t N, int of, int connectivity, uint32_t cap, const AccScratch& scratch, uint32_t rounds, uint32_t base, hipStream_t s);
 hipError_t launch_access_radius(const uint32_t* A, uint32_t N, int of, const AccScratch& scratch, hipStream_t s);
 
+// sight.hip -- the line-of-sight map of a whole N^3 grid (dxv_sight.h): map = N^3 uint32, the caller's; everything else in scratch, laid out by
+// sight_carve (dxv_sight.h): the tally's 68 words, the member mask and one bit plane per requested direction.  launch_sight: pack, ONE sweep launch
+// for all directions, the map, the tally; group = option sightgroup (0: the smallest row group).  The grid is read by the pack alone.
+// launch_sight_fill: the edit from a map -- every member of the map's kind whose word shares no bit with `directions` changes kind, in place.
+struct SightScratch;
+hipError_t launch_sight(const uint8_t* grid, uint32_t N, int of, uint32_t directions, uint32_t group, uint32_t* map, const SightScratch& scratch, hipStream_t s);
+hipError_t launch_sight_fill(uint8_t* grid, uint32_t N, int of, uint32_t directions, const uint32_t* map, hipStream_t s);
+
 // raycast.hip
 struct RayCastCB;
 hipError_t launch_raycast(const RayCastCB& cb, const uint8_t* grid, uint32_t N, uint32_t width, uint32_t height,

@@ -214,6 +214,8 @@ struct Options {
                              // continued where its frame is next synchronised
     int accessrounds = 0;    // dxv_access*: rounds of one batch (1 .. 64); 0 = kAccRoundsDefault (dxv_access.h).  Same maps: an access that needs more is
                              // continued where its frame is next synchronised
+    int sightgroup = 0;      // dxv_sight*: lanes of a row group of the sweep at the least (1, 2, 4, 8, 16); 0 = the next power of two >= the row's words
+                             // (dxv_sight.h: sight_group).  Same map, same tally: a test reaches the widest group without a grid of 514^3
     int morphform = 0;       // dxv_morph*: 0 = by the radius (dxv_morph.h: morph_form), 1 = bit planes, 2 = distance field + threshold.  Same grids.
     int thickcull = 3;       // dxv_thickness*: bit 0 = the Top cull, bit 1 = neighbour domination (dxv_thickness.h).  Same map, same histogram.
     int thickstages = 0;     // dxv_thickness*: 1 = every stage between events of its own and the paint counts its tests and atomics (dxv_thickness_stage_info); measurement
@@ -289,6 +291,7 @@ constexpr OptionRow kLaterOptions[] = {
     {"thinrounds", in_range(0, 64), "not in [0, 64]", &Options::thinrounds, OptionEffect::none},
     {"georounds", in_range(0, 64), "not in [0, 64]", &Options::georounds, OptionEffect::none},
     {"accessrounds", in_range(0, 64), "not in [0, 64]", &Options::accessrounds, OptionEffect::none},
+    {"sightgroup", one_of(0, 1, 2, 4, 8, 16), "not in {0,1,2,4,8,16}", &Options::sightgroup, OptionEffect::none},
     {"thickcull", in_range(0, 3), "not in {0,1,2,3}", &Options::thickcull, OptionEffect::none},
     {"thickstages", kOnOff, "not in {0,1}", &Options::thickstages, OptionEffect::none},
     {"partprune", in_range(0, 3), "not in {0,1,2,3}", &Options::partprune, OptionEffect::none},

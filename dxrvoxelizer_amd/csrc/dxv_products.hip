@@ -21,6 +21,7 @@
 #include "dxv_partition.h"
 #include "dxv_geodesic.h"
 #include "dxv_access.h"
+#include "dxv_sight.h"
 #include "dxv_skeleton.h"
 
 using namespace dxv;
@@ -66,6 +67,7 @@ static const ProductText kPartitionText = {"partition", "dxv_partition", "was la
 static const ProductText kGeodesicText = {"geodesic map", "dxv_geodesic", "was launched or edited again since its geodesic map was made: the map is stale"};
 static const ProductText kSkeletonText = {"skeleton", "dxv_skeleton", "was launched or edited again since its skeleton was made: labels and tables are stale"};
 static const ProductText kAccessText = {"access map", "dxv_access", "was launched or edited again since its access map was made: maps and histograms are stale"};
+static const ProductText kSightText = {"line-of-sight map", "dxv_sight", "was launched or edited again since its line-of-sight map was made: map and tally are stale"};
 
 // whether the selected frame has this product to hand out: 0, or 1 with the reason as the message
 static int check_current(const dxv_ctx* c, const char* who, const Frame::Made& made, const ProductText& text)
@@ -134,6 +136,7 @@ static const Readable kIntrusionMap = {kAccessText, [](const Frame& f) { return 
                                        false, kNoIntrusion};
 static const Readable kIntrusionHistogram = {kAccessText, [](const Frame& f) { return View{&f.acc, f.acc.histI.p, thickness_histogram_bytes(f.acc.cap), f.acc.wantIntrusion}; },
                                              false, kNoIntrusion};
+static const Readable kSightMap = {kSightText, [](const Frame& f) { return View{&f.sight, f.sight.map.p, cube(f.sight.dim) * sizeof(uint32_t)}; }};
 
 // whether the selected frame has this buffer to hand out, and *v, what it is: 0, or 1 -- with the reason as the message where an entry asks in
 // its own name, without a word for who = nullptr
@@ -236,6 +239,10 @@ void read_products(dxv_ctx* c, uint32_t i)
         f.part.cellsTested = pin.partCount[0];
         f.part.voxelsTested = pin.partCount[1];
         f.part.pending = false;
+    }
+    if (f.sight.pending) {                                              // the tally of the frame's last line-of-sight map
+        memcpy(f.sight.tally, pin.sightTally, sizeof(f.sight.tally));
+        f.sight.pending = false;
     }
     if (f.skel.prune.pending) {                                         // the counters of the frame's last prune
         f.skel.prune.branches = (uint32_t)pin.skelPrune[0];
@@ -1280,6 +1287,85 @@ int dxv_access_work_info(dxv_ctx* c, uint64_t* tiles_run, uint32_t* most_live_ti
 {
     return c ? flood_work_info(c, "dxv_access_work_info", cur_frame(c).acc, kAccessText, tiles_run, most_live_tiles, sparse_rounds) : 1;
 }
+
+// The line-of-sight map of the selected frame's grid (sight.hip; dxv_sight.h has the rule's routines), enqueued on the frame's stream behind
+// whatever it holds, under dxv_render_async's host-wait rule.  A fixed chain of kernels: nothing to settle; the tally goes into page-locked
+// words and is read where the frame is next synchronised.  Map and scratch are the frame's own.
+int dxv_sight_async(dxv_ctx* c, int of, uint32_t directions)
+{
+    if (!c) return 1;
+    if (of != DXV_COMP_SOLID && of != DXV_COMP_EMPTY) return fail(c, "dxv_sight: unknown kind %d (DXV_COMP_SOLID = 0, DXV_COMP_EMPTY = 1)", of);
+    if (!sight_directions_valid(directions))
+        return fail(c, "dxv_sight: directions 0x%08X is not a non-empty subset of DXV_SIGHT_ALL = 0x%08X (bit 13 is the zero vector, bits 27 .. 31 are none)", directions, kSightAll);
+    if (check_whole_grid(c, "dxv_sight")) return 1;
+    Frame& f = cur_frame(c);
+    const uint32_t N = f.grid_dim;
+    if (N > kSightMaxN) return fail(c, "dxv_sight: a grid of %u^3 voxels; at most %u^3 (a voxel's linear index must fit 30 bits)", N, kSightMaxN);
+    hipStream_t fs;
+    if (begin_operator(c, &fs)) return 1;
+    Frame::Sight& o = f.sight;
+    const size_t voxels = cube(N), scratch = sight_scratch_bytes(N, directions);
+    o.version = 0; o.have = false;
+    DXV_HIP(c, o.map.reserve(voxels, align256(voxels * sizeof(uint32_t)), fs));
+    DXV_HIP(c, o.scratch.reserve(scratch, scratch, fs));
+    SightScratch l{};
+    DXV_HIP(c, carve_buffer(o.scratch, l, sight_carve, N, directions));
+    DXV_HIP(c, timer_begin(f.timers[kTimerSight], c->opt.events != 0, fs));
+    DXV_HIP(c, launch_sight(f.grid.p, N, of, directions, (uint32_t)c->opt.sightgroup, o.map.p, l, fs));
+    PinnedFrame& pin = cur_pinned(c);
+    if (end_operator(c, f, fs, &f.timers[kTimerSight], pin.sightTally, l.tally, sizeof(pin.sightTally))) return 1;
+    o.pending = true;
+    o.dim = N; o.of = of; o.directions = directions; o.have = true; o.version = f.gridVersion;
+    return 0;
+}
+
+int dxv_sight(dxv_ctx* c, int of, uint32_t directions) { return blocking(c, dxv_sight_async(c, of, directions)); }
+
+const void* dxv_sight_device_ptr(const dxv_ctx* c) { return product_ptr(c, "dxv_sight_device_ptr", kSightMap); }
+size_t dxv_sight_bytes(const dxv_ctx* c) { return product_bytes(c, "dxv_sight_bytes", kSightMap); }
+int dxv_sight_download(dxv_ctx* c, void* host, size_t bytes) { return product_download(c, "dxv_sight_download", kSightMap, host, bytes); }
+
+// (the tally is the host's by the time the frame has been synchronised: the map's refusals, the byte count, the synchronisation, a copy)
+int dxv_sight_tally_download(dxv_ctx* c, void* host, size_t bytes)
+{
+    if (!c || check_current(c, "dxv_sight_tally_download", cur_frame(c).sight, kSightText)) return 1;
+    const size_t want = sizeof(cur_frame(c).sight.tally);
+    if (!host || bytes != want) return fail(c, "dxv_sight_tally_download: expected %zu bytes, got %zu", want, bytes);
+    if (dxv_sync(c)) return 1;
+    memcpy(host, cur_frame(c).sight.tally, want);
+    return 0;
+}
+
+int dxv_sight_info(dxv_ctx* c, float* ms, int* of, uint32_t* directions)
+{
+    if (!c || check_current(c, "dxv_sight_info", cur_frame(c).sight, kSightText)) return 1;
+    const Frame& f = cur_frame(c);
+    if (ms) *ms = f.timers[kTimerSight].ms;
+    if (of) *of = f.sight.of;
+    if (directions) *directions = f.sight.directions;
+    return 0;
+}
+
+// The selected frame's grid edited from its line-of-sight map (sight.hip: k_sight_fill), in place, enqueued on the frame's stream behind whatever
+// it holds -- under dxv_render_async's host-wait rule and dxv_fill_async's rules for the grid.  The map is what it reads: dxv_trim has left it.
+int dxv_sight_fill_async(dxv_ctx* c, uint32_t directions)
+{
+    if (!c) return 1;
+    if (check_current(c, "dxv_sight_fill", cur_frame(c).sight, kSightText)) return 1;
+    Frame& f = cur_frame(c);
+    Frame::Sight& o = f.sight;
+    if (!directions || (directions & ~o.directions))
+        return fail(c, "dxv_sight_fill: directions 0x%08X is not a non-empty subset of the 0x%08X the map of frame %u was made with", directions, o.directions, c->cur);
+    if (!f.grid.p || f.grid_dim != o.dim || !frame_renderable(f))
+        return fail(c, "dxv_sight_fill: the line-of-sight map of frame %u does not belong to its grid: it is stale", c->cur);
+    hipStream_t fs;
+    if (begin_operator(c, &fs)) return 1;
+    edited_in_place(f);                                                 // (this map is stale with the rest)
+    DXV_HIP(c, launch_sight_fill(f.grid.p, o.dim, o.of, directions, o.map.p, fs));
+    return end_operator(c, f, fs, nullptr);
+}
+
+int dxv_sight_fill(dxv_ctx* c, uint32_t directions) { return blocking(c, dxv_sight_fill_async(c, directions)); }
 
 // The path from `target` down to a seed of the selected frame's current map, synchronous: the frame is synchronised, the target's word is read,
 // one wave walks down (geodesic.hip: k_geo_path) into the frame's own words, and min(length, capacity) of them come back.

@@ -18,6 +18,7 @@ THIN_CURVE, THIN_KERNEL = 0, 1                                      # the kinds 
 ISO_MESH_DISTANCE, ISO_GRID_DISTANCE = 0, 1       # the field an isosurface is taken from (include/dxv.h)
 ISO_SPACE_VOXELS, ISO_SPACE_OBJECT = 0, 1         # ... and the space its vertices are in
 COMP_SOLID, COMP_EMPTY = 0, 1                     # what connected components are taken of (include/dxv.h)
+SIGHT_ALL = 0x07FFDFFF                            # the 26 directions of Sight: bit (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1), never bit 13 (include/dxv.h)
 GEO_FACES, GEO_CHAMFER = 0, 1                     # the metrics of Geodesic (include/dxv.h)
 GEO_SEEDS_BORDER, GEO_SEEDS_LIST, GEO_SEEDS_MASK = 0, 1, 2
 GEO_NONE, GEO_UNREACHED = 0xFFFFFFFF, 0xFFFFFFFE  # ... and the two codes of its map
@@ -136,6 +137,26 @@ def intrusion_curve(histogram, members=None):
     total = float(members) if members is not None else float(h[1:].sum())
     at_least = np.cumsum(h[:0:-1])[::-1]                                # at_least[t - 1] = the voxels with I >= t
     return thickness_voxels(t), (at_least / total if total else np.zeros(len(t)))
+
+
+def sight_bit(dx, dy, dz):
+    """The bit number of direction (dx, dy, dz) in {-1, 0, 1}^3 without 0 in a line-of-sight map's words (include/dxv.h): (dz + 1) * 9 +
+    (dy + 1) * 3 + (dx + 1).  The opposite direction has bit 26 - b; Sight(directions=1 << sight_bit(0, 0, 1)) asks for rays travelling up z."""
+    if not all(int(d) in (-1, 0, 1) for d in (dx, dy, dz)) or (int(dx), int(dy), int(dz)) == (0, 0, 0):
+        raise ValueError(f"sight_bit: ({dx}, {dy}, {dz}) is not one of the 26 lattice directions")
+    return (int(dz) + 1) * 9 + (int(dy) + 1) * 3 + int(dx) + 1
+
+
+def sight_axes(tally):
+    """The 13 axes of a SightTally, best pull axis first: a list of {"axis": a, "direction": (dx, dy, dz) of its bit 14 + a, "bits": the
+    axis' two bits as a mask, "neither": the members seen along neither of its directions -- the undercut volume of a two-part mould pulled
+    along it}, sorted by (neither, axis).  Meaningful for the axes both of whose directions the map was made with (SIGHT_ALL: all).  Pure numpy."""
+    neither = np.asarray(tally["neither"], np.uint64)
+    rows = []
+    for a in range(13):
+        b = 14 + a
+        rows.append({"axis": a, "direction": (b % 3 - 1, b // 3 % 3 - 1, b // 9 - 1), "bits": (1 << b) | (1 << (26 - b)), "neither": int(neither[a])})
+    return sorted(rows, key=lambda r: (r["neither"], r["axis"]))
 
 
 class Voxelizer:
@@ -926,6 +947,49 @@ class Voxelizer:
         tiles, most, sparse = C.c_uint64(), C.c_uint32(), C.c_uint32()
         self._check(self._lib.dxv_access_work_info(self._ctx, C.byref(tiles), C.byref(most), C.byref(sparse)))
         return {"tiles_run": tiles.value, "most_live_tiles": most.value, "sparse_rounds": sparse.value}
+
+    # ---- what a straight line reaches: the line-of-sight map of the frame's grid -------------------------
+    def Sight(self, of=COMP_EMPTY, directions=SIGHT_ALL, sync=True, frameIndex=None):
+        """The line-of-sight map of the selected frame's whole grid on the device (dxv_sight / dxv_sight_async; include/dxv.h has the rule):
+        per voxel a uint32 with bit sight_bit(dx, dy, dz) set when the voxel is a member (COMP_EMPTY / COMP_SOLID) and every voxel behind it
+        against the direction, up to the grid's border, is one too -- a ray entering the grid in that direction reaches it through members
+        only.  directions: a non-empty subset of SIGHT_ALL.  sync=True returns SightField(); sync=False only enqueues it."""
+        if frameIndex is not None:
+            self.SetFrame(frameIndex)
+        fn = self._lib.dxv_sight if sync else self._lib.dxv_sight_async
+        self._check(fn(self._ctx, int(of), int(directions)))
+        return self.SightField() if sync else True
+
+    def SightField(self):
+        """numpy copy uint32 [N, N, N] (z, y, x) of the selected frame's line-of-sight map (dxv_sight_download; synchronises the frame)."""
+        return self._download("sight", np.uint32, "cube", speaks="dxv_sight_device_ptr")
+
+    def sight_device_ptr(self):
+        """device pointer of the selected frame's line-of-sight map, 4 * N^3 bytes, for consumers on the GPU (exact after Sync)."""
+        return self._pointer("dxv_sight_device_ptr")
+
+    def SightTally(self):
+        """{members, seen uint64 [27], neither uint64 [13], count uint64 [27]} of the selected frame's map (dxv_sight_tally_download;
+        synchronises the frame): the members, those seen along each direction's bit, per axis asked for both ways those seen along neither
+        of its directions, and count[k] those seen along exactly k of the requested directions.  sight_axes ranks the axes."""
+        words = np.empty(68, np.uint64)
+        self._check(self._lib.dxv_sight_tally_download(self._ctx, words.ctypes.data_as(C.c_void_p), words.nbytes))
+        return {"members": int(words[0]), "seen": words[1:28].copy(), "neither": words[28:41].copy(), "count": words[41:68].copy()}
+
+    def SightInfo(self):
+        """{ms, of, directions} of the selected frame's last line-of-sight map as of its last Sync (dxv_sight_info)."""
+        ms, of, directions = C.c_float(), C.c_int(), C.c_uint32()
+        self._check(self._lib.dxv_sight_info(self._ctx, C.byref(ms), C.byref(of), C.byref(directions)))
+        return {"ms": ms.value, "of": of.value, "directions": directions.value}
+
+    def SightFill(self, directions, sync=True):
+        """Edit the selected frame's grid in place from its current line-of-sight map (dxv_sight_fill / _async): every member of the map's
+        kind that is seen along none of `directions` (a non-empty subset of the map's) changes kind -- empty becomes 1, solid becomes 0.  An
+        axis' two bits fill the undercuts of that pull axis, one bit the support volume of a build direction.  Every product of the frame,
+        this map included, is stale afterwards."""
+        fn = self._lib.dxv_sight_fill if sync else self._lib.dxv_sight_fill_async
+        self._check(fn(self._ctx, int(directions)))
+        return True
 
     def SelectComponents(self, rule, arg=0, sync=True):
         """Edit the selected frame's grid in place from its current labels (dxv_components_select / _async): the voxels of every component

@@ -1099,6 +1099,66 @@ DXV_API int dxv_access_info(dxv_ctx* ctx, float* ms, uint32_t* rounds, uint64_t*
  * and the rounds with fewer than 1024 live tiles.  These differ from run to run. */
 DXV_API int dxv_access_work_info(dxv_ctx* ctx, uint64_t* tiles_run, uint32_t* most_live_tiles, uint32_t* sparse_rounds);
 
+/* Line-of-sight map: along which of the 26 lattice directions a straight ray from outside the grid reaches a voxel (no reference
+ * counterpart).  dxv_access says what a ball can reach by any path; this operator answers the straight-line question: the undercuts of a mould
+ * pulled along an axis and the best of the 13 pull axes, the voxels under an overhang as seen from the build plate, the directions a straight
+ * tool, a coating or a cleaning jet gets to a voxel from, a part's shadow volume.  dxv_morph(DXV_MORPH_DILATE, r^2) first gives the sight of a
+ * straight tool of radius r.
+ * Input: the WHOLE grid of the selected frame's last launch, in any mode.  Bytes written through dxv_grid_device_ptr count too.  solid(p) iff
+ * byte(p) != 0.  Only voxels inside the grid exist.
+ * of = DXV_COMP_SOLID (0) or DXV_COMP_EMPTY (1) picks the members M.
+ * The directions are the 26 vectors d = (dx, dy, dz) in {-1, 0, 1}^3 without 0.  Direction d has bit b(d) = (dz + 1) * 9 + (dy + 1) * 3 +
+ * (dx + 1) of a uint32: bits 0 .. 26; bit 13, the zero vector, is never set; DXV_SIGHT_ALL = 0x07FFDFFF.  d and -d have bits b and 26 - b.  The
+ * 13 AXES are the pairs (d, -d) with b(d) > 13, axis a = b(d) - 14.  `directions` is a non-empty subset of DXV_SIGHT_ALL.
+ *     seen(c, d)   c in M and every voxel c - j d, j = 1, 2, ..., that lies inside the grid is in M: a ray that enters the grid travelling in
+ *                  direction d reaches c through members only.  A member with c - d outside the grid is seen along d.
+ * Equivalently V_d(c) = M(c) and (c - d outside the grid or V_d(c - d)).  Integers and bits only: the device's bytes equal a restatement byte
+ * for byte.
+ * Output: the map, one uint32 per voxel, element (iz * N + iy) * N + ix like the grid, 4 N^3 bytes: the OR of the bits of the requested
+ * directions along which the voxel is seen, 0 on a voxel that is no member; and a tally of 68 uint64, independent of any order:
+ *     [0]        members
+ *     [1 + b]    seen[27]: the members seen along direction b; 0 for bit 13 and for a direction not asked for
+ *     [28 + a]   neither[13]: for an axis both of whose directions were asked for, the members seen along neither -- the undercut volume of a
+ *                two-part mould pulled along that axis; 0 for the other axes
+ *     [41 + k]   count[27]: the members seen along exactly k of the requested directions; count[0] is the hidden volume
+ * dxv_sight_async -- ENQUEUED on the frame's stream behind whatever it holds; returns without waiting.  The grid is read and none of the
+ * frame's other products is written.
+ *  - A fixed chain of kernels, nothing to settle: after dxv_sync, or on the frame's stream behind the call, the map is exact.  The tally is
+ *    the host's once the frame has been synchronised.
+ *  - The host waits only under dxv_render_async's rule; a pending fill, thin, expansion, geodesic or access of the frame is settled first.
+ *  - Checked on the host before anything is enqueued, each an error with a message: of is valid; directions is not 0 and has neither bit 13
+ *    nor a bit from 27 on; the frame has been launched; its last launch was the whole grid; grid_dim is at most 1024 (the launch has
+ *    checked that it is even and at least 2).
+ *  - Map and scratch belong to the frame: frames run side by side.  The map is 4 bytes per voxel; the scratch -- the member mask and one bit
+ *    plane per requested direction, up to 27 bits per voxel -- goes back with dxv_trim, the map stays.
+ *  - Map and tally are STALE once the frame's grid version moves -- it is launched, filled, morphed, thinned, expanded, selected or
+ *    dxv_sight_fill'ed again: pointer, size, downloads, info and dxv_sight_fill then fail with a message.
+ *  - Option events = 1 (default): bracketed by the frame's own events, read at the frame's dxv_sync.
+ * dxv_sight -- the same + dxv_sync. */
+enum { DXV_SIGHT_ALL = 0x07FFDFFF };
+DXV_API int dxv_sight_async(dxv_ctx* ctx, int of, uint32_t directions);
+DXV_API int dxv_sight(dxv_ctx* ctx, int of, uint32_t directions);
+/* The map on the device (exact after dxv_sync) and its size, 4 * grid_dim^3 bytes.  NULL / 0 (the pointer with a message) before the frame's
+ * first map or when it is stale.  The download synchronises the frame first; bytes must be the size above. */
+DXV_API const void* dxv_sight_device_ptr(const dxv_ctx* ctx);
+DXV_API size_t dxv_sight_bytes(const dxv_ctx* ctx);
+DXV_API int dxv_sight_download(dxv_ctx* ctx, void* host, size_t bytes);
+/* The tally, 68 uint64 = 544 bytes, under the same rules. */
+DXV_API int dxv_sight_tally_download(dxv_ctx* ctx, void* host, size_t bytes);
+/* The selected frame's last map as of the frame's last dxv_sync: device time in milliseconds from its pack to its tally (HIP events, option
+ * events = 1; else 0), and what it was made with.  Any pointer may be NULL; fails with a message before the frame's first map or when it is
+ * stale. */
+DXV_API int dxv_sight_info(dxv_ctx* ctx, float* ms, int* of, uint32_t* directions);
+/* The edit from the map, in place: every member of the map's kind whose map word shares no bit with `directions` changes kind -- an EMPTY
+ * member becomes 1, the byte dxv_fill writes for solid; a SOLID member becomes 0; every other byte stays as it is.  With one axis' two bits
+ * this fills the undercuts of that pull axis; with one bit, the support volume of a build direction; with DXV_SIGHT_ALL, the hidden volume.
+ * Needs a current map; `directions` is a non-empty subset of the directions the map was made with.  Enqueued like dxv_morph_async, under
+ * dxv_fill_async's rules for the grid: the grid version moves, so this map and every other product of the frame are stale afterwards.
+ * Afterwards dxv_sight(of, directions) has count[0] == 0: the line behind a member that is seen consists of members seen along the same
+ * direction, so none of them was filled.  dxv_sight_fill -- the same + dxv_sync. */
+DXV_API int dxv_sight_fill_async(dxv_ctx* ctx, uint32_t directions);
+DXV_API int dxv_sight_fill(dxv_ctx* ctx, uint32_t directions);
+
 /* Multi-GPU: the built scene (nodes + triangle data) as one relocatable device blob, so that
  * rank 0 builds once and the host layer broadcasts it (RCCL over xGMI) to the other ranks.
  * export copies the blob into caller-provided DEVICE memory; import adopts a blob from DEVICE
@@ -1232,6 +1292,9 @@ DXV_API int dxv_get_stats(const dxv_ctx* ctx, dxv_stats* out);
  *                 synchronised.  Same map.
  *   accessrounds 0..64  dxv_access*: rounds of one batch (0, default: 16); an access that needs more is continued where its frame is next
  *                 synchronised.  Same maps.
+ *   sightgroup 0|1|2|4|8|16  dxv_sight*: lanes of a row group of the sweep at the least; 0 (default) = the next power of two >= the row's 64-bit
+ *                 words, which is what a larger value is raised to where it is less (test hook: the widest group without a 514^3 grid).
+ *                 Same map, same tally.
  *   morphform 0..2  dxv_morph*: 0 (default) = by the radius: bit planes up to radius_sq 1024, above it the distance field of the grid and its
  *                 threshold, per half; 1 / 2 = always the planes / always the field (measurement, cross-check).  Same grids.
  *   thickcull 0..3  dxv_thickness*: which centres are left out of the paint because their ball cannot raise anything: bit 0 = those whose ball

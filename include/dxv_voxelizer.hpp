@@ -509,6 +509,39 @@ public:
 		return m_ctx && dxv_access_info(m_ctx, &t.ms, &t.rounds, &t.seedsUsed, &t.reached, &t.unreached, &t.widest, &t.widestVoxel) == 0;
 	}
 
+	// What a straight line reaches (dxv_sight / dxv_sight_async; include/dxv.h has the rule): per voxel a uint32 with bit SightBit(dx, dy, dz) set
+	// when the voxel is a member and every voxel behind it against the direction, up to the grid's border, is one too.  directions: a non-empty
+	// subset of DXV_SIGHT_ALL.  Refers to the frame last selected; sync = false only enqueues (WaitFrame reports).
+	static uint32_t SightBit(int dx, int dy, int dz) { return (uint32_t)((dz + 1) * 9 + (dy + 1) * 3 + (dx + 1)); }
+	bool Sight(int of = DXV_COMP_EMPTY, uint32_t directions = DXV_SIGHT_ALL, bool sync = true)
+	{
+		return m_ctx && (sync ? dxv_sight(m_ctx, of, directions) : dxv_sight_async(m_ctx, of, directions)) == 0;
+	}
+	const void* DeviceSight() const { return m_ctx ? dxv_sight_device_ptr(m_ctx) : nullptr; }
+	bool SightField(std::vector<uint32_t>& field)
+	{
+		if (!m_ctx) return setError("SightField before Init");
+		const size_t bytes = dxv_sight_bytes(m_ctx);
+		if (!bytes) return false;
+		field.resize(bytes / sizeof(uint32_t));
+		return dxv_sight_download(m_ctx, field.data(), bytes) == 0;
+	}
+	// the tally: the members, those seen along each direction's bit, per axis asked for both ways those seen along neither of its directions,
+	// and count[k] those seen along exactly k of the requested directions
+	struct SightCounts { uint64_t members = 0, seen[27] = {}, neither[13] = {}, count[27] = {}; };
+	bool SightTally(SightCounts& t) { return m_ctx && dxv_sight_tally_download(m_ctx, &t, sizeof(t)) == 0; }
+	bool SightInfo(float& ms, int& of, uint32_t& directions) { return m_ctx && dxv_sight_info(m_ctx, &ms, &of, &directions) == 0; }
+	// the axis (0 .. 12, direction bit 14 + axis) with the fewest members seen along neither of its directions: the best pull axis
+	static int BestSightAxis(const SightCounts& t)
+	{
+		int best = 0;
+		for (int a = 1; a < 13; ++a)
+			if (t.neither[a] < t.neither[best]) best = a;
+		return best;
+	}
+	// The edit from that map, in place (dxv_sight_fill / dxv_sight_fill_async): every member seen along none of `directions` changes kind.
+	bool SightFill(uint32_t directions, bool sync = true) { return m_ctx && (sync ? dxv_sight_fill(m_ctx, directions) : dxv_sight_fill_async(m_ctx, directions)) == 0; }
+
 	// The exterior flood fill of that frame's whole grid, in place (dxv_fill / dxv_fill_async): DXV_FILL_SOLID leaves the walls and everything
 	// they enclose, DXV_FILL_INTERIOR the enclosed voxels alone.  Voxelize(gridDim, SURFACE) && Fill() is the solid of a mesh whose
 	// normals and watertightness cannot be trusted.  Refers to the frame last selected; sync = false only enqueues (WaitFrame reports).
