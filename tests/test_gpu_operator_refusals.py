@@ -3,7 +3,8 @@ dxv_measure*, dxv_thickness*, dxv_partition*, dxv_skeleton*, dxv_geodesic*, dxv_
 dxv_render_async) refuse, word for word: the WHOLE text of dxv_last_error against the sentence written out here, with ==.  A frame without a
 grid, a slab, a product that was never made or went stale or was made without the part asked for, a wrong byte count, a NULL ms, a caller's
 pointer the library cannot use -- and what is NOT said: a size never speaks (the measure's does), an empty table is NULL without a word.  One
-cube at 16^3 throughout; every call under test returns before it enqueues anything, or works on 16^3.  And what a launch does to a fill, a thin or a geodesic of its frame that nobody has settled yet: it drops it."""
+cube at 16^3 throughout; every call under test returns before it enqueues anything, or works on 16^3.  And what a launch does to a fill, a thin, a
+geodesic or an access of its frame that nobody has settled yet: it drops it; the verdict of an expansion it reads first."""
 import ctypes as C
 
 import numpy as np
@@ -578,3 +579,65 @@ def test_a_launch_drops_what_is_unsettled(v, dxv, cube):
     finally:
         for key in ("fillrounds", "thinrounds", "georounds"):
             v.set_option(key, 0)
+
+
+def test_a_launch_drops_an_unsettled_access(v, dxv, cube):
+    """an access in batches of one round with its intrusion map, followed at once by a launch of the same frame: the launch's grid is a fresh
+    context's, maps, histograms and tally are dropped with the batches nobody has read, and the same access afterwards gives what it gives in a
+    fresh context"""
+    lib, ctx = v._lib, v._ctx
+    tally = ("seeds_used", "reached", "unreached", "widest", "widest_voxel")
+    fresh = dxv.Voxelizer(0)
+    try:
+        fresh.InitFromArrays(*cube)
+        fresh.Voxelize(N)
+        launched = fresh.Grid()
+        access, intrusion = fresh.Access(dxv.COMP_SOLID, 6, CAP_SQ, "border")
+        histograms = fresh.AccessHistogram(), fresh.IntrusionHistogram()
+        info = fresh.AccessInfo()
+        assert access.any() and intrusion.any() and info["reached"] > 0
+    finally:
+        fresh.close()
+    try:
+        v.set_option("accessrounds", 1)
+        v.Voxelize(N)
+        assert lib.dxv_access_async(ctx, 0, 6, CAP_SQ, 0, None, 0, 1) == 0
+        v.Voxelize(N)
+        assert np.array_equal(v.Grid(), launched)
+        refused(v, lib.dxv_access_info(ctx, None, None, None, None, None, None, None),
+                "dxv_access_info: frame 0 was launched or edited again since its access map was made: maps and histograms are stale")
+        refused(v, lib.dxv_intrusion_device_ptr(ctx), "dxv_intrusion_device_ptr: frame 0 was launched or edited again since its access map was made: maps and histograms are stale")
+        assert lib.dxv_sync(ctx) == 0, last(v)                         # (nothing is left to settle)
+        assert lib.dxv_access(ctx, 0, 6, CAP_SQ, 0, None, 0, 1) == 0, last(v)
+        assert np.array_equal(v.AccessField(), access) and np.array_equal(v.IntrusionField(), intrusion)
+        assert np.array_equal(v.AccessHistogram(), histograms[0]) and np.array_equal(v.IntrusionHistogram(), histograms[1])
+        again = v.AccessInfo()
+        assert {k: again[k] for k in tally} == {k: info[k] for k in tally}
+        assert np.array_equal(v.Grid(), launched)                      # (an access only reads the grid)
+    finally:
+        v.set_option("accessrounds", 0)
+
+
+def test_a_launch_behind_an_expansion_whose_verdict_nobody_has_read(v, dxv, cube):
+    """an expansion from a caller's tree of another grid, followed at once by a launch of the same frame: the launch reads the verdict -- a
+    well-formed tree has nothing to report --, its grid is the launch's and not the tree's, and no later synchronisation speaks of the tree"""
+    from raycast_restated import write_grid
+    from test_gpu_octree import as_device_words
+    lib, ctx = v._lib, v._ctx
+    v.Voxelize(N)
+    launched = v.Grid()
+    other = launched.copy()
+    other[:N // 2] = 0
+    other[N // 2:, :3, :3] = 1
+    assert other.any() and not np.array_equal(other != 0, launched != 0)
+    write_grid(v, other)
+    nodes, _ = v.Octree()
+    tree = as_device_words(nodes)
+    v.Voxelize(N)
+    assert lib.dxv_octree_expand_async(ctx, C.c_void_p(tree.data_ptr()), len(nodes), 4) == 0, last(v)
+    v.Voxelize(N)
+    assert np.array_equal(v.Grid(), launched)
+    refused(v, lib.dxv_octree_info(ctx, None, None, None), "dxv_octree_info: frame 0 was launched, filled or expanded again since its octree was made: the tree is stale")
+    assert lib.dxv_sync(ctx) == 0, last(v)
+    assert lib.dxv_octree_expand(ctx, C.c_void_p(tree.data_ptr()), len(nodes), 4) == 0, last(v)      # the same call, read at once
+    assert np.array_equal(v.Grid(), (other != 0).astype(np.uint8))
